@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the WAH hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload sparse|clustered|dense|columns]
+    python bench.py --gpus N --steps K --warmup W [--workload sparse|clustered|dense|columns] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the JSON line: `value`, `ms_per_step` and what the timed
+steps themselves show (per-launch times from events recorded inside them, C/N, the roofline fractions they give).
+Everything else it can measure or check -- the round-trip check before timing, the HBM traffic by rocprofv3 child
+runs, the isolated compress loop, the copy ceiling, the index decode, the CPU baseline and the `columns` side block --
+runs only with --full.  --dump-outputs DIR writes what the last timed step computed (see dump_outputs()).
 
 N = 1 runs in this process.  N > 1: when the process was not started by a launcher (no WORLD_SIZE in the environment)
 it starts N fresh ranks itself -- `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
@@ -20,7 +26,7 @@ One "step" = one pass of the hot path over synthetic bitmaps already resident in
 barrier-bracketed wall clock.  There is no collective on the data path and RCCL is not initialised at all: the two
 scalars of the report (bytes, slowest rank's time) and the barriers go over gloo on 127.0.0.1.
 
-The JSON line also carries
+With --full the JSON line also carries
   roofline     : the dominant kernel (compress_pair_kernel) against the HBM roof.  achieved = algorithmic bytes per
                  launch (4N + 4C) / its average launch duration inside the round trip, measured
                  here with device events on the stream it runs on; launch_ms_isolated = the same kernel in a
@@ -79,7 +85,7 @@ def parse(argv=None):
     ap.add_argument("--columns-per-launch", type=int, default=COLUMNS_PER_LAUNCH)
     ap.add_argument("--per-column-launches", action="store_true", help="columns workload: one launch per column")
     ap.add_argument("--two-in-flight", action="store_true",
-                    help="round-trip workloads: also measure the throughput with two round trips in flight on two streams "
+                    help="round-trip workloads with --full: also measure the throughput with two round trips in flight on two streams "
                          "(a side field; off by default so that a kernel trace of the default command holds one launch at a time)")
     ap.add_argument("--streams", type=int, default=2,
                     help="columns workload: HIP streams the launches are spread over (one compressor = output buffer + workspace each)")
@@ -88,6 +94,11 @@ def parse(argv=None):
     ap.add_argument("--no-traffic", action="store_true", help="do not count HBM bytes with rocprofv3 child runs (roofline.traffic is then replayed from profiles/traffic.json)")
     ap.add_argument("--no-columns", action="store_true", help="round-trip workloads: leave out the `columns` side block (configs[4])")
     ap.add_argument("--columns-steps", type=int, default=5, help="steps of the `columns` side block")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement and check (traffic, isolated launches, copy ceiling, index decode, "
+                         "CPU baseline, `columns` side block, the round-trip check); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64; at most 64 MB)")
     ap.add_argument("--seed", type=int, default=1337)
     ap.add_argument("--master-port", type=int, default=None, help="rendezvous port when this process starts the ranks itself")
     ap.add_argument("--dry-launch", action="store_true", help="print the launcher command this call would run and exit")
@@ -171,6 +182,60 @@ def timed_steps(step, steps, warmup, dist=None, device=None):
     return elapsed
 
 
+DUMP_SAMPLE = 1 << 19   # sampled positions per array
+DUMP_BLOCKS = 1 << 16   # block sums per array
+DUMP_LIMIT = 64 << 20   # bytes of .npy data per run
+
+
+def word_summary(t, seed, unsigned=True):
+    """What --dump-outputs keeps of one device array of integer words, as float64 (exact: words below 2^32, block sums
+    below 2^53): its length, every element when it has at most DUMP_SAMPLE of them, else the elements at a fixed seeded
+    sample of positions (sorted, repeats dropped) -- the positions depend on `seed` and the length only -- and the sums of
+    DUMP_BLOCKS contiguous blocks, which cover every element.  `unsigned`: int32 storage of 32-bit words."""
+    import numpy as np
+    import torch
+
+    n = t.numel()
+    if n <= DUMP_SAMPLE:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.unique(np.random.default_rng(seed).integers(0, n, DUMP_SAMPLE, dtype=np.int64))
+    sample = t[torch.from_numpy(idx).to(t.device)].to(torch.int64)
+    bs = max(1, -(-n // DUMP_BLOCKS))
+    sums = torch.zeros(-(-n // bs), dtype=torch.int64, device=t.device)
+    chunk = bs * max(1, (1 << 26) // bs)  # bounded temporaries: a batch of columns is gigabytes
+    for s in range(0, n, chunk):
+        x = t[s:s + chunk].to(torch.int64)
+        if unsigned:
+            x &= 0xFFFFFFFF
+        pad = -x.numel() % bs
+        if pad:
+            x = torch.cat([x, x.new_zeros(pad)])
+        sums[s // bs: s // bs + x.numel() // bs] = x.view(-1, bs).sum(dim=1)
+    if unsigned:
+        sample &= 0xFFFFFFFF
+    return {"words": np.array([n], np.float64), "sample": sample.cpu().numpy().astype(np.float64),
+            "sample_index": idx.astype(np.float64), "block_sums": sums.cpu().numpy().astype(np.float64)}
+
+
+def dump_outputs(path, arrays, seed):
+    """--dump-outputs: `arrays` = {name: device tensor of words}, what a caller of the timed path receives from its last
+    step.  Writes path/<name>_<part>.npy for the parts of word_summary().  Same arguments, same inputs, same files: two
+    builds can be compared output for output."""
+    import numpy as np
+
+    parts = {}
+    for name, (t, unsigned) in arrays.items():
+        for part, a in word_summary(t, seed, unsigned).items():
+            parts[f"{name}_{part}"] = a
+    total = sum(a.nbytes for a in parts.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT})")
+    os.makedirs(path, exist_ok=True)
+    for name, a in parts.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def cpu_baseline(kind, param, sample_mib, seed):
     """Time the CPU oracle on a bounded sample of the workload (rank 0, N = 1 only)."""
     from tests import _oracle
@@ -232,7 +297,7 @@ def measure_traffic(args):
         for counter in ("FETCH_SIZE", "WRITE_SIZE"):
             out = os.path.join(tmp, counter)
             cmd = [prof, "--kernel-trace", "--pmc", counter, "--output-format", "csv", "-d", out, "--", sys.executable,
-                   os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-columns",
+                   os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-columns",
                    "--no-traffic", "--workload", args.workload, "--seed", str(args.seed)]
             if args.words:
                 cmd += ["--words", str(args.words)]
@@ -274,13 +339,13 @@ def column_plan(n_columns, rank, world, per_launch):
     return mine, batches
 
 
-def columns_measurement(args, dev, rank, world, dist, cpu_only, steps, warmup, desc):
+def columns_measurement(args, dev, rank, world, dist, cpu_only, steps, warmup, desc, dump=None):
     """BASELINE configs[4]: compress() of this rank's share of the independent 128 MiB columns (column c on rank c mod N),
     resident in HBM, `columns_per_launch` columns per launch, the launches round robin over a few streams.  Returns the
-    JSON object of the measurement on rank 0 (None elsewhere).  Every launch is checked once, outside the timed region,
-    one launch at a time (status + a C that fits its buffer); inside the timed region the launches of a stream write
-    their streams into that stream's output buffer one after the other -- nothing consumes them, the figure is the
-    compressor's throughput."""
+    JSON object of the measurement on rank 0 (None elsewhere).  With --full every launch is checked once, outside the
+    timed region, one launch at a time (status + a C that fits its buffer); inside the timed region the launches of a
+    stream write their streams into that stream's output buffer one after the other -- nothing consumes them, the figure
+    is the compressor's throughput.  `dump`: the --dump-outputs directory (rank 0 writes the last step's outputs)."""
     import torch
 
     n = args.words if (args.words and args.workload == "columns") else COLUMN_WORDS
@@ -329,24 +394,37 @@ def columns_measurement(args, dev, rank, world, dist, cpu_only, steps, warmup, d
                 if st is not None:
                     main.wait_stream(st)
 
-        # every launch once, on its own, with its status read back: an error of ANY launch is seen (inside the timed
-        # loop a later launch on the same compressor starts by clearing the error word), and its time is the kernel's
-        row, ev_ms = 0, []
-        for i, b in enumerate(batches):
-            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-            ev[0].record()
-            launch(i, b, row, comps[i % n_streams], None)
-            ev[1].record()
-            torch.cuda.synchronize(dev)
-            comps[i % n_streams].status()
-            ev_ms.append(ev[0].elapsed_time(ev[1]))
-            row += len(b)
-        one_stream_ms = sum(ev_ms) / max(len(ev_ms), 1)
-        c_words_rank = float(sizes.sum().item())
+        if args.full:
+            # every launch once, on its own, with its status read back: an error of ANY launch is seen (inside the timed
+            # loop a later launch on the same compressor starts by clearing the error word), and its time is the kernel's
+            row, ev_ms = 0, []
+            for i, b in enumerate(batches):
+                ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+                ev[0].record()
+                launch(i, b, row, comps[i % n_streams], None)
+                ev[1].record()
+                torch.cuda.synchronize(dev)
+                comps[i % n_streams].status()
+                ev_ms.append(ev[0].elapsed_time(ev[1]))
+                row += len(b)
+            one_stream_ms = sum(ev_ms) / max(len(ev_ms), 1)
     elapsed = timed_steps(step, steps, warmup, dist, dev)
     if not cpu_only:
         for comp in comps:
             comp.status()
+        c_words_rank = float(sizes.sum().item())  # (every launch of the last step wrote its C into its slot)
+        if dump and rank == 0:
+            # what the caller holds after the last step: C of every launch, and in each stream's compressor the streams
+            # of the last batch launched on it (the columns' streams back to back) with their segment index
+            arrays = {"launch_words": (sizes, False)}
+            for s, comp in enumerate(comps):
+                last = max((i for i in range(len(batches)) if i % n_streams == s), default=None)
+                if last is not None:
+                    arrays[f"stream{s}_compressed"] = (comp.out[:int(sizes[last].item())], True)
+                    if batched:
+                        n_seg = len(batches[last]) * n // wah.columns.SEGMENT_WORDS
+                        arrays[f"stream{s}_segment_offsets"] = (comp.seg_offsets[:n_seg + 1], False)
+            dump_outputs(dump, arrays, args.seed)
     stats = torch.tensor([4.0 * n * len(mine), c_words_rank], dtype=torch.float64)
     if dist is not None:
         dist.all_reduce(stats)
@@ -418,7 +496,7 @@ def run_rank(args):
 
     # ---- independent columns: compress only, fixed total -----------------------------------------------------------
     if args.workload == "columns":
-        out = columns_measurement(args, dev, rank, world, dist, cpu_only, args.steps, args.warmup, desc)
+        out = columns_measurement(args, dev, rank, world, dist, cpu_only, args.steps, args.warmup, desc, dump=args.dump_outputs)
         if rank == 0:
             out.update(extra)
             print(json.dumps(out), flush=True)
@@ -450,7 +528,8 @@ def run_rank(args):
     c_words = comp.result().numel()
     dec = wah.DeviceDecompressor(c_words, n + 1, device=dev)
     dec.run(comp.out)
-    assert torch.equal(dec.result()[:n], d_in), "round trip mismatch"
+    if args.full:
+        assert torch.equal(dec.result()[:n], d_in), "round trip mismatch"
 
     events = []
 
@@ -471,6 +550,88 @@ def run_rank(args):
     dec_ms = sorted(e[1].elapsed_time(e[2]) for e in timed)
     comp_avg = sum(comp_ms) / len(comp_ms)
     dec_avg = sum(dec_ms) / len(dec_ms)
+    if args.dump_outputs and rank == 0:
+        # what a caller of the round trip holds after the last step: the compressed stream and the decoded words
+        dump_outputs(args.dump_outputs, {"compressed": (comp.out[:int(comp.count.item())], True),
+                                         "decompressed": (dec.out[:int(dec.info[0].item())], True)}, args.seed)
+    full = full_measurements(args, wah, dev, world, n, c_words, d_in, comp, dec) if args.full else {}
+
+    if rank == 0:
+        in_bytes = 4.0 * n
+        groups = (32 * n + 30) // 31
+        algo_c = 4.0 * n + 4.0 * c_words                          # compress: read N, write C
+        algo_d = 4.0 * c_words + 4.0 * ((31 * groups + 31) // 32)  # decompress: read C, write N'
+        achieved = algo_c / (comp_avg * 1e-3) / 1e9
+        achieved_d = algo_d / (dec_avg * 1e-3) / 1e9
+        # the general decoder's route, as the LIBRARY reports it for the timed calls (wah_last_decode_route)
+        decode_kernels = {"one pass": "decode_tile_kernel + decode_expand_list_kernel (the tiles it puts on its list: a highly "
+                                      "compressed stream's all, an incompressible one's none)",
+                          "two launches": "decode_sums_kernel + decode_expand_kernel",
+                          "no wait": "decode_sums_kernel<no wait> + sums_offsets_kernel + decode_expand_kernel"}.get(dec.route, dec.route)
+        out = {
+            "metric": "compress+decompress GB/s (input bits), 1 GiB bitmap",
+            "value": round(world * args.steps * in_bytes / elapsed / 1e9, 3),
+            "unit": "GB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
+            "config": {"workload": desc, "words": n, "seed": args.seed, "bitmaps_per_gpu": 1,
+                       "parallelism": f"column-shard x{world}, no collective"},
+            "compression_ratio_C_over_N": round(c_words / n, 6),
+            "compress_GBps": round(in_bytes / (comp_avg * 1e-3) / 1e9, 2),
+            "decompress_GBps": round(in_bytes / (dec_avg * 1e-3) / 1e9, 2),
+            "compress_ms": {"avg": round(comp_avg, 4), "min": round(comp_ms[0], 4), "median": round(comp_ms[len(comp_ms) // 2], 4)},
+            "decompress_ms": {"avg": round(dec_avg, 4), "min": round(dec_ms[0], 4), "median": round(dec_ms[len(dec_ms) // 2], 4)},
+            "roofline": {"kernel": "compress_pair_kernel", "bound": "hbm", "achieved": round(achieved, 1),
+                         "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 4),
+                         "algorithmic_bytes_per_launch": algo_c, "launch_ms": round(comp_avg, 4)},
+            "roofline_decompress": {"kernel": decode_kernels, "bound": "hbm",
+                                    "achieved": round(achieved_d, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                                    "frac": round(achieved_d / HBM_PEAK_GBPS, 4),
+                                    "algorithmic_bytes_per_launch": algo_d, "launch_ms": round(dec_avg, 4)},
+        }
+        if args.full:
+            tr = getattr(args, "traffic", None) or load_traffic(args.workload) or {}
+            measured = bool(tr.get("measured"))
+            copy_gbps, comp_isolated, idx_ms = full["copy_gbps"], full["comp_isolated"], full["idx_ms"]
+            out["copy_ceiling_GBps"] = round(copy_gbps, 1)
+            out["roofline"].update({
+                "traffic": tr.get("compress_bytes_per_launch"), "traffic_measured_in_run": measured,
+                "traffic_source": tr.get("source"),
+                "launch_ms_isolated": round(comp_isolated, 4),
+                "frac_isolated": round(algo_c / (comp_isolated * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
+                "frac_of_copy_ceiling": round(achieved / copy_gbps, 4)})
+            out["roofline_decompress"].update({"traffic": tr.get("decompress_bytes_per_launch"),
+                                               "traffic_measured_in_run": measured})
+            out["roofline_decompress_indexed"] = {
+                "kernel": "decode_segments_kernel", "bound": "hbm",
+                "achieved": round(algo_d / (idx_ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBPS,
+                "unit": "GB/s", "frac": round(algo_d / (idx_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
+                "traffic": tr.get("decompress_indexed_bytes_per_launch"),
+                "traffic_measured_in_run": measured,
+                "algorithmic_bytes_per_launch": algo_d,
+                "launch_ms": round(idx_ms, 4),
+                "note": "side measurement with the segment index kept by the compressor; not part of value"}
+            out["two_round_trips_in_flight_GBps"] = round(full["two_in_flight"], 1) if full["two_in_flight"] else None
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(kind, param, args.cpu_sample_mib, args.seed)
+        out.update(extra)
+    # side block, never `value`: BASELINE configs[4] -- the 1024 independent 128 MiB columns, column c on rank c mod N --
+    # so that the full command (the one the driver runs at N = 1, 2, 4, 8) also carries the column-shard figure
+    if args.full and not args.no_columns:
+        del comp, dec, d_in
+        torch.cuda.empty_cache()
+        side = columns_measurement(args, dev, rank, world, dist, False, args.columns_steps, 1, WORKLOADS["columns"][2])
+        if rank == 0:
+            out["columns"] = {k: side[k] for k in ("metric", "value", "unit", "steps", "ms_per_step", "scaling", "config",
+                                                   "compression_ratio_C_over_N", "roofline")}
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    finish()
+
+
+def full_measurements(args, wah, dev, world, n, c_words, d_in, comp, dec):
+    """--full: the round trip's side measurements after the timed steps (they overwrite the timed path's outputs)."""
+    import torch
 
     # the compress kernel on its own: a compress-only loop (no expand kernel's write drain in front of it)
     for _ in range(2):
@@ -546,72 +707,7 @@ def run_rank(args):
     assert torch.equal(back[:n], d_in), "index decode mismatch"
     del icomp, istream, back
 
-    if rank == 0:
-        in_bytes = 4.0 * n
-        groups = (32 * n + 30) // 31
-        algo_c = 4.0 * n + 4.0 * c_words                          # compress: read N, write C
-        algo_d = 4.0 * c_words + 4.0 * ((31 * groups + 31) // 32)  # decompress: read C, write N'
-        achieved = algo_c / (comp_avg * 1e-3) / 1e9
-        achieved_d = algo_d / (dec_avg * 1e-3) / 1e9
-        # the general decoder's route, as the LIBRARY reports it for the timed calls (wah_last_decode_route)
-        decode_kernels = {"one pass": "decode_tile_kernel + decode_expand_list_kernel (the tiles it puts on its list: a highly "
-                                      "compressed stream's all, an incompressible one's none)",
-                          "two launches": "decode_sums_kernel + decode_expand_kernel",
-                          "no wait": "decode_sums_kernel<no wait> + sums_offsets_kernel + decode_expand_kernel"}.get(dec.route, dec.route)
-        tr = getattr(args, "traffic", None) or load_traffic(args.workload) or {}
-        measured = bool(tr.get("measured"))
-        out = {
-            "metric": "compress+decompress GB/s (input bits), 1 GiB bitmap",
-            "value": round(world * args.steps * in_bytes / elapsed / 1e9, 3),
-            "unit": "GB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
-            "config": {"workload": desc, "words": n, "seed": args.seed, "bitmaps_per_gpu": 1,
-                       "parallelism": f"column-shard x{world}, no collective"},
-            "compression_ratio_C_over_N": round(c_words / n, 6),
-            "compress_GBps": round(in_bytes / (comp_avg * 1e-3) / 1e9, 2),
-            "decompress_GBps": round(in_bytes / (dec_avg * 1e-3) / 1e9, 2),
-            "compress_ms": {"avg": round(comp_avg, 4), "min": round(comp_ms[0], 4), "median": round(comp_ms[len(comp_ms) // 2], 4)},
-            "decompress_ms": {"avg": round(dec_avg, 4), "min": round(dec_ms[0], 4), "median": round(dec_ms[len(dec_ms) // 2], 4)},
-            "copy_ceiling_GBps": round(copy_gbps, 1),
-            "two_round_trips_in_flight_GBps": round(two_in_flight, 1) if two_in_flight else None,
-            "roofline": {"kernel": "compress_pair_kernel", "bound": "hbm", "achieved": round(achieved, 1),
-                         "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 4),
-                         "traffic": tr.get("compress_bytes_per_launch"), "traffic_measured_in_run": measured,
-                         "traffic_source": tr.get("source"),
-                         "algorithmic_bytes_per_launch": algo_c, "launch_ms": round(comp_avg, 4),
-                         "launch_ms_isolated": round(comp_isolated, 4),
-                         "frac_isolated": round(algo_c / (comp_isolated * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
-                         "frac_of_copy_ceiling": round(achieved / copy_gbps, 4)},
-            "roofline_decompress": {"kernel": decode_kernels, "bound": "hbm",
-                                    "achieved": round(achieved_d, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                                    "frac": round(achieved_d / HBM_PEAK_GBPS, 4),
-                                    "traffic": tr.get("decompress_bytes_per_launch"), "traffic_measured_in_run": measured,
-                                    "algorithmic_bytes_per_launch": algo_d, "launch_ms": round(dec_avg, 4)},
-            "roofline_decompress_indexed": {"kernel": "decode_segments_kernel", "bound": "hbm",
-                                            "achieved": round(algo_d / (idx_ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBPS,
-                                            "unit": "GB/s", "frac": round(algo_d / (idx_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
-                                            "traffic": tr.get("decompress_indexed_bytes_per_launch"),
-                                            "traffic_measured_in_run": measured,
-                                            "algorithmic_bytes_per_launch": algo_d,
-                                            "launch_ms": round(idx_ms, 4),
-                                            "note": "side measurement with the segment index kept by the compressor; not part of value"},
-        }
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(kind, param, args.cpu_sample_mib, args.seed)
-        out.update(extra)
-    # side block, never `value`: BASELINE configs[4] -- the 1024 independent 128 MiB columns, column c on rank c mod N --
-    # so that the default command (the one the driver runs at N = 1, 2, 4, 8) also carries the column-shard figure
-    if not args.no_columns:
-        del comp, dec, d_in
-        torch.cuda.empty_cache()
-        side = columns_measurement(args, dev, rank, world, dist, False, args.columns_steps, 1, WORKLOADS["columns"][2])
-        if rank == 0:
-            out["columns"] = {k: side[k] for k in ("metric", "value", "unit", "steps", "ms_per_step", "scaling", "config",
-                                                   "compression_ratio_C_over_N", "roofline")}
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    finish()
+    return {"comp_isolated": comp_isolated, "two_in_flight": two_in_flight, "copy_gbps": copy_gbps, "idx_ms": idx_ms}
 
 
 def main(argv=None):
@@ -629,7 +725,8 @@ def main(argv=None):
         return 2
     # HBM bytes by the PMC counters, in child runs under rocprofv3, BEFORE this process touches the GPU (N = 1, real GPU only)
     args.traffic = None
-    if args.gpus == 1 and world_env is None and not args.no_traffic and not os.environ.get("WAH_BENCH_REHEARSE") and args.workload != "columns":
+    if args.full and args.gpus == 1 and world_env is None and not args.no_traffic and not os.environ.get("WAH_BENCH_REHEARSE") \
+            and args.workload != "columns":
         args.traffic = measure_traffic(args)
     run_rank(args)
     return 0

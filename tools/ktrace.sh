@@ -4,7 +4,7 @@ out=$1; shift
 cd /tmp; export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=/root/repo
 rm -rf $R/$out; mkdir -p $R/$out
-rocprofv3 --kernel-trace --stats --output-format csv -d $R/$out -- python3 $R/bench.py --no-cpu-baseline "$@" > $R/$out/bench.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $R/$out -- python3 $R/bench.py --full --no-cpu-baseline "$@" > $R/$out/bench.log 2>&1
 python3 - <<PY
 import csv,glob,collections
 d=collections.defaultdict(list)

@@ -8,13 +8,13 @@ rm -rf $out; mkdir -p $out
 cd /tmp; export TMPDIR=/tmp
 for wl in sparse clustered dense; do
   # (a) kernel trace + stats of the exact bench command
-  rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt_$wl -- python3 $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-columns --no-traffic --workload $wl > $out/bench_profiled_$wl.json 2> $out/kt_$wl.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt_$wl -- python3 $R/bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-columns --no-traffic --workload $wl > $out/bench_profiled_$wl.json 2> $out/kt_$wl.err
   # (b) HBM traffic: separate --pmc passes (FETCH_SIZE and WRITE_SIZE do not fit one pass)
   for c in FETCH_SIZE WRITE_SIZE; do
-    rocprofv3 --kernel-trace --pmc $c --output-format csv -d $out/pmc_${wl}_$c -- python3 $R/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-columns --no-traffic --workload $wl > /dev/null 2> $out/pmc_${wl}_$c.err
+    rocprofv3 --kernel-trace --pmc $c --output-format csv -d $out/pmc_${wl}_$c -- python3 $R/bench.py --steps 5 --warmup 1 --full --no-cpu-baseline --no-columns --no-traffic --workload $wl > /dev/null 2> $out/pmc_${wl}_$c.err
   done
   # (c) the un-profiled bench line
-  python3 $R/bench.py --steps 20 --warmup 3 --workload $wl > $out/bench_$wl.json 2> $out/bench_$wl.err
+  python3 $R/bench.py --steps 20 --warmup 3 --full --workload $wl > $out/bench_$wl.json 2> $out/bench_$wl.err
   echo "done $wl"
 done
 # (d) SQ counters of the three kernels on the headline workload (separate passes: 8 SQ slots per pass), same build, same run
@@ -23,7 +23,7 @@ for set in "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU S
            "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT" \
            "SQ_INST_CYCLES_VMEM_RD SQ_INST_CYCLES_VMEM_WR SQ_LDS_IDX_ACTIVE SQ_LDS_ADDR_CONFLICT SQ_INSTS_SMEM SQ_INSTS_BRANCH GRBM_GUI_ACTIVE GRBM_COUNT"; do
   i=$((i+1))
-  rocprofv3 --kernel-trace --pmc $set --output-format csv -d $out/sq_p$i -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-columns --no-traffic --workload sparse > /dev/null 2> $out/sq_p$i.err || echo "SQ pass $i failed"
+  rocprofv3 --kernel-trace --pmc $set --output-format csv -d $out/sq_p$i -- python3 $R/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-columns --no-traffic --workload sparse > /dev/null 2> $out/sq_p$i.err || echo "SQ pass $i failed"
 done
 # (e) the kernels of SURVEY 8(f) on the sparse and the clustered GiB (tools/next_rows_time.py): kernel trace per workload
 for wl in sparse clustered; do
@@ -80,7 +80,7 @@ for wl in ("sparse", "clustered", "dense"):
             m = re.search(r"(\w+_kernel)", r["Kernel_Name"])
             k = m.group(1) if m else r["Kernel_Name"][:48]
             d[k].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
-    lines.append(f"== {wl}: rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-columns --workload {wl}")
+    lines.append(f"== {wl}: rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-columns --workload {wl}")
     for k, v in sorted(d.items(), key=lambda kv: -sum(kv[1])):
         lines.append(f"  {k:36s} calls {len(v):4d}  avg {sum(v)/len(v):10.1f} us  min {min(v):10.1f}  max {max(v):10.1f}  total {sum(v):12.1f}")
     # PMC: bytes per launch
@@ -120,7 +120,7 @@ for f in glob.glob(f"{out}/sq_p*/**/*counter_collection.csv", recursive=True):
         if m:
             agg[m.group(1)][r["Counter_Name"]].append(float(r["Counter_Value"]))
 with open(f"{out}/pmc_sq_counters_sparse.txt", "w") as o:
-    o.write("rocprofv3 --kernel-trace --pmc <8 SQ counters per pass> -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-columns --workload sparse\n")
+    o.write("rocprofv3 --kernel-trace --pmc <8 SQ counters per pass> -- python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-columns --workload sparse\n")
     for k in agg:
         o.write(f"== {k}\n")
         for c, v in sorted(agg[k].items()):

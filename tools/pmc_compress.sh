@@ -12,7 +12,7 @@ for set in "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU S
            "FETCH_SIZE" "WRITE_SIZE" "GRBM_GUI_ACTIVE GRBM_COUNT"; do
   i=$((i+1))
   [ -n "$PMC_PASSES" ] && [ $i -gt $PMC_PASSES ] && break
-  rocprofv3 --kernel-trace --pmc $set --output-format csv -d $R/$out/p$i -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --workload $wl $BENCH_EXTRA > $R/$out/p$i.log 2>&1 || echo "pass $i failed"
+  rocprofv3 --kernel-trace --pmc $set --output-format csv -d $R/$out/p$i -- python3 $R/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --workload $wl $BENCH_EXTRA > $R/$out/p$i.log 2>&1 || echo "pass $i failed"
 done
 python3 - <<PY
 import csv, glob, collections, os
