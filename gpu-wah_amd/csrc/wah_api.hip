@@ -51,7 +51,7 @@ struct CompressLayout {
     size_t ctrl_off, desc_off, unseg_off, half, total; // total: what an input of this size needs
 };
 
-// first half: scan area of compress_pair_kernel / compress_tile_kernel (one block of kScanBlockWords per 64 x 256 tiles, +
+// first half: scan area of compress_pair_kernel / compress_tile_body (one block of kScanBlockWords per 64 x 256 tiles, +
 // the block a full last superrow publishes into); second half: scan area of the unsegmented mode (blocks of
 // kUnsegBlockWords), which the no-wait route borrows for its table of tile counts (offsets below 2^48: never a valid
 // epoch stamp)
@@ -460,39 +460,23 @@ static int compress_device_impl(const uint32_t *d_in, const uint32_t *d_in2, int
     a.n_words = n_words;
     a.n_segments = (uint32_t)l.n_segments;
     a.n_tiles = (uint32_t)l.n_tiles;
-    a.wave_segs = l.wave_segs;
-    a.unseg_desc = nullptr;
-    a.pair_layout = 0;
-    if (!d_in2 && !indexed && !unsegmented && !no_wait) { // the plain compress: pair-layout kernel, its own tile shape
-        const wah::TileShape shape = wah::compress_tile_shape(l.n_segments);
-        if (shape.body_pairs) {
-            a.pair_layout = 1;
-            a.wave_segs = 2 * shape.body_pairs;
-            a.tail_pairs = shape.tail_pairs;
-            a.big_tiles = shape.big_tiles;
-            a.n_tiles = shape.n_tiles;
-        }
-    }
-    if (unsegmented) { // fills cross the segment cut (compress_unseg_pair_kernel): its own scan area, the tile shapes of the plain compress
-        a.unseg_desc = reinterpret_cast<uint32_t *>(ws + l.unseg_off);
-        const wah::TileShape shape = wah::compress_tile_shape(l.n_segments);
-        const uint32_t body = shape.body_pairs ? shape.body_pairs : 3u; // (WAH_WAVE_PAIRS=0 switches only the plain compress's kernel off)
-        a.pair_layout = 1;
-        a.wave_segs = 2 * body;
-        a.tail_pairs = shape.body_pairs ? shape.tail_pairs : 3u;
-        a.big_tiles = shape.body_pairs ? shape.big_tiles : (uint32_t)ceil_div((l.n_segments + 1) / 2, (uint64_t)wah::kCompressTileWaves * 3u);
-        a.n_tiles = shape.body_pairs ? shape.n_tiles : a.big_tiles;
-    }
-    if (indexed) { // groups come from two indexed streams (bitop_tile_kernel): its own tile shape
-        a.wave_segs = wah::kIndexedSegsPerWave;
-        a.n_tiles = (uint32_t)ceil_div(l.n_segments, (uint64_t)wah::kCompressTileWaves * wah::kIndexedSegsPerWave);
-    }
+    a.wave_segs = l.wave_segs; // (pair mode: compress_tile_pair_kernel)
+    // unsegmented: fills cross the segment cut (compress_unseg_pair_kernel), its own scan area
+    a.unseg_desc = unsegmented ? reinterpret_cast<uint32_t *>(ws + l.unseg_off) : nullptr;
     if (no_wait) { // count / scan / place: nobody waits for anybody.  Its own tile shape (two segments per wave; the plain
                    // compress: two pairs); the table of tile counts lies in the workspace's second half
         a.wave_segs = (d_in2 || indexed) ? 2u : wah::compress_nowait_wave_segs(); // (plain and unsegmented: two PAIRS per wave)
         a.n_tiles = (uint32_t)ceil_div(l.n_segments, (uint64_t)wah::kCompressTileWaves * a.wave_segs);
         a.tile_counts = reinterpret_cast<uint64_t *>(ws + l.unseg_off);
-        a.pair_layout = 0;
+    } else if (indexed) { // groups come from two indexed streams (bitop_tile_kernel): its own tile shape
+        a.wave_segs = wah::kIndexedSegsPerWave;
+        a.n_tiles = (uint32_t)ceil_div(l.n_segments, (uint64_t)wah::kCompressTileWaves * wah::kIndexedSegsPerWave);
+    } else if (!d_in2) { // the plain compress and its unsegmented mode: pair-layout kernels, tiles of their own shapes
+        const wah::TileShape shape = wah::compress_tile_shape(l.n_segments);
+        a.wave_segs = 2 * shape.body_pairs;
+        a.tail_pairs = shape.tail_pairs;
+        a.big_tiles = shape.big_tiles;
+        a.n_tiles = shape.n_tiles;
     }
     a.fast_segments = aligned16(d_in) ? 1u : 0u;
     a.full_segments = (uint32_t)(n_words / wah::kSegWords);
@@ -509,7 +493,7 @@ static int compress_device_impl(const uint32_t *d_in, const uint32_t *d_in2, int
     a.host_result = host_result;
 #ifdef WAH_DIAG
     {
-        static const uint32_t tune = [] { // diagnostic build only: 77 / 78 = per-tile time line (tools/tile_timeline.py)
+        static const uint32_t tune = [] { // diagnostic build only: 78 = compress_pair_kernel's per-tile time line (tools/pair_timeline.py)
             const char *e = std::getenv("WAH_TUNE"); // (this block exists in the diagnostic build only)
             return e ? (uint32_t)std::strtoul(e, nullptr, 0) : 0u;
         }();
@@ -670,14 +654,10 @@ static int decode_common(const uint32_t *d_comp, uint64_t c_words, uint32_t *d_o
     // tickets and list entries come out of one address each at 86 per microsecond: 98 us where the sums kernel takes 41).  The library cannot look at the stream without a pass over it, so the default goes by what the
     // CAPACITY allows the stream to be: at most 7 words of output per word of stream, or more than 40 -- one pass; between --
     // the two launches.  A caller who knows better says so (WAH_ONE_PASS / WAH_TWO_LAUNCHES); decompress(), which has the stream
-    // in host memory, samples it and does.  (WAH_DECODE_TWO_PASS=1, experiment builds: always the two launches.)
-    static const bool two_pass_only = [] {
-        const char *f = wah::experiment_env("WAH_DECODE_TWO_PASS");
-        return f && f[0] == '1';
-    }();
+    // in host memory, samples it and does.
     // (7 words of output per word of stream: the tile kernel expands up to 7.5 groups = 7.27 words per word itself)
     const bool prefer_one_pass = route == 1 || (route == 0 && (out_capacity_words <= 7 * c_words || out_capacity_words > 40 * c_words));
-    const bool one_pass = do_scan && do_expand && !no_wait && prefer_one_pass && !two_pass_only && c_words != 0 && aligned16(d_comp);
+    const bool one_pass = do_scan && do_expand && !no_wait && prefer_one_pass && c_words != 0 && aligned16(d_comp);
     if (do_expand || do_scan) g_last_route = one_pass ? wah::kRouteOnePass : no_wait ? wah::kRouteNoWait : wah::kRouteTwoLaunches;
     if (one_pass) {
         if (clear_first) e = wah::launch_clear(ws, l.base_off, s); // (control block -- with the deferred tiles' counters -- and scan area)

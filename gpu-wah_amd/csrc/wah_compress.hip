@@ -18,8 +18,6 @@
 //     agent-scope accesses (correct across the 8 non-coherent XCD L2s), instead of thrust::exclusive_scan + moveData
 //     (compress.cu:133-166, kernels.cu:273-280); nothing is persistent and nothing is cleared between launches.
 #include <atomic>
-#include <cstdio>
-#include <cstdlib>
 
 #include "wah_device.hpp"
 #include "wah_segdecode.hpp"
@@ -28,8 +26,8 @@ namespace wah {
 namespace {
 
 // ===========================================================================
-// compress: per-segment building blocks (loads, regrouping, the two classify passes, final words); the tile kernel
-// that strings them together and its offset scan are described further down, at compress_tile_kernel.
+// compress: per-segment building blocks (loads, regrouping, the two classify passes, final words); the tile body
+// that strings them together and its offset scan are described further down, at compress_tile_body.
 // Per wave and segment in LDS: a 4 KiB STAGE buffer (the 992 input words, later the compacted run-end words in place)
 // and a 2 KiB position array (kernels.cu:126-141 run ends, :188-229 merge, :244-259 final words).
 // ===========================================================================
@@ -61,16 +59,15 @@ __device__ __forceinline__ u32x4 load16(__amdgpu_buffer_rsrc_t rsrc, u32 off) {
 
 // issue the four coalesced 16-byte loads of one segment (3968 B = 248 x 16 B; lanes 56..63 of the fourth load and
 // everything past the end of the bitmap read as zero: the descriptor's bounds do the zero padding of the tail, F5)
-template <bool kAligned>
 __device__ __forceinline__ void prefetch_segment(const u32 *in, const CompressArgs &a, u32 seg, u32 lane, Prefetch &p) {
     // whole segments: 3968 bytes; the (one) partial segment at the end of the bitmap: what is left of it
     const u32 bytes = seg < a.full_segments ? kSegWords * 4u : a.tail_bytes;
     const __amdgpu_buffer_rsrc_t rsrc = make_rsrc(in + (u64)seg * kSegWords, bytes);
     const u32 off = lane * 16u;
-    p.v[0] = load16<kAligned>(rsrc, off);
-    p.v[1] = load16<kAligned>(rsrc, off + 1024u);
-    p.v[2] = load16<kAligned>(rsrc, off + 2048u);
-    p.v[3] = load16<kAligned>(rsrc, off + 3072u);
+    p.v[0] = load16<true>(rsrc, off);
+    p.v[1] = load16<true>(rsrc, off + 1024u);
+    p.v[2] = load16<true>(rsrc, off + 2048u);
+    p.v[3] = load16<true>(rsrc, off + 3072u);
 }
 
 // pair mode: the word-by-word combination (include/wah.h: WAH_OP_*); words behind the bitmap stay zero for every op
@@ -220,7 +217,7 @@ __device__ __forceinline__ void classify_pass2(const SegGroups &g, SegEnds e, u3
 }
 
 // ===========================================================================
-// compress_tile_kernel
+// compress_tile_body: the tile kernels of the bit operations (compress_tile_pair_kernel, bitop_tile_kernel)
 //
 // Workgroup = one TILE of kTileWaves x kWaveSegs consecutive segments, short-lived; tile = arrival order (draw_tile).
 //   every wave : for each of its kWaveSegs segments: 4 x 16-byte loads -> LDS stage -> 16 groups per lane in registers
@@ -430,7 +427,7 @@ __device__ __forceinline__ u64 tile_scan_resolve(const CompressArgs &a, const Sc
             // pattern one ROCm 7.2 build of the decoder's scan got wrong -- wah_decode.hip, sums_resolve)
             scan_issue(a, g, lane, need_a, need_b, need_c, poll);
 #ifdef WAH_DIAG
-            ++*dg_polls;
+            if (dg_polls) ++*dg_polls;
 #endif
             continue;
         }
@@ -463,11 +460,11 @@ __device__ __forceinline__ u64 tile_scan_resolve(const CompressArgs &a, const Sc
         }
         scan_issue(a, g, lane, need_a, need_b, need_c, poll);
 #ifdef WAH_DIAG
-        ++*dg_polls;
+        if (dg_polls) ++*dg_polls;
 #endif
     }
 #ifdef WAH_DIAG
-    dg_t[4] = __builtin_amdgcn_s_memrealtime();
+    if (dg_t) dg_t[4] = __builtin_amdgcn_s_memrealtime(); // (compress_pair_body's time line; the tile body passes none)
 #endif
     const u64 base = sum_c + sum_b + sum_a;
     const u64 end = base + total;
@@ -490,32 +487,31 @@ __device__ __forceinline__ u64 tile_scan_resolve(const CompressArgs &a, const Sc
     return base;
 }
 
-// Where a wave's 31-bit groups come from -- the only thing that differs between compressing a bitmap and combining
-// compressed bitmaps: a SOURCE leaves the groups of one segment in registers (SegGroups) and keeps the next segment's
-// loads in flight meanwhile.
-//   BitmapSource  : the bitmap itself (wah_compress_device; kPair: two decoded bitmaps combined word by word, wah_bitop_device)
-//   IndexedSource : the same segment of TWO indexed compressed streams, expanded and combined group by group
-//                   (wah_bitop_indexed_device) -- the result is compressed without ever existing as a bitmap
-template <bool kPair, bool kAligned>
-struct BitmapSource {
-    Prefetch pre, pre2; // pre2: pair mode only, the second bitmap's words
+// Where a wave's 31-bit groups come from -- the only thing that differs between the two bit operations the tile body
+// serves: a SOURCE leaves the groups of one segment in registers (SegGroups) and keeps the next segment's loads in flight
+// meanwhile.
+//   BitmapPairSource : two decoded bitmaps (16-byte aligned) combined word by word (wah_bitop_device's pair mode)
+//   IndexedSource    : the same segment of TWO indexed compressed streams, expanded and combined group by group
+//                      (wah_bitop_indexed_device) -- the result is compressed without ever existing as a bitmap
+struct BitmapPairSource {
+    Prefetch pre, pre2; // the first and the second bitmap's words
     __device__ __forceinline__ void begin(const CompressArgs &a, u32 seg0, u32, u32 lane) {
         if (seg0 < a.n_segments) {
-            prefetch_segment<kAligned>(a.in, a, seg0, lane, pre);
-            if (kPair) prefetch_segment<kAligned>(a.in2, a, seg0, lane, pre2);
+            prefetch_segment(a.in, a, seg0, lane, pre);
+            prefetch_segment(a.in2, a, seg0, lane, pre2);
         }
     }
     // segment `seg` -> g; `more`: the wave has another segment after this one
     __device__ __forceinline__ void produce(const CompressArgs &a, u32 seg, bool more, u32 nvalid, u32 *stage, unsigned short *, u32 lane,
                                             SegGroups &g) {
-        if (kPair) combine_pair(pre, pre2, a.op);
+        combine_pair(pre, pre2, a.op);
         stage_prefetched(pre, stage, lane);
         // the wave re-reads other lanes' words: order the LDS traffic at wavefront scope (no barrier needed)
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         // the next segment's loads are in flight while this one is classified
         if (more && seg + 1 < a.n_segments) {
-            prefetch_segment<kAligned>(a.in, a, seg + 1, lane, pre);
-            if (kPair) prefetch_segment<kAligned>(a.in2, a, seg + 1, lane, pre2);
+            prefetch_segment(a.in, a, seg + 1, lane, pre);
+            prefetch_segment(a.in2, a, seg + 1, lane, pre2);
         }
         regroup(stage + ((31u * lane) >> 5), (31u * lane) & 31u, lane, nvalid, g);
     }
@@ -611,14 +607,6 @@ __device__ __forceinline__ void compress_tile_body(const CompressArgs &a, Source
     const u32 wave = wave_id();
     const u32 tile = kMode == kTileScan ? draw_tile(a.ctrl, &s_tile) : blockIdx.x;
     const u32 seg0 = (tile * kTileWaves + wave) * kWaveSegs; // this wave's segments: seg0 .. seg0 + kWaveSegs - 1
-#ifdef WAH_DIAG
-    u64 dg_t[8];
-    u32 dg_polls = 0;
-    dg_t[0] = __builtin_amdgcn_s_memrealtime();
-#define DG(i) dg_t[i] = __builtin_amdgcn_s_memrealtime()
-#else
-#define DG(i)
-#endif
 
     // ---- launch epoch (wah_device.hpp): the same value for every workgroup of the launch --------------------------------
     LaunchEpoch le = {};
@@ -657,7 +645,6 @@ __device__ __forceinline__ void compress_tile_body(const CompressArgs &a, Source
         if (seg < a.n_segments) {
             nval[j] = (seg == a.n_segments - 1) ? a.last_segment_groups : kSegGroups;
             src.produce(a, seg, j + 1 < kWaveSegs, nval[j], stage, pos, lane, grp[j]);
-            if (j == 0) DG(1);
             cnt[j] = classify_pass1(grp[j], never, ends[j]) - (kSegGroups - nval[j]);
         }
     }
@@ -665,9 +652,7 @@ __device__ __forceinline__ void compress_tile_body(const CompressArgs &a, Source
 #pragma unroll
     for (u32 j = 0; j < kWaveSegs; ++j) count += cnt[j];
     if (lane == 0) s_count[wave] = count;
-    DG(2);
     __syncthreads();
-    DG(3);
 
     // ---- wave 0: the tile's count goes out, the sweep of the others' counts is issued --------------------------------
     const ScanGeom g = scan_geom(tile);
@@ -688,12 +673,6 @@ __device__ __forceinline__ void compress_tile_body(const CompressArgs &a, Source
                 __hip_atomic_store(block + (g.row - g.row0) * kRowTiles + g.idx, (epoch << kGranuleCountBits) | total, __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_AGENT);
         }
-#ifdef WAH_DIAG
-        if (a.tune == 77u) { // time line mode: how long does the sweep itself take?
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            DG(5);
-        }
-#endif
     }
 
     if (kMode == kTileCount) return;
@@ -712,51 +691,15 @@ __device__ __forceinline__ void compress_tile_body(const CompressArgs &a, Source
         }
     }
 
-    DG(6);
     if (kMode == kTileScan && wave == 0) {
         // the sweep of the other tiles' counts: one round trip of three loads per lane, issued only now (see
         // compress_pair_body: issued right behind the publication it mostly finds the nearest predecessors missing)
         scan_issue(a, g, lane, true, g.has_prev, true, poll);
-#ifdef WAH_DIAG
-        const u64 base = tile_scan_resolve(a, g, block, le, tile, total, lane, poll, dg_t, &dg_polls);
-#else
         const u64 base = tile_scan_resolve(a, g, block, le, tile, total, lane, poll, nullptr, nullptr);
-#endif
         if (lane == 0) s_base = base;
     }
     __syncthreads();
-#ifdef WAH_DIAG
-    if (wave == 0 && lane == 0 && a.seg_offsets && (a.tune == 77u || a.tune == 78u)) { // per-tile time line (tools/tile_timeline.py)
-        a.seg_offsets[(u64)tile * 8 + 0] = dg_t[0]; // start
-        a.seg_offsets[(u64)tile * 8 + 1] = dg_t[3]; // counts known (barrier 1 passed) = publish
-        a.seg_offsets[(u64)tile * 8 + 2] = dg_t[5]; // first sweep returned
-        a.seg_offsets[(u64)tile * 8 + 3] = dg_t[4]; // offset known
-        a.seg_offsets[(u64)tile * 8 + 4] = dg_polls;
-        a.seg_offsets[(u64)tile * 8 + 5] = dg_t[6]; // pass 2 + final words done
-        a.seg_offsets[(u64)tile * 8 + 6] = __builtin_amdgcn_s_memrealtime(); // barrier 2 passed
-    }
-    if (wave == 0 && lane == 0 && tile % 67u == 0u) { // a sample: the atomics must not become the bottleneck
-        unsigned long long *d = reinterpret_cast<unsigned long long *>(a.ctrl + 192);
-        atomicAdd(d + 0, (unsigned long long)(dg_t[1] - dg_t[0])); // loads -> staged
-        atomicAdd(d + 1, (unsigned long long)(dg_t[2] - dg_t[1])); // classify
-        atomicAdd(d + 2, (unsigned long long)(dg_t[3] - dg_t[2])); // barrier 1 (slowest wave of the tile)
-        atomicAdd(d + 3, (unsigned long long)(dg_t[4] - dg_t[3])); // scan
-        atomicAdd(d + 4, (unsigned long long)dg_polls);
-        atomicAdd(d + 5, 1ull);
-        atomicAdd(d + 6, (unsigned long long)(__builtin_amdgcn_s_memrealtime() - dg_t[0]));
-        u32 xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        xcc &= 7u;
-        atomicAdd(d + 8 + xcc, (unsigned long long)(dg_t[4] - dg_t[3]));  // scan (incl. pass 2) by XCD
-        atomicAdd(d + 16 + xcc, (unsigned long long)dg_polls);            // re-polls by XCD
-        atomicAdd(d + 24 + xcc, 1ull);                                     // sampled tiles by XCD
-        if (xcc != (tile & 7u)) atomicAdd(d + 7, 1ull);                    // tiles NOT on XCD blockIdx % 8
-    }
-#endif
 
-#ifdef WAH_DIAG
-    if (a.seg_offsets && (a.tune == 77u || a.tune == 78u)) return; // time line mode: the index buffer holds the stamps
-#endif
     // ---- the parked words to their place ---------------------------------------------------------------------------
     u64 base = uniform64(s_base) + uniform32(s_prefix[wave]);
 #pragma unroll
@@ -1075,17 +1018,18 @@ __global__ __launch_bounds__(64) void unseg_offsets_kernel(const CompressArgs a)
 
 #include "wah_compress_unseg_pair.inc"
 
-template <bool kPair, bool kAligned, u32 kWaveSegs>
-__global__ __launch_bounds__(kTileWaves * 64, kWaveSegs <= 2 ? 6 : 4) void compress_tile_kernel(const CompressArgs a) {
-    BitmapSource<kPair, kAligned> src;
-    compress_tile_body<BitmapSource<kPair, kAligned>, kWaveSegs>(a, src);
+// ---- the pair mode (wah_bitop_device's combining compress): kWaveSegs segments per wave (compress_wave_segs) ------------
+template <u32 kWaveSegs>
+__global__ __launch_bounds__(kTileWaves * 64, kWaveSegs <= 2 ? 6 : 4) void compress_tile_pair_kernel(const CompressArgs a) {
+    BitmapPairSource src;
+    compress_tile_body<BitmapPairSource, kWaveSegs>(a, src);
 }
 
-// ---- the no-wait route of the pair mode (wah_bitop_device's combining compress): two segments per wave ----------------
+// ---- ... and its no-wait route: two segments per wave ------------------------------------------------------------------
 template <int kMode>
 __global__ __launch_bounds__(kTileWaves * 64, 4) void compress_tile_pair_nowait_kernel(const CompressArgs a) {
-    BitmapSource<true, true> src;
-    compress_tile_body<BitmapSource<true, true>, 2, kMode>(a, src);
+    BitmapPairSource src;
+    compress_tile_body<BitmapPairSource, 2, kMode>(a, src);
 }
 
 // ---- the no-wait route (kTileCount / kTilePlace of compress_pair_body): two pairs per wave, whatever the size of the bitmap ------
@@ -1157,13 +1101,12 @@ __global__ __launch_bounds__(kTileWaves * 64, 4) void bitop_tile_kernel(const Co
 
 } // namespace
 
-template <bool kPair, bool kAligned>
-static void launch_tiles(const CompressArgs &a, hipStream_t s) {
+static void launch_tile_pairs(const CompressArgs &a, hipStream_t s) { // the pair mode: compress_tile_pair_kernel
     const dim3 grid(a.n_tiles), block(kTileWaves * 64);
     switch (a.wave_segs) {
-    case 1: hipLaunchKernelGGL((compress_tile_kernel<kPair, kAligned, 1>), grid, block, 0, s, a); break;
-    case 2: hipLaunchKernelGGL((compress_tile_kernel<kPair, kAligned, 2>), grid, block, 0, s, a); break;
-    default: hipLaunchKernelGGL((compress_tile_kernel<kPair, kAligned, (u32)kCompressMaxWaveSegs>), grid, block, 0, s, a); break;
+    case 1: hipLaunchKernelGGL(compress_tile_pair_kernel<1>, grid, block, 0, s, a); break;
+    case 2: hipLaunchKernelGGL(compress_tile_pair_kernel<2>, grid, block, 0, s, a); break;
+    default: hipLaunchKernelGGL(compress_tile_pair_kernel<(u32)kCompressMaxWaveSegs>, grid, block, 0, s, a); break;
     }
 }
 
@@ -1234,26 +1177,16 @@ static void launch_pairs(const CompressArgs &a, hipStream_t s) {
 }
 
 hipError_t launch_compress(const CompressArgs &a, hipStream_t s) {
-    if (a.pair_layout && !a.unseg_desc) {
-        if (a.fast_segments)
-            launch_pairs<true>(a, s);
-        else
-            launch_pairs<false>(a, s);
-        return hipGetLastError();
-    }
-    if (a.unseg_desc) {
-        if (a.fast_segments)
-            launch_unseg<true>(a, s);
-        else
-            launch_unseg<false>(a, s);
-        return hipGetLastError();
-    }
-    if (a.in2)
-        launch_tiles<true, true>(a, s);
+    if (a.in2) // pair mode
+        launch_tile_pairs(a, s);
+    else if (a.unseg_desc && a.fast_segments)
+        launch_unseg<true>(a, s);
+    else if (a.unseg_desc)
+        launch_unseg<false>(a, s);
     else if (a.fast_segments)
-        launch_tiles<false, true>(a, s);
+        launch_pairs<true>(a, s);
     else // input only 4-byte aligned: dword loads
-        launch_tiles<false, false>(a, s);
+        launch_pairs<false>(a, s);
     return hipGetLastError();
 }
 
@@ -1271,11 +1204,6 @@ hipError_t launch_bitop_tiles(const CompressArgs &a, const BitopOperands &ops, h
 
 // segments per wavefront for a bitmap of n_segments: enough tiles to occupy the chip first, long tiles after that
 uint32_t compress_wave_segs(uint64_t n_segments) {
-    static const int forced = [] { // experiments only
-        const char *e = experiment_env("WAH_WAVE_SEGS");
-        return e ? std::atoi(e) : 0;
-    }();
-    if (forced == 1 || forced == 2 || forced == 4 || forced == kCompressMaxWaveSegs) return (uint32_t)forced;
     // measured on 4 MiB .. 512 MiB bitmaps (tools/scratch/size_s_sweep.py): 4 MiB 8.0 / 8.6 / 12.9 us with 1 / 2 / 5
     // segments per wave, 16 MiB 16.2 / 13.1 / 15.0, 32 MiB 27.5 / 21.9 / 17.8, 128 MiB 76.6 / 57.2 / 50.6
     if (n_segments <= 2400) return 1;
@@ -1289,10 +1217,6 @@ uint32_t compress_wave_segs(uint64_t n_segments) {
 // it into ONE more round, so that a launch does not end with a few full-size tiles running alone.  Bitmaps of less than a
 // round: one shape, the smallest that fits them into one round.
 TileShape compress_tile_shape(uint64_t n_segments) {
-    static const int forced = [] { // experiments only: 0 switches the kernel off, 1..3: one shape
-        const char *e = experiment_env("WAH_WAVE_PAIRS");
-        return e ? std::atoi(e) : -1;
-    }();
     // (per device: a process may drive several, and not all of them need be the same part)
     static std::atomic<uint32_t> slots_of[64];
     int dev = 0;
@@ -1308,29 +1232,13 @@ TileShape compress_tile_shape(uint64_t n_segments) {
     const uint64_t pairs = (n_segments + 1) / 2;
     const uint64_t w = (uint64_t)kTileWaves;
     TileShape t = {3, 3, 0, 0};
-    if (forced == 0) return TileShape{0, 0, 0, 0};
-    static const char *shape_env = experiment_env("WAH_SHAPE"); // experiments only: "big_tiles,tail_pairs" (body tiles of 3 pairs)
-    if (shape_env) {
-        unsigned long big = 0, tail = 0;
-        if (std::sscanf(shape_env, "%lu,%lu", &big, &tail) == 2 && tail >= 1 && tail <= 2 && big * w * 3 <= pairs) {
-            t.tail_pairs = (uint32_t)tail;
-            t.big_tiles = (uint32_t)big;
-            t.n_tiles = t.big_tiles + (uint32_t)((pairs - big * w * 3 + w * tail - 1) / (w * tail));
-            return t;
-        }
-    }
-    if (forced >= 1 && forced <= 3) {
-        t.body_pairs = t.tail_pairs = (uint32_t)forced;
-        t.big_tiles = t.n_tiles = (uint32_t)((pairs + w * forced - 1) / (w * forced));
-        return t;
-    }
     auto fits = [&](uint64_t rest) -> uint32_t { // smallest shape that puts `rest` pairs into one round (3: whatever it takes)
         return rest <= slots * w ? 1u : rest <= slots * w * 2 ? 2u : 3u;
     };
     const uint64_t round = slots * w * 3; // pairs of a full round of body tiles
     const uint64_t rounds = pairs / round;
     const uint64_t rest = pairs - rounds * round;
-    if (rounds == 0 || rest == 0) { // one shape.  Less than a round: measured (sparse, tools/pair_sizes.py; 1 / 2 / 3 pairs
+    if (rounds == 0 || rest == 0) { // one shape.  Less than a round: measured (sparse, each shape forced; 1 / 2 / 3 pairs
         // per wave): 8 MiB 8.4 / 10.0 / 12.1 us, 16 MiB 12.3 / 11.5 / 13.3, 32 MiB 22.4 / 18.4 / 16.1, 64 MiB 36.1 / 32.4 / 26.6 --
         // few long tiles beat many short ones as soon as the bitmap is worth more than the launch's latency chain
         const uint32_t p = rounds == 0 ? (pairs <= 1400 ? 1u : pairs <= 3000 ? 2u : 3u) : 3u;

@@ -1,6 +1,6 @@
 // wah_compress_pair.inc -- the PAIR-layout compress kernel (included by wah_compress.hip, inside namespace wah::{anonymous}).
 //
-// Same tile protocol as compress_tile_kernel (arrival tickets, launch epochs, row scan: see there), different use of the
+// Same tile protocol as compress_tile_body (arrival tickets, launch epochs, row scan: see there), different use of the
 // wavefront.  There a step is 64 consecutive groups across the lanes, so "the next group" is a DPP move, every step needs
 // its own rank (v_mbcnt + v_bcnt pairs) and fill lengths come out of a position array in LDS: 395 vector + 67 LDS
 // instructions per segment, and the kernel spends half of its wave cycles issuing them (profiles/r02_pmc_sq_counters).
@@ -297,6 +297,9 @@ __device__ __forceinline__ void compress_pair_body(const CompressArgs &a, const 
 #ifdef WAH_DIAG
     u64 dg_t[8] = {};
     dg_t[0] = __builtin_amdgcn_s_memrealtime();
+#define DG(i) dg_t[i] = __builtin_amdgcn_s_memrealtime()
+#else
+#define DG(i)
 #endif
     if (kMode == kTileCount && tile == 0 && threadIdx.x == 0 && !a.keep_error)
         __hip_atomic_store(a.ctrl + kCtlError, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -384,7 +387,7 @@ __device__ __forceinline__ void compress_pair_body(const CompressArgs &a, const 
     DG(5);
     if (kMode == kTileScan && wave == 0) {
         // The sweep of the other tiles' counts goes out HERE, after pass 2, not right behind the publication (where
-        // compress_tile_kernel issues it to hide its round trip): that early the nearest predecessors have not published
+        // compress_tile_body issues it to hide its round trip): that early the nearest predecessors have not published
         // yet, the sweep has to be repeated anyway, and every repetition is a round trip to lines that other XCDs are
         // writing.  Measured on the 1 GiB bitmaps (sparse / clustered / dense, isolated launches, three pairs per wave):
         // 0.2905 / 0.2098 / 0.3949 ms with the early sweep, 0.2795 / 0.1813 / 0.3845 ms with this one.

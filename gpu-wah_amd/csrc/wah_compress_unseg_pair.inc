@@ -2,7 +2,7 @@
 // (included by wah_compress.hip behind the unsegmented section, inside namespace wah::{anonymous}).
 //
 // The bookkeeping described at the head of that section, with the PAIR of segments a wavefront classifies at once as the unit
-// (round 2 did it per segment on the tile body of compress_tile_kernel): inside a pair nothing is cut (pair_pass1<false>:
+// (round 2 did it per segment on the tile body, compress_tile_body): inside a pair nothing is cut (pair_pass1<false>:
 // a run crosses from the pair's first segment into its second by itself), the pair's last group closes its run as it
 // does in the segmented mode, and where that cut falls inside a run the same two local rules apply to the pair:
 //   drop_p  = the trailing fill of pair p continues into p + 1     -> the pair emits one word less (its last)

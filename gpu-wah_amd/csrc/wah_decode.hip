@@ -1341,11 +1341,7 @@ hipError_t launch_decode_expand(const ExpandArgs &a0, u64 n_tiles, hipStream_t s
     // taking every parts-th group of kExpandWaves segments.  The true output size is only known on the device; the
     // capacity bounds it, and a part with nothing to do costs one 16 KiB tile read.
     ExpandArgs a = a0;
-    static const u64 want = [] { // workgroups: 256 CUs x 6 resident x ~2.7 (experiments: WAH_EXPAND_WANT)
-        const char *e = experiment_env("WAH_EXPAND_WANT");
-        const long v = e ? std::atol(e) : 0;
-        return v > 0 ? (u64)v : 4096ull;
-    }();
+    constexpr u64 want = 4096; // workgroups: 256 CUs x 6 resident x ~2.7
     const u64 segs_per_tile = a.out_capacity / kSegWords / n_tiles;
     u64 parts = (want + n_tiles - 1) / n_tiles;
     // ... and a workgroup should not expand much more than 24 segments (six per wave): the chip writes faster the shorter its
@@ -1369,10 +1365,7 @@ hipError_t launch_decode_expand(const ExpandArgs &a0, u64 n_tiles, hipStream_t s
 
 // the general decoder in one pass (decode_tile_kernel) + the launch that takes what it deferred
 hipError_t launch_decode_tiles(const ScanArgs &sa, const ExpandArgs &xa, u64 *defer, hipStream_t s) {
-    static const u32 batch = [] { // tiles per workgroup: 2 (experiments: WAH_DT_BATCH=1)
-        const char *e = experiment_env("WAH_DT_BATCH");
-        return e && e[0] == '1' ? 1u : 2u;
-    }();
+    constexpr u32 batch = 2; // tiles per workgroup
     TileDecodeArgs t;
     t.comp = sa.comp;
     t.c_words = sa.c_words;
@@ -1390,21 +1383,14 @@ hipError_t launch_decode_tiles(const ScanArgs &sa, const ExpandArgs &xa, u64 *de
     t.gen_desc = sa.gen_desc;
     t.scan_words = sa.scan_words;
     t.host_result = sa.host_result;
-    if (batch == 1)
-        hipLaunchKernelGGL(decode_tile_kernel<1>, dim3(t.n_wg_tiles), dim3(kDtWaves * 64), 0, s, t);
-    else
-        hipLaunchKernelGGL(decode_tile_kernel<2>, dim3(t.n_wg_tiles), dim3(kDtWaves * 64), 0, s, t);
+    hipLaunchKernelGGL(decode_tile_kernel<batch>, dim3(t.n_wg_tiles), dim3(kDtWaves * 64), 0, s, t);
 #ifdef WAH_DIAG
     if (std::getenv("WAH_DIAG_NO_LIST")) return hipGetLastError(); // (the time line in the output's head survives: tools/decode_tile_timeline.py)
 #endif
     ExpandArgs x = xa;
     x.parts = 1;
     x.defer_list = nullptr; // (the list is this launch's own argument)
-    static const unsigned list_dyn_lds = [] { // experiments only: dynamic LDS as an occupancy limiter (WAH_LIST_DYNLDS = bytes)
-        const char *e = experiment_env("WAH_LIST_DYNLDS");
-        return e ? (unsigned)std::strtoul(e, nullptr, 0) : 0u;
-    }();
-    hipLaunchKernelGGL(decode_expand_list_kernel, dim3(defer_list_grid(xa.out_capacity, xa.c_words)), dim3(kExpandThreads), list_dyn_lds, s, x, (const u64 *)t.defer_list, (const u32 *)t.defer_count, t.defer_capacity, 0u);
+    hipLaunchKernelGGL(decode_expand_list_kernel, dim3(defer_list_grid(xa.out_capacity, xa.c_words)), dim3(kExpandThreads), 0, s, x, (const u64 *)t.defer_list, (const u32 *)t.defer_count, t.defer_capacity, 0u);
     return hipGetLastError();
 }
 

@@ -483,9 +483,6 @@ __global__ __launch_bounds__(kDtWaves * 64, (kP <= 2 ? WAH_DT_MINW : 4)) void de
         const u32 wbase = (u32)(uintptr_t)(lds_u32_ptr)s_words;
         const u64 k_begin = (tb + kSegGroups - 1) / kSegGroups;
         const u64 k_end = (tb + total32 + kSegGroups - 1) / kSegGroups;
-#ifdef WAH_DT_PROBE_NO_EXPANSION // probe: the kernel without its segment loop
-        if (a.out_capacity != ~0ull) continue;
-#endif
 #ifdef WAH_DIAG
         if (jj == 0) DGT(8); else DGT(14);
 #endif
@@ -543,9 +540,6 @@ __global__ __launch_bounds__(kDtWaves * 64, (kP <= 2 ? WAH_DT_MINW : 4)) void de
             }
             if (seg_w0 >= a.out_capacity) continue;
             if (a.out_capacity - seg_w0 < seg_words) seg_words = (u32)(a.out_capacity - seg_w0);
-#ifdef WAH_DT_PROBE_NO_STORES // probe (tools/experiments): every store falls outside the descriptor and is dropped by the hardware
-            seg_words = a.out_capacity == ~0ull ? seg_words : 0u;
-#endif
             const __amdgpu_buffer_rsrc_t rsrc = make_rsrc(a.out + seg_w0, seg_words * 4u); // stores past the end are dropped
 
             // start flags of the segment's groups, 32 per lane, aligned to the segment: lane l = groups 32 l .. 32 l + 31

@@ -116,7 +116,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *p, u32 b
 }
 
 // ---------------------------------------------------------------------------
-// Launch epochs: how the scan areas of the tile kernels (compress_tile_kernel, decode_sums_kernel) get by without
+// Launch epochs: how the scan areas of the tile kernels (compress_tile_body, decode_sums_kernel) get by without
 // being cleared.  Everything a launch publishes is stamped with the launch epoch kept in the control block: read by
 // every workgroup at its start, advanced by the LAST tile once its scan is complete -- by then every other tile has
 // published, hence started.  A zeroed workspace is epoch 0 = "nothing valid".  When the epoch space is used up, the

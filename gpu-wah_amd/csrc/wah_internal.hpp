@@ -10,10 +10,11 @@
 
 namespace wah {
 
-// Experiment switches (tile shapes, batch sizes, forced routes: what tools/*.sh sweep) are read from the environment only
-// by builds made with -DWAH_EXPERIMENTS (`make -C gpu-wah_amd exp` -> libwah_hip_exp.so, used through WAH_LIB_PATH); the
-// shipped library reads none of them.  (What it does read is documented in include/wah.h: WAH_HOST_CACHE,
-// WAH_FORCE_FALLBACK, WAH_FAULT_INJECT.)
+// The one experiment switch, WAH_BITOP_ROUTE (forces the route of the indexed bit operations: "runs" / "groups", for
+// tools/bitop_density_time.py, which compares the two), is read from the environment only by builds made with
+// -DWAH_EXPERIMENTS (`make -C gpu-wah_amd exp` -> libwah_hip_exp.so, used through WAH_LIB_PATH); the shipped library
+// does not read it.  (What it does read is documented in include/wah.h: WAH_HOST_CACHE, WAH_FORCE_FALLBACK,
+// WAH_FAULT_INJECT.)
 inline const char *experiment_env(const char *name) {
 #ifdef WAH_EXPERIMENTS
     return getenv(name);
@@ -36,7 +37,7 @@ constexpr uint32_t kSteps = 16; // 64 groups (one wavefront) per step
 
 // ---- inter-workgroup control block (uint32 words)
 // decode / aux kernels: zeroed before each launch.  compress: zeroed ONCE (wah_workspace_init_device), then kept up by
-// the kernel itself (launch epochs, see compress_tile_kernel).
+// the kernel itself (launch epochs, see compress_tile_body).
 constexpr uint32_t kCtlStart = 0;        // arrival ticket: order in which workgroups start running (alone on its 128-byte line:
                                          // every workgroup of a launch adds to it)
 constexpr uint32_t kCtlEpoch = 64;       // tile kernels: epoch of the NEXT launch (0 = fresh workspace); read-mostly line
@@ -60,7 +61,7 @@ constexpr uint32_t kBucketSaturated = 0xFFFFFFFFu; // a bucket holding a count a
 #define WAH_DEFER_PART_SEGS 32 // (clustered GiB through the list, one box: 16: 0.281 ms, 24: 0.251, 32: 0.2455, 48: 0.253)
 #endif
 constexpr uint32_t kDeferPartSegs = WAH_DEFER_PART_SEGS;  // output segments per work item of the list's launch (eight per wave: the chip writes faster the
-                                         // shorter its waves live, tools/expand_want_sweep.sh)
+                                         // shorter its waves live: launch_decode_expand)
 constexpr uint32_t kCtlWords = 256;      // 1 KiB
 constexpr uint32_t kErrTimeout = 1u;     // a bounded wait expired
 constexpr uint32_t kErrCapacity = 2u;    // output would exceed its capacity
@@ -77,12 +78,12 @@ constexpr int kCompressTileWaves = WAH_TILE_WAVES;
 constexpr int kCompressMaxWaveSegs = 5; // segments a wavefront compresses one after the other: 1, 2 or this (by bitmap size)
 uint32_t compress_wave_segs(uint64_t n_segments);
 // pair-layout kernel: the tile shapes of a launch (compress_pair_kernel): body tiles of body_pairs pairs per wavefront, then
-// tail tiles of tail_pairs; body_pairs == 0: kernel switched off
+// tail tiles of tail_pairs
 struct TileShape {
     uint32_t body_pairs, tail_pairs, big_tiles, n_tiles;
 };
 TileShape compress_tile_shape(uint64_t n_segments);
-// scan area of the compress kernel (see compress_tile_kernel): one block per superrow of 64 rows x 256 tiles
+// scan area of the compress kernels (see compress_tile_body): one block per superrow of 64 rows x 256 tiles
 constexpr uint32_t kRowSlots = 65;                 // u64 slots of a superrow: words in front of it, words of each of its rows
 constexpr uint32_t kScanSlotsAt = 64 * 256;        // 32-bit words: the slots follow the superrow's granules
 constexpr uint32_t kScanBlockWords = 64 * 256 + 256; // granules + slots, padded to 1 KiB
@@ -107,8 +108,9 @@ struct CompressArgs {
     uint32_t op;           // ... with WAH_OP_AND / OR / XOR / ANDNOT
     uint64_t n_words;
     uint32_t n_segments;          // ceil(G / 1024)
-    uint32_t wave_segs;           // segments per wavefront of this launch (compress_wave_segs)
-    uint32_t pair_layout;         // 1: compress_pair_kernel (a lane owns 32 consecutive groups; wave_segs / 2 pairs per wavefront)
+    uint32_t wave_segs;           // segments per wavefront of this launch (compress_wave_segs); pair layout (the plain compress:
+                                  // a lane owns 32 consecutive groups): wave_segs / 2 pairs per wavefront
+    uint32_t reserved;            // (unused: keeps the kernels' offsets of the fields behind it, and so their machine code)
     uint32_t n_tiles;             // ceil(n_segments / (kCompressTileWaves * wave_segs)); pair layout: body + tail tiles
     uint32_t big_tiles;           // pair layout: tiles [0, big_tiles) have wave_segs / 2 pairs per wave, the rest tail_pairs
     uint32_t tail_pairs;          // pair layout: pairs per wave of the tail tiles (== wave_segs / 2: one shape)
@@ -121,14 +123,14 @@ struct CompressArgs {
     uint64_t *out_words;   // device scalar: C
     uint64_t *seg_offsets; // optional, n_segments + 1 entries
     uint32_t *ctrl;        // kCtlWords
-    uint32_t *gen_desc;    // scan area: blocks of kScanBlockWords (see compress_tile_kernel)
+    uint32_t *gen_desc;    // scan area: blocks of kScanBlockWords (see compress_tile_body)
     uint32_t *unseg_desc;  // non-null: unsegmented mode, its scan area: blocks of kUnsegBlockWords (compress_unseg_pair_kernel)
     uint64_t *tile_counts; // no-wait route only: one entry per tile, its word count, then where its words start
     uint64_t scan_words;   // 32-bit words of the whole scan area
     int keep_error;        // 1: the control block was cleared by the caller and may already hold an upstream error
     uint64_t *host_result; // optional, page-locked HOST memory: [0] = 1 | error bits << 32, [1] = C, written by the last tile
                            // (the host-pointer entry points read them after one event wait, without a copy)
-    uint32_t tune;         // WAH_DIAG builds only (WAH_TUNE): time line modes of tools/tile_timeline.py; 0 otherwise
+    uint32_t tune;         // WAH_DIAG builds only (WAH_TUNE): 78 = the time line of tools/pair_timeline.py; 0 otherwise
 };
 
 struct ScanArgs {

@@ -84,8 +84,8 @@ void wah_free(void *p);
  * missed) does it go by the reference's order: scan the stream, read the size back, allocate, expand -- two passes
  * over the stream, two round trips.
  *
- * Environment read by the library (nothing else is; the experiment switches of tools/ exist only in builds made with
- * -DWAH_EXPERIMENTS): WAH_HOST_CACHE=0 (above); WAH_FORCE_FALLBACK=1 (every launch by its no-wait route, below);
+ * Environment read by the library (nothing else is; the one experiment switch, WAH_BITOP_ROUTE, exists only in builds
+ * made with -DWAH_EXPERIMENTS): WAH_HOST_CACHE=0 (above); WAH_FORCE_FALLBACK=1 (every launch by its no-wait route, below);
  * WAH_FAULT_INJECT=timeout -- fault injection: compress() / decompress() treat their first launch as if a bounded
  * in-kernel wait had expired and take the no-wait route by themselves, as they would on a GPU shared in a way that
  * starves the waits (the reference has no failure handling to compare with, compress.cu:89-114). */

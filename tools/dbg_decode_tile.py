@@ -1,5 +1,5 @@
 """Where the one-pass decoder's output differs from the bitmap: first mismatching words, their segments, how many segments are wrong.
-usage: WAH_DT_BATCH=2 python tools/dbg_decode_tile.py [sparse|dense] [size_MiB]"""
+usage: python tools/dbg_decode_tile.py [sparse|dense] [size_MiB]"""
 import importlib, os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 wah = importlib.import_module("gpu-wah_amd")
@@ -52,7 +52,7 @@ if bad.numel():
     print(f"segment {sg}: best alignment of its output with the bitmap: shift {best[1]} groups, {best[0]} of {gb.size} bits equal; ones in got {int(gb.sum())}, in want {int(wb[off0:off0+gb.size].sum())}")
 
 # tile bases and granules in the workspace against what the stream says
-P = int(os.environ.get("WAH_DT_BATCH", "2"))
+P = 2  # tiles per workgroup (launch_decode_tiles)
 W = dec.ws_bytes
 half = ((W - 1024) // 2) & ~255
 ws = dec.workspace

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Time line of decode_tile_kernel (DIAGNOSTIC build: the stamps overwrite the head of the output buffer): per workgroup = per
-BATCH of tiles (two tiles of 8192 words; WAH_DT_BATCH=1: one), when it started, had its last tile staged and all of them counted,
+BATCH of tiles (two tiles of 8192 words), when it started, had its last tile staged and all of them counted,
 published its total, had the first tile's start flags, knew its base, finished (s_memrealtime, 100 MHz).
 A workload `uI` is the uniform bitmap with one bit in 2^I (u9, u10: every tile goes onto the list; the list's launch is left out --
 WAH_DIAG_NO_LIST -- so that the stamps survive, and the route is forced to the one pass).
@@ -11,7 +11,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-os.environ["WAH_LIB_PATH"] = os.path.join(ROOT, "gpu-wah_amd", "libwah_hip_diag.so")
+os.environ["WAH_LIB_PATH"] = os.path.join(ROOT, "gpu-wah_amd", "build", "libwah_hip_diag.so")  # make -C gpu-wah_amd diag
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
@@ -34,7 +34,7 @@ for kind in sys.argv[1:] or ["sparse"]:
     dec.status()
     dec.run(stream)
     dec.status()
-    batch = 1 if os.environ.get("WAH_DT_BATCH") == "1" else 2
+    batch = 2  # tiles per workgroup (launch_decode_tiles)
     n_tiles = (stream.numel() + 8192 * batch - 1) // (8192 * batch)  # workgroups
     t = dec.out[: n_tiles * 32].view(torch.int64).cpu().numpy().reshape(n_tiles, 16)
     # (the stamps lie where the first workgroups' output goes: rows that were written over afterwards are dropped)

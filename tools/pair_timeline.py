@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time line of compress_pair_kernel (DIAGNOSTIC build, WAH_TUNE=78): per tile, when it started, had its first pair's
+"""Time line of compress_pair_kernel (DIAGNOSTIC build, make -C gpu-wah_amd diag; WAH_TUNE=78): per tile, when it started, had its first pair's
 words in registers, finished pass 1, published, finished pass 2, knew its offset (s_memrealtime, 100 MHz); tiles in
 flight over time.  usage: python tools/pair_timeline.py [sparse|clustered|dense ...]"""
 import importlib
@@ -8,7 +8,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-os.environ["WAH_LIB_PATH"] = os.path.join(ROOT, "gpu-wah_amd", "libwah_hip_diag.so")
+os.environ["WAH_LIB_PATH"] = os.path.join(ROOT, "gpu-wah_amd", "build", "libwah_hip_diag.so")
 os.environ["WAH_TUNE"] = "78"
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
@@ -26,9 +26,21 @@ def wall_clock_khz():
     return v.value if rc == 0 else 0
 
 
+def tile_count(n_words):
+    """Tiles of the launch, by the rule of compress_tile_shape() (wah_compress.hip): whole rounds of the chip's workgroup slots
+    (two per CU) in body tiles of three pairs per wave, the rest in the smallest shape that fits it into one more round."""
+    pairs = ((32 * n_words + 30) // 31 + 2047) // 2048
+    slots, w = 2 * torch.cuda.get_device_properties(0).multi_processor_count, 8
+    rounds, rest = divmod(pairs, slots * w * 3)
+    if rounds == 0 or rest == 0:
+        p = 3 if rounds else (1 if pairs <= 1400 else 2 if pairs <= 3000 else 3)
+        return -(-pairs // (w * p))
+    tail = 1 if rest <= slots * w else 2 if rest <= slots * w * 2 else 3
+    return rounds * slots + -(-rest // (w * tail))
+
+
 khz = wall_clock_khz() or 100000
 print(f"wall clock rate: {khz} kHz")
-tile_segs = 16 * int(os.environ.get("WAH_WAVE_PAIRS", "3"))
 for kind in sys.argv[1:] or ["sparse"]:
     d = {"sparse": lambda: wah.gen_uniform_device(n, 1337, 0.01), "dense": lambda: wah.gen_uniform_device(n, 1337, 0.5),
          "clustered": lambda: wah.gen_clustered_device(n, 1337)}[kind]()
@@ -42,7 +54,7 @@ for kind in sys.argv[1:] or ["sparse"]:
     ev[1].record()
     comp.status()
     print(f"--- {kind}: the stamped launch between two events on its stream: {ev[0].elapsed_time(ev[1]) * 1e3:.1f} us")
-    n_tiles = int(os.environ.get("N_TILES", "0")) or (270600 + tile_segs - 1) // tile_segs
+    n_tiles = int(os.environ.get("N_TILES", "0")) or tile_count(n)
     cap = comp.capacity
     # 8 x u64 per tile at the END of the output buffer, the last tile's first (wah_compress_pair.inc)
     t = comp.out[: cap].view(torch.int64)[(cap // 2) - 8 * n_tiles: cap // 2].cpu().numpy().reshape(n_tiles, 8)[::-1].astype(np.int64)
