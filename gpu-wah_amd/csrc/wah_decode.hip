@@ -241,7 +241,10 @@ __device__ __forceinline__ bool dt_defer_many(u64 *c, u64 *list, u32 capacity, u
 #pragma unroll
     for (u32 i = 0; i < kMany; ++i)
         if ((valid >> i) & 1u) {
-            list[2ull * slot] = tile[i] | ((u64)(parts[i] | (buckets ? kDeferBuckets : 0u)) << 32);
+            // (expand_tile scans the 64 bucket sums in 32 bits: buckets without a count above 2^25 hold up to 2^31 groups each,
+            //  2^37 together -- so only a tile of fewer than 2^31 groups, the bound of expand_segment_tame, is offered them)
+            const bool with_buckets = buckets && groups[i] < (1ull << 31);
+            list[2ull * slot] = tile[i] | ((u64)(parts[i] | (with_buckets ? kDeferBuckets : 0u)) << 32);
             list[2ull * slot + 1] = before;
             ++slot;
             before += parts[i];
@@ -784,12 +787,13 @@ __device__ __forceinline__ void expand_segment_tame(const ExpandArgs &a, u32 *s_
 // group of four -- and with `buckets` (the tile's 64 sums of group counts per 64 words, left by decode_tile_kernel) the workgroup stages
 // only the words those segments need instead of the whole tile: a tile of a highly compressed stream is shared by eight or
 // more work items, each of which used to read all 16 KiB of it and count them (a quarter of the item's life, 1.13 x the
-// algorithmic traffic on the clustered GiB).
+// algorithmic traffic on the clustered GiB).  The buckets' scan is 32-bit: the list carries them for tiles of fewer than 2^31
+// groups only (dt_defer_many); a bucket holding a count above 2^25 marks the tile to be staged whole (kBucketSaturated).
 template <bool kContiguous>
 __device__ __forceinline__ void expand_tile(const ExpandArgs &a, u32 tile, u32 part, u32 parts, const u32 *buckets) {
     __shared__ __attribute__((aligned(16))) u32 s_words[kTileLdsWords];
     __shared__ u64 s_coarse[kCoarse + 1]; // groups in front of word 64 c, relative to the tile start
-    __shared__ u32 s_coarse32[kCoarse + 1]; // the same in 32 bits (valid when the tile total is below 2^31)
+    __shared__ u32 s_coarse32[kCoarse + 1]; // the same in 32 bits (read only when the tile total is below 2^31: tame, buckets)
     __shared__ u64 s_wave_sum[kExpandWaves];
     // (the list's launch: 2 KB per wave -- the image of half a segment for expand_segment_tame's scatter)
     __shared__ __attribute__((aligned(16))) unsigned char s_flag[kExpandWaves][(WAH_EXPAND_SCATTER || (WAH_LIST_SCATTER && kContiguous)) ? 2048u : kFlagBytes]; // 1: a word starts at this group
@@ -837,7 +841,7 @@ __device__ __forceinline__ void expand_tile(const ExpandArgs &a, u32 tile, u32 p
     }
     if (partial) {
         const u64 base_p = base_ahead;
-        const u32 total_p = uniform32(s_coarse32[kCoarse]); // (< 2^31: no bucket is saturated)
+        const u32 total_p = uniform32(s_coarse32[kCoarse]); // (< 2^31: dt_defer_many offers buckets to such tiles only)
         const u64 kb = (base_p + kSegGroups - 1) / kSegGroups;
         const u64 ke = (base_p + total_p + kSegGroups - 1) / kSegGroups;
         const u64 per = (ke - kb + parts - 1) / parts; // the tile's segments in `parts` EQUAL shares (see below)

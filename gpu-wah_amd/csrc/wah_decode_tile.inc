@@ -307,7 +307,8 @@ __global__ __launch_bounds__(kDtWaves * 64, (kP <= 2 ? WAH_DT_MINW : 4)) void de
         // ---- a tile that goes onto the list: its group counts summed per 64 words, for the work items that will expand it (each
         //      stages only the words of its own 32 segments then: expand_tile).  The tile's words are in the image (load layout:
         //      a lane's four words of a piece, sixteen lanes = a bucket of 64 words: one DPP row sum); counts above 2^25 -- 64 of
-        //      them would not fit 32 bits -- mark the bucket instead, and the tile is staged whole.
+        //      them would not fit 32 bits -- mark the bucket instead, and the tile is staged whole.  (64 unmarked buckets still
+        //      hold up to 2^37 groups: the list offers the sums only for tiles of fewer than 2^31, dt_defer_many.)
         if (deferred[j]) {
             const u64 n_et = (a.c_words + kScanTileWords - 1) / kScanTileWords;
             const u64 et = 2ull * ((u64)wt * kP + j) + (wave >> 2);

@@ -174,7 +174,7 @@ struct ExpandArgs {
     uint32_t n_tile_wgs;        // workgroups in front of them: tiles x parts (set by the launcher)
     const uint32_t *tile_buckets; // per expand tile 64 sums of group counts, one per 64 words (kBucketSaturated: no sum), written by
                                   // decode_tile_kernel for the tiles it puts on the list with kDeferBuckets: a work item of the list's
-                                  // launch then stages only the words its segments need
+                                  // launch then stages only the words its segments need (tiles of fewer than 2^31 groups)
 };
 
 // wah_decompress_segments_device: decode a range of segments through the index of wah_compress_device_indexed

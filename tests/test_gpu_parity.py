@@ -293,7 +293,8 @@ def test_decode_tile_boundaries_and_odd_streams(wah, oracle):
             want = oracle.decompress(comp)
             got = _host(wah.decompress_device(_dev(comp), len(want)))
             assert np.array_equal(got, want), (n, p)
-    # foreign streams: count 0, giant fills (tile totals >= 2^31), fills straddling segments, unmerged fills
+    # foreign streams: count 0, long fills (tile totals of up to a few million groups; tiles of 2^31 groups and more:
+    # tests/test_gpu_wide_streams.py), fills straddling segments, unmerged fills
     streams = [
         np.array([0x80000000 | 5000, 0x12345, 0xC0000000 | 3000, 0x80000001, 0x7FFFFFFE], np.uint32),
         np.array([0x80000000, 0xC0000000, 7, 0x80000000 | 40, 0xC0000000, 9], np.uint32),
