@@ -123,9 +123,9 @@ __device__ __forceinline__ u32 pair_pass1(const LaneGroups &g, u32 lane, u32 nev
 // from this lane's group 0 back to the last run end of the lanes below, minus one: length of a fill that ends at group k
 // of this lane = k + nl.  The last group of a segment always ends a run, so a lane of the pair's second segment never
 // looks back beyond its segment's start.
-//   variant kPass2Plain / kPass2Skip (few words: steps without a run end are branched over) / kPass2Swizzled (the words
-//           land in the piece layout of store_literals; park_pair reads with the swizzled lane number)
-enum : int { kPass2Plain = 0, kPass2Skip = 1, kPass2Swizzled = 2 };
+//   variant kPass2Skip (few words: steps without a run end are branched over) / kPass2Swizzled (the words land in the
+//           piece layout of store_literals; park_pair reads with the swizzled lane number)
+enum : int { kPass2Skip = 1, kPass2Swizzled = 2 };
 __device__ __forceinline__ void pair_pass2(const LaneGroups &g, u32 f, u32 rank0, u32 lane, u32 *lds, int variant) {
     // 1 + pair position of my last run end (0: none), its prefix maximum over the lanes, and that of the lanes BELOW me
     const u32 p1 = f ? kLaneGroups * lane + 32u - (u32)__builtin_ctz(f) : 0u;
@@ -165,7 +165,7 @@ __device__ __forceinline__ void pair_pass2(const LaneGroups &g, u32 f, u32 rank0
             : WAH_PP2_OUT
             : WAH_PP2_IN(24)
             : "vcc", "scc", "memory");
-    } else if (variant == kPass2Swizzled) {
+    } else {
         asm volatile(
 #include "pair_pass2_swz_0.inc"
             : WAH_PP2_OUT
@@ -185,27 +185,6 @@ __device__ __forceinline__ void pair_pass2(const LaneGroups &g, u32 f, u32 rank0
 #include "pair_pass2_swz_3.inc"
             : WAH_PP2_OUT
             : WAH_PP2_IN(24), [c70] "s"(0x70u)
-            : "vcc", "scc", "memory");
-    } else {
-        asm volatile(
-#include "pair_pass2_0.inc"
-            : WAH_PP2_OUT
-            : WAH_PP2_IN(0)
-            : "vcc", "scc", "memory");
-        asm volatile(
-#include "pair_pass2_1.inc"
-            : WAH_PP2_OUT
-            : WAH_PP2_IN(8)
-            : "vcc", "scc", "memory");
-        asm volatile(
-#include "pair_pass2_2.inc"
-            : WAH_PP2_OUT
-            : WAH_PP2_IN(16)
-            : "vcc", "scc", "memory");
-        asm volatile(
-#include "pair_pass2_3.inc"
-            : WAH_PP2_OUT
-            : WAH_PP2_IN(24)
             : "vcc", "scc", "memory");
     }
 #undef WAH_PP2_OUT
@@ -257,6 +236,10 @@ constexpr u32 kPairSparseBelow = 384; // words per pair below which pass 2 takes
 // the SAME number of words: at p = 1/8 (C/N = 1.032: four in ten pairs are literals but for a word or two, so 32 lanes store
 // to one bank 32 times over) the 992 MiB bitmap of the report sweep took 0.613 ms against 0.39 ms at p = 1/4 and p = 1/16.
 constexpr u32 kPairSwizzleFrom = WAH_PAIR_SWIZZLE_FROM;
+// (The two thresholds were separate knobs while pass 2 had a third variant -- plain layout, no skipping -- for the pairs in
+//  between; the A/B builds with -DWAH_PAIR_SWIZZLE_FROM=1984 / 4096 behind profiles/r03_pass2_swizzle_ab.txt used it.  The variant
+//  is gone, those builds are retired, and the two have to move together.)
+static_assert(kPairSparseBelow == kPairSwizzleFrom, "pass 2 has no variant for the pairs in between (plain layout, no skipping)");
 
 // ... and from the registers to their place in the output (kernels.cu:256 + moveData, kernels.cu:273-280): dense 1 KiB
 // stores through a descriptor that ends with the pair's words (and with the output's capacity: what lies behind is dropped)
@@ -373,7 +356,7 @@ __device__ __forceinline__ void compress_pair_body(const CompressArgs &a, const 
             store_literals(grp[j], lane, stage);
         else
             pair_pass2(grp[j], flags[j], rank0[j], lane, stage,
-                       cnt[j] < kPairSparseBelow ? kPass2Skip : cnt[j] >= kPairSwizzleFrom ? kPass2Swizzled : kPass2Plain);
+                       cnt[j] < kPairSparseBelow ? kPass2Skip : kPass2Swizzled);
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         const u32 read_lane = literals || cnt[j] >= kPairSwizzleFrom ? lane ^ ((lane >> 3) & 7u) : lane;
         if (j + 1 < kWavePairs) {

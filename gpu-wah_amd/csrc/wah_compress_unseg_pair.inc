@@ -137,7 +137,7 @@ __device__ __forceinline__ void compress_unseg_pair_body(const CompressArgs &a, 
             store_literals(grp[j], lane, stage);
         else
             pair_pass2(grp[j], flags[j], rank0[j], lane, stage,
-                       cnt[j] < kPairSparseBelow ? kPass2Skip : cnt[j] >= kPairSwizzleFrom ? kPass2Swizzled : kPass2Plain);
+                       cnt[j] < kPairSparseBelow ? kPass2Skip : kPass2Swizzled);
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         const u32 read_lane = literals || cnt[j] >= kPairSwizzleFrom ? lane ^ ((lane >> 3) & 7u) : lane;
         if (j + 1 < kWavePairs) {

@@ -125,8 +125,10 @@ size_t wah_decompress_workspace_bytes(uint64_t c_words, uint64_t out_capacity_wo
  * needs no initialisation.)  Asynchronous on `stream`. */
 int wah_workspace_init_device(void *d_workspace, size_t workspace_bytes, void *stream);
 
-/* d_in: n_words words, 16-byte aligned.  d_out: room for out_capacity_words
- * (wah_max_compressed_words(n) always suffices).  d_out_words: one device
+/* d_in: n_words words, 16-byte aligned (a pointer that is only 4-byte aligned is accepted and takes slower loads).
+ * d_out: room for out_capacity_words (wah_max_compressed_words(n) always suffices; exactly C is enough), 4-byte aligned:
+ * every store of the output goes through a descriptor that starts at a word of its own and ends with the capacity, so
+ * the output may start at any word and nothing is written in front of it or behind it.  d_out_words: one device
  * uint64 that receives C.  d_workspace: wah_compress_workspace_bytes(n_words) bytes or more, initialised as above.
  * Result status is left in the workspace; read it with wah_compress_status() after the stream has been synchronised.
  * One kernel launch, nothing else: no clearing pass, no residency requirement (the kernel's workgroups are short-lived
@@ -146,8 +148,8 @@ int wah_compress_device(const uint32_t *d_in, uint64_t n_words, uint32_t *d_out,
  * offsets with bounded in-kernel waits on workgroups that started earlier (reference: thrust::exclusive_scan between two
  * kernels, compress.cu:129-166); should such a wait ever expire the launch reports WAH_ERR_TIMEOUT, and this is the
  * route to take instead: compress() does so by itself, a caller of the device API passes the flag (or sets
- * WAH_FORCE_FALLBACK=1 in the environment, which sends every plain compress launch this way).  Not combinable with
- * WAH_UNSEGMENTED.  The route itself reads nothing of the workspace's earlier content; before the one-launch kernel is used
+ * WAH_FORCE_FALLBACK=1 in the environment, which sends every plain compress launch this way).  Combined with
+ * WAH_UNSEGMENTED: the unsegmented stream by the same three launches.  The route itself reads nothing of the workspace's earlier content; before the one-launch kernel is used
  * again after a WAH_ERR_TIMEOUT the workspace must be initialised again (wah_workspace_init_device). */
 #define WAH_NO_WAIT 2u
 int wah_compress_device_ex(const uint32_t *d_in, uint64_t n_words, uint32_t *d_out, uint64_t out_capacity_words,
@@ -192,8 +194,9 @@ typedef struct {
 } wah_column_shard;
 int wah_compress_columns_multi_device(int n_shards, const wah_column_shard *shards, uint64_t n_words_per_column, int *status);
 
-/* d_comp: c_words compressed words, 16-byte aligned.  d_out: room for
- * out_capacity_words decoded words.  d_out_info: two device uint64:
+/* d_comp: c_words compressed words, 16-byte aligned (4-byte aligned is accepted: see below).  d_out: room for
+ * out_capacity_words decoded words, 4-byte aligned (as for wah_compress_device; the same for the d_out of
+ * wah_decompress_device_ex, wah_decompress_expand_device and wah_decompress_segments_device).  d_out_info: two device uint64:
  * [0] = ceil(31*G/32) decoded words, [1] = G groups.
  * Two decoders, the same words out of both.  ONE PASS over the stream (decode_tile_kernel): it decides tile by tile
  * (8192 words), from the tile's own words, whether the workgroup that holds the tile expands it (up to about 7 groups

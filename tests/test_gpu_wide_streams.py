@@ -43,19 +43,20 @@ def out_buffer(wah):
 
 
 class _Decoder:
-    """The stream of a case on the device (16-byte aligned, and a copy that is only 4-byte aligned), a workspace for the exact
-    capacity, the info words."""
+    """The stream of a case on the device (16-byte aligned, or `offset` words behind such a boundary; and a copy that is only
+    4-byte aligned), a workspace for the exact capacity, the info words."""
 
-    def __init__(self, wah, stream, capacity):
+    def __init__(self, wah, stream, capacity, offset=0):
         import torch
 
         self.lib = wah.lib()
         self.c = int(stream.size)
         self.cap = int(capacity)
-        self.d = _dev(stream)
+        self.d_buf = _dev(np.concatenate([np.zeros(offset, np.uint32), stream]))
+        self.d = self.d_buf[offset:]
         self.d_odd_buf = _dev(np.concatenate([np.zeros(1, np.uint32), stream]))
         self.d_odd = self.d_odd_buf[1:]
-        assert self.d.data_ptr() % 16 == 0 and self.d_odd.data_ptr() % 16 == 4
+        assert self.d.data_ptr() % 16 == 4 * offset and self.d_odd.data_ptr() % 16 == 4
         self.ws_bytes = int(self.lib.wah_decompress_workspace_bytes(self.c, self.cap))
         self.ws = torch.zeros(self.ws_bytes, dtype=torch.uint8, device="cuda")
         self.info = torch.zeros(2, dtype=torch.int64, device="cuda")
