@@ -40,6 +40,9 @@ from .api import (  # noqa: F401
     bitop_device,
     bitop_indexed_device,
     bitop_many_indexed_device,
+    bitop_list_indexed_device,
+    bitop_operand_table,
+    BitopOperand,
     merge_fills_device,
     StreamReport,
     gen_uniform_device,

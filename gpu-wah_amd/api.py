@@ -60,6 +60,9 @@ ABI_SYMBOLS = {
     "wah_bitop_indexed_device": (_int, [_int, _u64, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
     "wah_bitop_indexed_status": (_int, [_vp, _u64, _vp]),
     "wah_bitop_many_indexed_device": (_int, [_int, _u64, _int, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
+    "wah_bitop_list_scratch_bytes": (_sz, [_u64, _u64]),
+    "wah_bitop_list_indexed_device": (_int, [_int, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
+    "wah_bitop_list_status": (_int, [_vp, _u64, _u64, _vp]),
     "wah_gen_uniform_device": (_int, [_vp, _u64, _u64, _u64, _vp]),
     "wah_gen_clustered_device": (_int, [_vp, _u64, _u64, _u64, _vp]),
     "wah_copy_device": (_int, [_vp, _vp, _u64, _vp]),
@@ -465,6 +468,57 @@ def bitop_many_indexed_device(op, operands, n_words, scratch=None, out=None, out
     if not check:
         return out, count, out_offsets
     _check(lib().wah_bitop_indexed_status(scratch.data_ptr(), n, sp), "bitop_many_indexed")
+    return out[: int(count.item())], out_offsets
+
+
+class BitopOperand(ctypes.Structure):
+    """wah_bitop_operand of include/wah.h: one row of an operand table (24 bytes, no padding)."""
+    _fields_ = [("d_stream", ctypes.c_void_p), ("stream_words", ctypes.c_uint64), ("d_offsets", ctypes.c_void_p)]
+
+
+def bitop_operand_table(operands, device=None):
+    """The wah_bitop_operand array of a list of (stream, seg_offsets) pairs of any length, as an int64 device tensor of
+    shape [k, 3]: rows of (stream pointer, stream words, index pointer).  The table holds RAW POINTERS and no reference to
+    the tensors they point into: the caller keeps those alive for as long as the table is used."""
+    torch = _torch()
+    if not operands:
+        raise WahError("an operand table needs at least one operand")
+    rows = []
+    for st, offs in operands:
+        _as_words(torch, st)
+        if offs.dtype != torch.int64 or not offs.is_cuda or not offs.is_contiguous():
+            raise WahError("a segment index is a contiguous int64 CUDA tensor")
+        rows.append((st.data_ptr(), st.numel(), offs.data_ptr()))
+    return torch.tensor(rows, dtype=torch.int64, device=operands[0][0].device if device is None else device)
+
+
+def bitop_list_indexed_device(op, operands, n_words, scratch=None, out=None, out_offsets=None, check=True):
+    """compress(A op B op C ...) for ANY number of operands in one call (wah_bitop_list_indexed_device).  operands: a list of
+    (stream, seg_offsets) pairs, or a ready table (bitop_operand_table, columns.column_operand_table) -- only the device
+    reads it.  Returns as bitop_indexed_device: (stream, seg_offsets), or with check=False, which only enqueues,
+    (out, count tensor, out_offsets)."""
+    torch = _torch()
+    table = operands if isinstance(operands, torch.Tensor) else bitop_operand_table(operands)
+    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 3 or table.shape[0] < 1 or not table.is_cuda or not table.is_contiguous():
+        raise WahError("an operand table is a contiguous int64 CUDA tensor of shape [k, 3], k >= 1")
+    dev = table.device
+    n, k = int(n_words), int(table.shape[0])
+    cap = max_compressed_words(n)
+    n_seg = (cap + 1023) // 1024
+    if scratch is None:
+        scratch = torch.empty(int(lib().wah_bitop_list_scratch_bytes(n, k)), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+    if out_offsets is None:
+        out_offsets = torch.zeros(n_seg + 1, dtype=torch.int64, device=dev)
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    sp = _stream_ptr(torch)
+    _check(lib().wah_bitop_list_indexed_device(OPS[op], n, k, table.data_ptr(), out.data_ptr(), out.numel(), count.data_ptr(),
+                                               out_offsets.data_ptr(), scratch.data_ptr(), scratch.numel(), sp),
+           "wah_bitop_list_indexed_device")
+    if not check:
+        return out, count, out_offsets
+    _check(lib().wah_bitop_list_status(scratch.data_ptr(), n, k, sp), "bitop_list_indexed")
     return out[: int(count.item())], out_offsets
 
 

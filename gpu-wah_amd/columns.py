@@ -72,6 +72,47 @@ def compress_column_matrix(compressor, matrix, wait=True):
     return stream, compressor.seg_offsets[:: segs][: columns + 1]
 
 
+def column_operand_table(stream, seg_offsets, n_words_per_column, column_ids, out=None):
+    """The operand table (include/wah.h: wah_bitop_operand; api.bitop_operand_table) that selects columns of a
+    compress_column_matrix result by their numbers, built ON THE DEVICE: `stream` is the whole matrix stream, `seg_offsets`
+    the compressor's whole index (DeviceCompressor.seg_offsets, not the per-column slice), and column c is the window
+    whose index starts at entry c * n_words_per_column / 992.  column_ids: an int64 device tensor (no host round trip: the
+    numbers are not checked against the matrix, the caller vouches for them) or a Python list.  out: an existing
+    [len(column_ids), 3] table to overwrite in place -- what a captured graph replayed with another selection needs.
+    Like every table it holds raw pointers: keep `stream` and `seg_offsets` alive."""
+    import torch
+
+    if n_words_per_column % SEGMENT_WORDS or n_words_per_column <= 0:
+        raise ValueError("columns of a column matrix are a multiple of 992 words long")
+    segs = n_words_per_column // SEGMENT_WORDS
+    if not torch.is_tensor(column_ids):
+        ids = [int(c) for c in column_ids]
+        if not ids or min(ids) < 0 or (max(ids) + 1) * segs + 1 > seg_offsets.numel():
+            raise ValueError("column numbers outside the matrix")
+        column_ids = torch.tensor(ids, dtype=torch.int64, device=stream.device)
+    if column_ids.dtype != torch.int64 or column_ids.dim() != 1 or column_ids.numel() < 1 or column_ids.device != stream.device:
+        raise ValueError("column_ids: a non-empty one-dimensional int64 tensor on the stream's device")
+    if seg_offsets.dtype != torch.int64 or not seg_offsets.is_contiguous() or seg_offsets.device != stream.device:
+        raise ValueError("seg_offsets: the compressor's contiguous int64 index")
+    if out is None:
+        out = torch.empty((column_ids.numel(), 3), dtype=torch.int64, device=stream.device)
+    elif out.dtype != torch.int64 or tuple(out.shape) != (column_ids.numel(), 3) or not out.is_contiguous() or out.device != stream.device:
+        raise ValueError("out: a contiguous int64 [len(column_ids), 3] tensor on the stream's device")
+    out[:, 0] = stream.data_ptr()
+    out[:, 1] = stream.numel()
+    out[:, 2] = column_ids * (segs * 8) + seg_offsets.data_ptr()
+    return out
+
+
+def combine_columns(wah, op, stream, seg_offsets, n_words_per_column, column_ids, **reuse):
+    """`value IN (...)` / `lo <= value <= hi` on an equality-encoded index in one call: op ("or", "and", "xor", "andnot") over
+    the selected columns of a compress_column_matrix result, any number of them (wah_bitop_list_indexed_device).  Arguments
+    as column_operand_table; reuse: scratch / out / out_offsets / check of api.bitop_list_indexed_device.  Returns
+    (stream, seg_offsets) of the result bitmap."""
+    table = column_operand_table(stream, seg_offsets, n_words_per_column, column_ids)
+    return wah.bitop_list_indexed_device(op, table, n_words_per_column, **reuse)
+
+
 def compress_column_ranges(compressor, flat, lengths, wait=True):
     """Columns of DIFFERENT lengths (each a multiple of 992 words) stored back to back in `flat`: still one launch.
     Returns (stream, column_offsets) like compress_column_matrix: column c is stream[column_offsets[c] :

@@ -32,21 +32,7 @@ namespace {
 // word (one bit in 2^11, two operands, 63 words per segment: 0.55 ms without the image, 0.15 with).
 constexpr u32 kRunsLdsWords = WAH_RUNS_LDS_WORDS;
 
-// the combination of two group values (31 bits) by the minterms of `acc op operand` (include/wah.h: WAH_OP_AND 0, OR 1, XOR 2,
-// ANDNOT 3: A and not B and not C ...): three masks, wave-uniform, made once -- no branch on the operation inside a step
-struct RunsOp {
-    u32 ab, a_nb, na_b;
-};
-__device__ __forceinline__ RunsOp runs_op(u32 op) {
-    RunsOp m;
-    m.ab = op <= 1u ? ~0u : 0u;
-    m.a_nb = op == 0u ? 0u : ~0u;
-    m.na_b = op == 1u || op == 2u ? ~0u : 0u;
-    return m;
-}
-__device__ __forceinline__ u32 runs_combine(u32 r, u32 v, const RunsOp &m) {
-    return ((r & v & m.ab) | (r & ~v & m.a_nb) | (~r & v & m.na_b)) & kOnes31;
-}
+// (RunsOp, runs_op, runs_combine: wah_device.hpp)
 
 // One segment of K operands merged by one lane, WITHOUT branches inside a step (the lanes of a wave are at different places
 // of different segments: every branch would be taken both ways).  word(j, i): word i of operand j, i in [begin[j], end[j]).

@@ -200,6 +200,23 @@ __device__ __forceinline__ u32 word_groups(u32 w) {
     return (w & kFillZero) ? (w & kCountMask) : 1u; // kernels.cu:298-304
 }
 
+// the combination of two group values (31 bits) by the minterms of `acc op operand` (include/wah.h: WAH_OP_AND 0, OR 1, XOR 2,
+// ANDNOT 3: A and not B and not C ...): three masks, wave-uniform, made once -- no branch on the operation inside a step
+// (the run merge of wah_bitop_runs.hip, the operand list of wah_bitop_list.hip)
+struct RunsOp {
+    u32 ab, a_nb, na_b;
+};
+__device__ __forceinline__ RunsOp runs_op(u32 op) {
+    RunsOp m;
+    m.ab = op <= 1u ? ~0u : 0u;
+    m.a_nb = op == 0u ? 0u : ~0u;
+    m.na_b = op == 1u || op == 2u ? ~0u : 0u;
+    return m;
+}
+__device__ __forceinline__ u32 runs_combine(u32 r, u32 v, const RunsOp &m) {
+    return ((r & v & m.ab) | (r & ~v & m.a_nb) | (~r & v & m.na_b)) & kOnes31;
+}
+
 // expand / checker / merge kernels: one workgroup of four wavefronts per 4096-word tile
 constexpr int kExpandThreads = kExpandWaves * 64;                 // 256
 constexpr int kExpandWordsPerThread = kScanTileWords / kExpandThreads; // 16

@@ -211,6 +211,22 @@ struct BitopManyArgs {
     int op; // WAH_OP_*
 };
 
+// wah_bitop_list_indexed_device (wah_bitop_list.hip): any number of operands, named by a table in DEVICE memory that only
+// the kernel reads (the mirror of wah_bitop_operand, include/wah.h); g as above
+struct BitopListOperand {
+    const uint32_t *comp;
+    uint64_t c_words;
+    const uint64_t *offs;
+};
+constexpr uint64_t kMaxBitopListOperands = 1ull << 24; // WAH_BITOP_LIST_MAX_OPERANDS
+struct BitopListArgs {
+    SegmentsArgs g;
+    const BitopListOperand *table;
+    uint32_t n;  // operands
+    uint32_t op; // WAH_OP_*
+};
+hipError_t launch_bitop_list_segments(const BitopListArgs &a, hipStream_t s);
+
 // ... on operands of few words per segment: their runs merged in the compressed domain, one lane per segment
 // (wah_bitop_runs.hip): count pass, scan of the tile totals, write pass
 struct BitopRunsArgs {

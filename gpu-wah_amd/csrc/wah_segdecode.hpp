@@ -110,6 +110,32 @@ __device__ __forceinline__ u32 seg_group(int s, const u32 (&f)[4], u32 &before, 
     return grp;
 }
 
+// wavefronts of a workgroup of the kernels that give every wavefront one segment (decode_segments_kernel,
+// bitop_many_segments_kernel, bitop_list_segments_kernel)
+#ifndef WAH_SEG_WAVES
+#define WAH_SEG_WAVES 4
+#endif
+constexpr int kSegDecodeWaves = WAH_SEG_WAVES;
+
+// where the 992 words of segment first_segment + k go, and the lane constants of the 31 -> 32 repack
+struct SegStore {
+    __amdgpu_buffer_rsrc_t rsrc;
+    u32 o, up, soff;
+};
+__device__ __forceinline__ SegStore seg_store_setup(u32 *out, u64 out_words, u64 seg, u64 k, u32 lane) {
+    SegStore st;
+    const u64 seg_w0 = seg * kSegWords;
+    const u32 seg_words = out_words > seg_w0 ? (u32)(out_words - seg_w0 < kSegWords ? out_words - seg_w0 : kSegWords) : 0u;
+    st.rsrc = make_rsrc(out + k * kSegWords, seg_words * 4u); // stores past the end are dropped
+    st.o = lane & 31u;
+    st.up = 31u - ((lane - 1u) & 31u);
+    st.soff = st.o != 31u ? (lane - (lane >> 5)) * 4u : 0xFFFFF000u; // lanes 31, 63 only lend their group
+    return st;
+}
+__device__ __forceinline__ void seg_store(const SegStore &st, int s, u32 grp) {
+    const u32 hi_part = (u32)__builtin_amdgcn_mov_dpp((int)(grp << st.up), 0x130 /* wave_shl:1 */, 0xf, 0xf, true);
+    __builtin_amdgcn_raw_buffer_store_b32((grp >> st.o) | hi_part, st.rsrc, st.soff + 248u * s, 0, 0);
+}
 
 } // namespace
 } // namespace wah

@@ -362,6 +362,43 @@ int wah_bitop_many_indexed_device(int op, uint64_t n_words, int n_operands, cons
                                   uint64_t out_capacity_words, uint64_t *d_out_words, uint64_t *d_out_offsets, void *d_scratch,
                                   size_t scratch_bytes, void *stream);
 
+/* The same for ANY number of operands, named by a table in DEVICE memory: the query an equality-encoded bitmap index
+ * exists for -- `value IN (...)`, `lo <= value <= hi` are the OR of as many bitmaps as the list or the range has bins.
+ * Semantics as above, word for word: left to right, A op B op C ... (WAH_OP_ANDNOT: A and not B and not C ...); the result
+ * is what compress() emits for the combined bitmap of n_words words (ragged ends included; n_words == 0: an empty stream);
+ * d_out_offsets (may be NULL) receives the result's own segment index, so results chain into every indexed call.
+ *   d_operands: n_operands entries, 8-byte aligned, 1 <= n_operands <= WAH_BITOP_LIST_MAX_OPERANDS.  An operand may appear
+ *   more than once (OR is idempotent, XOR cancels).  An entry may be a WINDOW into a longer stream, which is what a column
+ *   of a column matrix is (wah_compress_columns_multi_device, one launch over back-to-back columns): d_offsets then
+ *   points into the matrix index at the column's first segment, its entries count from the start of the whole stream, and
+ *   stream_words is the whole stream's length -- which is why an entry carries pointers, not a column number.
+ * The library never reads the table on the host: the call is asynchronous on `stream`, allocates nothing, never
+ * synchronises, and a captured graph replayed after the table was overwritten in place combines the NEW selection.  For
+ * the same reason there is one route whatever the operands hold (their lengths are only bounds, known to the device): one
+ * wavefront per segment applies every operand's words to the segment's 1024 groups where they lie -- a fill that is the
+ * operation's identity costs its load only, so the cost goes with the operands' words plus the fills that change the
+ * result, not with n_operands x n_words -- and the compress passes run over the one decoded bitmap that leaves.
+ *   d_scratch: wah_bitop_list_scratch_bytes(n_words, n_operands) bytes, 256-byte aligned, no initialisation; it EQUALS
+ *   wah_bitop_indexed_scratch_bytes(n_words) for every n_operands (nothing in it goes with the operands' number).
+ * Errors the host can see come back before any HIP call: a bad op, n_operands out of range, a null or misaligned scratch or
+ * table, null outputs, n_words >= 2^40: WAH_ERR_ARG; too small a scratch: WAH_ERR_WORKSPACE.  Everything only the device
+ * sees is reported by wah_bitop_list_status(), which synchronises the stream: WAH_ERR_STREAM for an entry with a null or
+ * misaligned index or stream or a length of 2^40 or more, an index range that is not inside stream_words, a segment whose
+ * words do not make up exactly its groups, an empty fill; WAH_ERR_CAPACITY for too small an output (nothing is written behind
+ * out_capacity_words).  An entry is checked before a pointer of it is followed, an index range before the stream is read
+ * through it, and EVERY operand's every segment is checked: nothing stops early, so the verdict does not depend on the data. */
+typedef struct {
+    const uint32_t *d_stream;  /* the operand's words, 4-byte aligned                         */
+    uint64_t stream_words;     /* its length, or a capacity that bounds it                    */
+    const uint64_t *d_offsets; /* its segment index: n_segments + 1 entries, into d_stream    */
+} wah_bitop_operand;           /* 24 bytes, no padding */
+#define WAH_BITOP_LIST_MAX_OPERANDS (1u << 24)
+size_t wah_bitop_list_scratch_bytes(uint64_t n_words, uint64_t n_operands);
+int wah_bitop_list_indexed_device(int op, uint64_t n_words, uint64_t n_operands, const wah_bitop_operand *d_operands,
+                                  uint32_t *d_out, uint64_t out_capacity_words, uint64_t *d_out_words, uint64_t *d_out_offsets,
+                                  void *d_scratch, size_t scratch_bytes, void *stream);
+int wah_bitop_list_status(void *d_scratch, uint64_t n_words, uint64_t n_operands, void *stream);
+
 /* ------------------------------------------------------------------------- *
  * Benchmark support: synthetic bitmaps generated in HBM (include/wah_gen.h
  * states the bit-exact definition; replaces tests.cpp:42-64), and a plain
