@@ -27,12 +27,41 @@ The switches (gpu-wah_amd/csrc) and the probes that sit on them:
   more than 1024 tiles                     bitop_runs_scan_kernel (per >= 2),     MANY_TILES_*; a stream of > 1024 x 4096 words
                                            sums_offsets_kernel, wah_decode.hip
 
+The operand-list bit operation (wah_bitop_list.hip; list_paths() restates which way every batch and word of a segment goes):
+
+  64 operands per chunk, one per lane      list_gather, j0 += 64, list_advance's  LIST_OPERAND_COUNTS, LIST_POSITIONS (a live operand in
+    (row 0 alone takes m_first)              c.j >= 63u, j0 + cons.j == 0u          rows 0, 1, 62 .. 65, 128; row 0 again in 64, 128)
+  128 words per batch                      list_advance, list_issue,              LIST_SEGMENT_WORDS (128 b - 1, 128 b, 128 b + 1) x
+                                             list_apply_batch                       LIST_WAYS
+  kListDepth = 4 batches in flight         the producer / consumer rotation       LIST_SCHEDULES (0, 1, 3, 4, 5, 8 and more batches a
+                                                                                    chunk; list_chunk_rotation)
+  a full batch of literals                 list_apply_batch's fast path           LIST_WAYS ("fill ends a batch", "fill starts the next
+                                                                                    batch", "fill first": a fast batch that ends AT 1024)
+  kListShortFill = 8; 64 groups a step     s0 / s1, list_put_rest, list_put_long  LIST_FILL_GROUPS x LIST_FILL_WORD_INDEX
+  identity or effect                       list_op, eff0 / eff1, the settled test both kinds of fill under all of LIST_OPS
+  one-word segment settled                 list_gather                            list_fill_probes (one word), list_ragged_layouts
+  kSegDecodeWaves = 4 segments a           wah_segdecode.hpp, the grid            LIST_SEGMENTS
+    workgroup
+  counts clamped to 2 x 1024               list_apply_batch                       LIST_BAD_COUNTS (refused: tests/test_gpu_switch_points.py)
+
 THRESHOLDS restates the constants; tests/test_switch_reference.py reads them out of the sources and fails when they differ,
 naming the probe list that has to move with them.
 
 Found while reading, not reachable: launch_runs_k gives bitop_runs_kernel NO image (lds_words == 0) when an average tile
 exceeds WAH_RUNS_LDS_WORDS; launch_bitop_runs picks the tile shape so that an average tile fits with a tenth to spare, and 64
 segments of at most 112 words always do, so that branch is never taken.
+
+Of the list kernel, by list_paths(): in list_apply_batch's fast-path test `pos + 128 <= 1024` is never false for a FULL batch
+of literals of a valid segment (128 literals are 128 groups of at most 1024), and list_gather's `only >= kFillZero` is never
+false for a valid one-word segment (a segment never has exactly one group).  Both are false only for streams that are
+refused; tests/test_gpu_switch_points.py holds one refusal for each (a batch of literals behind 897 groups, a lone literal).
+Two comparisons of the list kernel can be moved without any change of what it computes, so no probe can sit on them:
+list_advance's `128 (b + 1) < cnt` as `<=` gives an operand of 128 b words one more batch, which holds no word (its descriptor
+ends in front of it, every lane is outside cnt): the same groups, the same total, the same verdict; and the fast path's
+`wi + 128 <= cnt` as `<` sends an operand's last full batch of literals through the general code, which puts the same 128
+literals at the same 128 groups (the fast path is that code without the scan).  Libraries built with either change pass
+every test of tests/test_gpu_switch_points.py and tests/test_gpu_bitop_list.py; "fill first" segments of 128 b words and the
+LIST_SEGMENT_WORDS of 128 b are the inputs on which the two versions run different code.
 
 Pass 2 had a third variant, kPass2Plain (pair_pass2_0..3.inc), for the pairs between kPairSparseBelow and kPairSwizzleFrom.
 Both are 384, no pair reached it, and it is gone: a static_assert in wah_compress_pair.inc and
@@ -74,6 +103,12 @@ THRESHOLDS = {
     "runs image": ((3, 2, 1024, 255), "runs_lds_image_words / lds_boundary_tile_words"),
     "runs scan threads": (1024, "SCAN_ROUND_TILES / MANY_TILES_64, MANY_TILES_256"),
     "sums offsets threads": (1024, "SCAN_ROUND_TILES (test_no_wait_decoder_beyond_one_scan_round)"),
+    "kListShortFill": (8, "LIST_FILL_GROUPS"),
+    "WAH_LIST_DEPTH": (4, "LIST_SCHEDULES"),
+    "list batch words": (128, "LIST_SEGMENT_WORDS / LIST_FILL_WORD_INDEX / LIST_SCHEDULES"),
+    "list chunk operands": (64, "LIST_OPERAND_COUNTS / LIST_POSITIONS"),
+    "WAH_SEG_WAVES": (4, "LIST_SEGMENTS"),
+    "list count clamp factor": (2, "LIST_BAD_COUNTS"),
 }
 PAIR_SWITCH = THRESHOLDS["kPairSparseBelow"][0]
 DT_MAX_GROUPS = THRESHOLDS["WAH_DT_MAXG"][0] * 1024
@@ -433,3 +468,330 @@ RUNS_SHAPE_SEGMENTS = (256 * 2, 256 * 2 + 1, 256 * 2 + 63, 256 * 2 + 64, 256 * 2
 MANY_TILES_64 = 64 * 1024 + 1     # segments: 1025 tiles of 64
 MANY_TILES_256 = 256 * 1024 + 1   # segments: 1025 tiles of 256
 SCAN_ROUND_TILES = THRESHOLDS["runs scan threads"][0]           # tiles one round of the scans takes (4096-word tiles in the decoder)
+
+
+# ---- the operand-list bit operation (wah_bitop_list.hip) --------------------------------------------------------------------
+LIST_OPS = ("and", "or", "xor", "andnot")
+LIST_SHORT_FILL = THRESHOLDS["kListShortFill"][0]
+LIST_DEPTH = THRESHOLDS["WAH_LIST_DEPTH"][0]
+LIST_BATCH = THRESHOLDS["list batch words"][0]
+LIST_CHUNK = THRESHOLDS["list chunk operands"][0]
+SEG_WAVES = THRESHOLDS["WAH_SEG_WAVES"][0]
+LIST_CLAMP = THRESHOLDS["list count clamp factor"][0] * SEG_GROUPS
+COUNT_MASK = 0x3FFFFFFF
+
+# groups of a fill: by its own lane up to 8 (1 group: the first store only), by the whole wave 64 a step beyond
+LIST_FILL_GROUPS = (1, 2, 3, LIST_SHORT_FILL - 1, LIST_SHORT_FILL, LIST_SHORT_FILL + 1, 63, 64, 65, 127, 128, 129, 700)
+# the word that holds it: lane 0's first, its second, lane 63's first and second, the same of the second batch, the third's first
+LIST_FILL_WORD_INDEX = (0, 1, LIST_BATCH - 2, LIST_BATCH - 1, LIST_BATCH, LIST_BATCH + 1, 2 * LIST_BATCH - 1, 2 * LIST_BATCH)
+LIST_SEGMENT_WORDS = tuple(sorted({1, 2, SEG_GROUPS - 1, SEG_GROUPS} | {LIST_BATCH * b + d for b in range(1, 8) for d in (-1, 0, 1)}))
+LIST_WAYS = ("literals + fill", "fill ends a batch", "fill starts the next batch", "fill first")
+LIST_OPERAND_COUNTS = (1, 2, LIST_CHUNK - 1, LIST_CHUNK, LIST_CHUNK + 1, 2 * LIST_CHUNK - 1, 2 * LIST_CHUNK, 2 * LIST_CHUNK + 1, 4097)
+LIST_POSITIONS = (0, 1, LIST_CHUNK - 2, LIST_CHUNK - 1, LIST_CHUNK, LIST_CHUNK + 1, 2 * LIST_CHUNK)  # table rows of a non-trivial operand
+LIST_SEGMENTS = (1, SEG_WAVES - 1, SEG_WAVES, SEG_WAVES + 1)
+LIST_BAD_COUNTS = (LIST_CLAMP - 1, LIST_CLAMP, LIST_CLAMP + 1, COUNT_MASK)
+# words per segment of the operands of ONE chunk (1: a single fill word, settled where it is the operation's identity)
+LIST_SCHEDULES = ((5,), (257,), (1024,), (128, 128, 128, 128), (128, 128, 128, 128, 1), (128, 128, 128, 128, 2), (129, 1, 257, 128, 1024),
+                  (300, 1, 1, 129, 1, 513, 1, 1, 1, 2), (1,) * 64, (1,) * 64 + (129, 1, 640), (1024, 1024, 1024))
+
+
+def list_groups(layout, rng):
+    """The groups of a segment from runs (kind, n): "lit" n random literals, "ones" / "zeros" n groups of a fill."""
+    parts = []
+    for kind, n in layout:
+        assert n >= 1 and kind in ("lit", "ones", "zeros"), (kind, n)
+        parts.append(literals(rng, n) if kind == "lit" else np.full(n, M31 if kind == "ones" else 0, np.uint32))
+    return np.concatenate(parts)
+
+
+def list_layout_words(layout):
+    """What the layout compresses to: 0 per literal, the fill word per maximal run of one kind of fill."""
+    out = []
+    last = None
+    for kind, n in layout:
+        if kind == "lit":
+            out.extend([0] * n)
+        elif kind == last:
+            out[-1] += n
+        else:
+            out.append((FILL1 if kind == "ones" else FILL0) | n)
+        last = kind
+    return np.array(out, np.uint32)
+
+
+def list_segment(layout, rng, tail_words=None):
+    """The bitmap words of one segment: 992 words from a layout of 1024 groups; or, for the bitmap's last segment, tail_words
+    words from a layout of ceil(32 tail_words / 31) groups -- the last group then holds only the bits the bitmap has (a literal
+    keeps its lowest bit set; a fill of ones cannot end there unless the group is whole: tail_words a multiple of 31)."""
+    g = list_groups(layout, rng)
+    if tail_words is None:
+        assert g.size == SEG_GROUPS, g.size
+        return pack(g)
+    assert g.size == (32 * tail_words + 30) // 31, (g.size, tail_words)
+    bits = 32 * tail_words - 31 * (g.size - 1)  # of the last group
+    if bits < 31:
+        assert layout[-1][0] != "ones"
+        g[-1] &= (1 << bits) - 1
+        if layout[-1][0] == "lit":
+            g[-1] |= 1
+    words = pack(g)
+    assert not words[tail_words:].any()
+    return words[:tail_words]
+
+
+def list_fill_layout(word_index, fill_bit, n_groups, total_words):
+    """The layout of list_fill_at: word_index literals, the fill, literals, and one trailing fill of the other kind."""
+    fill, other = ("ones", "zeros") if fill_bit else ("zeros", "ones")
+    if total_words == word_index + 1:  # the fill is the segment's last word
+        assert n_groups == SEG_GROUPS - word_index
+        return ([("lit", word_index)] if word_index else []) + [(fill, n_groups)]
+    lits = total_words - word_index - 2
+    rest = SEG_GROUPS - word_index - n_groups - lits
+    assert lits >= 0 and rest >= 1, (word_index, n_groups, total_words)
+    return ([("lit", word_index)] if word_index else []) + [(fill, n_groups)] + ([("lit", lits)] if lits else []) + [(other, rest)]
+
+
+def list_fill_at(word_index, fill_bit, n_groups, total_words, rng):
+    """A segment of exactly total_words words whose word word_index is a fill of fill_bit of n_groups groups (it starts at
+    group word_index: only literals lie in front of it); the rest is literals, padded by a trailing fill of the other kind."""
+    return list_segment(list_fill_layout(word_index, fill_bit, n_groups, total_words), rng)
+
+
+def list_fill_probes():
+    """[(word index, fill bit, groups, words of the segment)]: LIST_FILL_WORD_INDEX x LIST_FILL_GROUPS x both kinds, with 0 to
+    139 literals behind the fill; and the one-word segments."""
+    out = []
+    for wi in LIST_FILL_WORD_INDEX:
+        for n in LIST_FILL_GROUPS:
+            lits = min((7 * wi + n) % 140, SEG_GROUPS - wi - n - 1)
+            out.extend((wi, bit, n, wi + 2 + lits) for bit in (0, 1))
+    return out + [(0, 0, SEG_GROUPS, 1), (0, 1, SEG_GROUPS, 1)]
+
+
+def list_many_fills_layouts():
+    """Segments whose batches hold MANY fills with an effect: 56 fills of 9 groups of either kind side by side (a lane's first
+    word and its second, both orders: list_put_long's mask has 56 bits), short fills in every lane (list_put_rest in all of
+    them), fills of 64 groups back to back, and long and short ones mixed in one batch."""
+    out = []
+    for a, b in (("ones", "zeros"), ("zeros", "ones")):
+        out.append([(a, LIST_SHORT_FILL + 1), (b, LIST_SHORT_FILL + 1)] * 56 + [("lit", 16)])
+        out.append([(a, 2), ("lit", 1), (b, 3), ("lit", 2)] * 128)  # (five words: either kind in first and in second words)
+        out.append([(a, 64), (b, 64)] * 8)
+        out.append([("lit", 1), (a, 17), (b, LIST_SHORT_FILL), ("lit", 2), (b, 1), (a, LIST_SHORT_FILL)] * 27 + [(b, 25)])
+    assert all(sum(n for _, n in layout) == SEG_GROUPS for layout in out)
+    return out
+
+
+def list_words_layout(words, way, fill_bit):
+    """A layout of exactly `words` words (None: this way cannot give that count)."""
+    fill, other = ("ones", "zeros") if fill_bit else ("zeros", "ones")
+    lit = lambda n: [("lit", n)] if n else []  # noqa: E731
+    if way == "literals + fill":  # literals only where 1024
+        return lit(SEG_GROUPS) if words == SEG_GROUPS else lit(words - 1) + [(fill, SEG_GROUPS - words + 1)]
+    if way == "fill ends a batch":  # a fill as the very last word of the last FULL batch, 127 literals in front: not the fast path
+        if words < LIST_BATCH:
+            return None
+        at = LIST_BATCH * (words // LIST_BATCH) - 1
+        after = words - at - 1  # words behind the fill: literals and one fill of the other kind
+        if after == 0:
+            return lit(at) + [(fill, SEG_GROUPS - at)]
+        room = SEG_GROUPS - words + 2  # groups of the two fills together
+        mine = min(3, room - 1)
+        return lit(at) + [(fill, mine)] + lit(after - 1) + [(other, room - mine)]
+    if way == "fill starts the next batch":  # full batches of literals (the fast path), then a batch whose FIRST word is a fill
+        full = LIST_BATCH * ((words - 1) // LIST_BATCH)
+        if full == 0:
+            return None
+        return lit(full) + [(fill, SEG_GROUPS - words + 1)] + lit(words - full - 1)
+    assert way == "fill first", way  # where words is a multiple of 128 the last batch is full, literals, and ENDS at group 1024
+    return [(fill, SEG_GROUPS - words + 1)] + lit(words - 1) if words > 1 else None
+
+
+def list_words_probes():
+    """[(words, way, fill bit, layout)]: every LIST_SEGMENT_WORDS by every way that can give it, the fill kinds in turn."""
+    out = []
+    for words in LIST_SEGMENT_WORDS:
+        for way in LIST_WAYS:
+            bit = len(out) & 1
+            layout = list_words_layout(words, way, bit)
+            if layout is not None:
+                out.append((words, way, bit, layout))
+    return out
+
+
+def list_probe_bitmap(layouts, rng, tail=None):
+    """The segments of the layouts back to back; tail: (layout, tail_words) of a last, short segment."""
+    segs = [list_segment(layout, rng) for layout in layouts]
+    if tail is not None:
+        segs.append(list_segment(tail[0], rng, tail[1]))
+    return np.concatenate(segs)
+
+
+def list_schedule_layout(words, one_word_bit, j=0):
+    """A layout of `words` words for a schedule's operand: literals around one fill (1: the fill alone, of one_word_bit)."""
+    if words == 1:
+        return [("ones" if one_word_bit else "zeros", SEG_GROUPS)]
+    return list_words_layout(words, LIST_WAYS[j % 2 * 3], j // 2 % 2)
+
+
+def list_schedule_operands(schedule, one_word_bit, n_segments, rng):
+    """len(schedule) bitmaps of n_segments segments: operand j holds schedule[(j + s) % k] words in segment s when k <= 64 (every
+    segment sees the schedule rotated), schedule[j] in every segment beyond (the chunks stay what the schedule says)."""
+    k = len(schedule)
+    maps = []
+    for j in range(k):
+        counts = [schedule[(j + s) % k if k <= LIST_CHUNK else j] for s in range(n_segments)]
+        maps.append(list_probe_bitmap([list_schedule_layout(c, one_word_bit, j + s) for s, c in enumerate(counts)], rng))
+    return maps
+
+
+def list_schedule_counts(schedule, n_segments):
+    """[segment][operand] -> the words list_schedule_operands gives it."""
+    k = len(schedule)
+    return [[schedule[(j + s) % k if k <= LIST_CHUNK else j] for j in range(k)] for s in range(n_segments)]
+
+
+def list_ragged_layouts(tail_words):
+    """The last segment of tail_words words, three ways: one fill of zeros (the identity except under AND), the nearest to one
+    fill of ones (the identity under AND alone: one word only where the last group is whole), literals up to the last group."""
+    g = (32 * tail_words + 30) // 31
+    whole = (32 * tail_words) % 31 == 0
+    return {"zeros": [("zeros", g)], "ones": [("ones", g)] if whole else [("ones", g - 1), ("lit", 1)], "literals": [("lit", g)]}
+
+
+def list_paths(words, nvalid, op, first=False):
+    """bitop_list_segments_kernel restated for ONE operand's words of one segment of nvalid groups under operation op (first:
+    the operand is row 0 of the table): which way every batch and every word goes.  Returns a dict:
+      settled   list_gather settles it (one identity fill of exactly nvalid groups): no batch at all
+      batches   [{fast, last, pos (groups covered before it), rest (list_put_rest runs), words: [(way, groups, first group)]}]
+                way: "literal" / "identity" / "own first" (an effect fill of 1 group) / "own rest" (2 .. 8) / "wave" (9 and more)
+                / "outside" (it would end behind group 1024: nothing is put) / "empty"; a fast batch lists 128 x "fast"
+      ok        the verdict: no empty word and exactly nvalid groups at the last batch"""
+    words = np.asarray(words, np.uint32)
+    cnt = int(words.size)
+    assert op in LIST_OPS and 1 <= cnt <= nvalid <= SEG_GROUPS  # (list_gather refuses any other range)
+    rest_effect = FILL0 if op == "and" else FILL1               # m_rest.fill: what the settled test looks at
+    only = int(words[0])
+    if cnt == 1 and only >= FILL0 and (only & COUNT_MASK) == nvalid and (only & FILL1) != rest_effect:
+        return {"settled": True, "batches": [], "ok": True}
+    applied = "or" if first and op == "andnot" else op          # m_first
+    effect = FILL0 if applied == "and" else FILL1
+    pos, empty, batches = 0, False, []
+    for wi in range(0, cnt, LIST_BATCH):
+        batch = [int(w) for w in words[wi: wi + LIST_BATCH]]
+        full = wi + LIST_BATCH <= cnt
+        info = {"last": wi + LIST_BATCH >= cnt, "pos": pos, "full": full, "rest": False}
+        if full and pos + LIST_BATCH <= SEG_GROUPS and not any(w & FILL0 for w in batch):
+            info.update(fast=True, words=[("fast", 1, pos + i) for i in range(LIST_BATCH)])
+            pos += LIST_BATCH
+        else:
+            ways = []
+            for w in batch:
+                n = min(w & COUNT_MASK, LIST_CLAMP) if w & FILL0 else 1
+                empty |= n == 0
+                if n == 0:
+                    way = "empty"
+                elif pos + n > SEG_GROUPS:
+                    way = "outside"
+                elif not w & FILL0:
+                    way = "literal"
+                elif (w & FILL1) != effect:
+                    way = "identity"
+                else:
+                    way = "own first" if n == 1 else "own rest" if n <= LIST_SHORT_FILL else "wave"
+                ways.append((way, n, pos))
+                pos += n
+            info.update(fast=False, words=ways, rest=any(way == "own rest" for way, _, _ in ways))
+        batches.append(info)
+    return {"settled": False, "batches": batches, "ok": not empty and pos == nvalid}
+
+
+def list_chunk_rotation(counts, depth=None):
+    """The producer / consumer rotation over ONE chunk's live operands (counts: their words, settled ones left out): for every
+    batch the consumer applies, how many operand boundaries lie between it and the producer's cursor (64: the producer is done)."""
+    depth = LIST_DEPTH if depth is None else depth
+    seq = [(j, b) for j, c in enumerate(counts) for b in range((c + LIST_BATCH - 1) // LIST_BATCH)]
+    return [(seq[i + depth][0] - seq[i][0]) if i + depth < len(seq) else LIST_CHUNK for i in range(len(seq))]
+
+
+def list_table_rows(n_rows, pool_size, placed=None):
+    """Row -> pool entry of a table of n_rows rows: the pool's entries 1 .. in turn (0: the trivial operand, used by `placed`
+    tables only); placed {row: entry}: every other row is entry 0."""
+    if placed is None:
+        return [1 + r % (pool_size - 1) for r in range(n_rows)]
+    assert all(0 <= r < n_rows for r in placed)
+    return [placed.get(r, 0) for r in range(n_rows)]
+
+
+def list_fold(op, pool, rows):
+    """The bitmap a table of rows (indices into pool) combines to, without stacking 4097 bitmaps: AND / OR over the distinct rows,
+    XOR over those that occur an odd number of times, ANDNOT the first row and not the OR of the others."""
+    pool = [np.asarray(p, np.uint32) for p in pool]
+    if op == "and":
+        return np.bitwise_and.reduce([pool[i] for i in sorted(set(rows))])
+    if op == "or":
+        return np.bitwise_or.reduce([pool[i] for i in sorted(set(rows))])
+    if op == "xor":
+        odd = [i for i in sorted(set(rows)) if rows.count(i) % 2]
+        return np.bitwise_xor.reduce([pool[i] for i in odd]) if odd else np.zeros_like(pool[0])
+    assert op == "andnot", op
+    rest = sorted(set(rows[1:]))
+    return pool[rows[0]] & ~np.bitwise_or.reduce([pool[i] for i in rest]) if rest else pool[rows[0]].copy()
+
+
+def list_pool(rng, n_segments=3, size=5):
+    """A small pool of bitmaps of n_segments segments for the tables of LIST_OPERAND_COUNTS / LIST_POSITIONS: entries 1 .. are
+    literals around fills of both kinds (2 to 1024 words a segment); entry 0 is left to the caller (the operation's trivial
+    operand: all zeros, or all ones under AND -- one identity fill per segment, settled)."""
+    counts = (2, LIST_BATCH + 2, SEG_GROUPS, 40, 2 * LIST_BATCH)
+    pool = [None]
+    for j in range(1, size):
+        pool.append(list_probe_bitmap([list_words_layout(counts[(j + s) % len(counts)], LIST_WAYS[(j + s) % 2 * 3], (j + s) // 2 % 2)
+                                       for s in range(n_segments)], rng))
+    return pool
+
+
+def list_trivial(op, n_words):
+    """The operand that changes nothing (and, as row 0 of ANDNOT, leaves nothing): one identity fill per whole segment."""
+    return np.full(n_words, 0xFFFFFFFF if op == "and" else 0, np.uint32)
+
+
+# tables in which only the `placed` rows are not the trivial operand: {name: (rows of the table, {row: pool entry})}
+LIST_PLACED = {f"alone in row {r}": (max(r + 1, LIST_CHUNK + 1), {r: 1}) for r in LIST_POSITIONS}
+LIST_PLACED["rows 0, 1, 63, 64 and 128"] = (2 * LIST_CHUNK + 1, {0: 1, 1: 2, LIST_CHUNK - 1: 3, LIST_CHUNK: 4, 2 * LIST_CHUNK: 2})
+LIST_PLACED["row 0 again in rows 64 and 128"] = (2 * LIST_CHUNK + 1, {0: 1, LIST_CHUNK: 1, 2 * LIST_CHUNK: 1})
+LIST_PLACED["rows 62 and 63"] = (LIST_CHUNK, {0: 3, LIST_CHUNK - 2: 1, LIST_CHUNK - 1: 2})
+
+
+def list_refusals(rng):
+    """[(name, the words of one segment of 1024 groups)]: hand-built words that must be refused.  Every one is a range of 1 to
+    1024 words (list_gather accepts it), so it is refused by what the words say -- and list_paths() says the same."""
+    def lits_with(cnt, at, word):
+        w = literals(rng, cnt)
+        w[at] = word
+        return w
+
+    out = []
+    for k, (cnt, at) in enumerate(((50, 10), (200, 150), (1000, 900))):  # the fill in batch 1, 2 and 8
+        for d in (-1, 1):
+            out.append((f"{SEG_GROUPS + d} groups, the fill in batch {at // LIST_BATCH + 1}",
+                        lits_with(cnt, at, (FILL1 if (k + d) & 2 else FILL0) | (SEG_GROUPS - (cnt - 1) + d))))
+    for k, n in enumerate(LIST_BAD_COUNTS):
+        out.append((f"one count of {n}", lits_with(40, 7, (FILL1 if k & 1 else FILL0) | n)))
+    out.append((f"{LIST_BATCH} counts of {COUNT_MASK}", np.full(LIST_BATCH, FILL1 | COUNT_MASK, np.uint32)))
+    out.append((f"a second batch of {LIST_BATCH} counts of {COUNT_MASK}",
+                np.concatenate([literals(rng, LIST_BATCH), np.full(LIST_BATCH, FILL0 | COUNT_MASK, np.uint32)])))
+    for cnt, at, kind in ((200, LIST_BATCH - 1, FILL0), (400, 300, FILL1)):  # the groups ARE 1024: only the empty word is wrong
+        w = lits_with(cnt, at, kind)
+        w[-1] = (FILL0 if kind == FILL1 else FILL1) | (SEG_GROUPS - (cnt - 2))
+        out.append((f"an empty fill in word {at}", w))
+    out.append(("a full batch of literals behind 897 groups", np.concatenate([[FILL0 | 770], literals(rng, 2 * LIST_BATCH - 1)]).astype(np.uint32)))
+    out.append(("a lone literal", literals(rng, 1)))
+    return out
+
+
+def list_refused_stream(bitmap_streams, segment, words):
+    """(stream, index) of an operand whose segments are bitmap_streams (the oracle's, one array per segment) except that
+    `segment` holds `words`: the index is the stream's own, every range inside it."""
+    segs = [np.asarray(words if s == segment else w, np.uint32) for s, w in enumerate(bitmap_streams)]
+    return np.concatenate(segs), np.concatenate([[0], np.cumsum([w.size for w in segs])]).astype(np.int64)

@@ -1,6 +1,11 @@
 """GPU tests of wah_bitop_list_indexed_device: one bit operation over an operand list of any length that lives in device
 memory (include/wah.h), and its front ends in columns.py.  Everything is exact: the result's words, their count and its segment
-index against compress() of the bitmaps combined with numpy -- the CPU oracle and an indexed compress of the combined bitmap."""
+index against compress() of the bitmaps combined with numpy -- the CPU oracle and an indexed compress of the combined bitmap.
+
+These tests use the call from outside: random and clustered bitmaps, 1 to 300 operands, refusals, graph replay -- which way a
+segment takes inside the kernel is left to the data.  The cases that sit ON its switch points (128 words a batch, four batches
+in flight, 64 operands a chunk, fills of 8 / 9 / 64 groups, the settled one-word segment, the refusals at 1023 / 1025 groups and
+at the count clamp) are built in tests/_switch.py and run by the test_list_* tests of tests/test_gpu_switch_points.py."""
 import importlib
 import os
 

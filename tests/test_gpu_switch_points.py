@@ -19,6 +19,15 @@ Which test sits on which switch:
   256 / 128 / 64 segments per workgroup                                      test_bitop_runs_tile_shapes
   a tile of exactly the LDS image's words, one more, far more               test_bitop_runs_tile_of_exactly_the_lds_image, test_bitop_runs_tile_beyond_the_lds_image
   more than 1024 tiles: the scans' second round                              test_bitops_with_more_than_1024_tiles, test_no_wait_decoder_beyond_one_scan_round
+  the operand-list bit operation (wah_bitop_list.hip; expected: the numpy fold of the operand bitmaps through oracle.compress,
+  the index as _Case computes it, an output of exactly C words between sentinels):
+    128 words a batch, the fast path of a full batch of literals             test_list_segment_words, test_list_stream_offsets
+    fills of 1 .. 8 groups by their lane, 9 and more by the wave, 64 a step  test_list_fill_groups
+    kListDepth = 4 batches in flight, settled operands                       test_list_batch_schedules
+    64 operands a chunk, m_first for row 0 alone                             test_list_operand_counts, test_list_operand_positions
+    the settled one-word segment, nvalid < 1024                              test_list_ragged_ends, test_list_refused_identity_fill_of_another_length
+    kSegDecodeWaves = 4 segments a workgroup                                 test_list_segment_counts
+    1023 / 1025 groups, the count clamp, empty fills, bad rows 63 / 64 / 4096 test_list_refusals_at_the_boundaries, test_list_refused_rows
 """
 import functools
 
@@ -514,3 +523,253 @@ def test_fuzz_on_every_route(wah, oracle, seed):
             _check_compress(case, comp, route, d_in, tag=f", input + {offset} words")
     st = _random_foreign_stream(rng, int(rng.choice([3000, 4096 * 2 + 3, 4096 * 9 + 100])), max_groups=8_000_000)
     _decode_routes(wah, f"foreign stream, seed {seed}", st, oracle.decompress(st), oracle.decoded_groups(st))
+
+
+# ---- (h) the operand-list bit operation at its switch points ----------------------------------------------------------------
+WAH_ERR_STREAM = -6
+
+
+class _ListOperands:
+    """Bitmaps as operands of wah_bitop_list_indexed_device: the ORACLE's stream of each and the index computed on the CPU
+    (_Case), on the device; a scratch that every call of the object shares."""
+
+    def __init__(self, wah, maps, n):
+        import torch
+
+        self.wah, self.n, self.maps = wah, int(n), [np.ascontiguousarray(m, np.uint32) for m in maps]
+        assert all(m.size == self.n for m in self.maps)
+        self.cases = [_Case("operand", m) for m in self.maps]
+        self.dev = [(_dev(c.want), torch.from_numpy(c.index).cuda()) for c in self.cases]
+        self.scratch = torch.empty(int(wah.lib().wah_bitop_list_scratch_bytes(self.n, 1)), dtype=torch.uint8, device="cuda")
+
+    def enqueue(self, op, operands, capacity, out_offset=0):
+        """One call over `operands` ((stream, index) pairs or a table) into a guarded output of `capacity` words; returns
+        (status, C as the launch reports it, buffer, output view, index)."""
+        import torch
+
+        wah = self.wah
+        table = operands if isinstance(operands, torch.Tensor) else wah.bitop_operand_table(operands)
+        buf, out = _guarded(capacity, out_offset)
+        n_seg = (self.n + sw.SEG_WORDS - 1) // sw.SEG_WORDS
+        offs = torch.full((n_seg + 1,), -1, dtype=torch.int64, device="cuda")
+        _, count, _ = wah.bitop_list_indexed_device(op, table, self.n, scratch=self.scratch, out=out, out_offsets=offs, check=False)
+        status = int(wah.lib().wah_bitop_list_status(self.scratch.data_ptr(), self.n, int(table.shape[0]), None))
+        return status, int(count.item()), buf, out, offs
+
+    def check(self, op, rows, combined, what, operands=None, many=True):
+        """The table of rows (indices into the operands) under op: exactly the oracle's stream of `combined` and its index, into
+        an output of exactly C words between sentinels; for up to 8 rows also wah_bitop_many_indexed_device's very output."""
+        want = _Case("combined", combined)
+        assert want.n == self.n
+        operands = [self.dev[i] for i in rows] if operands is None else operands
+        status, c, buf, out, offs = self.enqueue(op, operands, want.want.size)
+        what = f"{what} [{op}, {len(operands)} operands]"
+        assert status == 0 and c == want.want.size, (what, status, c, want.want.size)
+        got = _host(out)
+        if not np.array_equal(got, want.want):
+            bad = int(np.flatnonzero(got != want.want)[0])
+            seg = int(np.searchsorted(want.index, bad, side="right")) - 1
+            raise AssertionError(f"{what}: word {bad} (segment {seg}, its word {bad - int(want.index[seg])}) is {got[bad]:#010x}, the oracle's {want.want[bad]:#010x}")
+        assert _untouched(buf, out, want.want.size), f"{what}: written outside the output"
+        assert np.array_equal(offs.cpu().numpy(), want.index), (what, "index")
+        if many and len(operands) <= 8:
+            ref, ref_offs = self.wah.bitop_many_indexed_device(op, operands, self.n)
+            assert ref.numel() == c and np.array_equal(_host(ref), got) and np.array_equal(ref_offs.cpu().numpy()[: want.index.size], want.index), (what, "many")
+
+    def fold(self, op, rows, what, **kw):
+        self.check(op, rows, FOLD[op](np.stack([self.maps[i] for i in rows])).astype(np.uint32), what, **kw)
+
+
+def _dense(rng, n_segments):
+    """Literals only: every group of the other operand meets a random one, so a group applied wrongly shows."""
+    return sw.pack(sw.literals(rng, n_segments * sw.SEG_GROUPS))
+
+
+@pytest.mark.parametrize("op", sw.LIST_OPS)
+def test_list_segment_words(wah, op):
+    """Operand segments of every LIST_SEGMENT_WORDS (1, 2, 128 b - 1, 128 b, 128 b + 1, 1023, 1024 words) built every LIST_WAYS
+    way -- a fill that ends a full batch, that starts the next one, a fast batch that ends at group 1024 -- alone, as the first
+    operand and as a later one of a dense operand, and against the same segments in reverse order."""
+    rng = np.random.default_rng(300)
+    layouts = [p[3] for p in sw.list_words_probes()]
+    probe = sw.list_probe_bitmap(layouts, rng)
+    ops = _ListOperands(wah, [probe, _dense(rng, len(layouts)), sw.list_probe_bitmap(layouts[::-1], rng)], probe.size)
+    for rows in ([0], [0, 1], [1, 0], [0, 2], [2, 1, 0]):
+        ops.fold(op, rows, f"segment words, rows {rows}")
+
+
+@pytest.mark.parametrize("op", sw.LIST_OPS)
+def test_list_fill_groups(wah, op):
+    """A fill of every LIST_FILL_GROUPS (1, 2, 3, 7, 8, 9, 63, 64, 65, 127, 128, 129, 700 groups) in every LIST_FILL_WORD_INDEX
+    (lane 0's and lane 63's first and second word, of the first and of later batches), of ones and of zeros, and the segments of
+    one fill; and batches of many fills (list_many_fills_layouts): alone, in front of and behind a dense operand, and against the
+    same segments in reverse order."""
+    rng = np.random.default_rng(301)
+    layouts = [sw.list_fill_layout(wi, bit, n, total) for wi, bit, n, total in sw.list_fill_probes()] + sw.list_many_fills_layouts()
+    probe = sw.list_probe_bitmap(layouts, rng)
+    ops = _ListOperands(wah, [probe, _dense(rng, len(layouts)), _dense(rng, len(layouts)), sw.list_probe_bitmap(layouts[::-1], rng)], probe.size)
+    for rows in ([0], [0, 1], [1, 0], [1, 0, 2], [0, 3], [3, 1, 0]):
+        ops.fold(op, rows, f"fill groups, rows {rows}")
+
+
+@pytest.mark.parametrize("schedule", sw.LIST_SCHEDULES, ids=lambda s: "-".join(map(str, s)) if len(s) < 12 else f"{len(s)}_operands_{s[-1]}")
+def test_list_batch_schedules(wah, schedule):
+    """The chunks of LIST_SCHEDULES: 0, 1, 3, 4, 5, 8 and more batches in a chunk of kListDepth = 4 in flight, the producer one
+    and two operands ahead of the consumer, settled operands between live ones (the one-word segments are the operation's
+    identity under one of the two fill kinds), a chunk of settled operands in front of a live one."""
+    rng = np.random.default_rng(302 + len(schedule))
+    n_segments = 5 if len(schedule) <= sw.LIST_CHUNK else 2
+    for bit in (0, 1):
+        maps = sw.list_schedule_operands(schedule, bit, n_segments, rng)
+        ops = _ListOperands(wah, maps, n_segments * sw.SEG_WORDS)
+        for op in sw.LIST_OPS:
+            ops.fold(op, list(range(len(maps))), f"schedule {schedule[:12]}, one-word fills of {bit}")
+
+
+def _pool_operands(wah, seed):
+    """Entries 1 .. of list_pool, and as entries 0 and len(pool) the all-zero and the all-one bitmap."""
+    pool = sw.list_pool(np.random.default_rng(seed))
+    n = pool[1].size
+    pool[0] = sw.list_trivial("or", n)
+    pool.append(sw.list_trivial("and", n))
+    return _ListOperands(wah, pool, n), pool
+
+
+@pytest.mark.parametrize("k", sw.LIST_OPERAND_COUNTS)
+def test_list_operand_counts(wah, k):
+    """Tables of 1, 2, 63, 64, 65, 127, 128, 129 and 4097 rows (the rows of a small pool in turn: a row is 24 bytes)."""
+    ops, pool = _pool_operands(wah, 303)
+    rows = sw.list_table_rows(k, len(pool) - 1)
+    for op in sw.LIST_OPS:
+        ops.check(op, rows, sw.list_fold(op, pool, rows), f"{k} rows")
+
+
+@pytest.mark.parametrize("name", list(sw.LIST_PLACED))
+def test_list_operand_positions(wah, name):
+    """LIST_PLACED: every row but the placed ones is the operation's trivial operand (settled while the chunk is gathered) -- the
+    only live operand in row 0, 1, 62, 63, 64, 65, 128; live operands in rows 0, 1, 63, 64 and 128 of one table; row 0's bitmap
+    again in rows 64 and 128 (ANDNOT: A and not A -- m_first is row 0's alone); live operands in lanes 62 and 63."""
+    ops, pool = _pool_operands(wah, 304)
+    n_rows, placed = sw.LIST_PLACED[name]
+    for op in sw.LIST_OPS:
+        trivial = len(pool) - 1 if op == "and" else 0
+        rows = [e if e else trivial for e in sw.list_table_rows(n_rows, len(pool) - 1, placed)]
+        ops.check(op, rows, sw.list_fold(op, pool, rows), name)
+
+
+@pytest.mark.parametrize("tail", sw.LAST_SEGMENT_WORDS)
+def test_list_ragged_ends(wah, tail):
+    """A last segment of 2, 31, 32, 34, 1023 groups that is one fill of zeros (settled with count == nvalid; under AND a fill with
+    an effect), one fill of ones as far as a bitmap can hold one, or literals up to the last group."""
+    rng = np.random.default_rng(305 + tail)
+    head = [sw.list_words_layout(130, "fill first", 1), sw.list_words_layout(1024, "literals + fill", 0)]
+    ways = sw.list_ragged_layouts(tail)
+    maps = [sw.list_probe_bitmap(head, rng, tail=(layout, tail)) for layout in ways.values()]
+    n = maps[0].size
+    maps.append(rng.integers(0, 2**32, n, dtype=np.uint64).astype(np.uint32))
+    ops = _ListOperands(wah, maps, n)
+    for op in sw.LIST_OPS:
+        for rows in ([0], [1], [2], [0, 3], [3, 0], [1, 3], [3, 1], [2, 3], [3, 2, 1, 0], [0, 1, 2, 3]):
+            ops.fold(op, rows, f"a last segment of {tail} words, rows {rows}")
+
+
+@pytest.mark.parametrize("n_segments", sw.LIST_SEGMENTS)
+def test_list_segment_counts(wah, n_segments):
+    """1, 3, 4 and 5 segments (kSegDecodeWaves = 4 a workgroup: idle waves in the last one), whole and with a short last one."""
+    rng = np.random.default_rng(306 + n_segments)
+    for tail in (0, 30):
+        maps = []
+        for j in range(3):
+            layouts = [sw.list_words_layout((2, 129, 1024, 300, 7)[(s + j) % 5], sw.LIST_WAYS[(s + j) % 2 * 3], (s + j) & 1) for s in range(n_segments - (1 if tail else 0))]
+            maps.append(sw.list_probe_bitmap(layouts, rng, tail=(list(sw.list_ragged_layouts(tail).values())[j], tail) if tail else None))
+        ops = _ListOperands(wah, maps, maps[0].size)
+        for op in sw.LIST_OPS:
+            ops.fold(op, [0, 1, 2], f"{n_segments} segments, tail {tail}")
+            ops.fold(op, [2, 0], f"{n_segments} segments, tail {tail}")
+
+
+def test_list_stream_offsets(wah):
+    """One operand's stream 0, 1, 2, 3 words behind a 16-byte boundary (the batches are loaded eight bytes a lane)."""
+    rng = np.random.default_rng(307)
+    layouts = [p[3] for p in sw.list_words_probes()][::3]
+    maps = [sw.list_probe_bitmap(layouts, rng), _dense(rng, len(layouts)), sw.list_probe_bitmap(layouts[::-1], rng)]
+    ops = _ListOperands(wah, maps, maps[0].size)
+    for at in range(3):
+        for offset in range(4):
+            moved = list(ops.dev)
+            moved[at] = (_at_offset(ops.cases[at].want, offset), ops.dev[at][1])
+            for op in sw.LIST_OPS:
+                ops.fold(op, [0, 1, 2], f"operand {at} + {offset} words", operands=moved)
+
+
+def _refused(ops, operands, valid_rows, what):
+    """`operands` gives WAH_ERR_STREAM under every operation, nothing is written behind the output's capacity, and the valid rows
+    give the right words on the same scratch afterwards."""
+    capacity = ops.wah.max_compressed_words(ops.n)
+    for op in sw.LIST_OPS:
+        status, _, buf, out, _ = ops.enqueue(op, operands, capacity)
+        assert status == WAH_ERR_STREAM, (what, op, status)
+        assert _untouched(buf, out, capacity), f"{what} [{op}]: written behind the capacity"
+        ops.fold(op, valid_rows, f"after {what}", many=False)
+
+
+def test_list_refusals_at_the_boundaries(wah):
+    """Hand-built words that the kernel must refuse (tests/_switch.py list_refusals: 1023 and 1025 groups with the fill in batch
+    1, 2 and 8; counts of 2047, 2048, 2049 and 2^30 - 1, 128 of them; an empty fill in lane 63's second word and in a later
+    batch; a batch of literals behind 897 groups; a lone literal), as a later operand and as the first.  Every stream has its
+    OWN index, every range inside it: these check a verdict, whatever the kernel does it reads allocated memory only."""
+    import torch
+
+    rng = np.random.default_rng(308)
+    ops, pool = _pool_operands(wah, 308)
+    oracle = _oracle.load()
+    valid = [oracle.compress(pool[2][lo: lo + sw.SEG_WORDS]) for lo in range(0, ops.n, sw.SEG_WORDS)]
+    for name, words in sw.list_refusals(rng):
+        for segment in (1, 2):
+            stream, index = sw.list_refused_stream(valid, segment, words)
+            bad = (_dev(stream), torch.from_numpy(index).cuda())
+            _refused(ops, [ops.dev[1], bad, ops.dev[3]], [1, 3], f"{name} (segment {segment}, row 1)")
+        _refused(ops, [bad, ops.dev[1]], [2, 1], f"{name} (row 0)")
+        _refused(ops, [bad], [2], f"{name} (alone)")
+
+
+@pytest.mark.parametrize("tail", [30, 991])
+def test_list_refused_identity_fill_of_another_length(wah, tail):
+    """The settled path's own check (count == nvalid): as an operand, the all-zero stream of a bitmap one word shorter and one
+    longer with as many segments -- its last segment is ONE identity fill of nvalid - 1 and of nvalid + 1 groups."""
+    import torch
+
+    rng = np.random.default_rng(309)
+    n = sw.SEG_WORDS + tail
+    maps = [rng.integers(0, 2**32, n, dtype=np.uint64).astype(np.uint32), np.zeros(n, np.uint32)]
+    ops = _ListOperands(wah, maps, n)
+    nvalid = (32 * tail + 30) // 31
+    for other, d in ((n - 1, -1), (n + 1, 1)):
+        zero = _Case("zeros", np.zeros(other, np.uint32))
+        assert list(zero.want) == [sw.FILL0 | sw.SEG_GROUPS, sw.FILL0 | (nvalid + d)] and list(zero.index) == [0, 1, 2]
+        bad = (_dev(zero.want), torch.from_numpy(zero.index).cuda())
+        for operands in ([ops.dev[0], bad], [bad, ops.dev[0]], [bad], [ops.dev[0], ops.dev[1], bad]):
+            _refused(ops, operands, [0, 1], f"an identity fill of nvalid {d:+d} groups among {len(operands)}")
+
+
+@pytest.mark.parametrize("k, row", [(sw.LIST_CHUNK, sw.LIST_CHUNK - 1), (sw.LIST_CHUNK + 1, sw.LIST_CHUNK), (4097, 4096)])
+def test_list_refused_rows(wah, k, row):
+    """A bad entry in row 63, in row 64 only, and in the last of 4097 rows: an operand whose one segment has 1025 groups, and a
+    table entry without an index."""
+    import torch
+
+    rng = np.random.default_rng(310)
+    ops, pool = _pool_operands(wah, 310)
+    oracle = _oracle.load()
+    valid = [oracle.compress(pool[2][lo: lo + sw.SEG_WORDS]) for lo in range(0, ops.n, sw.SEG_WORDS)]
+    name, words = sw.list_refusals(rng)[1]
+    assert name.startswith("1025 groups")
+    stream, index = sw.list_refused_stream(valid, 2, words)
+    bad = (_dev(stream), torch.from_numpy(index).cuda())
+    rows = sw.list_table_rows(k, len(pool) - 1)
+    operands = [ops.dev[i] for i in rows]
+    operands[row] = bad
+    _refused(ops, operands, rows[:3], f"{name} in row {row} of {k}")
+    table = wah.bitop_operand_table([ops.dev[i] for i in rows])
+    table[row, 2] = 0
+    _refused(ops, table, rows[:3], f"no index in row {row} of {k}")

@@ -36,6 +36,12 @@ SOURCES = {
     "runs image": ("wah_bitop_runs.hip", r"want = \(total \* kTileSegs \* (\d+)u / (\d+)u / a\.n_segments \+ (\d+)u\) & ~\(u64\)(\d+)u;"),
     "runs scan threads": ("wah_bitop_runs.hip", r"const u64 per = \(n_tiles \+ 1023u\) / (\d+)u;"),
     "sums offsets threads": ("wah_decode.hip", r"sums_offsets_kernel, dim3\(1\), dim3\((\d+)\)"),
+    "kListShortFill": ("wah_bitop_list.hip", r"constexpr u32 kListShortFill = (\d+);"),
+    "WAH_LIST_DEPTH": ("wah_bitop_list.hip", r"#define WAH_LIST_DEPTH (\d+)"),
+    "list batch words": ("wah_bitop_list.hip", r"if \((\d+)u \* \(c\.b \+ 1u\) < cnt\)"),
+    "list chunk operands": ("wah_bitop_list.hip", r"j0 < a\.n; j0 \+= (\d+)u\)"),
+    "WAH_SEG_WAVES": ("wah_segdecode.hpp", r"#define WAH_SEG_WAVES (\d+)"),
+    "list count clamp factor": ("wah_bitop_list.hip", r"n0 = in0 \? min\(word_groups\(w0\), (\d+)u \* kSegGroups\)"),
 }
 
 
@@ -76,17 +82,20 @@ def test_thresholds_are_the_sources_own():
     with open(os.path.join(os.path.dirname(CSRC), "Makefile")) as f:
         makefile = f.read()
     assert "WAH_PAIR_SWIZZLE_FROM" not in makefile and "WAH_DT_MAXG" not in makefile  # (no target builds with other values)
+    assert "WAH_LIST_DEPTH" not in makefile and "WAH_SEG_WAVES" not in makefile
 
 
 def test_a_retuned_threshold_is_noticed(tmp_path):
-    """A copy of the sources with WAH_PAIR_SWIZZLE_FROM / WAH_DT_MAXG moved by one: the message names the probe list."""
-    for name, probes in (("WAH_PAIR_SWIZZLE_FROM", "PAIR_COUNTS"), ("WAH_DT_MAXG", "TILE_TOTALS")):
+    """A copy of the sources with WAH_PAIR_SWIZZLE_FROM / WAH_DT_MAXG / WAH_LIST_DEPTH / kListShortFill / WAH_SEG_WAVES moved
+    by one: the message names the probe list."""
+    for name, probes in (("WAH_PAIR_SWIZZLE_FROM", "PAIR_COUNTS"), ("WAH_DT_MAXG", "TILE_TOTALS"), ("WAH_LIST_DEPTH", "LIST_SCHEDULES"),
+                         ("kListShortFill", "LIST_FILL_GROUPS"), ("WAH_SEG_WAVES", "LIST_SEGMENTS")):
         copy = tmp_path / name
         copy.mkdir()
         for f in os.listdir(CSRC):
             with open(os.path.join(CSRC, f)) as h:
                 text = h.read()
-            text = re.sub(rf"(#define {name} )(\d+)", lambda m: m.group(1) + str(int(m.group(2)) + 1), text)
+            text = re.sub(rf"(#define {name} |constexpr u32 {name} = )(\d+)", lambda m: m.group(1) + str(int(m.group(2)) + 1), text)
             (copy / f).write_text(text)
         with pytest.raises(AssertionError, match=rf"{name} is \d+ .* move {probes} "):
             check_thresholds(str(copy))
@@ -339,3 +348,238 @@ def test_every_probe_pair_lands_in_every_slot_of_every_shape():
     assert [sw.wave_segs(2 * (fronts[name] + n_probes)) for name in ("padding 0", "two pairs per wave, shift 0", "three pairs per wave, shift 0")] == [1, 2, 5]
     bitmap, pairs = sw.shaped_probe_bitmap(np.random.default_rng(1), 5)
     assert pairs == 5 + n_probes and bitmap.size == pairs * 2 * sw.SEG_WORDS and not bitmap[: 5 * 2 * sw.SEG_WORDS].any()
+
+
+# ---- the operand-list bit operation ------------------------------------------------------------------------------------------
+def _segment_streams(oracle, bitmap):
+    """[(the oracle's words of a segment, its groups)] of a bitmap."""
+    out = []
+    for lo in range(0, bitmap.size, sw.SEG_WORDS):
+        part = bitmap[lo: lo + sw.SEG_WORDS]
+        out.append((oracle.compress(part), (32 * part.size + 30) // 31))
+    return out
+
+
+def _is_layout(comp, layout):
+    """comp is list_layout_words(layout): the fills where it says, with their counts, literals elsewhere."""
+    want = sw.list_layout_words(layout)
+    fills = want != 0
+    return comp.size == want.size and np.array_equal(comp[fills], want[fills]) and not np.any(comp[~fills] & sw.FILL0)
+
+
+def test_list_segments_compress_to_the_stated_words(oracle):
+    rng = np.random.default_rng(20)
+    probes = sw.list_words_probes()
+    assert {w for w, _, _, _ in probes} == set(sw.LIST_SEGMENT_WORDS) >= {1, 2, 127, 128, 129, 255, 256, 257, 384, 511, 512, 513, 1023, 1024}
+    for way in sw.LIST_WAYS:  # every way gives every count it can give: all of them but the few a way excludes by its nature
+        assert {w for w, y, _, _ in probes if y == way} >= {w for w in sw.LIST_SEGMENT_WORDS if w > sw.LIST_BATCH}, way
+    assert {b for _, _, b, _ in probes} == {0, 1}
+    for words, way, bit, layout in probes:
+        seg = sw.list_segment(layout, rng)
+        comp = oracle.compress(seg)
+        assert seg.size == sw.SEG_WORDS and comp.size == words and _is_layout(comp, layout), (words, way)
+        fill = np.flatnonzero(comp & sw.FILL0)
+        if way == "fill ends a batch":
+            assert fill[0] % sw.LIST_BATCH == sw.LIST_BATCH - 1 and fill[0] + 1 == words // sw.LIST_BATCH * sw.LIST_BATCH, (words, fill)
+        elif way == "fill starts the next batch":
+            assert list(fill) == [(words - 1) // sw.LIST_BATCH * sw.LIST_BATCH], (words, fill)
+        elif way == "fill first":
+            assert list(fill) == [0]
+        else:
+            assert list(fill) == ([words - 1] if words < sw.SEG_GROUPS else [])
+    bitmap = sw.list_probe_bitmap([p[3] for p in probes], rng)
+    assert [w.size for w, _ in _segment_streams(oracle, bitmap)] == [p[0] for p in probes]
+
+
+def test_list_fills_are_where_they_are_stated(oracle):
+    rng = np.random.default_rng(21)
+    probes = sw.list_fill_probes()
+    assert {(wi, n) for wi, _, n, _ in probes} >= {(wi, n) for wi in sw.LIST_FILL_WORD_INDEX for n in sw.LIST_FILL_GROUPS}
+    assert {1, 2, 7, 8, 9, 63, 64, 65, 128, 129} <= set(sw.LIST_FILL_GROUPS) and set(sw.LIST_FILL_WORD_INDEX) == {0, 1, 126, 127, 128, 129, 255, 256}
+    for wi, bit, n, total in probes:
+        seg = sw.list_fill_at(wi, bit, n, total, rng)
+        comp = oracle.compress(seg)
+        assert comp.size == total and comp[wi] == ((sw.FILL1 if bit else sw.FILL0) | n), (wi, bit, n, total)
+        assert not np.any(comp[:wi] & sw.FILL0), "literals in front: the fill starts at group wi"
+        assert np.count_nonzero(comp & sw.FILL0) == (2 if total > wi + 1 else 1)
+        assert _is_layout(comp, sw.list_fill_layout(wi, bit, n, total))
+    for layout in sw.list_many_fills_layouts():
+        assert _is_layout(oracle.compress(sw.list_segment(layout, rng)), layout)
+
+
+def test_list_schedules_hold_the_stated_words(oracle):
+    rng = np.random.default_rng(22)
+    for schedule in sw.LIST_SCHEDULES:
+        n_segments = 5 if len(schedule) <= sw.LIST_CHUNK else 2
+        for bit in (0, 1):
+            maps = sw.list_schedule_operands(schedule, bit, n_segments, rng)
+            counts = sw.list_schedule_counts(schedule, n_segments)
+            assert len(maps) == len(schedule) and counts[0] == list(schedule)
+            got = [[w.size for w, _ in _segment_streams(oracle, m)] for m in maps]
+            assert [list(c) for c in zip(*got)] == counts, schedule
+            ones = [int(w[0]) for m in maps for w, _ in _segment_streams(oracle, m) if w.size == 1]
+            assert all(w == ((sw.FILL1 if bit else sw.FILL0) | sw.SEG_GROUPS) for w in ones)
+
+
+def test_list_ragged_ends(oracle):
+    rng = np.random.default_rng(23)
+    groups = []
+    for tail in sw.LAST_SEGMENT_WORDS:
+        ways = sw.list_ragged_layouts(tail)
+        for name, layout in ways.items():
+            bitmap = sw.list_probe_bitmap([[("lit", 1024)]], rng, tail=(layout, tail))
+            assert bitmap.size == sw.SEG_WORDS + tail
+            comp, nvalid = _segment_streams(oracle, bitmap)[1]
+            assert nvalid == sum(n for _, n in layout) and oracle.decoded_groups(comp) == nvalid
+            if name == "zeros":
+                assert list(comp) == [sw.FILL0 | nvalid]
+            elif name == "ones":
+                assert comp[0] == (sw.FILL1 | (nvalid if comp.size == 1 else nvalid - 1)) and comp.size == (1 if tail % 31 == 0 else 2)
+            else:
+                assert comp.size == nvalid and not np.any(comp & sw.FILL0)
+        groups.append(nvalid)
+    assert groups == [2, 31, 32, 34, 1023]
+
+
+def test_list_tables_and_refusals(oracle):
+    rng = np.random.default_rng(24)
+    pool = sw.list_pool(rng)
+    assert all(p.size == 3 * sw.SEG_WORDS for p in pool[1:])
+    for op in sw.LIST_OPS:
+        pool[0] = sw.list_trivial(op, pool[1].size)
+        for w, nvalid in _segment_streams(oracle, pool[0]):
+            assert sw.list_paths(w, nvalid, op)["settled"] and sw.list_paths(w, nvalid, op, first=True)["settled"]
+        for k in (1, 2, 5, 9, 64, 129):  # list_fold is the plain fold of the stacked rows
+            rows = sw.list_table_rows(k, len(pool))
+            fold = {"and": np.bitwise_and.reduce, "or": np.bitwise_or.reduce, "xor": np.bitwise_xor.reduce}.get(op)
+            stack = np.stack([pool[i] for i in rows])
+            want = fold(stack) if fold else (stack[0] & ~np.bitwise_or.reduce(stack[1:]) if k > 1 else stack[0])
+            assert np.array_equal(sw.list_fold(op, pool, rows), want), (op, k)
+        for name, (n_rows, placed) in sw.LIST_PLACED.items():
+            rows = sw.list_table_rows(n_rows, len(pool), placed)
+            assert len(rows) == n_rows and all(rows[r] == e for r, e in placed.items()) and sum(1 for e in rows if e) == len(placed)
+    a = pool[1]
+    n_rows, placed = sw.LIST_PLACED["row 0 again in rows 64 and 128"]
+    rows = sw.list_table_rows(n_rows, len(pool), placed)
+    assert not sw.list_fold("andnot", [sw.list_trivial("andnot", a.size)] + pool[1:], rows).any() and a.any()   # A and not A
+    valid = [w for w, _ in _segment_streams(oracle, pool[2])]
+    for name, words in sw.list_refusals(rng):
+        assert 1 <= words.size <= sw.SEG_GROUPS and words.dtype == np.uint32, name
+        for op in sw.LIST_OPS:
+            for first in (False, True):
+                path = sw.list_paths(words, sw.SEG_GROUPS, op, first)
+                assert not path["settled"] and not path["ok"], (name, op)
+                for b in path["batches"]:  # nothing is put outside the accumulator: every applied word ends at or below group 1024
+                    assert all(p + n <= sw.SEG_GROUPS for way, n, p in b["words"] if way not in ("outside", "empty", "identity")), name
+        stream, index = sw.list_refused_stream(valid, 1, words)
+        assert index[0] == 0 and index[-1] == stream.size and np.all(np.diff(index) >= 1) and np.array_equal(stream[index[1]: index[2]], words)
+        assert np.array_equal(stream[: index[1]], valid[0]) and np.array_equal(stream[index[2]:], valid[2])
+
+
+def test_list_probes_reach_every_path(oracle):
+    """list_paths() over the oracle's streams of the probe bitmaps of tests/test_gpu_switch_points.py: every predicate of the
+    list kernel is seen true and false, with the boundary and its neighbours where it is a comparison."""
+    rng = np.random.default_rng(25)
+    segments = []  # (words, nvalid)
+    words_bitmap = sw.list_probe_bitmap([p[3] for p in sw.list_words_probes()], rng)
+    fills_bitmap = sw.list_probe_bitmap([sw.list_fill_layout(wi, bit, n, total) for wi, bit, n, total in sw.list_fill_probes()]
+                                        + sw.list_many_fills_layouts(), rng)
+    segments += _segment_streams(oracle, words_bitmap) + _segment_streams(oracle, fills_bitmap)
+    for tail in sw.LAST_SEGMENT_WORDS:
+        for layout in sw.list_ragged_layouts(tail).values():
+            segments.append(_segment_streams(oracle, sw.list_probe_bitmap([], rng, tail=(layout, tail)))[0])
+    refused = [w for _, w in sw.list_refusals(rng)]
+    for op in sw.LIST_OPS:
+        for first in (False, True):
+            paths = [sw.list_paths(w, nv, op, first) for w, nv in segments]
+            assert all(p["ok"] for p in paths)
+            batches = [b for p in paths for b in p["batches"]]
+            ways = {way for b in batches for way, _, _ in b["words"]}
+            assert ways == {"fast", "literal", "identity", "own first", "own rest", "wave"}, (op, first, ways)
+            # identity or effect: both kinds of fill both ways (list_op); under ANDNOT row 0 is applied as OR
+            effect_kind = sw.FILL0 if (op == "and") else sw.FILL1
+            kinds = {(int(w[wi0 + i]) & sw.FILL1, way != "identity") for (w, _), p in zip(segments, paths)
+                     for wi0, b in zip(range(0, 1024, sw.LIST_BATCH), p["batches"]) if not b["fast"]
+                     for i, (way, _, _) in enumerate(b["words"]) if int(w[wi0 + i]) & sw.FILL0}
+            assert kinds == {(effect_kind, True), (effect_kind ^ 0x40000000, False)}, (op, first, kinds)
+            # kListShortFill; the first store alone, list_put_rest, list_put_long and its steps of 64 groups
+            effect = [(n, p, i) for b in batches for i, (way, n, p) in enumerate(b["words"]) if way in ("own first", "own rest", "wave")]
+            counts = {n for n, _, _ in effect}
+            _sides(counts, lambda n: n <= sw.LIST_SHORT_FILL, sw.LIST_SHORT_FILL)
+            _sides(counts, lambda n: n > 1, 2)                     # s0 > 1: list_put_rest
+            _sides(counts, lambda n: n >= 64, 64)                  # lane 63 has a group in the first step
+            _sides(counts, lambda n: n > 128, 128)                 # a third step
+            assert {True, False} == {b["rest"] for b in batches if not b["fast"]}
+            wave = [(n, p, i) for n, p, i in effect if n > sw.LIST_SHORT_FILL]
+            assert {p % 64 == 0 for _, p, _ in wave} == {True, False}
+            assert {i for _, _, i in wave} >= {0, 1, sw.LIST_BATCH - 2, sw.LIST_BATCH - 1}   # lane 0 and lane 63, w0 and w1
+            assert {i for n, _, i in effect if 1 < n <= sw.LIST_SHORT_FILL} >= {0, 1, sw.LIST_BATCH - 2, sw.LIST_BATCH - 1}
+            # list_put_long's mask: many long fills in one batch, in the lanes' first words and in their second ones
+            for parity in (0, 1):
+                assert max(sum(1 for i, (way, _, _) in enumerate(b["words"]) if way == "wave" and i % 2 == parity) for b in batches) >= 56
+                assert max(sum(1 for i, (way, _, _) in enumerate(b["words"]) if way == "own rest" and i % 2 == parity) for b in batches) >= 10
+            assert any({"wave", "own rest", "own first", "identity", "literal"} <= {way for way, _, _ in b["words"]} for b in batches)
+            # the batches of a segment: 128 (b + 1) < cnt, and which batch is the last
+            live = [(w.size, p) for (w, _), p in zip(segments, paths) if not p["settled"]]
+            sizes = {c for c, _ in live}
+            for b in range(1, 8):
+                _sides(sizes, lambda c: sw.LIST_BATCH * b < c, sw.LIST_BATCH * b)
+            assert {len(p["batches"]) for _, p in live} == set(range(1, 9))
+            assert all((len(p["batches"]) == (c + sw.LIST_BATCH - 1) // sw.LIST_BATCH) and [b["last"] for b in p["batches"]] == [False] * (len(p["batches"]) - 1) + [True]
+                       for c, p in live)
+            # the fast path: each of its three conditions decides somewhere
+            assert {(b["fast"], b["last"]) for b in batches} == {(True, True), (True, False), (False, True), (False, False)}
+            general = [b for b in batches if not b["fast"]]
+            assert any(b["full"] for b in general) and any(not b["full"] and all(way == "literal" for way, _, _ in b["words"]) for b in general)
+            assert any(b["full"] and sum(1 for way, _, _ in b["words"] if way != "literal") == 1 and b["words"][-1][0] != "literal" for b in general)
+            assert sw.SEG_GROUPS - sw.LIST_BATCH in {b["pos"] for b in batches if b["fast"]}       # pos + 128 == 1024 ...
+            late = [sw.list_paths(w, sw.SEG_GROUPS, op, first) for w in refused]                   # ... and 1025: only when refused
+            assert any(not b["fast"] and b["full"] and b["pos"] == sw.SEG_GROUPS - sw.LIST_BATCH + 1 and all(way in ("literal", "outside") for way, _, _ in b["words"])
+                       for p in late for b in p["batches"])
+            # the settled test: each of its four conditions decides somewhere
+            one = [(int(w[0]), nv, p["settled"]) for (w, nv), p in zip(segments, paths) if w.size == 1]
+            assert {(s, nv == sw.SEG_GROUPS) for _, nv, s in one} == {(True, True), (True, False), (False, True), (False, False)}, (op, first)
+            assert any(p["settled"] is False and w.size == 2 and w[0] & sw.FILL0 for (w, _), p in zip(segments, paths))  # cnt == 2
+            lone = [sw.list_paths(w, sw.SEG_GROUPS, op, first) for w in refused if w.size == 1]
+            assert lone and not any(p["settled"] or p["ok"] for p in lone)                          # a literal
+            for nv in (2, 31, 1024):                                                                 # a count that is not nvalid
+                ident = (sw.FILL1 if op == "and" else sw.FILL0)
+                assert sw.list_paths([ident | nv], nv, op, first)["settled"]
+                for d in (-1, 1):
+                    wrong = sw.list_paths([ident | (nv + d)], nv, op, first)
+                    assert not wrong["settled"] and not wrong["ok"]
+    # the clamp of a count
+    _sides(set(sw.LIST_BAD_COUNTS), lambda n: n > sw.LIST_CLAMP, sw.LIST_CLAMP)
+    assert sw.COUNT_MASK in sw.LIST_BAD_COUNTS and sw.LIST_BATCH * sw.LIST_CLAMP < 2**32 <= sw.LIST_BATCH * sw.COUNT_MASK
+    # 64 operands a chunk: the tables' lengths, the rows of a live operand
+    for chunk in (sw.LIST_CHUNK, 2 * sw.LIST_CHUNK):
+        _sides(set(sw.LIST_OPERAND_COUNTS), lambda k: k > chunk, chunk)
+    assert max(sw.LIST_OPERAND_COUNTS) > 64 * sw.LIST_CHUNK
+    _sides(set(sw.LIST_POSITIONS), lambda r: r >= sw.LIST_CHUNK, sw.LIST_CHUNK)            # j0 += 64: the second chunk
+    lanes = {r % sw.LIST_CHUNK for r in sw.LIST_POSITIONS}
+    assert {0, 1, sw.LIST_CHUNK - 2, sw.LIST_CHUNK - 1} <= lanes                              # c.j >= 63u: lanes 62 and 63
+    assert {r for r in sw.LIST_POSITIONS if r % sw.LIST_CHUNK == 0} >= {0, sw.LIST_CHUNK, 2 * sw.LIST_CHUNK}   # j0 + cons.j == 0u: lane 0 of every chunk
+    assert any(set(pl) >= {sw.LIST_CHUNK - 2, sw.LIST_CHUNK - 1} for _, pl in sw.LIST_PLACED.values())       # live lanes 62 AND 63
+    # kSegDecodeWaves segments a workgroup
+    _sides(set(sw.LIST_SEGMENTS), lambda s: s > sw.SEG_WAVES, sw.SEG_WAVES)
+    assert {(-s) % sw.SEG_WAVES for s in sw.LIST_SEGMENTS} >= {0, 1, sw.SEG_WAVES - 1}       # idle waves of the last workgroup
+    # kListDepth batches in flight: the batches of a chunk, the operand boundaries between consumer and producer
+    totals, ahead, between, all_settled_then_live = set(), set(), False, False
+    for schedule in sw.LIST_SCHEDULES:
+        for op in sw.LIST_OPS:
+            for bit in (0, 1):
+                word = (sw.FILL1 if bit else sw.FILL0) | sw.SEG_GROUPS
+                settled = sw.list_paths([word], sw.SEG_GROUPS, op)["settled"]
+                for counts in sw.list_schedule_counts(schedule, 5 if len(schedule) <= sw.LIST_CHUNK else 2):
+                    chunks = [counts[j0: j0 + sw.LIST_CHUNK] for j0 in range(0, len(counts), sw.LIST_CHUNK)]
+                    lives = [[c for c in chunk if not (c == 1 and settled)] for chunk in chunks]
+                    for chunk, alive in zip(chunks, lives):
+                        totals.add(sum((c + sw.LIST_BATCH - 1) // sw.LIST_BATCH for c in alive))
+                        ahead |= set(sw.list_chunk_rotation(alive))
+                        flags = [not (c == 1 and settled) for c in chunk]
+                        between |= any(flags[i] and not flags[i + 1] and any(flags[i + 2:]) for i in range(len(flags) - 2))
+                    all_settled_then_live |= len(lives) > 1 and not lives[0] and bool(lives[1])
+    _sides(totals, lambda b: b > sw.LIST_DEPTH, sw.LIST_DEPTH)
+    assert {0, 1, 3, 4, 5, 8} <= totals and max(totals) >= 9, totals
+    assert {0, 1, 2, sw.LIST_CHUNK} <= ahead, ahead
+    assert between and all_settled_then_live
