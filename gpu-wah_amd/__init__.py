@@ -43,6 +43,9 @@ from .api import (  # noqa: F401
     bitop_list_indexed_device,
     bitop_operand_table,
     BitopOperand,
+    bitop_clauses_indexed_device,
+    bitop_clause_table,
+    CLAUSE_NEGATE,
     merge_fills_device,
     StreamReport,
     gen_uniform_device,

@@ -63,6 +63,9 @@ ABI_SYMBOLS = {
     "wah_bitop_list_scratch_bytes": (_sz, [_u64, _u64]),
     "wah_bitop_list_indexed_device": (_int, [_int, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
     "wah_bitop_list_status": (_int, [_vp, _u64, _u64, _vp]),
+    "wah_bitop_clauses_scratch_bytes": (_sz, [_u64, _u64, _u64]),
+    "wah_bitop_clauses_indexed_device": (_int, [_u64, _u64, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
+    "wah_bitop_clauses_status": (_int, [_vp, _u64, _u64, _u64, _vp]),
     "wah_gen_uniform_device": (_int, [_vp, _u64, _u64, _u64, _vp]),
     "wah_gen_clustered_device": (_int, [_vp, _u64, _u64, _u64, _vp]),
     "wah_copy_device": (_int, [_vp, _vp, _u64, _vp]),
@@ -519,6 +522,61 @@ def bitop_list_indexed_device(op, operands, n_words, scratch=None, out=None, out
     if not check:
         return out, count, out_offsets
     _check(lib().wah_bitop_list_status(scratch.data_ptr(), n, k, sp), "bitop_list_indexed")
+    return out[: int(count.item())], out_offsets
+
+
+CLAUSE_NEGATE = -(1 << 63)  # WAH_CLAUSE_NEGATE (bit 63) as the int64 a clause table holds
+
+
+def bitop_clause_table(clauses, device=None):
+    """The two device tables of a conjunction of clauses (wah_bitop_clauses_indexed_device): clauses is a list of
+    (operands, negate) with operands a non-empty list of (stream, seg_offsets) pairs.  Returns (operand_table [k, 3] int64,
+    clause_ends [c] int64): the operands of all clauses back to back (bitop_operand_table), and per clause the index one past
+    its last operand, bit 63 set for a negated clause.  The tables hold RAW POINTERS and no reference to the tensors they
+    point into: the caller keeps those alive for as long as the tables are used."""
+    torch = _torch()
+    if not clauses:
+        raise WahError("a clause table needs at least one clause")
+    flat, ends = [], []
+    for operands, negate in clauses:
+        if not operands:
+            raise WahError("a clause needs at least one operand")
+        flat.extend(operands)
+        ends.append(len(flat) | (CLAUSE_NEGATE if negate else 0))
+    table = bitop_operand_table(flat, device=device)
+    return table, torch.tensor(ends, dtype=torch.int64, device=table.device)
+
+
+def bitop_clauses_indexed_device(clauses, n_words, scratch=None, out=None, out_offsets=None, check=True):
+    """compress(AND over clauses of [NOT] (OR of the clause's operands)) in one call (wah_bitop_clauses_indexed_device): a
+    conjunction of IN / NOT IN lists over a bitmap index.  clauses: a list of (operands, negate) as for bitop_clause_table,
+    or the ready pair (operand_table, clause_ends) -- only the device reads them.  Returns as bitop_list_indexed_device:
+    (stream, seg_offsets), or with check=False, which only enqueues, (out, count tensor, out_offsets)."""
+    torch = _torch()
+    ready = isinstance(clauses, (tuple, list)) and len(clauses) == 2 and all(isinstance(t, torch.Tensor) for t in clauses)
+    table, ends = clauses if ready else bitop_clause_table(clauses)
+    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 3 or table.shape[0] < 1 or not table.is_cuda or not table.is_contiguous():
+        raise WahError("an operand table is a contiguous int64 CUDA tensor of shape [k, 3], k >= 1")
+    if ends.dtype != torch.int64 or ends.dim() != 1 or not 1 <= ends.shape[0] <= table.shape[0] or ends.device != table.device or not ends.is_contiguous():
+        raise WahError("clause ends are a contiguous int64 tensor of 1 to k entries on the operand table's device")
+    dev = table.device
+    n, k, c = int(n_words), int(table.shape[0]), int(ends.shape[0])
+    cap = max_compressed_words(n)
+    n_seg = (cap + 1023) // 1024
+    if scratch is None:
+        scratch = torch.empty(int(lib().wah_bitop_clauses_scratch_bytes(n, k, c)), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+    if out_offsets is None:
+        out_offsets = torch.zeros(n_seg + 1, dtype=torch.int64, device=dev)
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    sp = _stream_ptr(torch)
+    _check(lib().wah_bitop_clauses_indexed_device(n, c, ends.data_ptr(), k, table.data_ptr(), out.data_ptr(), out.numel(),
+                                                  count.data_ptr(), out_offsets.data_ptr(), scratch.data_ptr(), scratch.numel(), sp),
+           "wah_bitop_clauses_indexed_device")
+    if not check:
+        return out, count, out_offsets
+    _check(lib().wah_bitop_clauses_status(scratch.data_ptr(), n, k, c, sp), "bitop_clauses_indexed")
     return out[: int(count.item())], out_offsets
 
 

@@ -113,6 +113,41 @@ def combine_columns(wah, op, stream, seg_offsets, n_words_per_column, column_ids
     return wah.bitop_list_indexed_device(op, table, n_words_per_column, **reuse)
 
 
+def filter_columns(wah, predicates, n_words_per_column, tables=None, **reuse):
+    """A conjunction of predicates over SEVERAL attributes in one call (wah_bitop_clauses_indexed_device): predicates is a
+    list of (stream, seg_offsets, column_ids, negate), one per attribute, each naming columns of its OWN
+    compress_column_matrix result (arguments as column_operand_table; all matrices of one column length).  A predicate is
+    `attribute IN (its columns)`, negate: NOT IN; the result is their AND.  tables: an existing (operand_table, clause_ends)
+    pair of the same counts to overwrite in place -- what a captured graph replayed with another query needs; reuse:
+    scratch / out / out_offsets / check of api.bitop_clauses_indexed_device.  Device-resident column_ids cause no host
+    round trip.  Returns (stream, seg_offsets) of the result bitmap."""
+    import torch
+
+    if not predicates:
+        raise ValueError("at least one predicate")
+    sizes = [int(ids.numel()) if torch.is_tensor(ids) else len(ids) for _, _, ids, _ in predicates]
+    if min(sizes) < 1:
+        raise ValueError("a predicate names at least one column")
+    dev = predicates[0][0].device
+    ends, total = [], 0
+    for size, (_, _, _, negate) in zip(sizes, predicates):
+        total += size
+        ends.append(total | (wah.CLAUSE_NEGATE if negate else 0))
+    if tables is None:
+        table = torch.empty((total, 3), dtype=torch.int64, device=dev)
+        clause_ends = torch.empty(len(ends), dtype=torch.int64, device=dev)
+    else:
+        table, clause_ends = tables
+        if tuple(table.shape) != (total, 3) or tuple(clause_ends.shape) != (len(ends),) or clause_ends.dtype != torch.int64:
+            raise ValueError("tables: an int64 [operands, 3] table and an int64 [predicates] tensor of this query's counts")
+    clause_ends.copy_(torch.tensor(ends, dtype=torch.int64))
+    at = 0
+    for size, (stream, seg_offsets, ids, _) in zip(sizes, predicates):
+        column_operand_table(stream, seg_offsets, n_words_per_column, ids, out=table[at: at + size])
+        at += size
+    return wah.bitop_clauses_indexed_device((table, clause_ends), n_words_per_column, **reuse)
+
+
 def compress_column_ranges(compressor, flat, lengths, wait=True):
     """Columns of DIFFERENT lengths (each a multiple of 992 words) stored back to back in `flat`: still one launch.
     Returns (stream, column_offsets) like compress_column_matrix: column c is stream[column_offsets[c] :

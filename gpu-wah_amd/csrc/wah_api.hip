@@ -1302,6 +1302,74 @@ int wah_bitop_list_status(void *d_scratch, uint64_t n_words, uint64_t n_operands
     return wah_bitop_indexed_status(d_scratch, n_words, stream);
 }
 
+// A conjunction of clauses, each the OR of its operands or the complement of it (wah_bitop_list.hip,
+// bitop_clauses_segments_kernel).  Scratch and road as the list call's: one decoded bitmap, then the compress passes.
+static_assert(WAH_CLAUSE_NEGATE == wah::kClauseNegate, "one flag");
+size_t wah_bitop_clauses_scratch_bytes(uint64_t n_words, uint64_t n_operands, uint64_t n_clauses) {
+    (void)n_operands;
+    (void)n_clauses;
+    return bitop_indexed_layout(n_words).total;
+}
+
+int wah_bitop_clauses_indexed_device(uint64_t n_words, uint64_t n_clauses, const uint64_t *d_clause_ends, uint64_t n_operands,
+                                     const wah_bitop_operand *d_operands, uint32_t *d_out, uint64_t out_capacity_words,
+                                     uint64_t *d_out_words, uint64_t *d_out_offsets, void *d_scratch, size_t scratch_bytes, void *stream) {
+    g_err[0] = 0;
+    if (!d_scratch || (reinterpret_cast<uintptr_t>(d_scratch) & 255u)) {
+        set_err("bad scratch pointer");
+        return WAH_ERR_ARG;
+    }
+    if (n_operands < 1 || n_operands > wah::kMaxBitopListOperands || !d_operands || (reinterpret_cast<uintptr_t>(d_operands) & 7u) ||
+        n_words >= (1ull << 40)) {
+        set_err("between 1 and 2^24 operands in an 8-byte aligned table, fewer than 2^40 words");
+        return WAH_ERR_ARG;
+    }
+    if (n_clauses < 1 || n_clauses > n_operands || !d_clause_ends || (reinterpret_cast<uintptr_t>(d_clause_ends) & 7u)) {
+        set_err("between 1 and n_operands clauses in an 8-byte aligned table");
+        return WAH_ERR_ARG;
+    }
+    if (!d_out_words || (n_words && !d_out)) {
+        set_err("null pointer");
+        return WAH_ERR_ARG;
+    }
+    const BitopIndexedLayout l = bitop_indexed_layout(n_words);
+    if (scratch_bytes < l.total) {
+        set_err("scratch too small");
+        return WAH_ERR_WORKSPACE;
+    }
+    char *sc = static_cast<char *>(d_scratch);
+    uint32_t *combined = reinterpret_cast<uint32_t *>(sc + l.bitmap);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint64_t groups = wah_max_compressed_words(n_words);
+    wah::BitopClausesArgs a = {};
+    a.g.first_segment = 0;
+    a.g.n_segments = ceil_div(groups, (uint64_t)wah::kSegGroups);
+    a.g.groups = groups;
+    // (ceil(31 G / 32) words: n_words, or n_words + 1 when the last group has spare bits -- a negated clause sets them, and they
+    //  land in that one word more, which the bitmap area has room for and the compress passes, told n_words, never read)
+    a.g.out_words = wah_decoded_words(groups);
+    a.g.out = combined;
+    a.g.ctrl = reinterpret_cast<uint32_t *>(sc);
+    a.table = reinterpret_cast<const wah::BitopListOperand *>(d_operands);
+    a.clause_ends = d_clause_ends;
+    a.n = (uint32_t)n_operands;
+    a.n_clauses = (uint32_t)n_clauses;
+    hipError_t e = wah::launch_clear(sc, wah::kCtlWords * sizeof(uint32_t), s); // (read by wah_bitop_clauses_status)
+    if (e == hipSuccess) e = wah::launch_bitop_clauses_segments(a, s);
+    if (e != hipSuccess) {
+        set_err("combining pass launch", e);
+        return WAH_ERR_HIP;
+    }
+    return compress_device_impl(combined, nullptr, 0, nullptr, n_words, d_out, out_capacity_words, d_out_words, d_out_offsets,
+                                sc + l.ws_c, l.ws_c_bytes, stream, true);
+}
+
+int wah_bitop_clauses_status(void *d_scratch, uint64_t n_words, uint64_t n_operands, uint64_t n_clauses, void *stream) {
+    (void)n_operands;
+    (void)n_clauses;
+    return wah_bitop_indexed_status(d_scratch, n_words, stream);
+}
+
 // ---------------------------------------------------------------------------
 // host-pointer entry points (the reference's API)
 // ---------------------------------------------------------------------------

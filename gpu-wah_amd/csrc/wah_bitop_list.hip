@@ -266,7 +266,142 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, 8) void bitop_list_segments_k
     for (int s = 0; s < (int)kSteps; ++s) seg_store(st, s, (u32)(64 * s) + lane < nvalid ? acc[64 * s + (int)lane] : 0u); // groups at and behind nvalid: zero
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// wah_bitop_clauses_indexed_device: AND over clauses of (negate ? NOT : ) OR of the clause's operands -- a whole WHERE clause
+// of IN / NOT IN lists over a bitmap index.  The operand table is the list call's, flattened over the clauses; a second
+// table in device memory holds one 64-bit word per clause: the index one past its last operand, bit 63 = negate.
+//
+// The inner level is the list kernel's under OR, unchanged: the LDS accumulator holds the CURRENT clause's OR, the table is
+// walked 64 operands at a time whatever the clauses are, kListDepth batches are in flight.  The outer level is sixteen
+// registers per lane: the result's group 64 s + lane (the layout seg_store wants; an LDS row per step, no bank conflicts),
+// preset to all ones.  When the consumer reaches an operand at or behind the current clause's end the clause is FOLDED --
+// result &= clause ^ (negate ? all ones : 0), accumulator zeroed -- and the next clause begins; the crossing is found from
+// operand numbers, so a clause whose operands were all settled in the gather (its OR is the zeroed accumulator) is folded like
+// any other, by the next operand that has words or behind the last chunk.  Nothing looks at the result before the end: a
+// result that has become all zeros skips nothing, every operand's every segment is checked as in the list kernel.
+//
+// Clause ends reach the wave 64 at a time, one per lane, and are checked where they are loaded, before one of them steers a
+// fold: strictly increasing, at most n_operands (which also refuses every bit besides the index and bit 63), the last one
+// equal to n_operands.  After a bad window nothing folds any more and the launch reports kErrStream.
+constexpr u32 kClauseNever = 0x7FFFFFFFu; // an end no operand number reaches
+
+struct ClauseWindow {
+    u32 v; // clause base + lane: its end (at most 2^24) | negate << 31; kClauseNever: no such clause, or a refused table
+    bool bad;
+};
+__device__ __forceinline__ ClauseWindow clause_window(const u64 *ends, u32 base, u32 n_clauses, u32 n, u32 lane) {
+    const u32 i = base + lane;
+    const bool has = i < n_clauses;
+    u64 e = 0, before = 0;
+    if (has) {
+        const ListGlobalU64 p = (ListGlobalU64)(uintptr_t)ends + i;
+        e = p[0];
+        if (i) before = p[-1];
+    }
+    const u64 end = e & ~kClauseNegate, prev = before & ~kClauseNegate;
+    const bool bad = has && (end > (u64)n || end <= prev || (i + 1u == n_clauses && end != (u64)n));
+    ClauseWindow w;
+    w.bad = __ballot(bad) != 0ull; // wave-uniform
+    w.v = has && !w.bad ? (u32)end | ((e & kClauseNegate) ? 0x80000000u : 0u) : kClauseNever;
+    return w;
+}
+
+__global__ __launch_bounds__(kSegDecodeWaves * 64, 8) void bitop_clauses_segments_kernel(const BitopClausesArgs a) {
+    __shared__ __attribute__((aligned(16))) u32 s_acc[kSegDecodeWaves][kSegGroups];
+    const u32 wave = wave_id(), lane = lane_id();
+    const u64 k = (u64)blockIdx.x * kSegDecodeWaves + wave;
+    if (k >= a.g.n_segments) return;
+    const u64 seg = a.g.first_segment + k;
+    const u64 g0 = seg * kSegGroups;
+    const u32 nvalid = a.g.groups - g0 < kSegGroups ? (u32)(a.g.groups - g0) : kSegGroups;
+    u32 *acc = s_acc[wave];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) reinterpret_cast<uint4 *>(acc)[64 * i + (int)lane] = make_uint4(0u, 0u, 0u, 0u);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+
+    u32 res[kSteps]; // the AND over the clauses folded so far: group 64 s + lane
+#pragma unroll
+    for (int s = 0; s < (int)kSteps; ++s) res[s] = kOnes31;
+    // the current clause (wave-uniform): its number, its window's first clause, its end and flag
+    ClauseWindow win = clause_window(a.clause_ends, 0u, a.n_clauses, a.n, lane);
+    bool table_bad = win.bad;
+    u32 ci = 0, cbase = 0;
+    u32 cur = (u32)__builtin_amdgcn_readlane((int)win.v, 0);
+    // fold the current clause into the result and begin the next one
+    auto fold = [&]() {
+        const u32 flip = (int)cur < 0 ? kOnes31 : 0u;
+#pragma unroll
+        for (int s = 0; s < (int)kSteps; ++s) res[s] &= acc[64 * s + (int)lane] ^ flip;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+#pragma unroll
+        for (int i = 0; i < 4; ++i) reinterpret_cast<uint4 *>(acc)[64 * i + (int)lane] = make_uint4(0u, 0u, 0u, 0u);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        ++ci;
+        if (ci - cbase == 64u) {
+            cbase = ci;
+            win = clause_window(a.clause_ends, cbase, a.n_clauses, a.n, lane);
+            table_bad |= win.bad;
+        }
+        cur = (u32)__builtin_amdgcn_readlane((int)win.v, (int)(ci - cbase));
+    };
+
+    const ListOp m = list_op(1u); // a clause is an OR
+    bool lane_bad = false, empty_word = false;
+    bool sums_ok = true;
+#pragma nounroll
+    for (u32 j0 = 0; j0 < a.n; j0 += 64u) {
+        const ListChunk ch = list_gather(a.table, j0, a.n, seg, nvalid, m.fill, lane);
+        lane_bad |= ch.bad;
+        const u64 live = __ballot(ch.cnt != 0u);
+        ListCursor prod = list_first(live), cons = prod;
+        ListPair q[kListDepth];
+#pragma unroll
+        for (int i = 0; i < kListDepth; ++i) {
+            list_issue(q[i], prod, ch, lane);
+            list_advance(prod, ch, live);
+        }
+        u32 pos = 0;
+#pragma nounroll
+        while (cons.j < 64u) {
+#pragma unroll
+            for (int i = 0; i < kListDepth; ++i) {
+                if (cons.j < 64u) { // wave-uniform
+                    const u32 cnt = (u32)__builtin_amdgcn_readlane((int)ch.cnt, (int)cons.j);
+                    const u32 wi = 128u * cons.b;
+                    if (cons.b == 0u) {
+                        pos = 0u;
+#pragma nounroll
+                        while ((cur & kClauseNever) <= j0 + cons.j) fold(); // this operand begins another clause (or a later one)
+                    }
+                    list_apply_batch(acc, q[i][0], q[i][1], wi, cnt, pos, empty_word, m, lane);
+                    if (wi + 128u >= cnt) sums_ok = sums_ok && pos == nvalid; // the operand's last batch
+                }
+                list_advance(cons, ch, live);
+                list_issue(q[i], prod, ch, lane);
+                list_advance(prod, ch, live);
+            }
+        }
+    }
+    // behind the last operand: the last clause, and in front of it those whose operands had no words to apply
+#pragma nounroll
+    while ((cur & kClauseNever) <= a.n) fold();
+    if (!sums_ok || table_bad || __ballot(lane_bad || empty_word) != 0ull) {
+        if (lane == 0) atomicOr(a.g.ctrl + kCtlError, kErrStream);
+        return;
+    }
+    const SegStore st = seg_store_setup(a.g.out, a.g.out_words, seg, k, lane);
+#pragma unroll
+    for (int s = 0; s < (int)kSteps; ++s) seg_store(st, s, (u32)(64 * s) + lane < nvalid ? res[s] : 0u); // groups at and behind nvalid: zero
+}
+
 } // namespace
+
+hipError_t launch_bitop_clauses_segments(const BitopClausesArgs &a, hipStream_t s) {
+    if (a.g.n_segments == 0) return hipSuccess;
+    const u64 grid = (a.g.n_segments + kSegDecodeWaves - 1) / kSegDecodeWaves;
+    hipLaunchKernelGGL(bitop_clauses_segments_kernel, dim3((unsigned)grid), dim3(kSegDecodeWaves * 64), 0, s, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_bitop_list_segments(const BitopListArgs &a, hipStream_t s) {
     if (a.g.n_segments == 0) return hipSuccess;

@@ -227,6 +227,18 @@ struct BitopListArgs {
 };
 hipError_t launch_bitop_list_segments(const BitopListArgs &a, hipStream_t s);
 
+// wah_bitop_clauses_indexed_device (wah_bitop_list.hip): AND over clauses of (negated) ORs.  table: the flattened operands of
+// all clauses; clause_ends: one word per clause in DEVICE memory, the index one past its last operand | kClauseNegate
+constexpr uint64_t kClauseNegate = 1ull << 63; // WAH_CLAUSE_NEGATE
+struct BitopClausesArgs {
+    SegmentsArgs g;
+    const BitopListOperand *table;
+    const uint64_t *clause_ends;
+    uint32_t n;         // operands
+    uint32_t n_clauses; // 1 .. n
+};
+hipError_t launch_bitop_clauses_segments(const BitopClausesArgs &a, hipStream_t s);
+
 // ... on operands of few words per segment: their runs merged in the compressed domain, one lane per segment
 // (wah_bitop_runs.hip): count pass, scan of the tile totals, write pass
 struct BitopRunsArgs {

@@ -399,6 +399,40 @@ int wah_bitop_list_indexed_device(int op, uint64_t n_words, uint64_t n_operands,
                                   void *d_scratch, size_t scratch_bytes, void *stream);
 int wah_bitop_list_status(void *d_scratch, uint64_t n_words, uint64_t n_operands, void *stream);
 
+/* A whole conjunction of IN / NOT IN lists in ONE call -- `city IN (...) AND age BETWEEN 30 AND 39 AND status NOT IN (...)`:
+ *     result = AND over clauses i of ( negate_i ? NOT (OR of clause i's operands) : (OR of clause i's operands) )
+ * over bitmaps of n_words words, NOT over the bitmap's 32 * n_words bits.  The result is what compress() emits for that
+ * bitmap (ragged ends included; n_words == 0: an empty stream); d_out_offsets (may be NULL) receives its segment index, so
+ * results chain into every indexed call.  Word for word: one clause, not negated, is the list call's WAH_OP_OR; clauses of one
+ * operand each, none negated, its WAH_OP_AND; one positive clause {A} and negated clauses its WAH_OP_ANDNOT with A first; one
+ * negated clause of one operand the complement of a compressed bitmap.
+ *   d_operands: the operands of all clauses back to back, clause 0 first: n_operands entries as for the list call (8-byte
+ *   aligned, 1 <= n_operands <= WAH_BITOP_LIST_MAX_OPERANDS, windows into column matrices allowed, operands may repeat).
+ *   d_clause_ends: n_clauses entries (1 <= n_clauses <= n_operands) in DEVICE memory, 8-byte aligned: the low bits of entry i
+ *   are the index one past clause i's last operand in d_operands (clause 0 starts at 0), bit 63 is WAH_CLAUSE_NEGATE.  The
+ *   ends are strictly increasing (no empty clause) and the last one equals n_operands.
+ * Like the list call it never reads a table on the host, is asynchronous on `stream`, allocates nothing and never
+ * synchronises: a captured graph replayed after BOTH tables were overwritten in place (same counts; other boundaries, flags,
+ * operands) answers the NEW query.  One route: one wavefront per segment ORs the current clause's operands as the list call
+ * does and folds the clause into the running AND, which it keeps in registers, when the walk over the flattened table crosses
+ * the clause's end; one decoded bitmap leaves, and the compress passes run over it.  No intermediate per clause exists.
+ *   d_scratch: wah_bitop_clauses_scratch_bytes(n_words, n_operands, n_clauses) bytes, 256-byte aligned, no initialisation;
+ *   it EQUALS wah_bitop_indexed_scratch_bytes(n_words) for every n_operands and n_clauses.
+ * Errors the host can see come back before any HIP call: n_clauses < 1 or > n_operands, n_operands out of range, a null or
+ * misaligned scratch or table, null outputs, n_words >= 2^40: WAH_ERR_ARG; too small a scratch: WAH_ERR_WORKSPACE (the
+ * argument checks come first).  Everything only the device sees is reported by wah_bitop_clauses_status(), which synchronises
+ * the stream: WAH_ERR_STREAM for everything the list call refuses in an operand, and for a clause table that is not strictly
+ * increasing, has bits set besides the index and WAH_CLAUSE_NEGATE, or does not end at n_operands; WAH_ERR_CAPACITY for too
+ * small an output.  A clause end is checked before it steers anything, and EVERY operand's every segment is checked: a result
+ * that has already become all zeros skips nothing, so the verdict does not depend on the data. */
+#define WAH_CLAUSE_NEGATE (1ull << 63)
+size_t wah_bitop_clauses_scratch_bytes(uint64_t n_words, uint64_t n_operands, uint64_t n_clauses);
+int wah_bitop_clauses_indexed_device(uint64_t n_words, uint64_t n_clauses, const uint64_t *d_clause_ends, uint64_t n_operands,
+                                     const wah_bitop_operand *d_operands, uint32_t *d_out, uint64_t out_capacity_words,
+                                     uint64_t *d_out_words, uint64_t *d_out_offsets, void *d_scratch, size_t scratch_bytes,
+                                     void *stream);
+int wah_bitop_clauses_status(void *d_scratch, uint64_t n_words, uint64_t n_operands, uint64_t n_clauses, void *stream);
+
 /* ------------------------------------------------------------------------- *
  * Benchmark support: synthetic bitmaps generated in HBM (include/wah_gen.h
  * states the bit-exact definition; replaces tests.cpp:42-64), and a plain
