@@ -44,6 +44,21 @@ The operand-list bit operation (wah_bitop_list.hip; list_paths() restates which 
     workgroup
   counts clamped to 2 x 1024               list_apply_batch                       LIST_BAD_COUNTS (refused: tests/test_gpu_switch_points.py)
 
+The walk kernels of wah_aux.hip (checker, index builder, fill merger; the probes are built by tests/_walk.py, proven by
+tests/test_walk_reference.py and run by tests/test_gpu_walk_kernels.py):
+
+  4096 words a tile, 256 threads of 16       walk_load_tile, the position sum       WALK_EDGES (word 16 t, 1024 w, 4096 k and a word
+    words, 4 waves of 1024 (kScanTileWords,    (wave scan + s_wave_sum + tile_base),   inside a thread) x pair_probes, position_probes,
+    kExpandWaves)                              prev from registers / LDS / global      index_probes; END_WORDS (4096 k - 1, 4096 k, + 1)
+  the 16-byte test of the tile load          walk_load_tile's `& 15u`               PLACEMENT_BYTES (0, 4, 8, 12 behind a boundary)
+  1024 groups a segment                      n_cross, n_unmerged, index_kernel      position_probes (q + count = 1024 and 1025),
+                                                                                      pair_probes ("aligned second")
+  a thread / wave / tile keeps nothing       the suffix minima of merge_scatter_    RUN_LENGTHS, run_probes
+                                               kernel, tile_first
+  1024 tiles a round of the merge scan       merge_scan_kernel (s_carry both ways)  SCAN_ROUND_TILE_COUNTS, scan_round_streams
+  no run across 2^29 groups                  merge_dropped (kMergeBlockShift)       BLOCK_MULTIPLES, block_probes
+  offsets_capacity, out_capacity             index_kernel, merge_scan_kernel        the capacity tests of test_gpu_walk_kernels.py
+
 THRESHOLDS restates the constants; tests/test_switch_reference.py reads them out of the sources and fails when they differ,
 naming the probe list that has to move with them.
 
@@ -62,6 +77,11 @@ ends in front of it, every lane is outside cnt): the same groups, the same total
 literals at the same 128 groups (the fast path is that code without the scan).  Libraries built with either change pass
 every test of tests/test_gpu_switch_points.py and tests/test_gpu_bitop_list.py; "fill first" segments of 128 b words and the
 LIST_SEGMENT_WORDS of 128 b are the inputs on which the two versions run different code.
+
+Of the walk kernels: `have_prev` (validate_kernel, merge_load_tile) can be `true` without any change of what they compute --
+walk_load_tile gives the word in front of the stream's first word as 0, a literal, which is no predecessor to merge with; a
+library built that way passes every test of tests/test_gpu_walk_kernels.py.  The merger looks at the word IN FRONT of a fill
+only: two fills of a kind with an empty fill between them both stay (run_probes' last stream).
 
 Pass 2 had a third variant, kPass2Plain (pair_pass2_0..3.inc), for the pairs between kPairSparseBelow and kPairSwizzleFrom.
 Both are 384, no pair reached it, and it is gone: a static_assert in wah_compress_pair.inc and
@@ -84,6 +104,11 @@ PAIR_GROUPS = 2048
 
 # name -> (value, the probe list that has to move when the constant does)
 THRESHOLDS = {
+    "kScanTileWords": (4096, "WALK_EDGES / END_WORDS / SCAN_ROUND_TILE_COUNTS (tests/_walk.py)"),
+    "kExpandWaves": (4, "WALK_EDGES (tests/_walk.py: 64 x this many threads, words per thread and per wave)"),
+    "kMergeBlockShift": (29, "BLOCK_MULTIPLES / block_probes (tests/_walk.py)"),
+    "merge scan tiles": ((1024, 1024), "SCAN_ROUND_TILE_COUNTS / scan_round_streams (tests/_walk.py)"),
+    "walk vector load alignment": (15, "PLACEMENT_BYTES (tests/_walk.py)"),
     "kPairSparseBelow": (384, "PAIR_COUNTS"),
     "WAH_PAIR_SWIZZLE_FROM": (384, "PAIR_COUNTS"),
     "WAH_DT_MAXG": (60, "TILE_TOTALS"),

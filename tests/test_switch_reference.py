@@ -17,6 +17,11 @@ CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
 
 # name -> (file, expression whose group 1 is the value)
 SOURCES = {
+    "kScanTileWords": ("wah_internal.hpp", r"constexpr int kScanTileWords = (\d+);"),
+    "kExpandWaves": ("wah_internal.hpp", r"constexpr int kExpandWaves = (\d+);"),
+    "kMergeBlockShift": ("wah_aux.hip", r"constexpr u32 kMergeBlockShift = (\d+);"),
+    "merge scan tiles": ("wah_aux.hip", r"__launch_bounds__\((\d+)\) void merge_scan_kernel\([\s\S]*?base < a\.n_tiles; base \+= (\d+)\)"),
+    "walk vector load alignment": ("wah_aux.hip", r"\(reinterpret_cast<uintptr_t>\(comp\) & (\d+)u\) == 0 && tile_w0 \+ kScanTileWords <= c_words"),
     "kPairSparseBelow": ("wah_compress_pair.inc", r"constexpr u32 kPairSparseBelow = (\d+);"),
     "WAH_PAIR_SWIZZLE_FROM": ("wah_compress_pair.inc", r"#define WAH_PAIR_SWIZZLE_FROM (\d+)"),
     "WAH_DT_MAXG": ("wah_decode_tile.inc", r"#define WAH_DT_MAXG (\d+)"),
@@ -71,8 +76,9 @@ def check_thresholds(csrc=CSRC):
     """Raises AssertionError naming the constant and the probe list of tests/_switch.py that has to move with it."""
     for name, (value, probes) in sw.THRESHOLDS.items():
         got = _source_value(name, csrc)
+        where = "" if "(tests/" in probes else " (tests/_switch.py)"   # (the walk's probe lists name their own file)
         assert got == value, (f"{name} is {got} in gpu-wah_amd/csrc but tests/_switch.py THRESHOLDS says {value}: the probes no longer "
-                              f"sit on the switch -- move {probes} (tests/_switch.py) with it and update THRESHOLDS")
+                              f"sit on the switch -- move {probes}{where} with it and update THRESHOLDS")
 
 
 def test_thresholds_are_the_sources_own():
@@ -86,16 +92,17 @@ def test_thresholds_are_the_sources_own():
 
 
 def test_a_retuned_threshold_is_noticed(tmp_path):
-    """A copy of the sources with WAH_PAIR_SWIZZLE_FROM / WAH_DT_MAXG / WAH_LIST_DEPTH / kListShortFill / WAH_SEG_WAVES moved
-    by one: the message names the probe list."""
+    """A copy of the sources with WAH_PAIR_SWIZZLE_FROM / WAH_DT_MAXG / WAH_LIST_DEPTH / kListShortFill / WAH_SEG_WAVES /
+    kMergeBlockShift / kScanTileWords / kExpandWaves moved by one: the message names the probe list."""
     for name, probes in (("WAH_PAIR_SWIZZLE_FROM", "PAIR_COUNTS"), ("WAH_DT_MAXG", "TILE_TOTALS"), ("WAH_LIST_DEPTH", "LIST_SCHEDULES"),
-                         ("kListShortFill", "LIST_FILL_GROUPS"), ("WAH_SEG_WAVES", "LIST_SEGMENTS")):
+                         ("kListShortFill", "LIST_FILL_GROUPS"), ("WAH_SEG_WAVES", "LIST_SEGMENTS"), ("kMergeBlockShift", "BLOCK_MULTIPLES"),
+                         ("kScanTileWords", "WALK_EDGES"), ("kExpandWaves", "WALK_EDGES")):
         copy = tmp_path / name
         copy.mkdir()
         for f in os.listdir(CSRC):
             with open(os.path.join(CSRC, f)) as h:
                 text = h.read()
-            text = re.sub(rf"(#define {name} |constexpr u32 {name} = )(\d+)", lambda m: m.group(1) + str(int(m.group(2)) + 1), text)
+            text = re.sub(rf"(#define {name} |constexpr (?:u32|int) {name} = )(\d+)", lambda m: m.group(1) + str(int(m.group(2)) + 1), text)
             (copy / f).write_text(text)
         with pytest.raises(AssertionError, match=rf"{name} is \d+ .* move {probes} "):
             check_thresholds(str(copy))

@@ -7,12 +7,36 @@ sys.path.insert(0, ROOT)
 import numpy as np
 import torch
 from tests import _oracle
+from tests import _walk
 from tests import test_gpu_parity as T
 
 oracle = _oracle.load()
 wah = importlib.import_module("gpu-wah_amd")
 nd = int(sys.argv[1]) if len(sys.argv) > 1 else 100
 nc = int(sys.argv[2]) if len(sys.argv) > 2 else 40
+
+
+def check_stream_calls(st, seed):
+    """wah_validate_device, wah_merge_fills_device and wah_build_index_device against the vectorised references of
+    tests/_walk.py (no limit on the stream's length); returns the number of mismatches."""
+    bad = 0
+    if tuple(wah.validate_device(T._dev(st))) != _walk.report(st):
+        bad += 1
+        print("VALIDATE MISMATCH seed", seed)
+    if not np.array_equal(T._host(wah.merge_fills_device(T._dev(st))), _walk.merged(st)):
+        bad += 1
+        print("MERGE MISMATCH seed", seed)
+    want_index = _walk.index(st)
+    try:
+        got_index = wah.build_index_device(T._dev(st))[0].cpu().numpy()
+    except wah.WahError:
+        got_index = None
+    if (got_index is None) != isinstance(want_index, str) or (got_index is not None and not np.array_equal(got_index, want_index)):
+        bad += 1
+        print("BUILD INDEX MISMATCH (foreign stream) seed", seed)
+    return bad
+
+
 bad = 0
 t0 = time.time()
 for seed in range(nd):
@@ -25,15 +49,14 @@ for seed in range(nd):
         bad += 1
         d = np.nonzero(got[: min(len(got), len(want))] != want[: min(len(got), len(want))])[0]
         print("DECODE MISMATCH seed", seed, "words", len(st), "len", len(got), len(want), "first diffs", d[:5])
-    if len(st) <= 20000:  # the word-by-word Python restatements are slow
-        if tuple(wah.validate_device(T._dev(st))) != T._py_report(st):
-            bad += 1
-            print("VALIDATE MISMATCH seed", seed)
-        if not np.array_equal(T._host(wah.merge_fills_device(T._dev(st))), T._py_merge_fills(st)):
-            bad += 1
-            print("MERGE MISMATCH seed", seed)
+    bad += check_stream_calls(st, seed)
     if seed % 20 == 0:
         print("decode seed", seed, "ok so far, bad =", bad, f"{time.time() - t0:.0f}s", flush=True)
+for seed in range((nd + 19) // 20):  # more than one round of 1024 tiles: the stream-level calls alone (too many groups to decode)
+    rng = np.random.default_rng(70000 + seed)
+    st = T._random_foreign_stream(rng, int(rng.choice([4096 * 1024, 4096 * 1025 + 3, 4096 * 2049 - 1])), max_groups=1 << 46)
+    bad += check_stream_calls(st, f"{seed} (long)")
+    print("long stream seed", seed, "words", len(st), "bad =", bad, f"{time.time() - t0:.0f}s", flush=True)
 for seed in range(nc):
     rng = np.random.default_rng(90000 + seed)
     n = int(rng.choice([1, 31, 991, 992, 993, 992 * 15, 992 * 15 + 1, 992 * 15 * 256 + 17, 992 * 4000]))
