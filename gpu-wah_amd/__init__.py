@@ -46,6 +46,8 @@ from .api import (  # noqa: F401
     bitop_clauses_indexed_device,
     bitop_clause_table,
     CLAUSE_NEGATE,
+    count_device,
+    positions_device,
     merge_fills_device,
     StreamReport,
     gen_uniform_device,

@@ -66,6 +66,10 @@ ABI_SYMBOLS = {
     "wah_bitop_clauses_scratch_bytes": (_sz, [_u64, _u64, _u64]),
     "wah_bitop_clauses_indexed_device": (_int, [_u64, _u64, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
     "wah_bitop_clauses_status": (_int, [_vp, _u64, _u64, _u64, _vp]),
+    "wah_select_scratch_bytes": (_sz, [_u64, _u64]),
+    "wah_count_list_indexed_device": (_int, [_u64, _u64, _vp, _vp, _vp, _sz, _vp]),
+    "wah_positions_indexed_device": (_int, [_u64, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _sz, _vp]),
+    "wah_select_status": (_int, [_vp, _vp]),
     "wah_gen_uniform_device": (_int, [_vp, _u64, _u64, _u64, _vp]),
     "wah_gen_clustered_device": (_int, [_vp, _u64, _u64, _u64, _vp]),
     "wah_copy_device": (_int, [_vp, _vp, _u64, _vp]),
@@ -578,6 +582,78 @@ def bitop_clauses_indexed_device(clauses, n_words, scratch=None, out=None, out_o
         return out, count, out_offsets
     _check(lib().wah_bitop_clauses_status(scratch.data_ptr(), n, k, c, sp), "bitop_clauses_indexed")
     return out[: int(count.item())], out_offsets
+
+
+def count_device(operands_or_table, n_words, scratch=None, counts=None, check=True):
+    """The set bits of every operand, counted in the compressed domain in one call (wah_count_list_indexed_device): an int64
+    tensor [k], entry i for operand i.  operands_or_table: a list of (stream, seg_offsets) pairs, or a ready [k, 3] table
+    (bitop_operand_table, columns.column_operand_table) -- only the device reads it.  The pad bits behind the bitmap's last
+    word are never counted.  scratch / counts: reuse these tensors; check=False: only enqueue (the caller reads
+    wah_select_status later)."""
+    torch = _torch()
+    table = operands_or_table if isinstance(operands_or_table, torch.Tensor) else bitop_operand_table(operands_or_table)
+    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 3 or table.shape[0] < 1 or not table.is_cuda or not table.is_contiguous():
+        raise WahError("an operand table is a contiguous int64 CUDA tensor of shape [k, 3], k >= 1")
+    dev = table.device
+    n, k = int(n_words), int(table.shape[0])
+    if scratch is None:
+        scratch = torch.empty(int(lib().wah_select_scratch_bytes(n, k)), dtype=torch.uint8, device=dev)
+    if counts is None:
+        counts = torch.empty(k, dtype=torch.int64, device=dev)
+    elif counts.dtype != torch.int64 or tuple(counts.shape) != (k,) or not counts.is_contiguous() or counts.device != dev:
+        raise WahError("counts: a contiguous int64 [k] tensor on the table's device")
+    sp = _stream_ptr(torch)
+    _check(lib().wah_count_list_indexed_device(n, k, table.data_ptr(), counts.data_ptr(), scratch.data_ptr(), scratch.numel(), sp),
+           "wah_count_list_indexed_device")
+    if check:
+        _check(lib().wah_select_status(scratch.data_ptr(), sp), "count")
+    return counts
+
+
+def positions_device(stream, seg_offsets, n_words, first=0, limit=None, out=None, scratch=None, check=True):
+    """The positions (row numbers) of the set bits of one indexed compressed bitmap, ascending, without decoding it
+    (wah_positions_indexed_device): those of ranks [first, first + limit).  Returns (positions int64 tensor, total set bits).
+    With limit=None TWO calls are made: the first one asks for the total only, the second one writes into an output of
+    exactly total - first entries.  out: write into this int64 tensor (its length is the limit when none is given);
+    scratch: reuse this tensor.  check=False (needs a limit or an out): only enqueue and return (out, info tensor) with
+    info = [total, number written]."""
+    torch = _torch()
+    _as_words(torch, stream)
+    if seg_offsets.dtype != torch.int64 or not seg_offsets.is_cuda or not seg_offsets.is_contiguous():
+        raise WahError("a segment index is a contiguous int64 CUDA tensor")
+    dev = stream.device
+    n, first = int(n_words), int(first)
+    if first < 0 or (limit is not None and int(limit) < 0):
+        raise WahError("first and limit are not negative")
+    if scratch is None:
+        scratch = torch.empty(int(lib().wah_select_scratch_bytes(n, 1)), dtype=torch.uint8, device=dev)
+    info = torch.empty(2, dtype=torch.int64, device=dev)
+    sp = _stream_ptr(torch)
+
+    def call(dst, cap):
+        _check(lib().wah_positions_indexed_device(n, stream.data_ptr(), stream.numel(), seg_offsets.data_ptr(), first,
+                                                  dst.data_ptr() if cap else None, cap, info.data_ptr(), scratch.data_ptr(),
+                                                  scratch.numel(), sp), "wah_positions_indexed_device")
+
+    if out is not None:
+        if out.dtype != torch.int64 or out.dim() != 1 or not out.is_contiguous() or out.device != dev:
+            raise WahError("out: a contiguous one-dimensional int64 tensor on the stream's device")
+        limit = int(out.numel()) if limit is None else min(int(limit), int(out.numel()))
+    if limit is None:
+        if not check:
+            raise WahError("check=False needs a limit or an out: the output's size comes from a first, checked call")
+        call(info, 0)
+        _check(lib().wah_select_status(scratch.data_ptr(), sp), "positions")
+        limit = max(int(info[0].item()) - first, 0)
+    limit = int(limit)
+    if out is None:
+        out = torch.empty(limit, dtype=torch.int64, device=dev)
+    call(out, limit)
+    if not check:
+        return out, info
+    _check(lib().wah_select_status(scratch.data_ptr(), sp), "positions")
+    total, written = (int(v) for v in info.tolist())
+    return out[:written], total
 
 
 StreamReport = collections.namedtuple(

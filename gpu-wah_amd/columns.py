@@ -148,6 +148,22 @@ def filter_columns(wah, predicates, n_words_per_column, tables=None, **reuse):
     return wah.bitop_clauses_indexed_device((table, clause_ends), n_words_per_column, **reuse)
 
 
+def count_columns(wah, stream, seg_offsets, n_words_per_column, column_ids, **reuse):
+    """The set bits of each selected column of a compress_column_matrix result, in one call (wah_count_list_indexed_device):
+    over all columns of an equality-encoded attribute the `GROUP BY value` histogram.  Arguments as column_operand_table;
+    reuse: scratch / counts / check of api.count_device.  Device-resident column_ids cause no host round trip.  Returns an
+    int64 tensor [len(column_ids)]."""
+    table = column_operand_table(stream, seg_offsets, n_words_per_column, column_ids)
+    return wah.count_device(table, n_words_per_column, **reuse)
+
+
+def select_rows(wah, predicates, n_words_per_column, first=0, limit=None):
+    """`SELECT rowid ... WHERE <conjunction> LIMIT limit OFFSET first` in two calls that never decode a bitmap: filter_columns
+    (predicates as there), then api.positions_device over its result.  Returns (row numbers int64 tensor, matching rows)."""
+    result, result_offsets = filter_columns(wah, predicates, n_words_per_column)
+    return wah.positions_device(result, result_offsets, n_words_per_column, first=first, limit=limit)
+
+
 def compress_column_ranges(compressor, flat, lengths, wait=True):
     """Columns of DIFFERENT lengths (each a multiple of 992 words) stored back to back in `flat`: still one launch.
     Returns (stream, column_offsets) like compress_column_matrix: column c is stream[column_offsets[c] :

@@ -1370,6 +1370,144 @@ int wah_bitop_clauses_status(void *d_scratch, uint64_t n_words, uint64_t n_opera
     return wah_bitop_indexed_status(d_scratch, n_words, stream);
 }
 
+// Set bits counted and listed in the compressed domain (wah_select.hip).  The scratch: control block, then the positions
+// call's rank table (one u64 per segment + 1) and the two upper levels of its scan (one u64 per 4096 entries of the level
+// below) -- it goes with n_words / 992, not with the operands' number or their words.
+namespace {
+struct SelectLayout {
+    uint64_t n_segments;
+    size_t ranks, level1, level2, total;
+};
+SelectLayout select_layout(uint64_t n_words) {
+    SelectLayout l;
+    l.n_segments = ceil_div(wah_max_compressed_words(n_words), (uint64_t)wah::kSegGroups);
+    const uint64_t n0 = l.n_segments + 1, n1 = ceil_div(n0, (uint64_t)wah::kRankChunk), n2 = ceil_div(n1, (uint64_t)wah::kRankChunk);
+    size_t at = wah::kCtlWords * sizeof(uint32_t);
+    l.ranks = at;
+    at += round256(n0 * sizeof(uint64_t));
+    l.level1 = at;
+    at += round256(n1 * sizeof(uint64_t));
+    l.level2 = at;
+    at += round256(n2 * sizeof(uint64_t));
+    l.total = at;
+    return l;
+}
+uint32_t select_pad_bits(uint64_t n_words) { return (uint32_t)(31u * wah_max_compressed_words(n_words) - 32u * n_words); }
+} // namespace
+
+size_t wah_select_scratch_bytes(uint64_t n_words, uint64_t n_operands) {
+    (void)n_operands;
+    return select_layout(n_words).total;
+}
+
+int wah_count_list_indexed_device(uint64_t n_words, uint64_t n_operands, const wah_bitop_operand *d_operands, uint64_t *d_counts,
+                                  void *d_scratch, size_t scratch_bytes, void *stream) {
+    g_err[0] = 0;
+    if (!d_scratch || (reinterpret_cast<uintptr_t>(d_scratch) & 255u)) {
+        set_err("bad scratch pointer");
+        return WAH_ERR_ARG;
+    }
+    if (n_operands < 1 || n_operands > wah::kMaxBitopListOperands || !d_operands || (reinterpret_cast<uintptr_t>(d_operands) & 7u) ||
+        n_words >= (1ull << 40)) {
+        set_err("between 1 and 2^24 operands in an 8-byte aligned table, fewer than 2^40 words");
+        return WAH_ERR_ARG;
+    }
+    if (!d_counts || (reinterpret_cast<uintptr_t>(d_counts) & 7u)) {
+        set_err("null or misaligned counts");
+        return WAH_ERR_ARG;
+    }
+    const SelectLayout l = select_layout(n_words);
+    if (scratch_bytes < l.total) {
+        set_err("scratch too small");
+        return WAH_ERR_WORKSPACE;
+    }
+    char *sc = static_cast<char *>(d_scratch);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    wah::SelectCountArgs a = {};
+    a.table = reinterpret_cast<const wah::BitopListOperand *>(d_operands);
+    a.n_operands = (uint32_t)n_operands;
+    a.pad_bits = select_pad_bits(n_words);
+    a.groups = wah_max_compressed_words(n_words);
+    a.n_segments = l.n_segments;
+    a.counts = d_counts;
+    a.ctrl = reinterpret_cast<uint32_t *>(sc);
+    hipError_t e = wah::launch_clear(sc, wah::kCtlWords * sizeof(uint32_t), s); // (read by wah_select_status)
+    if (e == hipSuccess) e = wah::launch_clear(d_counts, n_operands * sizeof(uint64_t), s);
+    if (e == hipSuccess) e = wah::launch_select_count(a, s);
+    if (e != hipSuccess) {
+        set_err("count pass launch", e);
+        return WAH_ERR_HIP;
+    }
+    return WAH_OK;
+}
+
+int wah_positions_indexed_device(uint64_t n_words, const uint32_t *d_stream, uint64_t stream_words, const uint64_t *d_offsets,
+                                 uint64_t first_rank, uint64_t *d_out, uint64_t out_capacity, uint64_t *d_out_info, void *d_scratch,
+                                 size_t scratch_bytes, void *stream) {
+    g_err[0] = 0;
+    if (!d_scratch || (reinterpret_cast<uintptr_t>(d_scratch) & 255u)) {
+        set_err("bad scratch pointer");
+        return WAH_ERR_ARG;
+    }
+    if (n_words >= (1ull << 40)) {
+        set_err("fewer than 2^40 words");
+        return WAH_ERR_ARG;
+    }
+    if (!d_out_info || (reinterpret_cast<uintptr_t>(d_out_info) & 7u) || (out_capacity && !d_out) || (reinterpret_cast<uintptr_t>(d_out) & 7u)) {
+        set_err("null or misaligned output");
+        return WAH_ERR_ARG;
+    }
+    const SelectLayout l = select_layout(n_words);
+    if (scratch_bytes < l.total) {
+        set_err("scratch too small");
+        return WAH_ERR_WORKSPACE;
+    }
+    char *sc = static_cast<char *>(d_scratch);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    uint64_t *ranks = reinterpret_cast<uint64_t *>(sc + l.ranks);
+    // the operand itself (a null or misaligned stream or index, a length of 2^40 or more) is judged where the table call's
+    // rows are: on the device, before a pointer of it is followed
+    wah::SelectCountArgs c = {};
+    c.one.comp = d_stream;
+    c.one.c_words = stream_words;
+    c.one.offs = d_offsets;
+    c.n_operands = 1;
+    c.pad_bits = select_pad_bits(n_words);
+    c.groups = wah_max_compressed_words(n_words);
+    c.n_segments = l.n_segments;
+    c.counts = ranks;
+    c.ctrl = reinterpret_cast<uint32_t *>(sc);
+    wah::SelectEmitArgs a = {};
+    a.g.comp = d_stream;
+    a.g.c_words = stream_words;
+    a.g.seg_offsets = d_offsets;
+    a.g.n_segments = l.n_segments;
+    a.g.groups = c.groups;
+    a.g.ctrl = c.ctrl;
+    a.ranks = ranks;
+    a.first = first_rank;
+    a.end = first_rank + out_capacity < first_rank ? ~0ull : first_rank + out_capacity;
+    a.capacity = out_capacity;
+    a.out = d_out;
+    a.info = d_out_info;
+    a.pad_bits = c.pad_bits;
+    hipError_t e = wah::launch_clear(sc, wah::kCtlWords * sizeof(uint32_t), s); // (read by wah_select_status)
+    if (e == hipSuccess) e = wah::launch_select_count(c, s);
+    if (e == hipSuccess)
+        e = wah::launch_select_rank_scan(ranks, l.n_segments, reinterpret_cast<uint64_t *>(sc + l.level1), reinterpret_cast<uint64_t *>(sc + l.level2), s);
+    if (e == hipSuccess) e = wah::launch_select_emit(a, s);
+    if (e != hipSuccess) {
+        set_err("positions launch", e);
+        return WAH_ERR_HIP;
+    }
+    return WAH_OK;
+}
+
+int wah_select_status(void *d_scratch, void *stream) {
+    if (!d_scratch) return WAH_ERR_ARG;
+    return read_status(d_scratch, stream);
+}
+
 // ---------------------------------------------------------------------------
 // host-pointer entry points (the reference's API)
 // ---------------------------------------------------------------------------

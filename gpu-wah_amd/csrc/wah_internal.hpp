@@ -259,6 +259,35 @@ struct BitopRunsArgs {
 };
 hipError_t launch_bitop_runs(const BitopRunsArgs &a, hipStream_t s);
 
+// wah_count_list_indexed_device / wah_positions_indexed_device (wah_select.hip): set bits counted and listed in the compressed
+// domain.  The count pass: per table row (table != nullptr: counts has n_operands entries, cleared by the caller, added into)
+// or per segment of the one operand `one` (counts has n_segments entries, every one stored).
+struct SelectCountArgs {
+    const BitopListOperand *table;
+    BitopListOperand one;
+    uint32_t n_operands;
+    uint32_t pad_bits;   // 31 G - 32 n_words: bits of the bitmap's last group that lie behind the bitmap (0 .. 30)
+    uint64_t groups, n_segments;
+    uint64_t *counts;
+    uint32_t *ctrl;
+};
+hipError_t launch_select_count(const SelectCountArgs &a, hipStream_t s);
+// the rank table's scan: chunks of this many entries, one entry per chunk a level up
+constexpr uint32_t kRankChunk = 4096;
+hipError_t launch_select_rank_scan(uint64_t *ranks, uint64_t n_segments, uint64_t *level1, uint64_t *level2, hipStream_t s);
+// the emit pass: g = stream, index, geometry and control block of the one operand (first_segment, out, out_words not used)
+constexpr uint32_t kSelectStageSlots = 64 * 31; // 16-bit LDS slots per wavefront: the set bits of one step of 64 groups
+struct SelectEmitArgs {
+    SegmentsArgs g;
+    const uint64_t *ranks; // n_segments + 1: set bits in front of every segment, then the total
+    uint64_t first, end;   // the window of ranks (end = first + capacity, saturating)
+    uint64_t capacity;
+    uint64_t *out;         // capacity entries
+    uint64_t *info;        // [0] total, [1] written
+    uint32_t pad_bits;
+};
+hipError_t launch_select_emit(const SelectEmitArgs &a, hipStream_t s);
+
 // wah_bitop_device: what the operands' decodes left behind, checked on the device before the combining pass
 struct PairCheck {
     const uint64_t *info_a, *info_b; // [decoded words, groups] of the two operands

@@ -433,6 +433,54 @@ int wah_bitop_clauses_indexed_device(uint64_t n_words, uint64_t n_clauses, const
                                      void *stream);
 int wah_bitop_clauses_status(void *d_scratch, uint64_t n_words, uint64_t n_operands, uint64_t n_clauses, void *stream);
 
+/* What a query wants from a result bitmap, WITHOUT decoding it: how many bits it has set (COUNT(*)) and which ones (row
+ * numbers, with LIMIT / OFFSET).  A bitmap of n_words words has its bits at positions p = 32 * word + bit, LSB first; group g,
+ * bit j, of its stream is position 31 * g + j.  "Set bits" are the positions p < 32 * n_words whose bit is 1: the 0 to 30 pad
+ * bits of the last group (31 * G - 32 * n_words, G = wah_max_compressed_words(n_words)) are never counted or listed, even in a
+ * hand-built stream that sets them -- by a last literal with pad bits, or by a one-fill that covers the last group
+ * (compress() never sets them).  So a count equals the popcount of the first n_words decoded words, for every accepted stream.
+ * Operands are indexed streams of compress() for bitmaps of n_words words, exactly as for wah_bitop_list_indexed_device, and
+ * the same things are refused with WAH_ERR_STREAM, reported by wah_select_status(), which synchronises the stream: a null or
+ * misaligned stream or index, a length of 2^40 or more, an index range outside stream_words, a segment whose words do not make
+ * up exactly its groups, an empty fill.  An entry is checked before a pointer of it is followed, an index range before the
+ * stream is read through it, and EVERY segment of every operand is checked, so the verdict does not depend on the data.
+ *
+ * wah_count_list_indexed_device: d_counts receives n_operands uint64, the set bits of each operand; entry i belongs to table
+ * row i.  Over the columns of an equality-encoded attribute that is the GROUP BY histogram, over results of the clause call a
+ * batch of COUNT(*)s.  d_operands as for the list call (8-byte aligned, 1 <= n_operands <= WAH_BITOP_LIST_MAX_OPERANDS,
+ * operands may repeat, windows into column matrices allowed).  The call clears d_counts itself.  The table is read only by the
+ * device: the call is asynchronous on `stream`, allocates nothing and never synchronises, and a captured graph replayed after
+ * the table was overwritten in place counts the NEW selection.  n_words == 0: all counts 0.  Work is shared out by (operand,
+ * segment) -- one operand of a long bitmap and thousands of short ones both fill the chip --; words are counted where they lie (a literal: its popcount; a one-fill: 31 bits per group; a
+ * zero-fill: nothing), so the cost goes with the operands' words, not with n_operands x n_words.  A refused operand's count
+ * is unspecified.
+ *
+ * wah_positions_indexed_device: ONE operand, given by host arguments (a window into a column matrix: d_offsets points into the
+ * matrix index at the column's first segment, stream_words is the whole stream's length).  Writes the positions of the set
+ * bits of ranks [first_rank, first_rank + out_capacity) to d_out[0 ..), ascending, as uint64; d_out_info[0] receives the total
+ * of set bits, d_out_info[1] the number written, min(max(total - first_rank, 0), out_capacity).  A window that is too small is
+ * not an error (LIMIT / OFFSET); nothing is written at or behind d_out[out_capacity].  out_capacity == 0 with a null d_out is
+ * allowed and gives the total only.  Three steps, none of which waits for another workgroup: the count pass above with one
+ * count per segment, a multi-level prefix sum of those, and one wavefront per segment that returns at once when its ranks miss
+ * the window and otherwise stages its bits' positions in LDS and stores them 64 consecutive entries at a time.  A refused
+ * stream writes nothing to d_out and zeros to d_out_info.
+ *
+ *   d_scratch: wah_select_scratch_bytes(n_words, n_operands) bytes, 256-byte aligned, no initialisation.  The size is a
+ *   multiple of 256, never 0, and grows with n_words only: the control words, one uint64 per segment of 992 words + 1 (the
+ *   positions call's rank table), and one uint64 per 4096 of those for each of the two upper levels of its prefix sum.
+ *   Nothing in it goes with n_operands; one scratch serves both calls.
+ * Errors the host can see come back before any HIP call, argument checks first: a null or misaligned scratch (256 B), table,
+ * d_counts, d_out or d_out_info (8 B), n_operands out of range, n_words >= 2^40: WAH_ERR_ARG; too small a scratch:
+ * WAH_ERR_WORKSPACE.  wah_select_status(NULL, ...): WAH_ERR_ARG. */
+size_t wah_select_scratch_bytes(uint64_t n_words, uint64_t n_operands);
+int wah_count_list_indexed_device(uint64_t n_words, uint64_t n_operands, const wah_bitop_operand *d_operands,
+                                  uint64_t *d_counts, void *d_scratch, size_t scratch_bytes, void *stream);
+int wah_positions_indexed_device(uint64_t n_words, const uint32_t *d_stream, uint64_t stream_words,
+                                 const uint64_t *d_offsets, uint64_t first_rank, uint64_t *d_out,
+                                 uint64_t out_capacity, uint64_t *d_out_info, void *d_scratch,
+                                 size_t scratch_bytes, void *stream);
+int wah_select_status(void *d_scratch, void *stream);
+
 /* ------------------------------------------------------------------------- *
  * Benchmark support: synthetic bitmaps generated in HBM (include/wah_gen.h
  * states the bit-exact definition; replaces tests.cpp:42-64), and a plain
