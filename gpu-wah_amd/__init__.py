@@ -47,6 +47,7 @@ from .api import (  # noqa: F401
     bitop_clause_table,
     CLAUSE_NEGATE,
     count_device,
+    count_masked_device,
     positions_device,
     merge_fills_device,
     StreamReport,

@@ -68,6 +68,7 @@ ABI_SYMBOLS = {
     "wah_bitop_clauses_status": (_int, [_vp, _u64, _u64, _u64, _vp]),
     "wah_select_scratch_bytes": (_sz, [_u64, _u64]),
     "wah_count_list_indexed_device": (_int, [_u64, _u64, _vp, _vp, _vp, _sz, _vp]),
+    "wah_count_masked_indexed_device": (_int, [_u64, _u64, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
     "wah_positions_indexed_device": (_int, [_u64, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _sz, _vp]),
     "wah_select_status": (_int, [_vp, _vp]),
     "wah_gen_uniform_device": (_int, [_vp, _u64, _u64, _u64, _vp]),
@@ -607,6 +608,39 @@ def count_device(operands_or_table, n_words, scratch=None, counts=None, check=Tr
            "wah_count_list_indexed_device")
     if check:
         _check(lib().wah_select_status(scratch.data_ptr(), sp), "count")
+    return counts
+
+
+def count_masked_device(masks, operands, n_words, scratch=None, counts=None, check=True):
+    """The set bits every mask shares with every operand, counted in one call without decoding an operand or writing a bitmap
+    (wah_count_masked_indexed_device): an int64 tensor [m, k], entry [i, j] the popcount of mask i AND operand j -- the GROUP BY
+    histogram under a WHERE filter, a cross-tab.  masks / operands: each a list of (stream, seg_offsets) pairs, or a ready
+    [m, 3] / [k, 3] table (bitop_operand_table, columns.column_operand_table) -- only the device reads them; m * k <= 2^24.  The
+    pad bits behind the bitmap's last word are never counted.  scratch / counts: reuse these tensors (scratch as for
+    count_device); check=False: only enqueue (the caller reads wah_select_status later)."""
+    torch = _torch()
+    tables = []
+    for what in (masks, operands):
+        table = what if isinstance(what, torch.Tensor) else bitop_operand_table(what)
+        if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 3 or table.shape[0] < 1 or not table.is_cuda or not table.is_contiguous():
+            raise WahError("a mask or operand table is a contiguous int64 CUDA tensor of shape [k, 3], k >= 1")
+        tables.append(table)
+    mt, ot = tables
+    dev = ot.device
+    if mt.device != dev:
+        raise WahError("the mask table and the operand table are on one device")
+    n, m, k = int(n_words), int(mt.shape[0]), int(ot.shape[0])
+    if scratch is None:
+        scratch = torch.empty(int(lib().wah_select_scratch_bytes(n, k)), dtype=torch.uint8, device=dev)
+    if counts is None:
+        counts = torch.empty((m, k), dtype=torch.int64, device=dev)
+    elif counts.dtype != torch.int64 or tuple(counts.shape) != (m, k) or not counts.is_contiguous() or counts.device != dev:
+        raise WahError("counts: a contiguous int64 [m, k] tensor on the tables' device")
+    sp = _stream_ptr(torch)
+    _check(lib().wah_count_masked_indexed_device(n, m, mt.data_ptr(), k, ot.data_ptr(), counts.data_ptr(), scratch.data_ptr(),
+                                                 scratch.numel(), sp), "wah_count_masked_indexed_device")
+    if check:
+        _check(lib().wah_select_status(scratch.data_ptr(), sp), "count_masked")
     return counts
 
 

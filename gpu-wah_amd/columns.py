@@ -157,6 +157,54 @@ def count_columns(wah, stream, seg_offsets, n_words_per_column, column_ids, **re
     return wah.count_device(table, n_words_per_column, **reuse)
 
 
+def count_columns_where(wah, predicates, stream, seg_offsets, n_words_per_column, column_ids, **reuse):
+    """`SELECT b, COUNT(*) WHERE <conjunction> GROUP BY b` in two calls that decode no bitmap: filter_columns (predicates as
+    there), then the set bits each selected column of attribute b's matrix (stream, seg_offsets, column_ids as
+    column_operand_table) shares with its result (wah_count_masked_indexed_device).  With device-resident column_ids there is no
+    host round trip between the two: the filter is only enqueued, the mask row names its output buffer with the buffer's
+    capacity as the length -- the index it wrote bounds what is read -- and one check comes at the end.  reuse: scratch / counts
+    ([1, len(column_ids)]) / check of api.count_masked_device, and filter=dict(...) with tables / scratch / out / out_offsets
+    of filter_columns (check=False reads no status at all: pass the filter's scratch to read its own later).  Returns an int64
+    tensor [len(column_ids)]."""
+    import torch
+
+    filter_reuse = dict(reuse.pop("filter", None) or {})
+    check = reuse.pop("check", True)
+    n = int(n_words_per_column)
+    table = column_operand_table(stream, seg_offsets, n, column_ids)
+    dev = table.device
+    if filter_reuse.get("scratch") is None:
+        total = sum(int(ids.numel()) if torch.is_tensor(ids) else len(ids) for _, _, ids, _ in predicates)
+        filter_reuse["scratch"] = torch.empty(int(wah.lib().wah_bitop_clauses_scratch_bytes(n, total, len(predicates))), dtype=torch.uint8, device=dev)
+    filter_reuse["check"] = False
+    out, _, out_offsets = filter_columns(wah, predicates, n, **filter_reuse)
+    mask = torch.empty((1, 3), dtype=torch.int64, device=dev)
+    mask[0, 0] = out.data_ptr()
+    mask[0, 1] = out.numel()
+    mask[0, 2] = out_offsets.data_ptr()
+    scratch = reuse.pop("scratch", None)
+    if scratch is None:
+        scratch = torch.empty(int(wah.lib().wah_select_scratch_bytes(n, table.shape[0])), dtype=torch.uint8, device=dev)
+    counts = wah.count_masked_device(mask, table, n, scratch=scratch, check=False, **reuse)
+    if check:
+        from . import api
+
+        sp = api._stream_ptr(torch)
+        api._check(wah.lib().wah_bitop_clauses_status(filter_reuse["scratch"].data_ptr(), n, 1, 1, sp), "count_columns_where: the filter")
+        api._check(wah.lib().wah_select_status(scratch.data_ptr(), sp), "count_columns_where: the count")
+    return counts.view(-1)
+
+
+def crosstab_columns(wah, a, b, n_words_per_column, **reuse):
+    """`SELECT a, b, COUNT(*) GROUP BY a, b` over two equality-encoded attributes in one call (wah_count_masked_indexed_device):
+    a and b are each (stream, seg_offsets, column_ids) of a compress_column_matrix result of its own (arguments as
+    column_operand_table; one column length); the columns of a are the masks, those of b the operands.  reuse: scratch / counts
+    / check of api.count_masked_device.  Returns an int64 tensor [len(a's column_ids), len(b's column_ids)]."""
+    masks = column_operand_table(a[0], a[1], n_words_per_column, a[2])
+    operands = column_operand_table(b[0], b[1], n_words_per_column, b[2])
+    return wah.count_masked_device(masks, operands, n_words_per_column, **reuse)
+
+
 def select_rows(wah, predicates, n_words_per_column, first=0, limit=None):
     """`SELECT rowid ... WHERE <conjunction> LIMIT limit OFFSET first` in two calls that never decode a bitmap: filter_columns
     (predicates as there), then api.positions_device over its result.  Returns (row numbers int64 tensor, matching rows)."""

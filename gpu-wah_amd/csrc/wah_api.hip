@@ -1441,6 +1441,51 @@ int wah_count_list_indexed_device(uint64_t n_words, uint64_t n_operands, const w
     return WAH_OK;
 }
 
+int wah_count_masked_indexed_device(uint64_t n_words, uint64_t n_masks, const wah_bitop_operand *d_masks, uint64_t n_operands,
+                                    const wah_bitop_operand *d_operands, uint64_t *d_counts, void *d_scratch, size_t scratch_bytes,
+                                    void *stream) {
+    g_err[0] = 0;
+    if (!d_scratch || (reinterpret_cast<uintptr_t>(d_scratch) & 255u)) {
+        set_err("bad scratch pointer");
+        return WAH_ERR_ARG;
+    }
+    if (n_masks < 1 || n_masks > wah::kMaxBitopListOperands || n_operands < 1 || n_operands > wah::kMaxBitopListOperands ||
+        n_masks * n_operands > wah::kMaxBitopListOperands || !d_masks || (reinterpret_cast<uintptr_t>(d_masks) & 7u) || !d_operands ||
+        (reinterpret_cast<uintptr_t>(d_operands) & 7u) || n_words >= (1ull << 40)) {
+        set_err("at least one mask and one operand, at most 2^24 pairs, in 8-byte aligned tables, fewer than 2^40 words");
+        return WAH_ERR_ARG;
+    }
+    if (!d_counts || (reinterpret_cast<uintptr_t>(d_counts) & 7u)) {
+        set_err("null or misaligned counts");
+        return WAH_ERR_ARG;
+    }
+    const SelectLayout l = select_layout(n_words);
+    if (scratch_bytes < l.total) {
+        set_err("scratch too small");
+        return WAH_ERR_WORKSPACE;
+    }
+    char *sc = static_cast<char *>(d_scratch);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    wah::CountMaskedArgs a = {};
+    a.masks = reinterpret_cast<const wah::BitopListOperand *>(d_masks);
+    a.operands = reinterpret_cast<const wah::BitopListOperand *>(d_operands);
+    a.n_masks = (uint32_t)n_masks;
+    a.n_operands = (uint32_t)n_operands;
+    a.pad_bits = select_pad_bits(n_words);
+    a.groups = wah_max_compressed_words(n_words);
+    a.n_segments = l.n_segments;
+    a.counts = d_counts;
+    a.ctrl = reinterpret_cast<uint32_t *>(sc);
+    hipError_t e = wah::launch_clear(sc, wah::kCtlWords * sizeof(uint32_t), s); // (read by wah_select_status)
+    if (e == hipSuccess) e = wah::launch_clear(d_counts, n_masks * n_operands * sizeof(uint64_t), s);
+    if (e == hipSuccess) e = wah::launch_count_masked(a, s);
+    if (e != hipSuccess) {
+        set_err("masked count launch", e);
+        return WAH_ERR_HIP;
+    }
+    return WAH_OK;
+}
+
 int wah_positions_indexed_device(uint64_t n_words, const uint32_t *d_stream, uint64_t stream_words, const uint64_t *d_offsets,
                                  uint64_t first_rank, uint64_t *d_out, uint64_t out_capacity, uint64_t *d_out_info, void *d_scratch,
                                  size_t scratch_bytes, void *stream) {

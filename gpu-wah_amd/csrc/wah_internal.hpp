@@ -272,6 +272,19 @@ struct SelectCountArgs {
     uint32_t *ctrl;
 };
 hipError_t launch_select_count(const SelectCountArgs &a, hipStream_t s);
+// wah_count_masked_indexed_device (wah_select.hip): the set bits of (mask AND operand) for every pair of a mask table and an
+// operand table, no operand decoded and no bitmap written.  counts: n_masks x n_operands entries, row-major, cleared by the
+// caller, added into.
+struct CountMaskedArgs {
+    const BitopListOperand *masks, *operands;
+    uint32_t n_masks, n_operands; // n_masks * n_operands <= kMaxBitopListOperands
+    uint32_t pad_bits;            // as SelectCountArgs
+    uint32_t chunk;               // operands that share one mask image, 1 .. 64 (set by the launcher)
+    uint64_t groups, n_segments;
+    uint64_t *counts;
+    uint32_t *ctrl;
+};
+hipError_t launch_count_masked(const CountMaskedArgs &a, hipStream_t s);
 // the rank table's scan: chunks of this many entries, one entry per chunk a level up
 constexpr uint32_t kRankChunk = 4096;
 hipError_t launch_select_rank_scan(uint64_t *ranks, uint64_t n_segments, uint64_t *level1, uint64_t *level2, hipStream_t s);

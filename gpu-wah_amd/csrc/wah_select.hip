@@ -3,7 +3,10 @@
 // equality-encoded attribute) and which ones (wah_positions_indexed_device: the positions of the set bits of a window of ranks,
 // in ascending order -- SELECT rowid ... LIMIT / OFFSET).  The reference has no counterpart.
 //
-// Three kinds of launches, and no workgroup of any of them waits for another:
+// and how many bits it shares with each of many others (wah_count_masked_indexed_device: the popcount of mask AND operand for every
+// pair of two tables -- GROUP BY under a WHERE filter, the cross-tab of two attributes).
+//
+// Four kinds of launches, and no workgroup of any of them waits for another:
 //   select_count_kernel   (operand, segment) pairs shared out over the launch's wavefronts in contiguous runs.  The table row is checked before its index pointer
 //                         is followed, the index range (seg_range) before the stream is read through it; the segment's words
 //                         are loaded two per lane per batch of 128 (seg_load_words) and counted where they lie -- a literal is
@@ -13,6 +16,12 @@
 //                         its run and adds into the operand's count with a 64-bit vector atomic when the operand changes, a
 //                         workgroup merges its four runs' ends first; the positions call stores every segment's count into its
 //                         rank table instead.  The cost goes with the operands' words.
+//   count_masked_kernel   (mask, chunk of up to 64 operands, segment) items shared out in the same contiguous runs.  The mask's segment
+//                         is decoded (seg_mark / seg_group) into a per-wavefront LDS image M[1024] of its groups, pad bits cleared,
+//                         beside P[1024], the exclusive prefix sum of their popcounts; the words of the chunk's operands are counted
+//                         where they lie against it, lane l keeping the l-th operand's count: a literal at group lo is popcount(x & M[lo]), a one-fill of n groups P[lo + n] - P[lo], a
+//                         zero-fill nothing.  A mask segment of one fill word needs no image: zeros count nothing, ones count
+//                         as select_count_kernel does.  LDS: 10 KiB per wavefront, 40 960 B per workgroup: four workgroups per CU.
 //   rank_reduce_kernel /  the exclusive prefix sum of the rank table (one u64 per segment, + 1 for the total): chunks of 4096
 //   rank_scan_kernel      entries, their totals one level up (two levels up for more than 2^24 segments), scanned there, then
 //                         every chunk scans itself in place on top of what lies in front of it.  The top level is at most
@@ -180,6 +189,222 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, 8) void select_count_kernel(c
     }
 }
 
+// ---- counts under a mask -----------------------------------------------------------------------------------------------------
+__device__ __forceinline__ SelectRow table_row(const BitopListOperand *table, u64 j) {
+    const SelConstU64 e = (SelConstU64)(uintptr_t)(table + j);
+    SelectRow r;
+    r.comp = e[0];
+    r.c_words = e[1];
+    r.offs = e[2];
+    return r;
+}
+
+// what a wavefront knows of the mask segment it holds
+constexpr u32 kMaskNone = 0, kMaskZeros = 1, kMaskOnes = 2, kMaskImage = 3, kMaskBad = 4;
+// LDS of one wavefront: P (2 KiB; its first KiB are the mark phase's flags, which are in registers before P is written), the mark
+// phase's words (4 KiB), M (4 KiB).  Four wavefronts: 40 960 B, a quarter of a CU's 160 KiB to the byte -- which is why P has no
+// entry 1024 (the total is a scalar) and the workgroup's merge at the end borrows wavefront 0's M.
+constexpr u32 kMaskedP = 0, kMaskedWords = 2048, kMaskedM = 2048 + 4096, kMaskedWaveLds = 2048 + 4096 + 4096;
+
+// the bits an operand word of n groups at group lo shares with the mask image
+__device__ __forceinline__ u32 image_bits(u32 x, u32 n, u32 lo, const u32 *M, const unsigned short *P, u32 p_total) {
+    if (n == 0u) return 0u; // (no word here, or an empty fill: refused)
+    if ((int)x >= 0) return (u32)__builtin_popcount(x & M[min(lo, kSegGroups - 1u)]);
+    if ((x & kFillOne) != kFillOne) return 0u;
+    // (a corrupt stream's positions may lie behind the segment: it is refused, and nothing is read out of bounds)
+    const u32 hi = lo + n;
+    const u32 p_hi = hi >= kSegGroups ? p_total : (u32)P[hi], p_lo = lo >= kSegGroups ? p_total : (u32)P[lo];
+    return p_hi - p_lo;
+}
+
+// counts[i * n_operands + j] += the set bits of mask i AND operand j.  A work item is (mask i, chunk c of a.chunk <= 64 consecutive
+// operands, segment): the mask segment's image is made once and serves the chunk's operands one after the other, lane l of the
+// wavefront keeping the count of the chunk's l-th operand.  The items, ordered (i, c, segment), are shared out in contiguous runs
+// exactly as select_count_kernel shares its pairs out, and for the same reason: a wavefront sums its run and issues its atomics --
+// one wave instruction over the chunk's consecutive counts -- when (i, c) changes, the workgroup's run ends merged in LDS first.
+// (The first version took (mask, operand, segment) triples in the order (i, j, segment) and made the image anew for every
+// operand: 3.5 - 5 us per triple and wavefront, nearly all of it the image: DESIGN 5.11.)  Consecutive items share the mask
+// segment only in bitmaps of one segment; then the image is kept.  EVERY segment of every mask and operand is checked, also under
+// a mask segment of zeros: the verdict does not depend on the data.
+__global__ __launch_bounds__(kSegDecodeWaves * 64) void count_masked_kernel(const CountMaskedArgs a) {
+    __shared__ __attribute__((aligned(16))) unsigned char s_lds[kSegDecodeWaves][kMaskedWaveLds];
+    const u32 wave = wave_id(), lane = lane_id();
+    unsigned char *flag = s_lds[wave] + kMaskedP;
+    unsigned short *P = reinterpret_cast<unsigned short *>(s_lds[wave] + kMaskedP);
+    u32 *words = reinterpret_cast<u32 *>(s_lds[wave] + kMaskedWords);
+    u32 *M = reinterpret_cast<u32 *>(s_lds[wave] + kMaskedM);
+    const u64 n_chunks = ((u64)a.n_operands + a.chunk - 1) / a.chunk;
+    const u64 n_items = (u64)a.n_masks * n_chunks * a.n_segments;
+    const u64 n_waves = (u64)gridDim.x * kSegDecodeWaves;
+    const u64 per = (n_items + n_waves - 1) / n_waves;
+    const u64 w = (u64)blockIdx.x * kSegDecodeWaves + wave;
+    const u64 begin = w * per < n_items ? w * per : n_items, end = begin + per < n_items ? begin + per : n_items;
+    const u32 pad_mask = kOnes31 >> a.pad_bits;
+    u64 item = begin;
+    u64 q = begin / a.n_segments; // the pairs' group: i * n_chunks + c
+    u64 seg = begin - q * a.n_segments;
+    u64 i = q / n_chunks, c = q - i * n_chunks;
+    u32 jj = 0; // the operand inside the chunk
+    u64 acc = 0; // lane l: operand c * chunk + l under mask i
+    bool refused = false;
+    u32 kind = kMaskNone, p_total = 0;
+    u64 img_i = 0, img_seg = 0;
+    SelectRow mrow = {}, orow = {}, next_mrow = {}, next_orow = {};
+    SegRange next_m = {}, next_o = {};
+    if (begin < end) {
+        next_mrow = table_row(a.masks, i);
+        next_orow = table_row(a.operands, c * a.chunk);
+        next_m = select_range(next_mrow, a.groups, seg);
+        next_o = select_range(next_orow, a.groups, seg);
+    }
+#pragma nounroll
+    while (item < end) {
+        const SegRange mrg = next_m, org = next_o;
+        mrow = next_mrow;
+        orow = next_orow;
+        const bool fresh = jj == 0u && (kind == kMaskNone || i != img_i || seg != img_seg); // wave-uniform
+        SegmentsArgs msa = {}, osa = {};
+        msa.comp = reinterpret_cast<const u32 *>((uintptr_t)mrow.comp);
+        osa.comp = reinterpret_cast<const u32 *>((uintptr_t)orow.comp);
+        u32 m0[kSegBatches], m1[kSegBatches], x0[kSegBatches], x1[kSegBatches];
+        if (fresh) seg_load_words(msa, mrg, m0, m1, lane);
+        seg_load_words(osa, org, x0, x1, lane);
+        // what comes behind this operand's segment: the chunk's next operand, or the next item
+        const u64 j0 = c * a.chunk;
+        const u32 jn = a.n_operands - j0 < a.chunk ? (u32)(a.n_operands - j0) : a.chunk;
+        const bool last_jj = jj + 1u == jn;
+        const bool last_seg = seg + 1 == a.n_segments;
+        const bool last_c = c + 1 == n_chunks;
+        const u64 seg_next = last_seg ? 0ull : seg + 1, q_next = last_seg ? q + 1 : q;
+        const u64 c_next = !last_seg ? c : last_c ? 0ull : c + 1, i_next = last_seg && last_c ? i + 1 : i;
+        if (!last_jj) {
+            next_orow = table_row(a.operands, j0 + jj + 1u);
+            next_o = select_range(next_orow, a.groups, seg);
+        } else if (item + 1 < end) {
+            next_orow = table_row(a.operands, c_next * a.chunk);
+            if (i_next != i) next_mrow = table_row(a.masks, i_next);
+            next_m = select_range(next_mrow, a.groups, seg_next);
+            next_o = select_range(next_orow, a.groups, seg_next);
+        }
+        if (fresh) {
+            img_i = i;
+            img_seg = seg;
+            const u32 first = (u32)__builtin_amdgcn_readfirstlane((int)m0[0]); // lane 0 holds the segment's first word
+            if (!mrg.bad && mrg.cnt == 1u && (first & kFillZero) && (first & kCountMask) == mrg.nvalid) {
+                kind = (first & kFillOne) == kFillOne ? kMaskOnes : kMaskZeros; // one fill over the segment: no image
+            } else if (!seg_mark(mrg, m0, m1, flag, words, lane)) {
+                kind = kMaskBad;
+            } else {
+                kind = kMaskImage;
+                const uint4 fq = reinterpret_cast<const uint4 *>(flag)[lane];
+                const u32 f[4] = {fq.x, fq.y, fq.z, fq.w};
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // P goes over the flags
+                u32 before = 0xFFFFFFFFu, run = 0;
+                // the bitmap's last group loses its pad bits
+                const u32 pad_group = last_seg ? mrg.nvalid - 1u : 0xFFFFFFFFu;
+#pragma unroll
+                for (int s = 0; s < (int)kSteps; ++s) {
+                    u32 grp = seg_group(s, f, before, words, mrg.cnt, mrg.nvalid, lane);
+                    const u32 g = (u32)(64 * s) + lane;
+                    if (g == pad_group) grp &= pad_mask;
+                    const u32 cnt = (u32)__builtin_popcount(grp);
+                    const u32 incl = wave_scan_incl32(cnt);
+                    M[g] = grp;
+                    P[g] = (unsigned short)(run + incl - cnt); // at most 31 744
+                    run += (u32)__builtin_amdgcn_readlane((int)incl, 63);
+                }
+                p_total = run;
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            }
+        }
+        // the operand's words, where they lie
+        const u32 last = last_seg ? org.cnt - 1u : 0xFFFFFFFFu;
+        u32 bits = 0, grps = 0;
+        bool empty_word = false;
+        if (kind == kMaskImage) { // wave-uniform
+            u32 pos = 0; // groups covered by the batches so far
+#pragma unroll
+            for (int b = 0; b < kSegBatches; ++b) {
+                if (128u * b < org.cnt) { // wave-uniform
+                    const u32 i0 = 128u * b + 2u * lane;
+                    const bool in0 = i0 < org.cnt, in1 = i0 + 1u < org.cnt;
+                    const u32 n0 = in0 ? min(word_groups(x0[b]), 2u * kSegGroups) : 0u, n1 = in1 ? min(word_groups(x1[b]), 2u * kSegGroups) : 0u;
+                    empty_word |= (in0 && n0 == 0u) || (in1 && n1 == 0u);
+                    // a full batch of literals (dense data): consecutive positions, no scan
+                    const u32 incl = (128u * b + 128u <= org.cnt && __ballot((int)(x0[b] | x1[b]) < 0) == 0) ? 2u * lane + 2u : wave_scan_incl32(n0 + n1);
+                    const u32 lo1 = pos + incl - n1, lo0 = lo1 - n0;
+                    bits += image_bits(x0[b], n0, lo0, M, P, p_total) + image_bits(x1[b], n1, lo1, M, P, p_total);
+                    pos += (u32)__builtin_amdgcn_readlane((int)incl, 63);
+                }
+            }
+            grps = pos;
+        } else {
+            const bool ones_mask = kind == kMaskOnes;
+#pragma unroll
+            for (int b = 0; b < kSegBatches; ++b) {
+                if (128u * b < org.cnt) { // wave-uniform
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        const u32 x = h ? x1[b] : x0[b];
+                        const u32 k = 128u * b + 2u * lane + h;
+                        const bool in = k < org.cnt;
+                        const u32 n = in ? min(word_groups(x), 2u * kSegGroups) : 0u;
+                        empty_word |= in && n == 0u;
+                        const bool lit = (int)x >= 0, ones = (x & kFillOne) == kFillOne;
+                        const u32 pad = k == last ? a.pad_bits : 0u;
+                        const u32 fill_bits = ones && n ? 31u * n - pad : 0u;
+                        bits += !in || !ones_mask ? 0u : lit ? (u32)__builtin_popcount(x & (k == last ? pad_mask : kOnes31)) : fill_bits;
+                        grps += n;
+                    }
+                }
+            }
+            grps = wave_total32(grps);
+        }
+        const u32 total_bits = wave_total32(bits);
+        const bool ok = kind != kMaskBad && !org.bad && grps == org.nvalid && __ballot(empty_word) == 0ull;
+        refused |= !ok;
+        if (lane == jj && ok) acc += (u64)total_bits;
+        if (!last_jj) {
+            ++jj;
+        } else {
+            if (last_seg && item + 1 < end) { // the run goes on with another chunk or mask
+                if (acc) atomicAdd(reinterpret_cast<unsigned long long *>(a.counts + i * a.n_operands + j0 + lane), (unsigned long long)acc);
+                acc = 0;
+            }
+            if (item + 1 < end) {
+                q = q_next;
+                seg = seg_next;
+                i = i_next;
+                c = c_next;
+            }
+            ++item;
+            jj = 0;
+        }
+    }
+    if (refused && lane == 0) atomicOr(a.ctrl + kCtlError, kErrStream);
+    // what the workgroup's wavefronts hold for the chunks their runs end in: consecutive runs, so equal chunks are neighbours
+    __syncthreads(); // (every image is done with: the merge borrows them)
+    u64 *s_q = reinterpret_cast<u64 *>(s_lds[0] + kMaskedWords);
+    reinterpret_cast<u64 *>(M)[lane] = acc;
+    if (lane == 0) s_q[wave] = begin < end ? q : ~0ull;
+    __syncthreads();
+    if (wave == 0) {
+        u64 at = ~0ull, sum = 0;
+        for (int v = 0; v <= kSegDecodeWaves; ++v) {
+            const u64 qv = v < kSegDecodeWaves ? s_q[v] : ~0ull;
+            if (qv != at) { // wave-uniform
+                if (at != ~0ull && sum) {
+                    const u64 mi = at / n_chunks, mc = at - mi * n_chunks;
+                    atomicAdd(reinterpret_cast<unsigned long long *>(a.counts + mi * a.n_operands + mc * a.chunk + lane), (unsigned long long)sum);
+                }
+                at = qv;
+                sum = 0;
+            }
+            if (v < kSegDecodeWaves) sum += reinterpret_cast<const u64 *>(s_lds[v] + kMaskedM)[lane];
+        }
+    }
+}
+
 // ---- the rank scan -----------------------------------------------------------------------------------------------------------
 constexpr u32 kRankThreads = 256;
 constexpr u32 kRankPerThread = kRankChunk / kRankThreads; // 16
@@ -310,6 +535,20 @@ hipError_t launch_select_count(const SelectCountArgs &a, hipStream_t s) {
     } else {
         hipLaunchKernelGGL(select_count_kernel<false>, dim3(select_count_grid(a.n_segments)), dim3(kSegDecodeWaves * 64), 0, s, a);
     }
+    return hipGetLastError();
+}
+
+// ... of the masked count: its 40 960 B of LDS let four workgroups onto a CU.  The chunk: as many operands per mask image as leave
+// every wavefront of a full grid eight items or more, 64 at the most
+hipError_t launch_count_masked(const CountMaskedArgs &a, hipStream_t s) {
+    if (a.n_segments == 0) return hipSuccess;
+    constexpr u64 most = 256u * 4u;
+    CountMaskedArgs b = a;
+    b.chunk = 64;
+    auto items = [&](u64 chunk) { return (u64)a.n_masks * ((a.n_operands + chunk - 1) / chunk) * a.n_segments; };
+    while (b.chunk > 1 && items(b.chunk) < 8 * most * kSegDecodeWaves) b.chunk /= 2;
+    const u64 want = (items(b.chunk) + kSegDecodeWaves - 1) / kSegDecodeWaves;
+    hipLaunchKernelGGL(count_masked_kernel, dim3((unsigned)(want > most ? most : want)), dim3(kSegDecodeWaves * 64), 0, s, b);
     return hipGetLastError();
 }
 

@@ -465,16 +465,37 @@ int wah_bitop_clauses_status(void *d_scratch, uint64_t n_words, uint64_t n_opera
  * the window and otherwise stages its bits' positions in LDS and stores them 64 consecutive entries at a time.  A refused
  * stream writes nothing to d_out and zeros to d_out_info.
  *
+ * wah_count_masked_indexed_device: the histogram of the rows a filter selects -- `SELECT b, COUNT(*) WHERE <conjunction> GROUP BY
+ * b`, the cross-tab `GROUP BY a, b`, SUM over a bit-sliced attribute.  d_counts receives n_masks * n_operands uint64, row-major:
+ * d_counts[i * n_operands + j] is the number of positions p < 32 * n_words set in BOTH mask i and operand j -- the popcount of the
+ * AND of the first n_words decoded words of the two streams, for every accepted pair; the pad bits are never counted, whichever
+ * of the two streams sets them.  d_masks and d_operands are two tables as for the list call (8-byte aligned, windows into column
+ * matrices allowed, rows may repeat, a stream may be a mask and an operand); 1 <= n_masks, 1 <= n_operands, n_masks * n_operands
+ * <= WAH_BITOP_LIST_MAX_OPERANDS.  A mask row may name the output buffer and index of a clause or list call enqueued before it on
+ * the stream and not yet checked: stream_words is then the buffer's capacity, and the index bounds the words that are read.  The
+ * call clears d_counts itself.  The tables are read only by the device: the call is asynchronous on `stream`, allocates nothing
+ * and never synchronises, and a captured graph replayed after a table was overwritten in place counts the NEW selection.
+ * n_words == 0: all counts 0.  Work is shared out by (mask, chunk of up to 64 consecutive operands, segment); no operand is decoded
+ * and no bitmap written: the mask's segment is expanded ONCE per chunk into its 1024 groups and the prefix sums of their popcounts
+ * in LDS, and the words of the chunk's operands are counted against them where they lie (a literal: one AND and a popcount; a
+ * one-fill: a difference of two prefix sums; a zero-fill: nothing), so the cost goes with the operands' words.  A mask segment that is one fill needs no expansion: under zeros the
+ * operand's segment is checked and counts nothing, under ones it is counted as by the call above.  EVERY segment of every mask
+ * and of every operand is checked, also under an empty mask segment; a mask row is refused for what an operand row is refused for.
+ * Counts of a refused call are unspecified.
+ *
  *   d_scratch: wah_select_scratch_bytes(n_words, n_operands) bytes, 256-byte aligned, no initialisation.  The size is a
  *   multiple of 256, never 0, and grows with n_words only: the control words, one uint64 per segment of 992 words + 1 (the
  *   positions call's rank table), and one uint64 per 4096 of those for each of the two upper levels of its prefix sum.
- *   Nothing in it goes with n_operands; one scratch serves both calls.
+ *   Nothing in it goes with n_operands or n_masks; one scratch serves all three calls.
  * Errors the host can see come back before any HIP call, argument checks first: a null or misaligned scratch (256 B), table,
- * d_counts, d_out or d_out_info (8 B), n_operands out of range, n_words >= 2^40: WAH_ERR_ARG; too small a scratch:
+ * d_counts, d_out or d_out_info (8 B), n_operands, n_masks or their product out of range, n_words >= 2^40: WAH_ERR_ARG; too small a scratch:
  * WAH_ERR_WORKSPACE.  wah_select_status(NULL, ...): WAH_ERR_ARG. */
 size_t wah_select_scratch_bytes(uint64_t n_words, uint64_t n_operands);
 int wah_count_list_indexed_device(uint64_t n_words, uint64_t n_operands, const wah_bitop_operand *d_operands,
                                   uint64_t *d_counts, void *d_scratch, size_t scratch_bytes, void *stream);
+int wah_count_masked_indexed_device(uint64_t n_words, uint64_t n_masks, const wah_bitop_operand *d_masks,
+                                    uint64_t n_operands, const wah_bitop_operand *d_operands, uint64_t *d_counts,
+                                    void *d_scratch, size_t scratch_bytes, void *stream);
 int wah_positions_indexed_device(uint64_t n_words, const uint32_t *d_stream, uint64_t stream_words,
                                  const uint64_t *d_offsets, uint64_t first_rank, uint64_t *d_out,
                                  uint64_t out_capacity, uint64_t *d_out_info, void *d_scratch,
