@@ -19,6 +19,7 @@
 //     (compress.cu:133-166, kernels.cu:273-280); nothing is persistent and nothing is cleared between launches.
 #include <atomic>
 
+#include "wah_asm_blocks.hpp"
 #include "wah_device.hpp"
 #include "wah_segdecode.hpp"
 
@@ -106,7 +107,7 @@ __device__ __forceinline__ void stage_prefetched(const Prefetch &p, u32 *lds, u3
 //             -- all that the other workgroups need to know of it, so the kernel publishes it right here.
 //   pass 2    compact: run-end words go to LDS at rank = running count + v_mbcnt over the saved mask, with the group
 //             position beside them (fill lengths are position differences, see final_words_to_regs).
-// Passes 1 and 2 are generated, hand-scheduled blocks (csrc/classify_pass*.inc, tools/gen_classify_block.py).
+// Passes 1 and 2 are hand-scheduled blocks: WAH_P1_BLOCK, WAH_P2_BLOCK and WAH_P2SKIP_BLOCK (wah_asm_blocks.hpp).
 // The bitmap's last segment may be short (F5): the groups that do not exist are replaced by a literal -- literals
 // never merge, so the last real group closes its run and each of them becomes one entry BEHIND the real ones, which
 // is simply not counted.
@@ -142,18 +143,14 @@ __device__ __forceinline__ u32 classify_pass1(const SegGroups &g, u32 never, Seg
     u32 na, ta, nb, tb;
     u32 f;
     asm volatile("v_mov_b32 %0, 0" : "=v"(f));
-    asm volatile(
-#include "classify_pass1.inc"
-        : [f] "+&v"(f), [cnt] "+&s"(cnt), [st] "=&s"(st), [na] "=&v"(na), [ta] "=&v"(ta), [nb] "=&v"(nb), [tb] "=&v"(tb)
-        : [x0] "v"(g.x[0]), [x1] "v"(g.x[1]), [x2] "v"(g.x[2]), [x3] "v"(g.x[3]), [x4] "v"(g.x[4]), [x5] "v"(g.x[5]), [x6] "v"(g.x[6]),
-          [x7] "v"(g.x[7]), [x8] "v"(g.x[8])
-        : "vcc", "scc");
-    asm volatile(
-#include "classify_pass1.inc"
-        : [f] "+&v"(f), [cnt] "+&s"(cnt), [st] "=&s"(st), [na] "=&v"(na), [ta] "=&v"(ta), [nb] "=&v"(nb), [tb] "=&v"(tb)
-        : [x0] "v"(g.x[8]), [x1] "v"(g.x[9]), [x2] "v"(g.x[10]), [x3] "v"(g.x[11]), [x4] "v"(g.x[12]), [x5] "v"(g.x[13]),
-          [x6] "v"(g.x[14]), [x7] "v"(g.x[15]), [x8] "v"(never)
-        : "vcc", "scc");
+#define WAH_P1_OUT [f] "+&v"(f), [cnt] "+&s"(cnt), [st] "=&s"(st), [na] "=&v"(na), [ta] "=&v"(ta), [nb] "=&v"(nb), [tb] "=&v"(tb)
+#define WAH_P1_IN(b, last)                                                                                                              \
+    [x0] "v"(g.x[b]), [x1] "v"(g.x[b + 1]), [x2] "v"(g.x[b + 2]), [x3] "v"(g.x[b + 3]), [x4] "v"(g.x[b + 4]), [x5] "v"(g.x[b + 5]),         \
+        [x6] "v"(g.x[b + 6]), [x7] "v"(g.x[b + 7]), [x8] "v"(last)
+    asm volatile(WAH_P1_BLOCK : WAH_P1_OUT : WAH_P1_IN(0, g.x[8]) : "vcc", "scc");
+    asm volatile(WAH_P1_BLOCK : WAH_P1_OUT : WAH_P1_IN(8, never) : "vcc", "scc");
+#undef WAH_P1_OUT
+#undef WAH_P1_IN
     e = f;
     return cnt;
 }
@@ -187,33 +184,19 @@ __device__ __forceinline__ void classify_pass2(const SegGroups &g, SegEnds e, u3
     u32 na, ta, nb, tb, ps;
     const u32 lane2 = lane_v * 0x10001u; // the lane id in both halves: position words are built two at a time
     u32 f = e << 16;                     // step 0 at the top
-    if (sparse) {
-        asm volatile(
-#include "classify_pass2_skip_a.inc"
-            : [f] "+&v"(f), [na] "=&v"(na), [ta] "=&v"(ta), [nb] "=&v"(nb), [tb] "=&v"(tb), [ps] "=&v"(ps), [cn] "+&v"(count_v)
-            : [x0] "v"(g.x[0]), [x1] "v"(g.x[1]), [x2] "v"(g.x[2]), [x3] "v"(g.x[3]), [x4] "v"(g.x[4]), [x5] "v"(g.x[5]), [x6] "v"(g.x[6]),
-              [x7] "v"(g.x[7]), [ln2] "v"(lane_v), [vb] "s"(vbase), [pb] "s"(pbase), [dm] "v"(dump_slot)
-            : "vcc", "scc", "memory");
-        asm volatile(
-#include "classify_pass2_skip_b.inc"
-            : [f] "+&v"(f), [na] "=&v"(na), [ta] "=&v"(ta), [nb] "=&v"(nb), [tb] "=&v"(tb), [ps] "=&v"(ps), [cn] "+&v"(count_v)
-            : [x0] "v"(g.x[8]), [x1] "v"(g.x[9]), [x2] "v"(g.x[10]), [x3] "v"(g.x[11]), [x4] "v"(g.x[12]), [x5] "v"(g.x[13]),
-              [x6] "v"(g.x[14]), [x7] "v"(g.x[15]), [ln2] "v"(lane_v), [vb] "s"(vbase), [pb] "s"(pbase), [dm] "v"(dump_slot)
-            : "vcc", "scc", "memory");
+#define WAH_P2_OUT [f] "+&v"(f), [na] "=&v"(na), [ta] "=&v"(ta), [nb] "=&v"(nb), [tb] "=&v"(tb), [ps] "=&v"(ps), [cn] "+&v"(count_v)
+#define WAH_P2_IN(b, ln)                                                                                                                \
+    [x0] "v"(g.x[b]), [x1] "v"(g.x[b + 1]), [x2] "v"(g.x[b + 2]), [x3] "v"(g.x[b + 3]), [x4] "v"(g.x[b + 4]), [x5] "v"(g.x[b + 5]),         \
+        [x6] "v"(g.x[b + 6]), [x7] "v"(g.x[b + 7]), [ln2] "v"(ln), [vb] "s"(vbase), [pb] "s"(pbase), [dm] "v"(dump_slot)
+    if (sparse) { // every step builds its own position word: the plain lane id
+        asm volatile(WAH_P2SKIP_BLOCK(0) : WAH_P2_OUT : WAH_P2_IN(0, lane_v) : "vcc", "scc", "memory");
+        asm volatile(WAH_P2SKIP_BLOCK(8) : WAH_P2_OUT : WAH_P2_IN(8, lane_v) : "vcc", "scc", "memory");
         return;
     }
-    asm volatile(
-#include "classify_pass2_a.inc"
-        : [f] "+&v"(f), [na] "=&v"(na), [ta] "=&v"(ta), [nb] "=&v"(nb), [tb] "=&v"(tb), [ps] "=&v"(ps), [cn] "+&v"(count_v)
-        : [x0] "v"(g.x[0]), [x1] "v"(g.x[1]), [x2] "v"(g.x[2]), [x3] "v"(g.x[3]), [x4] "v"(g.x[4]), [x5] "v"(g.x[5]), [x6] "v"(g.x[6]),
-          [x7] "v"(g.x[7]), [ln2] "v"(lane2), [vb] "s"(vbase), [pb] "s"(pbase), [dm] "v"(dump_slot)
-        : "vcc", "memory");
-    asm volatile(
-#include "classify_pass2_b.inc"
-        : [f] "+&v"(f), [na] "=&v"(na), [ta] "=&v"(ta), [nb] "=&v"(nb), [tb] "=&v"(tb), [ps] "=&v"(ps), [cn] "+&v"(count_v)
-        : [x0] "v"(g.x[8]), [x1] "v"(g.x[9]), [x2] "v"(g.x[10]), [x3] "v"(g.x[11]), [x4] "v"(g.x[12]), [x5] "v"(g.x[13]),
-          [x6] "v"(g.x[14]), [x7] "v"(g.x[15]), [ln2] "v"(lane2), [vb] "s"(vbase), [pb] "s"(pbase), [dm] "v"(dump_slot)
-        : "vcc", "memory");
+    asm volatile(WAH_P2_BLOCK(0) : WAH_P2_OUT : WAH_P2_IN(0, lane2) : "vcc", "memory");
+    asm volatile(WAH_P2_BLOCK(8) : WAH_P2_OUT : WAH_P2_IN(8, lane2) : "vcc", "memory");
+#undef WAH_P2_OUT
+#undef WAH_P2_IN
 }
 
 // ===========================================================================

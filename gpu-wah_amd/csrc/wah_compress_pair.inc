@@ -119,9 +119,9 @@ __device__ __forceinline__ u32 pair_pass1(const LaneGroups &g, u32 lane, u32 nev
 // PASS 2: the lane's final words (kernels.cu:244-249) to LDS at their rank.
 //   rank0   words of the pair in front of this lane's (exclusive prefix sum of the popcounts)
 //   f       the lane's flag word
-// The generated blocks (tools/gen_pair_blocks.py) do the work; what they need to start with is nl = 1 + the distance
-// from this lane's group 0 back to the last run end of the lanes below, minus one: length of a fill that ends at group k
-// of this lane = k + nl.  The last group of a segment always ends a run, so a lane of the pair's second segment never
+// The hand-scheduled blocks (WAH_PP2_BLOCK, wah_asm_blocks.hpp) do the work; what they need to start with is nl = 1 + the
+// distance from this lane's group 0 back to the last run end of the lanes below, minus one: length of a fill that ends at
+// group k of this lane = k + nl.  The last group of a segment always ends a run, so a lane of the pair's second segment never
 // looks back beyond its segment's start.
 //   variant kPass2Skip (few words: steps without a run end are branched over) / kPass2Swizzled (the words land in the
 //           piece layout of store_literals; park_pair reads with the swizzled lane number)
@@ -145,47 +145,15 @@ __device__ __forceinline__ void pair_pass2(const LaneGroups &g, u32 f, u32 rank0
     [x0] "v"(g.x[b]), [x1] "v"(g.x[b + 1]), [x2] "v"(g.x[b + 2]), [x3] "v"(g.x[b + 3]), [x4] "v"(g.x[b + 4]), [x5] "v"(g.x[b + 5]),         \
         [x6] "v"(g.x[b + 6]), [x7] "v"(g.x[b + 7])
     if (variant == kPass2Skip) {
-        asm volatile(
-#include "pair_pass2_skip_0.inc"
-            : WAH_PP2_OUT
-            : WAH_PP2_IN(0)
-            : "vcc", "scc", "memory");
-        asm volatile(
-#include "pair_pass2_skip_1.inc"
-            : WAH_PP2_OUT
-            : WAH_PP2_IN(8)
-            : "vcc", "scc", "memory");
-        asm volatile(
-#include "pair_pass2_skip_2.inc"
-            : WAH_PP2_OUT
-            : WAH_PP2_IN(16)
-            : "vcc", "scc", "memory");
-        asm volatile(
-#include "pair_pass2_skip_3.inc"
-            : WAH_PP2_OUT
-            : WAH_PP2_IN(24)
-            : "vcc", "scc", "memory");
+        asm volatile(WAH_PP2_BLOCK(skip, 0) : WAH_PP2_OUT : WAH_PP2_IN(0) : "vcc", "scc", "memory");
+        asm volatile(WAH_PP2_BLOCK(skip, 8) : WAH_PP2_OUT : WAH_PP2_IN(8) : "vcc", "scc", "memory");
+        asm volatile(WAH_PP2_BLOCK(skip, 16) : WAH_PP2_OUT : WAH_PP2_IN(16) : "vcc", "scc", "memory");
+        asm volatile(WAH_PP2_BLOCK(skip, 24) : WAH_PP2_OUT : WAH_PP2_IN(24) : "vcc", "scc", "memory");
     } else {
-        asm volatile(
-#include "pair_pass2_swz_0.inc"
-            : WAH_PP2_OUT
-            : WAH_PP2_IN(0), [c70] "s"(0x70u)
-            : "vcc", "scc", "memory");
-        asm volatile(
-#include "pair_pass2_swz_1.inc"
-            : WAH_PP2_OUT
-            : WAH_PP2_IN(8), [c70] "s"(0x70u)
-            : "vcc", "scc", "memory");
-        asm volatile(
-#include "pair_pass2_swz_2.inc"
-            : WAH_PP2_OUT
-            : WAH_PP2_IN(16), [c70] "s"(0x70u)
-            : "vcc", "scc", "memory");
-        asm volatile(
-#include "pair_pass2_swz_3.inc"
-            : WAH_PP2_OUT
-            : WAH_PP2_IN(24), [c70] "s"(0x70u)
-            : "vcc", "scc", "memory");
+        asm volatile(WAH_PP2_BLOCK(swz, 0) : WAH_PP2_OUT : WAH_PP2_IN(0), [c70] "s"(0x70u) : "vcc", "scc", "memory");
+        asm volatile(WAH_PP2_BLOCK(swz, 8) : WAH_PP2_OUT : WAH_PP2_IN(8), [c70] "s"(0x70u) : "vcc", "scc", "memory");
+        asm volatile(WAH_PP2_BLOCK(swz, 16) : WAH_PP2_OUT : WAH_PP2_IN(16), [c70] "s"(0x70u) : "vcc", "scc", "memory");
+        asm volatile(WAH_PP2_BLOCK(swz, 24) : WAH_PP2_OUT : WAH_PP2_IN(24), [c70] "s"(0x70u) : "vcc", "scc", "memory");
     }
 #undef WAH_PP2_OUT
 #undef WAH_PP2_IN
