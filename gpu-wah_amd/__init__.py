@@ -49,6 +49,8 @@ from .api import (  # noqa: F401
     count_device,
     count_masked_device,
     positions_device,
+    from_positions_device,
+    from_positions_max_words,
     merge_fills_device,
     StreamReport,
     gen_uniform_device,

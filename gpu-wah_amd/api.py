@@ -71,6 +71,10 @@ ABI_SYMBOLS = {
     "wah_count_masked_indexed_device": (_int, [_u64, _u64, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
     "wah_positions_indexed_device": (_int, [_u64, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _sz, _vp]),
     "wah_select_status": (_int, [_vp, _vp]),
+    "wah_from_positions_max_words": (_u64, [_u64, _u64, _u64]),
+    "wah_from_positions_scratch_bytes": (_sz, [_u64, _u64]),
+    "wah_from_positions_device": (_int, [_u64, _u64, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
+    "wah_from_positions_status": (_int, [_vp, _vp]),
     "wah_gen_uniform_device": (_int, [_vp, _u64, _u64, _u64, _vp]),
     "wah_gen_clustered_device": (_int, [_vp, _u64, _u64, _u64, _vp]),
     "wah_copy_device": (_int, [_vp, _vp, _u64, _vp]),
@@ -688,6 +692,48 @@ def positions_device(stream, seg_offsets, n_words, first=0, limit=None, out=None
     _check(lib().wah_select_status(scratch.data_ptr(), sp), "positions")
     total, written = (int(v) for v in info.tolist())
     return out[:written], total
+
+
+def from_positions_max_words(n_words, n_lists, n_rows):
+    return int(lib().wah_from_positions_max_words(int(n_words), int(n_lists), int(n_rows)))
+
+
+def from_positions_device(rows, list_ends, n_words, scratch=None, out=None, out_offsets=None, check=True):
+    """Compressed bitmaps of n_words words straight from sorted lists of row numbers, any number of lists in one call and no
+    decoded bitmap (wah_from_positions_device).  rows: a contiguous int64 CUDA tensor, the lists back to back, each strictly
+    ascending and below 32 * n_words; list_ends: a contiguous int64 CUDA tensor on the same device, one past every list's last
+    row (never decreasing, the last one len(rows)) -- only the device reads them.  Returns (stream, seg_offsets): the lists'
+    compress() streams back to back and the n_lists * S + 1 entries of their segment index (S = segments of one bitmap); list c
+    is the operand (stream, seg_offsets[c * S:]).  scratch / out / out_offsets: reuse these tensors (out defaults to
+    wah_from_positions_max_words words); check=False: only enqueue and return (out, count tensor, out_offsets)."""
+    torch = _torch()
+    for t, what in ((rows, "rows"), (list_ends, "list_ends")):
+        if t.dtype != torch.int64 or t.dim() != 1 or not t.is_cuda or not t.is_contiguous():
+            raise WahError(f"{what}: a contiguous one-dimensional int64 CUDA tensor")
+    if list_ends.device != rows.device or list_ends.numel() < 1:
+        raise WahError("list_ends: at least one entry, on the rows' device")
+    dev = rows.device
+    n, k, r = int(n_words), int(list_ends.numel()), int(rows.numel())
+    n_seg = (max_compressed_words(n) + 1023) // 1024
+    if scratch is None:
+        scratch = torch.empty(int(lib().wah_from_positions_scratch_bytes(n, k)), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.empty(max(from_positions_max_words(n, k, r), 1), dtype=torch.int32, device=dev)
+    else:
+        _as_words(torch, out)
+    if out_offsets is None:
+        out_offsets = torch.empty(k * n_seg + 1, dtype=torch.int64, device=dev)
+    elif out_offsets.dtype != torch.int64 or out_offsets.numel() < k * n_seg + 1 or not out_offsets.is_contiguous() or out_offsets.device != dev:
+        raise WahError("out_offsets: a contiguous int64 tensor of n_lists * segments + 1 entries on the rows' device")
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    sp = _stream_ptr(torch)
+    _check(lib().wah_from_positions_device(n, k, list_ends.data_ptr(), rows.data_ptr() if r else None, r, out.data_ptr(), out.numel(),
+                                           count.data_ptr(), out_offsets.data_ptr(), scratch.data_ptr(), scratch.numel(), sp),
+           "wah_from_positions_device")
+    if not check:
+        return out, count, out_offsets
+    _check(lib().wah_from_positions_status(scratch.data_ptr(), sp), "from_positions")
+    return out[: int(count.item())], out_offsets[: k * n_seg + 1]
 
 
 StreamReport = collections.namedtuple(

@@ -212,6 +212,56 @@ def select_rows(wah, predicates, n_words_per_column, first=0, limit=None):
     return wah.positions_device(result, result_offsets, n_words_per_column, first=first, limit=limit)
 
 
+def bitmaps_from_rows(wah, row_lists, n_words, **reuse):
+    """One compressed bitmap of n_words words per list of row numbers, in one call and without a decoded bitmap
+    (wah_from_positions_device): row_lists is a Python list of int64 device tensors, each strictly ascending (a join's row ids, a
+    tombstone list; an empty tensor is an empty bitmap).  reuse: scratch / out / out_offsets / check of
+    api.from_positions_device.  Returns its (stream, seg_offsets): list c is the operand (stream, seg_offsets[c * S:]), S the
+    segments of one bitmap; with n_words a multiple of 992 the pair goes into column_operand_table as a column matrix does."""
+    import torch
+
+    if not row_lists:
+        raise ValueError("at least one list")
+    dev = row_lists[0].device
+    rows = torch.cat([r.reshape(-1) for r in row_lists]).contiguous()
+    ends = torch.tensor([int(r.numel()) for r in row_lists], dtype=torch.int64).cumsum(0).to(dev)
+    return wah.from_positions_device(rows, ends, n_words, **reuse)
+
+
+def index_from_keys(wah, keys, n_values, n_words_per_column=None, check=True):
+    """The equality-encoded bitmap index of a key column without its decoded bit matrix [n_values, rows / 32]: keys is an int64
+    device tensor with one value in [0, n_values) per row.  Grouping the rows is plumbing -- one stable torch.sort, whose indices
+    are each value's rows in ascending order, and one torch.bincount, whose running sum is where each value's rows end --; the
+    bitmaps are one wah_from_positions_device call.  n_words_per_column defaults to ceil(rows / 32) rounded up to a multiple of
+    992.  check=True: keys outside [0, n_values) raise (one host read of their minimum and maximum) and the call's status is read;
+    check=False reads nothing back and returns the whole output buffer.  Returns (stream, seg_offsets, n_words_per_column), which
+    go in as the arguments of the same names of column_operand_table, combine_columns, filter_columns, count_columns,
+    crosstab_columns and select_rows."""
+    import torch
+
+    if keys.dtype != torch.int64 or keys.dim() != 1 or not keys.is_cuda:
+        raise ValueError("keys: a one-dimensional int64 device tensor")
+    n_values, rows = int(n_values), int(keys.numel())
+    if n_values < 1:
+        raise ValueError("at least one value")
+    if n_words_per_column is None:
+        n_words_per_column = max(-(-((rows + 31) // 32) // SEGMENT_WORDS), 1) * SEGMENT_WORDS
+    n = int(n_words_per_column)
+    if n % SEGMENT_WORDS or n <= 0 or 32 * n < rows:
+        raise ValueError("columns are a multiple of 992 words long and hold every row")
+    if check and rows:
+        lo, hi = (int(v) for v in torch.aminmax(keys))
+        if lo < 0 or hi >= n_values:
+            raise ValueError(f"keys outside [0, {n_values})")
+    order = torch.sort(keys, stable=True).indices
+    ends = torch.bincount(keys, minlength=n_values)[:n_values].cumsum(0)
+    if not check:
+        out, _, out_offsets = wah.from_positions_device(order, ends, n, check=False)
+        return out, out_offsets, n
+    stream, seg_offsets = wah.from_positions_device(order, ends, n)
+    return stream, seg_offsets, n
+
+
 def compress_column_ranges(compressor, flat, lengths, wait=True):
     """Columns of DIFFERENT lengths (each a multiple of 992 words) stored back to back in `flat`: still one launch.
     Returns (stream, column_offsets) like compress_column_matrix: column c is stream[column_offsets[c] :

@@ -1553,6 +1553,104 @@ int wah_select_status(void *d_scratch, void *stream) {
     return read_status(d_scratch, stream);
 }
 
+// Compressed bitmaps from sorted lists of row numbers (wah_from_positions.hip).  The scratch: control block, then the two upper
+// levels of the prefix sum over the n_lists x S + 1 index entries (one u64 per 4096 entries of the level below); the scan itself
+// runs in place in the caller's index.
+namespace {
+struct FromPositionsLayout {
+    uint64_t groups, n_segments, n_items;
+    size_t level1, level2, total;
+};
+FromPositionsLayout from_positions_layout(uint64_t n_words, uint64_t n_lists) {
+    FromPositionsLayout l;
+    l.groups = wah_max_compressed_words(n_words);
+    l.n_segments = ceil_div(l.groups, (uint64_t)wah::kSegGroups);
+    l.n_items = n_lists * l.n_segments;
+    const uint64_t n0 = l.n_items + 1, n1 = ceil_div(n0, (uint64_t)wah::kRankChunk), n2 = ceil_div(n1, (uint64_t)wah::kRankChunk);
+    size_t at = wah::kCtlWords * sizeof(uint32_t);
+    l.level1 = at;
+    at += round256(n1 * sizeof(uint64_t));
+    l.level2 = at;
+    at += round256(n2 * sizeof(uint64_t));
+    l.total = at;
+    return l;
+}
+} // namespace
+
+uint64_t wah_from_positions_max_words(uint64_t n_words, uint64_t n_lists, uint64_t n_rows) {
+    // (n_lists x G passes 2^64 for the longest bitmaps and the most lists)
+    const unsigned __int128 groups = wah_max_compressed_words(n_words), segments = ceil_div((uint64_t)groups, (uint64_t)wah::kSegGroups);
+    const unsigned __int128 all_literals = (unsigned __int128)n_lists * groups;
+    const unsigned __int128 by_rows = (unsigned __int128)n_lists * segments + 2 * (unsigned __int128)n_rows;
+    const unsigned __int128 m = all_literals < by_rows ? all_literals : by_rows;
+    return m > (unsigned __int128)~0ull ? ~0ull : (uint64_t)m;
+}
+
+size_t wah_from_positions_scratch_bytes(uint64_t n_words, uint64_t n_lists) { return from_positions_layout(n_words, n_lists).total; }
+
+int wah_from_positions_device(uint64_t n_words, uint64_t n_lists, const uint64_t *d_list_ends, const uint64_t *d_rows, uint64_t n_rows,
+                              uint32_t *d_out, uint64_t out_capacity_words, uint64_t *d_out_words, uint64_t *d_out_offsets,
+                              void *d_scratch, size_t scratch_bytes, void *stream) {
+    g_err[0] = 0;
+    if (n_lists < 1 || n_lists > wah::kMaxBitopListOperands || n_words == 0 || n_words >= (1ull << 40) || n_rows >= (1ull << 40)) {
+        set_err("between 1 and 2^24 lists, between 1 and 2^40 - 1 words, fewer than 2^40 rows");
+        return WAH_ERR_ARG;
+    }
+    const FromPositionsLayout l = from_positions_layout(n_words, n_lists);
+    if (l.n_items >= (1ull << 31)) {
+        set_err("lists x segments of 992 words: fewer than 2^31");
+        return WAH_ERR_ARG;
+    }
+    if (!d_scratch || (reinterpret_cast<uintptr_t>(d_scratch) & 255u)) {
+        set_err("bad scratch pointer");
+        return WAH_ERR_ARG;
+    }
+    if (!d_list_ends || (reinterpret_cast<uintptr_t>(d_list_ends) & 7u) || (n_rows && !d_rows) || (reinterpret_cast<uintptr_t>(d_rows) & 7u)) {
+        set_err("null or misaligned list ends or rows");
+        return WAH_ERR_ARG;
+    }
+    if (!d_out || (reinterpret_cast<uintptr_t>(d_out) & 3u) || !d_out_words || (reinterpret_cast<uintptr_t>(d_out_words) & 7u) || !d_out_offsets ||
+        (reinterpret_cast<uintptr_t>(d_out_offsets) & 7u)) {
+        set_err("null or misaligned output");
+        return WAH_ERR_ARG;
+    }
+    if (scratch_bytes < l.total) {
+        set_err("scratch too small");
+        return WAH_ERR_WORKSPACE;
+    }
+    char *sc = static_cast<char *>(d_scratch);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    wah::FromPositionsArgs a = {};
+    a.rows = d_rows;
+    a.list_ends = d_list_ends;
+    a.n_rows = n_rows;
+    a.n_lists = n_lists;
+    a.n_bits = 32u * n_words;
+    a.groups = l.groups;
+    a.n_segments = l.n_segments;
+    a.out = d_out;
+    a.out_capacity = out_capacity_words;
+    a.out_words = d_out_words;
+    a.offsets = d_out_offsets;
+    a.ctrl = reinterpret_cast<uint32_t *>(sc);
+    hipError_t e = wah::launch_clear(sc, wah::kCtlWords * sizeof(uint32_t), s); // (read by wah_from_positions_status)
+    if (e == hipSuccess) e = wah::launch_from_positions_check(a, s);
+    if (e == hipSuccess) e = wah::launch_from_positions_segments(a, false, s);
+    if (e == hipSuccess)
+        e = wah::launch_select_rank_scan(d_out_offsets, l.n_items, reinterpret_cast<uint64_t *>(sc + l.level1), reinterpret_cast<uint64_t *>(sc + l.level2), s);
+    if (e == hipSuccess) e = wah::launch_from_positions_segments(a, true, s);
+    if (e != hipSuccess) {
+        set_err("from_positions launch", e);
+        return WAH_ERR_HIP;
+    }
+    return WAH_OK;
+}
+
+int wah_from_positions_status(void *d_scratch, void *stream) {
+    if (!d_scratch) return WAH_ERR_ARG;
+    return read_status(d_scratch, stream);
+}
+
 // ---------------------------------------------------------------------------
 // host-pointer entry points (the reference's API)
 // ---------------------------------------------------------------------------

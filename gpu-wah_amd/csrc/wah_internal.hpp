@@ -301,6 +301,25 @@ struct SelectEmitArgs {
 };
 hipError_t launch_select_emit(const SelectEmitArgs &a, hipStream_t s);
 
+// wah_from_positions_device (wah_from_positions.hip): sorted lists of row numbers in, their compress() streams back to back and
+// the segment index of the whole out.  offsets: n_lists * n_segments + 1 entries -- the count pass stores every (list, segment)'s
+// words there, launch_select_rank_scan turns them into the index in place, the emit pass reads it.
+struct FromPositionsArgs {
+    const uint64_t *rows;      // n_rows positions, the lists back to back
+    const uint64_t *list_ends; // n_lists: one past every list's last row
+    uint64_t n_rows, n_lists;
+    uint64_t n_bits;           // 32 n_words: a row is below it
+    uint64_t groups;           // G of ONE bitmap
+    uint64_t n_segments;       // S = ceil(G / 1024), per list
+    uint32_t *out;
+    uint64_t out_capacity;
+    uint64_t *out_words;
+    uint64_t *offsets;
+    uint32_t *ctrl;
+};
+hipError_t launch_from_positions_check(const FromPositionsArgs &a, hipStream_t s);
+hipError_t launch_from_positions_segments(const FromPositionsArgs &a, bool emit, hipStream_t s);
+
 // wah_bitop_device: what the operands' decodes left behind, checked on the device before the combining pass
 struct PairCheck {
     const uint64_t *info_a, *info_b; // [decoded words, groups] of the two operands

@@ -502,6 +502,47 @@ int wah_positions_indexed_device(uint64_t n_words, const uint32_t *d_stream, uin
                                  size_t scratch_bytes, void *stream);
 int wah_select_status(void *d_scratch, void *stream);
 
+/* The way INTO the index that does not go through a decoded bitmap: compressed bitmaps straight from sorted lists of row numbers
+ * -- the rows of every value of a key column (one stable sort groups them), the row ids a join returns, a tombstone list.  The
+ * reverse of wah_positions_indexed_device; not in the reference, whose compress() takes the decoded bitmap (compress.cu:41-209).
+ *   d_rows: n_rows positions p = 32 * word + bit, the lists back to back.  d_list_ends: n_lists entries in DEVICE memory: list c
+ *   is d_rows[end(c - 1) .. end(c)) with end(-1) = 0.  Inside a list the positions ascend strictly and are below 32 * n_words; a
+ *   list may be empty; the ends never decrease and the last one equals n_rows.  n_rows == 0 with a null d_rows is allowed.
+ * d_out receives the streams of all lists back to back, list 0 first, each word for word what compress() emits for the bitmap of
+ * n_words words that has exactly those bits set (ragged n_words included: the pad bits of the last group stay zero).
+ * d_out_offsets (required) receives n_lists * S + 1 entries, S = ceil(G / 1024), G = wah_max_compressed_words(n_words): entry
+ * c * S + s is the first word of segment s of list c, counted from d_out[0]; the last entry is the total, which d_out_words
+ * receives too.  For n_words % 992 == 0 the pair is exactly the (stream, whole index) of a column matrix compressed in one launch
+ * (wah_compress_device_indexed over back-to-back columns), so every indexed call takes it unchanged; for any n_words a
+ * wah_bitop_operand with d_offsets = d_out_offsets + c * S is list c.
+ *   wah_from_positions_max_words: an out_capacity_words that always suffices: min(n_lists * G, n_lists * S + 2 * n_rows) -- a
+ *   segment with r rows has at most r literal or one-fill words and r + 1 gaps.
+ *   d_scratch: wah_from_positions_scratch_bytes(n_words, n_lists) bytes, 256-byte aligned, no initialisation: the control words
+ *   and the two upper levels (one uint64 per 4096 entries of the level below) of the prefix sum over the index entries, which
+ *   itself runs in place in d_out_offsets.  A multiple of 256, never 0.
+ * The lists are read only by the device: the call is asynchronous on `stream`, allocates nothing and never synchronises, and a
+ * captured graph replayed after d_rows and d_list_ends were overwritten in place (same n_rows, same n_lists) builds the NEW
+ * lists.  Three steps, none of which waits for another workgroup: a pass that checks every end and every row; one wavefront per
+ * (list, segment) that finds its slice of the list by searching for the segment's bit range and counts the segment's words -- no
+ * row: one zero-fill; up to 64 rows: in registers, a row per lane; more: through an image of the segment's 1024 groups in LDS --;
+ * the prefix sum of the counts; and the same wavefronts again, which now store the words, 64 consecutive ones at a time.  No
+ * decoded bitmap exists at any point: the cost goes with n_rows and n_lists * S.
+ * Errors the host can see come back before any HIP call, argument checks first: n_lists < 1 or > WAH_BITOP_LIST_MAX_OPERANDS,
+ * n_lists * S >= 2^31, n_words == 0 or >= 2^40, n_rows >= 2^40, a null or misaligned d_list_ends, d_out_offsets, d_out_words
+ * (8 B), d_out (4 B) or scratch (256 B), a null d_rows with n_rows > 0: WAH_ERR_ARG; too small a scratch: WAH_ERR_WORKSPACE.
+ * Everything only the device sees is reported by wah_from_positions_status(), which synchronises the stream: WAH_ERR_STREAM for a
+ * row at or beyond 32 * n_words, two neighbours of one list that do not ascend strictly (duplicates included), ends that
+ * decrease, a last end that is not n_rows -- a descent across a list boundary is legal --; WAH_ERR_CAPACITY for too small an
+ * output (nothing is written at or behind d_out[out_capacity_words]).  EVERY row and every end is checked, so the verdict does not
+ * depend on the data, and an end is checked before it bounds a read of d_rows.  Rows that do not ascend are refused, not
+ * sorted; the output of a refused call is unspecified.  wah_from_positions_status(NULL, ...): WAH_ERR_ARG. */
+uint64_t wah_from_positions_max_words(uint64_t n_words, uint64_t n_lists, uint64_t n_rows);
+size_t wah_from_positions_scratch_bytes(uint64_t n_words, uint64_t n_lists);
+int wah_from_positions_device(uint64_t n_words, uint64_t n_lists, const uint64_t *d_list_ends, const uint64_t *d_rows,
+                              uint64_t n_rows, uint32_t *d_out, uint64_t out_capacity_words, uint64_t *d_out_words,
+                              uint64_t *d_out_offsets, void *d_scratch, size_t scratch_bytes, void *stream);
+int wah_from_positions_status(void *d_scratch, void *stream);
+
 /* ------------------------------------------------------------------------- *
  * Benchmark support: synthetic bitmaps generated in HBM (include/wah_gen.h
  * states the bit-exact definition; replaces tests.cpp:42-64), and a plain
