@@ -46,6 +46,10 @@ from .api import (  # noqa: F401
     bitop_clauses_indexed_device,
     bitop_clause_table,
     CLAUSE_NEGATE,
+    bsi_range_device,
+    bsi_bounds,
+    BSI_MAX_SLICES,
+    BSI_EXISTS,
     count_device,
     count_masked_device,
     positions_device,

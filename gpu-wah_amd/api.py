@@ -66,6 +66,9 @@ ABI_SYMBOLS = {
     "wah_bitop_clauses_scratch_bytes": (_sz, [_u64, _u64, _u64]),
     "wah_bitop_clauses_indexed_device": (_int, [_u64, _u64, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
     "wah_bitop_clauses_status": (_int, [_vp, _u64, _u64, _u64, _vp]),
+    "wah_bsi_range_scratch_bytes": (_sz, [_u64, _u64]),
+    "wah_bsi_range_indexed_device": (_int, [_u64, _u64, _vp, _vp, ctypes.c_uint, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
+    "wah_bsi_range_status": (_int, [_vp, _u64, _u64, _vp]),
     "wah_select_scratch_bytes": (_sz, [_u64, _u64]),
     "wah_count_list_indexed_device": (_int, [_u64, _u64, _vp, _vp, _vp, _sz, _vp]),
     "wah_count_masked_indexed_device": (_int, [_u64, _u64, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
@@ -586,6 +589,70 @@ def bitop_clauses_indexed_device(clauses, n_words, scratch=None, out=None, out_o
     if not check:
         return out, count, out_offsets
     _check(lib().wah_bitop_clauses_status(scratch.data_ptr(), n, k, c, sp), "bitop_clauses_indexed")
+    return out[: int(count.item())], out_offsets
+
+
+BSI_MAX_SLICES = 64  # WAH_BSI_MAX_SLICES
+BSI_EXISTS = 1  # WAH_BSI_EXISTS
+
+
+def bsi_bounds(lo, hi, device, out=None):
+    """The bounds of wah_bsi_range_indexed_device as an int64 device tensor [2]: two Python ints in 0 .. 2^64 - 1, stored as
+    their two's-complement bit patterns.  out: an existing tensor to overwrite in place -- what a captured graph replayed
+    with another range needs."""
+    import torch
+
+    pair = []
+    for v in (lo, hi):
+        v = int(v)
+        if not 0 <= v < 1 << 64:
+            raise WahError("a bound is an unsigned integer below 2^64")
+        pair.append(v - (1 << 64) if v >= 1 << 63 else v)
+    t = torch.tensor(pair, dtype=torch.int64)
+    if out is None:
+        return t.to(device)
+    out.copy_(t)
+    return out
+
+
+def bsi_range_device(table, bounds, n_words, exists=False, scratch=None, out=None, out_offsets=None, check=True):
+    """compress(lo <= value <= hi [AND exists]) over a bit-sliced attribute in one call (wah_bsi_range_indexed_device).  table:
+    a list of (stream, seg_offsets) pairs or a ready [rows, 3] table (bitop_operand_table, columns.column_operand_table), one
+    row per slice, MOST significant first, and with exists=True the existence bitmap as one more row behind them.  bounds: an
+    int64 device tensor [2] (lo, hi as 64-bit patterns; only the device reads it) or a (lo, hi) pair of Python ints up to
+    2^64 - 1 (bsi_bounds).  Returns as bitop_clauses_indexed_device: (stream, seg_offsets), or with check=False, which only
+    enqueues, (out, count tensor, out_offsets)."""
+    torch = _torch()
+    if not isinstance(table, torch.Tensor):
+        table = bitop_operand_table(table)
+    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 3 or not table.is_cuda or not table.is_contiguous():
+        raise WahError("a slice table is a contiguous int64 CUDA tensor of shape [rows, 3]")
+    dev = table.device
+    k = int(table.shape[0]) - (1 if exists else 0)
+    if not 1 <= k <= BSI_MAX_SLICES:
+        raise WahError("between 1 and 64 slices (and one more row with exists=True)")
+    if not isinstance(bounds, torch.Tensor):
+        lo, hi = bounds
+        bounds = bsi_bounds(lo, hi, dev)
+    if bounds.dtype != torch.int64 or tuple(bounds.shape) != (2,) or bounds.device != dev or not bounds.is_contiguous():
+        raise WahError("bounds: a contiguous int64 [2] tensor on the table's device, or a (lo, hi) pair")
+    n = int(n_words)
+    cap = max_compressed_words(n)
+    n_seg = (cap + 1023) // 1024
+    if scratch is None:
+        scratch = torch.empty(int(lib().wah_bsi_range_scratch_bytes(n, k)), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+    if out_offsets is None:
+        out_offsets = torch.zeros(n_seg + 1, dtype=torch.int64, device=dev)
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    sp = _stream_ptr(torch)
+    _check(lib().wah_bsi_range_indexed_device(n, k, table.data_ptr(), bounds.data_ptr(), BSI_EXISTS if exists else 0, out.data_ptr(),
+                                              out.numel(), count.data_ptr(), out_offsets.data_ptr(), scratch.data_ptr(),
+                                              scratch.numel(), sp), "wah_bsi_range_indexed_device")
+    if not check:
+        return out, count, out_offsets
+    _check(lib().wah_bsi_range_status(scratch.data_ptr(), n, k, sp), "bsi_range")
     return out[: int(count.item())], out_offsets
 
 

@@ -262,6 +262,103 @@ def index_from_keys(wah, keys, n_values, n_words_per_column=None, check=True):
     return stream, seg_offsets, n
 
 
+def bsi_from_values(wah, values, n_bits, n_words_per_column=None, exists=None):
+    """The bit-sliced index of a value column (O'Neil & Quass): one bitmap per BIT of the value instead of one per distinct
+    value, what a price, a timestamp or an id needs.  values: an int64 device tensor with one value in [0, 2^n_bits) per row,
+    n_bits <= 63; exists: a bool device tensor of the same length, the rows that have a value at all (their values elsewhere
+    are stored as 0), or None.  Building is plumbing: the decoded slice matrix [n_bits (+ 1), n_words], MOST significant slice
+    first and the existence row last, is made with torch ops and compressed in one launch (compress_column_matrix) -- slices
+    are mostly incompressible, which is the compressor's own road.  n_words_per_column defaults to ceil(rows / 32) rounded up
+    to a multiple of 992.  Returns (stream, seg_offsets, n_words_per_column, n_bits, has_exists): the first three go into
+    column_operand_table as a column matrix's do (slice i is column i, the existence bitmap column n_bits), the tuple as a
+    whole into range_column, compare_column and sum_column_where."""
+    import torch
+
+    if values.dtype != torch.int64 or values.dim() != 1 or not values.is_cuda:
+        raise ValueError("values: a one-dimensional int64 device tensor")
+    n_bits, rows = int(n_bits), int(values.numel())
+    if not 1 <= n_bits <= 63:
+        raise ValueError("between 1 and 63 bits")
+    if exists is not None and (exists.dtype != torch.bool or tuple(exists.shape) != (rows,) or exists.device != values.device):
+        raise ValueError("exists: a bool tensor of the values' length on their device")
+    if n_words_per_column is None:
+        n_words_per_column = max(-(-((rows + 31) // 32) // SEGMENT_WORDS), 1) * SEGMENT_WORDS
+    n = int(n_words_per_column)
+    if n % SEGMENT_WORDS or n <= 0 or 32 * n < rows:
+        raise ValueError("columns are a multiple of 992 words long and hold every row")
+    if rows:
+        lo, hi = (int(v) for v in torch.aminmax(values))
+        if lo < 0 or hi >= 1 << n_bits:
+            raise ValueError(f"values outside [0, 2^{n_bits})")
+    dev = values.device
+    weights = torch.ones(32, dtype=torch.int64, device=dev) << torch.arange(32, dtype=torch.int64, device=dev)
+
+    def pack(bits, row):  # bits: int64 0 / 1 per row -> the bitmap's words, position 32 * word + bit
+        padded = torch.zeros(32 * n, dtype=torch.int64, device=dev)
+        padded[:rows] = bits
+        words = (padded.view(n, 32) * weights).sum(1)
+        row.copy_(torch.where(words >= 1 << 31, words - (1 << 32), words))
+
+    have = None if exists is None else exists.to(torch.int64)
+    matrix = torch.empty((n_bits + (exists is not None), n), dtype=torch.int32, device=dev)
+    for i in range(n_bits):
+        bits = (values >> (n_bits - 1 - i)) & 1
+        pack(bits if have is None else bits & have, matrix[i])
+    if have is not None:
+        pack(have, matrix[n_bits])
+    comp = wah.DeviceCompressor(matrix.numel(), device=dev, indexed=True)
+    stream, _ = compress_column_matrix(comp, matrix)
+    return stream, comp.seg_offsets, n, n_bits, exists is not None
+
+
+def range_column(wah, bsi, lo, hi, table=None, bounds=None, **reuse):
+    """`lo <= value <= hi` (both inclusive) over a bit-sliced attribute in one call (wah_bsi_range_indexed_device): bsi is what
+    bsi_from_values returned, lo and hi Python ints up to 2^64 - 1 -- an empty range is all zeros, hi beyond the attribute's
+    width its maximum.  table / bounds: an existing [n_bits (+ 1), 3] slice table and int64 [2] bounds tensor to overwrite in
+    place -- what a captured graph replayed with another range needs; reuse: scratch / out / out_offsets / check of
+    api.bsi_range_device.  Returns (stream, seg_offsets) of the result bitmap, usable as a predicate's single column in
+    filter_columns: (stream, seg_offsets, [0], negate) with the result's own length as the column length."""
+    stream, seg_offsets, n, n_bits, has_exists = bsi
+    table = column_operand_table(stream, seg_offsets, n, list(range(n_bits + (1 if has_exists else 0))), out=table)
+    bounds = wah.bsi_bounds(lo, hi, stream.device, out=bounds)
+    return wah.bsi_range_device(table, bounds, n, exists=has_exists, **reuse)
+
+
+def compare_column(wah, bsi, op, c, **reuse):
+    """`value op c` over a bit-sliced attribute, op one of "<", "<=", ">", ">=", "==", as the matching range of range_column
+    ("<" with c == 0 and ">" with c at the attribute's maximum are empty ranges, not errors; != is == as a negated predicate of
+    filter_columns).  Arguments and result as range_column."""
+    n_bits = bsi[3]
+    top, c = (1 << n_bits) - 1, int(c)
+    if c < 0:
+        raise ValueError("values are unsigned")
+    empty = (1, 0)
+    if op == "<":
+        lo, hi = (0, c - 1) if c > 0 else empty
+    elif op == "<=":
+        lo, hi = 0, c
+    elif op == ">":
+        lo, hi = (c + 1, top) if c < top else empty
+    elif op == ">=":
+        lo, hi = (c, top) if c <= top else empty
+    elif op == "==":
+        lo, hi = (c, c) if c <= top else empty
+    else:
+        raise ValueError('op: one of "<", "<=", ">", ">=", "=="')
+    return range_column(wah, bsi, lo, min(hi, (1 << 64) - 1), **reuse)
+
+
+def sum_column_where(wah, bsi, mask_stream, mask_offsets):
+    """`SELECT SUM(value) WHERE <mask>` over a bit-sliced attribute without decoding a bitmap: ONE wah_count_masked_indexed_device
+    call with the mask (an indexed compressed bitmap of the attribute's column length: a filter_columns or range_column result)
+    as the one mask row and the slices as operands, then sum(count[i] << significance of slice i) in Python ints, which do not
+    overflow.  Rows outside an existence bitmap were stored as 0 and add nothing.  Returns a Python int."""
+    stream, seg_offsets, n, n_bits, _ = bsi
+    slices = column_operand_table(stream, seg_offsets, n, list(range(n_bits)))
+    counts = wah.count_masked_device([(mask_stream, mask_offsets)], slices, n).view(-1).tolist()
+    return sum(int(cnt) << (n_bits - 1 - i) for i, cnt in enumerate(counts))
+
+
 def compress_column_ranges(compressor, flat, lengths, wait=True):
     """Columns of DIFFERENT lengths (each a multiple of 992 words) stored back to back in `flat`: still one launch.
     Returns (stream, column_offsets) like compress_column_matrix: column c is stream[column_offsets[c] :

@@ -1370,6 +1370,68 @@ int wah_bitop_clauses_status(void *d_scratch, uint64_t n_words, uint64_t n_opera
     return wah_bitop_indexed_status(d_scratch, n_words, stream);
 }
 
+// lo <= value <= hi over a bit-sliced attribute (wah_bitop_list.hip, bsi_range_segments_kernel).  Scratch and road as the
+// clause call's: one decoded bitmap, then the compress passes.  The bounds stay in device memory: nothing here reads them.
+static_assert(WAH_BSI_MAX_SLICES == wah::kMaxBsiSlices, "one bound");
+size_t wah_bsi_range_scratch_bytes(uint64_t n_words, uint64_t n_slices) {
+    (void)n_slices;
+    return bitop_indexed_layout(n_words).total;
+}
+
+int wah_bsi_range_indexed_device(uint64_t n_words, uint64_t n_slices, const wah_bitop_operand *d_slices, const uint64_t *d_bounds,
+                                 unsigned flags, uint32_t *d_out, uint64_t out_capacity_words, uint64_t *d_out_words,
+                                 uint64_t *d_out_offsets, void *d_scratch, size_t scratch_bytes, void *stream) {
+    g_err[0] = 0;
+    if (n_slices < 1 || n_slices > WAH_BSI_MAX_SLICES || (flags & ~WAH_BSI_EXISTS)) {
+        set_err("between 1 and 64 slices, no flag besides WAH_BSI_EXISTS");
+        return WAH_ERR_ARG;
+    }
+    if (!d_slices || (reinterpret_cast<uintptr_t>(d_slices) & 7u) || !d_bounds || (reinterpret_cast<uintptr_t>(d_bounds) & 7u) ||
+        !d_scratch || (reinterpret_cast<uintptr_t>(d_scratch) & 255u)) {
+        set_err("null or misaligned slice table, bounds or scratch");
+        return WAH_ERR_ARG;
+    }
+    if (!d_out_words || (n_words && !d_out) || n_words >= (1ull << 40)) {
+        set_err("null output pointer, or 2^40 words or more");
+        return WAH_ERR_ARG;
+    }
+    const BitopIndexedLayout l = bitop_indexed_layout(n_words);
+    if (scratch_bytes < l.total) {
+        set_err("scratch too small");
+        return WAH_ERR_WORKSPACE;
+    }
+    char *sc = static_cast<char *>(d_scratch);
+    uint32_t *combined = reinterpret_cast<uint32_t *>(sc + l.bitmap);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint64_t groups = wah_max_compressed_words(n_words);
+    wah::BsiRangeArgs a = {};
+    a.g.first_segment = 0;
+    a.g.n_segments = ceil_div(groups, (uint64_t)wah::kSegGroups);
+    a.g.groups = groups;
+    // (as for a negated clause: with lo == 0 the last group's spare bits match and land in the one word more that
+    //  wah_decoded_words counts, which the bitmap area has room for and the compress passes, told n_words, never read)
+    a.g.out_words = wah_decoded_words(groups);
+    a.g.out = combined;
+    a.g.ctrl = reinterpret_cast<uint32_t *>(sc);
+    a.table = reinterpret_cast<const wah::BitopListOperand *>(d_slices);
+    a.bounds = d_bounds;
+    a.n_slices = (uint32_t)n_slices;
+    a.has_exists = (flags & WAH_BSI_EXISTS) ? 1u : 0u;
+    hipError_t e = wah::launch_clear(sc, wah::kCtlWords * sizeof(uint32_t), s); // (read by wah_bsi_range_status)
+    if (e == hipSuccess) e = wah::launch_bsi_range_segments(a, s);
+    if (e != hipSuccess) {
+        set_err("range sweep launch", e);
+        return WAH_ERR_HIP;
+    }
+    return compress_device_impl(combined, nullptr, 0, nullptr, n_words, d_out, out_capacity_words, d_out_words, d_out_offsets,
+                                sc + l.ws_c, l.ws_c_bytes, stream, true);
+}
+
+int wah_bsi_range_status(void *d_scratch, uint64_t n_words, uint64_t n_slices, void *stream) {
+    (void)n_slices;
+    return wah_bitop_indexed_status(d_scratch, n_words, stream);
+}
+
 // Set bits counted and listed in the compressed domain (wah_select.hip).  The scratch: control block, then the positions
 // call's rank table (one u64 per segment + 1) and the two upper levels of its scan (one u64 per 4096 entries of the level
 // below) -- it goes with n_words / 992, not with the operands' number or their words.

@@ -394,7 +394,148 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, 8) void bitop_clauses_segment
     for (int s = 0; s < (int)kSteps; ++s) seg_store(st, s, (u32)(64 * s) + lane < nvalid ? res[s] : 0u); // groups at and behind nvalid: zero
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// wah_bsi_range_indexed_device: lo <= value <= hi over a bit-sliced attribute (O'Neil & Quass) -- one bitmap per BIT of the
+// value, most significant first, and a range predicate is one sweep over them.  The walk is the clauses kernel's with one
+// clause per table row: the LDS accumulator holds the CURRENT slice (ORed into the zeroed image exactly as a clause is), and
+// when the consumer crosses to another row the slice is FOLDED into the sweep's state, which lives in registers, group
+// 64 s + lane.  The crossing is found from row numbers, so a slice whose segment was settled in the gather (one zero fill)
+// is folded like any other: a zero slice under a bound bit of 1 moves every still-equal row to "below".
+//
+// The fold is the O'Neil step for both bounds in one sweep.  With the slice's bits B and the bounds' bits l, h at this
+// significance (wave-uniform scalars):  GT |= EQlo & B if l == 0;  EQlo &= l ? B : ~B;  LT |= EQhi & ~B if h == 1;
+// EQhi &= h ? B : ~B;  result = (GT | EQlo) & (LT | EQhi).  Four arrays of sixteen are cut to three: while the bounds' bits
+// agree EQlo == EQhi and neither GT nor LT decides anything; at the first bit where they differ (l = 0, h = 1 for lo < hi)
+// the still-equal rows split into those that follow lo, all of them below hi already, and those that follow hi, all above
+// lo already.  From there on GT only grows inside the first set and LT inside the second, both mean "strictly inside", and
+// they share one array:  result = IN | EQlo | EQhi.  An empty range (lo > hi, or lo beyond the slices' width) walks and
+// checks everything all the same and stores zeros: the verdict depends neither on the data nor on the bounds.
+// The existence row, where there is one, is the last row and is folded as a plain AND.
+//
+// 48 registers of state do not fit beside the walk in the 64 that eight waves per SIMD allow: the kernel asks for four
+// (128 registers; its 16 KiB of LDS per workgroup would allow more).
+constexpr int kBsiWavesPerSimd = 4;
+
+__global__ __launch_bounds__(kSegDecodeWaves * 64, kBsiWavesPerSimd) void bsi_range_segments_kernel(const BsiRangeArgs a) {
+    __shared__ __attribute__((aligned(16))) u32 s_acc[kSegDecodeWaves][kSegGroups];
+    const u32 wave = wave_id(), lane = lane_id();
+    const u64 k = (u64)blockIdx.x * kSegDecodeWaves + wave;
+    if (k >= a.g.n_segments) return;
+    const u64 seg = a.g.first_segment + k;
+    const u64 g0 = seg * kSegGroups;
+    const u32 nvalid = a.g.groups - g0 < kSegGroups ? (u32)(a.g.groups - g0) : kSegGroups;
+    u32 *acc = s_acc[wave];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) reinterpret_cast<uint4 *>(acc)[64 * i + (int)lane] = make_uint4(0u, 0u, 0u, 0u);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+
+    // the bounds (wave-uniform, read here and nowhere on the host), clamped to the slices' width
+    const u32 ns = a.n_slices, n_rows = a.n_slices + a.has_exists;
+    const u64 vmax = ns >= 64u ? ~0ull : (1ull << ns) - 1ull;
+    const u64 lo = a.bounds[0], hi_given = a.bounds[1];
+    const bool none = lo > hi_given || lo > vmax; // an empty range
+    const u64 hi = hi_given < vmax ? hi_given : vmax;
+
+    u32 eq_lo[kSteps], eq_hi[kSteps], in[kSteps]; // rows equal to lo / to hi so far; rows strictly inside: group 64 s + lane
+#pragma unroll
+    for (int s = 0; s < (int)kSteps; ++s) {
+        eq_lo[s] = kOnes31;
+        eq_hi[s] = kOnes31;
+        in[s] = 0u;
+    }
+    u32 cur = 0;           // the row the accumulator holds (wave-uniform)
+    bool diverged = false; // a more significant bit of the bounds differed
+    // fold the current row into the state and begin the next one
+    auto fold = [&]() {
+        if (cur < ns) {
+            const u32 sig = ns - 1u - cur;
+            const bool l = (lo >> sig) & 1ull, h = (hi >> sig) & 1ull;
+            const u32 gt = diverged && !l ? kOnes31 : 0u, lt = diverged && h ? kOnes31 : 0u;
+            const u32 flip_lo = l ? 0u : kOnes31, flip_hi = h ? 0u : kOnes31;
+#pragma unroll
+            for (int s = 0; s < (int)kSteps; ++s) {
+                const u32 b = acc[64 * s + (int)lane];
+                in[s] |= (eq_lo[s] & b & gt) | (eq_hi[s] & ~b & lt);
+                eq_lo[s] &= b ^ flip_lo;
+                eq_hi[s] &= b ^ flip_hi;
+            }
+            diverged = diverged || l != h;
+        } else { // the existence bitmap
+#pragma unroll
+            for (int s = 0; s < (int)kSteps; ++s) {
+                const u32 b = acc[64 * s + (int)lane];
+                in[s] &= b;
+                eq_lo[s] &= b;
+                eq_hi[s] &= b;
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+#pragma unroll
+        for (int i = 0; i < 4; ++i) reinterpret_cast<uint4 *>(acc)[64 * i + (int)lane] = make_uint4(0u, 0u, 0u, 0u);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        ++cur;
+    };
+
+    const ListOp m = list_op(1u); // a slice is ORed into the zeroed image
+    bool lane_bad = false, empty_word = false;
+    bool sums_ok = true;
+#pragma nounroll
+    for (u32 j0 = 0; j0 < n_rows; j0 += 64u) {
+        const ListChunk ch = list_gather(a.table, j0, n_rows, seg, nvalid, m.fill, lane);
+        lane_bad |= ch.bad;
+        const u64 live = __ballot(ch.cnt != 0u);
+        ListCursor prod = list_first(live), cons = prod;
+        ListPair q[kListDepth];
+#pragma unroll
+        for (int i = 0; i < kListDepth; ++i) {
+            list_issue(q[i], prod, ch, lane);
+            list_advance(prod, ch, live);
+        }
+        u32 pos = 0;
+#pragma nounroll
+        while (cons.j < 64u) {
+#pragma unroll
+            for (int i = 0; i < kListDepth; ++i) {
+                if (cons.j < 64u) { // wave-uniform
+                    const u32 cnt = (u32)__builtin_amdgcn_readlane((int)ch.cnt, (int)cons.j);
+                    const u32 wi = 128u * cons.b;
+                    if (cons.b == 0u) {
+                        pos = 0u;
+#pragma nounroll
+                        while (cur < j0 + cons.j) fold(); // this row's words begin: the rows in front of it are complete
+                    }
+                    list_apply_batch(acc, q[i][0], q[i][1], wi, cnt, pos, empty_word, m, lane);
+                    if (wi + 128u >= cnt) sums_ok = sums_ok && pos == nvalid; // the row's last batch
+                }
+                list_advance(cons, ch, live);
+                list_issue(q[i], prod, ch, lane);
+                list_advance(prod, ch, live);
+            }
+        }
+    }
+    // behind the last row: the last one, and in front of it those that had no words to apply
+#pragma nounroll
+    while (cur < n_rows) fold();
+    if (!sums_ok || __ballot(lane_bad || empty_word) != 0ull) {
+        if (lane == 0) atomicOr(a.g.ctrl + kCtlError, kErrStream);
+        return;
+    }
+    const SegStore st = seg_store_setup(a.g.out, a.g.out_words, seg, k, lane);
+#pragma unroll
+    for (int s = 0; s < (int)kSteps; ++s) {
+        const u32 r = none ? 0u : in[s] | eq_lo[s] | eq_hi[s];
+        seg_store(st, s, (u32)(64 * s) + lane < nvalid ? r : 0u); // groups at and behind nvalid: zero
+    }
+}
+
 } // namespace
+
+hipError_t launch_bsi_range_segments(const BsiRangeArgs &a, hipStream_t s) {
+    if (a.g.n_segments == 0) return hipSuccess;
+    const u64 grid = (a.g.n_segments + kSegDecodeWaves - 1) / kSegDecodeWaves;
+    hipLaunchKernelGGL(bsi_range_segments_kernel, dim3((unsigned)grid), dim3(kSegDecodeWaves * 64), 0, s, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_bitop_clauses_segments(const BitopClausesArgs &a, hipStream_t s) {
     if (a.g.n_segments == 0) return hipSuccess;

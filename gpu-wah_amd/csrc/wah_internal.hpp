@@ -239,6 +239,18 @@ struct BitopClausesArgs {
 };
 hipError_t launch_bitop_clauses_segments(const BitopClausesArgs &a, hipStream_t s);
 
+// wah_bsi_range_indexed_device (wah_bitop_list.hip): lo <= value <= hi over a bit-sliced attribute.  table: n_slices rows,
+// most significant slice first, then the existence bitmap if has_exists; bounds: lo, hi in DEVICE memory
+constexpr uint32_t kMaxBsiSlices = 64; // WAH_BSI_MAX_SLICES
+struct BsiRangeArgs {
+    SegmentsArgs g;
+    const BitopListOperand *table;
+    const uint64_t *bounds;
+    uint32_t n_slices;   // 1 .. 64
+    uint32_t has_exists; // 0 or 1: one more row
+};
+hipError_t launch_bsi_range_segments(const BsiRangeArgs &a, hipStream_t s);
+
 // ... on operands of few words per segment: their runs merged in the compressed domain, one lane per segment
 // (wah_bitop_runs.hip): count pass, scan of the tile totals, write pass
 struct BitopRunsArgs {

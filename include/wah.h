@@ -433,6 +433,43 @@ int wah_bitop_clauses_indexed_device(uint64_t n_words, uint64_t n_clauses, const
                                      void *stream);
 int wah_bitop_clauses_status(void *d_scratch, uint64_t n_words, uint64_t n_operands, uint64_t n_clauses, void *stream);
 
+/* `lo <= value <= hi` over a BIT-SLICED attribute in ONE call (O'Neil & Quass): an attribute of many distinct values -- a
+ * price, a timestamp, an id -- is stored as one bitmap per BIT of the value, n_slices of them, not one per value, and a range
+ * predicate is one most-significant-bit-first sweep over them.
+ *   d_slices: n_slices rows (1 <= n_slices <= WAH_BSI_MAX_SLICES), plus ONE more with WAH_BSI_EXISTS in flags, entries as for
+ *   the list call (8-byte aligned, windows into column matrices allowed, the length may be a capacity, a row may name the
+ *   not-yet-checked output of an earlier call on the stream).  The table is in sweep order: the value of row p (position
+ *   32 * word + bit) is the unsigned integer whose bit n_slices - 1 - i is bit p of table row i -- row 0 is the MOST
+ *   significant slice.  With WAH_BSI_EXISTS table row n_slices is the existence bitmap: the rows that have a value at all.
+ *   d_bounds: lo = d_bounds[0], hi = d_bounds[1], two uint64 in DEVICE memory, 8-byte aligned.
+ * The result is the bitmap of the rows with lo <= value <= hi, both inclusive, ANDed with the existence bitmap where there is
+ * one: word for word what compress() emits for that bitmap of n_words words (ragged ends included, pad bits never matter;
+ * n_words == 0: an empty stream); d_out_offsets (may be NULL) receives its segment index, so the result goes into the
+ * clause call as one more operand.  <, <=, >, >=, = are all ranges; != is = put through a negated clause of the clause call.
+ * Bounds are data, never errors: lo > hi gives all zeros; for n_slices < 64, hi >= 2^n_slices behaves as 2^n_slices - 1 and
+ * lo >= 2^n_slices gives all zeros.  WITHOUT an existence bitmap the rows of the bitmap beyond the caller's own row count
+ * (up to 32 * n_words) have the value 0 like any other row whose slices are all zero: they MATCH when lo == 0.
+ * Bounds and table are read by the device only: the call is asynchronous on `stream`, allocates nothing, never synchronises,
+ * and a captured graph replayed after d_bounds (and / or the table) was overwritten in place answers the NEW query.  One
+ * route: one wavefront per segment ORs a slice into an LDS image as the list call does, folds it into the sweep's state,
+ * which it keeps in registers, when the walk crosses to the next row, and the compress passes run over the one decoded
+ * bitmap that leaves.
+ *   d_scratch: wah_bsi_range_scratch_bytes(n_words, n_slices) bytes, 256-byte aligned, no initialisation; it EQUALS
+ *   wah_bitop_indexed_scratch_bytes(n_words) for every n_slices.
+ * Errors the host can see come back before any HIP call, the argument checks first: n_slices outside 1 .. 64, unknown flag
+ * bits, a null or misaligned table, bounds (8 B) or scratch (256 B), a null d_out_words, a null d_out with n_words > 0,
+ * n_words >= 2^40: WAH_ERR_ARG; too small a scratch: WAH_ERR_WORKSPACE.  Everything only the device sees is reported by
+ * wah_bsi_range_status(), which synchronises the stream: WAH_ERR_STREAM for everything the list call refuses in an operand,
+ * WAH_ERR_CAPACITY for too small an output.  EVERY row's every segment is checked: an empty range, or a result that has
+ * become all zeros, skips nothing, so the verdict depends neither on the data nor on the bounds. */
+#define WAH_BSI_MAX_SLICES 64u
+#define WAH_BSI_EXISTS 1u /* flags: the table has one more row behind the slices, the existence bitmap */
+size_t wah_bsi_range_scratch_bytes(uint64_t n_words, uint64_t n_slices);
+int wah_bsi_range_indexed_device(uint64_t n_words, uint64_t n_slices, const wah_bitop_operand *d_slices, const uint64_t *d_bounds,
+                                 unsigned flags, uint32_t *d_out, uint64_t out_capacity_words, uint64_t *d_out_words,
+                                 uint64_t *d_out_offsets, void *d_scratch, size_t scratch_bytes, void *stream);
+int wah_bsi_range_status(void *d_scratch, uint64_t n_words, uint64_t n_slices, void *stream);
+
 /* What a query wants from a result bitmap, WITHOUT decoding it: how many bits it has set (COUNT(*)) and which ones (row
  * numbers, with LIMIT / OFFSET).  A bitmap of n_words words has its bits at positions p = 32 * word + bit, LSB first; group g,
  * bit j, of its stream is position 31 * g + j.  "Set bits" are the positions p < 32 * n_words whose bit is 1: the 0 to 30 pad
