@@ -50,6 +50,12 @@ from .api import (  # noqa: F401
     bsi_bounds,
     BSI_MAX_SLICES,
     BSI_EXISTS,
+    bsi_kth_device,
+    bsi_kth_query,
+    BSI_KTH_ASCENDING,
+    BSI_KTH_DESCENDING,
+    BSI_KTH_QUANTILE,
+    BSI_KTH_MAX_FILTERS,
     count_device,
     count_masked_device,
     positions_device,

@@ -69,6 +69,9 @@ ABI_SYMBOLS = {
     "wah_bsi_range_scratch_bytes": (_sz, [_u64, _u64]),
     "wah_bsi_range_indexed_device": (_int, [_u64, _u64, _vp, _vp, ctypes.c_uint, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
     "wah_bsi_range_status": (_int, [_vp, _u64, _u64, _vp]),
+    "wah_bsi_kth_scratch_bytes": (_sz, [_u64, _u64]),
+    "wah_bsi_kth_indexed_device": (_int, [_u64, _u64, _u64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "wah_bsi_kth_status": (_int, [_vp, _vp]),
     "wah_select_scratch_bytes": (_sz, [_u64, _u64]),
     "wah_count_list_indexed_device": (_int, [_u64, _u64, _vp, _vp, _vp, _sz, _vp]),
     "wah_count_masked_indexed_device": (_int, [_u64, _u64, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
@@ -654,6 +657,67 @@ def bsi_range_device(table, bounds, n_words, exists=False, scratch=None, out=Non
         return out, count, out_offsets
     _check(lib().wah_bsi_range_status(scratch.data_ptr(), n, k, sp), "bsi_range")
     return out[: int(count.item())], out_offsets
+
+
+BSI_KTH_ASCENDING, BSI_KTH_DESCENDING, BSI_KTH_QUANTILE = 0, 1, 2  # WAH_BSI_KTH_*
+BSI_KTH_MAX_FILTERS = 64  # WAH_BSI_KTH_MAX_FILTERS
+
+
+def bsi_kth_query(kind, a, b=1, device="cuda:0", out=None):
+    """The query of wah_bsi_kth_indexed_device as an int64 device tensor [3]: {kind, a, b}, three Python ints in 0 .. 2^64 - 1
+    stored as their two's-complement bit patterns.  BSI_KTH_ASCENDING / BSI_KTH_DESCENDING: rank a from the bottom / the top,
+    0-based; BSI_KTH_QUANTILE: rank floor(a * (total - 1) / b) from the bottom.  Nothing is judged here: an unknown kind, b == 0
+    or a > b are answered by the device with found = 0.  out: an existing tensor to overwrite in place -- what a captured graph
+    replayed with another query needs."""
+    import torch
+
+    words = []
+    for v in (kind, a, b):
+        v = int(v)
+        if not 0 <= v < 1 << 64:
+            raise WahError("a query word is an unsigned integer below 2^64")
+        words.append(v - (1 << 64) if v >= 1 << 63 else v)
+    t = torch.tensor(words, dtype=torch.int64)
+    if out is None:
+        return t.to(device)
+    out.copy_(t)
+    return out
+
+
+def bsi_kth_device(table, query, n_words, n_filters, scratch=None, result=None, check=True):
+    """The value of a given rank among the rows the filters select, over a bit-sliced attribute, in one call
+    (wah_bsi_kth_indexed_device).  table: a list of (stream, seg_offsets) pairs or a ready [rows, 3] table (bitop_operand_table,
+    columns.column_operand_table): n_filters filter rows FIRST, then one row per slice, MOST significant first.  query: an int64
+    device tensor [3] (bsi_kth_query; only the device reads it) or a (kind, a, b) triple of Python ints.  Returns the int64
+    device tensor [5] {found, value, total, less, equal} (64-bit patterns: a value at or above 2^63 reads as negative).
+    scratch / result: reuse these tensors; check=False: only enqueue (the caller reads wah_bsi_kth_status later)."""
+    torch = _torch()
+    if not isinstance(table, torch.Tensor):
+        table = bitop_operand_table(table)
+    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 3 or not table.is_cuda or not table.is_contiguous():
+        raise WahError("a row table is a contiguous int64 CUDA tensor of shape [rows, 3]")
+    dev = table.device
+    f = int(n_filters)
+    k = int(table.shape[0]) - f
+    if not 0 <= f <= BSI_KTH_MAX_FILTERS or not 1 <= k <= BSI_MAX_SLICES:
+        raise WahError("at most 64 filter rows, then between 1 and 64 slices")
+    if not isinstance(query, torch.Tensor):
+        query = bsi_kth_query(*query, device=dev)
+    if query.dtype != torch.int64 or tuple(query.shape) != (3,) or query.device != dev or not query.is_contiguous():
+        raise WahError("query: a contiguous int64 [3] tensor on the table's device, or a (kind, a, b) triple")
+    n = int(n_words)
+    if scratch is None:
+        scratch = torch.empty(int(lib().wah_bsi_kth_scratch_bytes(n, k)), dtype=torch.uint8, device=dev)
+    if result is None:
+        result = torch.empty(5, dtype=torch.int64, device=dev)
+    elif result.dtype != torch.int64 or tuple(result.shape) != (5,) or result.device != dev or not result.is_contiguous():
+        raise WahError("result: a contiguous int64 [5] tensor on the table's device")
+    sp = _stream_ptr(torch)
+    _check(lib().wah_bsi_kth_indexed_device(n, f, k, table.data_ptr(), query.data_ptr(), result.data_ptr(), scratch.data_ptr(),
+                                            scratch.numel(), sp), "wah_bsi_kth_indexed_device")
+    if check:
+        _check(lib().wah_bsi_kth_status(scratch.data_ptr(), sp), "bsi_kth")
+    return result
 
 
 def count_device(operands_or_table, n_words, scratch=None, counts=None, check=True):

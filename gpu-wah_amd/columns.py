@@ -359,6 +359,97 @@ def sum_column_where(wah, bsi, mask_stream, mask_offsets):
     return sum(int(cnt) << (n_bits - 1 - i) for i, cnt in enumerate(counts))
 
 
+def _kth_column(wah, bsi, query, mask, reuse):
+    """One wah_bsi_kth_indexed_device call over a bsi_from_values result: the filters -- the mask, then the existence bitmap --
+    in front of the slices.  Returns the five result words as Python ints in 0 .. 2^64 - 1."""
+    import torch
+
+    stream, seg_offsets, n, n_bits, has_exists = bsi
+    ids = ([n_bits] if has_exists else []) + list(range(n_bits))
+    n_mask = 0 if mask is None else 1
+    table = torch.empty((n_mask + len(ids), 3), dtype=torch.int64, device=stream.device)
+    if mask is not None:
+        mask_stream, mask_offsets = mask
+        table[0] = torch.tensor([mask_stream.data_ptr(), mask_stream.numel(), mask_offsets.data_ptr()], dtype=torch.int64)
+    column_operand_table(stream, seg_offsets, n, ids, out=table[n_mask:])
+    result = wah.bsi_kth_device(table, query, n, n_mask + (1 if has_exists else 0), **reuse)
+    return [int(v) & ((1 << 64) - 1) for v in result.tolist()]
+
+
+def kth_column_where(wah, bsi, k, mask=None, largest=False, **reuse):
+    """The k-th smallest (largest=True: k-th largest) value, k counted from 0, of a bit-sliced attribute among the rows of a mask,
+    in one call and without decoding a bitmap (wah_bsi_kth_indexed_device).  bsi: what bsi_from_values returned; mask: (stream,
+    seg_offsets) of an indexed compressed bitmap of the attribute's column length -- a filter_columns or range_column result --
+    or None for every row.  The attribute's existence bitmap, when it has one, is a filter too; without one every row of the
+    column counts, those behind the caller's own with the value 0.  reuse: scratch / result of api.bsi_kth_device.  Returns
+    (value, total): total the rows selected, value None when there are not more than k of them."""
+    kind = wah.BSI_KTH_DESCENDING if largest else wah.BSI_KTH_ASCENDING
+    found, value, total, _, _ = _kth_column(wah, bsi, (kind, int(k), 1), mask, reuse)
+    return (value if found else None), total
+
+
+def quantile_column_where(wah, bsi, num, den, mask=None, **reuse):
+    """The value of rank floor(num * (total - 1) / den) from the bottom, 0 <= num <= den, den > 0: 0/1 the minimum, 1/2 the
+    lower median, 99/100 the 99th percentile, 1/1 the maximum.  Arguments and result as kth_column_where; value is None when no
+    row is selected."""
+    num, den = int(num), int(den)
+    if den <= 0 or not 0 <= num <= den:
+        raise ValueError("a quantile is num / den with 0 <= num <= den and den > 0")
+    found, value, total, _, _ = _kth_column(wah, bsi, (wah.BSI_KTH_QUANTILE, num, den), mask, reuse)
+    return (value if found else None), total
+
+
+def min_column_where(wah, bsi, mask=None, **reuse):
+    """`SELECT MIN(value) WHERE <mask>`: quantile_column_where at 0/1."""
+    return quantile_column_where(wah, bsi, 0, 1, mask, **reuse)
+
+
+def max_column_where(wah, bsi, mask=None, **reuse):
+    """`SELECT MAX(value) WHERE <mask>`: quantile_column_where at 1/1."""
+    return quantile_column_where(wah, bsi, 1, 1, mask, **reuse)
+
+
+def median_column_where(wah, bsi, mask=None, **reuse):
+    """The lower median: quantile_column_where at 1/2."""
+    return quantile_column_where(wah, bsi, 1, 2, mask, **reuse)
+
+
+def top_rows(wah, bsi, k, mask=None, largest=True):
+    """`SELECT rowid ... WHERE <mask> ORDER BY value DESC LIMIT k` (largest=False: ASC) as row numbers, without decoding a bitmap:
+    the k-th value t is the threshold (wah_bsi_kth_indexed_device); the rows strictly beyond it are `value > t` (or `< t`) by
+    range_column, ANDed with the mask by filter_columns and listed by api.positions_device; the rows of `value == t` fill up
+    the rest, the first k - count of them in row order.  Plumbing over existing calls, with host reads of the result words in
+    between.  Returns an int64 tensor of min(k, selected rows) row numbers: the strictly-better rows first, in row order,
+    then the ties, in row order."""
+    import torch
+
+    stream, _, n, n_bits, _ = bsi
+    k = int(k)
+    empty = torch.empty(0, dtype=torch.int64, device=stream.device)
+    if k <= 0:
+        return empty
+    kind = wah.BSI_KTH_DESCENDING if largest else wah.BSI_KTH_ASCENDING
+    found, t, total, less, equal = _kth_column(wah, bsi, (kind, k - 1, 1), mask, {})
+    if not found:
+        if total == 0:
+            return empty
+        k = total  # fewer rows than asked for: all of them, the last one's value the threshold
+        found, t, total, less, equal = _kth_column(wah, bsi, (kind, k - 1, 1), mask, {})
+    better = total - less - equal if largest else less
+
+    def rows_of(lo, hi, limit):
+        got, offs = range_column(wah, bsi, lo, hi)
+        if mask is not None:
+            got, offs = filter_columns(wah, [(got, offs, [0], False), (mask[0], mask[1], [0], False)], n)
+        return wah.positions_device(got, offs, n, limit=limit)[0]
+
+    parts = []
+    if better:
+        parts.append(rows_of(t + 1, (1 << n_bits) - 1, better) if largest else rows_of(0, t - 1, better))
+    parts.append(rows_of(t, t, k - better))
+    return torch.cat(parts)
+
+
 def compress_column_ranges(compressor, flat, lengths, wait=True):
     """Columns of DIFFERENT lengths (each a multiple of 992 words) stored back to back in `flat`: still one launch.
     Returns (stream, column_offsets) like compress_column_matrix: column c is stream[column_offsets[c] :

@@ -1432,6 +1432,85 @@ int wah_bsi_range_status(void *d_scratch, uint64_t n_words, uint64_t n_slices, v
     return wah_bitop_indexed_status(d_scratch, n_words, stream);
 }
 
+// The value of a given rank over a bit-sliced attribute (wah_bitop_list.hip, bsi_kth_pass_kernel / bsi_kth_decide_kernel).  The
+// scratch: control block, the decision state, then one histogram per pass and copy -- nothing of it goes with n_words.  The
+// query stays in device memory: nothing here reads it.
+static_assert(WAH_BSI_KTH_ASCENDING == 0 && WAH_BSI_KTH_DESCENDING == 1 && WAH_BSI_KTH_QUANTILE == 2, "the kinds the decide kernel knows");
+static_assert(WAH_BSI_KTH_MAX_FILTERS == wah::kBsiKthMaxFilters, "one bound");
+namespace {
+struct BsiKthLayout {
+    uint32_t passes;
+    size_t state, hist, total;
+};
+BsiKthLayout bsi_kth_layout(uint64_t n_slices) {
+    BsiKthLayout l;
+    if (n_slices < 1 || n_slices > WAH_BSI_MAX_SLICES) n_slices = WAH_BSI_MAX_SLICES; // (the size of a call that is refused anyway)
+    l.passes = (uint32_t)ceil_div(n_slices, (uint64_t)wah::kBsiKthDigitBits);
+    l.state = wah::kCtlWords * sizeof(uint32_t);
+    l.hist = l.state + round256(wah::kBsiKthStateWords * sizeof(uint64_t));
+    l.total = l.hist + round256((size_t)l.passes * wah::kBsiKthCopies * wah::kBsiKthBuckets * sizeof(uint64_t));
+    return l;
+}
+} // namespace
+
+size_t wah_bsi_kth_scratch_bytes(uint64_t n_words, uint64_t n_slices) {
+    (void)n_words;
+    return bsi_kth_layout(n_slices).total;
+}
+
+int wah_bsi_kth_indexed_device(uint64_t n_words, uint64_t n_filters, uint64_t n_slices, const wah_bitop_operand *d_rows,
+                               const uint64_t *d_query, uint64_t *d_result, void *d_scratch, size_t scratch_bytes, void *stream) {
+    g_err[0] = 0;
+    if (n_slices < 1 || n_slices > WAH_BSI_MAX_SLICES || n_filters > WAH_BSI_KTH_MAX_FILTERS) {
+        set_err("between 1 and 64 slices, at most 64 filters");
+        return WAH_ERR_ARG;
+    }
+    if (!d_rows || (reinterpret_cast<uintptr_t>(d_rows) & 7u) || !d_query || (reinterpret_cast<uintptr_t>(d_query) & 7u) || !d_result ||
+        (reinterpret_cast<uintptr_t>(d_result) & 7u) || !d_scratch || (reinterpret_cast<uintptr_t>(d_scratch) & 255u)) {
+        set_err("null or misaligned row table, query, result or scratch");
+        return WAH_ERR_ARG;
+    }
+    if (n_words >= (1ull << 40)) {
+        set_err("2^40 words or more");
+        return WAH_ERR_ARG;
+    }
+    const BsiKthLayout l = bsi_kth_layout(n_slices);
+    if (scratch_bytes < l.total) {
+        set_err("scratch too small");
+        return WAH_ERR_WORKSPACE;
+    }
+    char *sc = static_cast<char *>(d_scratch);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    wah::BsiKthArgs a = {};
+    a.table = reinterpret_cast<const wah::BitopListOperand *>(d_rows);
+    a.query = d_query;
+    a.result = d_result;
+    a.state = reinterpret_cast<uint64_t *>(sc + l.state);
+    a.hist = reinterpret_cast<uint64_t *>(sc + l.hist);
+    a.ctrl = reinterpret_cast<uint32_t *>(sc);
+    a.groups = wah_max_compressed_words(n_words);
+    a.n_segments = ceil_div(a.groups, (uint64_t)wah::kSegGroups);
+    a.n_filters = (uint32_t)n_filters;
+    a.n_slices = (uint32_t)n_slices;
+    a.pad_bits = (uint32_t)(31u * a.groups - 32u * n_words);
+    hipError_t e = wah::launch_clear(sc, l.total, s); // the control words (read by wah_bsi_kth_status), the state, the histograms
+    for (uint32_t p = 0; p < l.passes && e == hipSuccess; ++p) {
+        a.pass = p;
+        e = wah::launch_bsi_kth_pass(a, s);
+        if (e == hipSuccess) e = wah::launch_bsi_kth_decide(a, s);
+    }
+    if (e != hipSuccess) {
+        set_err("radix select launch", e);
+        return WAH_ERR_HIP;
+    }
+    return WAH_OK;
+}
+
+int wah_bsi_kth_status(void *d_scratch, void *stream) {
+    if (!d_scratch) return WAH_ERR_ARG;
+    return read_status(d_scratch, stream);
+}
+
 // Set bits counted and listed in the compressed domain (wah_select.hip).  The scratch: control block, then the positions
 // call's rank table (one u64 per segment + 1) and the two upper levels of its scan (one u64 per 4096 entries of the level
 // below) -- it goes with n_words / 992, not with the operands' number or their words.

@@ -528,7 +528,267 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, kBsiWavesPerSimd) void bsi_ra
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// wah_bsi_kth_indexed_device: the value of a given rank (MIN, MAX, a quantile, the k-th largest) among the rows that a set of
+// filter bitmaps selects, over the same bit-sliced attribute -- a radix select over the slices, most significant first.  The
+// value is resolved in DIGITS of kBsiKthDigitBits slices: pass p counts, for every pattern of digit p, the selected rows whose
+// more significant bits equal the prefix decided so far and whose digit is that pattern; a one-wave kernel behind it picks the
+// bucket that holds the rank and extends the prefix.  The order of the launches on the stream is the only synchronisation.
+//
+// A pass is the range kernel's walk over the filter rows and the slices up to the end of its digit, one wavefront per segment.
+// `eq` -- the rows still in the running -- lives in registers, group 64 s + lane, as eq_lo does there: it starts as the
+// segment's valid bits (the pad bits of the bitmap's last group cleared), is ANDed with every filter row, and with B or ~B of
+// every slice above the digit according to the prefix's bit (wave-uniform, read from the scratch).  The digit's own slices are
+// kept as they are: the last one never leaves the LDS image -- the last row of a walk is only ever folded behind the loop, and
+// there the counting takes its place --, the two in front of it go into registers of their own, and the first slice of a digit
+// of four into a second LDS image (eq and THREE arrays of sixteen beside the walk spill five registers at the 128 that four
+// waves per SIMD allow; eq and two are the range kernel's 48, and 32 KiB of LDS per workgroup still allow five workgroups).  Every
+// lane counts popcount(eq & pattern) for the 2^digit patterns, sixteen DPP sums make them the wave's, and lane b adds bucket b
+// with one 64-bit atomic if it is not zero.  Nothing of bitmap size is written, and nothing is kept per segment between the
+// passes: the next pass walks the filters and the slices above its digit again, which costs their words once more but needs
+// no state that goes with n_words -- sixteen words per lane and segment written and read back would be as many bytes as two
+// incompressible slices, per pass.
+//
+// A short last digit (n_slices no multiple of the width) is right-aligned: the slices it does not have read as zero, so only
+// the buckets below 2^(its width) are counted into.  Every pass walks and checks all of its rows whatever the prefix, the
+// query or the counts are, and the last pass walks every row of the table.
+constexpr int kBsiKthWavesPerSimd = 4;
+constexpr int kBsiKthInRegs = kBsiKthDigitBits >= 3u ? 2 : (int)kBsiKthDigitBits - 1; // slices of a digit held in registers
+constexpr bool kBsiKthInLds = kBsiKthDigitBits == 4u;                                  // ... and one more in an LDS image
+static_assert(kBsiKthDigitBits >= 1u && kBsiKthDigitBits <= 4u, "a digit is one to four slices");
+
+__global__ __launch_bounds__(kSegDecodeWaves * 64, kBsiKthWavesPerSimd) void bsi_kth_pass_kernel(const BsiKthArgs a) {
+    __shared__ __attribute__((aligned(16))) u32 s_acc[kSegDecodeWaves][kSegGroups];
+    __shared__ __attribute__((aligned(16))) u32 s_top[kBsiKthInLds ? kSegDecodeWaves : 1][kSegGroups]; // the slice of bucket bit 3
+    const u32 wave = wave_id(), lane = lane_id();
+    const u64 k = (u64)blockIdx.x * kSegDecodeWaves + wave;
+    if (k >= a.n_segments) return;
+    const u64 seg = k;
+    const u64 g0 = seg * kSegGroups;
+    const u32 nvalid = a.groups - g0 < kSegGroups ? (u32)(a.groups - g0) : kSegGroups;
+    u32 *acc = s_acc[wave];
+    u32 *top = s_top[kBsiKthInLds ? wave : 0u];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        reinterpret_cast<uint4 *>(acc)[64 * i + (int)lane] = make_uint4(0u, 0u, 0u, 0u);
+        if (kBsiKthInLds) reinterpret_cast<uint4 *>(top)[64 * i + (int)lane] = make_uint4(0u, 0u, 0u, 0u); // (a short digit has no such slice)
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+
+    // the rows of this pass (wave-uniform): the filters, then the slices up to the end of digit `pass`
+    const u32 nf = a.n_filters, ns = a.n_slices;
+    const u32 digit_first = a.pass * kBsiKthDigitBits;
+    const u32 digit_end = min(digit_first + kBsiKthDigitBits, ns);
+    const u32 n_rows = nf + digit_end;
+    const u64 prefix = a.state[kKthPrefix]; // what the passes in front of this one decided
+
+    u32 eq[kSteps];                           // selected rows whose bits above the digit equal the prefix: group 64 s + lane
+    u32 dg[kBsiKthInRegs ? kBsiKthInRegs : 1][kSteps]; // the digit's slices in front of its last: dg[j] is bit j + 1 of the bucket number
+    const u64 last_group = a.groups - 1ull - g0; // (beyond nvalid in every segment but the bitmap's last)
+#pragma unroll
+    for (int s = 0; s < (int)kSteps; ++s) {
+        const u32 g = (u32)(64 * s) + lane;
+        eq[s] = g >= nvalid ? 0u : (u64)g == last_group ? kOnes31 >> a.pad_bits : kOnes31;
+#pragma unroll
+        for (int j = 0; j < kBsiKthInRegs; ++j) dg[j][s] = 0u;
+    }
+    u32 cur = 0; // the row the accumulator holds (wave-uniform)
+    // fold the current row into the state and begin the next one (never the pass's last row: that one is counted)
+    auto fold = [&]() {
+        if (cur < nf + digit_first) {
+            // a filter: AND; a slice above the digit: AND with B or ~B by the prefix's bit
+            const u32 sig = ns - 1u - (cur - nf); // (not used for a filter)
+            const u32 flip = cur < nf || ((prefix >> (sig & 63u)) & 1ull) ? 0u : kOnes31;
+#pragma unroll
+            for (int s = 0; s < (int)kSteps; ++s) eq[s] &= acc[64 * s + (int)lane] ^ flip;
+        } else {
+            const u32 j = digit_end - 2u - (cur - nf); // 0 .. digit - 2
+#pragma unroll
+            for (int jj = 0; jj < kBsiKthInRegs; ++jj)
+                if (j == (u32)jj) {
+#pragma unroll
+                    for (int s = 0; s < (int)kSteps; ++s) dg[jj][s] = acc[64 * s + (int)lane];
+                }
+            if (kBsiKthInLds && j == (u32)kBsiKthInRegs) {
+#pragma unroll
+                for (int s = 0; s < (int)kSteps; ++s) top[64 * s + (int)lane] = acc[64 * s + (int)lane];
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+#pragma unroll
+        for (int i = 0; i < 4; ++i) reinterpret_cast<uint4 *>(acc)[64 * i + (int)lane] = make_uint4(0u, 0u, 0u, 0u);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        ++cur;
+    };
+
+    const ListOp m = list_op(1u); // a row is ORed into the zeroed image
+    bool lane_bad = false, empty_word = false;
+    bool sums_ok = true;
+#pragma nounroll
+    for (u32 j0 = 0; j0 < n_rows; j0 += 64u) {
+        const ListChunk ch = list_gather(a.table, j0, n_rows, seg, nvalid, m.fill, lane);
+        lane_bad |= ch.bad;
+        const u64 live = __ballot(ch.cnt != 0u);
+        ListCursor prod = list_first(live), cons = prod;
+        ListPair q[kListDepth];
+#pragma unroll
+        for (int i = 0; i < kListDepth; ++i) {
+            list_issue(q[i], prod, ch, lane);
+            list_advance(prod, ch, live);
+        }
+        u32 pos = 0;
+#pragma nounroll
+        while (cons.j < 64u) {
+#pragma unroll
+            for (int i = 0; i < kListDepth; ++i) {
+                if (cons.j < 64u) { // wave-uniform
+                    const u32 cnt = (u32)__builtin_amdgcn_readlane((int)ch.cnt, (int)cons.j);
+                    const u32 wi = 128u * cons.b;
+                    if (cons.b == 0u) {
+                        pos = 0u;
+#pragma nounroll
+                        while (cur < j0 + cons.j) fold(); // this row's words begin: the rows in front of it are complete
+                    }
+                    list_apply_batch(acc, q[i][0], q[i][1], wi, cnt, pos, empty_word, m, lane);
+                    if (wi + 128u >= cnt) sums_ok = sums_ok && pos == nvalid; // the row's last batch
+                }
+                list_advance(cons, ch, live);
+                list_issue(q[i], prod, ch, lane);
+                list_advance(prod, ch, live);
+            }
+        }
+    }
+    // behind the last row that had words: the rows in front of the pass's last one; that one stays in the image
+#pragma nounroll
+    while (cur + 1u < n_rows) fold();
+    if (!sums_ok || __ballot(lane_bad || empty_word) != 0ull) {
+        if (lane == 0) atomicOr(a.ctrl + kCtlError, kErrStream);
+        return;
+    }
+    // bucket b: the rows of eq whose digit is b -- bit 0 the image's slice, bit j + 1 dg[j], bit 3 the second image's
+    u32 count[kBsiKthBuckets];
+#pragma unroll
+    for (int b = 0; b < (int)kBsiKthBuckets; ++b) count[b] = 0u;
+#pragma unroll
+    for (int s = 0; s < (int)kSteps; ++s) {
+        const u32 low = acc[64 * s + (int)lane];
+        const u32 high = kBsiKthInLds ? top[64 * s + (int)lane] : 0u;
+#pragma unroll
+        for (int hi = 0; hi < (int)(kBsiKthBuckets / 2u); ++hi) {
+            u32 e = eq[s];
+#pragma unroll
+            for (int j = 0; j < kBsiKthInRegs; ++j) e &= (hi >> j) & 1 ? dg[j][s] : ~dg[j][s];
+            if (kBsiKthInLds) e &= (hi >> kBsiKthInRegs) & 1 ? high : ~high;
+            count[2 * hi + 1] += (u32)__builtin_popcount(e & low);
+            count[2 * hi] += (u32)__builtin_popcount(e & ~low);
+        }
+    }
+    u32 mine = 0; // lane b: bucket b of the wave
+#pragma unroll
+    for (int b = 0; b < (int)kBsiKthBuckets; ++b) {
+        const u32 t = wave_total32(count[b]);
+        if (lane == (u32)b) mine = t;
+    }
+    unsigned long long *hist = reinterpret_cast<unsigned long long *>(a.hist) + ((u64)a.pass * kBsiKthCopies + blockIdx.x % kBsiKthCopies) * kBsiKthBuckets;
+    if (lane < kBsiKthBuckets && mine != 0u) atomicAdd(hist + lane, (unsigned long long)mine);
+}
+
+// floor(x * y / d) for x <= d, d > 0: the 128-bit product by shift and subtract (one lane, once per call)
+__device__ __forceinline__ u64 kth_muldiv(u64 x, u64 y, u64 d) {
+    const u64 hi = __umul64hi(x, y), lo = x * y;
+    u64 rem = 0, quot = 0; // (the quotient is at most y: it fits)
+#pragma nounroll
+    for (int i = 127; i >= 0; --i) {
+        const u64 bit = i >= 64 ? (hi >> (i - 64)) & 1ull : (lo >> i) & 1ull;
+        const bool carry = rem >> 63;
+        rem = (rem << 1) | bit;
+        quot <<= 1;
+        if (carry || rem >= d) {
+            rem -= d;
+            quot |= 1ull;
+        }
+    }
+    return quot;
+}
+
+// One wave behind every pass: sums the copies of the pass's histogram (lane b: bucket b), and lane 0 decides.  Pass 0 turns
+// the query into a rank from the bottom (total = the sum of the first histogram; a rank from the top is total - 1 - rank); every
+// pass picks the bucket that holds the rank, adds the buckets below it to `less`, and puts its number into the prefix; the last
+// one writes the result.  A query that names no row (found = 0) changes nothing of what is walked.
+__global__ __launch_bounds__(64) void bsi_kth_decide_kernel(const BsiKthArgs a) {
+    __shared__ u64 s_hist[kBsiKthBuckets];
+    const u32 lane = lane_id();
+    if (lane < kBsiKthBuckets) {
+        u64 sum = 0;
+        for (u32 c = 0; c < kBsiKthCopies; ++c) sum += a.hist[((u64)a.pass * kBsiKthCopies + c) * kBsiKthBuckets + lane];
+        s_hist[lane] = sum;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const u32 ns = a.n_slices;
+    const u32 digit_end = min((a.pass + 1u) * kBsiKthDigitBits, ns);
+    const bool last = digit_end == ns;
+    u64 rank = a.state[kKthRank], less = a.state[kKthLess], total = a.state[kKthTotal];
+    bool found = a.state[kKthFound] != 0ull;
+    if (a.pass == 0u) {
+        total = 0;
+        for (u32 b = 0; b < kBsiKthBuckets; ++b) total += s_hist[b];
+        const u64 kind = a.query[0], qa = a.query[1], qb = a.query[2];
+        found = false;
+        if (total != 0ull) {
+            if (kind == 0ull || kind == 1ull) { // WAH_BSI_KTH_ASCENDING, WAH_BSI_KTH_DESCENDING
+                found = qa < total;
+                rank = kind == 0ull ? qa : total - 1ull - qa;
+            } else if (kind == 2ull && qb != 0ull && qa <= qb) { // WAH_BSI_KTH_QUANTILE
+                found = true;
+                rank = kth_muldiv(qa, total - 1ull, qb);
+            }
+        }
+        less = 0;
+        a.state[kKthTotal] = total;
+        a.state[kKthFound] = found ? 1ull : 0ull;
+    }
+    u64 equal = 0, bucket = 0;
+    if (found) {
+        u64 below = 0;
+        for (u32 b = 0; b < kBsiKthBuckets; ++b) {
+            const u64 h = s_hist[b];
+            if (rank < below + h) {
+                bucket = b;
+                equal = h;
+                break;
+            }
+            below += h;
+        }
+        rank -= below;
+        less += below;
+    }
+    const u64 prefix = a.state[kKthPrefix] | (bucket << (ns - digit_end));
+    a.state[kKthPrefix] = prefix;
+    a.state[kKthRank] = rank;
+    a.state[kKthLess] = less;
+    if (last) {
+        a.result[0] = found ? 1ull : 0ull;
+        a.result[1] = found ? prefix : 0ull;
+        a.result[2] = total;
+        a.result[3] = found ? less : 0ull;
+        a.result[4] = found ? equal : 0ull;
+    }
+}
+
 } // namespace
+
+hipError_t launch_bsi_kth_pass(const BsiKthArgs &a, hipStream_t s) {
+    if (a.n_segments == 0) return hipSuccess;
+    const u64 grid = (a.n_segments + kSegDecodeWaves - 1) / kSegDecodeWaves;
+    hipLaunchKernelGGL(bsi_kth_pass_kernel, dim3((unsigned)grid), dim3(kSegDecodeWaves * 64), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_bsi_kth_decide(const BsiKthArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(bsi_kth_decide_kernel, dim3(1), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_bsi_range_segments(const BsiRangeArgs &a, hipStream_t s) {
     if (a.g.n_segments == 0) return hipSuccess;

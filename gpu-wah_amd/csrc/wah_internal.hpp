@@ -251,6 +251,43 @@ struct BsiRangeArgs {
 };
 hipError_t launch_bsi_range_segments(const BsiRangeArgs &a, hipStream_t s);
 
+// wah_bsi_kth_indexed_device (wah_bitop_list.hip): the value of a given rank among the rows the filters select -- a radix select
+// over the slices, kBsiKthDigitBits of them per pass, most significant digit first.  table: n_filters filter rows, then
+// n_slices slice rows, most significant first; query: kind, a, b in DEVICE memory; result: found, value, total, less, equal.
+// state and hist lie in the scratch (cleared by the caller): what the decide kernel of one pass leaves for the next pass,
+// and per pass kBsiKthCopies histograms of kBsiKthBuckets counts, added into by the pass kernel's waves.
+#ifndef WAH_BSI_KTH_DIGIT_BITS
+#define WAH_BSI_KTH_DIGIT_BITS 4 // (32 incompressible slices of 32 MiB: 2: 2.63 ms, 3: 2.06, 4: 1.55 -- DESIGN.md 5.14)
+#endif
+#ifndef WAH_BSI_KTH_COPIES
+#define WAH_BSI_KTH_COPIES 8 // (the same: 1: 1.75 ms, 8: 1.55, 64: 1.56)
+#endif
+constexpr uint32_t kBsiKthDigitBits = WAH_BSI_KTH_DIGIT_BITS; // 1 .. 4
+constexpr uint32_t kBsiKthBuckets = 1u << kBsiKthDigitBits;
+constexpr uint32_t kBsiKthCopies = WAH_BSI_KTH_COPIES; // histograms per pass, chosen by workgroup index; each on 128-byte lines of its own
+constexpr uint32_t kBsiKthMaxFilters = 64;
+constexpr uint32_t kBsiKthStateWords = 16; // u64: kKth* below
+constexpr uint32_t kKthPrefix = 0; // the value's bits decided so far, at their own significance
+constexpr uint32_t kKthRank = 1;   // the rank from the bottom among the rows that share the prefix
+constexpr uint32_t kKthLess = 2;   // selected rows below the prefix's range
+constexpr uint32_t kKthFound = 3;  // 1: the query names a row
+constexpr uint32_t kKthTotal = 4;  // selected rows
+struct BsiKthArgs {
+    const BitopListOperand *table;
+    const uint64_t *query;
+    uint64_t *result;
+    uint64_t *state; // kBsiKthStateWords
+    uint64_t *hist;  // passes x kBsiKthCopies x kBsiKthBuckets
+    uint32_t *ctrl;
+    uint64_t groups, n_segments;
+    uint32_t n_filters; // 0 .. 64
+    uint32_t n_slices;  // 1 .. 64
+    uint32_t pass;      // 0 .. ceil(n_slices / kBsiKthDigitBits) - 1
+    uint32_t pad_bits;  // as SelectCountArgs
+};
+hipError_t launch_bsi_kth_pass(const BsiKthArgs &a, hipStream_t s);
+hipError_t launch_bsi_kth_decide(const BsiKthArgs &a, hipStream_t s);
+
 // ... on operands of few words per segment: their runs merged in the compressed domain, one lane per segment
 // (wah_bitop_runs.hip): count pass, scan of the tile totals, write pass
 struct BitopRunsArgs {

@@ -470,6 +470,52 @@ int wah_bsi_range_indexed_device(uint64_t n_words, uint64_t n_slices, const wah_
                                  uint64_t *d_out_offsets, void *d_scratch, size_t scratch_bytes, void *stream);
 int wah_bsi_range_status(void *d_scratch, uint64_t n_words, uint64_t n_slices, void *stream);
 
+/* The ORDER statistics of a bit-sliced attribute in ONE call -- `MIN(price) WHERE ...`, MAX, the median or any percentile, the
+ * k-th largest, the threshold of `ORDER BY price DESC LIMIT k`: the value of a given rank among the rows that a set of filter
+ * bitmaps selects (O'Neil & Quass; Rinfret, O'Neil & O'Neil).  It is a radix select over the slices, most significant first, all
+ * of it on the device, and nothing of bitmap size is written.
+ *   d_rows: n_filters + n_slices entries as for the list call (8-byte aligned, windows into column matrices allowed, the
+ *   length may be a capacity, a row may name the not-yet-checked output of an earlier call on the stream).  The FILTERS come
+ *   first, 0 <= n_filters <= WAH_BSI_KTH_MAX_FILTERS: bitmaps that are ANDed -- the attribute's existence bitmap, the result of
+ *   a clause or range call.  The slices follow in sweep order, exactly as for the range call: the first slice row is the MOST
+ *   significant, 1 <= n_slices <= WAH_BSI_MAX_SLICES.  The SELECTED rows are the positions p < 32 * n_words set in every
+ *   filter; the pad bits of the last group are never selected, whichever stream sets them.  With n_filters == 0 all
+ *   32 * n_words positions are selected: rows behind the caller's own row count then count with the value 0, as the range
+ *   call documents.
+ *   d_query: three uint64 in DEVICE memory, 8-byte aligned: {kind, a, b}.  WAH_BSI_KTH_ASCENDING: the value of rank a from
+ *   the bottom, 0-based (a = 0: MIN); WAH_BSI_KTH_DESCENDING: rank a from the top (a = 0: MAX; a = k - 1: the threshold of a
+ *   top-k); WAH_BSI_KTH_QUANTILE: rank floor(a * (total - 1) / b) from the bottom, the product taken in 128 bits, for b > 0
+ *   and a <= b -- 0/1 is MIN, 1/1 is MAX, 1/2 the lower median.  b is not read by the other two kinds.
+ *   d_result: five uint64, 8-byte aligned: {found, value, total, less, equal}.  total is the number of selected rows, less
+ *   the number of selected rows whose value is below `value`, equal the number with exactly `value` (so the rows of `value`
+ *   have the ranks less .. less + equal - 1 from the bottom).  The query is data, never an error: a rank at or beyond total,
+ *   total == 0, an unknown kind, b == 0 or a > b give found = 0, and value, less and equal are then 0; total is still right,
+ *   and everything is still walked and checked.  n_words == 0: total = 0.
+ * Table and query are read by the device only: the call is asynchronous on `stream`, allocates nothing, never synchronises,
+ * and a captured graph replayed after d_query (and / or the table) was overwritten in place answers the NEW query.  The value
+ * is resolved in digits of four slices (the last digit may be shorter): per digit one launch in which one wavefront per
+ * segment walks the filter rows and the slices down to the digit's end as the range call does, keeps the rows that still
+ * match the bits decided so far in registers, and adds the segment's count of every pattern of the digit into a histogram;
+ * and a one-wave launch that picks the bucket holding the rank.  No workgroup waits for another: the order of the launches is
+ * the only synchronisation -- 2 * ceil(n_slices / 4) launches and the scratch clear.  The cost goes with the words of the
+ * rows walked: the filters once per digit, slice i once per digit from its own on; no decoded bitmap exists at any point.
+ *   d_scratch: wah_bsi_kth_scratch_bytes(n_words, n_slices) bytes, 256-byte aligned, no initialisation: the control words,
+ *   the decision state and the histograms.  A multiple of 256, never 0; nothing in it goes with n_words or n_filters.
+ * Errors the host can see come back before any HIP call, the argument checks first: n_slices outside 1 .. 64, n_filters
+ * above 64, a null or misaligned table, query, result (8 B) or scratch (256 B), n_words >= 2^40: WAH_ERR_ARG; too small a
+ * scratch: WAH_ERR_WORKSPACE.  Everything only the device sees is reported by wah_bsi_kth_status(), which synchronises the
+ * stream: WAH_ERR_STREAM for everything the list call refuses in an operand.  EVERY row's every segment is checked in every
+ * launch that walks it, and the last digit's launch walks them all: the verdict depends neither on the data nor on the
+ * query.  The result of a refused call is unspecified.  wah_bsi_kth_status(NULL, ...): WAH_ERR_ARG. */
+#define WAH_BSI_KTH_MAX_FILTERS 64u
+#define WAH_BSI_KTH_ASCENDING 0u
+#define WAH_BSI_KTH_DESCENDING 1u
+#define WAH_BSI_KTH_QUANTILE 2u
+size_t wah_bsi_kth_scratch_bytes(uint64_t n_words, uint64_t n_slices);
+int wah_bsi_kth_indexed_device(uint64_t n_words, uint64_t n_filters, uint64_t n_slices, const wah_bitop_operand *d_rows,
+                               const uint64_t *d_query, uint64_t *d_result, void *d_scratch, size_t scratch_bytes, void *stream);
+int wah_bsi_kth_status(void *d_scratch, void *stream);
+
 /* What a query wants from a result bitmap, WITHOUT decoding it: how many bits it has set (COUNT(*)) and which ones (row
  * numbers, with LIMIT / OFFSET).  A bitmap of n_words words has its bits at positions p = 32 * word + bit, LSB first; group g,
  * bit j, of its stream is position 31 * g + j.  "Set bits" are the positions p < 32 * n_words whose bit is 1: the 0 to 30 pad
