@@ -428,6 +428,29 @@ def bitop_device(op, d_a, d_b, n_words):
     return out[: int(count.item())].clone()
 
 
+def _compressed_result(name, n_words, dev, scratch_bytes, enqueue, status, scratch, out, out_offsets, check):
+    """What the calls that return a compressed bitmap with its segment index share.  Allocates what the caller did not pass --
+    scratch of scratch_bytes() bytes, out of max_compressed_words words, out_offsets of one entry per segment + 1 -- and runs
+    enqueue(*tail), the C call `name` with its leading arguments bound: tail is what all of them end with, (out, its capacity,
+    count, out_offsets, scratch, its bytes, stream).  check=False: returns (out, count tensor, out_offsets); otherwise
+    status(scratch pointer, stream) is read and the result is (out[:count], out_offsets)."""
+    torch = _torch()
+    cap = max_compressed_words(n_words)
+    if scratch is None:
+        scratch = torch.empty(int(scratch_bytes()), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+    if out_offsets is None:
+        out_offsets = torch.zeros((cap + 1023) // 1024 + 1, dtype=torch.int64, device=dev)
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    sp = _stream_ptr(torch)
+    _check(enqueue(out.data_ptr(), out.numel(), count.data_ptr(), out_offsets.data_ptr(), scratch.data_ptr(), scratch.numel(), sp), name)
+    if not check:
+        return out, count, out_offsets
+    _check(status(scratch.data_ptr(), sp), name[len("wah_"):-len("_device")])
+    return out[: int(count.item())], out_offsets
+
+
 def bitop_indexed_device(op, d_a, a_offsets, d_b, b_offsets, n_words, scratch=None, out=None, out_offsets=None, check=True):
     """compress(A op B) from two compressed bitmaps that come with their segment indexes (wah_bitop_indexed_device).
     Returns (stream, seg_offsets) of the result; scratch / out / out_offsets: reuse these tensors; check=False: only
@@ -436,25 +459,11 @@ def bitop_indexed_device(op, d_a, a_offsets, d_b, b_offsets, n_words, scratch=No
     _as_words(torch, d_a)
     _as_words(torch, d_b)
     n = int(n_words)
-    cap = max_compressed_words(n)
-    n_seg = (cap + 1023) // 1024
-    sc_bytes = int(lib().wah_bitop_indexed_scratch_bytes(n))
-    if scratch is None:
-        scratch = torch.empty(sc_bytes, dtype=torch.uint8, device=d_a.device)
-    if out is None:
-        out = torch.empty(max(cap, 1), dtype=torch.int32, device=d_a.device)
-    if out_offsets is None:
-        out_offsets = torch.zeros(n_seg + 1, dtype=torch.int64, device=d_a.device)
-    count = torch.zeros(1, dtype=torch.int64, device=d_a.device)
-    sp = _stream_ptr(torch)
-    _check(lib().wah_bitop_indexed_device(OPS[op], n, d_a.data_ptr(), d_a.numel(), a_offsets.data_ptr(), d_b.data_ptr(),
-                                          d_b.numel(), b_offsets.data_ptr(), out.data_ptr(), out.numel(), count.data_ptr(),
-                                          out_offsets.data_ptr(), scratch.data_ptr(), scratch.numel(), sp),
-           "wah_bitop_indexed_device")
-    if not check:
-        return out, count, out_offsets
-    _check(lib().wah_bitop_indexed_status(scratch.data_ptr(), n, sp), "bitop_indexed")
-    return out[: int(count.item())], out_offsets
+    return _compressed_result(
+        "wah_bitop_indexed_device", n, d_a.device, lambda: lib().wah_bitop_indexed_scratch_bytes(n),
+        lambda *tail: lib().wah_bitop_indexed_device(OPS[op], n, d_a.data_ptr(), d_a.numel(), a_offsets.data_ptr(), d_b.data_ptr(),
+                                                     d_b.numel(), b_offsets.data_ptr(), *tail),
+        lambda sc, sp: lib().wah_bitop_indexed_status(sc, n, sp), scratch, out, out_offsets, check)
 
 
 def bitop_many_indexed_device(op, operands, n_words, scratch=None, out=None, out_offsets=None, check=True):
@@ -464,29 +473,14 @@ def bitop_many_indexed_device(op, operands, n_words, scratch=None, out=None, out
     k = len(operands)
     for st, _ in operands:
         _as_words(torch, st)
-    dev = operands[0][0].device
     n = int(n_words)
-    cap = max_compressed_words(n)
-    n_seg = (cap + 1023) // 1024
-    sc_bytes = int(lib().wah_bitop_indexed_scratch_bytes(n))
-    if scratch is None:
-        scratch = torch.empty(sc_bytes, dtype=torch.uint8, device=dev)
-    if out is None:
-        out = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
-    if out_offsets is None:
-        out_offsets = torch.zeros(n_seg + 1, dtype=torch.int64, device=dev)
-    count = torch.zeros(1, dtype=torch.int64, device=dev)
     streams = (ctypes.c_void_p * k)(*[st.data_ptr() for st, _ in operands])
     words = (ctypes.c_uint64 * k)(*[st.numel() for st, _ in operands])
     offsets = (ctypes.c_void_p * k)(*[o.data_ptr() for _, o in operands])
-    sp = _stream_ptr(torch)
-    _check(lib().wah_bitop_many_indexed_device(OPS[op], n, k, streams, words, offsets, out.data_ptr(), out.numel(),
-                                               count.data_ptr(), out_offsets.data_ptr(), scratch.data_ptr(), scratch.numel(), sp),
-           "wah_bitop_many_indexed_device")
-    if not check:
-        return out, count, out_offsets
-    _check(lib().wah_bitop_indexed_status(scratch.data_ptr(), n, sp), "bitop_many_indexed")
-    return out[: int(count.item())], out_offsets
+    return _compressed_result(
+        "wah_bitop_many_indexed_device", n, operands[0][0].device, lambda: lib().wah_bitop_indexed_scratch_bytes(n),
+        lambda *tail: lib().wah_bitop_many_indexed_device(OPS[op], n, k, streams, words, offsets, *tail),
+        lambda sc, sp: lib().wah_bitop_indexed_status(sc, n, sp), scratch, out, out_offsets, check)
 
 
 class BitopOperand(ctypes.Structure):
@@ -510,34 +504,27 @@ def bitop_operand_table(operands, device=None):
     return torch.tensor(rows, dtype=torch.int64, device=operands[0][0].device if device is None else device)
 
 
+def _operand_table(x, what="an operand table"):
+    """x as the [k, 3] table the device reads: a list of (stream, seg_offsets) pairs is converted (bitop_operand_table), a
+    ready tensor is checked."""
+    torch = _torch()
+    table = x if isinstance(x, torch.Tensor) else bitop_operand_table(x)
+    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 3 or table.shape[0] < 1 or not table.is_cuda or not table.is_contiguous():
+        raise WahError(f"{what} is a contiguous int64 CUDA tensor of shape [k, 3], k >= 1")
+    return table
+
+
 def bitop_list_indexed_device(op, operands, n_words, scratch=None, out=None, out_offsets=None, check=True):
     """compress(A op B op C ...) for ANY number of operands in one call (wah_bitop_list_indexed_device).  operands: a list of
     (stream, seg_offsets) pairs, or a ready table (bitop_operand_table, columns.column_operand_table) -- only the device
     reads it.  Returns as bitop_indexed_device: (stream, seg_offsets), or with check=False, which only enqueues,
     (out, count tensor, out_offsets)."""
-    torch = _torch()
-    table = operands if isinstance(operands, torch.Tensor) else bitop_operand_table(operands)
-    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 3 or table.shape[0] < 1 or not table.is_cuda or not table.is_contiguous():
-        raise WahError("an operand table is a contiguous int64 CUDA tensor of shape [k, 3], k >= 1")
-    dev = table.device
+    table = _operand_table(operands)
     n, k = int(n_words), int(table.shape[0])
-    cap = max_compressed_words(n)
-    n_seg = (cap + 1023) // 1024
-    if scratch is None:
-        scratch = torch.empty(int(lib().wah_bitop_list_scratch_bytes(n, k)), dtype=torch.uint8, device=dev)
-    if out is None:
-        out = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
-    if out_offsets is None:
-        out_offsets = torch.zeros(n_seg + 1, dtype=torch.int64, device=dev)
-    count = torch.zeros(1, dtype=torch.int64, device=dev)
-    sp = _stream_ptr(torch)
-    _check(lib().wah_bitop_list_indexed_device(OPS[op], n, k, table.data_ptr(), out.data_ptr(), out.numel(), count.data_ptr(),
-                                               out_offsets.data_ptr(), scratch.data_ptr(), scratch.numel(), sp),
-           "wah_bitop_list_indexed_device")
-    if not check:
-        return out, count, out_offsets
-    _check(lib().wah_bitop_list_status(scratch.data_ptr(), n, k, sp), "bitop_list_indexed")
-    return out[: int(count.item())], out_offsets
+    return _compressed_result(
+        "wah_bitop_list_indexed_device", n, table.device, lambda: lib().wah_bitop_list_scratch_bytes(n, k),
+        lambda *tail: lib().wah_bitop_list_indexed_device(OPS[op], n, k, table.data_ptr(), *tail),
+        lambda sc, sp: lib().wah_bitop_list_status(sc, n, k, sp), scratch, out, out_offsets, check)
 
 
 CLAUSE_NEGATE = -(1 << 63)  # WAH_CLAUSE_NEGATE (bit 63) as the int64 a clause table holds
@@ -570,29 +557,14 @@ def bitop_clauses_indexed_device(clauses, n_words, scratch=None, out=None, out_o
     torch = _torch()
     ready = isinstance(clauses, (tuple, list)) and len(clauses) == 2 and all(isinstance(t, torch.Tensor) for t in clauses)
     table, ends = clauses if ready else bitop_clause_table(clauses)
-    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 3 or table.shape[0] < 1 or not table.is_cuda or not table.is_contiguous():
-        raise WahError("an operand table is a contiguous int64 CUDA tensor of shape [k, 3], k >= 1")
+    table = _operand_table(table)
     if ends.dtype != torch.int64 or ends.dim() != 1 or not 1 <= ends.shape[0] <= table.shape[0] or ends.device != table.device or not ends.is_contiguous():
         raise WahError("clause ends are a contiguous int64 tensor of 1 to k entries on the operand table's device")
-    dev = table.device
     n, k, c = int(n_words), int(table.shape[0]), int(ends.shape[0])
-    cap = max_compressed_words(n)
-    n_seg = (cap + 1023) // 1024
-    if scratch is None:
-        scratch = torch.empty(int(lib().wah_bitop_clauses_scratch_bytes(n, k, c)), dtype=torch.uint8, device=dev)
-    if out is None:
-        out = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
-    if out_offsets is None:
-        out_offsets = torch.zeros(n_seg + 1, dtype=torch.int64, device=dev)
-    count = torch.zeros(1, dtype=torch.int64, device=dev)
-    sp = _stream_ptr(torch)
-    _check(lib().wah_bitop_clauses_indexed_device(n, c, ends.data_ptr(), k, table.data_ptr(), out.data_ptr(), out.numel(),
-                                                  count.data_ptr(), out_offsets.data_ptr(), scratch.data_ptr(), scratch.numel(), sp),
-           "wah_bitop_clauses_indexed_device")
-    if not check:
-        return out, count, out_offsets
-    _check(lib().wah_bitop_clauses_status(scratch.data_ptr(), n, k, c, sp), "bitop_clauses_indexed")
-    return out[: int(count.item())], out_offsets
+    return _compressed_result(
+        "wah_bitop_clauses_indexed_device", n, table.device, lambda: lib().wah_bitop_clauses_scratch_bytes(n, k, c),
+        lambda *tail: lib().wah_bitop_clauses_indexed_device(n, c, ends.data_ptr(), k, table.data_ptr(), *tail),
+        lambda sc, sp: lib().wah_bitop_clauses_status(sc, n, k, c, sp), scratch, out, out_offsets, check)
 
 
 BSI_MAX_SLICES = 64  # WAH_BSI_MAX_SLICES
@@ -626,10 +598,7 @@ def bsi_range_device(table, bounds, n_words, exists=False, scratch=None, out=Non
     2^64 - 1 (bsi_bounds).  Returns as bitop_clauses_indexed_device: (stream, seg_offsets), or with check=False, which only
     enqueues, (out, count tensor, out_offsets)."""
     torch = _torch()
-    if not isinstance(table, torch.Tensor):
-        table = bitop_operand_table(table)
-    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 3 or not table.is_cuda or not table.is_contiguous():
-        raise WahError("a slice table is a contiguous int64 CUDA tensor of shape [rows, 3]")
+    table = _operand_table(table, "a slice table")
     dev = table.device
     k = int(table.shape[0]) - (1 if exists else 0)
     if not 1 <= k <= BSI_MAX_SLICES:
@@ -640,23 +609,10 @@ def bsi_range_device(table, bounds, n_words, exists=False, scratch=None, out=Non
     if bounds.dtype != torch.int64 or tuple(bounds.shape) != (2,) or bounds.device != dev or not bounds.is_contiguous():
         raise WahError("bounds: a contiguous int64 [2] tensor on the table's device, or a (lo, hi) pair")
     n = int(n_words)
-    cap = max_compressed_words(n)
-    n_seg = (cap + 1023) // 1024
-    if scratch is None:
-        scratch = torch.empty(int(lib().wah_bsi_range_scratch_bytes(n, k)), dtype=torch.uint8, device=dev)
-    if out is None:
-        out = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
-    if out_offsets is None:
-        out_offsets = torch.zeros(n_seg + 1, dtype=torch.int64, device=dev)
-    count = torch.zeros(1, dtype=torch.int64, device=dev)
-    sp = _stream_ptr(torch)
-    _check(lib().wah_bsi_range_indexed_device(n, k, table.data_ptr(), bounds.data_ptr(), BSI_EXISTS if exists else 0, out.data_ptr(),
-                                              out.numel(), count.data_ptr(), out_offsets.data_ptr(), scratch.data_ptr(),
-                                              scratch.numel(), sp), "wah_bsi_range_indexed_device")
-    if not check:
-        return out, count, out_offsets
-    _check(lib().wah_bsi_range_status(scratch.data_ptr(), n, k, sp), "bsi_range")
-    return out[: int(count.item())], out_offsets
+    return _compressed_result(
+        "wah_bsi_range_indexed_device", n, dev, lambda: lib().wah_bsi_range_scratch_bytes(n, k),
+        lambda *tail: lib().wah_bsi_range_indexed_device(n, k, table.data_ptr(), bounds.data_ptr(), BSI_EXISTS if exists else 0, *tail),
+        lambda sc, sp: lib().wah_bsi_range_status(sc, n, k, sp), scratch, out, out_offsets, check)
 
 
 BSI_KTH_ASCENDING, BSI_KTH_DESCENDING, BSI_KTH_QUANTILE = 0, 1, 2  # WAH_BSI_KTH_*
@@ -692,10 +648,7 @@ def bsi_kth_device(table, query, n_words, n_filters, scratch=None, result=None, 
     device tensor [5] {found, value, total, less, equal} (64-bit patterns: a value at or above 2^63 reads as negative).
     scratch / result: reuse these tensors; check=False: only enqueue (the caller reads wah_bsi_kth_status later)."""
     torch = _torch()
-    if not isinstance(table, torch.Tensor):
-        table = bitop_operand_table(table)
-    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 3 or not table.is_cuda or not table.is_contiguous():
-        raise WahError("a row table is a contiguous int64 CUDA tensor of shape [rows, 3]")
+    table = _operand_table(table, "a row table")
     dev = table.device
     f = int(n_filters)
     k = int(table.shape[0]) - f
@@ -727,9 +680,7 @@ def count_device(operands_or_table, n_words, scratch=None, counts=None, check=Tr
     word are never counted.  scratch / counts: reuse these tensors; check=False: only enqueue (the caller reads
     wah_select_status later)."""
     torch = _torch()
-    table = operands_or_table if isinstance(operands_or_table, torch.Tensor) else bitop_operand_table(operands_or_table)
-    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 3 or table.shape[0] < 1 or not table.is_cuda or not table.is_contiguous():
-        raise WahError("an operand table is a contiguous int64 CUDA tensor of shape [k, 3], k >= 1")
+    table = _operand_table(operands_or_table)
     dev = table.device
     n, k = int(n_words), int(table.shape[0])
     if scratch is None:
@@ -754,13 +705,7 @@ def count_masked_device(masks, operands, n_words, scratch=None, counts=None, che
     pad bits behind the bitmap's last word are never counted.  scratch / counts: reuse these tensors (scratch as for
     count_device); check=False: only enqueue (the caller reads wah_select_status later)."""
     torch = _torch()
-    tables = []
-    for what in (masks, operands):
-        table = what if isinstance(what, torch.Tensor) else bitop_operand_table(what)
-        if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 3 or table.shape[0] < 1 or not table.is_cuda or not table.is_contiguous():
-            raise WahError("a mask or operand table is a contiguous int64 CUDA tensor of shape [k, 3], k >= 1")
-        tables.append(table)
-    mt, ot = tables
+    mt, ot = _operand_table(masks, "a mask table"), _operand_table(operands)
     dev = ot.device
     if mt.device != dev:
         raise WahError("the mask table and the operand table are on one device")

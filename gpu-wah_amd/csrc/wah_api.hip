@@ -40,6 +40,34 @@ void set_err(const char *what, hipError_t e = hipSuccess) {
 inline uint64_t ceil_div(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
 inline size_t round256(size_t x) { return (x + 255) & ~(size_t)255; }
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+inline bool aligned(const void *p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) == 0; }
+
+// a call that is refused: the text wah_last_error() returns, and the code the call returns
+int refuse(const char *what, int rc, hipError_t e = hipSuccess) {
+    set_err(what, e);
+    return rc;
+}
+
+// a bitmap of n_words words: its 31-bit groups, its segments of kSegGroups groups, and the bits of its last group that lie
+// behind the bitmap (31 G - 32 n_words: 0 .. 30)
+struct SegGeometry {
+    uint64_t groups, n_segments;
+    uint32_t pad_bits;
+};
+SegGeometry seg_geometry(uint64_t n_words) {
+    SegGeometry g;
+    g.groups = wah_max_compressed_words(n_words);
+    g.n_segments = ceil_div(g.groups, (uint64_t)wah::kSegGroups);
+    g.pad_bits = (uint32_t)(31u * g.groups - 32u * n_words);
+    return g;
+}
+
+// what the indexed calls ask of their scratch, and of an operand table in device memory (wah_bitop_operand rows)
+inline bool scratch_ok(const void *d_scratch) { return d_scratch && aligned(d_scratch, 255); }
+inline bool table_ok(uint64_t n, const void *d_table, uint64_t n_words) {
+    return n >= 1 && n <= wah::kMaxBitopListOperands && d_table && aligned(d_table, 7) && n_words < (1ull << 40);
+}
+constexpr const char *kBadTable = "between 1 and 2^24 operands in an 8-byte aligned table, fewer than 2^40 words";
 
 // Workspace layouts.  Everything a launch stamps with its epoch lives in areas whose PLACE depends on the workspace's size
 // only, never on the size of the input: one workspace serves inputs of different sizes in turn (include/wah.h), and an
@@ -57,8 +85,9 @@ struct CompressLayout {
 // epoch stamp)
 CompressLayout compress_layout(uint64_t n_words, size_t workspace_bytes = 0) {
     CompressLayout l;
-    l.n_groups = wah_max_compressed_words(n_words);
-    l.n_segments = ceil_div(l.n_groups, wah::kSegGroups);
+    const SegGeometry g = seg_geometry(n_words);
+    l.n_groups = g.groups;
+    l.n_segments = g.n_segments;
     l.wave_segs = wah::compress_wave_segs(l.n_segments);
     l.n_tiles = ceil_div(l.n_segments, (uint64_t)wah::kCompressTileWaves * l.wave_segs);
     // sized for the shortest tiles: a workspace serves any smaller bitmap too
@@ -1011,8 +1040,7 @@ int wah_decompress_segments_device(const uint32_t *d_comp, uint64_t c_words, con
         set_err("workspace too small");
         return WAH_ERR_WORKSPACE;
     }
-    const uint64_t groups = wah_max_compressed_words(n_words); // G = ceil(32 n / 31)
-    const uint64_t all_segments = (groups + wah::kSegGroups - 1) / wah::kSegGroups;
+    const uint64_t groups = seg_geometry(n_words).groups, all_segments = seg_geometry(n_words).n_segments; // G = ceil(32 n / 31)
     if (first_segment > all_segments || n_segments > all_segments - first_segment) {
         set_err("segment range outside the bitmap");
         return WAH_ERR_ARG;
@@ -1061,7 +1089,7 @@ BitopIndexedLayout bitop_indexed_layout(uint64_t n_words) {
     l.decoded_capacity = n_words + 1; // ceil(31 G / 32) is n_words or n_words + 1
     l.ws_c_bytes = wah_compress_workspace_bytes(n_words);
     l.bitmap = round256(wah::kCtlWords * sizeof(uint32_t));
-    const uint64_t n_segments = ceil_div(wah_max_compressed_words(n_words), (uint64_t)wah::kSegGroups);
+    const uint64_t n_segments = seg_geometry(n_words).n_segments;
     l.runs_tiles = l.bitmap + round256(n_segments * sizeof(uint32_t));
     l.runs_temp = l.runs_tiles + round256((n_segments / 64 + 2) * sizeof(uint64_t));
     const size_t runs_end = l.runs_temp + round256((kRunsMaxWordsPerSeg * n_segments + 16) * sizeof(uint32_t));
@@ -1079,18 +1107,16 @@ BitopIndexedLayout bitop_indexed_layout(uint64_t n_words) {
 bool bitop_runs_route(int op, uint64_t n_words, int n, const uint32_t *const *comp, const uint64_t *c_words, const uint64_t *const *offs,
                       uint32_t *d_out, uint64_t out_capacity_words, uint64_t *d_out_words, uint64_t *d_out_offsets, char *sc,
                       const BitopIndexedLayout &l, hipStream_t s, int *rc) {
-    const uint64_t groups = wah_max_compressed_words(n_words);
-    const uint64_t n_segments = ceil_div(groups, (uint64_t)wah::kSegGroups);
+    const SegGeometry g = seg_geometry(n_words);
     uint64_t total = 0;
     for (int j = 0; j < n; ++j) total += c_words[j];
     g_last_bitop_route = WAH_BITOP_ROUTE_GROUPS;
     const char *force = wah::experiment_env("WAH_BITOP_ROUTE"); // (experiment builds: "runs" / "groups", tools/bitop_density_time.py)
     const uint64_t temp_words = (l.ws_c - l.runs_temp) / sizeof(uint32_t);
-    if (n_words == 0 || total + 16 > temp_words || (force ? force[0] != 'r' : total > kRunsMaxWordsPerSeg * n_segments)) return false;
+    if (n_words == 0 || total + 16 > temp_words || (force ? force[0] != 'r' : total > kRunsMaxWordsPerSeg * g.n_segments)) return false;
     g_last_bitop_route = WAH_BITOP_ROUTE_RUNS;
     if (!d_out_words || !d_out) {
-        set_err("null pointer");
-        *rc = WAH_ERR_ARG;
+        *rc = refuse("null pointer", WAH_ERR_ARG);
         return true;
     }
     wah::BitopRunsArgs a = {};
@@ -1101,8 +1127,8 @@ bool bitop_runs_route(int op, uint64_t n_words, int n, const uint32_t *const *co
     }
     a.n = n;
     a.op = op;
-    a.groups = groups;
-    a.n_segments = n_segments;
+    a.groups = g.groups;
+    a.n_segments = g.n_segments;
     a.seg_count = reinterpret_cast<uint32_t *>(sc + l.bitmap);
     a.tile_total = reinterpret_cast<uint64_t *>(sc + l.runs_tiles);
     a.temp = reinterpret_cast<uint32_t *>(sc + l.runs_temp);
@@ -1112,15 +1138,35 @@ bool bitop_runs_route(int op, uint64_t n_words, int n, const uint32_t *const *co
     a.out_offsets = d_out_offsets;
     a.ctrl = reinterpret_cast<uint32_t *>(sc);
     // (both control blocks wah_bitop_indexed_status reads: this route's, and the compress workspace's, which it does not use)
-    hipError_t e = wah::launch_clear(sc + l.ws_c, wah::kCtlWords * sizeof(uint32_t), s);
+    hipError_t e = wah::launch_clear(sc, wah::kCtlWords * sizeof(uint32_t), s);
+    if (e == hipSuccess) e = wah::launch_clear(sc + l.ws_c, wah::kCtlWords * sizeof(uint32_t), s);
     if (e == hipSuccess) e = wah::launch_bitop_runs(a, s);
-    if (e != hipSuccess) {
-        set_err("run-merge launch", e);
-        *rc = WAH_ERR_HIP;
-        return true;
-    }
-    *rc = WAH_OK;
+    *rc = e == hipSuccess ? WAH_OK : refuse("run-merge launch", WAH_ERR_HIP, e);
     return true;
+}
+
+// The road of the calls that combine indexed operands into ONE decoded bitmap: the control words cleared (the call's *_status
+// reads them), the combining kernel `launch` run over every segment into the scratch's bitmap area, the compress passes over
+// that.  a: the kernel's arguments, its geometry a.g filled in here.  The bitmap area takes ceil(31 G / 32) words: n_words, or
+// n_words + 1 when the last group has spare bits -- a negated clause, or a range with lo == 0, sets them, and they land in that
+// one word more, which the area has room for and the compress passes, told n_words, never read.
+extern "C++" template <class Args, class Launch>
+int combine_then_compress(Args &a, Launch launch, const char *label, uint64_t n_words, uint32_t *d_out, uint64_t out_capacity_words,
+                          uint64_t *d_out_words, uint64_t *d_out_offsets, char *sc, const BitopIndexedLayout &l, void *stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    uint32_t *combined = reinterpret_cast<uint32_t *>(sc + l.bitmap);
+    const SegGeometry g = seg_geometry(n_words);
+    a.g.first_segment = 0;
+    a.g.n_segments = g.n_segments;
+    a.g.groups = g.groups;
+    a.g.out_words = wah_decoded_words(g.groups);
+    a.g.out = combined;
+    a.g.ctrl = reinterpret_cast<uint32_t *>(sc);
+    hipError_t e = wah::launch_clear(sc, wah::kCtlWords * sizeof(uint32_t), s);
+    if (e == hipSuccess) e = launch(a, s);
+    if (e != hipSuccess) return refuse(label, WAH_ERR_HIP, e);
+    return compress_device_impl(combined, nullptr, 0, nullptr, n_words, d_out, out_capacity_words, d_out_words, d_out_offsets,
+                                sc + l.ws_c, l.ws_c_bytes, stream, true);
 }
 } // namespace
 
@@ -1131,31 +1177,14 @@ int wah_bitop_indexed_device(int op, uint64_t n_words, const uint32_t *d_a, uint
                              uint64_t out_capacity_words, uint64_t *d_out_words, uint64_t *d_out_offsets, void *d_scratch,
                              size_t scratch_bytes, void *stream) {
     g_err[0] = 0;
-    if (op < WAH_OP_AND || op > WAH_OP_ANDNOT || !d_scratch || (reinterpret_cast<uintptr_t>(d_scratch) & 255u)) {
-        set_err("bad operation or scratch pointer");
-        return WAH_ERR_ARG;
-    }
+    if (op < WAH_OP_AND || op > WAH_OP_ANDNOT || !scratch_ok(d_scratch)) return refuse("bad operation or scratch pointer", WAH_ERR_ARG);
     if (!d_a_offsets || !d_b_offsets || (a_words && !d_a) || (b_words && !d_b) || n_words >= (1ull << 40) ||
-        a_words >= (1ull << 40) || b_words >= (1ull << 40) || (reinterpret_cast<uintptr_t>(d_a) & 3u) ||
-        (reinterpret_cast<uintptr_t>(d_b) & 3u)) {
-        set_err("null or misaligned operand");
-        return WAH_ERR_ARG;
-    }
+        a_words >= (1ull << 40) || b_words >= (1ull << 40) || !aligned(d_a, 3) || !aligned(d_b, 3))
+        return refuse("null or misaligned operand", WAH_ERR_ARG);
     const BitopIndexedLayout l = bitop_indexed_layout(n_words);
-    if (scratch_bytes < l.total) {
-        set_err("scratch too small");
-        return WAH_ERR_WORKSPACE;
-    }
+    if (scratch_bytes < l.total) return refuse("scratch too small", WAH_ERR_WORKSPACE);
     char *sc = static_cast<char *>(d_scratch);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    // ONE kernel: both operands are walked segment by segment through their indexes, combined group by group in
-    // registers, and the combined groups go straight into the compress passes -- no decoded bitmap is written or read
-    // (the scratch's bitmap area stays unused on this route; the many-operand call still goes through it).
-    hipError_t e = wah::launch_clear(sc, wah::kCtlWords * sizeof(uint32_t), s); // (read by wah_bitop_indexed_status)
-    if (e != hipSuccess) {
-        set_err("clearing the scratch", e);
-        return WAH_ERR_HIP;
-    }
     {
         const uint32_t *const comp[2] = {d_a, d_b};
         const uint64_t words[2] = {a_words, b_words};
@@ -1163,6 +1192,11 @@ int wah_bitop_indexed_device(int op, uint64_t n_words, const uint32_t *d_a, uint
         int rc = WAH_OK;
         if (bitop_runs_route(op, n_words, 2, comp, words, offs, d_out, out_capacity_words, d_out_words, d_out_offsets, sc, l, s, &rc)) return rc;
     }
+    // ONE kernel: both operands are walked segment by segment through their indexes, combined group by group in
+    // registers, and the combined groups go straight into the compress passes -- no decoded bitmap is written or read
+    // (the scratch's bitmap area stays unused on this route; the many-operand call still goes through it).
+    hipError_t e = wah::launch_clear(sc, wah::kCtlWords * sizeof(uint32_t), s); // (read by wah_bitop_indexed_status)
+    if (e != hipSuccess) return refuse("clearing the scratch", WAH_ERR_HIP, e);
     wah::BitopOperands ops;
     ops.comp_a = d_a;
     ops.comp_b = d_b;
@@ -1170,7 +1204,7 @@ int wah_bitop_indexed_device(int op, uint64_t n_words, const uint32_t *d_a, uint
     ops.c_words_b = b_words;
     ops.offs_a = d_a_offsets;
     ops.offs_b = d_b_offsets;
-    ops.groups = wah_max_compressed_words(n_words);
+    ops.groups = seg_geometry(n_words).groups;
     ops.op = (uint32_t)op;
     return compress_device_impl(nullptr, nullptr, 0, nullptr, n_words, d_out, out_capacity_words, d_out_words, d_out_offsets,
                                 sc + l.ws_c, l.ws_c_bytes, stream, true, nullptr, &ops);
@@ -1181,59 +1215,29 @@ int wah_bitop_many_indexed_device(int op, uint64_t n_words, int n_operands, cons
                                   uint64_t out_capacity_words, uint64_t *d_out_words, uint64_t *d_out_offsets, void *d_scratch,
                                   size_t scratch_bytes, void *stream) {
     g_err[0] = 0;
-    if (op < WAH_OP_AND || op > WAH_OP_ANDNOT || !d_scratch || (reinterpret_cast<uintptr_t>(d_scratch) & 255u)) {
-        set_err("bad operation or scratch pointer");
-        return WAH_ERR_ARG;
-    }
+    if (op < WAH_OP_AND || op > WAH_OP_ANDNOT || !scratch_ok(d_scratch)) return refuse("bad operation or scratch pointer", WAH_ERR_ARG);
     if (n_operands < 1 || n_operands > wah::kMaxBitopOperands || !d_streams || !stream_words || !d_offsets ||
-        n_words >= (1ull << 40)) {
-        set_err("between 1 and 8 operands, each with its stream, length and index");
-        return WAH_ERR_ARG;
-    }
+        n_words >= (1ull << 40))
+        return refuse("between 1 and 8 operands, each with its stream, length and index", WAH_ERR_ARG);
     wah::BitopManyArgs a = {};
     for (int j = 0; j < n_operands; ++j) {
-        if (!d_offsets[j] || (stream_words[j] && !d_streams[j]) || stream_words[j] >= (1ull << 40) ||
-            (reinterpret_cast<uintptr_t>(d_streams[j]) & 3u)) {
-            set_err("null or misaligned operand");
-            return WAH_ERR_ARG;
-        }
+        if (!d_offsets[j] || (stream_words[j] && !d_streams[j]) || stream_words[j] >= (1ull << 40) || !aligned(d_streams[j], 3))
+            return refuse("null or misaligned operand", WAH_ERR_ARG);
         a.comp[j] = d_streams[j];
         a.c_words[j] = stream_words[j];
         a.offs[j] = d_offsets[j];
     }
     const BitopIndexedLayout l = bitop_indexed_layout(n_words);
-    if (scratch_bytes < l.total) {
-        set_err("scratch too small");
-        return WAH_ERR_WORKSPACE;
-    }
+    if (scratch_bytes < l.total) return refuse("scratch too small", WAH_ERR_WORKSPACE);
     char *sc = static_cast<char *>(d_scratch);
-    uint32_t *combined = reinterpret_cast<uint32_t *>(sc + l.bitmap);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const uint64_t groups = wah_max_compressed_words(n_words);
-    hipError_t e = wah::launch_clear(sc, wah::kCtlWords * sizeof(uint32_t), s);
-    if (e == hipSuccess) {
-        int rc = WAH_OK;
-        if (bitop_runs_route(op, n_words, n_operands, d_streams, stream_words, d_offsets, d_out, out_capacity_words, d_out_words,
-                             d_out_offsets, sc, l, s, &rc))
-            return rc;
-    }
-    if (e == hipSuccess) {
-        a.g.first_segment = 0;
-        a.g.n_segments = (groups + wah::kSegGroups - 1) / wah::kSegGroups;
-        a.g.groups = groups;
-        a.g.out_words = wah_decoded_words(groups);
-        a.g.out = combined;
-        a.g.ctrl = reinterpret_cast<uint32_t *>(sc);
-        a.n = n_operands;
-        a.op = op;
-        e = wah::launch_bitop_many_segments(a, s);
-    }
-    if (e != hipSuccess) {
-        set_err("combining pass launch", e);
-        return WAH_ERR_HIP;
-    }
-    return compress_device_impl(combined, nullptr, 0, nullptr, n_words, d_out, out_capacity_words, d_out_words, d_out_offsets,
-                                sc + l.ws_c, l.ws_c_bytes, stream, true);
+    int rc = WAH_OK;
+    if (bitop_runs_route(op, n_words, n_operands, d_streams, stream_words, d_offsets, d_out, out_capacity_words, d_out_words, d_out_offsets, sc,
+                         l, static_cast<hipStream_t>(stream), &rc))
+        return rc;
+    a.n = n_operands;
+    a.op = op;
+    return combine_then_compress(a, wah::launch_bitop_many_segments, "combining pass launch", n_words, d_out, out_capacity_words, d_out_words,
+                                 d_out_offsets, sc, l, stream);
 }
 
 int wah_bitop_indexed_status(void *d_scratch, uint64_t n_words, void *stream) {
@@ -1255,46 +1259,17 @@ int wah_bitop_list_indexed_device(int op, uint64_t n_words, uint64_t n_operands,
                                   uint64_t out_capacity_words, uint64_t *d_out_words, uint64_t *d_out_offsets, void *d_scratch,
                                   size_t scratch_bytes, void *stream) {
     g_err[0] = 0;
-    if (op < WAH_OP_AND || op > WAH_OP_ANDNOT || !d_scratch || (reinterpret_cast<uintptr_t>(d_scratch) & 255u)) {
-        set_err("bad operation or scratch pointer");
-        return WAH_ERR_ARG;
-    }
-    if (n_operands < 1 || n_operands > wah::kMaxBitopListOperands || !d_operands || (reinterpret_cast<uintptr_t>(d_operands) & 7u) ||
-        n_words >= (1ull << 40)) {
-        set_err("between 1 and 2^24 operands in an 8-byte aligned table, fewer than 2^40 words");
-        return WAH_ERR_ARG;
-    }
-    if (!d_out_words || (n_words && !d_out)) {
-        set_err("null pointer");
-        return WAH_ERR_ARG;
-    }
+    if (op < WAH_OP_AND || op > WAH_OP_ANDNOT || !scratch_ok(d_scratch)) return refuse("bad operation or scratch pointer", WAH_ERR_ARG);
+    if (!table_ok(n_operands, d_operands, n_words)) return refuse(kBadTable, WAH_ERR_ARG);
+    if (!d_out_words || (n_words && !d_out)) return refuse("null pointer", WAH_ERR_ARG);
     const BitopIndexedLayout l = bitop_indexed_layout(n_words);
-    if (scratch_bytes < l.total) {
-        set_err("scratch too small");
-        return WAH_ERR_WORKSPACE;
-    }
-    char *sc = static_cast<char *>(d_scratch);
-    uint32_t *combined = reinterpret_cast<uint32_t *>(sc + l.bitmap);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const uint64_t groups = wah_max_compressed_words(n_words);
+    if (scratch_bytes < l.total) return refuse("scratch too small", WAH_ERR_WORKSPACE);
     wah::BitopListArgs a = {};
-    a.g.first_segment = 0;
-    a.g.n_segments = ceil_div(groups, (uint64_t)wah::kSegGroups);
-    a.g.groups = groups;
-    a.g.out_words = wah_decoded_words(groups);
-    a.g.out = combined;
-    a.g.ctrl = reinterpret_cast<uint32_t *>(sc);
     a.table = reinterpret_cast<const wah::BitopListOperand *>(d_operands);
     a.n = (uint32_t)n_operands;
     a.op = (uint32_t)op;
-    hipError_t e = wah::launch_clear(sc, wah::kCtlWords * sizeof(uint32_t), s); // (read by wah_bitop_list_status)
-    if (e == hipSuccess) e = wah::launch_bitop_list_segments(a, s);
-    if (e != hipSuccess) {
-        set_err("combining pass launch", e);
-        return WAH_ERR_HIP;
-    }
-    return compress_device_impl(combined, nullptr, 0, nullptr, n_words, d_out, out_capacity_words, d_out_words, d_out_offsets,
-                                sc + l.ws_c, l.ws_c_bytes, stream, true);
+    return combine_then_compress(a, wah::launch_bitop_list_segments, "combining pass launch", n_words, d_out, out_capacity_words, d_out_words, d_out_offsets,
+                                 static_cast<char *>(d_scratch), l, stream);
 }
 
 int wah_bitop_list_status(void *d_scratch, uint64_t n_words, uint64_t n_operands, void *stream) {
@@ -1315,53 +1290,20 @@ int wah_bitop_clauses_indexed_device(uint64_t n_words, uint64_t n_clauses, const
                                      const wah_bitop_operand *d_operands, uint32_t *d_out, uint64_t out_capacity_words,
                                      uint64_t *d_out_words, uint64_t *d_out_offsets, void *d_scratch, size_t scratch_bytes, void *stream) {
     g_err[0] = 0;
-    if (!d_scratch || (reinterpret_cast<uintptr_t>(d_scratch) & 255u)) {
-        set_err("bad scratch pointer");
-        return WAH_ERR_ARG;
-    }
-    if (n_operands < 1 || n_operands > wah::kMaxBitopListOperands || !d_operands || (reinterpret_cast<uintptr_t>(d_operands) & 7u) ||
-        n_words >= (1ull << 40)) {
-        set_err("between 1 and 2^24 operands in an 8-byte aligned table, fewer than 2^40 words");
-        return WAH_ERR_ARG;
-    }
-    if (n_clauses < 1 || n_clauses > n_operands || !d_clause_ends || (reinterpret_cast<uintptr_t>(d_clause_ends) & 7u)) {
-        set_err("between 1 and n_operands clauses in an 8-byte aligned table");
-        return WAH_ERR_ARG;
-    }
-    if (!d_out_words || (n_words && !d_out)) {
-        set_err("null pointer");
-        return WAH_ERR_ARG;
-    }
+    if (!scratch_ok(d_scratch)) return refuse("bad scratch pointer", WAH_ERR_ARG);
+    if (!table_ok(n_operands, d_operands, n_words)) return refuse(kBadTable, WAH_ERR_ARG);
+    if (n_clauses < 1 || n_clauses > n_operands || !d_clause_ends || !aligned(d_clause_ends, 7))
+        return refuse("between 1 and n_operands clauses in an 8-byte aligned table", WAH_ERR_ARG);
+    if (!d_out_words || (n_words && !d_out)) return refuse("null pointer", WAH_ERR_ARG);
     const BitopIndexedLayout l = bitop_indexed_layout(n_words);
-    if (scratch_bytes < l.total) {
-        set_err("scratch too small");
-        return WAH_ERR_WORKSPACE;
-    }
-    char *sc = static_cast<char *>(d_scratch);
-    uint32_t *combined = reinterpret_cast<uint32_t *>(sc + l.bitmap);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const uint64_t groups = wah_max_compressed_words(n_words);
+    if (scratch_bytes < l.total) return refuse("scratch too small", WAH_ERR_WORKSPACE);
     wah::BitopClausesArgs a = {};
-    a.g.first_segment = 0;
-    a.g.n_segments = ceil_div(groups, (uint64_t)wah::kSegGroups);
-    a.g.groups = groups;
-    // (ceil(31 G / 32) words: n_words, or n_words + 1 when the last group has spare bits -- a negated clause sets them, and they
-    //  land in that one word more, which the bitmap area has room for and the compress passes, told n_words, never read)
-    a.g.out_words = wah_decoded_words(groups);
-    a.g.out = combined;
-    a.g.ctrl = reinterpret_cast<uint32_t *>(sc);
     a.table = reinterpret_cast<const wah::BitopListOperand *>(d_operands);
     a.clause_ends = d_clause_ends;
     a.n = (uint32_t)n_operands;
     a.n_clauses = (uint32_t)n_clauses;
-    hipError_t e = wah::launch_clear(sc, wah::kCtlWords * sizeof(uint32_t), s); // (read by wah_bitop_clauses_status)
-    if (e == hipSuccess) e = wah::launch_bitop_clauses_segments(a, s);
-    if (e != hipSuccess) {
-        set_err("combining pass launch", e);
-        return WAH_ERR_HIP;
-    }
-    return compress_device_impl(combined, nullptr, 0, nullptr, n_words, d_out, out_capacity_words, d_out_words, d_out_offsets,
-                                sc + l.ws_c, l.ws_c_bytes, stream, true);
+    return combine_then_compress(a, wah::launch_bitop_clauses_segments, "combining pass launch", n_words, d_out, out_capacity_words, d_out_words, d_out_offsets,
+                                 static_cast<char *>(d_scratch), l, stream);
 }
 
 int wah_bitop_clauses_status(void *d_scratch, uint64_t n_words, uint64_t n_operands, uint64_t n_clauses, void *stream) {
@@ -1382,49 +1324,20 @@ int wah_bsi_range_indexed_device(uint64_t n_words, uint64_t n_slices, const wah_
                                  unsigned flags, uint32_t *d_out, uint64_t out_capacity_words, uint64_t *d_out_words,
                                  uint64_t *d_out_offsets, void *d_scratch, size_t scratch_bytes, void *stream) {
     g_err[0] = 0;
-    if (n_slices < 1 || n_slices > WAH_BSI_MAX_SLICES || (flags & ~WAH_BSI_EXISTS)) {
-        set_err("between 1 and 64 slices, no flag besides WAH_BSI_EXISTS");
-        return WAH_ERR_ARG;
-    }
-    if (!d_slices || (reinterpret_cast<uintptr_t>(d_slices) & 7u) || !d_bounds || (reinterpret_cast<uintptr_t>(d_bounds) & 7u) ||
-        !d_scratch || (reinterpret_cast<uintptr_t>(d_scratch) & 255u)) {
-        set_err("null or misaligned slice table, bounds or scratch");
-        return WAH_ERR_ARG;
-    }
-    if (!d_out_words || (n_words && !d_out) || n_words >= (1ull << 40)) {
-        set_err("null output pointer, or 2^40 words or more");
-        return WAH_ERR_ARG;
-    }
+    if (n_slices < 1 || n_slices > WAH_BSI_MAX_SLICES || (flags & ~WAH_BSI_EXISTS))
+        return refuse("between 1 and 64 slices, no flag besides WAH_BSI_EXISTS", WAH_ERR_ARG);
+    if (!d_slices || !aligned(d_slices, 7) || !d_bounds || !aligned(d_bounds, 7) || !scratch_ok(d_scratch))
+        return refuse("null or misaligned slice table, bounds or scratch", WAH_ERR_ARG);
+    if (!d_out_words || (n_words && !d_out) || n_words >= (1ull << 40)) return refuse("null output pointer, or 2^40 words or more", WAH_ERR_ARG);
     const BitopIndexedLayout l = bitop_indexed_layout(n_words);
-    if (scratch_bytes < l.total) {
-        set_err("scratch too small");
-        return WAH_ERR_WORKSPACE;
-    }
-    char *sc = static_cast<char *>(d_scratch);
-    uint32_t *combined = reinterpret_cast<uint32_t *>(sc + l.bitmap);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const uint64_t groups = wah_max_compressed_words(n_words);
+    if (scratch_bytes < l.total) return refuse("scratch too small", WAH_ERR_WORKSPACE);
     wah::BsiRangeArgs a = {};
-    a.g.first_segment = 0;
-    a.g.n_segments = ceil_div(groups, (uint64_t)wah::kSegGroups);
-    a.g.groups = groups;
-    // (as for a negated clause: with lo == 0 the last group's spare bits match and land in the one word more that
-    //  wah_decoded_words counts, which the bitmap area has room for and the compress passes, told n_words, never read)
-    a.g.out_words = wah_decoded_words(groups);
-    a.g.out = combined;
-    a.g.ctrl = reinterpret_cast<uint32_t *>(sc);
     a.table = reinterpret_cast<const wah::BitopListOperand *>(d_slices);
     a.bounds = d_bounds;
     a.n_slices = (uint32_t)n_slices;
     a.has_exists = (flags & WAH_BSI_EXISTS) ? 1u : 0u;
-    hipError_t e = wah::launch_clear(sc, wah::kCtlWords * sizeof(uint32_t), s); // (read by wah_bsi_range_status)
-    if (e == hipSuccess) e = wah::launch_bsi_range_segments(a, s);
-    if (e != hipSuccess) {
-        set_err("range sweep launch", e);
-        return WAH_ERR_HIP;
-    }
-    return compress_device_impl(combined, nullptr, 0, nullptr, n_words, d_out, out_capacity_words, d_out_words, d_out_offsets,
-                                sc + l.ws_c, l.ws_c_bytes, stream, true);
+    return combine_then_compress(a, wah::launch_bsi_range_segments, "range sweep launch", n_words, d_out, out_capacity_words, d_out_words, d_out_offsets,
+                                 static_cast<char *>(d_scratch), l, stream);
 }
 
 int wah_bsi_range_status(void *d_scratch, uint64_t n_words, uint64_t n_slices, void *stream) {
@@ -1461,26 +1374,16 @@ size_t wah_bsi_kth_scratch_bytes(uint64_t n_words, uint64_t n_slices) {
 int wah_bsi_kth_indexed_device(uint64_t n_words, uint64_t n_filters, uint64_t n_slices, const wah_bitop_operand *d_rows,
                                const uint64_t *d_query, uint64_t *d_result, void *d_scratch, size_t scratch_bytes, void *stream) {
     g_err[0] = 0;
-    if (n_slices < 1 || n_slices > WAH_BSI_MAX_SLICES || n_filters > WAH_BSI_KTH_MAX_FILTERS) {
-        set_err("between 1 and 64 slices, at most 64 filters");
-        return WAH_ERR_ARG;
-    }
-    if (!d_rows || (reinterpret_cast<uintptr_t>(d_rows) & 7u) || !d_query || (reinterpret_cast<uintptr_t>(d_query) & 7u) || !d_result ||
-        (reinterpret_cast<uintptr_t>(d_result) & 7u) || !d_scratch || (reinterpret_cast<uintptr_t>(d_scratch) & 255u)) {
-        set_err("null or misaligned row table, query, result or scratch");
-        return WAH_ERR_ARG;
-    }
-    if (n_words >= (1ull << 40)) {
-        set_err("2^40 words or more");
-        return WAH_ERR_ARG;
-    }
+    if (n_slices < 1 || n_slices > WAH_BSI_MAX_SLICES || n_filters > WAH_BSI_KTH_MAX_FILTERS)
+        return refuse("between 1 and 64 slices, at most 64 filters", WAH_ERR_ARG);
+    if (!d_rows || !aligned(d_rows, 7) || !d_query || !aligned(d_query, 7) || !d_result || !aligned(d_result, 7) || !scratch_ok(d_scratch))
+        return refuse("null or misaligned row table, query, result or scratch", WAH_ERR_ARG);
+    if (n_words >= (1ull << 40)) return refuse("2^40 words or more", WAH_ERR_ARG);
     const BsiKthLayout l = bsi_kth_layout(n_slices);
-    if (scratch_bytes < l.total) {
-        set_err("scratch too small");
-        return WAH_ERR_WORKSPACE;
-    }
+    if (scratch_bytes < l.total) return refuse("scratch too small", WAH_ERR_WORKSPACE);
     char *sc = static_cast<char *>(d_scratch);
     hipStream_t s = static_cast<hipStream_t>(stream);
+    const SegGeometry g = seg_geometry(n_words);
     wah::BsiKthArgs a = {};
     a.table = reinterpret_cast<const wah::BitopListOperand *>(d_rows);
     a.query = d_query;
@@ -1488,21 +1391,18 @@ int wah_bsi_kth_indexed_device(uint64_t n_words, uint64_t n_filters, uint64_t n_
     a.state = reinterpret_cast<uint64_t *>(sc + l.state);
     a.hist = reinterpret_cast<uint64_t *>(sc + l.hist);
     a.ctrl = reinterpret_cast<uint32_t *>(sc);
-    a.groups = wah_max_compressed_words(n_words);
-    a.n_segments = ceil_div(a.groups, (uint64_t)wah::kSegGroups);
+    a.groups = g.groups;
+    a.n_segments = g.n_segments;
     a.n_filters = (uint32_t)n_filters;
     a.n_slices = (uint32_t)n_slices;
-    a.pad_bits = (uint32_t)(31u * a.groups - 32u * n_words);
+    a.pad_bits = g.pad_bits;
     hipError_t e = wah::launch_clear(sc, l.total, s); // the control words (read by wah_bsi_kth_status), the state, the histograms
     for (uint32_t p = 0; p < l.passes && e == hipSuccess; ++p) {
         a.pass = p;
         e = wah::launch_bsi_kth_pass(a, s);
         if (e == hipSuccess) e = wah::launch_bsi_kth_decide(a, s);
     }
-    if (e != hipSuccess) {
-        set_err("radix select launch", e);
-        return WAH_ERR_HIP;
-    }
+    if (e != hipSuccess) return refuse("radix select launch", WAH_ERR_HIP, e);
     return WAH_OK;
 }
 
@@ -1516,13 +1416,13 @@ int wah_bsi_kth_status(void *d_scratch, void *stream) {
 // below) -- it goes with n_words / 992, not with the operands' number or their words.
 namespace {
 struct SelectLayout {
-    uint64_t n_segments;
+    SegGeometry g;
     size_t ranks, level1, level2, total;
 };
 SelectLayout select_layout(uint64_t n_words) {
     SelectLayout l;
-    l.n_segments = ceil_div(wah_max_compressed_words(n_words), (uint64_t)wah::kSegGroups);
-    const uint64_t n0 = l.n_segments + 1, n1 = ceil_div(n0, (uint64_t)wah::kRankChunk), n2 = ceil_div(n1, (uint64_t)wah::kRankChunk);
+    l.g = seg_geometry(n_words);
+    const uint64_t n0 = l.g.n_segments + 1, n1 = ceil_div(n0, (uint64_t)wah::kRankChunk), n2 = ceil_div(n1, (uint64_t)wah::kRankChunk);
     size_t at = wah::kCtlWords * sizeof(uint32_t);
     l.ranks = at;
     at += round256(n0 * sizeof(uint64_t));
@@ -1533,7 +1433,6 @@ SelectLayout select_layout(uint64_t n_words) {
     l.total = at;
     return l;
 }
-uint32_t select_pad_bits(uint64_t n_words) { return (uint32_t)(31u * wah_max_compressed_words(n_words) - 32u * n_words); }
 } // namespace
 
 size_t wah_select_scratch_bytes(uint64_t n_words, uint64_t n_operands) {
@@ -1544,41 +1443,25 @@ size_t wah_select_scratch_bytes(uint64_t n_words, uint64_t n_operands) {
 int wah_count_list_indexed_device(uint64_t n_words, uint64_t n_operands, const wah_bitop_operand *d_operands, uint64_t *d_counts,
                                   void *d_scratch, size_t scratch_bytes, void *stream) {
     g_err[0] = 0;
-    if (!d_scratch || (reinterpret_cast<uintptr_t>(d_scratch) & 255u)) {
-        set_err("bad scratch pointer");
-        return WAH_ERR_ARG;
-    }
-    if (n_operands < 1 || n_operands > wah::kMaxBitopListOperands || !d_operands || (reinterpret_cast<uintptr_t>(d_operands) & 7u) ||
-        n_words >= (1ull << 40)) {
-        set_err("between 1 and 2^24 operands in an 8-byte aligned table, fewer than 2^40 words");
-        return WAH_ERR_ARG;
-    }
-    if (!d_counts || (reinterpret_cast<uintptr_t>(d_counts) & 7u)) {
-        set_err("null or misaligned counts");
-        return WAH_ERR_ARG;
-    }
+    if (!scratch_ok(d_scratch)) return refuse("bad scratch pointer", WAH_ERR_ARG);
+    if (!table_ok(n_operands, d_operands, n_words)) return refuse(kBadTable, WAH_ERR_ARG);
+    if (!d_counts || !aligned(d_counts, 7)) return refuse("null or misaligned counts", WAH_ERR_ARG);
     const SelectLayout l = select_layout(n_words);
-    if (scratch_bytes < l.total) {
-        set_err("scratch too small");
-        return WAH_ERR_WORKSPACE;
-    }
+    if (scratch_bytes < l.total) return refuse("scratch too small", WAH_ERR_WORKSPACE);
     char *sc = static_cast<char *>(d_scratch);
     hipStream_t s = static_cast<hipStream_t>(stream);
     wah::SelectCountArgs a = {};
     a.table = reinterpret_cast<const wah::BitopListOperand *>(d_operands);
     a.n_operands = (uint32_t)n_operands;
-    a.pad_bits = select_pad_bits(n_words);
-    a.groups = wah_max_compressed_words(n_words);
-    a.n_segments = l.n_segments;
+    a.pad_bits = l.g.pad_bits;
+    a.groups = l.g.groups;
+    a.n_segments = l.g.n_segments;
     a.counts = d_counts;
     a.ctrl = reinterpret_cast<uint32_t *>(sc);
     hipError_t e = wah::launch_clear(sc, wah::kCtlWords * sizeof(uint32_t), s); // (read by wah_select_status)
     if (e == hipSuccess) e = wah::launch_clear(d_counts, n_operands * sizeof(uint64_t), s);
     if (e == hipSuccess) e = wah::launch_select_count(a, s);
-    if (e != hipSuccess) {
-        set_err("count pass launch", e);
-        return WAH_ERR_HIP;
-    }
+    if (e != hipSuccess) return refuse("count pass launch", WAH_ERR_HIP, e);
     return WAH_OK;
 }
 
@@ -1586,25 +1469,14 @@ int wah_count_masked_indexed_device(uint64_t n_words, uint64_t n_masks, const wa
                                     const wah_bitop_operand *d_operands, uint64_t *d_counts, void *d_scratch, size_t scratch_bytes,
                                     void *stream) {
     g_err[0] = 0;
-    if (!d_scratch || (reinterpret_cast<uintptr_t>(d_scratch) & 255u)) {
-        set_err("bad scratch pointer");
-        return WAH_ERR_ARG;
-    }
+    if (!scratch_ok(d_scratch)) return refuse("bad scratch pointer", WAH_ERR_ARG);
     if (n_masks < 1 || n_masks > wah::kMaxBitopListOperands || n_operands < 1 || n_operands > wah::kMaxBitopListOperands ||
-        n_masks * n_operands > wah::kMaxBitopListOperands || !d_masks || (reinterpret_cast<uintptr_t>(d_masks) & 7u) || !d_operands ||
-        (reinterpret_cast<uintptr_t>(d_operands) & 7u) || n_words >= (1ull << 40)) {
-        set_err("at least one mask and one operand, at most 2^24 pairs, in 8-byte aligned tables, fewer than 2^40 words");
-        return WAH_ERR_ARG;
-    }
-    if (!d_counts || (reinterpret_cast<uintptr_t>(d_counts) & 7u)) {
-        set_err("null or misaligned counts");
-        return WAH_ERR_ARG;
-    }
+        n_masks * n_operands > wah::kMaxBitopListOperands || !d_masks || !aligned(d_masks, 7) || !d_operands ||
+        !aligned(d_operands, 7) || n_words >= (1ull << 40))
+        return refuse("at least one mask and one operand, at most 2^24 pairs, in 8-byte aligned tables, fewer than 2^40 words", WAH_ERR_ARG);
+    if (!d_counts || !aligned(d_counts, 7)) return refuse("null or misaligned counts", WAH_ERR_ARG);
     const SelectLayout l = select_layout(n_words);
-    if (scratch_bytes < l.total) {
-        set_err("scratch too small");
-        return WAH_ERR_WORKSPACE;
-    }
+    if (scratch_bytes < l.total) return refuse("scratch too small", WAH_ERR_WORKSPACE);
     char *sc = static_cast<char *>(d_scratch);
     hipStream_t s = static_cast<hipStream_t>(stream);
     wah::CountMaskedArgs a = {};
@@ -1612,18 +1484,15 @@ int wah_count_masked_indexed_device(uint64_t n_words, uint64_t n_masks, const wa
     a.operands = reinterpret_cast<const wah::BitopListOperand *>(d_operands);
     a.n_masks = (uint32_t)n_masks;
     a.n_operands = (uint32_t)n_operands;
-    a.pad_bits = select_pad_bits(n_words);
-    a.groups = wah_max_compressed_words(n_words);
-    a.n_segments = l.n_segments;
+    a.pad_bits = l.g.pad_bits;
+    a.groups = l.g.groups;
+    a.n_segments = l.g.n_segments;
     a.counts = d_counts;
     a.ctrl = reinterpret_cast<uint32_t *>(sc);
     hipError_t e = wah::launch_clear(sc, wah::kCtlWords * sizeof(uint32_t), s); // (read by wah_select_status)
     if (e == hipSuccess) e = wah::launch_clear(d_counts, n_masks * n_operands * sizeof(uint64_t), s);
     if (e == hipSuccess) e = wah::launch_count_masked(a, s);
-    if (e != hipSuccess) {
-        set_err("masked count launch", e);
-        return WAH_ERR_HIP;
-    }
+    if (e != hipSuccess) return refuse("masked count launch", WAH_ERR_HIP, e);
     return WAH_OK;
 }
 
@@ -1631,23 +1500,12 @@ int wah_positions_indexed_device(uint64_t n_words, const uint32_t *d_stream, uin
                                  uint64_t first_rank, uint64_t *d_out, uint64_t out_capacity, uint64_t *d_out_info, void *d_scratch,
                                  size_t scratch_bytes, void *stream) {
     g_err[0] = 0;
-    if (!d_scratch || (reinterpret_cast<uintptr_t>(d_scratch) & 255u)) {
-        set_err("bad scratch pointer");
-        return WAH_ERR_ARG;
-    }
-    if (n_words >= (1ull << 40)) {
-        set_err("fewer than 2^40 words");
-        return WAH_ERR_ARG;
-    }
-    if (!d_out_info || (reinterpret_cast<uintptr_t>(d_out_info) & 7u) || (out_capacity && !d_out) || (reinterpret_cast<uintptr_t>(d_out) & 7u)) {
-        set_err("null or misaligned output");
-        return WAH_ERR_ARG;
-    }
+    if (!scratch_ok(d_scratch)) return refuse("bad scratch pointer", WAH_ERR_ARG);
+    if (n_words >= (1ull << 40)) return refuse("fewer than 2^40 words", WAH_ERR_ARG);
+    if (!d_out_info || !aligned(d_out_info, 7) || (out_capacity && !d_out) || !aligned(d_out, 7))
+        return refuse("null or misaligned output", WAH_ERR_ARG);
     const SelectLayout l = select_layout(n_words);
-    if (scratch_bytes < l.total) {
-        set_err("scratch too small");
-        return WAH_ERR_WORKSPACE;
-    }
+    if (scratch_bytes < l.total) return refuse("scratch too small", WAH_ERR_WORKSPACE);
     char *sc = static_cast<char *>(d_scratch);
     hipStream_t s = static_cast<hipStream_t>(stream);
     uint64_t *ranks = reinterpret_cast<uint64_t *>(sc + l.ranks);
@@ -1658,17 +1516,17 @@ int wah_positions_indexed_device(uint64_t n_words, const uint32_t *d_stream, uin
     c.one.c_words = stream_words;
     c.one.offs = d_offsets;
     c.n_operands = 1;
-    c.pad_bits = select_pad_bits(n_words);
-    c.groups = wah_max_compressed_words(n_words);
-    c.n_segments = l.n_segments;
+    c.pad_bits = l.g.pad_bits;
+    c.groups = l.g.groups;
+    c.n_segments = l.g.n_segments;
     c.counts = ranks;
     c.ctrl = reinterpret_cast<uint32_t *>(sc);
     wah::SelectEmitArgs a = {};
     a.g.comp = d_stream;
     a.g.c_words = stream_words;
     a.g.seg_offsets = d_offsets;
-    a.g.n_segments = l.n_segments;
-    a.g.groups = c.groups;
+    a.g.n_segments = l.g.n_segments;
+    a.g.groups = l.g.groups;
     a.g.ctrl = c.ctrl;
     a.ranks = ranks;
     a.first = first_rank;
@@ -1680,12 +1538,9 @@ int wah_positions_indexed_device(uint64_t n_words, const uint32_t *d_stream, uin
     hipError_t e = wah::launch_clear(sc, wah::kCtlWords * sizeof(uint32_t), s); // (read by wah_select_status)
     if (e == hipSuccess) e = wah::launch_select_count(c, s);
     if (e == hipSuccess)
-        e = wah::launch_select_rank_scan(ranks, l.n_segments, reinterpret_cast<uint64_t *>(sc + l.level1), reinterpret_cast<uint64_t *>(sc + l.level2), s);
+        e = wah::launch_select_rank_scan(ranks, l.g.n_segments, reinterpret_cast<uint64_t *>(sc + l.level1), reinterpret_cast<uint64_t *>(sc + l.level2), s);
     if (e == hipSuccess) e = wah::launch_select_emit(a, s);
-    if (e != hipSuccess) {
-        set_err("positions launch", e);
-        return WAH_ERR_HIP;
-    }
+    if (e != hipSuccess) return refuse("positions launch", WAH_ERR_HIP, e);
     return WAH_OK;
 }
 
@@ -1704,8 +1559,9 @@ struct FromPositionsLayout {
 };
 FromPositionsLayout from_positions_layout(uint64_t n_words, uint64_t n_lists) {
     FromPositionsLayout l;
-    l.groups = wah_max_compressed_words(n_words);
-    l.n_segments = ceil_div(l.groups, (uint64_t)wah::kSegGroups);
+    const SegGeometry g = seg_geometry(n_words);
+    l.groups = g.groups;
+    l.n_segments = g.n_segments;
     l.n_items = n_lists * l.n_segments;
     const uint64_t n0 = l.n_items + 1, n1 = ceil_div(n0, (uint64_t)wah::kRankChunk), n2 = ceil_div(n1, (uint64_t)wah::kRankChunk);
     size_t at = wah::kCtlWords * sizeof(uint32_t);
@@ -1720,7 +1576,8 @@ FromPositionsLayout from_positions_layout(uint64_t n_words, uint64_t n_lists) {
 
 uint64_t wah_from_positions_max_words(uint64_t n_words, uint64_t n_lists, uint64_t n_rows) {
     // (n_lists x G passes 2^64 for the longest bitmaps and the most lists)
-    const unsigned __int128 groups = wah_max_compressed_words(n_words), segments = ceil_div((uint64_t)groups, (uint64_t)wah::kSegGroups);
+    const SegGeometry g = seg_geometry(n_words);
+    const unsigned __int128 groups = g.groups, segments = g.n_segments;
     const unsigned __int128 all_literals = (unsigned __int128)n_lists * groups;
     const unsigned __int128 by_rows = (unsigned __int128)n_lists * segments + 2 * (unsigned __int128)n_rows;
     const unsigned __int128 m = all_literals < by_rows ? all_literals : by_rows;
@@ -1733,32 +1590,16 @@ int wah_from_positions_device(uint64_t n_words, uint64_t n_lists, const uint64_t
                               uint32_t *d_out, uint64_t out_capacity_words, uint64_t *d_out_words, uint64_t *d_out_offsets,
                               void *d_scratch, size_t scratch_bytes, void *stream) {
     g_err[0] = 0;
-    if (n_lists < 1 || n_lists > wah::kMaxBitopListOperands || n_words == 0 || n_words >= (1ull << 40) || n_rows >= (1ull << 40)) {
-        set_err("between 1 and 2^24 lists, between 1 and 2^40 - 1 words, fewer than 2^40 rows");
-        return WAH_ERR_ARG;
-    }
+    if (n_lists < 1 || n_lists > wah::kMaxBitopListOperands || n_words == 0 || n_words >= (1ull << 40) || n_rows >= (1ull << 40))
+        return refuse("between 1 and 2^24 lists, between 1 and 2^40 - 1 words, fewer than 2^40 rows", WAH_ERR_ARG);
     const FromPositionsLayout l = from_positions_layout(n_words, n_lists);
-    if (l.n_items >= (1ull << 31)) {
-        set_err("lists x segments of 992 words: fewer than 2^31");
-        return WAH_ERR_ARG;
-    }
-    if (!d_scratch || (reinterpret_cast<uintptr_t>(d_scratch) & 255u)) {
-        set_err("bad scratch pointer");
-        return WAH_ERR_ARG;
-    }
-    if (!d_list_ends || (reinterpret_cast<uintptr_t>(d_list_ends) & 7u) || (n_rows && !d_rows) || (reinterpret_cast<uintptr_t>(d_rows) & 7u)) {
-        set_err("null or misaligned list ends or rows");
-        return WAH_ERR_ARG;
-    }
-    if (!d_out || (reinterpret_cast<uintptr_t>(d_out) & 3u) || !d_out_words || (reinterpret_cast<uintptr_t>(d_out_words) & 7u) || !d_out_offsets ||
-        (reinterpret_cast<uintptr_t>(d_out_offsets) & 7u)) {
-        set_err("null or misaligned output");
-        return WAH_ERR_ARG;
-    }
-    if (scratch_bytes < l.total) {
-        set_err("scratch too small");
-        return WAH_ERR_WORKSPACE;
-    }
+    if (l.n_items >= (1ull << 31)) return refuse("lists x segments of 992 words: fewer than 2^31", WAH_ERR_ARG);
+    if (!scratch_ok(d_scratch)) return refuse("bad scratch pointer", WAH_ERR_ARG);
+    if (!d_list_ends || !aligned(d_list_ends, 7) || (n_rows && !d_rows) || !aligned(d_rows, 7))
+        return refuse("null or misaligned list ends or rows", WAH_ERR_ARG);
+    if (!d_out || !aligned(d_out, 3) || !d_out_words || !aligned(d_out_words, 7) || !d_out_offsets || !aligned(d_out_offsets, 7))
+        return refuse("null or misaligned output", WAH_ERR_ARG);
+    if (scratch_bytes < l.total) return refuse("scratch too small", WAH_ERR_WORKSPACE);
     char *sc = static_cast<char *>(d_scratch);
     hipStream_t s = static_cast<hipStream_t>(stream);
     wah::FromPositionsArgs a = {};
@@ -1780,10 +1621,7 @@ int wah_from_positions_device(uint64_t n_words, uint64_t n_lists, const uint64_t
     if (e == hipSuccess)
         e = wah::launch_select_rank_scan(d_out_offsets, l.n_items, reinterpret_cast<uint64_t *>(sc + l.level1), reinterpret_cast<uint64_t *>(sc + l.level2), s);
     if (e == hipSuccess) e = wah::launch_from_positions_segments(a, true, s);
-    if (e != hipSuccess) {
-        set_err("from_positions launch", e);
-        return WAH_ERR_HIP;
-    }
+    if (e != hipSuccess) return refuse("from_positions launch", WAH_ERR_HIP, e);
     return WAH_OK;
 }
 

@@ -1,10 +1,17 @@
-// wah_bitop_list.hip -- one bit operation over ANY number of indexed compressed bitmaps (wah_bitop_list_indexed_device):
-// `value IN (...)` and `lo <= value <= hi` on an equality-encoded bitmap index are the OR of as many bitmaps as the list or
-// the range has bins (the reference has no counterpart: its README.md:10 only names such operations).
+// wah_bitop_list.hip -- the queries that walk a table of indexed compressed bitmaps, one wavefront per output segment:
+//   bitop_list_segments_kernel     one bit operation over ANY number of operands (wah_bitop_list_indexed_device): `value IN (...)`
+//                                  and `lo <= value <= hi` on an equality-encoded bitmap index are the OR of as many bitmaps as the
+//                                  list or the range has bins (the reference has no counterpart: its README.md:10 only names such
+//                                  operations)
+//   bitop_clauses_segments_kernel  AND over clauses of (negated) ORs (wah_bitop_clauses_indexed_device)
+//   bsi_range_segments_kernel      lo <= value <= hi over a bit-sliced attribute (wah_bsi_range_indexed_device)
+//   bsi_kth_pass_kernel            one pass of the radix select over such an attribute (wah_bsi_kth_indexed_device)
+// The walk itself is written once (list_walk); a kernel adds the state it keeps per segment, what it does when the walk crosses to
+// another row of the table, and what it stores.
 //
-// The operands are named by a table in DEVICE memory (wah_bitop_operand, include/wah.h) that only this kernel reads: the host
+// The rows are named by a table in DEVICE memory (wah_bitop_operand, include/wah.h) that only these kernels read: the host
 // never sees it, so a captured launch replayed over a rewritten table combines the new selection.  Nothing is decided from the
-// operands' lengths on the host -- one route, whatever they hold.
+// rows' lengths on the host -- one route, whatever they hold.
 //
 // One wavefront owns one output segment; its accumulator is the segment's 1024 groups in LDS (4 KiB per wavefront, 16 KiB per
 // workgroup: bitop_many_segments_kernel holds 20).  An operand's segment is never expanded: its words are loaded in batches of
@@ -20,28 +27,6 @@
 // Every group of the segment is covered by exactly one word of an operand (the scan's positions are disjoint whatever the words
 // say), so no two lanes touch one accumulator group for one operand: no atomics.  A segment's cost goes with the words the
 // operands hold there plus the length of the fills that change the result, not with n_operands x 1024 groups.
-// The first operand is the same code on a preset accumulator (all ones for AND, zero otherwise; the first operand of ANDNOT
-// applied as OR).
-//
-// What such a wave waits for is memory, not instructions: an index bin of a few words per segment is two dependent round
-// trips (table entry -> index pair -> words) for a hundred instructions.  With the next operand's words in flight while the
-// current one is applied (the x / y rotation of bitop_many_segments_kernel, table entries and index pairs by scalar loads) every
-// operand still costs a whole round trip: 256 clustered operands of 32 MiB took 0.75 ms, 0.013 of the roofline.  So the
-// pipeline is not by operand:
-//   * the table is walked 64 operands at a time, one operand per LANE: entry, check, index pair, range check -- two round trips
-//     per 64 operands, by vector loads (an entry is checked before its index pointer is followed, a range before the stream is
-//     read through it);
-//   * the unit in flight is a BATCH of 128 words, whatever operand it belongs to: kListDepth batches are always on their way
-//     (a producer cursor runs that far ahead of the consumer's over the 64 operands' batches), in registers of their own --
-//     the loop is unrolled by the depth, so no batch is ever moved -- eight registers instead of the thirty-two of two whole
-//     segments, which lets eight waves per SIMD stay resident.
-// ... and it is instructions: with memory out of the way the kernel is bound by what it issues per batch (about 125 wave
-// instructions: 256 random bins of 221 words per segment 0.89 ms).  Two cases therefore never reach the general batch code: a
-// segment that is ONE fill of all its groups and the operation's identity -- nearly every segment of a clustered bin -- is
-// settled while the chunk is gathered, 64 operands at a time (list_gather); a full batch of literals -- every batch of a
-// dense operand -- is 128 consecutive groups, combined without scan or fill tests (list_apply_batch).
-// The accumulated segment is written as decoded words into the scratch's bitmap area (seg_store: 31 -> 32 repack), and the
-// compress passes run over that -- the road of wah_bitop_many_indexed_device, one bitmap-sized intermediate.
 #include "wah_segdecode.hpp"
 
 namespace wah {
@@ -210,26 +195,39 @@ __device__ __forceinline__ void list_apply_batch(u32 *acc, u32 w0, u32 w1, u32 w
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // the next batch's (the next operand's) lanes touch other groups than these
 }
 
-__global__ __launch_bounds__(kSegDecodeWaves * 64, 8) void bitop_list_segments_kernel(const BitopListArgs a) {
-    __shared__ __attribute__((aligned(16))) u32 s_acc[kSegDecodeWaves][kSegGroups];
-    const u32 wave = wave_id(), lane = lane_id();
-    const u64 k = (u64)blockIdx.x * kSegDecodeWaves + wave;
-    if (k >= a.g.n_segments) return;
-    const u64 seg = a.g.first_segment + k;
-    const u64 g0 = seg * kSegGroups;
-    const u32 nvalid = a.g.groups - g0 < kSegGroups ? (u32)(a.g.groups - g0) : kSegGroups;
-    u32 *acc = s_acc[wave];
-    const u32 preset = a.op == 0u ? kOnes31 : 0u;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) reinterpret_cast<uint4 *>(acc)[64 * i + (int)lane] = make_uint4(preset, preset, preset, preset);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-
-    const ListOp m_first = list_op(a.op == 3u ? 1u : a.op), m_rest = list_op(a.op);
-    bool lane_bad = false, empty_word = false; // per lane: a refused operand of mine; an empty word among mine
-    bool sums_ok = true;                       // wave-uniform: every operand's words made up exactly nvalid groups
+// The walk over the first n_rows rows of a table, for segment `seg` of nvalid groups: every row's words of that segment applied to
+// the accumulator in the table's order.  op_of(j): the operation row j is applied with (fill_with_effect: the kind of fill that
+// changes the accumulator under it, kFillOne or kFillZero -- one kind for the whole walk); begin_row(j) is called, wave-uniform,
+// before the first batch of row j is applied -- where a kernel that keeps one row at a time in the accumulator folds the rows in
+// front of j.  Returns the verdict, wave-uniform: no row refused, no empty word, every row's words exactly nvalid groups.
+//
+// What such a wave waits for is memory, not instructions: an index bin of a few words per segment is two dependent round
+// trips (table entry -> index pair -> words) for a hundred instructions.  With the next operand's words in flight while the
+// current one is applied (the x / y rotation of bitop_many_segments_kernel, table entries and index pairs by scalar loads) every
+// operand still costs a whole round trip: 256 clustered operands of 32 MiB took 0.75 ms, 0.013 of the roofline.  So the
+// pipeline is not by operand:
+//   * the table is walked 64 rows at a time, one row per LANE: entry, check, index pair, range check -- two round trips
+//     per 64 rows, by vector loads (an entry is checked before its index pointer is followed, a range before the stream is
+//     read through it);
+//   * the unit in flight is a BATCH of 128 words, whatever row it belongs to: kListDepth batches are always on their way
+//     (a producer cursor runs that far ahead of the consumer's over the 64 rows' batches), in registers of their own --
+//     the loop is unrolled by the depth, so no batch is ever moved -- eight registers instead of the thirty-two of two whole
+//     segments, which lets eight waves per SIMD stay resident.
+// ... and it is instructions: with memory out of the way the walk is bound by what it issues per batch (about 125 wave
+// instructions: 256 random bins of 221 words per segment 0.89 ms).  Two cases therefore never reach the general batch code: a
+// segment that is ONE fill of all its groups and the operation's identity -- nearly every segment of a clustered bin -- is
+// settled while the chunk is gathered, 64 rows at a time (list_gather); a full batch of literals -- every batch of a
+// dense operand -- is 128 consecutive groups, combined without scan or fill tests (list_apply_batch).
+// A settled row never becomes a batch, so begin_row is not called for it: a caller finds the rows it has to fold from the row
+// NUMBERS it is given, and folds the rows behind the last one that had words after the walk.
+template <class OpOf, class BeginRow>
+__device__ __forceinline__ bool list_walk(const BitopListOperand *table, u32 n_rows, u64 seg, u32 nvalid, u32 fill_with_effect, u32 *acc, u32 lane,
+                                          OpOf op_of, BeginRow begin_row) {
+    bool lane_bad = false, empty_word = false; // per lane: a refused row of mine; an empty word among mine
+    bool sums_ok = true;                       // wave-uniform: every row's words made up exactly nvalid groups
 #pragma nounroll
-    for (u32 j0 = 0; j0 < a.n; j0 += 64u) {
-        const ListChunk ch = list_gather(a.table, j0, a.n, seg, nvalid, m_rest.fill, lane);
+    for (u32 j0 = 0; j0 < n_rows; j0 += 64u) {
+        const ListChunk ch = list_gather(table, j0, n_rows, seg, nvalid, fill_with_effect, lane);
         lane_bad |= ch.bad;
         const u64 live = __ballot(ch.cnt != 0u);
         ListCursor prod = list_first(live), cons = prod;
@@ -247,9 +245,12 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, 8) void bitop_list_segments_k
                 if (cons.j < 64u) { // wave-uniform
                     const u32 cnt = (u32)__builtin_amdgcn_readlane((int)ch.cnt, (int)cons.j);
                     const u32 wi = 128u * cons.b;
-                    if (cons.b == 0u) pos = 0u;
-                    list_apply_batch(acc, q[i][0], q[i][1], wi, cnt, pos, empty_word, j0 + cons.j == 0u ? m_first : m_rest, lane);
-                    if (wi + 128u >= cnt) sums_ok = sums_ok && pos == nvalid; // the operand's last batch
+                    if (cons.b == 0u) {
+                        pos = 0u;
+                        begin_row(j0 + cons.j);
+                    }
+                    list_apply_batch(acc, q[i][0], q[i][1], wi, cnt, pos, empty_word, op_of(j0 + cons.j), lane);
+                    if (wi + 128u >= cnt) sums_ok = sums_ok && pos == nvalid; // the row's last batch
                 }
                 list_advance(cons, ch, live);
                 list_issue(q[i], prod, ch, lane); // (into the registers just used: no batch is ever moved)
@@ -257,7 +258,31 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, 8) void bitop_list_segments_k
             }
         }
     }
-    if (!sums_ok || __ballot(lane_bad || empty_word) != 0ull) {
+    return sums_ok && __ballot(lane_bad || empty_word) == 0ull;
+}
+
+// wah_bitop_list_indexed_device.  The first operand is the same code on a preset accumulator (all ones for AND, zero otherwise;
+// the first operand of ANDNOT applied as OR).  The accumulated segment is written as decoded words into the scratch's bitmap
+// area (seg_store: 31 -> 32 repack), and the compress passes run over that -- the road of wah_bitop_many_indexed_device, one
+// bitmap-sized intermediate.
+__global__ __launch_bounds__(kSegDecodeWaves * 64, 8) void bitop_list_segments_kernel(const BitopListArgs a) {
+    __shared__ __attribute__((aligned(16))) u32 s_acc[kSegDecodeWaves][kSegGroups];
+    const u32 wave = wave_id(), lane = lane_id();
+    const u64 k = (u64)blockIdx.x * kSegDecodeWaves + wave;
+    if (k >= a.g.n_segments) return;
+    const u64 seg = a.g.first_segment + k;
+    const u64 g0 = seg * kSegGroups;
+    const u32 nvalid = a.g.groups - g0 < kSegGroups ? (u32)(a.g.groups - g0) : kSegGroups;
+    u32 *acc = s_acc[wave];
+    const u32 preset = a.op == 0u ? kOnes31 : 0u;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) reinterpret_cast<uint4 *>(acc)[64 * i + (int)lane] = make_uint4(preset, preset, preset, preset);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+
+    const ListOp m_first = list_op(a.op == 3u ? 1u : a.op), m_rest = list_op(a.op);
+    const bool ok = list_walk(a.table, a.n, seg, nvalid, m_rest.fill, acc, lane,
+                              [&](u32 j) -> const ListOp & { return j == 0u ? m_first : m_rest; }, [](u32) {});
+    if (!ok) {
         if (lane == 0) atomicOr(a.g.ctrl + kCtlError, kErrStream);
         return;
     }
@@ -271,10 +296,10 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, 8) void bitop_list_segments_k
 // of IN / NOT IN lists over a bitmap index.  The operand table is the list call's, flattened over the clauses; a second
 // table in device memory holds one 64-bit word per clause: the index one past its last operand, bit 63 = negate.
 //
-// The inner level is the list kernel's under OR, unchanged: the LDS accumulator holds the CURRENT clause's OR, the table is
-// walked 64 operands at a time whatever the clauses are, kListDepth batches are in flight.  The outer level is sixteen
+// The inner level is list_walk under OR: the LDS accumulator holds the CURRENT clause's OR, and the table is walked whatever
+// the clauses are.  The outer level is sixteen
 // registers per lane: the result's group 64 s + lane (the layout seg_store wants; an LDS row per step, no bank conflicts),
-// preset to all ones.  When the consumer reaches an operand at or behind the current clause's end the clause is FOLDED --
+// preset to all ones.  When the walk reaches an operand at or behind the current clause's end the clause is FOLDED --
 // result &= clause ^ (negate ? all ones : 0), accumulator zeroed -- and the next clause begins; the crossing is found from
 // operand numbers, so a clause whose operands were all settled in the gather (its OR is the zeroed accumulator) is folded like
 // any other, by the next operand that has words or behind the last chunk.  Nothing looks at the result before the end: a
@@ -346,46 +371,14 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, 8) void bitop_clauses_segment
     };
 
     const ListOp m = list_op(1u); // a clause is an OR
-    bool lane_bad = false, empty_word = false;
-    bool sums_ok = true;
+    const bool ok = list_walk(a.table, a.n, seg, nvalid, m.fill, acc, lane, [&](u32) -> const ListOp & { return m; }, [&](u32 j) {
 #pragma nounroll
-    for (u32 j0 = 0; j0 < a.n; j0 += 64u) {
-        const ListChunk ch = list_gather(a.table, j0, a.n, seg, nvalid, m.fill, lane);
-        lane_bad |= ch.bad;
-        const u64 live = __ballot(ch.cnt != 0u);
-        ListCursor prod = list_first(live), cons = prod;
-        ListPair q[kListDepth];
-#pragma unroll
-        for (int i = 0; i < kListDepth; ++i) {
-            list_issue(q[i], prod, ch, lane);
-            list_advance(prod, ch, live);
-        }
-        u32 pos = 0;
-#pragma nounroll
-        while (cons.j < 64u) {
-#pragma unroll
-            for (int i = 0; i < kListDepth; ++i) {
-                if (cons.j < 64u) { // wave-uniform
-                    const u32 cnt = (u32)__builtin_amdgcn_readlane((int)ch.cnt, (int)cons.j);
-                    const u32 wi = 128u * cons.b;
-                    if (cons.b == 0u) {
-                        pos = 0u;
-#pragma nounroll
-                        while ((cur & kClauseNever) <= j0 + cons.j) fold(); // this operand begins another clause (or a later one)
-                    }
-                    list_apply_batch(acc, q[i][0], q[i][1], wi, cnt, pos, empty_word, m, lane);
-                    if (wi + 128u >= cnt) sums_ok = sums_ok && pos == nvalid; // the operand's last batch
-                }
-                list_advance(cons, ch, live);
-                list_issue(q[i], prod, ch, lane);
-                list_advance(prod, ch, live);
-            }
-        }
-    }
+        while ((cur & kClauseNever) <= j) fold(); // this operand begins another clause (or a later one)
+    });
     // behind the last operand: the last clause, and in front of it those whose operands had no words to apply
 #pragma nounroll
     while ((cur & kClauseNever) <= a.n) fold();
-    if (!sums_ok || table_bad || __ballot(lane_bad || empty_word) != 0ull) {
+    if (!ok || table_bad) {
         if (lane == 0) atomicOr(a.g.ctrl + kCtlError, kErrStream);
         return;
     }
@@ -398,7 +391,7 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, 8) void bitop_clauses_segment
 // wah_bsi_range_indexed_device: lo <= value <= hi over a bit-sliced attribute (O'Neil & Quass) -- one bitmap per BIT of the
 // value, most significant first, and a range predicate is one sweep over them.  The walk is the clauses kernel's with one
 // clause per table row: the LDS accumulator holds the CURRENT slice (ORed into the zeroed image exactly as a clause is), and
-// when the consumer crosses to another row the slice is FOLDED into the sweep's state, which lives in registers, group
+// when the walk crosses to another row the slice is FOLDED into the sweep's state, which lives in registers, group
 // 64 s + lane.  The crossing is found from row numbers, so a slice whose segment was settled in the gather (one zero fill)
 // is folded like any other: a zero slice under a bound bit of 1 moves every still-equal row to "below".
 //
@@ -477,46 +470,14 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, kBsiWavesPerSimd) void bsi_ra
     };
 
     const ListOp m = list_op(1u); // a slice is ORed into the zeroed image
-    bool lane_bad = false, empty_word = false;
-    bool sums_ok = true;
+    const bool ok = list_walk(a.table, n_rows, seg, nvalid, m.fill, acc, lane, [&](u32) -> const ListOp & { return m; }, [&](u32 j) {
 #pragma nounroll
-    for (u32 j0 = 0; j0 < n_rows; j0 += 64u) {
-        const ListChunk ch = list_gather(a.table, j0, n_rows, seg, nvalid, m.fill, lane);
-        lane_bad |= ch.bad;
-        const u64 live = __ballot(ch.cnt != 0u);
-        ListCursor prod = list_first(live), cons = prod;
-        ListPair q[kListDepth];
-#pragma unroll
-        for (int i = 0; i < kListDepth; ++i) {
-            list_issue(q[i], prod, ch, lane);
-            list_advance(prod, ch, live);
-        }
-        u32 pos = 0;
-#pragma nounroll
-        while (cons.j < 64u) {
-#pragma unroll
-            for (int i = 0; i < kListDepth; ++i) {
-                if (cons.j < 64u) { // wave-uniform
-                    const u32 cnt = (u32)__builtin_amdgcn_readlane((int)ch.cnt, (int)cons.j);
-                    const u32 wi = 128u * cons.b;
-                    if (cons.b == 0u) {
-                        pos = 0u;
-#pragma nounroll
-                        while (cur < j0 + cons.j) fold(); // this row's words begin: the rows in front of it are complete
-                    }
-                    list_apply_batch(acc, q[i][0], q[i][1], wi, cnt, pos, empty_word, m, lane);
-                    if (wi + 128u >= cnt) sums_ok = sums_ok && pos == nvalid; // the row's last batch
-                }
-                list_advance(cons, ch, live);
-                list_issue(q[i], prod, ch, lane);
-                list_advance(prod, ch, live);
-            }
-        }
-    }
+        while (cur < j) fold(); // this row's words begin: the rows in front of it are complete
+    });
     // behind the last row: the last one, and in front of it those that had no words to apply
 #pragma nounroll
     while (cur < n_rows) fold();
-    if (!sums_ok || __ballot(lane_bad || empty_word) != 0ull) {
+    if (!ok) {
         if (lane == 0) atomicOr(a.g.ctrl + kCtlError, kErrStream);
         return;
     }
@@ -622,46 +583,14 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, kBsiKthWavesPerSimd) void bsi
     };
 
     const ListOp m = list_op(1u); // a row is ORed into the zeroed image
-    bool lane_bad = false, empty_word = false;
-    bool sums_ok = true;
+    const bool ok = list_walk(a.table, n_rows, seg, nvalid, m.fill, acc, lane, [&](u32) -> const ListOp & { return m; }, [&](u32 j) {
 #pragma nounroll
-    for (u32 j0 = 0; j0 < n_rows; j0 += 64u) {
-        const ListChunk ch = list_gather(a.table, j0, n_rows, seg, nvalid, m.fill, lane);
-        lane_bad |= ch.bad;
-        const u64 live = __ballot(ch.cnt != 0u);
-        ListCursor prod = list_first(live), cons = prod;
-        ListPair q[kListDepth];
-#pragma unroll
-        for (int i = 0; i < kListDepth; ++i) {
-            list_issue(q[i], prod, ch, lane);
-            list_advance(prod, ch, live);
-        }
-        u32 pos = 0;
-#pragma nounroll
-        while (cons.j < 64u) {
-#pragma unroll
-            for (int i = 0; i < kListDepth; ++i) {
-                if (cons.j < 64u) { // wave-uniform
-                    const u32 cnt = (u32)__builtin_amdgcn_readlane((int)ch.cnt, (int)cons.j);
-                    const u32 wi = 128u * cons.b;
-                    if (cons.b == 0u) {
-                        pos = 0u;
-#pragma nounroll
-                        while (cur < j0 + cons.j) fold(); // this row's words begin: the rows in front of it are complete
-                    }
-                    list_apply_batch(acc, q[i][0], q[i][1], wi, cnt, pos, empty_word, m, lane);
-                    if (wi + 128u >= cnt) sums_ok = sums_ok && pos == nvalid; // the row's last batch
-                }
-                list_advance(cons, ch, live);
-                list_issue(q[i], prod, ch, lane);
-                list_advance(prod, ch, live);
-            }
-        }
-    }
+        while (cur < j) fold(); // this row's words begin: the rows in front of it are complete
+    });
     // behind the last row that had words: the rows in front of the pass's last one; that one stays in the image
 #pragma nounroll
     while (cur + 1u < n_rows) fold();
-    if (!sums_ok || __ballot(lane_bad || empty_word) != 0ull) {
+    if (!ok) {
         if (lane == 0) atomicOr(a.ctrl + kCtlError, kErrStream);
         return;
     }
@@ -776,38 +705,24 @@ __global__ __launch_bounds__(64) void bsi_kth_decide_kernel(const BsiKthArgs a) 
     }
 }
 
-} // namespace
-
-hipError_t launch_bsi_kth_pass(const BsiKthArgs &a, hipStream_t s) {
-    if (a.n_segments == 0) return hipSuccess;
-    const u64 grid = (a.n_segments + kSegDecodeWaves - 1) / kSegDecodeWaves;
-    hipLaunchKernelGGL(bsi_kth_pass_kernel, dim3((unsigned)grid), dim3(kSegDecodeWaves * 64), 0, s, a);
+// one wavefront per segment, kSegDecodeWaves of them per workgroup
+template <class Args>
+hipError_t launch_per_segment(void (*kernel)(const Args), u64 n_segments, const Args &a, hipStream_t s) {
+    if (n_segments == 0) return hipSuccess;
+    const u64 grid = (n_segments + kSegDecodeWaves - 1) / kSegDecodeWaves;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kSegDecodeWaves * 64), 0, s, a);
     return hipGetLastError();
 }
+
+} // namespace
+
+hipError_t launch_bitop_list_segments(const BitopListArgs &a, hipStream_t s) { return launch_per_segment(bitop_list_segments_kernel, a.g.n_segments, a, s); }
+hipError_t launch_bitop_clauses_segments(const BitopClausesArgs &a, hipStream_t s) { return launch_per_segment(bitop_clauses_segments_kernel, a.g.n_segments, a, s); }
+hipError_t launch_bsi_range_segments(const BsiRangeArgs &a, hipStream_t s) { return launch_per_segment(bsi_range_segments_kernel, a.g.n_segments, a, s); }
+hipError_t launch_bsi_kth_pass(const BsiKthArgs &a, hipStream_t s) { return launch_per_segment(bsi_kth_pass_kernel, a.n_segments, a, s); }
 
 hipError_t launch_bsi_kth_decide(const BsiKthArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(bsi_kth_decide_kernel, dim3(1), dim3(64), 0, s, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_bsi_range_segments(const BsiRangeArgs &a, hipStream_t s) {
-    if (a.g.n_segments == 0) return hipSuccess;
-    const u64 grid = (a.g.n_segments + kSegDecodeWaves - 1) / kSegDecodeWaves;
-    hipLaunchKernelGGL(bsi_range_segments_kernel, dim3((unsigned)grid), dim3(kSegDecodeWaves * 64), 0, s, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_bitop_clauses_segments(const BitopClausesArgs &a, hipStream_t s) {
-    if (a.g.n_segments == 0) return hipSuccess;
-    const u64 grid = (a.g.n_segments + kSegDecodeWaves - 1) / kSegDecodeWaves;
-    hipLaunchKernelGGL(bitop_clauses_segments_kernel, dim3((unsigned)grid), dim3(kSegDecodeWaves * 64), 0, s, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_bitop_list_segments(const BitopListArgs &a, hipStream_t s) {
-    if (a.g.n_segments == 0) return hipSuccess;
-    const u64 grid = (a.g.n_segments + kSegDecodeWaves - 1) / kSegDecodeWaves;
-    hipLaunchKernelGGL(bitop_list_segments_kernel, dim3((unsigned)grid), dim3(kSegDecodeWaves * 64), 0, s, a);
     return hipGetLastError();
 }
 

@@ -30,7 +30,7 @@ The switches (gpu-wah_amd/csrc) and the probes that sit on them:
 The operand-list bit operation (wah_bitop_list.hip; list_paths() restates which way every batch and word of a segment goes):
 
   64 operands per chunk, one per lane      list_gather, j0 += 64, list_advance's  LIST_OPERAND_COUNTS, LIST_POSITIONS (a live operand in
-    (row 0 alone takes m_first)              c.j >= 63u, j0 + cons.j == 0u          rows 0, 1, 62 .. 65, 128; row 0 again in 64, 128)
+    (row 0 alone takes m_first)              c.j >= 63u, op_of: j == 0u             rows 0, 1, 62 .. 65, 128; row 0 again in 64, 128)
   128 words per batch                      list_advance, list_issue,              LIST_SEGMENT_WORDS (128 b - 1, 128 b, 128 b + 1) x
                                              list_apply_batch                       LIST_WAYS
   kListDepth = 4 batches in flight         the producer / consumer rotation       LIST_SCHEDULES (0, 1, 3, 4, 5, 8 and more batches a

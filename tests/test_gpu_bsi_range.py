@@ -12,7 +12,7 @@ import importlib
 import numpy as np
 import pytest
 
-from tests import _bsi
+from tests import _bsi, _kth
 
 pytestmark = pytest.mark.gpu
 
@@ -137,6 +137,62 @@ def test_rows_without_existence_match_zero(wah, oracle):
     _check_cases(wah, oracle, streams, values, 12, None, [("lo 0", 0, 500), ("lo 1", 1, 500), ("all", 0, 4095), ("eq 0", 0, 0)], n, "no existence")
     exists = np.arange(32 * n) < 1000
     _check_cases(wah, oracle, streams, values, 12, exists, [("lo 0", 0, 500), ("lo 1", 1, 500), ("all", 0, 4095), ("eq 0", 0, 0)], n, "existence")
+
+
+def test_settled_rows_on_both_sides_of_the_chunk_edge_are_folded(wah, oracle):
+    """The one property the shared walk (list_walk, wah_bitop_list.hip) keeps for its four callers at once: a row whose segment
+    was settled in the gather -- one zero fill, never a batch -- is still folded, on either side of the edge between two chunks
+    of 64 table rows.  992 + 31 words: two segments, the second one ragged.  Values are 64-bit multiples of 16, so slices 60 .. 63
+    are all zero.
+      range    64 slices + existence, 65 rows: rows 60 .. 63 are zero fills, row 64, the first of the second chunk, folds them;
+               bounds whose low four bits are not zero, so that a zero slice skipped changes the result;
+      k-th     two filters + 64 slices, 66 rows: the zero slices are rows 62 .. 65, the last digit of the last pass;
+      clauses  ends 63, 64 and 66, operands 62 .. 65 empty: the second clause is one empty operand, the third two;
+      list     OR of 66 operands of which 62 .. 65 are empty.
+    Expected: tests/_bsi.py and tests/_kth.py from the values, the numpy fold of the operands through the oracle."""
+    n = SEG + 31
+    rows = 32 * n
+    rng = np.random.default_rng(6466)
+    values = _bsi.uniform_values(rng, rows, 64) & np.uint64(~0xF & _bsi.U64_MAX)
+    exists, mask = rng.random(rows) < 0.9, rng.random(rows) < 0.4
+    streams = Streams(wah, n)
+    matrix = _bsi.build_slices(values, 64, exists)
+    assert matrix.shape[0] == 65 and matrix[:60].any(axis=1).all() and not matrix[60:64].any()
+    ops = [streams.of(row) for row in matrix]
+    assert all(st.numel() == 2 for st, _ in ops[60:64])  # one fill word per segment
+
+    # range: a present value a is below a + 1 and b is above b - 1 only if the zero slices under the bounds' low bits are folded
+    ordered = np.sort(values[exists])
+    a, b = int(ordered[ordered.size // 4]), int(ordered[3 * ordered.size // 4])
+    cases = [("low bits 0001 / 1111", a + 1, b - 1), ("low bits 1111 / 0001", a - 1, b + 1), ("present bounds", a, b), ("one value", a, a)]
+    assert not np.array_equal(_bsi.expected_range(values, a + 1, b - 1, exists), _bsi.expected_range(values, a, b, exists))
+    table = wah.bitop_operand_table(ops)
+    for name, lo, hi in cases:
+        got, offs = wah.bsi_range_device(table, (lo, hi), n, exists=True)
+        _same(streams, oracle, got, offs, _bsi.expected_range(values, lo, hi, exists), ("range", name))
+
+    # k-th: every answer's low four bits come from the four settled slices
+    model = _kth.Model(values, exists & mask)
+    d_mask = streams.of(_bsi.pack_bits(mask))  # (the table holds raw pointers: d_mask stays alive)
+    rows_table = wah.bitop_operand_table([d_mask, ops[64]] + ops[:64])
+    assert rows_table.shape[0] == 66 and model.total > 16
+    for name, kind, qa, qb in _kth.query_cases(model.total):
+        got = wah.bsi_kth_device(rows_table, (kind, qa, qb), n, 2)
+        assert tuple(int(v) & _bsi.U64_MAX for v in got.tolist()) == model(kind, qa, qb), ("k-th", name)
+
+    # clauses and list: 62 sparse operands, then four empty ones
+    sparse = [_bsi.pack_bits(rng.random(rows) < 1 / 128) for _ in range(62)]
+    union = np.bitwise_or.reduce(sparse)
+    assert union.any() and not (union == _bsi.ONES).all()
+    empty = streams.of(np.zeros(n, np.uint32))
+    assert empty[0].numel() == 2
+    operands = [streams.of(words) for words in sparse] + [empty] * 4
+    got, offs = wah.bitop_list_indexed_device("or", operands, n)
+    _same(streams, oracle, got, offs, union, "list")
+    for negate, want in (((False, True, True), union), ((True, True, True), ~union), ((False, False, True), np.zeros(n, np.uint32))):
+        clauses = [(operands[:63], negate[0]), (operands[63:64], negate[1]), (operands[64:], negate[2])]
+        got, offs = wah.bitop_clauses_indexed_device(clauses, n)
+        _same(streams, oracle, got, offs, want, ("clauses", negate))
 
 
 # ---- 2: chaining and the column front ends --------------------------------------------------------------------------------------

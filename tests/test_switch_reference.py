@@ -44,7 +44,7 @@ SOURCES = {
     "kListShortFill": ("wah_bitop_list.hip", r"constexpr u32 kListShortFill = (\d+);"),
     "WAH_LIST_DEPTH": ("wah_bitop_list.hip", r"#define WAH_LIST_DEPTH (\d+)"),
     "list batch words": ("wah_bitop_list.hip", r"if \((\d+)u \* \(c\.b \+ 1u\) < cnt\)"),
-    "list chunk operands": ("wah_bitop_list.hip", r"j0 < a\.n; j0 \+= (\d+)u\)"),
+    "list chunk operands": ("wah_bitop_list.hip", r"j0 < n_rows; j0 \+= (\d+)u\)"),
     "WAH_SEG_WAVES": ("wah_segdecode.hpp", r"#define WAH_SEG_WAVES (\d+)"),
     "list count clamp factor": ("wah_bitop_list.hip", r"n0 = in0 \? min\(word_groups\(w0\), (\d+)u \* kSegGroups\)"),
 }
