@@ -56,6 +56,9 @@ from .api import (  # noqa: F401
     BSI_KTH_DESCENDING,
     BSI_KTH_QUANTILE,
     BSI_KTH_MAX_FILTERS,
+    fetch_device,
+    FETCH_BITS,
+    FETCH_FIRST,
     count_device,
     count_masked_device,
     positions_device,

@@ -72,6 +72,9 @@ ABI_SYMBOLS = {
     "wah_bsi_kth_scratch_bytes": (_sz, [_u64, _u64]),
     "wah_bsi_kth_indexed_device": (_int, [_u64, _u64, _u64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "wah_bsi_kth_status": (_int, [_vp, _vp]),
+    "wah_fetch_scratch_bytes": (_sz, [_u64, _u64]),
+    "wah_fetch_indexed_device": (_int, [ctypes.c_uint, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _sz, _vp]),
+    "wah_fetch_status": (_int, [_vp, _vp]),
     "wah_select_scratch_bytes": (_sz, [_u64, _u64]),
     "wah_count_list_indexed_device": (_int, [_u64, _u64, _vp, _vp, _vp, _sz, _vp]),
     "wah_count_masked_indexed_device": (_int, [_u64, _u64, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
@@ -671,6 +674,39 @@ def bsi_kth_device(table, query, n_words, n_filters, scratch=None, result=None, 
     if check:
         _check(lib().wah_bsi_kth_status(scratch.data_ptr(), sp), "bsi_kth")
     return result
+
+
+FETCH_BITS, FETCH_FIRST = 0, 1  # WAH_FETCH_*
+
+
+def fetch_device(table, rows, n_words, mode, scratch=None, out=None, check=True):
+    """The values of listed rows in one call, without decoding a bitmap (wah_fetch_indexed_device).  table: a list of (stream,
+    seg_offsets) pairs or a ready [k, 3] table (bitop_operand_table, columns.column_operand_table); rows: an int64 device tensor
+    of positions, NON-DESCENDING, each below 32 * n_words -- only the device reads either.  mode FETCH_BITS: entry i of the
+    result is the value whose bit k - 1 - j is bit rows[i] of table row j (row 0 most significant, k <= 64; 64-bit patterns: a
+    value at or above 2^63 reads as negative); FETCH_FIRST: the lowest j whose bitmap has the bit set, -1 (UINT64_MAX) if none.
+    Only the segments that hold a listed row are read and checked.  Returns the int64 device tensor [len(rows)].  scratch / out:
+    reuse these tensors; check=False: only enqueue (the caller reads wah_fetch_status later)."""
+    torch = _torch()
+    table = _operand_table(table)
+    dev = table.device
+    if mode not in (FETCH_BITS, FETCH_FIRST):
+        raise WahError("mode: FETCH_BITS or FETCH_FIRST")
+    if rows.dtype != torch.int64 or rows.dim() != 1 or rows.device != dev or not rows.is_contiguous():
+        raise WahError("rows: a contiguous one-dimensional int64 tensor on the table's device")
+    n, k, r = int(n_words), int(table.shape[0]), int(rows.numel())
+    if scratch is None:
+        scratch = torch.empty(int(lib().wah_fetch_scratch_bytes(n, r)), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.empty(r, dtype=torch.int64, device=dev)
+    elif out.dtype != torch.int64 or tuple(out.shape) != (r,) or out.device != dev or not out.is_contiguous():
+        raise WahError("out: a contiguous int64 [len(rows)] tensor on the table's device")
+    sp = _stream_ptr(torch)
+    _check(lib().wah_fetch_indexed_device(mode, n, k, table.data_ptr(), rows.data_ptr() if r else None, r, out.data_ptr() if r else None,
+                                          scratch.data_ptr(), scratch.numel(), sp), "wah_fetch_indexed_device")
+    if check:
+        _check(lib().wah_fetch_status(scratch.data_ptr(), sp), "fetch")
+    return out
 
 
 def count_device(operands_or_table, n_words, scratch=None, counts=None, check=True):

@@ -450,6 +450,58 @@ def top_rows(wah, bsi, k, mask=None, largest=True):
     return torch.cat(parts)
 
 
+def _fetch_columns(wah, stream, seg_offsets, n_words_per_column, column_ids, rows, mode):
+    """One wah_fetch_indexed_device call over columns of a compress_column_matrix result for rows in ANY order: the call wants
+    them non-descending, so they are sorted (torch.sort) and the result is scattered back -- plumbing."""
+    import torch
+
+    if rows.dtype != torch.int64 or rows.dim() != 1 or rows.device != stream.device:
+        raise ValueError("rows: a one-dimensional int64 tensor on the index's device")
+    table = column_operand_table(stream, seg_offsets, n_words_per_column, column_ids)
+    ordered, order = torch.sort(rows)
+    got = wah.fetch_device(table, ordered.contiguous(), n_words_per_column, mode)
+    out = torch.empty_like(got)
+    out[order] = got
+    return out
+
+
+def values_at_rows(wah, bsi, rows):
+    """`SELECT value ... WHERE rowid IN (rows)`: the values a bit-sliced attribute holds in the listed rows, in one call and
+    without decoding a slice (wah_fetch_indexed_device, WAH_FETCH_BITS).  bsi: what bsi_from_values returned; rows: an int64
+    device tensor of row numbers below 32 * n_words_per_column, in any order, duplicates allowed -- select_rows or top_rows
+    output goes in as it is.  With an existence bitmap that bitmap is the table's first row, so the top bit of every fetched
+    word says whether the row has a value.  Returns (values int64 tensor, have bool tensor or None), entry i for rows[i]."""
+    stream, seg_offsets, n, n_bits, has_exists = bsi
+    ids = ([n_bits] if has_exists else []) + list(range(n_bits))
+    got = _fetch_columns(wah, stream, seg_offsets, n, ids, rows, wah.FETCH_BITS)
+    if not has_exists:
+        return got, None
+    return got & ((1 << n_bits) - 1), ((got >> n_bits) & 1) != 0
+
+
+def keys_at_rows(wah, index, rows):
+    """The keys an equality-encoded attribute holds in the listed rows, in one call over ALL its value columns
+    (wah_fetch_indexed_device, WAH_FETCH_FIRST): index is what index_from_keys returned, rows as for values_at_rows.  Returns
+    an int64 tensor, entry i the key of rows[i], -1 where no column has the row (a row behind the key column's own length)."""
+    stream, seg_offsets, n = index
+    n_values = (int(seg_offsets.numel()) - 1) // (n // SEGMENT_WORDS)
+    return _fetch_columns(wah, stream, seg_offsets, n, list(range(n_values)), rows, wah.FETCH_FIRST)
+
+
+def select_values(wah, predicates, n_words_per_column, attributes, first=0, limit=None):
+    """`SELECT a, b ... WHERE <conjunction> LIMIT limit OFFSET first` without decoding a bitmap: select_rows (predicates as for
+    filter_columns), then one fetch per attribute over the rows it returned.  attributes: a list whose entries are what
+    bsi_from_values returned (fetched by values_at_rows: a (values, have) pair) or what index_from_keys returned (keys_at_rows:
+    a tensor of keys), all of the predicates' column length.  Returns (rows, [one result per attribute], matching rows)."""
+    rows, matching = select_rows(wah, predicates, n_words_per_column, first=first, limit=limit)
+    fetched = []
+    for attribute in attributes:
+        if attribute[2] != n_words_per_column:
+            raise ValueError("an attribute of another column length")
+        fetched.append(values_at_rows(wah, attribute, rows) if len(attribute) == 5 else keys_at_rows(wah, attribute, rows))
+    return rows, fetched, matching
+
+
 def compress_column_ranges(compressor, flat, lengths, wait=True):
     """Columns of DIFFERENT lengths (each a multiple of 992 words) stored back to back in `flat`: still one launch.
     Returns (stream, column_offsets) like compress_column_matrix: column c is stream[column_offsets[c] :

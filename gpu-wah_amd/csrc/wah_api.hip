@@ -1411,6 +1411,68 @@ int wah_bsi_kth_status(void *d_scratch, void *stream) {
     return read_status(d_scratch, stream);
 }
 
+// The values of listed rows (wah_bitop_list.hip, fetch_check_kernel / fetch_items_kernel).  The scratch: control block (with the
+// item count), then the item list: one entry per 64 listed rows and one more per segment a list can change into -- it goes
+// with the list, and with the bitmap only while the list is longer than the bitmap has segments.
+static_assert(WAH_FETCH_BITS == wah::kFetchBits && WAH_FETCH_FIRST == wah::kFetchFirst, "the modes the items kernel knows");
+namespace {
+struct FetchLayout {
+    SegGeometry g;
+    uint64_t capacity;
+    size_t items, total;
+};
+FetchLayout fetch_layout(uint64_t n_words, uint64_t n_rows) {
+    FetchLayout l;
+    const uint64_t most = 1ull << 40; // (the size of a call that is refused anyway)
+    l.g = seg_geometry(n_words < most ? n_words : most);
+    if (n_rows > most) n_rows = most;
+    l.capacity = ceil_div(n_rows, 64) + (n_rows < l.g.n_segments ? n_rows : l.g.n_segments);
+    l.items = wah::kCtlWords * sizeof(uint32_t);
+    l.total = l.items + round256(l.capacity * sizeof(uint64_t));
+    return l;
+}
+} // namespace
+
+size_t wah_fetch_scratch_bytes(uint64_t n_words, uint64_t n_rows) { return fetch_layout(n_words, n_rows).total; }
+
+int wah_fetch_indexed_device(unsigned mode, uint64_t n_words, uint64_t n_operands, const wah_bitop_operand *d_operands, const uint64_t *d_rows,
+                             uint64_t n_rows, uint64_t *d_out, void *d_scratch, size_t scratch_bytes, void *stream) {
+    g_err[0] = 0;
+    if (mode != WAH_FETCH_BITS && mode != WAH_FETCH_FIRST) return refuse("unknown mode", WAH_ERR_ARG);
+    if (n_operands < 1 || n_operands > (mode == WAH_FETCH_BITS ? (uint64_t)WAH_BSI_MAX_SLICES : (uint64_t)WAH_BITOP_LIST_MAX_OPERANDS))
+        return refuse("between 1 and 64 table rows (WAH_FETCH_BITS) or 2^24 (WAH_FETCH_FIRST)", WAH_ERR_ARG);
+    if (n_rows && !n_words) return refuse("listed rows of an empty bitmap", WAH_ERR_ARG);
+    if (n_words >= (1ull << 40) || n_rows >= (1ull << 40)) return refuse("2^40 words or listed rows, or more", WAH_ERR_ARG);
+    if (!table_ok(n_operands, d_operands, n_words) || (n_rows && (!d_rows || !d_out)) || !aligned(d_rows, 7) || !aligned(d_out, 7) ||
+        !scratch_ok(d_scratch))
+        return refuse("null or misaligned table, rows, output or scratch", WAH_ERR_ARG);
+    const FetchLayout l = fetch_layout(n_words, n_rows);
+    if (scratch_bytes < l.total) return refuse("scratch too small", WAH_ERR_WORKSPACE);
+    char *sc = static_cast<char *>(d_scratch);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    wah::FetchArgs a = {};
+    a.table = reinterpret_cast<const wah::BitopListOperand *>(d_operands);
+    a.rows = d_rows;
+    a.out = d_out;
+    a.items = reinterpret_cast<uint64_t *>(sc + l.items);
+    a.ctrl = reinterpret_cast<uint32_t *>(sc);
+    a.n_rows = n_rows;
+    a.n_bits = 32 * n_words;
+    a.groups = l.g.groups;
+    a.capacity = l.capacity;
+    a.n_operands = (uint32_t)n_operands;
+    hipError_t e = wah::launch_clear(sc, wah::kCtlWords * sizeof(uint32_t), s); // the error word (read by wah_fetch_status) and the item count
+    if (e == hipSuccess) e = wah::launch_fetch_check(a, s);
+    if (e == hipSuccess) e = wah::launch_fetch_items(a, mode, s);
+    if (e != hipSuccess) return refuse("fetch launch", WAH_ERR_HIP, e);
+    return WAH_OK;
+}
+
+int wah_fetch_status(void *d_scratch, void *stream) {
+    if (!d_scratch) return WAH_ERR_ARG;
+    return read_status(d_scratch, stream);
+}
+
 // Set bits counted and listed in the compressed domain (wah_select.hip).  The scratch: control block, then the positions
 // call's rank table (one u64 per segment + 1) and the two upper levels of its scan (one u64 per 4096 entries of the level
 // below) -- it goes with n_words / 992, not with the operands' number or their words.

@@ -6,6 +6,7 @@
 //   bitop_clauses_segments_kernel  AND over clauses of (negated) ORs (wah_bitop_clauses_indexed_device)
 //   bsi_range_segments_kernel      lo <= value <= hi over a bit-sliced attribute (wah_bsi_range_indexed_device)
 //   bsi_kth_pass_kernel            one pass of the radix select over such an attribute (wah_bsi_kth_indexed_device)
+//   fetch_items_kernel             the values of listed rows, one wavefront per 64 listed rows of a segment (wah_fetch_indexed_device)
 // The walk itself is written once (list_walk); a kernel adds the state it keeps per segment, what it does when the walk crosses to
 // another row of the table, and what it stores.
 //
@@ -705,6 +706,120 @@ __global__ __launch_bounds__(64) void bsi_kth_decide_kernel(const BsiKthArgs a) 
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// wah_fetch_indexed_device: the values of LISTED rows -- `SELECT price, city ... LIMIT 100` behind the row numbers.  The walk is
+// the range kernel's, one table row at a time ORed into the zeroed image; what is kept beside it is not per group but per
+// LISTED ROW: lane l owns one listed row of the segment, and when the walk crosses to another table row it reads the ONE bit
+// its row has in the image -- group p / 31 of the segment, bit p % 31 -- and the image is zeroed again.
+//   WAH_FETCH_BITS   the bit goes to significance n_operands - 1 - row (row 0 most significant: a bit-sliced attribute);
+//   WAH_FETCH_FIRST  the first table row whose bit is set is the value (the key of an equality-encoded attribute).
+// A table row that was settled in the gather (one zero fill) has no bit anywhere and is not folded at all: only rows that had
+// words are, so a clustered index of thousands of bins costs a listed segment its gather and the few bins that live there.
+//
+// Unlike every other caller of list_walk, ONLY the segments that hold a listed row are walked.  Two launches:
+//   fetch_check_kernel  one listed row per thread: below 32 n_words, not smaller than its predecessor.  Row i is the HEAD of an
+//                       item when i % 64 == 0 or its segment differs from row i - 1's, so an item is at most 64 consecutive
+//                       listed rows of one segment; the heads' list indices are appended to the item list -- a ballot, one
+//                       vector atomic add per wave -- in no particular order.
+//   fetch_items_kernel  the host cannot know how many items there are, so the grid has a fixed size (at most kFetchGridWaves
+//                       wavefronts) and its waves stride over the item list.  The launch order is the only synchronisation.
+//                       Nothing is read through a listed row unless the check pass accepted EVERY row: with an error in the
+//                       control block the kernel returns at once.
+// One wave owns its listed rows across all table rows: no atomics on the output.  A segment with R listed rows is walked
+// ceil(R / 64) times (more where items are cut at multiples of 64 of the LIST): the call is for lists that are short beside the
+// bitmap.
+constexpr u32 kFetchGridWaves = 8192; // wavefronts of fetch_items_kernel at the most: 256 CUs x 4 SIMDs x 8 waves
+constexpr u32 kFetchSegBits = kSegGroups * 31u;
+static_assert(kFetchGridWaves % kSegDecodeWaves == 0, "whole workgroups");
+
+__global__ __launch_bounds__(256) void fetch_check_kernel(const FetchArgs a) {
+    const u32 lane = lane_id();
+    const u64 n_waves = (u64)gridDim.x * 4u;
+    unsigned long long *counter = reinterpret_cast<unsigned long long *>(a.ctrl + kCtlFetchItems);
+    bool bad = false;
+#pragma nounroll
+    for (u64 base = ((u64)blockIdx.x * 4u + wave_id()) * 64u; base < a.n_rows; base += n_waves * 64u) { // (wave-uniform)
+        const u64 i = base + lane;
+        const bool has = i < a.n_rows;
+        u64 p = 0, before = 0;
+        if (has) {
+            p = a.rows[i];
+            if (i) before = a.rows[i - 1];
+        }
+        bad |= has && (p >= a.n_bits || p < before);
+        const bool head = has && (lane == 0u || p / kFetchSegBits != before / kFetchSegBits); // (base is a multiple of 64)
+        const u64 heads = __ballot(head);                                                    // (lane 0 has a row: never 0)
+        u64 first = 0;
+        if (lane == 0u) first = atomicAdd(counter, (unsigned long long)__popcll(heads));
+        first = uniform64(first);
+        // a list that does not ascend can have more heads than the list has room for: it is refused, and nothing is put outside
+        const u64 slot = first + (u64)__popcll(heads & ((1ull << lane) - 1ull));
+        if (head && slot < a.capacity) a.items[slot] = i;
+    }
+    if (__ballot(bad) != 0ull && lane == 0u) atomicOr(a.ctrl + kCtlError, kErrStream);
+}
+
+template <u32 kMode>
+__global__ __launch_bounds__(kSegDecodeWaves * 64, 8) void fetch_items_kernel(const FetchArgs a) {
+    __shared__ __attribute__((aligned(16))) u32 s_acc[kSegDecodeWaves][kSegGroups];
+    const u32 wave = wave_id(), lane = lane_id();
+    if (a.ctrl[kCtlError] != 0u) return; // a refused row: no stream is read
+    const u64 counted = *reinterpret_cast<const u64 *>(a.ctrl + kCtlFetchItems);
+    const u64 n_items = counted < a.capacity ? counted : a.capacity;
+    const u64 stride = (u64)gridDim.x * kSegDecodeWaves;
+    u32 *acc = s_acc[wave];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) reinterpret_cast<uint4 *>(acc)[64 * i + (int)lane] = make_uint4(0u, 0u, 0u, 0u);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    const ListOp m = list_op(1u); // a table row is ORed into the zeroed image
+
+#pragma nounroll
+    for (u64 t = (u64)blockIdx.x * kSegDecodeWaves + wave; t < n_items; t += stride) {
+        // the item: the listed rows from its head up to the next multiple of 64 of the list that lie in the head's segment (the
+        // list ascends: they are the first ones)
+        const u64 i0 = uniform64(a.items[t]);
+        if (i0 >= a.n_rows) continue;
+        const u64 behind = (i0 | 63ull) + 1ull;
+        const u64 i = i0 + lane;
+        const bool has = i < (behind < a.n_rows ? behind : a.n_rows);
+        const u64 p = has ? a.rows[i] : 0ull;
+        const u64 group = p / 31u;
+        const u64 seg = uniform64(group / kSegGroups);
+        const u64 g0 = seg * kSegGroups;
+        if (g0 >= a.groups) continue; // (no accepted row lies there)
+        const bool mine = has && group / kSegGroups == seg;
+        const u32 g = mine ? (u32)(group - g0) : 0u, bit = (u32)(p - group * 31u);
+        const u32 nvalid = a.groups - g0 < kSegGroups ? (u32)(a.groups - g0) : kSegGroups;
+
+        u64 v = kMode == kFetchFirst ? ~0ull : 0ull;
+        u32 cur = 0;       // the table row the image holds (wave-uniform)
+        bool open = false; // ... if it holds one: rows settled in the gather never get there
+        // fold the image's row into the listed rows' values and zero the image for the next one
+        auto fold = [&]() {
+            const u32 b = (acc[g] >> bit) & 1u;
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+#pragma unroll
+            for (int k = 0; k < 4; ++k) reinterpret_cast<uint4 *>(acc)[64 * k + (int)lane] = make_uint4(0u, 0u, 0u, 0u);
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            if (kMode == kFetchBits)
+                v |= (u64)b << ((a.n_operands - 1u - cur) & 63u); // (at most 64 table rows: 0 .. 63, never a shift by 64)
+            else if (b != 0u && v == ~0ull)
+                v = cur;
+        };
+        const bool ok = list_walk(a.table, a.n_operands, seg, nvalid, m.fill, acc, lane, [&](u32) -> const ListOp & { return m; }, [&](u32 j) {
+            if (open) fold(); // this row's words begin: the one in the image is complete
+            cur = j;
+            open = true;
+        });
+        if (open) fold();
+        if (!ok) {
+            if (lane == 0) atomicOr(a.ctrl + kCtlError, kErrStream);
+            return;
+        }
+        if (mine) a.out[i] = v;
+    }
+}
+
 // one wavefront per segment, kSegDecodeWaves of them per workgroup
 template <class Args>
 hipError_t launch_per_segment(void (*kernel)(const Args), u64 n_segments, const Args &a, hipStream_t s) {
@@ -720,6 +835,26 @@ hipError_t launch_bitop_list_segments(const BitopListArgs &a, hipStream_t s) { r
 hipError_t launch_bitop_clauses_segments(const BitopClausesArgs &a, hipStream_t s) { return launch_per_segment(bitop_clauses_segments_kernel, a.g.n_segments, a, s); }
 hipError_t launch_bsi_range_segments(const BsiRangeArgs &a, hipStream_t s) { return launch_per_segment(bsi_range_segments_kernel, a.g.n_segments, a, s); }
 hipError_t launch_bsi_kth_pass(const BsiKthArgs &a, hipStream_t s) { return launch_per_segment(bsi_kth_pass_kernel, a.n_segments, a, s); }
+
+hipError_t launch_fetch_check(const FetchArgs &a, hipStream_t s) {
+    if (a.n_rows == 0) return hipSuccess;
+    const u64 want = (a.n_rows + 255) / 256;
+    constexpr u64 most = 256u * 8u;
+    hipLaunchKernelGGL(fetch_check_kernel, dim3((unsigned)(want > most ? most : want)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// a grid of fixed size -- the item count is known to the device only --, smaller only where the item list has no room for more
+hipError_t launch_fetch_items(const FetchArgs &a, u32 mode, hipStream_t s) {
+    if (a.n_rows == 0) return hipSuccess;
+    const u64 waves = a.capacity < kFetchGridWaves ? a.capacity : kFetchGridWaves;
+    const dim3 grid((unsigned)((waves + kSegDecodeWaves - 1) / kSegDecodeWaves)), block(kSegDecodeWaves * 64);
+    if (mode == kFetchFirst)
+        hipLaunchKernelGGL(fetch_items_kernel<kFetchFirst>, grid, block, 0, s, a);
+    else
+        hipLaunchKernelGGL(fetch_items_kernel<kFetchBits>, grid, block, 0, s, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_bsi_kth_decide(const BsiKthArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(bsi_kth_decide_kernel, dim3(1), dim3(64), 0, s, a);

@@ -288,6 +288,28 @@ struct BsiKthArgs {
 hipError_t launch_bsi_kth_pass(const BsiKthArgs &a, hipStream_t s);
 hipError_t launch_bsi_kth_decide(const BsiKthArgs &a, hipStream_t s);
 
+// wah_fetch_indexed_device (wah_bitop_list.hip): the values of listed rows -- per listed row the one bit it has in every row
+// of the table.  rows: n_rows positions in DEVICE memory, non-descending; out: one u64 per listed row.  The check pass cuts the
+// list into ITEMS -- at most 64 consecutive listed rows of one segment -- and appends the list index of every item's first row
+// to `items` (capacity entries, in the scratch); how many there are stays in the control block at kCtlFetchItems (64 bits,
+// cleared by the caller).  The items pass walks one segment per item.
+constexpr uint32_t kCtlFetchItems = 224; // (a 128-byte line of the control block that no other call of this scratch uses)
+constexpr uint32_t kFetchBits = 0, kFetchFirst = 1; // WAH_FETCH_BITS, WAH_FETCH_FIRST
+struct FetchArgs {
+    const BitopListOperand *table;
+    const uint64_t *rows;
+    uint64_t *out;
+    uint64_t *items;
+    uint32_t *ctrl;
+    uint64_t n_rows;
+    uint64_t n_bits;   // 32 n_words: a row is below it
+    uint64_t groups;   // G of the bitmap
+    uint64_t capacity; // entries of `items`
+    uint32_t n_operands;
+};
+hipError_t launch_fetch_check(const FetchArgs &a, hipStream_t s);
+hipError_t launch_fetch_items(const FetchArgs &a, uint32_t mode, hipStream_t s);
+
 // ... on operands of few words per segment: their runs merged in the compressed domain, one lane per segment
 // (wah_bitop_runs.hip): count pass, scan of the tile totals, write pass
 struct BitopRunsArgs {

@@ -516,6 +516,48 @@ int wah_bsi_kth_indexed_device(uint64_t n_words, uint64_t n_filters, uint64_t n_
                                const uint64_t *d_query, uint64_t *d_result, void *d_scratch, size_t scratch_bytes, void *stream);
 int wah_bsi_kth_status(void *d_scratch, void *stream);
 
+/* The VALUES of listed rows in ONE call, without decoding a bitmap -- the last step of `SELECT price, city FROM t WHERE ...
+ * LIMIT 100`: the positions call gives the 100 row numbers, this call says what an attribute holds in them.  It is the inverse of
+ * the two ways into the index (a bit-sliced attribute, an equality-encoded one): values -> index -> values.
+ *   d_operands: a table exactly as for the list call (8-byte aligned, windows into column matrices allowed, rows may repeat, the
+ *   length may be a capacity, an entry may name the not-yet-checked output of an earlier call on the stream).
+ *   d_rows: n_rows positions p = 32 * word + bit in DEVICE memory, 8-byte aligned, NON-DESCENDING (duplicates are allowed and
+ *   each gets its own output), each below 32 * n_words -- so a pad bit can never be asked for, and pad bits never matter.
+ *   d_out: n_rows uint64, 8-byte aligned; entry i belongs to d_rows[i].
+ *   WAH_FETCH_BITS: out[i] = the unsigned value whose bit n_operands - 1 - j is bit d_rows[i] of table row j (row 0 is the MOST
+ *   significant, the sweep order of the range call): a bit-sliced attribute, 1 <= n_operands <= WAH_BSI_MAX_SLICES.  With the
+ *   existence bitmap as row 0 in front of up to 63 slices the top bit of the output says whether the row has a value.
+ *   WAH_FETCH_FIRST: out[i] = the lowest j whose bitmap has bit d_rows[i] set, UINT64_MAX if none has: the key of an
+ *   equality-encoded attribute, 1 <= n_operands <= WAH_BITOP_LIST_MAX_OPERANDS.
+ * Table and rows are read by the device only: the call is asynchronous on `stream`, allocates nothing, never synchronises, and a
+ * captured graph replayed after d_rows and / or the table were overwritten in place, with the same counts, fetches the NEW rows.
+ * Two launches and the clear of the control words; no workgroup waits for another.  The first checks every listed row and cuts
+ * the list into items of at most 64 consecutive listed rows of one segment; the second is a grid of fixed size whose wavefronts
+ * stride over the items: each walks the table for its segment as the range call does, and every lane picks the one bit of its
+ * own listed row out of the segment's image whenever the walk crosses to another table row.
+ * UNLIKE THE OTHER INDEXED CALLS, ONLY THE SEGMENTS THAT HOLD A LISTED ROW ARE READ AND CHECKED: the cost goes with the listed
+ * rows and the words the table's rows hold in the segments they touch, not with the index -- so the verdict depends on WHICH
+ * rows are listed (a malformed segment that no listed row lies in is never seen), and not on the data in them.  A segment with
+ * R listed rows is walked at least ceil(R / 64) times: for a list that approaches every row, decoding the slices is the better
+ * tool.
+ *   d_scratch: wah_fetch_scratch_bytes(n_words, n_rows) bytes, 256-byte aligned, no initialisation: the control words and the
+ *   item list, ceil(n_rows / 64) + min(n_rows, segments) entries.  A multiple of 256, never 0, monotone in n_rows.
+ * n_rows == 0 is WAH_OK (d_rows and d_out may be null) and wah_fetch_status() then reports WAH_OK.  Errors the host can see come
+ * back before any HIP call, the argument checks first: an unknown mode, n_operands == 0 or above 64 (BITS) or above
+ * WAH_BITOP_LIST_MAX_OPERANDS (FIRST), n_words == 0 with n_rows > 0, n_words >= 2^40 or n_rows >= 2^40, a null or misaligned
+ * table, rows, out (8 B) or scratch (256 B): WAH_ERR_ARG; too small a scratch: WAH_ERR_WORKSPACE.  Everything only the device
+ * sees is reported by wah_fetch_status(), which synchronises the stream: WAH_ERR_STREAM for a row at or beyond 32 * n_words, a
+ * row smaller than its predecessor, and everything the list call refuses in an operand, in the segments that are read.  EVERY
+ * listed row is checked, and before it steers a read: after a refused row the second launch reads no stream at all.  The output
+ * of a refused call is unspecified.  wah_fetch_status(NULL, ...): WAH_ERR_ARG. */
+#define WAH_FETCH_BITS 0u
+#define WAH_FETCH_FIRST 1u
+size_t wah_fetch_scratch_bytes(uint64_t n_words, uint64_t n_rows);
+int wah_fetch_indexed_device(unsigned mode, uint64_t n_words, uint64_t n_operands, const wah_bitop_operand *d_operands,
+                             const uint64_t *d_rows, uint64_t n_rows, uint64_t *d_out, void *d_scratch, size_t scratch_bytes,
+                             void *stream);
+int wah_fetch_status(void *d_scratch, void *stream);
+
 /* What a query wants from a result bitmap, WITHOUT decoding it: how many bits it has set (COUNT(*)) and which ones (row
  * numbers, with LIMIT / OFFSET).  A bitmap of n_words words has its bits at positions p = 32 * word + bit, LSB first; group g,
  * bit j, of its stream is position 31 * g + j.  "Set bits" are the positions p < 32 * n_words whose bit is 1: the 0 to 30 pad
