@@ -64,6 +64,7 @@ from .api import (  # noqa: F401
     positions_device,
     from_positions_device,
     from_positions_max_words,
+    bsi_build_device,
     merge_fills_device,
     StreamReport,
     gen_uniform_device,

@@ -84,6 +84,9 @@ ABI_SYMBOLS = {
     "wah_from_positions_scratch_bytes": (_sz, [_u64, _u64]),
     "wah_from_positions_device": (_int, [_u64, _u64, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
     "wah_from_positions_status": (_int, [_vp, _vp]),
+    "wah_bsi_build_scratch_bytes": (_sz, [_u64, _u64]),
+    "wah_bsi_build_device": (_int, [_u64, _u64, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
+    "wah_bsi_build_status": (_int, [_vp, _u64, _u64, _vp]),
     "wah_gen_uniform_device": (_int, [_vp, _u64, _u64, _u64, _vp]),
     "wah_gen_clustered_device": (_int, [_vp, _u64, _u64, _u64, _vp]),
     "wah_copy_device": (_int, [_vp, _vp, _u64, _vp]),
@@ -846,6 +849,50 @@ def from_positions_device(rows, list_ends, n_words, scratch=None, out=None, out_
         return out, count, out_offsets
     _check(lib().wah_from_positions_status(scratch.data_ptr(), sp), "from_positions")
     return out[: int(count.item())], out_offsets[: k * n_seg + 1]
+
+
+def bsi_build_device(values, n_bits, n_words, exists=None, scratch=None, out=None, out_offsets=None, check=True):
+    """The bit-sliced index of a value column in one call (wah_bsi_build_device): the column is transposed into its decoded slice
+    matrix on the device and that is compressed as one bitmap.  values: a contiguous one-dimensional int64 CUDA tensor, read as
+    UNSIGNED, every value below 2^n_bits, n_bits 1 .. 64; exists: a torch.bool tensor of the same length on the same device -- a
+    row without a value is stored as 0 and the existence bitmap becomes the last slice -- or None; only the device reads either.
+    n_words: the words of one slice, a multiple of 992 that holds every row.  Returns (stream, seg_offsets): the slices'
+    compress() streams back to back, MOST significant slice first, and the n_slices * (n_words / 992) + 1 entries of their
+    segment index; slice i is the operand (stream, seg_offsets[i * (n_words // 992):]), and the pair goes into
+    columns.column_operand_table as a column matrix's does.  scratch / out / out_offsets: reuse these tensors (out defaults to
+    wah_max_compressed_words(n_slices * n_words) words); check=False: only enqueue and return (out, count tensor, out_offsets)
+    -- the caller reads wah_bsi_build_status later."""
+    torch = _torch()
+    if values.dtype != torch.int64 or values.dim() != 1 or not values.is_cuda or not values.is_contiguous():
+        raise WahError("values: a contiguous one-dimensional int64 CUDA tensor")
+    dev = values.device
+    n, bits, r = int(n_words), int(n_bits), int(values.numel())
+    if exists is not None and (exists.dtype != torch.bool or tuple(exists.shape) != (r,) or exists.device != dev or not exists.is_contiguous()):
+        raise WahError("exists: a contiguous torch.bool tensor of the values' length on their device")
+    if not 1 <= bits <= 64 or n <= 0 or n % 992:
+        raise WahError("between 1 and 64 bits, slices of a multiple of 992 words")
+    k = bits + (exists is not None)
+    entries = k * (n // 992) + 1
+    if scratch is None:
+        scratch = torch.empty(int(lib().wah_bsi_build_scratch_bytes(n, k)), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.empty(max_compressed_words(k * n), dtype=torch.int32, device=dev)
+    else:
+        _as_words(torch, out)
+    if out_offsets is None:
+        out_offsets = torch.empty(entries, dtype=torch.int64, device=dev)
+    elif out_offsets.dtype != torch.int64 or out_offsets.numel() < entries or not out_offsets.is_contiguous() or out_offsets.device != dev:
+        raise WahError("out_offsets: a contiguous int64 tensor of n_slices * n_words / 992 + 1 entries on the values' device")
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    sp = _stream_ptr(torch)
+    # (an empty bool tensor still stands for "with an existence bitmap": the library tells by the pointer, so it gets the scratch's)
+    d_exists = None if exists is None else exists.data_ptr() if r else scratch.data_ptr()
+    _check(lib().wah_bsi_build_device(n, bits, values.data_ptr() if r else None, r, d_exists, out.data_ptr(), out.numel(), count.data_ptr(),
+                                      out_offsets.data_ptr(), scratch.data_ptr(), scratch.numel(), sp), "wah_bsi_build_device")
+    if not check:
+        return out, count, out_offsets
+    _check(lib().wah_bsi_build_status(scratch.data_ptr(), n, k, sp), "bsi_build")
+    return out[: int(count.item())], out_offsets[:entries]
 
 
 StreamReport = collections.namedtuple(

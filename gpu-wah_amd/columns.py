@@ -262,16 +262,8 @@ def index_from_keys(wah, keys, n_values, n_words_per_column=None, check=True):
     return stream, seg_offsets, n
 
 
-def bsi_from_values(wah, values, n_bits, n_words_per_column=None, exists=None):
-    """The bit-sliced index of a value column (O'Neil & Quass): one bitmap per BIT of the value instead of one per distinct
-    value, what a price, a timestamp or an id needs.  values: an int64 device tensor with one value in [0, 2^n_bits) per row,
-    n_bits <= 63; exists: a bool device tensor of the same length, the rows that have a value at all (their values elsewhere
-    are stored as 0), or None.  Building is plumbing: the decoded slice matrix [n_bits (+ 1), n_words], MOST significant slice
-    first and the existence row last, is made with torch ops and compressed in one launch (compress_column_matrix) -- slices
-    are mostly incompressible, which is the compressor's own road.  n_words_per_column defaults to ceil(rows / 32) rounded up
-    to a multiple of 992.  Returns (stream, seg_offsets, n_words_per_column, n_bits, has_exists): the first three go into
-    column_operand_table as a column matrix's do (slice i is column i, the existence bitmap column n_bits), the tuple as a
-    whole into range_column, compare_column and sum_column_where."""
+def _bsi_arguments(values, n_bits, n_words_per_column, exists):
+    """What bsi_from_values asks of its arguments; returns (n_bits, rows, n_words_per_column) as Python ints."""
     import torch
 
     if values.dtype != torch.int64 or values.dim() != 1 or not values.is_cuda:
@@ -286,6 +278,49 @@ def bsi_from_values(wah, values, n_bits, n_words_per_column=None, exists=None):
     n = int(n_words_per_column)
     if n % SEGMENT_WORDS or n <= 0 or 32 * n < rows:
         raise ValueError("columns are a multiple of 992 words long and hold every row")
+    return n_bits, rows, n
+
+
+def bsi_from_values(wah, values, n_bits, n_words_per_column=None, exists=None, check=True):
+    """The bit-sliced index of a value column (O'Neil & Quass): one bitmap per BIT of the value instead of one per distinct
+    value, what a price, a timestamp or an id needs.  values: an int64 device tensor with one value in [0, 2^n_bits) per row,
+    n_bits <= 63; exists: a bool device tensor of the same length, the rows that have a value at all (their values elsewhere
+    are stored as 0), or None.  One call (api.bsi_build_device, wah_bsi_build_device): the column is transposed on the device
+    into the decoded slice matrix [n_bits (+ 1), n_words], MOST significant slice first and the existence row last, and that is
+    compressed in one launch -- slices are mostly incompressible, which is the compressor's own road.  n_words_per_column
+    defaults to ceil(rows / 32) rounded up to a multiple of 992.  check=True: values outside [0, 2^n_bits) raise ValueError (the
+    call's status is read: no value is read back); check=False reads nothing back and returns the whole output buffer.  Returns
+    (stream, seg_offsets, n_words_per_column, n_bits, has_exists): the first three go into column_operand_table as a column
+    matrix's do (slice i is column i, the existence bitmap column n_bits), the tuple as a whole into range_column,
+    compare_column and sum_column_where."""
+    import torch
+
+    from . import api
+
+    n_bits, rows, n = _bsi_arguments(values, n_bits, n_words_per_column, exists)
+    has_exists = exists is not None
+    n_slices = n_bits + (1 if has_exists else 0)
+    values = values.contiguous()
+    if has_exists:
+        exists = exists.contiguous()
+    scratch = torch.empty(int(wah.lib().wah_bsi_build_scratch_bytes(n, n_slices)), dtype=torch.uint8, device=values.device)
+    out, count, out_offsets = wah.bsi_build_device(values, n_bits, n, exists=exists, scratch=scratch, check=False)
+    if not check:
+        return out, out_offsets, n, n_bits, has_exists
+    rc = int(wah.lib().wah_bsi_build_status(scratch.data_ptr(), n, n_slices, api._stream_ptr(torch)))
+    if rc == -6:  # WAH_ERR_STREAM: the transpose saw a value at or above 2^n_bits (a negative one is 2^63 or more)
+        raise ValueError(f"values outside [0, 2^{n_bits})")
+    api._check(rc, "bsi_from_values")
+    return out[: int(count.item())], out_offsets, n, n_bits, has_exists
+
+
+def _bsi_from_values_torch(wah, values, n_bits, n_words_per_column=None, exists=None):
+    """bsi_from_values as it was before wah_bsi_build_device, kept to be compared against (tools/bsi_build_time.py, the tests): the
+    decoded slice matrix is made with torch ops, one slice after the other, and compressed in one launch (compress_column_matrix);
+    the values' minimum and maximum are read back to the host.  Arguments and result as bsi_from_values with check=True."""
+    import torch
+
+    n_bits, rows, n = _bsi_arguments(values, n_bits, n_words_per_column, exists)
     if rows:
         lo, hi = (int(v) for v in torch.aminmax(values))
         if lo < 0 or hi >= 1 << n_bits:

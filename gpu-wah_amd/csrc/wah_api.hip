@@ -1692,6 +1692,62 @@ int wah_from_positions_status(void *d_scratch, void *stream) {
     return read_status(d_scratch, stream);
 }
 
+// A bit-sliced index from a column of values (wah_bsi_build.hip): the transpose writes the decoded slice matrix into the scratch,
+// the compress passes run over it as over any column matrix.  The scratch: [control words][slice matrix][compress workspace].
+namespace {
+struct BsiBuildLayout {
+    size_t matrix, ws_c, ws_c_bytes, total;
+};
+BsiBuildLayout bsi_build_layout(uint64_t n_words, uint64_t n_slices) {
+    BsiBuildLayout l;
+    l.matrix = round256(wah::kCtlWords * sizeof(uint32_t));
+    l.ws_c = l.matrix + round256(n_slices * n_words * sizeof(uint32_t));
+    l.ws_c_bytes = wah_compress_workspace_bytes(n_slices * n_words);
+    l.total = l.ws_c + round256(l.ws_c_bytes);
+    return l;
+}
+} // namespace
+
+size_t wah_bsi_build_scratch_bytes(uint64_t n_words, uint64_t n_slices) { return bsi_build_layout(n_words, n_slices).total; }
+
+int wah_bsi_build_device(uint64_t n_words, uint64_t n_bits, const uint64_t *d_values, uint64_t n_rows, const uint8_t *d_exists,
+                         uint32_t *d_out, uint64_t out_capacity_words, uint64_t *d_out_words, uint64_t *d_out_offsets, void *d_scratch,
+                         size_t scratch_bytes, void *stream) {
+    g_err[0] = 0;
+    if (n_bits < 1 || n_bits > 64) return refuse("between 1 and 64 bits", WAH_ERR_ARG);
+    const uint64_t n_slices = n_bits + (d_exists ? 1u : 0u);
+    if (n_words == 0 || n_words % wah::kSegWords || n_words >= (1ull << 40) || n_slices * n_words >= (1ull << 40))
+        return refuse("slices of a multiple of 992 words, all slices together fewer than 2^40 words", WAH_ERR_ARG);
+    if (n_rows > 32u * n_words) return refuse("more rows than a slice has bits", WAH_ERR_ARG);
+    if ((n_rows && !d_values) || !aligned(d_values, 7)) return refuse("null or misaligned values", WAH_ERR_ARG);
+    if (!d_out || !aligned(d_out, 3) || !d_out_words || !aligned(d_out_words, 7) || !d_out_offsets || !aligned(d_out_offsets, 7))
+        return refuse("null or misaligned output", WAH_ERR_ARG);
+    if (!scratch_ok(d_scratch)) return refuse("bad scratch pointer", WAH_ERR_ARG);
+    const BsiBuildLayout l = bsi_build_layout(n_words, n_slices);
+    if (scratch_bytes < l.total) return refuse("scratch too small", WAH_ERR_WORKSPACE);
+    char *sc = static_cast<char *>(d_scratch);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    wah::BsiBuildArgs a = {};
+    a.values = d_values;
+    a.exists = d_exists;
+    a.n_rows = n_rows;
+    a.n_words = n_words;
+    a.n_bits = (uint32_t)n_bits;
+    a.out = reinterpret_cast<uint32_t *>(sc + l.matrix);
+    a.ctrl = reinterpret_cast<uint32_t *>(sc);
+    hipError_t e = wah::launch_clear(sc, wah::kCtlWords * sizeof(uint32_t), s); // (read by wah_bsi_build_status)
+    if (e == hipSuccess) e = wah::launch_bsi_slices(a, s);
+    if (e != hipSuccess) return refuse("slice transpose launch", WAH_ERR_HIP, e);
+    return compress_device_impl(a.out, nullptr, 0, nullptr, n_slices * n_words, d_out, out_capacity_words, d_out_words, d_out_offsets,
+                                sc + l.ws_c, l.ws_c_bytes, stream, true);
+}
+
+int wah_bsi_build_status(void *d_scratch, uint64_t n_words, uint64_t n_slices, void *stream) {
+    if (!d_scratch) return WAH_ERR_ARG;
+    const int rc = read_status(d_scratch, stream); // the transpose: a value at or above 2^n_bits
+    return rc != WAH_OK ? rc : read_status(static_cast<char *>(d_scratch) + bsi_build_layout(n_words, n_slices).ws_c, stream);
+}
+
 // ---------------------------------------------------------------------------
 // host-pointer entry points (the reference's API)
 // ---------------------------------------------------------------------------

@@ -391,6 +391,19 @@ struct FromPositionsArgs {
 hipError_t launch_from_positions_check(const FromPositionsArgs &a, hipStream_t s);
 hipError_t launch_from_positions_segments(const FromPositionsArgs &a, bool emit, hipStream_t s);
 
+// wah_bsi_build_device (wah_bsi_build.hip): a column of 64-bit values in, the decoded slice matrix [n_bits (+ 1), n_words] out --
+// most significant slice first, the existence bitmap last when exists != nullptr.  Every word of the matrix is written.
+struct BsiBuildArgs {
+    const uint64_t *values; // n_rows values (may be null when n_rows == 0)
+    const uint8_t *exists;  // optional: n_rows bytes, 0 = the row has no value
+    uint64_t n_rows;        // <= 32 n_words; rows behind them hold the value 0 and do not exist
+    uint64_t n_words;       // words of one slice
+    uint32_t n_bits;        // 1 .. 64
+    uint32_t *out;
+    uint32_t *ctrl;
+};
+hipError_t launch_bsi_slices(const BsiBuildArgs &a, hipStream_t s);
+
 // wah_bitop_device: what the operands' decodes left behind, checked on the device before the combining pass
 struct PairCheck {
     const uint64_t *info_a, *info_b; // [decoded words, groups] of the two operands

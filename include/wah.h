@@ -668,6 +668,43 @@ int wah_from_positions_device(uint64_t n_words, uint64_t n_lists, const uint64_t
                               uint64_t *d_out_offsets, void *d_scratch, size_t scratch_bytes, void *stream);
 int wah_from_positions_status(void *d_scratch, void *stream);
 
+/* The way into the BIT-SLICED index: a column of values in, the index of its slices out, in one call -- what
+ * wah_bsi_range_indexed_device, wah_bsi_kth_indexed_device and wah_fetch_indexed_device read.  Not in the reference.
+ *   d_values: n_rows unsigned 64-bit values below 2^n_bits, n_bits 1 .. 64 (a negative int64 is a value of 2^63 or more).
+ *   d_exists: n_rows bytes in DEVICE memory, 0 = the row has no value (it is stored as value 0), anything else = it has one; NULL:
+ *   every row has one, and there is no existence bitmap.  n_slices = n_bits + (d_exists ? 1 : 0).
+ *   n_words: the words of ONE slice, a multiple of 992 with n_rows <= 32 * n_words; the rows behind n_rows are not loaded and count
+ *   as value 0, not existing.  n_rows == 0 with a null d_values is allowed: all-zero slices.
+ * The decoded slice matrix [n_slices, n_words] -- row i holds bit n_bits - 1 - i of every value, so row 0 is the MOST significant
+ * bit, the existence bitmap is the last row; table row p is word p / 32, bit p % 32 (LSB first) of every matrix row -- is written
+ * into the scratch and compressed there as ONE bitmap: d_out and d_out_offsets receive exactly what wah_compress_device_indexed
+ * leaves for it, the slices' compress() streams back to back (slice 0 first) and n_slices * (n_words / 992) + 1 index entries, entry
+ * i * (n_words / 992) + s the first word of segment s of slice i, the last one the total, which d_out_words receives too.  Every
+ * indexed call takes the pair unchanged: a wah_bitop_operand with d_offsets = d_out_offsets + i * (n_words / 992) is slice i.
+ * out_capacity_words = wah_max_compressed_words(n_slices * n_words) always suffices.
+ *   d_scratch: wah_bsi_build_scratch_bytes(n_words, n_slices) bytes, 256-byte aligned, no initialisation:
+ *       1024 + round256(4 * n_slices * n_words) + round256(wah_compress_workspace_bytes(n_slices * n_words))
+ *   -- the control words, the slice matrix, the compress workspace (round256: up to a multiple of 256).
+ * The values are read only by the device: the call is asynchronous on `stream`, allocates nothing and never synchronises, and a
+ * captured graph replayed after d_values and d_exists were overwritten in place builds the NEW index.  Two steps.  The transpose,
+ * in which no workgroup waits for another: a wavefront owns 2048 consecutive rows, reads each value once, 512 contiguous bytes per
+ * load, and for every slice writes 64 words made of 32 ballots with one 256-byte store; every word of the matrix is written, so it
+ * needs no clearing.  Then the one-launch compressor over the matrix (slices are mostly incompressible: 4 * n_slices * n_words
+ * bytes written once and read once: n_bits / 8 bytes per row, never more than the values themselves).
+ * Errors the host can see come back before any HIP call, argument checks first: n_bits outside 1 .. 64, n_words == 0 or not a
+ * multiple of 992, n_slices * n_words >= 2^40, n_rows > 32 * n_words, a null d_values with n_rows > 0, a misaligned d_values (8 B),
+ * a null or misaligned d_out (4 B), d_out_words, d_out_offsets (8 B) or scratch (256 B): WAH_ERR_ARG; too small a scratch:
+ * WAH_ERR_WORKSPACE.  Everything only the device sees is reported by wah_bsi_build_status(), which synchronises the stream:
+ * WAH_ERR_STREAM for a value at or above 2^n_bits -- EVERY row below n_rows is checked, whatever its existence byte says, so the
+ * verdict does not depend on which rows exist --; WAH_ERR_CAPACITY for too small an output (nothing is written at or behind
+ * d_out[out_capacity_words]).  The output of a refused call is unspecified.  wah_bsi_build_status(NULL, ...): WAH_ERR_ARG. */
+size_t wah_bsi_build_scratch_bytes(uint64_t n_words, uint64_t n_slices);
+int wah_bsi_build_device(uint64_t n_words, uint64_t n_bits, const uint64_t *d_values, uint64_t n_rows,
+                         const uint8_t *d_exists /* NULL: every row exists */, uint32_t *d_out,
+                         uint64_t out_capacity_words, uint64_t *d_out_words, uint64_t *d_out_offsets,
+                         void *d_scratch, size_t scratch_bytes, void *stream);
+int wah_bsi_build_status(void *d_scratch, uint64_t n_words, uint64_t n_slices, void *stream);
+
 /* ------------------------------------------------------------------------- *
  * Benchmark support: synthetic bitmaps generated in HBM (include/wah_gen.h
  * states the bit-exact definition; replaces tests.cpp:42-64), and a plain
