@@ -50,6 +50,11 @@ from .api import (  # noqa: F401
     bsi_bounds,
     BSI_MAX_SLICES,
     BSI_EXISTS,
+    bsi_compare_device,
+    bsi_compare_row_order,
+    BSI_EXISTS_A,
+    BSI_EXISTS_B,
+    CMP_OPS,
     bsi_kth_device,
     bsi_kth_query,
     BSI_KTH_ASCENDING,

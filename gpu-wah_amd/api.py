@@ -69,6 +69,9 @@ ABI_SYMBOLS = {
     "wah_bsi_range_scratch_bytes": (_sz, [_u64, _u64]),
     "wah_bsi_range_indexed_device": (_int, [_u64, _u64, _vp, _vp, ctypes.c_uint, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
     "wah_bsi_range_status": (_int, [_vp, _u64, _u64, _vp]),
+    "wah_bsi_compare_scratch_bytes": (_sz, [_u64, _u64, _u64]),
+    "wah_bsi_compare_indexed_device": (_int, [_int, _u64, _u64, _u64, _vp, ctypes.c_uint, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
+    "wah_bsi_compare_status": (_int, [_vp, _u64, _u64, _u64, _vp]),
     "wah_bsi_kth_scratch_bytes": (_sz, [_u64, _u64]),
     "wah_bsi_kth_indexed_device": (_int, [_u64, _u64, _u64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "wah_bsi_kth_status": (_int, [_vp, _vp]),
@@ -619,6 +622,54 @@ def bsi_range_device(table, bounds, n_words, exists=False, scratch=None, out=Non
         "wah_bsi_range_indexed_device", n, dev, lambda: lib().wah_bsi_range_scratch_bytes(n, k),
         lambda *tail: lib().wah_bsi_range_indexed_device(n, k, table.data_ptr(), bounds.data_ptr(), BSI_EXISTS if exists else 0, *tail),
         lambda sc, sp: lib().wah_bsi_range_status(sc, n, k, sp), scratch, out, out_offsets, check)
+
+
+BSI_EXISTS_A, BSI_EXISTS_B = 1, 2  # WAH_BSI_EXISTS_A, WAH_BSI_EXISTS_B
+CMP_OPS = {"<": 0, "<=": 1, ">": 2, ">=": 3, "==": 4, "!=": 5}  # WAH_CMP_*
+
+
+def bsi_compare_row_order(ka, kb, exists_a=False, exists_b=False):
+    """The table order of wah_bsi_compare_indexed_device for attributes of ka and kb slices, as a list of (attribute, slice
+    index) with attribute "a" or "b" and the slice index counted as in an attribute's own table: 0 is its MOST significant
+    slice, ka (kb) its existence bitmap.  The slices are interleaved by significance, most significant first, A's before B's
+    where both have one; then A's existence row, then B's.  Needs neither torch nor a device."""
+    ka, kb = int(ka), int(kb)
+    if not (1 <= ka <= BSI_MAX_SLICES and 1 <= kb <= BSI_MAX_SLICES):
+        raise WahError("between 1 and 64 slices per attribute")
+    order = []
+    for sig in range(max(ka, kb) - 1, -1, -1):
+        if sig < ka:
+            order.append(("a", ka - 1 - sig))
+        if sig < kb:
+            order.append(("b", kb - 1 - sig))
+    if exists_a:
+        order.append(("a", ka))
+    if exists_b:
+        order.append(("b", kb))
+    return order
+
+
+def bsi_compare_device(table, n_bits_a, n_bits_b, op, n_words, exists_a=False, exists_b=False, scratch=None, out=None, out_offsets=None,
+                       check=True):
+    """compress(A op B [AND exists]) row by row over two bit-sliced attributes in one call (wah_bsi_compare_indexed_device).
+    table: a list of (stream, seg_offsets) pairs or a ready [rows, 3] table in the order of bsi_compare_row_order(n_bits_a,
+    n_bits_b, exists_a, exists_b) -- only the device reads it.  op: a key of CMP_OPS; both values are read as unsigned.
+    Returns as bsi_range_device: (stream, seg_offsets), or with check=False, which only enqueues, (out, count tensor,
+    out_offsets)."""
+    if op not in CMP_OPS:
+        raise WahError(f"a comparison is one of {', '.join(CMP_OPS)}")
+    table = _operand_table(table, "a row table")
+    ka, kb = int(n_bits_a), int(n_bits_b)
+    flags = (BSI_EXISTS_A if exists_a else 0) | (BSI_EXISTS_B if exists_b else 0)
+    if not (1 <= ka <= BSI_MAX_SLICES and 1 <= kb <= BSI_MAX_SLICES):
+        raise WahError("between 1 and 64 slices per attribute")
+    if int(table.shape[0]) != ka + kb + bool(exists_a) + bool(exists_b):
+        raise WahError("the table has one row per slice of either attribute and one per existence bitmap")
+    n, code = int(n_words), CMP_OPS[op]
+    return _compressed_result(
+        "wah_bsi_compare_indexed_device", n, table.device, lambda: lib().wah_bsi_compare_scratch_bytes(n, ka, kb),
+        lambda *tail: lib().wah_bsi_compare_indexed_device(code, n, ka, kb, table.data_ptr(), flags, *tail),
+        lambda sc, sp: lib().wah_bsi_compare_status(sc, n, ka, kb, sp), scratch, out, out_offsets, check)
 
 
 BSI_KTH_ASCENDING, BSI_KTH_DESCENDING, BSI_KTH_QUANTILE = 0, 1, 2  # WAH_BSI_KTH_*

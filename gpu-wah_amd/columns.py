@@ -292,7 +292,7 @@ def bsi_from_values(wah, values, n_bits, n_words_per_column=None, exists=None, c
     call's status is read: no value is read back); check=False reads nothing back and returns the whole output buffer.  Returns
     (stream, seg_offsets, n_words_per_column, n_bits, has_exists): the first three go into column_operand_table as a column
     matrix's do (slice i is column i, the existence bitmap column n_bits), the tuple as a whole into range_column,
-    compare_column and sum_column_where."""
+    compare_column, compare_columns and sum_column_where."""
     import torch
 
     from . import api
@@ -381,6 +381,36 @@ def compare_column(wah, bsi, op, c, **reuse):
     else:
         raise ValueError('op: one of "<", "<=", ">", ">=", "=="')
     return range_column(wah, bsi, lo, min(hi, (1 << 64) - 1), **reuse)
+
+
+def compare_columns(wah, bsi_a, op, bsi_b, table=None, **reuse):
+    """`A op B` row by row over TWO bit-sliced attributes in one call (wah_bsi_compare_indexed_device): bsi_a and bsi_b are what
+    bsi_from_values returned for two value columns of the same column length, their widths may differ; op one of "<", "<=", ">",
+    ">=", "==", "!=", both values read as unsigned.  The result is ANDed with every existence bitmap there is; without one the
+    rows behind the caller's own hold 0 in both attributes and match "==", "<=" and ">=".  The table interleaves the two
+    attributes' slices by significance (api.bsi_compare_row_order), each attribute's rows from column_operand_table.  table: an
+    existing [rows, 3] table to overwrite in place -- what a captured graph replayed over other attributes of the same widths
+    needs; reuse: scratch / out / out_offsets / check of api.bsi_compare_device.  Returns (stream, seg_offsets) of the result
+    bitmap, usable as a predicate in filter_columns like a range_column result."""
+    import torch
+
+    if op not in wah.CMP_OPS:
+        raise ValueError('op: one of "<", "<=", ">", ">=", "==", "!="')
+    stream_a, offsets_a, n, ka, has_a = bsi_a
+    stream_b, offsets_b, n_b, kb, has_b = bsi_b
+    if n != n_b:
+        raise ValueError("the two attributes have different column lengths")
+    order = wah.bsi_compare_row_order(ka, kb, has_a, has_b)
+    dev = stream_a.device
+    if table is None:
+        table = torch.empty((len(order), 3), dtype=torch.int64, device=dev)
+    elif table.dtype != torch.int64 or tuple(table.shape) != (len(order), 3) or not table.is_contiguous() or table.device != dev:
+        raise ValueError("table: a contiguous int64 [rows, 3] tensor on the streams' device, one row per slice and existence bitmap")
+    for name, stream, offsets in (("a", stream_a, offsets_a), ("b", stream_b, offsets_b)):
+        rows = [j for j, (who, _) in enumerate(order) if who == name]
+        part = column_operand_table(stream, offsets, n, [c for who, c in order if who == name])
+        table.index_copy_(0, torch.tensor(rows, dtype=torch.int64, device=dev), part)
+    return wah.bsi_compare_device(table, ka, kb, op, n, exists_a=has_a, exists_b=has_b, **reuse)
 
 
 def sum_column_where(wah, bsi, mask_stream, mask_offsets):

@@ -1345,6 +1345,46 @@ int wah_bsi_range_status(void *d_scratch, uint64_t n_words, uint64_t n_slices, v
     return wah_bitop_indexed_status(d_scratch, n_words, stream);
 }
 
+// A op B row by row over two bit-sliced attributes (wah_bitop_list.hip, bsi_compare_segments_kernel).  Scratch and road as the
+// range call's: one decoded bitmap, then the compress passes.
+static_assert(WAH_CMP_LT == wah::kCmpLT && WAH_CMP_LE == wah::kCmpLE && WAH_CMP_GT == wah::kCmpGT && WAH_CMP_GE == wah::kCmpGE &&
+                  WAH_CMP_EQ == wah::kCmpEQ && WAH_CMP_NE == wah::kCmpNE,
+              "the operators the sweep knows");
+size_t wah_bsi_compare_scratch_bytes(uint64_t n_words, uint64_t n_slices_a, uint64_t n_slices_b) {
+    (void)n_slices_a;
+    (void)n_slices_b;
+    return bitop_indexed_layout(n_words).total;
+}
+
+int wah_bsi_compare_indexed_device(int op, uint64_t n_words, uint64_t n_slices_a, uint64_t n_slices_b, const wah_bitop_operand *d_rows,
+                                   unsigned flags, uint32_t *d_out, uint64_t out_capacity_words, uint64_t *d_out_words,
+                                   uint64_t *d_out_offsets, void *d_scratch, size_t scratch_bytes, void *stream) {
+    g_err[0] = 0;
+    if (op < WAH_CMP_LT || op > WAH_CMP_NE) return refuse("unknown comparison operator", WAH_ERR_ARG);
+    if (n_slices_a < 1 || n_slices_a > WAH_BSI_MAX_SLICES || n_slices_b < 1 || n_slices_b > WAH_BSI_MAX_SLICES ||
+        (flags & ~(WAH_BSI_EXISTS_A | WAH_BSI_EXISTS_B)))
+        return refuse("between 1 and 64 slices per attribute, no flag besides WAH_BSI_EXISTS_A and WAH_BSI_EXISTS_B", WAH_ERR_ARG);
+    if (!d_rows || !aligned(d_rows, 7) || !scratch_ok(d_scratch)) return refuse("null or misaligned row table or scratch", WAH_ERR_ARG);
+    if (!d_out_words || (n_words && !d_out) || n_words >= (1ull << 40)) return refuse("null output pointer, or 2^40 words or more", WAH_ERR_ARG);
+    const BitopIndexedLayout l = bitop_indexed_layout(n_words);
+    if (scratch_bytes < l.total) return refuse("scratch too small", WAH_ERR_WORKSPACE);
+    wah::BsiCompareArgs a = {};
+    a.table = reinterpret_cast<const wah::BitopListOperand *>(d_rows);
+    a.n_slices_a = (uint32_t)n_slices_a;
+    a.n_slices_b = (uint32_t)n_slices_b;
+    a.exists_a = (flags & WAH_BSI_EXISTS_A) ? 1u : 0u;
+    a.exists_b = (flags & WAH_BSI_EXISTS_B) ? 1u : 0u;
+    a.op = (uint32_t)op;
+    return combine_then_compress(a, wah::launch_bsi_compare_segments, "compare sweep launch", n_words, d_out, out_capacity_words, d_out_words,
+                                 d_out_offsets, static_cast<char *>(d_scratch), l, stream);
+}
+
+int wah_bsi_compare_status(void *d_scratch, uint64_t n_words, uint64_t n_slices_a, uint64_t n_slices_b, void *stream) {
+    (void)n_slices_a;
+    (void)n_slices_b;
+    return wah_bitop_indexed_status(d_scratch, n_words, stream);
+}
+
 // The value of a given rank over a bit-sliced attribute (wah_bitop_list.hip, bsi_kth_pass_kernel / bsi_kth_decide_kernel).  The
 // scratch: control block, the decision state, then one histogram per pass and copy -- nothing of it goes with n_words.  The
 // query stays in device memory: nothing here reads it.

@@ -5,6 +5,7 @@
 //                                  operations)
 //   bitop_clauses_segments_kernel  AND over clauses of (negated) ORs (wah_bitop_clauses_indexed_device)
 //   bsi_range_segments_kernel      lo <= value <= hi over a bit-sliced attribute (wah_bsi_range_indexed_device)
+//   bsi_compare_segments_kernel    A op B row by row over two bit-sliced attributes (wah_bsi_compare_indexed_device)
 //   bsi_kth_pass_kernel            one pass of the radix select over such an attribute (wah_bsi_kth_indexed_device)
 //   fetch_items_kernel             the values of listed rows, one wavefront per 64 listed rows of a segment (wah_fetch_indexed_device)
 // The walk itself is written once (list_walk); a kernel adds the state it keeps per segment, what it does when the walk crosses to
@@ -491,6 +492,113 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, kBsiWavesPerSimd) void bsi_ra
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
+// wah_bsi_compare_indexed_device: A op B row by row over TWO bit-sliced attributes of ka and kb slices -- the range kernel's
+// sweep with the constant's bit replaced by the other attribute's slice.  list_walk keeps one row at a time in the
+// accumulator, so the table is interleaved by significance, most significant first: for sig = max(ka, kb) - 1 .. 0 A's slice
+// of that significance (if sig < ka), then B's (if sig < kb); then A's existence row, then B's, where they have one.  With
+// d = |ka - kb| and kmin = min(ka, kb) that is d rows of the wider attribute alone, then kmin pairs (A, B): attribute and
+// significance of row j follow from ka, kb and the two flags by wave-uniform arithmetic, and nothing else describes the table.
+//
+// The state, group 64 s + lane: eq (rows whose more significant bits agree, preset to all ones), gt (rows where A is already
+// above B, preset to zero) and hold (A's slice of the current pair).  The fold, by row number as in the range kernel, so that a
+// slice settled in the gather (one zero fill) is folded as the zeros it is:
+//   a row of the wider attribute alone   the other attribute's bit is 0:  gt |= eq & acc (only if the row is A's);  eq &= ~acc
+//   A's slice of a pair                  hold = acc
+//   B's slice of a pair                  gt |= eq & hold & ~acc;  eq &= ~(hold ^ acc)
+//   an existence row                     ex &= acc
+// The negated operators (NE, LE, LT) set every row that gt / eq do not, so the existence rows cannot be folded into gt and eq
+// alone: a mask ex is needed.  It costs no register: behind the last slice `hold` is dead, so it is preset to all ones there and
+// becomes ex -- gt and eq are left as they are and every operator's result is ANDed with ex once, at the store (GT gt, GE
+// gt | eq, EQ eq, NE ~eq, LE ~gt, LT ~(gt | eq)).  48 registers of state, the range kernel's budget and its launch bound.
+// Nothing looks at the operator or the state before the store: every row's every segment is walked and checked.
+__global__ __launch_bounds__(kSegDecodeWaves * 64, kBsiWavesPerSimd) void bsi_compare_segments_kernel(const BsiCompareArgs a) {
+    __shared__ __attribute__((aligned(16))) u32 s_acc[kSegDecodeWaves][kSegGroups];
+    const u32 wave = wave_id(), lane = lane_id();
+    const u64 k = (u64)blockIdx.x * kSegDecodeWaves + wave;
+    if (k >= a.g.n_segments) return;
+    const u64 seg = a.g.first_segment + k;
+    const u64 g0 = seg * kSegGroups;
+    const u32 nvalid = a.g.groups - g0 < kSegGroups ? (u32)(a.g.groups - g0) : kSegGroups;
+    u32 *acc = s_acc[wave];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) reinterpret_cast<uint4 *>(acc)[64 * i + (int)lane] = make_uint4(0u, 0u, 0u, 0u);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+
+    // the table's shape (wave-uniform): `alone` rows of the wider attribute, then pairs up to n_slice_rows, then existence rows
+    const u32 ka = a.n_slices_a, kb = a.n_slices_b;
+    const bool a_wider = ka > kb;
+    const u32 alone = a_wider ? ka - kb : kb - ka;
+    const u32 n_slice_rows = ka + kb, n_rows = n_slice_rows + a.exists_a + a.exists_b;
+
+    u32 eq[kSteps], gt[kSteps], hold[kSteps]; // group 64 s + lane; hold: A's slice of the current pair, behind the slices ex
+#pragma unroll
+    for (int s = 0; s < (int)kSteps; ++s) {
+        eq[s] = kOnes31;
+        gt[s] = 0u;
+        hold[s] = 0u;
+    }
+    u32 cur = 0; // the row the accumulator holds (wave-uniform)
+    // fold the current row into the state and begin the next one
+    auto fold = [&]() {
+        if (cur < alone) { // the narrower attribute has a 0 here
+            const u32 a_mask = a_wider ? kOnes31 : 0u;
+#pragma unroll
+            for (int s = 0; s < (int)kSteps; ++s) {
+                const u32 v = acc[64 * s + (int)lane];
+                gt[s] |= eq[s] & v & a_mask;
+                eq[s] &= ~v;
+            }
+        } else if (cur < n_slice_rows) {
+            if (((cur - alone) & 1u) == 0u) { // A's slice of a pair
+#pragma unroll
+                for (int s = 0; s < (int)kSteps; ++s) hold[s] = acc[64 * s + (int)lane];
+            } else { // B's
+#pragma unroll
+                for (int s = 0; s < (int)kSteps; ++s) {
+                    const u32 b = acc[64 * s + (int)lane];
+                    gt[s] |= eq[s] & hold[s] & ~b;
+                    eq[s] &= ~(hold[s] ^ b);
+                }
+            }
+        } else { // an existence row; the first one turns hold into ex
+            const u32 keep = cur == n_slice_rows ? 0u : kOnes31;
+#pragma unroll
+            for (int s = 0; s < (int)kSteps; ++s) hold[s] = (hold[s] | ~keep) & acc[64 * s + (int)lane];
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+#pragma unroll
+        for (int i = 0; i < 4; ++i) reinterpret_cast<uint4 *>(acc)[64 * i + (int)lane] = make_uint4(0u, 0u, 0u, 0u);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        ++cur;
+    };
+
+    const ListOp m = list_op(1u); // a row is ORed into the zeroed image
+    const bool ok = list_walk(a.table, n_rows, seg, nvalid, m.fill, acc, lane, [&](u32) -> const ListOp & { return m; }, [&](u32 j) {
+#pragma nounroll
+        while (cur < j) fold(); // this row's words begin: the rows in front of it are complete
+    });
+    // behind the last row: the last one, and in front of it those that had no words to apply
+#pragma nounroll
+    while (cur < n_rows) fold();
+    if (!ok) {
+        if (lane == 0) atomicOr(a.g.ctrl + kCtlError, kErrStream);
+        return;
+    }
+    // result = ((gt & use_gt) | (eq & use_eq)) ^ flip, over the rows that exist in both
+    const u32 op = a.op;
+    const u32 use_gt = op == kCmpEQ || op == kCmpNE ? 0u : kOnes31;
+    const u32 use_eq = op == kCmpGT || op == kCmpLE ? 0u : kOnes31;
+    const u32 flip = op == kCmpNE || op == kCmpLE || op == kCmpLT ? kOnes31 : 0u;
+    const u32 no_ex = n_rows == n_slice_rows ? kOnes31 : 0u; // no existence row: hold is still a slice
+    const SegStore st = seg_store_setup(a.g.out, a.g.out_words, seg, k, lane);
+#pragma unroll
+    for (int s = 0; s < (int)kSteps; ++s) {
+        const u32 r = (((gt[s] & use_gt) | (eq[s] & use_eq)) ^ flip) & (hold[s] | no_ex) & kOnes31;
+        seg_store(st, s, (u32)(64 * s) + lane < nvalid ? r : 0u); // groups at and behind nvalid: zero
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
 // wah_bsi_kth_indexed_device: the value of a given rank (MIN, MAX, a quantile, the k-th largest) among the rows that a set of
 // filter bitmaps selects, over the same bit-sliced attribute -- a radix select over the slices, most significant first.  The
 // value is resolved in DIGITS of kBsiKthDigitBits slices: pass p counts, for every pattern of digit p, the selected rows whose
@@ -834,6 +942,7 @@ hipError_t launch_per_segment(void (*kernel)(const Args), u64 n_segments, const 
 hipError_t launch_bitop_list_segments(const BitopListArgs &a, hipStream_t s) { return launch_per_segment(bitop_list_segments_kernel, a.g.n_segments, a, s); }
 hipError_t launch_bitop_clauses_segments(const BitopClausesArgs &a, hipStream_t s) { return launch_per_segment(bitop_clauses_segments_kernel, a.g.n_segments, a, s); }
 hipError_t launch_bsi_range_segments(const BsiRangeArgs &a, hipStream_t s) { return launch_per_segment(bsi_range_segments_kernel, a.g.n_segments, a, s); }
+hipError_t launch_bsi_compare_segments(const BsiCompareArgs &a, hipStream_t s) { return launch_per_segment(bsi_compare_segments_kernel, a.g.n_segments, a, s); }
 hipError_t launch_bsi_kth_pass(const BsiKthArgs &a, hipStream_t s) { return launch_per_segment(bsi_kth_pass_kernel, a.n_segments, a, s); }
 
 hipError_t launch_fetch_check(const FetchArgs &a, hipStream_t s) {

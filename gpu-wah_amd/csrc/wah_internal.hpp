@@ -251,6 +251,19 @@ struct BsiRangeArgs {
 };
 hipError_t launch_bsi_range_segments(const BsiRangeArgs &a, hipStream_t s);
 
+// wah_bsi_compare_indexed_device (wah_bitop_list.hip): A op B row by row over two bit-sliced attributes.  table: the slices of
+// both interleaved by significance, most significant first (A's before B's where both have one), then A's existence bitmap if
+// exists_a, then B's if exists_b
+constexpr uint32_t kCmpLT = 0, kCmpLE = 1, kCmpGT = 2, kCmpGE = 3, kCmpEQ = 4, kCmpNE = 5; // WAH_CMP_*
+struct BsiCompareArgs {
+    SegmentsArgs g;
+    const BitopListOperand *table;
+    uint32_t n_slices_a, n_slices_b; // 1 .. 64 each
+    uint32_t exists_a, exists_b;     // 0 or 1: one more row each
+    uint32_t op;                     // kCmp*
+};
+hipError_t launch_bsi_compare_segments(const BsiCompareArgs &a, hipStream_t s);
+
 // wah_bsi_kth_indexed_device (wah_bitop_list.hip): the value of a given rank among the rows the filters select -- a radix select
 // over the slices, kBsiKthDigitBits of them per pass, most significant digit first.  table: n_filters filter rows, then
 // n_slices slice rows, most significant first; query: kind, a, b in DEVICE memory; result: found, value, total, less, equal.

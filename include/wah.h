@@ -470,6 +470,50 @@ int wah_bsi_range_indexed_device(uint64_t n_words, uint64_t n_slices, const wah_
                                  uint64_t *d_out_offsets, void *d_scratch, size_t scratch_bytes, void *stream);
 int wah_bsi_range_status(void *d_scratch, uint64_t n_words, uint64_t n_slices, void *stream);
 
+/* `A op B` ROW BY ROW over TWO bit-sliced attributes in ONE call -- `ship_date > commit_date`, `price < cost`, `a == b`: the
+ * range call's sweep with the constant's bit replaced by the other attribute's slice.  A has n_slices_a slices and B has
+ * n_slices_b, each 1 .. WAH_BSI_MAX_SLICES and possibly different; the narrower one counts as zero above its width.  BOTH
+ * values are read as UNSIGNED integers.
+ *   op: WAH_CMP_LT, _LE, _GT, _GE, _EQ or _NE.
+ *   d_rows: n_slices_a + n_slices_b rows, plus one for each of WAH_BSI_EXISTS_A and WAH_BSI_EXISTS_B in flags, entries as
+ *   for the list call (8-byte aligned, windows into column matrices allowed, the length may be a capacity, a row may name the
+ *   not-yet-checked output of an earlier call on the stream).  TABLE ORDER: the two attributes' slices interleaved by
+ *   significance, most significant first -- for sig = max(n_slices_a, n_slices_b) - 1 down to 0: A's slice of significance sig
+ *   if sig < n_slices_a, then B's if sig < n_slices_b; then A's existence bitmap with WAH_BSI_EXISTS_A; then B's with
+ *   WAH_BSI_EXISTS_B.  (For 3 and 2 slices: A2, A1, B1, A0, B0.)  Nothing else describes the table.
+ * The result is the bitmap of the rows where A op B holds, ANDed with every existence bitmap there is: word for word what
+ * compress() emits for that bitmap of n_words words (ragged ends included, pad bits never matter; n_words == 0: an empty
+ * stream); d_out_offsets (may be NULL) receives its segment index, so the result goes into the clause call as one more
+ * operand.  WITHOUT an existence bitmap the rows of the bitmap behind the caller's own row count (up to 32 * n_words) hold 0
+ * in BOTH attributes like any other row whose slices are all zero: they MATCH ==, <= and >=.
+ * The table is read by the device only: the call is asynchronous on `stream`, allocates nothing, never synchronises, and a
+ * captured graph replayed after the table was overwritten in place compares the NEW rows (the slice counts, the flags and
+ * the operator are host arguments and stay as captured).  One route: one wavefront per segment ORs a row into an LDS image
+ * as the list call does, folds it into the sweep's state (rows still equal, rows already greater, A's slice of the current
+ * significance), which it keeps in registers, when the walk crosses to the next row, and the compress passes run over the one
+ * decoded bitmap that leaves.
+ *   d_scratch: wah_bsi_compare_scratch_bytes(n_words, n_slices_a, n_slices_b) bytes, 256-byte aligned, no initialisation; it
+ *   EQUALS wah_bitop_indexed_scratch_bytes(n_words) for every pair of widths.
+ * Errors the host can see come back before any HIP call, the argument checks first: op outside 0 .. 5, a slice count outside
+ * 1 .. 64, unknown flag bits, a null or misaligned table (8 B) or scratch (256 B), a null d_out_words, a null d_out with
+ * n_words > 0, n_words >= 2^40: WAH_ERR_ARG; too small a scratch: WAH_ERR_WORKSPACE.  Everything only the device sees is
+ * reported by wah_bsi_compare_status(), which synchronises the stream: WAH_ERR_STREAM for everything the list call refuses
+ * in an operand, WAH_ERR_CAPACITY for too small an output.  EVERY row's every segment is checked whatever the operator and
+ * whatever the result has become, so the verdict depends neither on the data nor on the operator. */
+#define WAH_BSI_EXISTS_A 1u /* flags: A's existence bitmap is a row behind the slices */
+#define WAH_BSI_EXISTS_B 2u /* flags: B's existence bitmap is a row behind the slices (behind A's) */
+#define WAH_CMP_LT 0
+#define WAH_CMP_LE 1
+#define WAH_CMP_GT 2
+#define WAH_CMP_GE 3
+#define WAH_CMP_EQ 4
+#define WAH_CMP_NE 5
+size_t wah_bsi_compare_scratch_bytes(uint64_t n_words, uint64_t n_slices_a, uint64_t n_slices_b);
+int wah_bsi_compare_indexed_device(int op, uint64_t n_words, uint64_t n_slices_a, uint64_t n_slices_b, const wah_bitop_operand *d_rows,
+                                   unsigned flags, uint32_t *d_out, uint64_t out_capacity_words, uint64_t *d_out_words,
+                                   uint64_t *d_out_offsets, void *d_scratch, size_t scratch_bytes, void *stream);
+int wah_bsi_compare_status(void *d_scratch, uint64_t n_words, uint64_t n_slices_a, uint64_t n_slices_b, void *stream);
+
 /* The ORDER statistics of a bit-sliced attribute in ONE call -- `MIN(price) WHERE ...`, MAX, the median or any percentile, the
  * k-th largest, the threshold of `ORDER BY price DESC LIMIT k`: the value of a given rank among the rows that a set of filter
  * bitmaps selects (O'Neil & Quass; Rinfret, O'Neil & O'Neil).  It is a radix select over the slices, most significant first, all
