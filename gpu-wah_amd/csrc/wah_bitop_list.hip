@@ -8,8 +8,8 @@
 //   bsi_compare_segments_kernel    A op B row by row over two bit-sliced attributes (wah_bsi_compare_indexed_device)
 //   bsi_kth_pass_kernel            one pass of the radix select over such an attribute (wah_bsi_kth_indexed_device)
 //   fetch_items_kernel             the values of listed rows, one wavefront per 64 listed rows of a segment (wah_fetch_indexed_device)
-// The walk itself is written once (list_walk); a kernel adds the state it keeps per segment, what it does when the walk crosses to
-// another row of the table, and what it stores.
+// The walk itself is written once (list_walk), and so is the sweep that keeps one row at a time in the zeroed image (row_sweep);
+// a kernel adds the state it keeps per segment, how a row is folded into it, and what it stores or counts.
 //
 // The rows are named by a table in DEVICE memory (wah_bitop_operand, include/wah.h) that only these kernels read: the host
 // never sees it, so a captured launch replayed over a rewritten table combines the new selection.  Nothing is decided from the
@@ -263,34 +263,90 @@ __device__ __forceinline__ bool list_walk(const BitopListOperand *table, u32 n_r
     return sums_ok && __ballot(lane_bad || empty_word) == 0ull;
 }
 
-// wah_bitop_list_indexed_device.  The first operand is the same code on a preset accumulator (all ones for AND, zero otherwise;
+// the segment a wavefront owns: number k of the launch's, `seg` of the bitmap, nvalid groups (1024 but for the bitmap's last)
+struct WaveSegment {
+    u64 k, seg;
+    u32 nvalid;
+};
+// false: the launch has no segment for this wave
+__device__ __forceinline__ bool wave_segment(WaveSegment &w, u64 first_segment, u64 n_segments, u64 groups, u32 wave) {
+    w.k = (u64)blockIdx.x * kSegDecodeWaves + wave;
+    if (w.k >= n_segments) return false;
+    w.seg = first_segment + w.k;
+    const u64 g0 = w.seg * kSegGroups;
+    w.nvalid = groups - g0 < kSegGroups ? (u32)(groups - g0) : kSegGroups;
+    return true;
+}
+
+// all 1024 groups of a wave's LDS image set to v, fenced: the wave's other lanes read and write them next
+__device__ __forceinline__ void image_fill(u32 *acc, u32 v, u32 lane) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) reinterpret_cast<uint4 *>(acc)[64 * i + (int)lane] = make_uint4(v, v, v, v);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+}
+
+// The sweep of a kernel that keeps ONE row of the table at a time in the image: the walk under OR into the zeroed image `acc`,
+// and fold_row(cur), wave-uniform, once for every row cur = 0 .. n_fold - 1 in order, while the image holds exactly that row.
+// Returns the walk's verdict.
+//   * The crossing to another row is found from row NUMBERS: a row settled in the gather never reaches begin_row, so when
+//     row j's words begin every row in front of j is folded -- the settled ones as the zeros they are, out of the image that
+//     the fold before them left zeroed.
+//   * Two fences frame the zeroing: the first keeps fold_row's reads of the image, which are other lanes' groups than the
+//     lane's own 16-byte stores cover, in front of those stores; the second (image_fill's) keeps the stores in front of the
+//     next row's words.
+//   * The tail: begin_row is only ever called by a row that has words, so the last row, and the settled ones in front of it,
+//     are folded behind the walk.  n_fold is n_rows, or n_rows - 1 for a caller that wants the last row left in the image.
+template <class FoldRow>
+__device__ __forceinline__ bool row_sweep(const BitopListOperand *table, u32 n_rows, u32 n_fold, const WaveSegment &w, u32 *acc, u32 lane,
+                                          FoldRow fold_row) {
+    u32 cur = 0; // the row the image holds
+    auto fold = [&]() {
+        fold_row(cur);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        image_fill(acc, 0u, lane);
+        ++cur;
+    };
+    const ListOp m = list_op(1u);
+    const bool ok = list_walk(table, n_rows, w.seg, w.nvalid, m.fill, acc, lane, [&](u32) -> const ListOp & { return m; }, [&](u32 j) {
+#pragma nounroll
+        while (cur < j) fold();
+    });
+#pragma nounroll
+    while (cur < n_fold) fold();
+    return ok;
+}
+
+// a wave that refused something: the launch reports kErrStream (and a walk kernel's wave returns without storing)
+__device__ __forceinline__ void report_stream_error(u32 *ctrl, u32 lane) {
+    if (lane == 0) atomicOr(ctrl + kCtlError, kErrStream);
+}
+
+// the wave's result, value_of_step(s) for group 64 s + lane, as the segment's decoded words (seg_store: 31 -> 32 repack); groups at
+// and behind nvalid are written as zero
+template <class ValueOfStep>
+__device__ __forceinline__ void store_segment(const SegmentsArgs &g, const WaveSegment &w, u32 lane, ValueOfStep value_of_step) {
+    const SegStore st = seg_store_setup(g.out, g.out_words, w.seg, w.k, lane);
+#pragma unroll
+    for (int s = 0; s < (int)kSteps; ++s) seg_store(st, s, (u32)(64 * s) + lane < w.nvalid ? value_of_step(s) : 0u);
+}
+
+// wah_bitop_list_indexed_device. The first operand is the same code on a preset accumulator (all ones for AND, zero otherwise;
 // the first operand of ANDNOT applied as OR).  The accumulated segment is written as decoded words into the scratch's bitmap
 // area (seg_store: 31 -> 32 repack), and the compress passes run over that -- the road of wah_bitop_many_indexed_device, one
 // bitmap-sized intermediate.
 __global__ __launch_bounds__(kSegDecodeWaves * 64, 8) void bitop_list_segments_kernel(const BitopListArgs a) {
     __shared__ __attribute__((aligned(16))) u32 s_acc[kSegDecodeWaves][kSegGroups];
     const u32 wave = wave_id(), lane = lane_id();
-    const u64 k = (u64)blockIdx.x * kSegDecodeWaves + wave;
-    if (k >= a.g.n_segments) return;
-    const u64 seg = a.g.first_segment + k;
-    const u64 g0 = seg * kSegGroups;
-    const u32 nvalid = a.g.groups - g0 < kSegGroups ? (u32)(a.g.groups - g0) : kSegGroups;
+    WaveSegment w;
+    if (!wave_segment(w, a.g.first_segment, a.g.n_segments, a.g.groups, wave)) return;
     u32 *acc = s_acc[wave];
-    const u32 preset = a.op == 0u ? kOnes31 : 0u;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) reinterpret_cast<uint4 *>(acc)[64 * i + (int)lane] = make_uint4(preset, preset, preset, preset);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    image_fill(acc, a.op == 0u ? kOnes31 : 0u, lane);
 
     const ListOp m_first = list_op(a.op == 3u ? 1u : a.op), m_rest = list_op(a.op);
-    const bool ok = list_walk(a.table, a.n, seg, nvalid, m_rest.fill, acc, lane,
+    const bool ok = list_walk(a.table, a.n, w.seg, w.nvalid, m_rest.fill, acc, lane,
                               [&](u32 j) -> const ListOp & { return j == 0u ? m_first : m_rest; }, [](u32) {});
-    if (!ok) {
-        if (lane == 0) atomicOr(a.g.ctrl + kCtlError, kErrStream);
-        return;
-    }
-    const SegStore st = seg_store_setup(a.g.out, a.g.out_words, seg, k, lane);
-#pragma unroll
-    for (int s = 0; s < (int)kSteps; ++s) seg_store(st, s, (u32)(64 * s) + lane < nvalid ? acc[64 * s + (int)lane] : 0u); // groups at and behind nvalid: zero
+    if (!ok) return report_stream_error(a.g.ctrl, lane);
+    store_segment(a.g, w, lane, [&](int s) { return acc[64 * s + (int)lane]; });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -336,12 +392,10 @@ __device__ __forceinline__ ClauseWindow clause_window(const u64 *ends, u32 base,
 __global__ __launch_bounds__(kSegDecodeWaves * 64, 8) void bitop_clauses_segments_kernel(const BitopClausesArgs a) {
     __shared__ __attribute__((aligned(16))) u32 s_acc[kSegDecodeWaves][kSegGroups];
     const u32 wave = wave_id(), lane = lane_id();
-    const u64 k = (u64)blockIdx.x * kSegDecodeWaves + wave;
-    if (k >= a.g.n_segments) return;
-    const u64 seg = a.g.first_segment + k;
-    const u64 g0 = seg * kSegGroups;
-    const u32 nvalid = a.g.groups - g0 < kSegGroups ? (u32)(a.g.groups - g0) : kSegGroups;
+    WaveSegment w;
+    if (!wave_segment(w, a.g.first_segment, a.g.n_segments, a.g.groups, wave)) return;
     u32 *acc = s_acc[wave];
+    // (image_fill written out: this kernel fills its 64 VGPRs, and with the helper HERE it compiles to 8 bytes of scratch per lane)
 #pragma unroll
     for (int i = 0; i < 4; ++i) reinterpret_cast<uint4 *>(acc)[64 * i + (int)lane] = make_uint4(0u, 0u, 0u, 0u);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -360,9 +414,7 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, 8) void bitop_clauses_segment
 #pragma unroll
         for (int s = 0; s < (int)kSteps; ++s) res[s] &= acc[64 * s + (int)lane] ^ flip;
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-#pragma unroll
-        for (int i = 0; i < 4; ++i) reinterpret_cast<uint4 *>(acc)[64 * i + (int)lane] = make_uint4(0u, 0u, 0u, 0u);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        image_fill(acc, 0u, lane);
         ++ci;
         if (ci - cbase == 64u) {
             cbase = ci;
@@ -373,29 +425,22 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, 8) void bitop_clauses_segment
     };
 
     const ListOp m = list_op(1u); // a clause is an OR
-    const bool ok = list_walk(a.table, a.n, seg, nvalid, m.fill, acc, lane, [&](u32) -> const ListOp & { return m; }, [&](u32 j) {
+    const bool ok = list_walk(a.table, a.n, w.seg, w.nvalid, m.fill, acc, lane, [&](u32) -> const ListOp & { return m; }, [&](u32 j) {
 #pragma nounroll
         while ((cur & kClauseNever) <= j) fold(); // this operand begins another clause (or a later one)
     });
     // behind the last operand: the last clause, and in front of it those whose operands had no words to apply
 #pragma nounroll
     while ((cur & kClauseNever) <= a.n) fold();
-    if (!ok || table_bad) {
-        if (lane == 0) atomicOr(a.g.ctrl + kCtlError, kErrStream);
-        return;
-    }
-    const SegStore st = seg_store_setup(a.g.out, a.g.out_words, seg, k, lane);
-#pragma unroll
-    for (int s = 0; s < (int)kSteps; ++s) seg_store(st, s, (u32)(64 * s) + lane < nvalid ? res[s] : 0u); // groups at and behind nvalid: zero
+    if (!ok || table_bad) return report_stream_error(a.g.ctrl, lane);
+    store_segment(a.g, w, lane, [&](int s) { return res[s]; });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // wah_bsi_range_indexed_device: lo <= value <= hi over a bit-sliced attribute (O'Neil & Quass) -- one bitmap per BIT of the
-// value, most significant first, and a range predicate is one sweep over them.  The walk is the clauses kernel's with one
-// clause per table row: the LDS accumulator holds the CURRENT slice (ORed into the zeroed image exactly as a clause is), and
-// when the walk crosses to another row the slice is FOLDED into the sweep's state, which lives in registers, group
-// 64 s + lane.  The crossing is found from row numbers, so a slice whose segment was settled in the gather (one zero fill)
-// is folded like any other: a zero slice under a bound bit of 1 moves every still-equal row to "below".
+// value, most significant first, and a range predicate is one sweep over them (row_sweep): every slice in turn is FOLDED into
+// the sweep's state, which lives in registers, group 64 s + lane.  A slice whose segment was settled in the gather (one zero
+// fill) is folded like any other: a zero slice under a bound bit of 1 moves every still-equal row to "below".
 //
 // The fold is the O'Neil step for both bounds in one sweep.  With the slice's bits B and the bounds' bits l, h at this
 // significance (wave-uniform scalars):  GT |= EQlo & B if l == 0;  EQlo &= l ? B : ~B;  LT |= EQhi & ~B if h == 1;
@@ -414,15 +459,10 @@ constexpr int kBsiWavesPerSimd = 4;
 __global__ __launch_bounds__(kSegDecodeWaves * 64, kBsiWavesPerSimd) void bsi_range_segments_kernel(const BsiRangeArgs a) {
     __shared__ __attribute__((aligned(16))) u32 s_acc[kSegDecodeWaves][kSegGroups];
     const u32 wave = wave_id(), lane = lane_id();
-    const u64 k = (u64)blockIdx.x * kSegDecodeWaves + wave;
-    if (k >= a.g.n_segments) return;
-    const u64 seg = a.g.first_segment + k;
-    const u64 g0 = seg * kSegGroups;
-    const u32 nvalid = a.g.groups - g0 < kSegGroups ? (u32)(a.g.groups - g0) : kSegGroups;
+    WaveSegment w;
+    if (!wave_segment(w, a.g.first_segment, a.g.n_segments, a.g.groups, wave)) return;
     u32 *acc = s_acc[wave];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) reinterpret_cast<uint4 *>(acc)[64 * i + (int)lane] = make_uint4(0u, 0u, 0u, 0u);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    image_fill(acc, 0u, lane);
 
     // the bounds (wave-uniform, read here and nowhere on the host), clamped to the slices' width
     const u32 ns = a.n_slices, n_rows = a.n_slices + a.has_exists;
@@ -438,10 +478,8 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, kBsiWavesPerSimd) void bsi_ra
         eq_hi[s] = kOnes31;
         in[s] = 0u;
     }
-    u32 cur = 0;           // the row the accumulator holds (wave-uniform)
     bool diverged = false; // a more significant bit of the bounds differed
-    // fold the current row into the state and begin the next one
-    auto fold = [&]() {
+    const bool ok = row_sweep(a.table, n_rows, n_rows, w, acc, lane, [&](u32 cur) {
         if (cur < ns) {
             const u32 sig = ns - 1u - cur;
             const bool l = (lo >> sig) & 1ull, h = (hi >> sig) & 1ull;
@@ -464,44 +502,21 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, kBsiWavesPerSimd) void bsi_ra
                 eq_hi[s] &= b;
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-#pragma unroll
-        for (int i = 0; i < 4; ++i) reinterpret_cast<uint4 *>(acc)[64 * i + (int)lane] = make_uint4(0u, 0u, 0u, 0u);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        ++cur;
-    };
-
-    const ListOp m = list_op(1u); // a slice is ORed into the zeroed image
-    const bool ok = list_walk(a.table, n_rows, seg, nvalid, m.fill, acc, lane, [&](u32) -> const ListOp & { return m; }, [&](u32 j) {
-#pragma nounroll
-        while (cur < j) fold(); // this row's words begin: the rows in front of it are complete
     });
-    // behind the last row: the last one, and in front of it those that had no words to apply
-#pragma nounroll
-    while (cur < n_rows) fold();
-    if (!ok) {
-        if (lane == 0) atomicOr(a.g.ctrl + kCtlError, kErrStream);
-        return;
-    }
-    const SegStore st = seg_store_setup(a.g.out, a.g.out_words, seg, k, lane);
-#pragma unroll
-    for (int s = 0; s < (int)kSteps; ++s) {
-        const u32 r = none ? 0u : in[s] | eq_lo[s] | eq_hi[s];
-        seg_store(st, s, (u32)(64 * s) + lane < nvalid ? r : 0u); // groups at and behind nvalid: zero
-    }
+    if (!ok) return report_stream_error(a.g.ctrl, lane);
+    store_segment(a.g, w, lane, [&](int s) { return none ? 0u : in[s] | eq_lo[s] | eq_hi[s]; });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // wah_bsi_compare_indexed_device: A op B row by row over TWO bit-sliced attributes of ka and kb slices -- the range kernel's
-// sweep with the constant's bit replaced by the other attribute's slice.  list_walk keeps one row at a time in the
-// accumulator, so the table is interleaved by significance, most significant first: for sig = max(ka, kb) - 1 .. 0 A's slice
+// sweep with the constant's bit replaced by the other attribute's slice.  row_sweep keeps one row at a time in the
+// image, so the table is interleaved by significance, most significant first: for sig = max(ka, kb) - 1 .. 0 A's slice
 // of that significance (if sig < ka), then B's (if sig < kb); then A's existence row, then B's, where they have one.  With
 // d = |ka - kb| and kmin = min(ka, kb) that is d rows of the wider attribute alone, then kmin pairs (A, B): attribute and
 // significance of row j follow from ka, kb and the two flags by wave-uniform arithmetic, and nothing else describes the table.
 //
 // The state, group 64 s + lane: eq (rows whose more significant bits agree, preset to all ones), gt (rows where A is already
-// above B, preset to zero) and hold (A's slice of the current pair).  The fold, by row number as in the range kernel, so that a
-// slice settled in the gather (one zero fill) is folded as the zeros it is:
+// above B, preset to zero) and hold (A's slice of the current pair).  The fold:
 //   a row of the wider attribute alone   the other attribute's bit is 0:  gt |= eq & acc (only if the row is A's);  eq &= ~acc
 //   A's slice of a pair                  hold = acc
 //   B's slice of a pair                  gt |= eq & hold & ~acc;  eq &= ~(hold ^ acc)
@@ -514,15 +529,10 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, kBsiWavesPerSimd) void bsi_ra
 __global__ __launch_bounds__(kSegDecodeWaves * 64, kBsiWavesPerSimd) void bsi_compare_segments_kernel(const BsiCompareArgs a) {
     __shared__ __attribute__((aligned(16))) u32 s_acc[kSegDecodeWaves][kSegGroups];
     const u32 wave = wave_id(), lane = lane_id();
-    const u64 k = (u64)blockIdx.x * kSegDecodeWaves + wave;
-    if (k >= a.g.n_segments) return;
-    const u64 seg = a.g.first_segment + k;
-    const u64 g0 = seg * kSegGroups;
-    const u32 nvalid = a.g.groups - g0 < kSegGroups ? (u32)(a.g.groups - g0) : kSegGroups;
+    WaveSegment w;
+    if (!wave_segment(w, a.g.first_segment, a.g.n_segments, a.g.groups, wave)) return;
     u32 *acc = s_acc[wave];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) reinterpret_cast<uint4 *>(acc)[64 * i + (int)lane] = make_uint4(0u, 0u, 0u, 0u);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    image_fill(acc, 0u, lane);
 
     // the table's shape (wave-uniform): `alone` rows of the wider attribute, then pairs up to n_slice_rows, then existence rows
     const u32 ka = a.n_slices_a, kb = a.n_slices_b;
@@ -537,9 +547,7 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, kBsiWavesPerSimd) void bsi_co
         gt[s] = 0u;
         hold[s] = 0u;
     }
-    u32 cur = 0; // the row the accumulator holds (wave-uniform)
-    // fold the current row into the state and begin the next one
-    auto fold = [&]() {
+    const bool ok = row_sweep(a.table, n_rows, n_rows, w, acc, lane, [&](u32 cur) {
         if (cur < alone) { // the narrower attribute has a 0 here
             const u32 a_mask = a_wider ? kOnes31 : 0u;
 #pragma unroll
@@ -565,37 +573,15 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, kBsiWavesPerSimd) void bsi_co
 #pragma unroll
             for (int s = 0; s < (int)kSteps; ++s) hold[s] = (hold[s] | ~keep) & acc[64 * s + (int)lane];
         }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-#pragma unroll
-        for (int i = 0; i < 4; ++i) reinterpret_cast<uint4 *>(acc)[64 * i + (int)lane] = make_uint4(0u, 0u, 0u, 0u);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        ++cur;
-    };
-
-    const ListOp m = list_op(1u); // a row is ORed into the zeroed image
-    const bool ok = list_walk(a.table, n_rows, seg, nvalid, m.fill, acc, lane, [&](u32) -> const ListOp & { return m; }, [&](u32 j) {
-#pragma nounroll
-        while (cur < j) fold(); // this row's words begin: the rows in front of it are complete
     });
-    // behind the last row: the last one, and in front of it those that had no words to apply
-#pragma nounroll
-    while (cur < n_rows) fold();
-    if (!ok) {
-        if (lane == 0) atomicOr(a.g.ctrl + kCtlError, kErrStream);
-        return;
-    }
+    if (!ok) return report_stream_error(a.g.ctrl, lane);
     // result = ((gt & use_gt) | (eq & use_eq)) ^ flip, over the rows that exist in both
     const u32 op = a.op;
     const u32 use_gt = op == kCmpEQ || op == kCmpNE ? 0u : kOnes31;
     const u32 use_eq = op == kCmpGT || op == kCmpLE ? 0u : kOnes31;
     const u32 flip = op == kCmpNE || op == kCmpLE || op == kCmpLT ? kOnes31 : 0u;
     const u32 no_ex = n_rows == n_slice_rows ? kOnes31 : 0u; // no existence row: hold is still a slice
-    const SegStore st = seg_store_setup(a.g.out, a.g.out_words, seg, k, lane);
-#pragma unroll
-    for (int s = 0; s < (int)kSteps; ++s) {
-        const u32 r = (((gt[s] & use_gt) | (eq[s] & use_eq)) ^ flip) & (hold[s] | no_ex) & kOnes31;
-        seg_store(st, s, (u32)(64 * s) + lane < nvalid ? r : 0u); // groups at and behind nvalid: zero
-    }
+    store_segment(a.g, w, lane, [&](int s) { return (((gt[s] & use_gt) | (eq[s] & use_eq)) ^ flip) & (hold[s] | no_ex) & kOnes31; });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -631,19 +617,12 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, kBsiKthWavesPerSimd) void bsi
     __shared__ __attribute__((aligned(16))) u32 s_acc[kSegDecodeWaves][kSegGroups];
     __shared__ __attribute__((aligned(16))) u32 s_top[kBsiKthInLds ? kSegDecodeWaves : 1][kSegGroups]; // the slice of bucket bit 3
     const u32 wave = wave_id(), lane = lane_id();
-    const u64 k = (u64)blockIdx.x * kSegDecodeWaves + wave;
-    if (k >= a.n_segments) return;
-    const u64 seg = k;
-    const u64 g0 = seg * kSegGroups;
-    const u32 nvalid = a.groups - g0 < kSegGroups ? (u32)(a.groups - g0) : kSegGroups;
+    WaveSegment w;
+    if (!wave_segment(w, 0ull, a.n_segments, a.groups, wave)) return;
     u32 *acc = s_acc[wave];
     u32 *top = s_top[kBsiKthInLds ? wave : 0u];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        reinterpret_cast<uint4 *>(acc)[64 * i + (int)lane] = make_uint4(0u, 0u, 0u, 0u);
-        if (kBsiKthInLds) reinterpret_cast<uint4 *>(top)[64 * i + (int)lane] = make_uint4(0u, 0u, 0u, 0u); // (a short digit has no such slice)
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    image_fill(acc, 0u, lane);
+    if (kBsiKthInLds) image_fill(top, 0u, lane); // (a short digit has no such slice)
 
     // the rows of this pass (wave-uniform): the filters, then the slices up to the end of digit `pass`
     const u32 nf = a.n_filters, ns = a.n_slices;
@@ -654,17 +633,16 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, kBsiKthWavesPerSimd) void bsi
 
     u32 eq[kSteps];                           // selected rows whose bits above the digit equal the prefix: group 64 s + lane
     u32 dg[kBsiKthInRegs ? kBsiKthInRegs : 1][kSteps]; // the digit's slices in front of its last: dg[j] is bit j + 1 of the bucket number
-    const u64 last_group = a.groups - 1ull - g0; // (beyond nvalid in every segment but the bitmap's last)
+    const u64 last_group = a.groups - 1ull - w.seg * kSegGroups; // (beyond nvalid in every segment but the bitmap's last)
 #pragma unroll
     for (int s = 0; s < (int)kSteps; ++s) {
         const u32 g = (u32)(64 * s) + lane;
-        eq[s] = g >= nvalid ? 0u : (u64)g == last_group ? kOnes31 >> a.pad_bits : kOnes31;
+        eq[s] = g >= w.nvalid ? 0u : (u64)g == last_group ? kOnes31 >> a.pad_bits : kOnes31;
 #pragma unroll
         for (int j = 0; j < kBsiKthInRegs; ++j) dg[j][s] = 0u;
     }
-    u32 cur = 0; // the row the accumulator holds (wave-uniform)
-    // fold the current row into the state and begin the next one (never the pass's last row: that one is counted)
-    auto fold = [&]() {
+    // every row but the pass's last is folded: that one stays in the image and is counted
+    const bool ok = row_sweep(a.table, n_rows, n_rows - 1u, w, acc, lane, [&](u32 cur) {
         if (cur < nf + digit_first) {
             // a filter: AND; a slice above the digit: AND with B or ~B by the prefix's bit
             const u32 sig = ns - 1u - (cur - nf); // (not used for a filter)
@@ -684,25 +662,8 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, kBsiKthWavesPerSimd) void bsi
                 for (int s = 0; s < (int)kSteps; ++s) top[64 * s + (int)lane] = acc[64 * s + (int)lane];
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-#pragma unroll
-        for (int i = 0; i < 4; ++i) reinterpret_cast<uint4 *>(acc)[64 * i + (int)lane] = make_uint4(0u, 0u, 0u, 0u);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        ++cur;
-    };
-
-    const ListOp m = list_op(1u); // a row is ORed into the zeroed image
-    const bool ok = list_walk(a.table, n_rows, seg, nvalid, m.fill, acc, lane, [&](u32) -> const ListOp & { return m; }, [&](u32 j) {
-#pragma nounroll
-        while (cur < j) fold(); // this row's words begin: the rows in front of it are complete
     });
-    // behind the last row that had words: the rows in front of the pass's last one; that one stays in the image
-#pragma nounroll
-    while (cur + 1u < n_rows) fold();
-    if (!ok) {
-        if (lane == 0) atomicOr(a.ctrl + kCtlError, kErrStream);
-        return;
-    }
+    if (!ok) return report_stream_error(a.ctrl, lane);
     // bucket b: the rows of eq whose digit is b -- bit 0 the image's slice, bit j + 1 dg[j], bit 3 the second image's
     u32 count[kBsiKthBuckets];
 #pragma unroll
@@ -864,7 +825,7 @@ __global__ __launch_bounds__(256) void fetch_check_kernel(const FetchArgs a) {
         const u64 slot = first + (u64)__popcll(heads & ((1ull << lane) - 1ull));
         if (head && slot < a.capacity) a.items[slot] = i;
     }
-    if (__ballot(bad) != 0ull && lane == 0u) atomicOr(a.ctrl + kCtlError, kErrStream);
+    if (__ballot(bad) != 0ull) report_stream_error(a.ctrl, lane);
 }
 
 template <u32 kMode>
@@ -876,9 +837,7 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, 8) void fetch_items_kernel(co
     const u64 n_items = counted < a.capacity ? counted : a.capacity;
     const u64 stride = (u64)gridDim.x * kSegDecodeWaves;
     u32 *acc = s_acc[wave];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) reinterpret_cast<uint4 *>(acc)[64 * i + (int)lane] = make_uint4(0u, 0u, 0u, 0u);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    image_fill(acc, 0u, lane);
     const ListOp m = list_op(1u); // a table row is ORed into the zeroed image
 
 #pragma nounroll
@@ -902,13 +861,12 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, 8) void fetch_items_kernel(co
         u64 v = kMode == kFetchFirst ? ~0ull : 0ull;
         u32 cur = 0;       // the table row the image holds (wave-uniform)
         bool open = false; // ... if it holds one: rows settled in the gather never get there
-        // fold the image's row into the listed rows' values and zero the image for the next one
+        // fold the image's row into the listed rows' values and zero the image for the next one (not row_sweep: only the rows
+        // that had words are folded, so the crossing is begin_row itself and no row number is counted up to)
         auto fold = [&]() {
             const u32 b = (acc[g] >> bit) & 1u;
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-#pragma unroll
-            for (int k = 0; k < 4; ++k) reinterpret_cast<uint4 *>(acc)[64 * k + (int)lane] = make_uint4(0u, 0u, 0u, 0u);
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            image_fill(acc, 0u, lane);
             if (kMode == kFetchBits)
                 v |= (u64)b << ((a.n_operands - 1u - cur) & 63u); // (at most 64 table rows: 0 .. 63, never a shift by 64)
             else if (b != 0u && v == ~0ull)
@@ -920,10 +878,7 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, 8) void fetch_items_kernel(co
             open = true;
         });
         if (open) fold();
-        if (!ok) {
-            if (lane == 0) atomicOr(a.ctrl + kCtlError, kErrStream);
-            return;
-        }
+        if (!ok) return report_stream_error(a.ctrl, lane);
         if (mine) a.out[i] = v;
     }
 }
