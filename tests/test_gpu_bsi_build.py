@@ -1,7 +1,8 @@
 """GPU tests of wah_bsi_build_device (include/wah.h) and its front ends: the bit-sliced index of a value column in one call.
 Everything is exact: the words, their count and every index entry against the CPU oracle's compress() of the slice matrix that
 numpy builds FROM THE VALUES (tests/_slices.py, tests/_bsi.build_slices with zero_missing=True) and an indexed compress of it.
-tests/test_slices_reference.py proves that every case can fail.  The largest column is three segments."""
+tests/test_slices_reference.py proves that every case can fail.  The largest column is three segments.
+Sizes beyond one grid, where a wavefront takes a second block of 2048 rows: tests/test_gpu_full_grid.py."""
 import importlib
 
 import numpy as np

@@ -1,7 +1,8 @@
 """GPU tests of wah_from_positions_device (include/wah.h) and its front ends: compressed bitmaps straight from sorted lists of
 row numbers.  Everything is exact: the words, their count and every index entry against the reference of tests/_rows.py -- the
 CPU oracle's compress() of every list's decoded bitmap (the builders and their routes are proven in
-tests/test_rows_reference.py).  The largest bitmap is five segments."""
+tests/test_rows_reference.py).  The largest bitmap is five segments.
+Sizes beyond one grid, where a wavefront takes a second (list, segment) item or a check loop a second trip: tests/test_gpu_full_grid.py."""
 import importlib
 
 import numpy as np
