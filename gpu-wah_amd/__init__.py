@@ -55,6 +55,9 @@ from .api import (  # noqa: F401
     BSI_EXISTS_A,
     BSI_EXISTS_B,
     CMP_OPS,
+    bsi_arith_device,
+    bsi_arith_row_order,
+    ARITH_OPS,
     bsi_kth_device,
     bsi_kth_query,
     BSI_KTH_ASCENDING,

@@ -392,25 +392,86 @@ def compare_columns(wah, bsi_a, op, bsi_b, table=None, **reuse):
     existing [rows, 3] table to overwrite in place -- what a captured graph replayed over other attributes of the same widths
     needs; reuse: scratch / out / out_offsets / check of api.bsi_compare_device.  Returns (stream, seg_offsets) of the result
     bitmap, usable as a predicate in filter_columns like a range_column result."""
-    import torch
-
     if op not in wah.CMP_OPS:
         raise ValueError('op: one of "<", "<=", ">", ">=", "==", "!="')
-    stream_a, offsets_a, n, ka, has_a = bsi_a
-    stream_b, offsets_b, n_b, kb, has_b = bsi_b
+    _, _, n, ka, has_a = bsi_a
+    _, _, n_b, kb, has_b = bsi_b
     if n != n_b:
         raise ValueError("the two attributes have different column lengths")
-    order = wah.bsi_compare_row_order(ka, kb, has_a, has_b)
-    dev = stream_a.device
+    table = _two_attribute_table(wah.bsi_compare_row_order(ka, kb, has_a, has_b), bsi_a, bsi_b, table)
+    return wah.bsi_compare_device(table, ka, kb, op, n, exists_a=has_a, exists_b=has_b, **reuse)
+
+
+def _two_attribute_table(order, bsi_a, bsi_b, table=None):
+    """The row table of a call over TWO bit-sliced attributes of one column length: order is the call's table order, a list of
+    (attribute "a" or "b", column of that attribute) as api.bsi_compare_row_order and api.bsi_arith_row_order state it; each
+    attribute's rows come from column_operand_table.  table: an existing [rows, 3] table to overwrite in place."""
+    import torch
+
+    n, dev = bsi_a[2], bsi_a[0].device
     if table is None:
         table = torch.empty((len(order), 3), dtype=torch.int64, device=dev)
     elif table.dtype != torch.int64 or tuple(table.shape) != (len(order), 3) or not table.is_contiguous() or table.device != dev:
         raise ValueError("table: a contiguous int64 [rows, 3] tensor on the streams' device, one row per slice and existence bitmap")
-    for name, stream, offsets in (("a", stream_a, offsets_a), ("b", stream_b, offsets_b)):
+    for name, (stream, offsets, *_) in (("a", bsi_a), ("b", bsi_b)):
         rows = [j for j, (who, _) in enumerate(order) if who == name]
         part = column_operand_table(stream, offsets, n, [c for who, c in order if who == name])
         table.index_copy_(0, torch.tensor(rows, dtype=torch.int64, device=dev), part)
-    return wah.bsi_compare_device(table, ka, kb, op, n, exists_a=has_a, exists_b=has_b, **reuse)
+    return table
+
+
+def _arith_columns(wah, op, bsi_a, bsi_b, n_bits, table, reuse):
+    """add_columns / subtract_columns: one wah_bsi_arith_indexed_device call over two bsi_from_values results."""
+    import torch
+
+    from . import api
+
+    _, _, n, ka, has_a = bsi_a
+    _, _, n_b, kb, has_b = bsi_b
+    if n != n_b:
+        raise ValueError("the two attributes have different column lengths")
+    n_bits = min(max(ka, kb) + 1, 63) if n_bits is None else int(n_bits)
+    if not 1 <= n_bits <= 64:
+        raise ValueError("between 1 and 64 bits")
+    table = _two_attribute_table(wah.bsi_arith_row_order(ka, kb, has_a, has_b), bsi_a, bsi_b, table)
+    has_exists = bool(has_a or has_b)
+    flags = (wah.BSI_EXISTS_A if has_a else 0) | (wah.BSI_EXISTS_B if has_b else 0)
+    check = reuse.pop("check", True)
+    if reuse.get("scratch") is None:
+        reuse["scratch"] = torch.empty(int(wah.lib().wah_bsi_arith_scratch_bytes(n, n_bits, flags)), dtype=torch.uint8, device=table.device)
+    out, count, out_offsets = wah.bsi_arith_device(table, ka, kb, op, n_bits, n, exists_a=has_a, exists_b=has_b, check=False, **reuse)
+    if not check:
+        return out, out_offsets, n, n_bits, has_exists
+    api._check(wah.lib().wah_bsi_arith_status(reuse["scratch"].data_ptr(), n, n_bits, flags, api._stream_ptr(torch)), "bsi_arith")
+    return out[: int(count.item())], out_offsets, n, n_bits, has_exists
+
+
+def add_columns(wah, bsi_a, bsi_b, n_bits=None, table=None, **reuse):
+    """`A + B` row by row over TWO bit-sliced attributes in one call, as a NEW bit-sliced attribute (wah_bsi_arith_indexed_device):
+    bsi_a and bsi_b are what bsi_from_values -- or an earlier add_columns / subtract_columns -- returned for two value columns of
+    the same column length, their widths may differ, both values read as unsigned.  The result holds (A + B) mod 2^n_bits;
+    n_bits defaults to min(max(ka, kb) + 1, 63), which loses no carry below 63 bits (63 is the width this module handles
+    elsewhere; the call itself takes 1 .. 64).  With an existence bitmap in either attribute the result has one, the AND of those
+    present, and a row outside it is stored as 0.  The table puts the existence rows first and interleaves the slices least
+    significant first (api.bsi_arith_row_order).  table: an existing [rows, 3] table to overwrite in place -- what a captured
+    graph replayed over other attributes of the same widths needs; reuse: scratch / out / out_offsets / check of
+    api.bsi_arith_device.  Returns the five-tuple of bsi_from_values (stream, seg_offsets, n_words_per_column, n_bits,
+    has_exists), which goes into range_column, compare_columns, sum_column_where, kth_column_where, values_at_rows and another
+    add_columns as it is; check=False reads nothing back and returns the whole output buffer, as there."""
+    return _arith_columns(wah, "+", bsi_a, bsi_b, n_bits, table, reuse)
+
+
+def subtract_columns(wah, bsi_a, bsi_b, n_bits=None, table=None, **reuse):
+    """`A - B` row by row, arguments and result as add_columns.  The result holds (A - B) mod 2^n_bits, the two's-complement
+    difference: with the default n_bits = max(ka, kb) + 1 the MOST significant slice (column 0 of the result) is the borrow, set
+    exactly in the rows where A < B: the value is A - B where A >= B and 2^n_bits - (B - A) where not; a larger n_bits extends
+    the sign.  The slices are read as unsigned by every call they go into, so a predicate on the difference names
+    the sign beside it: `a - b <= c` for c >= 0 is `0 <= diff <= c AND a >= b` (a row with a < b has its top slice set and lies
+    far above c) --
+        diff = subtract_columns(wah, a, b)
+        filter_columns(wah, [(*range_column(wah, diff, 0, c), [0], False), (*compare_columns(wah, a, ">=", b), [0], False)], n)
+    -- and `a - b < 0` is compare_columns(wah, a, "<", b), or the top slice itself."""
+    return _arith_columns(wah, "-", bsi_a, bsi_b, n_bits, table, reuse)
 
 
 def sum_column_where(wah, bsi, mask_stream, mask_offsets):

@@ -6,6 +6,7 @@
 //   bitop_clauses_segments_kernel  AND over clauses of (negated) ORs (wah_bitop_clauses_indexed_device)
 //   bsi_range_segments_kernel      lo <= value <= hi over a bit-sliced attribute (wah_bsi_range_indexed_device)
 //   bsi_compare_segments_kernel    A op B row by row over two bit-sliced attributes (wah_bsi_compare_indexed_device)
+//   bsi_arith_segments_kernel      A + B, A - B row by row as a new bit-sliced attribute (wah_bsi_arith_indexed_device)
 //   bsi_kth_pass_kernel            one pass of the radix select over such an attribute (wah_bsi_kth_indexed_device)
 //   fetch_items_kernel             the values of listed rows, one wavefront per 64 listed rows of a segment (wah_fetch_indexed_device)
 // The walk itself is written once (list_walk), and so is the sweep that keeps one row at a time in the zeroed image (row_sweep);
@@ -585,6 +586,105 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, kBsiWavesPerSimd) void bsi_co
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
+// wah_bsi_arith_indexed_device: A + B or A - B row by row over two bit-sliced attributes of ka and kb slices, as a NEW bit-sliced
+// attribute of n_out slices -- a ripple carry over the slices.  The carry runs from the least significant slice up, so this
+// table is interleaved the other way round: A's existence row, then B's, where they have one (the first sum slice leaves the
+// wave before the sweep ends, and it leaves ANDed with them); then for sig = 0 .. max(ka, kb) - 1 A's slice of that significance
+// (if sig < ka), then B's (if sig < kb).  With kmin = min(ka, kb) that is kmin pairs (A, B), then |ka - kb| rows of the wider
+// attribute alone: attribute and significance of row j follow from ka, kb and the two flags by wave-uniform arithmetic.
+//
+// The state, group 64 s + lane: ex (preset to all ones), carry (preset to 0 for ADD and to all ones for SUB: A - B = A + ~B + 1)
+// and hold (A's slice of the current pair).  The fold:
+//   an existence row                     ex &= acc
+//   A's slice of a pair                  hold = acc
+//   the closing row of a significance    a, b = (hold, acc) for B's slice of a pair, (acc, 0) for A's alone, (0, acc) for B's alone;
+//                                        b ^= flip (all ones for SUB);  sum = a ^ b ^ carry;  carry = (a & b) | (carry & (a ^ b));
+//                                        sum & ex leaves as the segment's 992 decoded words of matrix row n_out - 1 - sig
+// which row is which comes down to three wave-uniform masks (what of hold and of the image is a, what of the image is b), so the
+// closing fold is one piece of code.  A closing row at or above n_out (a truncating call) is folded like any other -- the
+// verdict depends neither on the data nor on n_out -- and stored through a descriptor of no bytes: the hardware drops it.
+// Behind the sweep the slices sig = max(ka, kb) .. n_out - 1 come from the carry alone (ADD: carry & ex, then carry = 0 -- a zero
+// extension; SUB: ~carry & ex, carry unchanged -- the borrow, that is the sign, extended), then the ex row where there is one.
+// The matrix is the builder's: [n_out (+ 1), n_words], most significant slice first, n_words a multiple of 992, so every
+// segment is whole (1024 groups) and every word of the matrix is written by exactly one wave: it needs no clearing.
+// A slice settled in the gather is folded out of the zeroed image like any other row: it still advances the carry and still
+// emits its slice.  The walk's verdict is known only behind its last row: a wave that refuses something reports and stores
+// nothing more -- the slices it stored on the way are its own words of a matrix whose call is refused as a whole.
+// 48 registers of state, the compare kernel's budget and its launch bound; the sixteen stores of a closing fold need the lane
+// constants of the repack and four scalars for the descriptor on top, which still fit: no scratch (Makefile: asm).
+__global__ __launch_bounds__(kSegDecodeWaves * 64, kBsiWavesPerSimd) void bsi_arith_segments_kernel(const BsiArithArgs a) {
+    __shared__ __attribute__((aligned(16))) u32 s_acc[kSegDecodeWaves][kSegGroups];
+    const u32 wave = wave_id(), lane = lane_id();
+    WaveSegment w;
+    if (!wave_segment(w, 0ull, a.n_segments, a.groups, wave)) return;
+    u32 *acc = s_acc[wave];
+    image_fill(acc, 0u, lane);
+
+    // the table's shape (wave-uniform): the existence rows, then `pairs` rows in pairs, then rows of the wider attribute alone
+    const u32 ka = a.n_slices_a, kb = a.n_slices_b, n_out = a.n_slices_out;
+    const bool a_wider = ka > kb;
+    const u32 kmin = a_wider ? kb : ka, kmax = a_wider ? ka : kb;
+    const u32 n_ex = a.exists_a + a.exists_b, pairs = 2u * kmin, n_rows = n_ex + ka + kb;
+    const u32 flip = a.sub ? kOnes31 : 0u;
+
+    // matrix row `row` of this wave's segment; live == false: a descriptor of no bytes, every store through it is dropped
+    auto row_store = [&](u32 row, bool live) {
+        return seg_store_setup(a.matrix + (u64)row * a.n_words, live ? a.n_words : 0ull, w.seg, w.k, lane);
+    };
+
+    u32 ex[kSteps], carry[kSteps], hold[kSteps]; // group 64 s + lane; hold: A's slice of the current pair
+#pragma unroll
+    for (int s = 0; s < (int)kSteps; ++s) {
+        ex[s] = kOnes31;
+        carry[s] = flip;
+        hold[s] = 0u;
+    }
+    const bool ok = row_sweep(a.table, n_rows, n_rows, w, acc, lane, [&](u32 cur) {
+        if (cur < n_ex) {
+#pragma unroll
+            for (int s = 0; s < (int)kSteps; ++s) ex[s] &= acc[64 * s + (int)lane];
+            return;
+        }
+        const u32 r = cur - n_ex;
+        const bool paired = r < pairs;
+        if (paired && (r & 1u) == 0u) { // A's slice of a pair
+#pragma unroll
+            for (int s = 0; s < (int)kSteps; ++s) hold[s] = acc[64 * s + (int)lane];
+            return;
+        }
+        // the closing row of significance sig
+        const u32 sig = paired ? r >> 1 : r - kmin;
+        const u32 a_held = paired ? kOnes31 : 0u, a_here = !paired && a_wider ? kOnes31 : 0u, b_here = paired || !a_wider ? kOnes31 : 0u;
+        const bool live = sig < n_out;
+        const SegStore st = row_store(live ? n_out - 1u - sig : 0u, live);
+#pragma unroll
+        for (int s = 0; s < (int)kSteps; ++s) {
+            const u32 v = acc[64 * s + (int)lane];
+            const u32 x = (hold[s] & a_held) | (v & a_here), y = (v & b_here) ^ flip;
+            const u32 t = x ^ y;
+            seg_store(st, s, (t ^ carry[s]) & ex[s]);
+            carry[s] = (x & y) | (carry[s] & t);
+        }
+    });
+    if (!ok) return report_stream_error(a.ctrl, lane);
+    // the slices above both attributes, least significant first: the carry, or the borrow, and its extension
+#pragma nounroll
+    for (u32 sig = kmax; sig < n_out; ++sig) {
+        const SegStore st = row_store(n_out - 1u - sig, true);
+#pragma unroll
+        for (int s = 0; s < (int)kSteps; ++s) {
+            seg_store(st, s, (carry[s] ^ flip) & ex[s]);
+            carry[s] &= flip;
+        }
+    }
+    if (n_ex != 0u) {
+        const SegStore st = row_store(n_out, true);
+#pragma unroll
+        for (int s = 0; s < (int)kSteps; ++s) seg_store(st, s, ex[s]);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
 // wah_bsi_kth_indexed_device: the value of a given rank (MIN, MAX, a quantile, the k-th largest) among the rows that a set of
 // filter bitmaps selects, over the same bit-sliced attribute -- a radix select over the slices, most significant first.  The
 // value is resolved in DIGITS of kBsiKthDigitBits slices: pass p counts, for every pattern of digit p, the selected rows whose
@@ -898,6 +998,7 @@ hipError_t launch_bitop_list_segments(const BitopListArgs &a, hipStream_t s) { r
 hipError_t launch_bitop_clauses_segments(const BitopClausesArgs &a, hipStream_t s) { return launch_per_segment(bitop_clauses_segments_kernel, a.g.n_segments, a, s); }
 hipError_t launch_bsi_range_segments(const BsiRangeArgs &a, hipStream_t s) { return launch_per_segment(bsi_range_segments_kernel, a.g.n_segments, a, s); }
 hipError_t launch_bsi_compare_segments(const BsiCompareArgs &a, hipStream_t s) { return launch_per_segment(bsi_compare_segments_kernel, a.g.n_segments, a, s); }
+hipError_t launch_bsi_arith_segments(const BsiArithArgs &a, hipStream_t s) { return launch_per_segment(bsi_arith_segments_kernel, a.n_segments, a, s); }
 hipError_t launch_bsi_kth_pass(const BsiKthArgs &a, hipStream_t s) { return launch_per_segment(bsi_kth_pass_kernel, a.n_segments, a, s); }
 
 hipError_t launch_fetch_check(const FetchArgs &a, hipStream_t s) {

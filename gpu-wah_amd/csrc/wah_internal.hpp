@@ -264,6 +264,24 @@ struct BsiCompareArgs {
 };
 hipError_t launch_bsi_compare_segments(const BsiCompareArgs &a, hipStream_t s);
 
+// wah_bsi_arith_indexed_device (wah_bitop_list.hip): A + B or A - B row by row as a new bit-sliced attribute.  table: A's existence
+// bitmap if exists_a, then B's if exists_b, then the slices of both interleaved by significance, LEAST significant first (A's
+// before B's where both have one).  matrix: the decoded slice matrix [n_slices_out (+ 1 with an existence row), n_words] the
+// kernel writes every word of, most significant slice first, the AND of the existence bitmaps last
+constexpr uint32_t kArithAdd = 0, kArithSub = 1; // WAH_ARITH_*
+struct BsiArithArgs {
+    const BitopListOperand *table;
+    uint32_t *matrix;
+    uint32_t *ctrl;
+    uint64_t n_words;                // words of one slice, a multiple of kSegWords
+    uint64_t groups, n_segments;     // of one slice
+    uint32_t n_slices_a, n_slices_b; // 1 .. 64 each
+    uint32_t n_slices_out;           // 1 .. 64
+    uint32_t exists_a, exists_b;     // 0 or 1: one more row each
+    uint32_t sub;                    // 0: A + B, 1: A - B
+};
+hipError_t launch_bsi_arith_segments(const BsiArithArgs &a, hipStream_t s);
+
 // wah_bsi_kth_indexed_device (wah_bitop_list.hip): the value of a given rank among the rows the filters select -- a radix select
 // over the slices, kBsiKthDigitBits of them per pass, most significant digit first.  table: n_filters filter rows, then
 // n_slices slice rows, most significant first; query: kind, a, b in DEVICE memory; result: found, value, total, less, equal.

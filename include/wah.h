@@ -514,6 +514,61 @@ int wah_bsi_compare_indexed_device(int op, uint64_t n_words, uint64_t n_slices_a
                                    uint64_t *d_out_offsets, void *d_scratch, size_t scratch_bytes, void *stream);
 int wah_bsi_compare_status(void *d_scratch, uint64_t n_words, uint64_t n_slices_a, uint64_t n_slices_b, void *stream);
 
+/* `A + B` and `A - B` ROW BY ROW over TWO bit-sliced attributes in ONE call, as a NEW bit-sliced attribute -- `ship_date -
+ * order_date <= 30`, `price + tax > limit`, `MAX(end - start) WHERE ...`, `ORDER BY a + b LIMIT k`: a ripple carry over the
+ * slices, least significant first (O'Neil & Quass).  The result is an attribute like any other, so the range, compare, k-th,
+ * count and fetch calls, and a further call of this one, take it.  Not in the reference.
+ *   op: WAH_ARITH_ADD or WAH_ARITH_SUB.
+ *   A has n_slices_a slices and B has n_slices_b, each 1 .. WAH_BSI_MAX_SLICES and possibly different; BOTH are read as UNSIGNED
+ *   integers and the narrower one counts as zero above its width.
+ *   The result is (A op B) mod 2^n_slices_out, n_slices_out 1 .. 64 and the caller's choice.  max(n_slices_a, n_slices_b) + 1
+ *   never loses a carry; for SUB that top slice is the borrow, the sign of the two's-complement difference: it is set exactly
+ *   where A < B.  A smaller n_slices_out truncates; a larger one zero-extends for ADD and sign-extends for SUB.
+ *   flags: WAH_BSI_EXISTS_A | WAH_BSI_EXISTS_B.  With either one the result has an existence bitmap, the AND of those present: it
+ *   is the LAST row of the output, as in wah_bsi_build_device, and every output slice is ANDed with it -- a row that does not
+ *   exist is stored as value 0, as the builder stores it.  rows_out = n_slices_out + (flags ? 1 : 0).
+ *   d_rows: n_slices_a + n_slices_b rows, plus one for each flag, entries as for the list call (8-byte aligned, windows into
+ *   column matrices allowed, the length may be a capacity, a row may name the not-yet-checked output of an earlier call on the
+ *   stream).  TABLE ORDER: LEAST significant first, because the carry runs that way, and the existence bitmaps in FRONT, because
+ *   the first sum slice leaves before the sweep ends -- A's existence bitmap with WAH_BSI_EXISTS_A; then B's with
+ *   WAH_BSI_EXISTS_B; then for sig = 0 up to max(n_slices_a, n_slices_b) - 1: A's slice of significance sig if sig < n_slices_a,
+ *   then B's if sig < n_slices_b.  (For 3 and 2 slices with both flags: XA, XB, A0, B0, A1, B1, A2.)  Nothing else describes the
+ *   table.
+ *   n_words: the words of ONE slice, a non-zero multiple of 992 with rows_out * n_words < 2^40, as for the builder: the output
+ *   is a column matrix, whose rows start on segment boundaries.
+ * d_out, d_out_words and d_out_offsets receive exactly what wah_bsi_build_device leaves for the result's value column: the
+ * slices' compress() streams back to back, MOST significant slice first, the existence bitmap last; rows_out * (n_words / 992)
+ * + 1 index entries, entry i * (n_words / 992) + s the first word of segment s of output row i, the last one the total, which
+ * d_out_words receives too.  out_capacity_words = wah_max_compressed_words(rows_out * n_words) always suffices.  The operands may
+ * not overlap d_out or the scratch.
+ * The table is read by the device only: the call is asynchronous on `stream`, allocates nothing, never synchronises, and a
+ * captured graph replayed after the table was overwritten in place computes the NEW rows (the widths, op and the flags are host
+ * arguments and stay as captured).  One route: one wavefront per segment ORs a row into an LDS image as the list call does
+ * and, when the walk crosses to the next row, folds it into the sweep's state (the existence mask, the carry, A's slice of the
+ * current significance), which it keeps in registers; at the second slice of a significance the sum slice leaves as the
+ * segment's 992 decoded words of the result's slice matrix in the scratch -- every word of it is written once, it needs no
+ * clearing -- and the one-launch compressor runs over the matrix.  The operands' words are read once; 4 * rows_out * n_words
+ * bytes are written once and read once.
+ *   d_scratch: wah_bsi_arith_scratch_bytes(n_words, n_slices_out, flags) bytes, 256-byte aligned, no initialisation; it EQUALS
+ *   wah_bsi_build_scratch_bytes(n_words, rows_out):
+ *       1024 + round256(4 * rows_out * n_words) + round256(wah_compress_workspace_bytes(rows_out * n_words)).
+ * Errors the host can see come back before any HIP call, the argument checks first: an unknown op, a slice count (of A, of B
+ * or of the result) outside 1 .. 64, unknown flag bits, n_words == 0 or not a multiple of 992, rows_out * n_words >= 2^40, a
+ * null or misaligned table (8 B), scratch (256 B), d_out (4 B), d_out_words or d_out_offsets (8 B): WAH_ERR_ARG; too small a
+ * scratch: WAH_ERR_WORKSPACE.  Everything only the device sees is reported by wah_bsi_arith_status(), which synchronises the
+ * stream and reads the sweep's control words, then the compressor's: WAH_ERR_STREAM for everything the list call refuses in an
+ * operand, WAH_ERR_CAPACITY for too small an output (nothing is written at or behind d_out[out_capacity_words]).  EVERY row's
+ * every segment is walked and checked, the slices at or above n_slices_out that contribute nothing included, so the verdict
+ * depends neither on the data nor on n_slices_out.  The output of a refused call is unspecified.
+ * wah_bsi_arith_status(NULL, ...): WAH_ERR_ARG. */
+#define WAH_ARITH_ADD 0
+#define WAH_ARITH_SUB 1
+size_t wah_bsi_arith_scratch_bytes(uint64_t n_words, uint64_t n_slices_out, unsigned flags);
+int wah_bsi_arith_indexed_device(int op, uint64_t n_words, uint64_t n_slices_a, uint64_t n_slices_b, uint64_t n_slices_out,
+                                 const wah_bitop_operand *d_rows, unsigned flags, uint32_t *d_out, uint64_t out_capacity_words,
+                                 uint64_t *d_out_words, uint64_t *d_out_offsets, void *d_scratch, size_t scratch_bytes, void *stream);
+int wah_bsi_arith_status(void *d_scratch, uint64_t n_words, uint64_t n_slices_out, unsigned flags, void *stream);
+
 /* The ORDER statistics of a bit-sliced attribute in ONE call -- `MIN(price) WHERE ...`, MAX, the median or any percentile, the
  * k-th largest, the threshold of `ORDER BY price DESC LIMIT k`: the value of a given rank among the rows that a set of filter
  * bitmaps selects (O'Neil & Quass; Rinfret, O'Neil & O'Neil).  It is a radix select over the slices, most significant first, all
