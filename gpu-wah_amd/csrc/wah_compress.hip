@@ -14,13 +14,14 @@
 //     of mask operations per 64 groups plus one v_mbcnt rank per lane;
 //   * run-end words are compacted in LDS, turned into final words in REGISTERS (where they wait for the tile's output
 //     offset without holding LDS bandwidth) and leave the chip as dense 256-byte stores;
-//   * output offsets come from a one-hop "row scan" over 4-byte {epoch, count} granules written and read with
-//     agent-scope accesses (correct across the 8 non-coherent XCD L2s), instead of thrust::exclusive_scan + moveData
+//   * output offsets come from a one-hop "row scan" (wah_rowscan.hpp) over 4-byte {epoch, count} granules written and read
+//     with agent-scope accesses (correct across the 8 non-coherent XCD L2s), instead of thrust::exclusive_scan + moveData
 //     (compress.cu:133-166, kernels.cu:273-280); nothing is persistent and nothing is cleared between launches.
 #include <atomic>
 
 #include "wah_asm_blocks.hpp"
 #include "wah_device.hpp"
+#include "wah_rowscan.hpp"
 #include "wah_segdecode.hpp"
 
 namespace wah {
@@ -209,82 +210,33 @@ __device__ __forceinline__ void classify_pass2(const SegGroups &g, SegEnds e, u3
 //                = distance between consecutive run ends) parked in registers -> barrier -> dense 256-byte stores to
 //                their place in the output (kernels.cu:244-259 + moveData, kernels.cu:273-280).
 //   wave 0     : additionally publishes the tile's count right after the first barrier and resolves the tile's
-//                output offset with the ROW SCAN below; the sweep is in flight while all waves run pass 2.
-// Nothing is persistent: no residency census, nothing to clear between launches (launch epochs, below); the only
+//                output offset with the ROW SCAN (wah_rowscan.hpp: the protocol, its order and epochs; the granule here is
+//                u32 {epoch:16, words:16}); the sweep is in flight while all waves run pass 2.
+// Nothing is persistent: no residency census, nothing to clear between launches (launch epochs); the only
 // shared counter is the arrival ticket a workgroup draws its tile number from.  A wave that waits at the barrier
 // issues no instructions; the kernel is bound by the latency of the offset hop, not by instruction issue.
-//
-// Row scan (replaces thrust::exclusive_scan + the two blocking 8-byte reads of compress.cu:133-157).
-//   granule[t]           u32 {epoch:16, words:16} of tile t, published as soon as the tile's words are counted
-//   slot[s][0]           u64 {epoch:16, words:48}: words in front of superrow s  (superrow = kSuperRows rows)
-//   slot[s][1 + k]       u64 {epoch:16, words:48}: words of row k of superrow s  (row = kRowTiles tiles)
-// (scan area = one block per superrow: its 64 x 256 granules, then its 65 slots -- every entry has the same address and
-//  the same meaning whatever the size of the bitmap, so a workspace can serve bitmaps of different sizes in turn)
-// Tile (row r, index i) adds up, in ONE round trip of three loads per lane:
-//   granule[r][0 .. i)  +  granule[r-1][0 .. 256)  +  slot[s][1 ..] of rows s0 .. r-2  +  slot[s][0]
-// The last tile of a row publishes the row's slot as soon as its own row is complete (no dependency on anything
-// older), the last tile of a superrow publishes the next superrow's slot[.][0].  So every dependency is "published
-// by a tile with a smaller number" and at most one hop old; rows r-2 and older had >= one whole row of time.
-// Order: tile numbers are drawn in the order in which the workgroups start running (draw_tile, wah_device.hpp), so a
-// tile only ever waits for tiles that are running; every wait is bounded all the same (WAH_ERR_TIMEOUT, never a hang).
-// Epochs: the workspace is never cleared.  Every launch stamps what it publishes with the launch epoch kept in the
-// control block (read by every workgroup at its start, advanced by the LAST tile once its scan is complete -- by
-// then every other tile has published, hence started).  A zeroed workspace is epoch 0 = "nothing valid".  When
-// the 16-bit epoch is used up, the next launch has tile 0 clear the scan area while the others wait for it.
 // ===========================================================================
 constexpr u32 kTileWaves = (u32)kCompressTileWaves;
-constexpr u32 kRowTiles = 256;             // granules per row: one 16-byte load per lane
-constexpr u32 kSuperRows = 64;             // rows per superrow: one 8-byte load per lane
 constexpr u32 kGranuleCountBits = 16;             // words of a tile <= 8 * 4 * 1024 (stored minus nothing: 2^15 fits 16 bits)
 constexpr u32 kGranuleCountMask = (1u << kGranuleCountBits) - 1u;
-constexpr u32 kSlotShift = 48;             // u64 slots: value in the low 48 bits
-constexpr u64 kSlotMask = (1ull << kSlotShift) - 1ull;
 static_assert(kTileWaves * 6 * kSegGroups <= kGranuleCountMask, "tile count must fit the granule");
 static_assert(kEpochWrap < (1u << (32 - kGranuleCountBits)), "epochs must fit the granule");
-static_assert(kRowSlots == kSuperRows + 1, "slot layout");
 static_assert(kSlotShift - 32 == kGranuleCountBits, "the high half of a slot carries its epoch where a granule does");
-static_assert(kScanBlockWords >= kSuperRows * kRowTiles + 2 * kRowSlots && kScanSlotsAt == kSuperRows * kRowTiles, "scan block layout");
 
-constexpr u32 kDirectLanes = 16; // up to this many lanes with missing entries (the nearest ~64 predecessors) are simply read again
+constexpr u32 kDirectLanes = 16; // row_scan_wait: both compress scans read a sweep with few missing entries again at once
 
 struct TileScan {
     u32x4 a, b; // granules of my row (entries below me; the descriptor cuts the rest off) and of the previous row
     u64 c;      // slot of my superrow: lane 0 = words in front of it, lane 1 + k = words of its row k
 };
 
-struct ScanGeom {
-    u32 row, idx, sup, row0; // tile = row * kRowTiles + idx; superrow of the row and its first row
-    u32 n_slots;             // slots to read: [0] and the rows row0 .. row - 2
-    bool has_prev;           // the previous row belongs to the same superrow (else slot[0] covers it)
-};
-
-__device__ __forceinline__ ScanGeom scan_geom(u32 tile) {
-    ScanGeom g;
-    g.row = tile / kRowTiles;
-    g.idx = tile % kRowTiles;
-    g.sup = g.row / kSuperRows;
-    g.row0 = g.sup * kSuperRows;
-    g.has_prev = g.row > g.row0;
-    g.n_slots = g.has_prev ? g.row - g.row0 : 1u;
-    return g;
-}
-
 __device__ __forceinline__ void scan_issue(const CompressArgs &a, const ScanGeom &g, u32 lane, bool need_a, bool need_b, bool need_c,
                                            TileScan &p) {
-    u32 *const block = a.gen_desc + (u64)g.sup * kScanBlockWords; // my superrow's granules and slots
-    if (need_a) {
-        const __amdgpu_buffer_rsrc_t ra = make_rsrc(block + (g.row - g.row0) * kRowTiles, g.idx * 4u);
-        p.a = __builtin_amdgcn_raw_buffer_load_b128(ra, lane * 16u, 0, kAuxSc1);
-    }
-    if (need_b) {
-        const __amdgpu_buffer_rsrc_t rb = make_rsrc(block + (g.row - 1u - g.row0) * kRowTiles, kRowTiles * 4u);
-        p.b = __builtin_amdgcn_raw_buffer_load_b128(rb, lane * 16u, 0, kAuxSc1);
-    }
-    if (need_c) {
-        const __amdgpu_buffer_rsrc_t rc = make_rsrc(block + kScanSlotsAt, g.n_slots * 8u);
-        const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rc, lane * 8u, 0, kAuxSc1);
-        p.c = ((u64)v.y << 32) | v.x;
-    }
+    const SweepAt s = sweep_at(a.gen_desc + (u64)g.sup * kScanBlockWords, g);
+    if (need_a) p.a = __builtin_amdgcn_raw_buffer_load_b128(make_rsrc(s.block + s.row_in_super * kRowTiles, s.idx * 4u), lane * 16u, 0, kAuxSc1);
+    if (need_b)
+        p.b = __builtin_amdgcn_raw_buffer_load_b128(make_rsrc(s.block + (s.row_in_super - 1u) * kRowTiles, kRowTiles * 4u), lane * 16u, 0, kAuxSc1);
+    if (need_c) p.c = sweep_slots(s, kScanSlotsAt, lane);
 }
 
 // final words of one compacted segment (kernels.cu:244-249), from the wave's LDS buffer into 16 registers per lane:
@@ -342,114 +294,57 @@ __device__ __forceinline__ void emit_regs(const CompressArgs &a, u64 base, u32 c
     }
 }
 
+// The compress scan's policy (row_scan_wait): 4-byte granules {epoch:16, words:16}, four per lane and part
+struct TileScanPolicy {
+    using Word = u32; // (of a slot: its high half)
+    const CompressArgs &a;
+    const ScanGeom &g;
+    u32 *block;
+    u32 epoch, total;
+    TileScan &poll;
+    u32 sum_a = 0, sum_b = 0;
+    u64 sum_c = 0;
+
+    __device__ __forceinline__ u32 epoch_of(u32 w) const { return w >> kGranuleCountBits; }
+    __device__ __forceinline__ u32 missing(const u32x4 &q, u32 below, u32 lane) const {
+        const u32 k0 = 4u * lane;
+        return ((k0 < below && epoch_of(q.x) != epoch) ? 1u : 0u) | ((k0 + 1u < below && epoch_of(q.y) != epoch) ? 2u : 0u) |
+               ((k0 + 2u < below && epoch_of(q.z) != epoch) ? 4u : 0u) | ((k0 + 3u < below && epoch_of(q.w) != epoch) ? 8u : 0u);
+    }
+    // entries at and above my index lie behind the descriptor and read as zero
+    __device__ __forceinline__ static u32 words(const u32x4 &q) {
+        return uniform32(wave_sum32((q.x & kGranuleCountMask) + (q.y & kGranuleCountMask) + (q.z & kGranuleCountMask) + (q.w & kGranuleCountMask)));
+    }
+    __device__ __forceinline__ void issue(u32 lane, bool need_a, bool need_b, bool need_c) { scan_issue(a, g, lane, need_a, need_b, need_c, poll); }
+    __device__ __forceinline__ u32 missing_a(u32 lane) const { return missing(poll.a, g.idx, lane); }
+    __device__ __forceinline__ u32 missing_b(u32 lane) const { return missing(poll.b, kRowTiles, lane); }
+    __device__ __forceinline__ u32 missing_c(u32 lane) const { return slot_wanted(g, lane) && (u32)(poll.c >> kSlotShift) != epoch ? 1u : 0u; }
+    __device__ __forceinline__ void accept_a(u32 lane) {
+        sum_a = words(poll.a);
+        // my row is complete with me: its total is all that later superrow-mates need of it
+        if (g.idx == kRowTiles - 1u && lane == 0)
+            __hip_atomic_store(reinterpret_cast<u64 *>(block + kScanSlotsAt) + 1u + (g.row - g.row0), ((u64)epoch << kSlotShift) | ((u64)sum_a + total),
+                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __device__ __forceinline__ void accept_b(u32) { sum_b = words(poll.b); }
+    __device__ __forceinline__ void accept_c(u32 lane) { sum_c = uniform64(wave_sum(slot_wanted(g, lane) ? poll.c & kSlotMask : 0ull)); }
+    __device__ __forceinline__ const u32 *row_a() const { return block + (g.row - g.row0) * kRowTiles; }
+    __device__ __forceinline__ const u32 *row_b() const { return row_a() - kRowTiles; }
+    __device__ __forceinline__ const u32 *slot_word(u32 slot, u32) const { return block + kScanSlotsAt + 2u * slot + 1u; }
+};
+
 // Wave 0 of a tile, once the tile's count is out and its sweep issued (scan_issue): the tile's output offset, and what
-// the last tile of a row / of a superrow / of the launch leaves behind ("Row scan" above).  Returns the offset.
+// the last tile of a row / of a superrow / of the launch leaves behind (wah_rowscan.hpp).  Returns the offset.
 __device__ __forceinline__ u64 tile_scan_resolve(const CompressArgs &a, const ScanGeom &g, u32 *const block, const LaunchEpoch &le, u32 tile,
                                                  u32 total, u32 lane, TileScan &poll, u64 *dg_t, u32 *dg_polls) {
     const u32 epoch = le.epoch;
     (void)dg_t;
-    (void)dg_polls;
-    // ---- the tile's offset ---------------------------------------------------------------------------------------
-    // If a few entries of the sweep are still missing (the nearest predecessors), only their lanes read again.  If
-    // many are (a tile of an XCD that runs ahead of the others), the wave does NOT sweep again and again -- hundreds
-    // of waiting tiles re-reading 2.5 KB each every microsecond is traffic of the order of the bitmap's: it spins on
-    // ONE word, the missing entry with the highest tile number, the one that will be published last, and sweeps
-    // again when that one is there.
-    bool need_a = true, need_b = g.has_prev, need_c = true;
-    u32 sum_a = 0, sum_b = 0;
-    u64 sum_c = 0;
-    u32 spins = 0;
-    for (;;) {
-        u32 bad_a = 0, bad_b = 0; // per lane: which of my four entries are missing
-        bool bad_c = false;
-        u64 ba = 0, bb = 0, bc = 0;
-        if (need_a) {
-            const u32 k0 = 4u * lane;
-            bad_a = ((k0 < g.idx && (poll.a.x >> kGranuleCountBits) != epoch) ? 1u : 0u) | ((k0 + 1u < g.idx && (poll.a.y >> kGranuleCountBits) != epoch) ? 2u : 0u) |
-                    ((k0 + 2u < g.idx && (poll.a.z >> kGranuleCountBits) != epoch) ? 4u : 0u) | ((k0 + 3u < g.idx && (poll.a.w >> kGranuleCountBits) != epoch) ? 8u : 0u);
-            ba = __ballot(bad_a != 0u);
-            if (ba == 0) {
-                // entries at and above my index lie behind the descriptor and read as zero
-                sum_a = uniform32(wave_sum32((poll.a.x & kGranuleCountMask) + (poll.a.y & kGranuleCountMask) + (poll.a.z & kGranuleCountMask) + (poll.a.w & kGranuleCountMask)));
-                need_a = false;
-                // my row is complete with me: its total is all that later superrow-mates need of it
-                if (g.idx == kRowTiles - 1u && lane == 0)
-                    __hip_atomic_store(reinterpret_cast<u64 *>(block + kScanSlotsAt) + 1u + (g.row - g.row0),
-                                       ((u64)epoch << kSlotShift) | ((u64)sum_a + total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-        if (need_b) {
-            bad_b = ((poll.b.x >> kGranuleCountBits) != epoch ? 1u : 0u) | ((poll.b.y >> kGranuleCountBits) != epoch ? 2u : 0u) |
-                    ((poll.b.z >> kGranuleCountBits) != epoch ? 4u : 0u) | ((poll.b.w >> kGranuleCountBits) != epoch ? 8u : 0u);
-            bb = __ballot(bad_b != 0u);
-            if (bb == 0) {
-                sum_b = uniform32(wave_sum32((poll.b.x & kGranuleCountMask) + (poll.b.y & kGranuleCountMask) + (poll.b.z & kGranuleCountMask) + (poll.b.w & kGranuleCountMask)));
-                need_b = false;
-            }
-        }
-        if (need_c) {
-            // slot 0 of superrow 0 is never written: nothing lies in front of the first tile
-            const bool wanted = lane < g.n_slots && !(g.sup == 0u && lane == 0u);
-            bad_c = wanted && (u32)(poll.c >> kSlotShift) != epoch;
-            bc = __ballot(bad_c);
-            if (bc == 0) {
-                sum_c = uniform64(wave_sum(wanted ? poll.c & kSlotMask : 0ull));
-                need_c = false;
-            }
-        }
-        if (!(need_a || need_b || need_c)) break;
-        if (++spins > kMaxSpins) {
-            if (lane == 0) atomicOr(a.ctrl + kCtlError, kErrTimeout);
-            break;
-        }
-        const u32 n_bad = (u32)__builtin_popcountll(ba) + (u32)__builtin_popcountll(bb) + (u32)__builtin_popcountll(bc);
-        if (n_bad <= kDirectLanes) {
-            // a few stragglers among the nearest predecessors (the usual case): read again at once, without parking on one word
-            __builtin_amdgcn_s_sleep(4);
-            // (by every lane: a load under a per-lane condition into registers holding the other lanes' earlier values is a
-            // pattern one ROCm 7.2 build of the decoder's scan got wrong -- wah_decode.hip, sums_resolve)
-            scan_issue(a, g, lane, need_a, need_b, need_c, poll);
-#ifdef WAH_DIAG
-            if (dg_polls) ++*dg_polls;
-#endif
-            continue;
-        }
-        // the word to wait for: {epoch, ...} in its top bits, whichever array it belongs to
-        const u32 *target;
-        if (need_a) {
-            const u32 hl = 63u - (u32)__builtin_clzll(ba);
-            const u32 km = (u32)__builtin_amdgcn_readlane((int)bad_a, (int)hl);
-            target = block + (g.row - g.row0) * kRowTiles + 4u * hl + (31u - (u32)__builtin_clz(km));
-        } else if (need_b) {
-            const u32 hl = 63u - (u32)__builtin_clzll(bb);
-            const u32 km = (u32)__builtin_amdgcn_readlane((int)bad_b, (int)hl);
-            target = block + (g.row - 1u - g.row0) * kRowTiles + 4u * hl + (31u - (u32)__builtin_clz(km));
-        } else {
-            const u32 hl = 63u - (u32)__builtin_clzll(bc);
-            target = block + kScanSlotsAt + 2u * hl + 1u; // high half of the slot
-        }
-        bool timed_out = false;
-        for (;;) {
-            __builtin_amdgcn_s_sleep(8);
-            if ((__hip_atomic_load(target, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> kGranuleCountBits) == epoch) break;
-            if (++spins > kMaxSpins) {
-                timed_out = true;
-                break;
-            }
-        }
-        if (timed_out) {
-            if (lane == 0) atomicOr(a.ctrl + kCtlError, kErrTimeout);
-            break;
-        }
-        scan_issue(a, g, lane, need_a, need_b, need_c, poll);
-#ifdef WAH_DIAG
-        if (dg_polls) ++*dg_polls;
-#endif
-    }
+    TileScanPolicy p = {a, g, block, epoch, total, poll};
+    row_scan_wait<kDirectLanes>(p, g, a.ctrl, epoch, lane, dg_polls);
 #ifdef WAH_DIAG
     if (dg_t) dg_t[4] = __builtin_amdgcn_s_memrealtime(); // (compress_pair_body's time line; the tile body passes none)
 #endif
-    const u64 base = sum_c + sum_b + sum_a;
+    const u64 base = p.sum_c + p.sum_b + p.sum_a;
     const u64 end = base + total;
     if (lane == 0) {
         if (g.idx == kRowTiles - 1u && g.row - g.row0 == kSuperRows - 1u) // last tile of a superrow
@@ -723,36 +618,8 @@ constexpr u64 kUnsegLMask = (1ull << 17) - 1ull;    // granule: length of the ti
 constexpr u64 kSlotT = 1ull << 47;                  // slot B: the row is transparent
 constexpr u64 kSlotLMask = (1ull << 47) - 1ull;
 static_assert(kTileWaves * 3u * 2u * kSegGroups <= kUnsegLMask, "a tile's groups (three pairs per wave) must fit the granule's L");
-static_assert(kUnsegBlockWords >= kUnsegSlotsBAt + 2 * kRowSlots && kUnsegSlotsAAt == 2 * kSuperRows * kRowTiles, "unsegmented scan block layout");
 
 __device__ __forceinline__ bool is_fill_group(u32 v) { return v == 0u || v == kOnes31; }
-
-struct UnsegSweep {
-    u32x4 a[2], b[2]; // granules of my row (entries below me) and of the previous row: four per lane
-    u64 ca, cb;       // slots A (words) and B (T, L) of my superrow: lane 0 = the prefix, lane 1 + k = row k
-};
-
-__device__ __forceinline__ void unseg_issue(u32 *block, u32 row_in_super, u32 idx, u32 n_slots, u32 lane, bool need_a, bool need_b,
-                                            bool need_c, UnsegSweep &p) {
-    if (need_a) {
-        const __amdgpu_buffer_rsrc_t ra = make_rsrc(block + (u64)row_in_super * kRowTiles * 2u, idx * 8u);
-        p.a[0] = __builtin_amdgcn_raw_buffer_load_b128(ra, lane * 32u, 0, kAuxSc1);
-        p.a[1] = __builtin_amdgcn_raw_buffer_load_b128(ra, lane * 32u + 16u, 0, kAuxSc1);
-    }
-    if (need_b) {
-        const __amdgpu_buffer_rsrc_t rb = make_rsrc(block + (u64)(row_in_super - 1u) * kRowTiles * 2u, kRowTiles * 8u);
-        p.b[0] = __builtin_amdgcn_raw_buffer_load_b128(rb, lane * 32u, 0, kAuxSc1);
-        p.b[1] = __builtin_amdgcn_raw_buffer_load_b128(rb, lane * 32u + 16u, 0, kAuxSc1);
-    }
-    if (need_c) {
-        const __amdgpu_buffer_rsrc_t rca = make_rsrc(block + kUnsegSlotsAAt, n_slots * 8u);
-        const __amdgpu_buffer_rsrc_t rcb = make_rsrc(block + kUnsegSlotsBAt, n_slots * 8u);
-        const u32x2 va = __builtin_amdgcn_raw_buffer_load_b64(rca, lane * 8u, 0, kAuxSc1);
-        const u32x2 vb = __builtin_amdgcn_raw_buffer_load_b64(rcb, lane * 8u, 0, kAuxSc1);
-        p.ca = ((u64)va.y << 32) | va.x;
-        p.cb = ((u64)vb.y << 32) | vb.x;
-    }
-}
 
 // Fold of up to four (T, L) entries per lane, entry k of lane l having sequence number 4 l + k, walked from the RIGHT:
 // returns whether all of them are transparent, and the sum of L from the nearest non-transparent entry (included) on.
@@ -803,6 +670,66 @@ __device__ __forceinline__ u64 unseg_wave_carries(const u32 *s_t, const u32 *s_l
     return uniform64(__shfl(c, (int)kTileWaves));         // ("wave 8": behind the tile's last wave)
 }
 
+// The unsegmented scan's policy (row_scan_wait): 8-byte granules {epoch:16, words:16, T:1, L:17}, slots A (words) and B (T, L)
+struct UnsegScanPolicy {
+    using Word = u64;
+    const ScanGeom &g;
+    u32 *block;
+    u64 *my_row;
+    u32 epoch, total, tile_t, tile_l;
+    Sweep8<2> poll = {}; // c[0]: slots A (words), c[1]: slots B (T, L)
+    u64 words_a = 0, words_b = 0, words_c = 0, len_a = 0, len_b = 0, len_c = 0;
+    bool all_a = true, all_b = true;
+
+    __device__ __forceinline__ u64 *slots(u32 which) const { return reinterpret_cast<u64 *>(block + (which ? kUnsegSlotsBAt : kUnsegSlotsAAt)); }
+    __device__ __forceinline__ u32 epoch_of(u64 w) const { return (u32)(w >> kSlotShift); }
+    // words of a part's entries below `below` (entries behind the descriptor read as zero) and the fold of their (T, L)
+    __device__ __forceinline__ static bool fold(const u32x4 (&q)[2], u32 below, u32 lane, u64 &words, u64 &len) {
+        bool valid[4], t[4];
+        u64 l[4], sum = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const u64 gk = granule8(q, k);
+            valid[k] = 4u * lane + k < below;
+            t[k] = (gk & kUnsegT) != 0;
+            l[k] = gk & kUnsegLMask;
+            sum += (gk >> 32) & 0xFFFFull;
+        }
+        words = uniform64(wave_sum(sum));
+        return fold_right(valid, t, l, lane, len);
+    }
+    __device__ __forceinline__ void issue(u32 lane, bool need_a, bool need_b, bool need_c) {
+        sweep8_issue<kUnsegSlotsAAt, kUnsegSlotsBAt>(block, g, lane, need_a, need_b, need_c, poll);
+    }
+    __device__ __forceinline__ u32 missing_a(u32 lane) const { return sweep8_missing(poll.a, g.idx, lane, epoch); }
+    __device__ __forceinline__ u32 missing_b(u32 lane) const { return sweep8_missing(poll.b, kRowTiles, lane, epoch); }
+    __device__ __forceinline__ u32 missing_c(u32 lane) const { // bit 0: the slot of A, bit 1: of B
+        if (!slot_wanted(g, lane)) return 0u;
+        return (epoch_of(poll.c[0]) != epoch ? 1u : 0u) | (epoch_of(poll.c[1]) != epoch ? 2u : 0u);
+    }
+    __device__ __forceinline__ void accept_a(u32 lane) {
+        all_a = fold(poll.a, g.idx, lane, words_a, len_a);
+        if (g.idx == kRowTiles - 1u && lane == 0) { // my row is complete with me: its words and its (T, L)
+            __hip_atomic_store(slots(0) + 1u + (g.row - g.row0), ((u64)epoch << kSlotShift) | (words_a + total), __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+            const u64 row_tl = tile_t ? ((all_a ? kSlotT : 0ull) | (len_a + tile_l)) : (u64)tile_l;
+            __hip_atomic_store(slots(1) + 1u + (g.row - g.row0), ((u64)epoch << kSlotShift) | row_tl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    __device__ __forceinline__ void accept_b(u32 lane) { all_b = fold(poll.b, kRowTiles, lane, words_b, len_b); }
+    __device__ __forceinline__ void accept_c(u32 lane) {
+        const bool wanted = slot_wanted(g, lane);
+        words_c = uniform64(wave_sum(wanted ? poll.c[0] & kSlotMask : 0ull));
+        // walk from the right: lane 0 (the superrow prefix, an absolute length) ends it at the latest
+        const bool stop = lane < g.n_slots && (lane == 0u || !(poll.c[1] & kSlotT));
+        const u32 hl = 63u - (u32)__builtin_clzll(__ballot(stop));
+        len_c = uniform64(wave_sum(wanted && lane >= hl ? poll.c[1] & kSlotLMask : 0ull));
+    }
+    __device__ __forceinline__ const u64 *row_a() const { return my_row; }
+    __device__ __forceinline__ const u64 *row_b() const { return my_row - kRowTiles; }
+    __device__ __forceinline__ const u64 *slot_word(u32 slot, u32 missing) const { return slots(missing & 1u ? 0u : 1u) + slot; }
+};
+
 // Wave 0 of a tile of the unsegmented mode (compress_unseg_pair_body), after the tile's granule
 // {words, (T, L)} has gone out: the tile's offset and the length of the run that is open where it begins (the sweep of the
 // other tiles' granules is issued only here, late: compress_pair_body), the carries of the tile's waves (s_carry), what a
@@ -811,124 +738,14 @@ __device__ __forceinline__ void unseg_tile_resolve(const CompressArgs &a, const 
                                                    u32 total, u32 tile_t, u32 tile_l, u32 lane, const u32 *s_t, const u32 *s_l, u32 *s_carry,
                                                    u64 *s_base) {
     const u32 epoch = le.epoch;
-    UnsegSweep poll = {};
-    unseg_issue(block, g.row - g.row0, g.idx, g.n_slots, lane, true, g.has_prev, true, poll);
-    bool need_a = true, need_b = g.has_prev, need_c = true;
-    u64 words_a = 0, words_b = 0, words_c = 0, len_a = 0, len_b = 0, len_c = 0;
-    bool all_a = true, all_b = true;
-    u32 spins = 0;
-    auto granule = [](const u32x4 &q, int h) { return ((u64)(h ? q.w : q.y) << 32) | (h ? q.z : q.x); };
-    u64 *const slots_a = reinterpret_cast<u64 *>(block + kUnsegSlotsAAt);
-    u64 *const slots_b = reinterpret_cast<u64 *>(block + kUnsegSlotsBAt);
-    for (;;) {
-        u64 ba = 0, bb = 0, bc = 0;
-        u32 bad_a = 0, bad_b = 0;
-        bool bad_ca = false, bad_cb = false;
-        if (need_a) {
-            bool valid[4], t[4];
-            u64 len[4], sum = 0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const u64 gk = granule(poll.a[k >> 1], k & 1);
-                valid[k] = 4u * lane + k < g.idx;
-                if (valid[k] && (u32)(gk >> 48) != epoch) bad_a |= 1u << k;
-                t[k] = (gk & kUnsegT) != 0;
-                len[k] = gk & kUnsegLMask;
-                sum += (gk >> 32) & 0xFFFFull; // entries at and above my index lie behind the descriptor and read as zero
-            }
-            ba = __ballot(bad_a != 0u);
-            if (ba == 0) {
-                words_a = uniform64(wave_sum(sum));
-                all_a = fold_right(valid, t, len, lane, len_a);
-                need_a = false;
-                if (g.idx == kRowTiles - 1u && lane == 0) { // my row is complete with me: its words and its (T, L)
-                    __hip_atomic_store(slots_a + 1u + (g.row - g.row0), ((u64)epoch << 48) | (words_a + total), __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_AGENT);
-                    const u64 row_tl = tile_t ? ((all_a ? kSlotT : 0ull) | (len_a + tile_l)) : (u64)tile_l;
-                    __hip_atomic_store(slots_b + 1u + (g.row - g.row0), ((u64)epoch << 48) | row_tl, __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-        }
-        if (need_b) {
-            bool valid[4], t[4];
-            u64 len[4], sum = 0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const u64 gk = granule(poll.b[k >> 1], k & 1);
-                valid[k] = true;
-                if ((u32)(gk >> 48) != epoch) bad_b |= 1u << k;
-                t[k] = (gk & kUnsegT) != 0;
-                len[k] = gk & kUnsegLMask;
-                sum += (gk >> 32) & 0xFFFFull;
-            }
-            bb = __ballot(bad_b != 0u);
-            if (bb == 0) {
-                words_b = uniform64(wave_sum(sum));
-                all_b = fold_right(valid, t, len, lane, len_b);
-                need_b = false;
-            }
-        }
-        if (need_c) {
-            // slots 0 of superrow 0 are never written: nothing lies in front of the first tile
-            const bool wanted = lane < g.n_slots && !(g.sup == 0u && lane == 0u);
-            bad_ca = wanted && (u32)(poll.ca >> 48) != epoch;
-            bad_cb = wanted && (u32)(poll.cb >> 48) != epoch;
-            bc = __ballot(bad_ca || bad_cb);
-            if (bc == 0) {
-                words_c = uniform64(wave_sum(wanted ? poll.ca & ((1ull << 48) - 1ull) : 0ull));
-                // walk from the right: lane 0 (the superrow prefix, an absolute length) ends it at the latest
-                const bool stop = lane < g.n_slots && (lane == 0u || !(poll.cb & kSlotT));
-                const u32 hl = 63u - (u32)__builtin_clzll(__ballot(stop));
-                len_c = uniform64(wave_sum(wanted && lane >= hl ? poll.cb & kSlotLMask : 0ull));
-                need_c = false;
-            }
-        }
-        if (!(need_a || need_b || need_c)) break;
-        if (++spins > kMaxSpins) {
-            if (lane == 0) atomicOr(a.ctrl + kCtlError, kErrTimeout);
-            break;
-        }
-        if ((u32)__builtin_popcountll(ba) + (u32)__builtin_popcountll(bb) + (u32)__builtin_popcountll(bc) <= kDirectLanes) {
-            // a few stragglers among the nearest predecessors (the usual case): read again at once, without parking on one word
-            __builtin_amdgcn_s_sleep(4);
-            unseg_issue(block, g.row - g.row0, g.idx, g.n_slots, lane, need_a, need_b, need_c, poll);
-            continue;
-        }
-        // wait for the missing entry with the highest tile number, then read what is missing again
-        const u64 *target;
-        if (need_a) {
-            const u32 hl = 63u - (u32)__builtin_clzll(ba);
-            const u32 km = (u32)__builtin_amdgcn_readlane((int)bad_a, (int)hl);
-            target = my_row + 4u * hl + (31u - (u32)__builtin_clz(km));
-        } else if (need_b) {
-            const u32 hl = 63u - (u32)__builtin_clzll(bb);
-            const u32 km = (u32)__builtin_amdgcn_readlane((int)bad_b, (int)hl);
-            target = my_row - kRowTiles + 4u * hl + (31u - (u32)__builtin_clz(km));
-        } else {
-            const u32 hl = 63u - (u32)__builtin_clzll(bc);
-            target = (uniform32(__shfl((u32)bad_ca, (int)hl)) ? slots_a : slots_b) + hl;
-        }
-        bool timed_out = false;
-        for (;;) {
-            __builtin_amdgcn_s_sleep(8);
-            if ((u32)(__hip_atomic_load(target, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 48) == epoch) break;
-            if (++spins > kMaxSpins) {
-                timed_out = true;
-                break;
-            }
-        }
-        if (timed_out) {
-            if (lane == 0) atomicOr(a.ctrl + kCtlError, kErrTimeout);
-            break;
-        }
-        unseg_issue(block, g.row - g.row0, g.idx, g.n_slots, lane, need_a, need_b, need_c, poll);
-    }
-    const u64 base = words_c + words_b + words_a;
+    UnsegScanPolicy p = {g, block, my_row, epoch, total, tile_t, tile_l};
+    p.issue(lane, true, g.has_prev, true);
+    row_scan_wait<kDirectLanes>(p, g, a.ctrl, epoch, lane);
+    const u64 base = p.words_c + p.words_b + p.words_a;
     const u64 end = base + total;
     // the run that is open in front of this tile: through my row, the previous one, the older rows, the prefix
-    u64 carry = len_a;
-    if (all_a) carry += g.has_prev ? (all_b ? len_b + len_c : len_b) : len_c;
+    u64 carry = p.len_a;
+    if (p.all_a) carry += g.has_prev ? (p.all_b ? p.len_b + p.len_c : p.len_b) : p.len_c;
     const u64 c = unseg_wave_carries(s_t, s_l, s_carry, carry, lane);
     if (lane == 0) {
         *s_base = base;

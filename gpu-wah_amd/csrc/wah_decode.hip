@@ -1,6 +1,7 @@
 // wah_decode.hip -- decompress: decode_sums_kernel (tile bases) and decode_expand_kernel (see wah_compress.hip for the
 // conventions; the shared wavefront helpers are in wah_device.hpp)
 #include "wah_device.hpp"
+#include "wah_rowscan.hpp"
 #include "wah_segdecode.hpp"
 
 namespace wah {
@@ -14,7 +15,7 @@ namespace {
 // decompress.cu:66-115).  Here:
 //   pass 1  decode_sums_kernel   : streaming reduce.  Tiles of 4096 compressed words; per tile the number of 31-bit
 //                                   groups it expands to, turned into exclusive tile bases by the same one-hop
-//                                   row scan as compress.  Reads C once, writes 8 bytes per tile.
+//                                   row scan as compress (wah_rowscan.hpp).  Reads C once, writes 8 bytes per tile.
 //   pass 2  decode_expand_kernel : one workgroup per tile, tile words resident in LDS.  A tile OWNS the output
 //                                   segments (1024 groups -> 992 words) whose first group falls into it; each of its
 //                                   wavefronts expands whole segments: group -> source word by RANK (mbcnt over a
@@ -26,172 +27,79 @@ namespace {
 // Short-lived workgroups, one per WORKGROUP TILE of kSumWaves expand tiles (8 x 4096 words = 128 KiB of the stream),
 // workgroup tile = arrival order.  A wave sums the group counts (getCounts, kernels.cu:291-309) of one expand tile: all
 // sixteen 16-byte loads of a lane are issued before the first is used.  The workgroup tile's total is published as ONE
-// 8-byte granule {epoch:16, groups:48}; wave 0 then resolves the groups in front of the tile with the same one-hop ROW
-// SCAN as the compress kernel (wah_compress.hip), here over 8-byte granules:
-//   granule[r][0 .. i)  +  granule[r-1][0 .. 256)  +  slot[s][1 ..] of rows s0 .. r-2  +  slot[s][0]
-// (rows of 256 workgroup tiles, superrows of 64 rows; a row's last tile publishes the row's slot, a superrow's last tile
-// the next superrow's slot[0]) and writes the exclusive bases of its eight expand tiles.  Nothing is persistent: no
-// residency census; the arrival ticket is the only shared counter; launch epochs (wah_device.hpp) instead of clearing;
-// every wait is bounded.
+// 8-byte granule {epoch:16, groups:48}; wave 0 then resolves the groups in front of the tile with the one-hop ROW SCAN
+// (wah_rowscan.hpp: the protocol, rows and superrows, order, epochs, bounded waits) and writes the exclusive bases of its
+// eight expand tiles.  Nothing is persistent: no residency census; the arrival ticket is the only shared counter.
 // Totals saturate at 2^47 groups (a stream that claims more -- 500 TB of bitmap -- is reported as WAH_ERR_STREAM).
 constexpr u32 kSumWaves = (u32)kSumTilesPerGroup;
-constexpr u32 kSumRowTiles = 256;
-constexpr u32 kSumSuperRows = 64;
-constexpr u32 kSumSlotShift = 48;
-constexpr u64 kSumValueMask = (1ull << kSumSlotShift) - 1ull;
 constexpr u64 kSumSaturate = 1ull << 47;
-static_assert(kSumScanBlockWords >= 2 * kSumSuperRows * kSumRowTiles + 2 * (kSumSuperRows + 1) && kSumScanSlotsAt == 2 * kSumSuperRows * kSumRowTiles,
-              "scan block layout");
 
 __device__ __forceinline__ u64 sat_add(u64 x, u64 y) {
     const u64 s = x + y;
     return s < kSumSaturate ? s : kSumSaturate;
 }
 
-struct SumScan {
-    u32x4 a[2], b[2]; // 8-byte granules of my row (entries below me) and of the previous row: four per lane
-    u64 c;            // slot of my superrow: lane 0 = groups in front of it, lane 1 + k = groups of its row k
+// The sums scan's policy (row_scan_wait): 8-byte granules {epoch:16, groups:48}, one slot array
+struct SumScanPolicy {
+    using Word = u64;
+    const ScanGeom &g;
+    u32 *block;
+    u32 epoch;
+    u64 total;
+    Sweep8<1> poll = {};
+    u64 sum_a = 0, sum_b = 0, sum_c = 0;
+
+    __device__ __forceinline__ u64 *slots() const { return reinterpret_cast<u64 *>(block + kSumScanSlotsAt); }
+    __device__ __forceinline__ u32 epoch_of(u64 w) const { return (u32)(w >> kSlotShift); }
+    // entries at and above my index lie behind the descriptor and read as zero
+    __device__ __forceinline__ static u64 groups(const u32x4 (&q)[2]) {
+        u64 sum = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) sum += granule8(q, k) & kSlotMask;
+        return uniform64(wave_sum(sum));
+    }
+    __device__ __forceinline__ void issue(u32 lane, bool need_a, bool need_b, bool need_c) {
+        sweep8_issue<kSumScanSlotsAt>(block, g, lane, need_a, need_b, need_c, poll);
+    }
+    __device__ __forceinline__ u32 missing_a(u32 lane) const { return sweep8_missing(poll.a, g.idx, lane, epoch); }
+    __device__ __forceinline__ u32 missing_b(u32 lane) const { return sweep8_missing(poll.b, kRowTiles, lane, epoch); }
+    __device__ __forceinline__ u32 missing_c(u32 lane) const { return slot_wanted(g, lane) && epoch_of(poll.c[0]) != epoch ? 1u : 0u; }
+    __device__ __forceinline__ void accept_a(u32 lane) {
+        sum_a = groups(poll.a);
+        if (g.idx == kRowTiles - 1u && lane == 0) // my row is complete with me: publish its total
+            __hip_atomic_store(slots() + 1u + (g.row - g.row0), ((u64)epoch << kSlotShift) | sat_add(sum_a, total), __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __device__ __forceinline__ void accept_b(u32) { sum_b = groups(poll.b); }
+    __device__ __forceinline__ void accept_c(u32 lane) { sum_c = uniform64(wave_sum(slot_wanted(g, lane) ? poll.c[0] & kSlotMask : 0ull)); }
+    __device__ __forceinline__ const u64 *row_a() const { return reinterpret_cast<const u64 *>(block) + (u64)(g.row - g.row0) * kRowTiles; }
+    __device__ __forceinline__ const u64 *row_b() const { return row_a() - kRowTiles; }
+    __device__ __forceinline__ const u64 *slot_word(u32 slot, u32) const { return slots() + slot; }
 };
 
-// The descriptors are made of values that ARE the same in every lane (the tile's number and what follows from it); they
-// are passed through readfirstlane all the same: where the compiler cannot prove it (seen in decode_tile_kernel, where the
-// call sits inside `if (wave == 0)` of a large unrolled body) it wraps every load in a "waterfall" loop over the distinct
-// descriptors, and a re-read issued for SOME lanes then came back with the other lanes' earlier values zeroed (ROCm 7.2;
-// tools/dbg_decode_tile.py: the base of a first-generation tile of row 2 = the entries of lanes 30..61 only).
-__device__ __forceinline__ void sum_scan_issue(u32 *block_, u32 row_in_super_, u32 idx_, u32 n_slots_, u32 lane, bool need_a, bool need_b,
-                                               bool need_c, SumScan &p) {
-    u32 *const block = reinterpret_cast<u32 *>(uniform64(reinterpret_cast<u64>(block_)));
-    const u32 row_in_super = uniform32(row_in_super_), idx = uniform32(idx_), n_slots = uniform32(n_slots_);
-    if (need_a) {
-        const __amdgpu_buffer_rsrc_t ra = make_rsrc(block + (u64)row_in_super * kSumRowTiles * 2u, idx * 8u);
-        p.a[0] = __builtin_amdgcn_raw_buffer_load_b128(ra, lane * 32u, 0, kAuxSc1);
-        p.a[1] = __builtin_amdgcn_raw_buffer_load_b128(ra, lane * 32u + 16u, 0, kAuxSc1);
-    }
-    if (need_b) {
-        const __amdgpu_buffer_rsrc_t rb = make_rsrc(block + (u64)(row_in_super - 1u) * kSumRowTiles * 2u, kSumRowTiles * 8u);
-        p.b[0] = __builtin_amdgcn_raw_buffer_load_b128(rb, lane * 32u, 0, kAuxSc1);
-        p.b[1] = __builtin_amdgcn_raw_buffer_load_b128(rb, lane * 32u + 16u, 0, kAuxSc1);
-    }
-    if (need_c) {
-        const __amdgpu_buffer_rsrc_t rc = make_rsrc(block + kSumScanSlotsAt, n_slots * 8u);
-        const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rc, lane * 8u, 0, kAuxSc1);
-        p.c = ((u64)v.y << 32) | v.x;
-    }
-}
-
 // Wave 0 of a workgroup tile of a scan kernel (decode_sums_kernel, decode_tile_kernel), once the tile's total is known:
-// publishes it as ONE 8-byte granule {epoch:16, groups:48} and resolves the groups in front of the tile with the one-hop
-// ROW SCAN described at decode_sums_kernel; the last tile of a row publishes the row's slot, the last tile of a superrow
-// the next superrow's slot[0].  Returns the groups in front of the tile; `end` = that + total, both saturating at 2^47
-// (overflow: reported by the caller as WAH_ERR_STREAM).  kPublish = false: the caller has published the granule already
-// (sums_publish) and sweeps LATE -- the sweep of a tile that has other work to do first is the cheaper the later it goes out,
-// as in compress_pair_kernel.
+// publishes it as ONE 8-byte granule {epoch:16, groups:48} and resolves the groups in front of the tile with the row scan;
+// the last tile of a row publishes the row's slot, the last tile of a superrow the next superrow's slot[0].  Returns the
+// groups in front of the tile; `end` = that + total, both saturating at 2^47 (overflow: reported by the caller as
+// WAH_ERR_STREAM).  kPublish = false: the caller has published the granule already (sums_publish) and sweeps LATE -- the
+// sweep of a tile that has other work to do first is the cheaper the later it goes out, as in compress_pair_kernel.
 __device__ __forceinline__ void sums_publish(u32 *gen_desc, u32 wt, u32 epoch, u64 total) {
-    const u32 row = wt / kSumRowTiles, idx = wt % kSumRowTiles, sup = row / kSumSuperRows, row0 = sup * kSumSuperRows;
-    u64 *const my_row = reinterpret_cast<u64 *>(gen_desc + (u64)sup * kSumScanBlockWords) + (u64)(row - row0) * kSumRowTiles;
-    __hip_atomic_store(my_row + idx, ((u64)epoch << kSumSlotShift) | total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const ScanGeom g = scan_geom(wt);
+    u64 *const my_row = reinterpret_cast<u64 *>(gen_desc + (u64)g.sup * kSumScanBlockWords) + (u64)(g.row - g.row0) * kRowTiles;
+    __hip_atomic_store(my_row + g.idx, ((u64)epoch << kSlotShift) | total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 template <bool kPublish = true>
 __device__ __forceinline__ u64 sums_resolve(u32 *ctrl, u32 *gen_desc, u32 wt, u32 epoch, u64 total, u32 lane, u64 &end) {
-    const u32 row = wt / kSumRowTiles, idx = wt % kSumRowTiles, sup = row / kSumSuperRows, row0 = sup * kSumSuperRows;
-    const bool has_prev = row > row0;
-    const u32 n_slots = has_prev ? row - row0 : 1u;
-    u32 *const block = gen_desc + (u64)sup * kSumScanBlockWords;
-    u64 *const my_row = reinterpret_cast<u64 *>(block) + (u64)(row - row0) * kSumRowTiles;
-    u64 *const slots = reinterpret_cast<u64 *>(block + kSumScanSlotsAt);
-    if (kPublish && lane == 0) __hip_atomic_store(my_row + idx, ((u64)epoch << kSumSlotShift) | total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-
-    SumScan poll = {};
-    bool need_a = true, need_b = has_prev, need_c = true;
-    sum_scan_issue(block, row - row0, idx, n_slots, lane, need_a, need_b, need_c, poll);
-    u64 sum_a = 0, sum_b = 0, sum_c = 0;
-    u32 spins = 0;
-    auto granule = [](const u32x4 &q, int h) { return ((u64)(h ? q.w : q.y) << 32) | (h ? q.z : q.x); };
-    for (;;) {
-        u32 bad_a = 0, bad_b = 0;
-        bool bad_c = false;
-        u64 ba = 0, bb = 0, bc = 0;
-        if (need_a) {
-            u64 sum = 0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const u64 gk = granule(poll.a[k >> 1], k & 1);
-                if (4u * lane + k < idx && (u32)(gk >> kSumSlotShift) != epoch) bad_a |= 1u << k;
-                sum += gk & kSumValueMask; // entries at and above my index lie behind the descriptor and read as zero
-            }
-            ba = __ballot(bad_a != 0u);
-            if (ba == 0) {
-                sum_a = uniform64(wave_sum(sum));
-                need_a = false;
-                if (idx == kSumRowTiles - 1u && lane == 0) // my row is complete with me: publish its total
-                    __hip_atomic_store(slots + 1u + (row - row0), ((u64)epoch << kSumSlotShift) | sat_add(sum_a, total), __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-        if (need_b) {
-            u64 sum = 0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const u64 gk = granule(poll.b[k >> 1], k & 1);
-                if ((u32)(gk >> kSumSlotShift) != epoch) bad_b |= 1u << k;
-                sum += gk & kSumValueMask;
-            }
-            bb = __ballot(bad_b != 0u);
-            if (bb == 0) {
-                sum_b = uniform64(wave_sum(sum));
-                need_b = false;
-            }
-        }
-        if (need_c) {
-            // slot 0 of superrow 0 is never written: nothing lies in front of the first tile
-            const bool wanted = lane < n_slots && !(sup == 0u && lane == 0u);
-            bad_c = wanted && (u32)(poll.c >> kSumSlotShift) != epoch;
-            bc = __ballot(bad_c);
-            if (bc == 0) {
-                sum_c = uniform64(wave_sum(wanted ? poll.c & kSumValueMask : 0ull));
-                need_c = false;
-            }
-        }
-        if (!(need_a || need_b || need_c)) break;
-        if (++spins > kMaxSpins) {
-            if (lane == 0) atomicOr(ctrl + kCtlError, kErrTimeout);
-            break;
-        }
-        // wait for the missing entry with the highest tile number (published last), then read the missing lanes again
-        const u64 *target;
-        if (need_a) {
-            const u32 hl = 63u - (u32)__builtin_clzll(ba);
-            const u32 km = (u32)__builtin_amdgcn_readlane((int)bad_a, (int)hl);
-            target = my_row + 4u * hl + (31u - (u32)__builtin_clz(km));
-        } else if (need_b) {
-            const u32 hl = 63u - (u32)__builtin_clzll(bb);
-            const u32 km = (u32)__builtin_amdgcn_readlane((int)bad_b, (int)hl);
-            target = my_row - kSumRowTiles + 4u * hl + (31u - (u32)__builtin_clz(km));
-        } else {
-            target = slots + (63u - (u32)__builtin_clzll(bc));
-        }
-        bool timed_out = false;
-        for (;;) {
-            __builtin_amdgcn_s_sleep(8);
-            if ((u32)(__hip_atomic_load(target, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> kSumSlotShift) == epoch) break;
-            if (++spins > kMaxSpins) {
-                timed_out = true;
-                break;
-            }
-        }
-        if (timed_out) {
-            if (lane == 0) atomicOr(ctrl + kCtlError, kErrTimeout);
-            break;
-        }
-        // every lane reads again, not only those whose entries were missing: a re-read under a per-lane condition came back
-        // with the OTHER lanes' earlier values gone in decode_tile_kernel (ROCm 7.2; tools/dbg_decode_tile.py)
-        sum_scan_issue(block, row - row0, idx, n_slots, lane, need_a, need_b, need_c, poll);
-    }
-    const u64 base = sat_add(sat_add(sum_c, sum_b), sum_a);
+    if (kPublish && lane == 0) sums_publish(gen_desc, wt, epoch, total);
+    const ScanGeom g = scan_geom(wt);
+    SumScanPolicy p = {g, gen_desc + (u64)g.sup * kSumScanBlockWords, epoch, total};
+    p.issue(lane, true, g.has_prev, true);
+    row_scan_wait<0>(p, g, ctrl, epoch, lane);
+    const u64 base = sat_add(sat_add(p.sum_c, p.sum_b), p.sum_a);
     end = sat_add(base, total);
-    if (lane == 0 && idx == kSumRowTiles - 1u && row - row0 == kSumSuperRows - 1u) // last tile of a superrow
-        __hip_atomic_store(reinterpret_cast<u64 *>(gen_desc + (u64)(sup + 1u) * kSumScanBlockWords + kSumScanSlotsAt),
-                           ((u64)epoch << kSumSlotShift) | end, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (lane == 0 && g.idx == kRowTiles - 1u && g.row - g.row0 == kSuperRows - 1u) // last tile of a superrow
+        __hip_atomic_store(reinterpret_cast<u64 *>(gen_desc + (u64)(g.sup + 1u) * kSumScanBlockWords + kSumScanSlotsAt),
+                           ((u64)epoch << kSlotShift) | end, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return base;
 }
 

@@ -10,7 +10,7 @@
 //   barrier    : the batch's total goes out as ONE 8-byte granule (wave 0); nothing else of this batch is waited for
 //   every wave : while the other batches' totals are on their way: one START FLAG per word of the tile in LDS -- a bit mask
 //                over the tile's groups, bit p set iff a word starts at group p of the tile (LDS atomics: ds_or_b32)
-//   wave 0     : resolves the groups in front of the batch with the row scan of the sums kernel (sums_resolve, swept late)
+//   wave 0     : resolves the groups in front of the batch with the sums kernel's row scan (sums_resolve, swept late; wah_rowscan.hpp)
 //   every wave : the output segments that START inside the tile, one wavefront per segment (decompressWords + mergeWords,
 //                kernels.cu:321-385): per step of 64 groups the step's 64 start flags are two scalar registers, a group's
 //                source word is word number (starts at positions <= mine) - 1 of the tile (v_mbcnt + a running scalar
