@@ -230,6 +230,10 @@ struct TileScan {
     u64 c;      // slot of my superrow: lane 0 = words in front of it, lane 1 + k = words of its row k
 };
 
+// The sweep of the other tiles' counts.  All three bodies issue it LATE, behind pass 2, not right behind the tile's publication
+// (which would hide its round trip): that early the nearest predecessors have not published yet, the sweep has to be repeated
+// anyway, and every repetition is a round trip to lines that other XCDs are writing.  1 GiB sparse / clustered / dense, isolated
+// compress_pair_kernel, three pairs per wave: 0.2905 / 0.2098 / 0.3949 ms with the early sweep, 0.2795 / 0.1813 / 0.3845 late.
 __device__ __forceinline__ void scan_issue(const CompressArgs &a, const ScanGeom &g, u32 lane, bool need_a, bool need_b, bool need_c,
                                            TileScan &p) {
     const SweepAt s = sweep_at(a.gen_desc + (u64)g.sup * kScanBlockWords, g);
@@ -365,6 +369,33 @@ __device__ __forceinline__ u64 tile_scan_resolve(const CompressArgs &a, const Sc
     return base;
 }
 
+// ---- a tile's bookkeeping, the same in all three bodies (compress_tile_body, compress_pair_body, compress_unseg_pair_body);
+//      what they PUBLISH differs and stays with them: a 4-byte granule, an 8-byte granule with (T, L), or the no-wait table
+enum : int { kTileScan = 0, kTileCount = 1, kTilePlace = 2 }; // kMode of a body: the one launch / the halves of the no-wait route
+
+// A workgroup of the one-launch route begins: its tile (arrival ticket) and the launch epoch (wah_device.hpp: the same value
+// for every workgroup of the launch).  le.bad: the workspace is not one of ours (includes a tile number outside the grid:
+// nothing has been indexed with it) -- no words come out, and the kernel returns.
+__device__ __forceinline__ LaunchEpoch tile_begin(const CompressArgs &a, u32 *s_tile, u32 &tile) {
+    tile = draw_tile(a.ctrl, s_tile);
+    const LaunchEpoch le = launch_epoch_begin(a.ctrl, tile, a.n_tiles, a.gen_desc, a.scan_words, a.keep_error);
+    if (le.bad && blockIdx.x == 0 && threadIdx.x == 0) *a.out_words = 0;
+    return le;
+}
+// the no-wait route's count launch is a new launch: forget the previous one's status (no error is raised before its offsets kernel)
+__device__ __forceinline__ void count_launch_reset(const CompressArgs &a, u32 tile) {
+    if (tile == 0 && threadIdx.x == 0 && !a.keep_error) __hip_atomic_store(a.ctrl + kCtlError, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// wave 0, behind the barrier: the waves' counts -> s_prefix[w] = words of the waves below w; returns the tile's words
+__device__ __forceinline__ u32 fold_wave_counts(const u32 *s_count, u32 *s_prefix, u32 lane) {
+    const u32 mine = lane < kTileWaves ? s_count[lane] : 0u;
+    const u32 incl = wave_scan_incl32(mine);
+    if (lane < kTileWaves) s_prefix[lane] = incl - mine;
+    return (u32)__builtin_amdgcn_readlane((int)incl, 63);
+}
+// where the wave's first word goes, once the tile's offset is in s_base (behind the second barrier)
+__device__ __forceinline__ u64 wave_out_base(const u64 &s_base, const u32 *s_prefix, u32 wave) { return uniform64(s_base) + uniform32(s_prefix[wave]); }
+
 // Where a wave's 31-bit groups come from -- the only thing that differs between the two bit operations the tile body
 // serves: a SOURCE leaves the groups of one segment in registers (SegGroups) and keeps the next segment's loads in flight
 // meanwhile.
@@ -471,7 +502,6 @@ struct IndexedSource {
 // (wah_compress_device_ex, WAH_NO_WAIT; include/wah.h): three launches in which no workgroup ever waits for another --
 // count (pass 1 only: the tile's word count to a table), tile_offsets_kernel (exclusive scan of the table), place
 // (the whole tile again, its offset out of the table).  The bitmap is read twice; tile = blockIdx, no ticket, no epoch.
-enum : int { kTileScan = 0, kTileCount = 1, kTilePlace = 2 };
 template <class Source, u32 kWaveSegs, int kMode = kTileScan>
 __device__ __forceinline__ void compress_tile_body(const CompressArgs &a, Source &src) {
     __shared__ __attribute__((aligned(16))) u32 s_out[kTileWaves][kOutWords];
@@ -483,22 +513,11 @@ __device__ __forceinline__ void compress_tile_body(const CompressArgs &a, Source
 
     const u32 lane = lane_id();
     const u32 wave = wave_id();
-    const u32 tile = kMode == kTileScan ? draw_tile(a.ctrl, &s_tile) : blockIdx.x;
+    u32 tile = blockIdx.x;
+    const LaunchEpoch le = kMode == kTileScan ? tile_begin(a, &s_tile, tile) : LaunchEpoch{};
+    if (le.bad) return;
+    if (kMode == kTileCount) count_launch_reset(a, tile);
     const u32 seg0 = (tile * kTileWaves + wave) * kWaveSegs; // this wave's segments: seg0 .. seg0 + kWaveSegs - 1
-
-    // ---- launch epoch (wah_device.hpp): the same value for every workgroup of the launch --------------------------------
-    LaunchEpoch le = {};
-    if (kMode == kTileScan) {
-        le = launch_epoch_begin(a.ctrl, tile, a.n_tiles, a.gen_desc, a.scan_words, a.keep_error);
-        if (le.bad) {
-            if (blockIdx.x == 0 && threadIdx.x == 0) *a.out_words = 0;
-            return;
-        }
-    } else if (kMode == kTileCount && tile == 0 && threadIdx.x == 0 && !a.keep_error) {
-        // a new launch: forget the previous one's status (nothing of this route raises an error before tile_offsets_kernel)
-        __hip_atomic_store(a.ctrl + kCtlError, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    const u32 epoch = le.epoch;
 
     // ---- this wave's segments, one after the other through the wave's LDS buffer; the final words of each are parked
     //      in 16 registers per lane, so nothing of a tile that waits for its offset occupies LDS bandwidth or needs a
@@ -538,17 +557,14 @@ __device__ __forceinline__ void compress_tile_body(const CompressArgs &a, Source
     TileScan poll = {};
     u32 total = 0;
     if (wave == 0) {
-        const u32 mine = lane < kTileWaves ? s_count[lane] : 0u;
-        const u32 incl = wave_scan_incl32(mine);
-        if (lane < kTileWaves) s_prefix[lane] = incl - mine;
-        total = (u32)__builtin_amdgcn_readlane((int)incl, 63);
+        total = fold_wave_counts(s_count, s_prefix, lane);
         if (kMode == kTileCount) {
             if (lane == 0) a.tile_counts[tile] = total;
         } else if (kMode == kTilePlace) {
             if (lane == 0) s_base = a.tile_counts[tile]; // (an offset by now: tile_offsets_kernel)
         } else {
             if (lane == 0)
-                __hip_atomic_store(block + (g.row - g.row0) * kRowTiles + g.idx, (epoch << kGranuleCountBits) | total, __ATOMIC_RELAXED,
+                __hip_atomic_store(block + (g.row - g.row0) * kRowTiles + g.idx, (le.epoch << kGranuleCountBits) | total, __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_AGENT);
         }
     }
@@ -570,8 +586,7 @@ __device__ __forceinline__ void compress_tile_body(const CompressArgs &a, Source
     }
 
     if (kMode == kTileScan && wave == 0) {
-        // the sweep of the other tiles' counts: one round trip of three loads per lane, issued only now (see
-        // compress_pair_body: issued right behind the publication it mostly finds the nearest predecessors missing)
+        // the sweep of the other tiles' counts: one round trip of three loads per lane, issued only now (scan_issue)
         scan_issue(a, g, lane, true, g.has_prev, true, poll);
         const u64 base = tile_scan_resolve(a, g, block, le, tile, total, lane, poll, nullptr, nullptr);
         if (lane == 0) s_base = base;
@@ -579,7 +594,7 @@ __device__ __forceinline__ void compress_tile_body(const CompressArgs &a, Source
     __syncthreads();
 
     // ---- the parked words to their place ---------------------------------------------------------------------------
-    u64 base = uniform64(s_base) + uniform32(s_prefix[wave]);
+    u64 base = wave_out_base(s_base, s_prefix, wave);
 #pragma unroll
     for (u32 j = 0; j < kWaveSegs; ++j) {
         const u32 seg = seg0 + j;
@@ -732,7 +747,7 @@ struct UnsegScanPolicy {
 
 // Wave 0 of a tile of the unsegmented mode (compress_unseg_pair_body), after the tile's granule
 // {words, (T, L)} has gone out: the tile's offset and the length of the run that is open where it begins (the sweep of the
-// other tiles' granules is issued only here, late: compress_pair_body), the carries of the tile's waves (s_carry), what a
+// other tiles' granules is issued only here, late: scan_issue), the carries of the tile's waves (s_carry), what a
 // row's or superrow's last tile publishes, and what the launch's last tile leaves behind.
 __device__ __forceinline__ void unseg_tile_resolve(const CompressArgs &a, const ScanGeom &g, u32 *block, u64 *my_row, const LaunchEpoch &le, u32 tile,
                                                    u32 total, u32 tile_t, u32 tile_l, u32 lane, const u32 *s_t, const u32 *s_l, u32 *s_carry,
@@ -832,18 +847,6 @@ __global__ __launch_bounds__(kTileWaves * 64, 4) void compress_tile_pair_nowait_
     compress_tile_body<BitmapPairSource, 2, kMode>(a, src);
 }
 
-// ---- the no-wait route (kTileCount / kTilePlace of compress_pair_body): two pairs per wave, whatever the size of the bitmap ------
-template <bool kAligned, int kMode>
-__global__ __launch_bounds__(kTileWaves * 64, 4) void compress_nowait_kernel(const CompressArgs a) {
-    __shared__ __attribute__((aligned(1024))) u32 s_stage[kTileWaves][kPairStageWords]; // (the swizzle is made of address bits 7-9)
-    __shared__ u32 s_count[kTileWaves];
-    __shared__ u32 s_prefix[kTileWaves];
-    __shared__ u64 s_base;
-    const PairShared sm = {s_stage, s_count, s_prefix, &s_base};
-    const LaunchEpoch le = {};
-    compress_pair_body<kAligned, kNoWaitWaveSegs / 2, kMode>(a, sm, blockIdx.x, blockIdx.x * (kTileWaves * (kNoWaitWaveSegs / 2)), le);
-}
-
 // counts of the tiles -> where every tile's words start (exclusive scan, in place), + everything the last tile of the
 // scan route leaves behind: C, the index's last entry, the capacity check, the host's copy of the result.  One workgroup:
 // the table has one entry per 16 segments (64 KB of bitmap), a 1 GiB bitmap has 17 000 of them.
@@ -901,104 +904,88 @@ __global__ __launch_bounds__(kTileWaves * 64, 4) void bitop_tile_kernel(const Co
 
 } // namespace
 
+constexpr unsigned kTileThreads = kTileWaves * 64; // of a workgroup of every tile kernel
+
 static void launch_tile_pairs(const CompressArgs &a, hipStream_t s) { // the pair mode: compress_tile_pair_kernel
-    const dim3 grid(a.n_tiles), block(kTileWaves * 64);
+    const dim3 grid(a.n_tiles);
     switch (a.wave_segs) {
-    case 1: hipLaunchKernelGGL(compress_tile_pair_kernel<1>, grid, block, 0, s, a); break;
-    case 2: hipLaunchKernelGGL(compress_tile_pair_kernel<2>, grid, block, 0, s, a); break;
-    default: hipLaunchKernelGGL(compress_tile_pair_kernel<(u32)kCompressMaxWaveSegs>, grid, block, 0, s, a); break;
+    case 1: hipLaunchKernelGGL(compress_tile_pair_kernel<1>, grid, dim3(kTileThreads), 0, s, a); break;
+    case 2: hipLaunchKernelGGL(compress_tile_pair_kernel<2>, grid, dim3(kTileThreads), 0, s, a); break;
+    default: hipLaunchKernelGGL(compress_tile_pair_kernel<(u32)kCompressMaxWaveSegs>, grid, dim3(kTileThreads), 0, s, a); break;
     }
 }
 
-template <bool kAligned>
-static void launch_unseg(const CompressArgs &a, hipStream_t s) { // compress_unseg_pair_kernel: tile shapes as compress_pair_kernel's
-    const dim3 grid(a.n_tiles), block(kTileWaves * 64);
+// The tile shapes of a launch (compress_tile_shape) as the template arguments <body, tail> of a pair kernel of either family
+template <class Launch>
+static void with_tile_shape(const CompressArgs &a, const Launch &launch) {
     const u32 body = a.wave_segs / 2, tail = a.tail_pairs;
     if (body == 3 && tail == 1)
-        hipLaunchKernelGGL((compress_unseg_pair_kernel<kAligned, 3, 1>), grid, block, 0, s, a);
+        launch(WavePairs<3>{}, WavePairs<1>{});
     else if (body == 3 && tail == 2)
-        hipLaunchKernelGGL((compress_unseg_pair_kernel<kAligned, 3, 2>), grid, block, 0, s, a);
+        launch(WavePairs<3>{}, WavePairs<2>{});
     else if (body == 3)
-        hipLaunchKernelGGL((compress_unseg_pair_kernel<kAligned, 3, 3>), grid, block, 0, s, a);
+        launch(WavePairs<3>{}, WavePairs<3>{});
     else if (body == 2)
-        hipLaunchKernelGGL((compress_unseg_pair_kernel<kAligned, 2, 2>), grid, block, 0, s, a);
+        launch(WavePairs<2>{}, WavePairs<2>{});
     else
-        hipLaunchKernelGGL((compress_unseg_pair_kernel<kAligned, 1, 1>), grid, block, 0, s, a);
+        launch(WavePairs<1>{}, WavePairs<1>{});
 }
 
-uint32_t compress_nowait_wave_segs() { return kNoWaitWaveSegs; }
-
-hipError_t launch_compress_nowait(const CompressArgs &a, hipStream_t s) {
-    const dim3 grid(a.n_tiles), block(kTileWaves * 64);
-    if (a.in2) { // pair mode
-        hipLaunchKernelGGL(compress_tile_pair_nowait_kernel<kTileCount>, grid, block, 0, s, a);
-        hipLaunchKernelGGL(tile_offsets_kernel, dim3(1), dim3(1024), 0, s, a);
-        hipLaunchKernelGGL(compress_tile_pair_nowait_kernel<kTilePlace>, grid, block, 0, s, a);
-        return hipGetLastError();
-    }
-    if (a.unseg_desc) { // unsegmented mode
-        if (a.fast_segments) {
-            hipLaunchKernelGGL((compress_unseg_pair_nowait_kernel<true, kTileCount>), grid, block, 0, s, a);
-            hipLaunchKernelGGL(unseg_offsets_kernel, dim3(1), dim3(64), 0, s, a);
-            hipLaunchKernelGGL((compress_unseg_pair_nowait_kernel<true, kTilePlace>), grid, block, 0, s, a);
-        } else {
-            hipLaunchKernelGGL((compress_unseg_pair_nowait_kernel<false, kTileCount>), grid, block, 0, s, a);
-            hipLaunchKernelGGL(unseg_offsets_kernel, dim3(1), dim3(64), 0, s, a);
-            hipLaunchKernelGGL((compress_unseg_pair_nowait_kernel<false, kTilePlace>), grid, block, 0, s, a);
-        }
-        return hipGetLastError();
-    }
-    if (a.fast_segments) {
-        hipLaunchKernelGGL((compress_nowait_kernel<true, kTileCount>), grid, block, 0, s, a);
-        hipLaunchKernelGGL(tile_offsets_kernel, dim3(1), dim3(1024), 0, s, a);
-        hipLaunchKernelGGL((compress_nowait_kernel<true, kTilePlace>), grid, block, 0, s, a);
-    } else {
-        hipLaunchKernelGGL((compress_nowait_kernel<false, kTileCount>), grid, block, 0, s, a);
-        hipLaunchKernelGGL(tile_offsets_kernel, dim3(1), dim3(1024), 0, s, a);
-        hipLaunchKernelGGL((compress_nowait_kernel<false, kTilePlace>), grid, block, 0, s, a);
-    }
-    return hipGetLastError();
-}
-
-template <bool kAligned>
+template <bool kAligned> // false: input only 4-byte aligned, dword loads
 static void launch_pairs(const CompressArgs &a, hipStream_t s) {
-    const dim3 grid(a.n_tiles), block(kTileWaves * 64);
-    const u32 body = a.wave_segs / 2, tail = a.tail_pairs;
-    if (body == 3 && tail == 1)
-        hipLaunchKernelGGL((compress_pair_kernel<kAligned, 3, 1>), grid, block, 0, s, a);
-    else if (body == 3 && tail == 2)
-        hipLaunchKernelGGL((compress_pair_kernel<kAligned, 3, 2>), grid, block, 0, s, a);
-    else if (body == 3)
-        hipLaunchKernelGGL((compress_pair_kernel<kAligned, 3, 3>), grid, block, 0, s, a);
-    else if (body == 2)
-        hipLaunchKernelGGL((compress_pair_kernel<kAligned, 2, 2>), grid, block, 0, s, a);
-    else
-        hipLaunchKernelGGL((compress_pair_kernel<kAligned, 1, 1>), grid, block, 0, s, a);
+    with_tile_shape(a, [&](auto body, auto tail) {
+        constexpr u32 kBody = decltype(body)::value, kTail = decltype(tail)::value;
+        if (a.unseg_desc)
+            hipLaunchKernelGGL((compress_unseg_pair_kernel<kAligned, kBody, kTail>), dim3(a.n_tiles), dim3(kTileThreads), 0, s, a);
+        else
+            hipLaunchKernelGGL((compress_pair_kernel<kAligned, kBody, kTail>), dim3(a.n_tiles), dim3(kTileThreads), 0, s, a);
+    });
 }
 
 hipError_t launch_compress(const CompressArgs &a, hipStream_t s) {
     if (a.in2) // pair mode
         launch_tile_pairs(a, s);
-    else if (a.unseg_desc && a.fast_segments)
-        launch_unseg<true>(a, s);
-    else if (a.unseg_desc)
-        launch_unseg<false>(a, s);
     else if (a.fast_segments)
         launch_pairs<true>(a, s);
-    else // input only 4-byte aligned: dword loads
+    else
         launch_pairs<false>(a, s);
     return hipGetLastError();
 }
 
+uint32_t compress_nowait_wave_segs() { return kNoWaitWaveSegs; }
+
+// The no-wait route: count, offsets, place -- three launches in which nobody waits for anybody (the input is read or decoded
+// twice).  count / place: the two instances of a tile kernel; offsets: the one-workgroup scan of the table between them.
+template <class... Args, class... Extra>
+static hipError_t launch_count_scan_place(void (*count)(Args...), void (*place)(Args...), void (*offsets)(const CompressArgs), u32 offsets_threads,
+                                          const CompressArgs &a, hipStream_t s, const Extra &...extra) {
+    const dim3 grid(a.n_tiles);
+    hipLaunchKernelGGL(count, grid, dim3(kTileThreads), 0, s, a, extra...);
+    hipLaunchKernelGGL(offsets, dim3(1), dim3(offsets_threads), 0, s, a);
+    hipLaunchKernelGGL(place, grid, dim3(kTileThreads), 0, s, a, extra...);
+    return hipGetLastError();
+}
+
+template <bool kAligned>
+static hipError_t launch_pairs_nowait(const CompressArgs &a, hipStream_t s) {
+    if (a.unseg_desc)
+        return launch_count_scan_place(compress_unseg_pair_nowait_kernel<kAligned, kTileCount>, compress_unseg_pair_nowait_kernel<kAligned, kTilePlace>,
+                                       unseg_offsets_kernel, 64, a, s);
+    return launch_count_scan_place(compress_nowait_kernel<kAligned, kTileCount>, compress_nowait_kernel<kAligned, kTilePlace>, tile_offsets_kernel, 1024,
+                                   a, s);
+}
+
+hipError_t launch_compress_nowait(const CompressArgs &a, hipStream_t s) {
+    if (a.in2) // pair mode
+        return launch_count_scan_place(compress_tile_pair_nowait_kernel<kTileCount>, compress_tile_pair_nowait_kernel<kTilePlace>, tile_offsets_kernel,
+                                       1024, a, s);
+    return a.fast_segments ? launch_pairs_nowait<true>(a, s) : launch_pairs_nowait<false>(a, s);
+}
+
 hipError_t launch_bitop_tiles(const CompressArgs &a, const BitopOperands &ops, hipStream_t s) {
-    const dim3 grid(a.n_tiles), block(kTileWaves * 64);
-    if (a.tile_counts) { // the no-wait route: count, scan, place (nobody waits for anybody; the operands are decoded twice)
-        hipLaunchKernelGGL(bitop_tile_kernel<kTileCount>, grid, block, 0, s, a, ops);
-        hipLaunchKernelGGL(tile_offsets_kernel, dim3(1), dim3(1024), 0, s, a);
-        hipLaunchKernelGGL(bitop_tile_kernel<kTilePlace>, grid, block, 0, s, a, ops);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(bitop_tile_kernel<kTileScan>, grid, block, 0, s, a, ops);
+    if (a.tile_counts) // the no-wait route
+        return launch_count_scan_place(bitop_tile_kernel<kTileCount>, bitop_tile_kernel<kTilePlace>, tile_offsets_kernel, 1024, a, s, ops);
+    hipLaunchKernelGGL(bitop_tile_kernel<kTileScan>, dim3(a.n_tiles), dim3(kTileThreads), 0, s, a, ops);
     return hipGetLastError();
 }
 

@@ -1,4 +1,6 @@
-// wah_compress_pair.inc -- the PAIR-layout compress kernel (included by wah_compress.hip, inside namespace wah::{anonymous}).
+// wah_compress_pair.inc -- the PAIR layout of the compressor (included by wah_compress.hip, inside namespace wah::{anonymous}):
+// its building blocks, the passes of a wave over its pairs that BOTH pair-layout bodies run, and the segmented body, which
+// adds to them the segment index and the 4-byte granule of the row scan (the unsegmented one: wah_compress_unseg_pair.inc).
 //
 // Same tile protocol as compress_tile_body (arrival tickets, launch epochs, row scan: see there), different use of the
 // wavefront.  There a step is 64 consecutive groups across the lanes, so "the next group" is a DPP move, every step needs
@@ -220,6 +222,11 @@ __device__ __forceinline__ void emit_pair(const CompressArgs &a, u64 base, u32 c
         if (256u * t < count) __builtin_amdgcn_raw_buffer_store_b128(q[t], rsrc, off, 1024 * t, 0);
 }
 
+// ---- the wave's work on its pairs, shared by the two bodies (compress_pair_body below, compress_unseg_pair_body) ------------
+//   pair_wave_begin   what a wave knows before its first pair, and that pair's loads
+//   pair_count        PASS 1 of one pair: its words staged and regrouped, the next pair's loads issued, run ends flagged and ranked
+//   pair_pass2_park   PASS 2 of one pair: final words compacted in LDS, then parked in registers (the wave's last pair: left in LDS)
+//   emit_wave_pair    one pair's words, parked or still in LDS, to their place in the output
 // kWavePairs: pairs a wavefront compresses one after the other (the tile = kTileWaves x kWavePairs pairs): 1, 2 or 3.
 // More pairs per wave = fewer tiles = the fixed costs of a tile (ticket, first load, two barriers, the wait for the
 // offset, the burst of stores) paid less often: 1 GiB sparse 0.391 / 0.303 / 0.289 ms with 1 / 2 / 3 pairs; three is what
@@ -228,70 +235,141 @@ __device__ __forceinline__ void emit_pair(const CompressArgs &a, u64 base, u32 c
 // blockIdx.  (Workgroups that take TILE AFTER TILE were built on this body and measured: slower, tools/experiments.)
 // There are no "does this pair exist" branches: behind the bitmap's end the loads return zeros (a descriptor of no
 // bytes), no group is valid and no word comes out.
-// The workgroup's LDS, its tile number and the launch epoch come from the kernel (compress_pair_kernel: ONE launch may
-// run tiles of two shapes -- TileShape, wah_internal.hpp -- through two instances of this body over the same LDS).
-struct PairShared {
+// The workgroup's LDS, its tile number and the launch epoch come from the kernel (ONE launch may run tiles of two shapes
+// through two instances of a body over the same LDS: run_tile_shape).
+struct PairLds { // of a workgroup
     u32 (*stage)[kPairStageWords]; // [kTileWaves]: the staged pair, later its compacted words
-    u32 *count, *prefix;           // [kTileWaves]
-    u64 *base;
+    u32 *count, *prefix;           // [kTileWaves]: words of a wave's pairs / of the waves below it
+    u64 &base;                     // the tile's first word in the output
 };
+// (separate arrays, a set per kMode: a kernel is given only those it reads -- the no-wait count launch neither prefix nor base)
+template <int kMode>
+__device__ __forceinline__ PairLds pair_lds() {
+    __shared__ __attribute__((aligned(1024))) u32 s_stage[kTileWaves][kPairStageWords]; // (the swizzle is made of address bits 7-9)
+    __shared__ u32 s_count[kTileWaves];
+    __shared__ u32 s_prefix[kTileWaves];
+    __shared__ u64 s_base;
+    return {s_stage, s_count, s_prefix, s_base};
+}
+// the pairs' words parked in registers (the wave's LAST pair waits for the offset where it is: in LDS, read with `last_lane`)
+template <u32 kWavePairs>
+using Parked = u32x4[kWavePairs > 1 ? kWavePairs - 1 : 1][8];
 
+struct PairWave {
+    u32 lane, wave, n_pairs;
+    u32 pair0, never; // this wave's pairs: pair0 .. pair0 + kWavePairs - 1; "group after the last one": a value no 31-bit group can equal
+    u32 *stage;       // the wave's part of PairLds::stage
+};
+template <bool kAligned, u32 kWavePairs, int kMode>
+__device__ __forceinline__ PairWave pair_wave_begin(const CompressArgs &a, const PairLds &sm, u32 tile, u32 first_pair, PairLoad &pre) {
+    PairWave w;
+    w.lane = lane_id();
+    w.wave = wave_id();
+    w.n_pairs = (a.n_segments + 1u) >> 1;
+    if (kMode == kTileCount) count_launch_reset(a, tile);
+    w.stage = sm.stage[w.wave];
+    w.pair0 = first_pair + w.wave * kWavePairs;
+    asm volatile("v_mov_b32 %0, -1" : "=v"(w.never));
+    prefetch_pair<kAligned>(a, w.pair0, w.lane, pre);
+    return w;
+}
+
+// PASS 1 of pair pair0 + j, whose loads are in `pre` (more: the wave has another pair behind it, whose loads replace them).
+// Nothing but counts comes out of it, which is all the other workgroups wait for.
+struct PairCount {
+    u32 flags, rank0, incl; // the lane's flag word (pair_pass1); words of the pair in front of this lane's, and with them
+    u32 cnt, nvalid;        // words of the pair; its groups that exist: all except in the bitmap's last pair (and behind it)
+};
+template <bool kAligned, bool kCutMiddle>
+__device__ __forceinline__ PairCount pair_count(const CompressArgs &a, const PairWave &w, u32 j, bool more, PairLoad &pre, LaneGroups &g,
+                                                u64 *dg_regrouped = nullptr) {
+    const u32 pair = w.pair0 + j;
+    stage_pair(pre, w.stage, w.lane);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // the wave re-reads other lanes' words
+    if (more) prefetch_pair<kAligned>(a, pair + 1, w.lane, pre); // in flight while this pair is classified
+    regroup_pair(w.stage, w.lane, g);
+#ifdef WAH_DIAG
+    if (dg_regrouped) *dg_regrouped = __builtin_amdgcn_s_memrealtime();
+#endif
+    PairCount c;
+    c.nvalid = kPairGroups;
+    if (pair + 1u >= w.n_pairs) c.nvalid = pair >= w.n_pairs ? 0u : (a.n_segments - 1u - 2u * pair) * kSegGroups + a.last_segment_groups;
+    c.flags = pair_pass1<kCutMiddle>(g, w.lane, w.never, c.nvalid);
+    const u32 mine = (u32)__builtin_popcount(c.flags);
+    c.incl = wave_scan_incl32(mine);
+    c.rank0 = c.incl - mine;
+    c.cnt = (u32)__builtin_amdgcn_readlane((int)c.incl, 63);
+    return c;
+}
+
+// PASS 2 of the wave's pair j: final words compacted in LDS, then parked in registers -- but for the wave's last pair, which
+// nothing else needs the buffer after: it stays in LDS (read with last_lane), 32 registers less at the kernel's tightest spot.
+// (One pair, the loop over j in the bodies: as one function over the arrays of all the wave's pairs the compiler made the
+//  lane's constants of pair_pass2 again for every pair -- profiles/pair_body_refactor_asm.txt.)
+template <u32 kWavePairs>
+__device__ __forceinline__ void pair_pass2_park(const LaneGroups &g, u32 flags, u32 rank0, u32 cnt, const PairWave &w, u32 j, Parked<kWavePairs> &parked,
+                                                u32 &last_lane) {
+    const bool literals = cnt == kPairGroups && pair_all_literals(g);
+    if (literals)
+        store_literals(g, w.lane, w.stage);
+    else
+        pair_pass2(g, flags, rank0, w.lane, w.stage, cnt < kPairSparseBelow ? kPass2Skip : kPass2Swizzled);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    const u32 read_lane = literals || cnt >= kPairSwizzleFrom ? w.lane ^ ((w.lane >> 3) & 7u) : w.lane;
+    if (j + 1 < kWavePairs) {
+        park_pair(w.stage, read_lane, parked[j]);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // the buffer is written again next
+    } else {
+        last_lane = read_lane;
+    }
+}
+
+// the first n_out words of the wave's pair j to out[base ..]; ci: onto the first word (the unsegmented mode's count of a
+// leading fill that continues a run; the segmented body passes none and pays nothing for it)
+template <u32 kWavePairs>
+__device__ __forceinline__ void emit_wave_pair(const CompressArgs &a, const PairWave &w, u32 j, u64 base, u32 n_out, Parked<kWavePairs> &parked,
+                                               u32 last_lane, u32 ci = 0u) {
+    if (j + 1 < kWavePairs) {
+        if (w.lane == 0) parked[j][0].x += ci;
+        emit_pair(a, base, n_out, w.lane, parked[j]);
+    } else {
+        u32x4 q[8];
+        park_pair(w.stage, last_lane, q);
+        if (w.lane == 0) q[0].x += ci;
+        emit_pair(a, base, n_out, w.lane, q);
+    }
+}
+
+// ---- the segmented body adds: the words of a pair's FIRST segment (cnt_a) for the index, the 4-byte granule, (WAH_DIAG) the time line
 template <bool kAligned, u32 kWavePairs, int kMode = kTileScan>
-__device__ __forceinline__ void compress_pair_body(const CompressArgs &a, const PairShared &sm, u32 tile, u32 first_pair, const LaunchEpoch &le) {
-    u32(*const s_stage)[kPairStageWords] = sm.stage;
-    u32 *const s_count = sm.count;
-    u32 *const s_prefix = sm.prefix;
-    u64 &s_base = *sm.base;
-    const u32 lane = lane_id();
-    const u32 wave = wave_id();
-    const u32 n_pairs = (a.n_segments + 1u) >> 1;
+__device__ __forceinline__ void compress_pair_body(const CompressArgs &a, const PairLds &sm, u32 tile, u32 first_pair, const LaunchEpoch &le) {
 #ifdef WAH_DIAG
     u64 dg_t[8] = {};
     dg_t[0] = __builtin_amdgcn_s_memrealtime();
 #define DG(i) dg_t[i] = __builtin_amdgcn_s_memrealtime()
+#define DG_AT(i) (dg_t + (i))
 #else
 #define DG(i)
+#define DG_AT(i) nullptr
 #endif
-    if (kMode == kTileCount && tile == 0 && threadIdx.x == 0 && !a.keep_error)
-        __hip_atomic_store(a.ctrl + kCtlError, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const u32 epoch = le.epoch;
-
-    u32 *const stage = s_stage[wave];
-    const u32 pair0 = first_pair + wave * kWavePairs; // this wave's pairs: pair0 .. pair0 + kWavePairs - 1
-    u32 never;
-    asm volatile("v_mov_b32 %0, -1" : "=v"(never)); // "group after the last one": a value no 31-bit group can equal
     PairLoad pre;
-    prefetch_pair<kAligned>(a, pair0, lane, pre);
+    const PairWave w = pair_wave_begin<kAligned, kWavePairs, kMode>(a, sm, tile, first_pair, pre);
+    const u32 lane = w.lane, wave = w.wave;
 
     LaneGroups grp[kWavePairs];
     u32 flags[kWavePairs], rank0[kWavePairs];
     u32 cnt[kWavePairs], cnt_a[kWavePairs]; // words of the pair / of its first segment
-    u32x4 parked[kWavePairs > 1 ? kWavePairs - 1 : 1][8]; // (the wave's LAST pair waits for the offset where it is: in LDS)
-    u32 last_lane = lane;                                  // ... read with this lane number (swizzled after store_literals)
-
-    // ---- pass 1 of all the wave's pairs: nothing but their word counts, which is all the other workgroups wait for ---------
-#pragma unroll
-    for (u32 j = 0; j < kWavePairs; ++j) {
-        const u32 pair = pair0 + j;
-        stage_pair(pre, stage, lane);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // the wave re-reads other lanes' words
-        if (j + 1 < kWavePairs) prefetch_pair<kAligned>(a, pair + 1, lane, pre); // in flight while this pair is classified
-        regroup_pair(stage, lane, grp[j]);
-        if (j == 0) DG(7);
-        // groups of this pair that exist: all of them except in the bitmap's last pair (and behind it)
-        u32 nvalid = kPairGroups;
-        if (pair + 1u >= n_pairs) nvalid = pair >= n_pairs ? 0u : (a.n_segments - 1u - 2u * pair) * kSegGroups + a.last_segment_groups;
-        flags[j] = pair_pass1(grp[j], lane, never, nvalid);
-        const u32 mine = (u32)__builtin_popcount(flags[j]);
-        const u32 incl = wave_scan_incl32(mine);
-        rank0[j] = incl - mine;
-        cnt_a[j] = (u32)__builtin_amdgcn_readlane((int)incl, 31);
-        cnt[j] = (u32)__builtin_amdgcn_readlane((int)incl, 63);
-    }
+    Parked<kWavePairs> parked;
+    u32 last_lane = lane;
     u32 count = 0;
 #pragma unroll
-    for (u32 j = 0; j < kWavePairs; ++j) count += cnt[j];
-    if (lane == 0) s_count[wave] = count;
+    for (u32 j = 0; j < kWavePairs; ++j) {
+        const PairCount c = pair_count<kAligned, true>(a, w, j, j + 1 < kWavePairs, pre, grp[j], j == 0 ? DG_AT(7) : nullptr);
+        flags[j] = c.flags, rank0[j] = c.rank0, cnt[j] = c.cnt;
+        cnt_a[j] = (u32)__builtin_amdgcn_readlane((int)c.incl, 31);
+        count += cnt[j];
+    }
+    if (lane == 0) sm.count[wave] = count;
     DG(2);
     __syncthreads();
     DG(1);
@@ -301,47 +379,22 @@ __device__ __forceinline__ void compress_pair_body(const CompressArgs &a, const 
     u32 *const block = a.gen_desc + (u64)g.sup * kScanBlockWords;
     u32 total = 0;
     if (wave == 0) {
-        const u32 mine = lane < kTileWaves ? s_count[lane] : 0u;
-        const u32 incl = wave_scan_incl32(mine);
-        if (lane < kTileWaves) s_prefix[lane] = incl - mine;
-        total = (u32)__builtin_amdgcn_readlane((int)incl, 63);
+        total = fold_wave_counts(sm.count, sm.prefix, lane);
         if (kMode == kTileCount) {
             if (lane == 0) a.tile_counts[tile] = total;
         } else if (kMode == kTilePlace) {
-            if (lane == 0) s_base = a.tile_counts[tile]; // (an offset by now: tile_offsets_kernel)
+            if (lane == 0) sm.base = a.tile_counts[tile]; // (an offset by now: tile_offsets_kernel)
         } else if (lane == 0) {
-            __hip_atomic_store(block + (g.row - g.row0) * kRowTiles + g.idx, (epoch << kGranuleCountBits) | total, __ATOMIC_RELAXED,
+            __hip_atomic_store(block + (g.row - g.row0) * kRowTiles + g.idx, (le.epoch << kGranuleCountBits) | total, __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
         }
     }
     if (kMode == kTileCount) return;
 
-    // ---- pass 2 of all the wave's pairs: final words compacted in LDS, then parked in registers ----------------------------
 #pragma unroll
-    for (u32 j = 0; j < kWavePairs; ++j) {
-        const bool literals = cnt[j] == kPairGroups && pair_all_literals(grp[j]);
-        if (literals)
-            store_literals(grp[j], lane, stage);
-        else
-            pair_pass2(grp[j], flags[j], rank0[j], lane, stage,
-                       cnt[j] < kPairSparseBelow ? kPass2Skip : kPass2Swizzled);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        const u32 read_lane = literals || cnt[j] >= kPairSwizzleFrom ? lane ^ ((lane >> 3) & 7u) : lane;
-        if (j + 1 < kWavePairs) {
-            park_pair(stage, read_lane, parked[j]);
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // the buffer is written again next
-        } else {
-            last_lane = read_lane; // nothing else needs the buffer: 32 registers less at the kernel's tightest spot
-        }
-    }
-
+    for (u32 j = 0; j < kWavePairs; ++j) pair_pass2_park<kWavePairs>(grp[j], flags[j], rank0[j], cnt[j], w, j, parked, last_lane);
     DG(5);
-    if (kMode == kTileScan && wave == 0) {
-        // The sweep of the other tiles' counts goes out HERE, after pass 2, not right behind the publication (where
-        // compress_tile_body issues it to hide its round trip): that early the nearest predecessors have not published
-        // yet, the sweep has to be repeated anyway, and every repetition is a round trip to lines that other XCDs are
-        // writing.  Measured on the 1 GiB bitmaps (sparse / clustered / dense, isolated launches, three pairs per wave):
-        // 0.2905 / 0.2098 / 0.3949 ms with the early sweep, 0.2795 / 0.1813 / 0.3845 ms with this one.
+    if (kMode == kTileScan && wave == 0) { // (the sweep goes out only here, late: scan_issue)
         TileScan poll = {};
         scan_issue(a, g, lane, true, g.has_prev, true, poll);
 #ifdef WAH_DIAG
@@ -351,7 +404,7 @@ __device__ __forceinline__ void compress_pair_body(const CompressArgs &a, const 
 #else
         const u64 base = tile_scan_resolve(a, g, block, le, tile, total, lane, poll, nullptr, nullptr);
 #endif
-        if (lane == 0) s_base = base;
+        if (lane == 0) sm.base = base;
     }
     __syncthreads();
 #ifdef WAH_DIAG
@@ -370,22 +423,16 @@ __device__ __forceinline__ void compress_pair_body(const CompressArgs &a, const 
     }
 #endif
 
-    // ---- the parked words to their place -----------------------------------------------------------------------------------
-    u64 base = uniform64(s_base) + uniform32(s_prefix[wave]);
+    // ---- the parked words to their place, the pair's two segments into the index ---------------------------------------------
+    u64 base = wave_out_base(sm.base, sm.prefix, wave);
 #pragma unroll
     for (u32 j = 0; j < kWavePairs; ++j) {
-        const u32 pair = pair0 + j;
-        if (lane == 0 && a.seg_offsets && pair < n_pairs) {
+        const u32 pair = w.pair0 + j;
+        if (lane == 0 && a.seg_offsets && pair < w.n_pairs) {
             a.seg_offsets[2u * pair] = base;
             if (2u * pair + 1u < a.n_segments) a.seg_offsets[2u * pair + 1u] = base + cnt_a[j];
         }
-        if (j + 1 < kWavePairs) {
-            emit_pair(a, base, cnt[j], lane, parked[j]);
-        } else {
-            u32x4 q[8];
-            park_pair(stage, last_lane, q);
-            emit_pair(a, base, cnt[j], lane, q);
-        }
+        emit_wave_pair<kWavePairs>(a, w, j, base, cnt[j], parked, last_lane);
         base += cnt[j];
     }
 #ifdef WAH_DIAG
@@ -394,6 +441,8 @@ __device__ __forceinline__ void compress_pair_body(const CompressArgs &a, const 
         if (wave == 0 && lane == 0) dg_out[7] = __builtin_amdgcn_s_memrealtime(); // every wave's stores issued
     }
 #endif
+#undef DG
+#undef DG_AT
 }
 
 // One launch, tiles of up to TWO shapes.  Tiles [0, a.big_tiles) are BODY tiles of kBody pairs per wave; the tiles behind
@@ -401,22 +450,31 @@ __device__ __forceinline__ void compress_pair_body(const CompressArgs &a, const 
 // fills whole rounds of the chip's workgroup slots with body tiles and gives what is left over the smallest shape that
 // fits it into ONE more round: a launch used to end with a nearly empty round of full-size tiles (1 GiB: 6 tiles of 48
 // segments, 128 MiB: 193) that cost a full tile's life all the same.
+// body(WavePairs<n>, first pair of the tile): the body of either kernel family with n pairs per wave.
+template <u32 kN>
+struct WavePairs { static constexpr u32 value = kN; };
+template <u32 kBody, u32 kTail, class Body>
+__device__ __forceinline__ void run_tile_shape(const CompressArgs &a, u32 tile, const Body &body) {
+    if (kTail == kBody || tile < a.big_tiles)
+        body(WavePairs<kBody>{}, tile * (kTileWaves * kBody));
+    else
+        body(WavePairs<kTail>{}, a.big_tiles * (kTileWaves * kBody) + (tile - a.big_tiles) * (kTileWaves * kTail));
+}
+
 template <bool kAligned, u32 kBody, u32 kTail>
 __global__ __launch_bounds__(kTileWaves * 64, 4) void compress_pair_kernel(const CompressArgs a) {
-    __shared__ __attribute__((aligned(1024))) u32 s_stage[kTileWaves][kPairStageWords]; // (the swizzle is made of address bits 7-9)
-    __shared__ u32 s_count[kTileWaves];
-    __shared__ u32 s_prefix[kTileWaves];
-    __shared__ u64 s_base;
+    const PairLds lds = pair_lds<kTileScan>();
     __shared__ u32 s_tile;
-    const u32 tile = draw_tile(a.ctrl, &s_tile);
-    const LaunchEpoch le = launch_epoch_begin(a.ctrl, tile, a.n_tiles, a.gen_desc, a.scan_words, a.keep_error);
-    if (le.bad) { // (includes a tile number outside the grid: nothing has been indexed with it)
-        if (blockIdx.x == 0 && threadIdx.x == 0) *a.out_words = 0;
-        return;
-    }
-    const PairShared sm = {s_stage, s_count, s_prefix, &s_base};
-    if (kTail == kBody || tile < a.big_tiles)
-        compress_pair_body<kAligned, kBody>(a, sm, tile, tile * (kTileWaves * kBody), le);
-    else
-        compress_pair_body<kAligned, kTail>(a, sm, tile, a.big_tiles * (kTileWaves * kBody) + (tile - a.big_tiles) * (kTileWaves * kTail), le);
+    u32 tile;
+    const LaunchEpoch le = tile_begin(a, &s_tile, tile);
+    if (le.bad) return;
+    run_tile_shape<kBody, kTail>(a, tile, [&](auto n, u32 first_pair) __attribute__((always_inline)) {
+        compress_pair_body<kAligned, decltype(n)::value>(a, lds, tile, first_pair, le);
+    });
+}
+
+// ---- the no-wait route (kTileCount / kTilePlace): two pairs per wave, whatever the size of the bitmap; no ticket, no epoch ------
+template <bool kAligned, int kMode>
+__global__ __launch_bounds__(kTileWaves * 64, 4) void compress_nowait_kernel(const CompressArgs a) {
+    compress_pair_body<kAligned, kNoWaitWaveSegs / 2, kMode>(a, pair_lds<kMode>(), blockIdx.x, blockIdx.x * (kTileWaves * (kNoWaitWaveSegs / 2)), LaunchEpoch{});
 }

@@ -1,37 +1,35 @@
-// wah_compress_unseg_pair.inc -- the unsegmented mode (WAH_UNSEGMENTED) on the PAIR-layout body of compress_pair_kernel
+// wah_compress_unseg_pair.inc -- the unsegmented mode (WAH_UNSEGMENTED) on the shared passes of wah_compress_pair.inc
 // (included by wah_compress.hip behind the unsegmented section, inside namespace wah::{anonymous}).
 //
-// The bookkeeping described at the head of that section, with the PAIR of segments a wavefront classifies at once as the unit
-// (round 2 did it per segment on the tile body, compress_tile_body): inside a pair nothing is cut (pair_pass1<false>:
+// What it adds to them: the two bitmap words next to the wave's pairs, what each pair has at its two ends, merge / drop and
+// the wave's (T, L) out of those, the 8-byte granule {words, (T, L)} with unseg_tile_resolve, and the carry onto a merged
+// pair's first word.  That is the bookkeeping described at the head of the unsegmented section, with the PAIR of segments a
+// wavefront classifies at once as the unit: inside a pair nothing is cut (pair_pass1<false>:
 // a run crosses from the pair's first segment into its second by itself), the pair's last group closes its run as it
 // does in the segmented mode, and where that cut falls inside a run the same two local rules apply to the pair:
 //   drop_p  = the trailing fill of pair p continues into p + 1     -> the pair emits one word less (its last)
 //   merge_p = the leading fill of pair p continues one from p - 1  -> its first word's count grows by the open run's length
 // (never across a multiple of 2^29 groups = 2^18 pairs).  A pair that is ONE continuing run is transparent; waves, tiles,
-// rows and superrows fold (T, L) exactly as before (unseg_tile_resolve).  The stream is the same bit for bit.
+// rows and superrows fold (T, L) (unseg_fold_tile, unseg_tile_resolve).  The stream is the same bit for bit.
 // kMode: kTileScan = the one launch; kTileCount / kTilePlace = the two halves of its NO-WAIT route (tile = blockIdx, nobody
 // waits): count leaves {words, (T, L)} of every tile in a table, unseg_offsets_kernel turns them into {first word, length of
 // the run that is open where the tile begins}, place does the tile again and writes.
-template <bool kAligned, u32 kWavePairs, int kMode = kTileScan>
-__device__ __forceinline__ void compress_unseg_pair_body(const CompressArgs &a, const PairShared &sm, u32 *s_t, u32 *s_l, u32 *s_carry, u32 tile,
-                                                         u32 first_pair, const LaunchEpoch &le) {
-    u32(*const s_stage)[kPairStageWords] = sm.stage;
-    u32 *const s_count = sm.count;
-    u32 *const s_prefix = sm.prefix;
-    const u32 lane = lane_id();
-    const u32 wave = wave_id();
-    const u32 n_pairs = (a.n_segments + 1u) >> 1;
-    const u32 epoch = le.epoch;
-    constexpr u32 kCutPairs = kCutSegs / 2u;
-    if (kMode == kTileCount && tile == 0 && threadIdx.x == 0 && !a.keep_error)
-        __hip_atomic_store(a.ctrl + kCtlError, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+struct UnsegLds { // of a workgroup, beside PairLds: per wave (T, L) and the length of the run that is open where the wave begins
+    u32 *t, *l, *carry;
+};
+template <int kMode>
+__device__ __forceinline__ UnsegLds unseg_lds() {
+    __shared__ u32 s_t[kTileWaves], s_l[kTileWaves], s_carry[kTileWaves];
+    return {s_t, s_l, s_carry};
+}
 
-    u32 *const stage = s_stage[wave];
-    const u32 pair0 = first_pair + wave * kWavePairs;
-    u32 never;
-    asm volatile("v_mov_b32 %0, -1" : "=v"(never));
+template <bool kAligned, u32 kWavePairs, int kMode = kTileScan>
+__device__ __forceinline__ void compress_unseg_pair_body(const CompressArgs &a, const PairLds &sm, const UnsegLds &us, u32 tile, u32 first_pair,
+                                                         const LaunchEpoch &le) {
+    constexpr u32 kCutPairs = kCutSegs / 2u;
     PairLoad pre;
-    prefetch_pair<kAligned>(a, pair0, lane, pre);
+    const PairWave w = pair_wave_begin<kAligned, kWavePairs, kMode>(a, sm, tile, first_pair, pre);
+    const u32 lane = w.lane, wave = w.wave, n_pairs = w.n_pairs, pair0 = w.pair0;
     // the group in front of the wave's first pair and the one behind its last: one word of the bitmap each.  Loads without a
     // branch around them (a descriptor of four bytes or of none), looked at only after pass 1: as `if (...) x = a.in[i]` each
     // of them was waited for on the spot -- two memory round trips in a row in front of every tile's first pass.
@@ -45,29 +43,19 @@ __device__ __forceinline__ void compress_unseg_pair_body(const CompressArgs &a, 
     u32 flags[kWavePairs], rank0[kWavePairs], cnt[kWavePairs];
     u32 first[kWavePairs], last[kWavePairs], tail[kWavePairs];
     bool single[kWavePairs], merge[kWavePairs], drop[kWavePairs];
-    u32x4 parked[kWavePairs > 1 ? kWavePairs - 1 : 1][8];
+    Parked<kWavePairs> parked;
     u32 last_lane = lane;
 
     // ---- pass 1 of all the wave's pairs, and what each of them has at its two ends --------------------------------------
 #pragma unroll
     for (u32 j = 0; j < kWavePairs; ++j) {
-        const u32 pair = pair0 + j;
-        stage_pair(pre, stage, lane);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        if (j + 1 < kWavePairs) prefetch_pair<kAligned>(a, pair + 1, lane, pre);
-        regroup_pair(stage, lane, grp[j]);
-        u32 nvalid = kPairGroups;
-        if (pair + 1u >= n_pairs) nvalid = pair >= n_pairs ? 0u : (a.n_segments - 1u - 2u * pair) * kSegGroups + a.last_segment_groups;
-        flags[j] = pair_pass1<false>(grp[j], lane, never, nvalid);
-        const u32 mine = (u32)__builtin_popcount(flags[j]);
-        const u32 incl = wave_scan_incl32(mine);
-        rank0[j] = incl - mine;
-        cnt[j] = (u32)__builtin_amdgcn_readlane((int)incl, 63);
+        const PairCount c = pair_count<kAligned, false>(a, w, j, j + 1 < kWavePairs, pre, grp[j]);
+        flags[j] = c.flags, rank0[j] = c.rank0, cnt[j] = c.cnt;
         first[j] = uniform32(grp[j].x[0]);
         last[j] = 1u;
         tail[j] = 0;
         single[j] = false;
-        if (nvalid == kPairGroups) { // (wave-uniform)
+        if (c.nvalid == kPairGroups) { // (wave-uniform)
             last[j] = (u32)__builtin_amdgcn_readlane((int)grp[j].x[kLaneGroups - 1], 63);
             single[j] = cnt[j] == 1u;
             // length of the trailing run = distance from the last run end in front of group 2047 (flag word: bit 31 - k =
@@ -100,9 +88,9 @@ __device__ __forceinline__ void compress_unseg_pair_body(const CompressArgs &a, 
         }
     }
     if (lane == 0) {
-        s_count[wave] = count;
-        s_t[wave] = wave_t;
-        s_l[wave] = wave_l;
+        sm.count[wave] = count;
+        us.t[wave] = wave_t;
+        us.l[wave] = wave_l;
     }
     __syncthreads();
 
@@ -112,67 +100,41 @@ __device__ __forceinline__ void compress_unseg_pair_body(const CompressArgs &a, 
     u64 *const my_row = reinterpret_cast<u64 *>(block) + (u64)(g.row - g.row0) * kRowTiles;
     u32 total = 0, tile_t = 1u, tile_l = 0u;
     if (wave == 0) {
-        const u32 mine = lane < kTileWaves ? s_count[lane] : 0u;
-        const u32 incl = wave_scan_incl32(mine);
-        if (lane < kTileWaves) s_prefix[lane] = incl - mine;
-        total = (u32)__builtin_amdgcn_readlane((int)incl, 63);
-        unseg_fold_tile(s_t, s_l, lane, tile_t, tile_l);
+        total = fold_wave_counts(sm.count, sm.prefix, lane);
+        unseg_fold_tile(us.t, us.l, lane, tile_t, tile_l);
         if (kMode == kTileCount) {
             if (lane == 0) {
                 a.tile_counts[2ull * tile] = total;
                 a.tile_counts[2ull * tile + 1] = (tile_t ? kSlotT : 0ull) | tile_l;
             }
         } else if (kMode == kTileScan && lane == 0) {
-            __hip_atomic_store(my_row + g.idx, ((u64)epoch << 48) | ((u64)total << 32) | (tile_t ? kUnsegT : 0ull) | tile_l, __ATOMIC_RELAXED,
+            __hip_atomic_store(my_row + g.idx, ((u64)le.epoch << 48) | ((u64)total << 32) | (tile_t ? kUnsegT : 0ull) | tile_l, __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
         }
     }
     if (kMode == kTileCount) return;
 
-    // ---- pass 2 of all the wave's pairs: final words compacted in LDS, then parked in registers -----------------------------
 #pragma unroll
-    for (u32 j = 0; j < kWavePairs; ++j) {
-        const bool literals = cnt[j] == kPairGroups && pair_all_literals(grp[j]);
-        if (literals)
-            store_literals(grp[j], lane, stage);
-        else
-            pair_pass2(grp[j], flags[j], rank0[j], lane, stage,
-                       cnt[j] < kPairSparseBelow ? kPass2Skip : kPass2Swizzled);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        const u32 read_lane = literals || cnt[j] >= kPairSwizzleFrom ? lane ^ ((lane >> 3) & 7u) : lane;
-        if (j + 1 < kWavePairs) {
-            park_pair(stage, read_lane, parked[j]);
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        } else {
-            last_lane = read_lane;
-        }
-    }
+    for (u32 j = 0; j < kWavePairs; ++j) pair_pass2_park<kWavePairs>(grp[j], flags[j], rank0[j], cnt[j], w, j, parked, last_lane);
 
     if (kMode == kTilePlace && wave == 0) { // both out of the table (unseg_offsets_kernel)
-        (void)unseg_wave_carries(s_t, s_l, s_carry, a.tile_counts[2ull * tile + 1], lane);
-        if (lane == 0) *sm.base = a.tile_counts[2ull * tile];
+        (void)unseg_wave_carries(us.t, us.l, us.carry, a.tile_counts[2ull * tile + 1], lane);
+        if (lane == 0) sm.base = a.tile_counts[2ull * tile];
     }
-    if (kMode == kTileScan && wave == 0) unseg_tile_resolve(a, g, block, my_row, le, tile, total, tile_t, tile_l, lane, s_t, s_l, s_carry, sm.base);
+    if (kMode == kTileScan && wave == 0) // (issues its sweep only here, late: scan_issue)
+        unseg_tile_resolve(a, g, block, my_row, le, tile, total, tile_t, tile_l, lane, us.t, us.l, us.carry, &sm.base);
     __syncthreads();
 
     // ---- the parked words to their place: a continuing leading fill gets the open run's length, a continuing trailing
     //      fill is left to the pair in which the run ends ----------------------------------------------------------------------
-    u64 base = uniform64(*sm.base) + uniform32(s_prefix[wave]);
-    u32 c = uniform32(s_carry[wave]);
+    u64 base = wave_out_base(sm.base, sm.prefix, wave);
+    u32 c = uniform32(us.carry[wave]);
 #pragma unroll
     for (u32 j = 0; j < kWavePairs; ++j) {
         if (pair0 + j < n_pairs) { // (wave-uniform)
             const u32 ci = merge[j] ? c : 0u;
             const u32 n_out = cnt[j] - (drop[j] ? 1u : 0u);
-            if (j + 1 < kWavePairs) {
-                if (lane == 0) parked[j][0].x += ci; // (count of the leading fill; ci = 0 otherwise)
-                emit_pair(a, base, n_out, lane, parked[j]);
-            } else {
-                u32x4 q[8];
-                park_pair(stage, last_lane, q);
-                if (lane == 0) q[0].x += ci;
-                emit_pair(a, base, n_out, lane, q);
-            }
+            emit_wave_pair<kWavePairs>(a, w, j, base, n_out, parked, last_lane, ci); // (ci: onto the count of the leading fill)
             base += n_out;
             c = single[j] && merge[j] ? ci + kPairGroups : tail[j];
         }
@@ -180,36 +142,20 @@ __device__ __forceinline__ void compress_unseg_pair_body(const CompressArgs &a, 
 }
 
 template <bool kAligned, u32 kBody, u32 kTail>
-__global__ __launch_bounds__(kTileWaves * 64, 4) void compress_unseg_pair_kernel(const CompressArgs a) {
-    __shared__ __attribute__((aligned(1024))) u32 s_stage[kTileWaves][kPairStageWords]; // (the swizzle is made of address bits 7-9)
-    __shared__ u32 s_count[kTileWaves];
-    __shared__ u32 s_prefix[kTileWaves];
-    __shared__ u32 s_t[kTileWaves], s_l[kTileWaves], s_carry[kTileWaves];
-    __shared__ u64 s_base;
+__global__ __launch_bounds__(kTileWaves * 64, 4) void compress_unseg_pair_kernel(const CompressArgs a) { // tile shapes: run_tile_shape
+    const PairLds lds = pair_lds<kTileScan>();
+    const UnsegLds us = unseg_lds<kTileScan>();
     __shared__ u32 s_tile;
-    const u32 tile = draw_tile(a.ctrl, &s_tile);
-    const LaunchEpoch le = launch_epoch_begin(a.ctrl, tile, a.n_tiles, a.gen_desc, a.scan_words, a.keep_error);
-    if (le.bad) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) *a.out_words = 0;
-        return;
-    }
-    const PairShared sm = {s_stage, s_count, s_prefix, &s_base};
-    if (kTail == kBody || tile < a.big_tiles)
-        compress_unseg_pair_body<kAligned, kBody>(a, sm, s_t, s_l, s_carry, tile, tile * (kTileWaves * kBody), le);
-    else
-        compress_unseg_pair_body<kAligned, kTail>(a, sm, s_t, s_l, s_carry, tile,
-                                                  a.big_tiles * (kTileWaves * kBody) + (tile - a.big_tiles) * (kTileWaves * kTail), le);
+    u32 tile;
+    const LaunchEpoch le = tile_begin(a, &s_tile, tile);
+    if (le.bad) return;
+    run_tile_shape<kBody, kTail>(a, tile, [&](auto n, u32 first_pair) __attribute__((always_inline)) {
+        compress_unseg_pair_body<kAligned, decltype(n)::value>(a, lds, us, tile, first_pair, le);
+    });
 }
 
 // ---- the no-wait route of the unsegmented mode: two pairs per wave, whatever the size of the bitmap ------------------------
 template <bool kAligned, int kMode>
 __global__ __launch_bounds__(kTileWaves * 64, 4) void compress_unseg_pair_nowait_kernel(const CompressArgs a) {
-    __shared__ __attribute__((aligned(1024))) u32 s_stage[kTileWaves][kPairStageWords];
-    __shared__ u32 s_count[kTileWaves];
-    __shared__ u32 s_prefix[kTileWaves];
-    __shared__ u32 s_t[kTileWaves], s_l[kTileWaves], s_carry[kTileWaves];
-    __shared__ u64 s_base;
-    const PairShared sm = {s_stage, s_count, s_prefix, &s_base};
-    const LaunchEpoch le = {};
-    compress_unseg_pair_body<kAligned, kNoWaitWaveSegs / 2, kMode>(a, sm, s_t, s_l, s_carry, blockIdx.x, blockIdx.x * (kTileWaves * (kNoWaitWaveSegs / 2)), le);
+    compress_unseg_pair_body<kAligned, kNoWaitWaveSegs / 2, kMode>(a, pair_lds<kMode>(), unseg_lds<kMode>(), blockIdx.x, blockIdx.x * (kTileWaves * (kNoWaitWaveSegs / 2)), LaunchEpoch{});
 }

@@ -8,13 +8,13 @@ The switches (gpu-wah_amd/csrc) and the probes that sit on them:
   switch                                   where                                  probes
   ---------------------------------------  -------------------------------------  ------------------------------------------
   words of a segment pair < / >= 384       wah_compress_pair.inc (pass 2 variant  PAIR_COUNTS (383, 384, 385)
-    (kPairSparseBelow, kPairSwizzleFrom)   and park_pair's lane), the same line
-                                           in wah_compress_unseg_pair.inc
+    (kPairSparseBelow, kPairSwizzleFrom)   and park_pair's lane: pair_pass2_park,
+                                           run by both pair-layout bodies)
   pair of 2048 words, all literals or not  wah_compress_pair.inc                  PAIR_COUNTS (2046 .. 2048), FULL_PAIR_FILL_AT
     (store_literals / swizzled pass 2)       (pair_all_literals)
   256 t < count, t = 0 .. 7                emit_pair                              PAIR_COUNTS (256 k - 1, 256 k, 256 k + 1)
   1st / 2nd / 3rd pair of a wave, the      compress_pair_body, compress_tile_     SHAPE_CASES (the probes in every size class of
-    kernel instances <1,1> <2,2> <3,3>       shape, launch_pairs / launch_unseg     compress_tile_shape, shifted by 0, 1, 2 pairs),
+    kernel instances <1,1> <2,2> <3,3>       shape, with_tile_shape                 compress_tile_shape, shifted by 0, 1, 2 pairs),
     <3,1> <3,2>; two pairs (no wait)                                                PAIR_PADDINGS
   one-pass tile <= 61440 groups            wah_decode_tile.inc (deferred[],       TILE_TOTALS x TILE_WAYS x TILE_PLACES,
     (WAH_DT_MAXG x 1024), one count above    the clamp of a single count)           alternating_tile_stream

@@ -466,24 +466,39 @@ def test_merge_fills_unsegmented_form(wah, oracle):
     assert not wah.validate_device(wah.merge_fills_device(_dev(z))).segment_canonical
 
 
+def _islands(n, k, seed):  # zeros (or ones) with k short random islands: long runs through many transparent tiles
+    x = np.zeros(n, np.uint32) if seed % 2 else np.full(n, 0xFFFFFFFF, np.uint32)
+    for p in np.random.default_rng(seed).integers(0, n - 40, k):
+        x[p: p + 37] = np.random.default_rng(seed + int(p)).integers(0, 2**32, 37, dtype=np.uint64).astype(np.uint32)
+    return x
+
+
+def _run_boundary_cases():
+    """Runs of k whole segments, zeros and ones in turn, that end on and next to the boundaries of the no-wait route's pair (2
+    segments), wave (4) and tile (32); with them the long runs: transparent tiles, a bitmap shorter than a segment, islands."""
+    cases = []
+    for k in (1, 2, 3, 4, 5, 31, 32, 33, 64, 100):
+        blocks = np.zeros((40, k, 992), np.uint32)
+        blocks[1::2] = 0xFFFFFFFF
+        cases.append(blocks.reshape(-1))
+        if k == 3:
+            cases.append(blocks.reshape(-1)[:-5].copy())  # ... and a short last segment
+    cases += [np.zeros(992 * 700 + 3, np.uint32), np.full(992 * 333, 0xFFFFFFFF, np.uint32), np.zeros(31, np.uint32),
+              _islands(992 * 3000 + 77, 5, 4)]
+    return cases
+
+
 def test_unsegmented_encoder_mode(wah, oracle):
     """wah_compress_device_ex(..., WAH_UNSEGMENTED) == merge_fills(compress(x)), bit for bit, in the one pass: runs that
     cross segments, waves, tiles, rows of tiles, and (last case) a superrow of tiles and the 2^29-group cut."""
     import torch
 
     rng = np.random.default_rng(11)
-
-    def islands(n, k, seed):  # zeros (or ones) with k short random islands: long runs through many transparent tiles
-        x = np.zeros(n, np.uint32) if seed % 2 else np.full(n, 0xFFFFFFFF, np.uint32)
-        for p in np.random.default_rng(seed).integers(0, n - 40, k):
-            x[p: p + 37] = np.random.default_rng(seed + int(p)).integers(0, 2**32, 37, dtype=np.uint64).astype(np.uint32)
-        return x
-
     alternating = np.zeros(992 * 64, np.uint32)
     alternating.reshape(64, 992)[1::2] = 0xFFFFFFFF
     cases = [np.zeros(992 * 700 + 3, np.uint32), np.full(992 * 333, 0xFFFFFFFF, np.uint32), oracle.gen_uniform(992 * 900, 2, 2.0**-14),
              oracle.gen_clustered(992 * 600 + 11, 3, 50000), oracle.gen_uniform(992 * 40, 4, 0.3), alternating,
-             islands(992 * 30000, 9, 1), islands(992 * 30000 + 77, 40, 2), islands(992 * 9000, 3, 3), np.zeros(31, np.uint32),
+             _islands(992 * 30000, 9, 1), _islands(992 * 30000 + 77, 40, 2), _islands(992 * 9000, 3, 3), np.zeros(31, np.uint32),
              oracle.gen_clustered(992 * 30000, 5, 2_000_000)]
     for k in (2, 3, 24, 48, 50):  # runs of k whole segments, zeros and ones in turn: run ends ON pair, wave and tile boundaries
         blocks = np.zeros((130, k, 992), np.uint32)
@@ -515,6 +530,26 @@ def test_unsegmented_encoder_mode(wah, oracle):
         wah.DeviceCompressor(992, indexed=True, unsegmented=True)
     assert wah.lib().wah_compress_device_ex(z.data_ptr(), 992, comp.out.data_ptr(), comp.capacity, comp.count.data_ptr(), 6,
                                             comp.workspace.data_ptr(), comp.ws_bytes, None) == -1
+
+
+def test_unsegmented_no_wait_run_boundaries(wah, oracle):
+    """The unsegmented no-wait route (flags 3: compress_unseg_pair_nowait_kernel, two pairs per wave, 32 segments per tile) where
+    runs end on and next to its own pair, wave and tile boundaries: its merge / drop / carry logic against the restatement,
+    and on the same inputs the unsegmented one-launch kernel (flags 1) and the segmented no-wait route (flags 2), which run
+    through the same passes.  Every stream exact; the flags-3 stream decodes to the input."""
+    for x in _run_boundary_cases():
+        segmented = oracle.compress(x)
+        merged = _py_merge_fills(segmented)
+        d = _dev(x)
+        for flags, want in ((3, merged), (1, merged), (2, segmented)):
+            comp = wah.DeviceCompressor(len(x), unsegmented=bool(flags & 1), no_wait=bool(flags & 2))
+            comp.run(d)
+            got = _host(comp.result())
+            assert np.array_equal(got, want), (flags, len(x), len(got), len(want))
+            if flags == 3:
+                back = _host(wah.decompress_device(comp.result().clone(), len(x) + 1))
+                assert np.array_equal(back[: len(x)], x), len(x)
+            del comp
 
 
 # ---------------------------------------------------------------- host decompress: kept output buffer; count slots, streams
