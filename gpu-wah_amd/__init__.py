@@ -58,6 +58,8 @@ from .api import (  # noqa: F401
     bsi_arith_device,
     bsi_arith_row_order,
     ARITH_OPS,
+    bsi_mul_device,
+    bsi_mul_row_order,
     bsi_kth_device,
     bsi_kth_query,
     BSI_KTH_ASCENDING,

@@ -75,6 +75,9 @@ ABI_SYMBOLS = {
     "wah_bsi_arith_scratch_bytes": (_sz, [_u64, _u64, ctypes.c_uint]),
     "wah_bsi_arith_indexed_device": (_int, [_int, _u64, _u64, _u64, _u64, _vp, ctypes.c_uint, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
     "wah_bsi_arith_status": (_int, [_vp, _u64, _u64, ctypes.c_uint, _vp]),
+    "wah_bsi_mul_scratch_bytes": (_sz, [_u64, _u64, _u64, ctypes.c_uint]),
+    "wah_bsi_mul_indexed_device": (_int, [_u64, _u64, _u64, _u64, _vp, ctypes.c_uint, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
+    "wah_bsi_mul_status": (_int, [_vp, _u64, _u64, _u64, ctypes.c_uint, _vp]),
     "wah_bsi_kth_scratch_bytes": (_sz, [_u64, _u64]),
     "wah_bsi_kth_indexed_device": (_int, [_u64, _u64, _u64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "wah_bsi_kth_status": (_int, [_vp, _vp]),
@@ -743,6 +746,66 @@ def bsi_arith_device(table, n_bits_a, n_bits_b, op, n_bits_out, n_words, exists_
     if not check:
         return out, count, out_offsets
     _check(lib().wah_bsi_arith_status(scratch.data_ptr(), n, k_out, flags, sp), "bsi_arith")
+    return out[: int(count.item())], out_offsets[:entries]
+
+
+def bsi_mul_row_order(ka, kb, exists_a=False, exists_b=False):
+    """The table order of wah_bsi_mul_indexed_device for attributes of ka and kb slices, as a list of (attribute, slice index)
+    counted as in bsi_compare_row_order: 0 is an attribute's MOST significant slice, ka (kb) its existence bitmap.  A's existence
+    row, then B's, come FIRST; then ALL of A's slices, LEAST significant first; then ALL of B's, LEAST significant first -- no
+    interleaving: every slice of B meets the whole of A.  Needs neither torch nor a device."""
+    ka, kb = int(ka), int(kb)
+    if not (1 <= ka <= BSI_MAX_SLICES and 1 <= kb <= BSI_MAX_SLICES):
+        raise WahError("between 1 and 64 slices per attribute")
+    order = []
+    if exists_a:
+        order.append(("a", ka))
+    if exists_b:
+        order.append(("b", kb))
+    order += [("a", ka - 1 - sig) for sig in range(ka)]
+    order += [("b", kb - 1 - sig) for sig in range(kb)]
+    return order
+
+
+def bsi_mul_device(table, n_bits_a, n_bits_b, n_bits_out, n_words, exists_a=False, exists_b=False, scratch=None, out=None,
+                   out_offsets=None, check=True):
+    """The bit-sliced index of (A * B) mod 2^n_bits_out, row by row over two bit-sliced attributes, in one call
+    (wah_bsi_mul_indexed_device).  table: a list of (stream, seg_offsets) pairs or a ready [rows, 3] table in the order of
+    bsi_mul_row_order(n_bits_a, n_bits_b, exists_a, exists_b) -- only the device reads it.  Both values are read as unsigned.
+    n_bits_out: 1 .. 64; n_bits_a + n_bits_b loses nothing, fewer truncate, more zero-extend.  The call takes the operands as
+    given; the narrower one as A keeps the scratch small.  n_words, the existence flags, the result and scratch / out /
+    out_offsets / check: as bsi_arith_device -- with check=False the caller reads wah_bsi_mul_status later."""
+    torch = _torch()
+    table = _operand_table(table, "a row table")
+    dev = table.device
+    ka, kb, k_out, n = int(n_bits_a), int(n_bits_b), int(n_bits_out), int(n_words)
+    flags = (BSI_EXISTS_A if exists_a else 0) | (BSI_EXISTS_B if exists_b else 0)
+    if not (1 <= ka <= BSI_MAX_SLICES and 1 <= kb <= BSI_MAX_SLICES and 1 <= k_out <= BSI_MAX_SLICES):
+        raise WahError("between 1 and 64 slices per attribute and in the result")
+    if int(table.shape[0]) != ka + kb + bool(exists_a) + bool(exists_b):
+        raise WahError("the table has one row per slice of either attribute and one per existence bitmap")
+    if n <= 0 or n % 992:
+        raise WahError("slices of a multiple of 992 words")
+    rows_out = k_out + (1 if flags else 0)
+    entries = rows_out * (n // 992) + 1
+    if scratch is None:
+        scratch = torch.empty(int(lib().wah_bsi_mul_scratch_bytes(n, ka, k_out, flags)), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.empty(max_compressed_words(rows_out * n), dtype=torch.int32, device=dev)
+    else:
+        _as_words(torch, out)
+    if out_offsets is None:
+        out_offsets = torch.empty(entries, dtype=torch.int64, device=dev)
+    elif out_offsets.dtype != torch.int64 or out_offsets.numel() < entries or not out_offsets.is_contiguous() or out_offsets.device != dev:
+        raise WahError("out_offsets: a contiguous int64 tensor of rows_out * n_words / 992 + 1 entries on the table's device")
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    sp = _stream_ptr(torch)
+    _check(lib().wah_bsi_mul_indexed_device(n, ka, kb, k_out, table.data_ptr(), flags, out.data_ptr(), out.numel(), count.data_ptr(),
+                                            out_offsets.data_ptr(), scratch.data_ptr(), scratch.numel(), sp),
+           "wah_bsi_mul_indexed_device")
+    if not check:
+        return out, count, out_offsets
+    _check(lib().wah_bsi_mul_status(scratch.data_ptr(), n, ka, k_out, flags, sp), "bsi_mul")
     return out[: int(count.item())], out_offsets[:entries]
 
 

@@ -474,6 +474,50 @@ def subtract_columns(wah, bsi_a, bsi_b, n_bits=None, table=None, **reuse):
     return _arith_columns(wah, "-", bsi_a, bsi_b, n_bits, table, reuse)
 
 
+def multiply_columns(wah, bsi_a, bsi_b, n_bits=None, table=None, **reuse):
+    """`A * B` row by row over TWO bit-sliced attributes in one call, as a NEW bit-sliced attribute (wah_bsi_mul_indexed_device):
+    arguments and result as add_columns.  The result holds (A * B) mod 2^n_bits, both values read as unsigned; n_bits defaults
+    to min(ka + kb, 63), which loses nothing below 63 bits (the call itself takes 1 .. 64).  The operation is commutative and the
+    call keeps an image of its first operand in the scratch, so the NARROWER attribute is passed as A (bsi_a where the widths
+    are equal); multiply_columns(a, b) and multiply_columns(b, a) return the same streams.  The table
+    puts the existence rows first, then all of A's slices, then all of B's, least significant first (api.bsi_mul_row_order); a
+    table passed in is overwritten in that order."""
+    import torch
+
+    from . import api
+
+    if bsi_b[3] < bsi_a[3]:
+        bsi_a, bsi_b = bsi_b, bsi_a
+    _, _, n, ka, has_a = bsi_a
+    _, _, n_b, kb, has_b = bsi_b
+    if n != n_b:
+        raise ValueError("the two attributes have different column lengths")
+    n_bits = min(ka + kb, 63) if n_bits is None else int(n_bits)
+    if not 1 <= n_bits <= 64:
+        raise ValueError("between 1 and 64 bits")
+    table = _two_attribute_table(wah.bsi_mul_row_order(ka, kb, has_a, has_b), bsi_a, bsi_b, table)
+    has_exists = bool(has_a or has_b)
+    flags = (wah.BSI_EXISTS_A if has_a else 0) | (wah.BSI_EXISTS_B if has_b else 0)
+    check = reuse.pop("check", True)
+    if reuse.get("scratch") is None:
+        reuse["scratch"] = torch.empty(int(wah.lib().wah_bsi_mul_scratch_bytes(n, ka, n_bits, flags)), dtype=torch.uint8, device=table.device)
+    out, count, out_offsets = wah.bsi_mul_device(table, ka, kb, n_bits, n, exists_a=has_a, exists_b=has_b, check=False, **reuse)
+    if not check:
+        return out, out_offsets, n, n_bits, has_exists
+    api._check(wah.lib().wah_bsi_mul_status(reuse["scratch"].data_ptr(), n, ka, n_bits, flags, api._stream_ptr(torch)), "bsi_mul")
+    return out[: int(count.item())], out_offsets, n, n_bits, has_exists
+
+
+def sum_product_where(wah, bsi_a, bsi_b, mask_stream, mask_offsets):
+    """`SELECT SUM(a * b) WHERE <mask>` over two bit-sliced attributes: multiply_columns with all ka + kb slices, then
+    sum_column_where over the product.  Raises ValueError where ka + kb > 64: the product would be truncated.  Returns a
+    Python int."""
+    ka, kb = bsi_a[3], bsi_b[3]
+    if ka + kb > 64:
+        raise ValueError("the product of the two attributes needs more than 64 bits")
+    return sum_column_where(wah, multiply_columns(wah, bsi_a, bsi_b, n_bits=ka + kb), mask_stream, mask_offsets)
+
+
 def sum_column_where(wah, bsi, mask_stream, mask_offsets):
     """`SELECT SUM(value) WHERE <mask>` over a bit-sliced attribute without decoding a bitmap: ONE wah_count_masked_indexed_device
     call with the mask (an indexed compressed bitmap of the attribute's column length: a filter_columns or range_column result)

@@ -1796,6 +1796,19 @@ namespace {
 constexpr unsigned kArithFlags = WAH_BSI_EXISTS_A | WAH_BSI_EXISTS_B;
 // the result's matrix rows: its slices, and the AND of the existence bitmaps where there is one
 inline uint64_t arith_rows_out(uint64_t n_slices_out, unsigned flags) { return n_slices_out + ((flags & kArithFlags) ? 1u : 0u); }
+// the argument checks of the calls that compute a new attribute from two (arithmetic, multiplication): WAH_OK or the refusal
+int two_attribute_args(uint64_t n_words, uint64_t n_slices_a, uint64_t n_slices_b, uint64_t n_slices_out, const wah_bitop_operand *d_rows,
+                       unsigned flags, const uint32_t *d_out, const uint64_t *d_out_words, const uint64_t *d_out_offsets, const void *d_scratch) {
+    if (n_slices_a < 1 || n_slices_a > WAH_BSI_MAX_SLICES || n_slices_b < 1 || n_slices_b > WAH_BSI_MAX_SLICES || n_slices_out < 1 ||
+        n_slices_out > WAH_BSI_MAX_SLICES || (flags & ~kArithFlags))
+        return refuse("between 1 and 64 slices per attribute and in the result, no flag besides WAH_BSI_EXISTS_A and WAH_BSI_EXISTS_B", WAH_ERR_ARG);
+    if (n_words == 0 || n_words % wah::kSegWords || n_words >= (1ull << 40) || arith_rows_out(n_slices_out, flags) * n_words >= (1ull << 40))
+        return refuse("slices of a multiple of 992 words, all slices of the result together fewer than 2^40 words", WAH_ERR_ARG);
+    if (!d_rows || !aligned(d_rows, 7) || !scratch_ok(d_scratch)) return refuse("null or misaligned row table or scratch", WAH_ERR_ARG);
+    if (!d_out || !aligned(d_out, 3) || !d_out_words || !aligned(d_out_words, 7) || !d_out_offsets || !aligned(d_out_offsets, 7))
+        return refuse("null or misaligned output", WAH_ERR_ARG);
+    return WAH_OK;
+}
 } // namespace
 
 size_t wah_bsi_arith_scratch_bytes(uint64_t n_words, uint64_t n_slices_out, unsigned flags) {
@@ -1807,15 +1820,9 @@ int wah_bsi_arith_indexed_device(int op, uint64_t n_words, uint64_t n_slices_a, 
                                  uint64_t *d_out_words, uint64_t *d_out_offsets, void *d_scratch, size_t scratch_bytes, void *stream) {
     g_err[0] = 0;
     if (op != WAH_ARITH_ADD && op != WAH_ARITH_SUB) return refuse("unknown arithmetic operation", WAH_ERR_ARG);
-    if (n_slices_a < 1 || n_slices_a > WAH_BSI_MAX_SLICES || n_slices_b < 1 || n_slices_b > WAH_BSI_MAX_SLICES || n_slices_out < 1 ||
-        n_slices_out > WAH_BSI_MAX_SLICES || (flags & ~kArithFlags))
-        return refuse("between 1 and 64 slices per attribute and in the result, no flag besides WAH_BSI_EXISTS_A and WAH_BSI_EXISTS_B", WAH_ERR_ARG);
+    if (const int rc = two_attribute_args(n_words, n_slices_a, n_slices_b, n_slices_out, d_rows, flags, d_out, d_out_words, d_out_offsets, d_scratch))
+        return rc;
     const uint64_t rows_out = arith_rows_out(n_slices_out, flags);
-    if (n_words == 0 || n_words % wah::kSegWords || n_words >= (1ull << 40) || rows_out * n_words >= (1ull << 40))
-        return refuse("slices of a multiple of 992 words, all slices of the result together fewer than 2^40 words", WAH_ERR_ARG);
-    if (!d_rows || !aligned(d_rows, 7) || !scratch_ok(d_scratch)) return refuse("null or misaligned row table or scratch", WAH_ERR_ARG);
-    if (!d_out || !aligned(d_out, 3) || !d_out_words || !aligned(d_out_words, 7) || !d_out_offsets || !aligned(d_out_offsets, 7))
-        return refuse("null or misaligned output", WAH_ERR_ARG);
     const BsiBuildLayout l = bsi_build_layout(n_words, rows_out);
     if (scratch_bytes < l.total) return refuse("scratch too small", WAH_ERR_WORKSPACE);
     char *sc = static_cast<char *>(d_scratch);
@@ -1842,6 +1849,59 @@ int wah_bsi_arith_indexed_device(int op, uint64_t n_words, uint64_t n_slices_a, 
 }
 
 int wah_bsi_arith_status(void *d_scratch, uint64_t n_words, uint64_t n_slices_out, unsigned flags, void *stream) {
+    if (!d_scratch) return WAH_ERR_ARG;
+    const int rc = read_status(d_scratch, stream); // the sweep: everything the list call refuses in an operand
+    if (rc != WAH_OK) return rc;
+    return read_status(static_cast<char *>(d_scratch) + bsi_build_layout(n_words, arith_rows_out(n_slices_out, flags)).ws_c, stream);
+}
+
+// A * B row by row over two bit-sliced attributes, as a new one (wah_bitop_list.hip, bsi_mul_segments_kernel).  The arithmetic
+// call's scratch and road, and behind them the sweep's working area: per segment A's image and the accumulator in group form,
+// n_slices_a + n_slices_out slices of 1024 groups, which needs no initialisation.
+namespace {
+inline size_t mul_work_bytes(uint64_t n_words, uint64_t n_slices_a, uint64_t n_slices_out) {
+    return (size_t)(n_words / wah::kSegWords) * (size_t)(n_slices_a + n_slices_out) * wah::kSegGroups * sizeof(uint32_t);
+}
+} // namespace
+
+size_t wah_bsi_mul_scratch_bytes(uint64_t n_words, uint64_t n_slices_a, uint64_t n_slices_out, unsigned flags) {
+    return bsi_build_layout(n_words, arith_rows_out(n_slices_out, flags)).total + mul_work_bytes(n_words, n_slices_a, n_slices_out);
+}
+
+int wah_bsi_mul_indexed_device(uint64_t n_words, uint64_t n_slices_a, uint64_t n_slices_b, uint64_t n_slices_out,
+                               const wah_bitop_operand *d_rows, unsigned flags, uint32_t *d_out, uint64_t out_capacity_words,
+                               uint64_t *d_out_words, uint64_t *d_out_offsets, void *d_scratch, size_t scratch_bytes, void *stream) {
+    g_err[0] = 0;
+    if (const int rc = two_attribute_args(n_words, n_slices_a, n_slices_b, n_slices_out, d_rows, flags, d_out, d_out_words, d_out_offsets, d_scratch))
+        return rc;
+    const uint64_t rows_out = arith_rows_out(n_slices_out, flags);
+    const BsiBuildLayout l = bsi_build_layout(n_words, rows_out);
+    if (scratch_bytes < l.total + mul_work_bytes(n_words, n_slices_a, n_slices_out)) return refuse("scratch too small", WAH_ERR_WORKSPACE);
+    char *sc = static_cast<char *>(d_scratch);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const SegGeometry g = seg_geometry(n_words);
+    wah::BsiMulArgs a = {};
+    a.table = reinterpret_cast<const wah::BitopListOperand *>(d_rows);
+    a.matrix = reinterpret_cast<uint32_t *>(sc + l.matrix);
+    a.work = reinterpret_cast<uint32_t *>(sc + l.total); // (a multiple of 256 bytes: the quads are aligned)
+    a.ctrl = reinterpret_cast<uint32_t *>(sc);
+    a.n_words = n_words;
+    a.groups = g.groups;
+    a.n_segments = g.n_segments;
+    a.n_slices_a = (uint32_t)n_slices_a;
+    a.n_slices_b = (uint32_t)n_slices_b;
+    a.n_slices_out = (uint32_t)n_slices_out;
+    a.exists_a = (flags & WAH_BSI_EXISTS_A) ? 1u : 0u;
+    a.exists_b = (flags & WAH_BSI_EXISTS_B) ? 1u : 0u;
+    hipError_t e = wah::launch_clear(sc, wah::kCtlWords * sizeof(uint32_t), s); // (read by wah_bsi_mul_status)
+    if (e == hipSuccess) e = wah::launch_bsi_mul_segments(a, s);
+    if (e != hipSuccess) return refuse("multiplication sweep launch", WAH_ERR_HIP, e);
+    return compress_device_impl(a.matrix, nullptr, 0, nullptr, rows_out * n_words, d_out, out_capacity_words, d_out_words, d_out_offsets,
+                                sc + l.ws_c, l.ws_c_bytes, stream, true);
+}
+
+int wah_bsi_mul_status(void *d_scratch, uint64_t n_words, uint64_t n_slices_a, uint64_t n_slices_out, unsigned flags, void *stream) {
+    (void)n_slices_a; // (the working area lies behind everything the status reads)
     if (!d_scratch) return WAH_ERR_ARG;
     const int rc = read_status(d_scratch, stream); // the sweep: everything the list call refuses in an operand
     if (rc != WAH_OK) return rc;

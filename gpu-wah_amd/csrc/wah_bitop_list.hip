@@ -7,6 +7,7 @@
 //   bsi_range_segments_kernel      lo <= value <= hi over a bit-sliced attribute (wah_bsi_range_indexed_device)
 //   bsi_compare_segments_kernel    A op B row by row over two bit-sliced attributes (wah_bsi_compare_indexed_device)
 //   bsi_arith_segments_kernel      A + B, A - B row by row as a new bit-sliced attribute (wah_bsi_arith_indexed_device)
+//   bsi_mul_segments_kernel        A * B row by row as a new bit-sliced attribute (wah_bsi_mul_indexed_device)
 //   bsi_kth_pass_kernel            one pass of the radix select over such an attribute (wah_bsi_kth_indexed_device)
 //   fetch_items_kernel             the values of listed rows, one wavefront per 64 listed rows of a segment (wah_fetch_indexed_device)
 // The walk itself is written once (list_walk), and so is the sweep that keeps one row at a time in the zeroed image (row_sweep);
@@ -685,6 +686,135 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, kBsiWavesPerSimd) void bsi_ar
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
+// wah_bsi_mul_indexed_device: A * B row by row over two bit-sliced attributes of ka and kb slices, as a NEW bit-sliced attribute
+// of n_out slices -- schoolbook shift-and-add over the slices.  Every slice of B meets every slice of A, so this table is not
+// interleaved: A's existence row, then B's, where they have one; then ALL of A's slices, least significant first; then ALL of
+// B's, least significant first.  A is complete before the first slice of B arrives.
+//
+// What does not fit into registers lies in the wave's own area of the scratch (BsiMulArgs.work), in GROUP form, 31-bit groups in
+// 32-bit words, no repack: ka slices of A's image, then the accumulator P of n_out slices, 4 KiB each.  A slice is four
+// quarters of 64 quads: quad 64 q + lane holds the lane's groups 64 (4 q + t) + lane, t = 0 .. 3 -- the groups the lane owns
+// everywhere in this file -- so a lane moves a slice as four 16-byte accesses, a wave's access is 1 KiB without a gap, and a lane
+// only ever writes and later reads ITS OWN sixteen groups: program order is all the ordering there is, no fence, no atomics.
+// The state beside the walk is ex (preset to all ones); b and carry live inside one fold.  The fold:
+//   an existence row      ex &= acc
+//   A's slice i           the image's groups leave into slice i of the wave's area
+//   B's slice j           b = the image's groups; carry = 0; for i = 0 .. ka - 1 while i + j < n_out:
+//                             x = A_i & b;  p = P[i + j];  t = p ^ x;  P[i + j] = t ^ carry;  carry = (p & x) | (carry & t)
+//                         then P[ka + j] = carry where ka + j < n_out
+//   B's slice 0           reads no P: P[i] = A_i & b, P[ka] = 0
+// After j partial products P < 2^(ka + j): every slice step j reads has been written (by induction P[0 .. ka + j - 1], below
+// n_out), and its carry goes out into a slice nobody has written yet -- no clearing launch, and the carry never ripples further.
+// A slice of B that is all zero in this segment (wave-uniform: one ballot; a settled row is folded as the zeros it is) skips the
+// loop and writes P[ka + j] = 0 alone -- sparse slices and the zero bits of a constant cost next to nothing.  The skip is inside
+// the fold: the walk and its checks are untouched, every row's every segment is walked whatever the data and whatever n_out.
+// The fold runs quarter by quarter: b, carry, x, p and the next step's x and p are one quad each, so the loads of step i + 1 are
+// in flight behind the stores of step i within the launch bound.
+// Behind the sweep P[sig] & ex leaves through seg_store into matrix row n_out - 1 - sig for every sig < n_out, zeros at and above
+// ka + kb, then the ex row where there is one.  Every word of the matrix is written by exactly one wave.  A wave that refuses
+// something has written its own area of the scratch only; it reports and stores nothing.
+typedef u32 MulQuad __attribute__((ext_vector_type(4)));
+constexpr u32 kSliceQuads = kSegGroups / 4u; // 256: the quads of one slice of a wave's area
+__global__ __launch_bounds__(kSegDecodeWaves * 64, kBsiWavesPerSimd) void bsi_mul_segments_kernel(const BsiMulArgs a) {
+    __shared__ __attribute__((aligned(16))) u32 s_acc[kSegDecodeWaves][kSegGroups];
+    const u32 wave = wave_id(), lane = lane_id();
+    WaveSegment w;
+    if (!wave_segment(w, 0ull, a.n_segments, a.groups, wave)) return;
+    u32 *acc = s_acc[wave];
+    image_fill(acc, 0u, lane);
+
+    const u32 ka = a.n_slices_a, kb = a.n_slices_b, n_out = a.n_slices_out;
+    const u32 n_ex = a.exists_a + a.exists_b, n_rows = n_ex + ka + kb;
+    const u32 n_acc = ka + kb < n_out ? ka + kb : n_out; // the accumulator's slices that are ever written
+    // the lane's quad of quarter 0 of A's slice 0, and of P[0]
+    MulQuad *const image = reinterpret_cast<MulQuad *>(a.work) + w.k * (u64)(ka + n_out) * kSliceQuads + lane;
+    MulQuad *const prod = image + (u64)ka * kSliceQuads;
+
+    u32 ex[kSteps]; // group 64 s + lane
+#pragma unroll
+    for (int s = 0; s < (int)kSteps; ++s) ex[s] = kOnes31;
+    const bool ok = row_sweep(a.table, n_rows, n_rows, w, acc, lane, [&](u32 cur) {
+        if (cur < n_ex) {
+#pragma unroll
+            for (int s = 0; s < (int)kSteps; ++s) ex[s] &= acc[64 * s + (int)lane];
+            return;
+        }
+        const u32 r = cur - n_ex;
+        if (r < ka) { // A's slice r
+            MulQuad *const dst = image + (u64)r * kSliceQuads;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                MulQuad v;
+#pragma unroll
+                for (int t = 0; t < 4; ++t) v[t] = acc[64 * (4 * q + t) + (int)lane];
+                dst[64 * q] = v;
+            }
+            return;
+        }
+        // B's slice j
+        const u32 j = r - ka;
+        const u32 n_i = j >= n_out ? 0u : (ka < n_out - j ? ka : n_out - j); // the steps that land below n_out
+        const bool top = ka + j < n_out;                                     // the carry's slice exists
+        u32 any = 0u;
+#pragma unroll
+        for (int s = 0; s < (int)kSteps; ++s) any |= acc[64 * s + (int)lane];
+        if (j != 0u && __ballot(any != 0u) == 0ull) { // nothing to add: the carry slot alone
+            if (top) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) prod[(u64)(ka + j) * kSliceQuads + 64 * q] = MulQuad(0u);
+            }
+            return;
+        }
+#pragma nounroll
+        for (u32 q = 0; q < 4u; ++q) {
+            MulQuad b;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) b[t] = acc[64u * (4u * q + (u32)t) + lane];
+            const MulQuad *const A = image + 64u * q;
+            MulQuad *const P = prod + (u64)j * kSliceQuads + 64u * q;
+            MulQuad carry = MulQuad(0u);
+            if (j == 0u) {
+#pragma unroll 2
+                for (u32 i = 0; i < n_i; ++i) P[(u64)i * kSliceQuads] = A[(u64)i * kSliceQuads] & b;
+            } else if (n_i != 0u) {
+                MulQuad x = A[0], p = P[0];
+#pragma nounroll
+                for (u32 i = 0; i < n_i; ++i) {
+                    MulQuad xn = x, pn = p;
+                    if (i + 1u < n_i) { // (wave-uniform) step i + 1's loads, in front of step i's store
+                        xn = A[(u64)(i + 1u) * kSliceQuads];
+                        pn = P[(u64)(i + 1u) * kSliceQuads];
+                    }
+                    x &= b;
+                    const MulQuad t = p ^ x;
+                    P[(u64)i * kSliceQuads] = t ^ carry;
+                    carry = (p & x) | (carry & t);
+                    x = xn;
+                    p = pn;
+                }
+            }
+            if (top) P[(u64)ka * kSliceQuads] = carry;
+        }
+    });
+    if (!ok) return report_stream_error(a.ctrl, lane);
+    // the product's slices, least significant first; at and above ka + kb there is nothing but zeros
+#pragma nounroll
+    for (u32 sig = 0; sig < n_out; ++sig) {
+        const SegStore st = seg_store_setup(a.matrix + (u64)(n_out - 1u - sig) * a.n_words, a.n_words, w.seg, w.k, lane);
+        MulQuad v[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[q] = sig < n_acc ? prod[(u64)sig * kSliceQuads + 64 * q] : MulQuad(0u);
+#pragma unroll
+        for (int s = 0; s < (int)kSteps; ++s) seg_store(st, s, v[s / 4][s % 4] & ex[s]);
+    }
+    if (n_ex != 0u) {
+        const SegStore st = seg_store_setup(a.matrix + (u64)n_out * a.n_words, a.n_words, w.seg, w.k, lane);
+#pragma unroll
+        for (int s = 0; s < (int)kSteps; ++s) seg_store(st, s, ex[s]);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
 // wah_bsi_kth_indexed_device: the value of a given rank (MIN, MAX, a quantile, the k-th largest) among the rows that a set of
 // filter bitmaps selects, over the same bit-sliced attribute -- a radix select over the slices, most significant first.  The
 // value is resolved in DIGITS of kBsiKthDigitBits slices: pass p counts, for every pattern of digit p, the selected rows whose
@@ -999,6 +1129,7 @@ hipError_t launch_bitop_clauses_segments(const BitopClausesArgs &a, hipStream_t 
 hipError_t launch_bsi_range_segments(const BsiRangeArgs &a, hipStream_t s) { return launch_per_segment(bsi_range_segments_kernel, a.g.n_segments, a, s); }
 hipError_t launch_bsi_compare_segments(const BsiCompareArgs &a, hipStream_t s) { return launch_per_segment(bsi_compare_segments_kernel, a.g.n_segments, a, s); }
 hipError_t launch_bsi_arith_segments(const BsiArithArgs &a, hipStream_t s) { return launch_per_segment(bsi_arith_segments_kernel, a.n_segments, a, s); }
+hipError_t launch_bsi_mul_segments(const BsiMulArgs &a, hipStream_t s) { return launch_per_segment(bsi_mul_segments_kernel, a.n_segments, a, s); }
 hipError_t launch_bsi_kth_pass(const BsiKthArgs &a, hipStream_t s) { return launch_per_segment(bsi_kth_pass_kernel, a.n_segments, a, s); }
 
 hipError_t launch_fetch_check(const FetchArgs &a, hipStream_t s) {

@@ -282,6 +282,23 @@ struct BsiArithArgs {
 };
 hipError_t launch_bsi_arith_segments(const BsiArithArgs &a, hipStream_t s);
 
+// wah_bsi_mul_indexed_device (wah_bitop_list.hip): A * B row by row as a new bit-sliced attribute.  table: A's existence bitmap if
+// exists_a, then B's if exists_b, then ALL of A's slices, least significant first, then ALL of B's, least significant first.
+// matrix: as BsiArithArgs.  work: n_segments areas of (n_slices_a + n_slices_out) slices of kSegGroups groups each, a wave's own:
+// A's image, then the accumulator; uninitialised
+struct BsiMulArgs {
+    const BitopListOperand *table;
+    uint32_t *matrix;
+    uint32_t *work;
+    uint32_t *ctrl;
+    uint64_t n_words;                // words of one slice, a multiple of kSegWords
+    uint64_t groups, n_segments;     // of one slice
+    uint32_t n_slices_a, n_slices_b; // 1 .. 64 each
+    uint32_t n_slices_out;           // 1 .. 64
+    uint32_t exists_a, exists_b;     // 0 or 1: one more row each
+};
+hipError_t launch_bsi_mul_segments(const BsiMulArgs &a, hipStream_t s);
+
 // wah_bsi_kth_indexed_device (wah_bitop_list.hip): the value of a given rank among the rows the filters select -- a radix select
 // over the slices, kBsiKthDigitBits of them per pass, most significant digit first.  table: n_filters filter rows, then
 // n_slices slice rows, most significant first; query: kind, a, b in DEVICE memory; result: found, value, total, less, equal.

@@ -569,6 +569,51 @@ int wah_bsi_arith_indexed_device(int op, uint64_t n_words, uint64_t n_slices_a, 
                                  uint64_t *d_out_words, uint64_t *d_out_offsets, void *d_scratch, size_t scratch_bytes, void *stream);
 int wah_bsi_arith_status(void *d_scratch, uint64_t n_words, uint64_t n_slices_out, unsigned flags, void *stream);
 
+/* `A * B` ROW BY ROW over TWO bit-sliced attributes in ONE call, as a NEW bit-sliced attribute -- `price * qty > limit`, `ORDER
+ * BY price * qty DESC LIMIT k`, `SUM(extended_price * discount) WHERE ...`: schoolbook shift-and-add over the slices.  The
+ * result is an attribute like any other, as that of wah_bsi_arith_indexed_device, whose contract this one follows word for word
+ * except where stated here.  Not in the reference.
+ *   The result is (A * B) mod 2^n_slices_out, BOTH operands read as UNSIGNED, n_slices_out 1 .. 64 and the caller's choice:
+ *   n_slices_a + n_slices_b slices lose nothing (that sum may reach 128: beyond 64 the call truncates), fewer truncate, more
+ *   zero-extend.
+ *   flags: WAH_BSI_EXISTS_A | WAH_BSI_EXISTS_B, as there: the AND of the bitmaps present is the LAST row of the output, and every
+ *   output slice is ANDed with it.  rows_out = n_slices_out + (flags ? 1 : 0).
+ *   d_rows: n_slices_a + n_slices_b rows, plus one for each flag, entries as for the list call.  TABLE ORDER: A's existence
+ *   bitmap with WAH_BSI_EXISTS_A; then B's with WAH_BSI_EXISTS_B; then ALL of A's slices, least significant first; then ALL of B's
+ *   slices, least significant first.  There is NO interleaving: every slice of B meets every slice of A, so A has to be complete
+ *   before the first slice of B arrives.  (For 3 and 2 slices with both flags: XA, XB, A0, A1, A2, B0, B1.)  Nothing else
+ *   describes the table.  The operation is commutative and the call takes the operands as given; the narrower one as A keeps
+ *   the scratch small.
+ *   n_words, d_out, d_out_words, d_out_offsets, out_capacity_words: exactly those of wah_bsi_arith_indexed_device -- slices MOST
+ *   significant first, the existence bitmap last, rows_out * (n_words / 992) + 1 index entries, n_words a non-zero multiple of
+ *   992 with rows_out * n_words < 2^40.
+ * Asynchronous on `stream`, allocates nothing, never synchronises; the table is read by the device only, so a captured graph
+ * replayed after the table was overwritten in place computes the NEW rows.  One route: one wavefront per segment walks the
+ * table as the arithmetic call does; the fold of a slice of A puts the segment's 1024 groups into the wave's own area of the
+ * scratch, the fold of slice j of B adds (A & B_j) << j into an accumulator of n_slices_out slices that lies there too, one
+ * ripple carry over A's slices whose carry leaves into a slice no earlier step has written -- nothing is cleared.  A slice of B
+ * that is all zero in a segment skips that addition (a constant multiplier costs its set bits only) but is walked and checked
+ * like any other.  Behind the sweep the accumulator leaves as the result's decoded slice matrix and the one-launch compressor
+ * runs over it.
+ *   d_scratch: wah_bsi_mul_scratch_bytes(n_words, n_slices_a, n_slices_out, flags) bytes, 256-byte aligned, no initialisation:
+ *       wah_bsi_arith_scratch_bytes(n_words, n_slices_out, flags) + 4096 * (n_words / 992) * (n_slices_a + n_slices_out),
+ *   that is 1024 + round256(4 * rows_out * n_words) + round256(wah_compress_workspace_bytes(rows_out * n_words)) and 4 KiB per
+ *   segment for each slice of A and of the result.
+ * Errors the host can see come back before any HIP call, the argument checks first: a slice count (of A, of B or of the
+ * result) outside 1 .. 64, unknown flag bits, n_words == 0 or not a multiple of 992, rows_out * n_words >= 2^40, a null or
+ * misaligned table (8 B), scratch (256 B), d_out (4 B), d_out_words or d_out_offsets (8 B): WAH_ERR_ARG; too small a scratch:
+ * WAH_ERR_WORKSPACE.  Everything only the device sees is reported by wah_bsi_mul_status(), which synchronises the stream and
+ * reads the sweep's control words, then the compressor's: WAH_ERR_STREAM for everything the list call refuses in an operand,
+ * WAH_ERR_CAPACITY for too small an output (nothing is written at or behind d_out[out_capacity_words]).  EVERY row's every
+ * segment is walked and checked, the slices that contribute nothing -- above n_slices_out, or where the other operand is zero --
+ * included, so the verdict depends neither on the data nor on n_slices_out.  The output of a refused call is unspecified.
+ * wah_bsi_mul_status(NULL, ...): WAH_ERR_ARG. */
+size_t wah_bsi_mul_scratch_bytes(uint64_t n_words, uint64_t n_slices_a, uint64_t n_slices_out, unsigned flags);
+int wah_bsi_mul_indexed_device(uint64_t n_words, uint64_t n_slices_a, uint64_t n_slices_b, uint64_t n_slices_out,
+                               const wah_bitop_operand *d_rows, unsigned flags, uint32_t *d_out, uint64_t out_capacity_words,
+                               uint64_t *d_out_words, uint64_t *d_out_offsets, void *d_scratch, size_t scratch_bytes, void *stream);
+int wah_bsi_mul_status(void *d_scratch, uint64_t n_words, uint64_t n_slices_a, uint64_t n_slices_out, unsigned flags, void *stream);
+
 /* The ORDER statistics of a bit-sliced attribute in ONE call -- `MIN(price) WHERE ...`, MAX, the median or any percentile, the
  * k-th largest, the threshold of `ORDER BY price DESC LIMIT k`: the value of a given rank among the rows that a set of filter
  * bitmaps selects (O'Neil & Quass; Rinfret, O'Neil & O'Neil).  It is a radix select over the slices, most significant first, all
