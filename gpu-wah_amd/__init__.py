@@ -71,6 +71,10 @@ from .api import (  # noqa: F401
     FETCH_FIRST,
     count_device,
     count_masked_device,
+    group_sum_device,
+    GROUP_MAX_FILTERS,
+    GROUP_MAX_ROWS,
+    GROUP_MAX_ATTRS,
     positions_device,
     from_positions_device,
     from_positions_max_words,

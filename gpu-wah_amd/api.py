@@ -87,6 +87,7 @@ ABI_SYMBOLS = {
     "wah_select_scratch_bytes": (_sz, [_u64, _u64]),
     "wah_count_list_indexed_device": (_int, [_u64, _u64, _vp, _vp, _vp, _sz, _vp]),
     "wah_count_masked_indexed_device": (_int, [_u64, _u64, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
+    "wah_group_sum_indexed_device": (_int, [_u64, _u64, _vp, _u64, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "wah_positions_indexed_device": (_int, [_u64, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _sz, _vp]),
     "wah_select_status": (_int, [_vp, _vp]),
     "wah_from_positions_max_words": (_u64, [_u64, _u64, _u64]),
@@ -949,6 +950,55 @@ def count_masked_device(masks, operands, n_words, scratch=None, counts=None, che
     if check:
         _check(lib().wah_select_status(scratch.data_ptr(), sp), "count_masked")
     return counts
+
+
+GROUP_MAX_FILTERS, GROUP_MAX_ROWS, GROUP_MAX_ATTRS = 64, 8, 64  # WAH_GROUP_MAX_*
+
+
+def group_sum_device(filters, groups, operands, attr_bits, n_words, rows_per_group=1, scratch=None, group_rows=None, counts=None,
+                     sums=None, check=True):
+    """`SELECT g, COUNT(*), SUM(x), SUM(y) WHERE <filters> GROUP BY g` over bit-sliced attributes in one call, no bitmap written
+    and nothing read back (wah_group_sum_indexed_device).  The mask of group g is the AND of all `filters` rows (None or empty:
+    no filter) and of rows g * rows_per_group .. of `groups` (1 .. 8 rows per group: one per grouping attribute); `operands` are
+    the attributes' slices back to back, attribute t's attr_bits[t] slices most significant first (a host list of widths 1 .. 64
+    that add up to the operand count; at most 64 attributes).  The three tables: each a list of (stream, seg_offsets) pairs, or a
+    ready [k, 3] table (bitop_operand_table, columns.column_operand_table) -- only the device reads them; G * K <= 2^24.  Returns
+    (group_rows [G], counts [G, K], sums [G, A, 2]) as int64 device tensors: COUNT(*) per group, the set bits every group's
+    conjunction shares with every operand, and per attribute the low and high 64 bits of its sum (bit patterns: a low word at or
+    above 2^63 reads as negative).  The pad bits behind the bitmap's last word are never counted.  scratch / group_rows / counts
+    / sums: reuse these tensors (scratch as for count_device); check=False: only enqueue (the caller reads wah_select_status
+    later)."""
+    torch = _torch()
+    gt, ot = _operand_table(groups, "a group table"), _operand_table(operands)
+    dev = ot.device
+    ft = _operand_table(filters, "a filter table") if filters is not None and len(filters) else None
+    if gt.device != dev or (ft is not None and ft.device != dev):
+        raise WahError("the filter table, the group table and the operand table are on one device")
+    r = int(rows_per_group)
+    if r < 1 or gt.shape[0] % r:
+        raise WahError("the group table holds rows_per_group >= 1 rows for every group")
+    bits = [int(b) for b in attr_bits]
+    if not bits or len(bits) > GROUP_MAX_ATTRS or any(b < 1 or b > 64 for b in bits):
+        raise WahError("attr_bits: 1 .. 64 widths of 1 .. 64 slices")
+    n, f, g, k, a = int(n_words), 0 if ft is None else int(ft.shape[0]), int(gt.shape[0]) // r, int(ot.shape[0]), len(bits)
+    if scratch is None:
+        scratch = torch.empty(int(lib().wah_select_scratch_bytes(n, k)), dtype=torch.uint8, device=dev)
+    outs = []
+    for name, given, shape in (("group_rows", group_rows, (g,)), ("counts", counts, (g, k)), ("sums", sums, (g, a, 2))):
+        if given is None:
+            given = torch.empty(shape, dtype=torch.int64, device=dev)
+        elif given.dtype != torch.int64 or tuple(given.shape) != shape or not given.is_contiguous() or given.device != dev:
+            raise WahError(f"{name}: a contiguous int64 {list(shape)} tensor on the tables' device")
+        outs.append(given)
+    group_rows, counts, sums = outs
+    widths = (ctypes.c_uint8 * a)(*bits)
+    sp = _stream_ptr(torch)
+    _check(lib().wah_group_sum_indexed_device(n, f, ft.data_ptr() if f else None, g, r, gt.data_ptr(), k, ot.data_ptr(), a, widths,
+                                              group_rows.data_ptr(), counts.data_ptr(), sums.data_ptr(), scratch.data_ptr(),
+                                              scratch.numel(), sp), "wah_group_sum_indexed_device")
+    if check:
+        _check(lib().wah_select_status(scratch.data_ptr(), sp), "group_sum")
+    return group_rows, counts, sums
 
 
 def positions_device(stream, seg_offsets, n_words, first=0, limit=None, out=None, scratch=None, check=True):

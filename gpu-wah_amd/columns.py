@@ -529,6 +529,96 @@ def sum_column_where(wah, bsi, mask_stream, mask_offsets):
     return sum(int(cnt) << (n_bits - 1 - i) for i, cnt in enumerate(counts))
 
 
+def _group_tables(wah, keys, n_words_per_column, where):
+    """The tables a grouped call ANDs: (filter table [F, 3] or None, group table [G, R, 3], the keys' column counts).  The groups
+    are the Cartesian product of the keys' columns in row-major order, made by indexing on the device."""
+    import torch
+
+    n = int(n_words_per_column)
+    if not 1 <= len(keys) <= 8:
+        raise ValueError("between 1 and 8 grouping attributes")
+    tables = [column_operand_table(stream, seg_offsets, n, ids) for stream, seg_offsets, ids in keys]
+    shape = tuple(int(t.shape[0]) for t in tables)
+    dev = tables[0].device
+    picks = torch.cartesian_prod(*[torch.arange(k, device=dev) for k in shape]).view(-1, len(keys))
+    groups = torch.stack([t[picks[:, r]] for r, t in enumerate(tables)], dim=1).contiguous()
+    if where is None:
+        where = []
+    elif isinstance(where, tuple):
+        where = [where]
+    return (wah.bitop_operand_table(list(where)) if len(where) else None), groups, shape
+
+
+def aggregate_columns(wah, keys, attributes, n_words_per_column, where=None, **reuse):
+    """`SELECT g, h, COUNT(*), SUM(x), COUNT(x), SUM(y) WHERE <where> GROUP BY g, h` in ONE call that decodes no bitmap, writes
+    none and finishes nothing on the host (wah_group_sum_indexed_device).  keys: a list of 1 .. 8 (stream, seg_offsets, column_ids)
+    of equality-encoded attributes (compress_column_matrix / index_from_keys results; arguments as column_operand_table): the
+    groups are the Cartesian product of their columns, row-major.  attributes: a list of bsi_from_values / add_columns /
+    subtract_columns / multiply_columns results of the same column length; one that has an existence bitmap gets that bitmap as
+    one more attribute of 1 bit, whose "sum" is COUNT(value) (rows outside it were stored as 0 and add nothing to the sum).
+    where: None, one (stream, seg_offsets) pair or a list of them -- filter_columns / range_column / compare_columns results --,
+    all ANDed.  reuse: scratch / group_rows / counts / sums / check of api.group_sum_device.  Returns a dict:
+      rows:   int64 device tensor shaped by the keys' column counts: COUNT(*) per group;
+      sums:   per attribute an object array of that shape of Python ints, low + (high << 64): SUM(value);
+      counts: per attribute COUNT(value) as an int64 device tensor of that shape: the existence count, or `rows` itself where
+              the attribute has no existence bitmap.
+    AVG(value) is sums / counts wherever counts is not 0; it is not computed here."""
+    import numpy as np
+    import torch
+
+    n = int(n_words_per_column)
+    if not attributes:
+        raise ValueError("at least one attribute")
+    filters, groups, shape = _group_tables(wah, keys, n, where)
+    parts, bits, places = [], [], []  # places: (the attribute's place in attr_bits, its existence bitmap's or None)
+    for stream, seg_offsets, n_attr, n_bits, has_exists in attributes:
+        if n_attr != n:
+            raise ValueError("the attributes' columns are as long as the keys'")
+        parts.append(column_operand_table(stream, seg_offsets, n, list(range(n_bits + (1 if has_exists else 0)))))
+        places.append((len(bits), len(bits) + 1 if has_exists else None))
+        bits += [n_bits, 1] if has_exists else [n_bits]
+    if len(bits) > wah.GROUP_MAX_ATTRS:
+        raise ValueError("at most 64 attributes, existence bitmaps included")
+    rows, _, sums = wah.group_sum_device(filters, groups.view(-1, 3), torch.cat(parts), bits, n, rows_per_group=len(keys), **reuse)
+    rows = rows.view(shape)
+    words = sums.cpu().numpy().astype(object) & ((1 << 64) - 1)
+    whole = (words[:, :, 0] + (words[:, :, 1] << 64)).reshape(shape + (len(bits),))
+    return {"rows": rows,
+            "sums": [np.ascontiguousarray(whole[..., at]) for at, _ in places],
+            "counts": [rows if ex is None else sums[:, ex, 0].reshape(shape) for _, ex in places]}
+
+
+def extremes_by(wah, keys, bsi, n_words_per_column, where=None):
+    """`SELECT g, h, MIN(value), MAX(value) WHERE <where> GROUP BY g, h` as plumbing over wah_bsi_kth_indexed_device, which ANDs
+    its filter rows itself: per group TWO quantile calls (0/1 and 1/1) whose filters are the `where` rows, the group's own rows
+    and the attribute's existence bitmap -- G x 2 calls, each with a host read of its result; no new kernel.  keys / where as
+    aggregate_columns, bsi one bsi_from_values result of the same column length; at most 64 filter rows in all.  Returns
+    (minima, maxima): two object arrays shaped by the keys' column counts, Python ints, None where no row of the group is
+    selected."""
+    import numpy as np
+    import torch
+
+    n = int(n_words_per_column)
+    stream, seg_offsets, n_attr, n_bits, has_exists = bsi
+    if n_attr != n:
+        raise ValueError("the attribute's columns are as long as the keys'")
+    filters, groups, shape = _group_tables(wah, keys, n, where)
+    front = 0 if filters is None else int(filters.shape[0])
+    n_filters = front + len(keys) + (1 if has_exists else 0)
+    table = torch.empty((n_filters + n_bits, 3), dtype=torch.int64, device=stream.device)
+    if filters is not None:
+        table[:front] = filters
+    column_operand_table(stream, seg_offsets, n, ([n_bits] if has_exists else []) + list(range(n_bits)), out=table[front + len(keys):])
+    ends = [wah.bsi_kth_query(wah.BSI_KTH_QUANTILE, num, 1, device=stream.device) for num in (0, 1)]
+    out = [np.empty(len(groups), dtype=object) for _ in ends]
+    for g in range(len(groups)):
+        table[front: front + len(keys)] = groups[g]
+        for values, query in zip(out, ends):
+            found, value = wah.bsi_kth_device(table, query, n, n_filters)[:2].tolist()
+            values[g] = (value & ((1 << 64) - 1)) if found else None
+    return out[0].reshape(shape), out[1].reshape(shape)
+
+
 def _kth_column(wah, bsi, query, mask, reuse):
     """One wah_bsi_kth_indexed_device call over a bsi_from_values result: the filters -- the mask, then the existence bitmap --
     in front of the slices.  Returns the five result words as Python ints in 0 .. 2^64 - 1."""

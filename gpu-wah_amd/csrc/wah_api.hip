@@ -1598,6 +1598,65 @@ int wah_count_masked_indexed_device(uint64_t n_words, uint64_t n_masks, const wa
     return WAH_OK;
 }
 
+static_assert(WAH_GROUP_MAX_FILTERS == wah::kGroupMaxFilters && WAH_GROUP_MAX_ROWS == wah::kGroupMaxRows &&
+                  WAH_GROUP_MAX_ATTRS == wah::kGroupMaxAttrs, "the limits the grouped count knows");
+
+int wah_group_sum_indexed_device(uint64_t n_words, uint64_t n_filters, const wah_bitop_operand *d_filters, uint64_t n_groups,
+                                 uint64_t rows_per_group, const wah_bitop_operand *d_groups, uint64_t n_operands,
+                                 const wah_bitop_operand *d_operands, uint64_t n_attrs, const uint8_t *attr_bits, uint64_t *d_group_rows,
+                                 uint64_t *d_counts, uint64_t *d_sums, void *d_scratch, size_t scratch_bytes, void *stream) {
+    g_err[0] = 0;
+    if (!scratch_ok(d_scratch)) return refuse("bad scratch pointer", WAH_ERR_ARG);
+    if (n_filters > wah::kGroupMaxFilters || (n_filters && !d_filters) || !aligned(d_filters, 7))
+        return refuse("at most 64 filter rows in an 8-byte aligned table (null only when there is none)", WAH_ERR_ARG);
+    if (rows_per_group < 1 || rows_per_group > wah::kGroupMaxRows || n_groups < 1 || n_groups > wah::kMaxBitopListOperands ||
+        n_groups * rows_per_group > wah::kMaxBitopListOperands || n_operands < 1 || n_operands > wah::kMaxBitopListOperands ||
+        n_groups * n_operands > wah::kMaxBitopListOperands || !d_groups || !aligned(d_groups, 7) || !d_operands ||
+        !aligned(d_operands, 7) || n_words >= (1ull << 40))
+        return refuse("at least one group of 1 to 8 rows and one operand, at most 2^24 group rows and 2^24 (group, operand) pairs, in "
+                      "8-byte aligned tables, fewer than 2^40 words", WAH_ERR_ARG);
+    if (n_attrs < 1 || n_attrs > wah::kGroupMaxAttrs || !attr_bits) return refuse("between 1 and 64 attributes and their widths", WAH_ERR_ARG);
+    uint64_t slices = 0;
+    for (uint64_t t = 0; t < n_attrs; ++t) {
+        if (attr_bits[t] < 1 || attr_bits[t] > 64) return refuse("an attribute of no slice or of more than 64", WAH_ERR_ARG);
+        slices += attr_bits[t];
+    }
+    if (slices != n_operands) return refuse("the attributes' widths do not add up to n_operands", WAH_ERR_ARG);
+    if (!d_group_rows || !aligned(d_group_rows, 7) || !d_counts || !aligned(d_counts, 7) || !d_sums || !aligned(d_sums, 7))
+        return refuse("null or misaligned group rows, counts or sums", WAH_ERR_ARG);
+    const SelectLayout l = select_layout(n_words);
+    if (scratch_bytes < l.total) return refuse("scratch too small", WAH_ERR_WORKSPACE);
+    char *sc = static_cast<char *>(d_scratch);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    wah::GroupCountArgs a = {};
+    a.filters = reinterpret_cast<const wah::BitopListOperand *>(d_filters);
+    a.keys = reinterpret_cast<const wah::BitopListOperand *>(d_groups);
+    a.operands = reinterpret_cast<const wah::BitopListOperand *>(d_operands);
+    a.n_filters = (uint32_t)n_filters;
+    a.rows_per_group = (uint32_t)rows_per_group;
+    a.n_groups = (uint32_t)n_groups;
+    a.n_operands = (uint32_t)n_operands;
+    a.pad_bits = l.g.pad_bits;
+    a.groups = l.g.groups;
+    a.n_segments = l.g.n_segments;
+    a.rows = d_group_rows;
+    a.counts = d_counts;
+    a.ctrl = reinterpret_cast<uint32_t *>(sc);
+    wah::GroupFoldArgs f = {};
+    f.counts = d_counts;
+    f.sums = d_sums;
+    f.n_groups = a.n_groups;
+    f.n_operands = a.n_operands;
+    f.n_attrs = (uint32_t)n_attrs;
+    for (uint64_t t = 0; t < n_attrs; ++t) f.bits[t] = attr_bits[t];
+    hipError_t e = wah::launch_clear(sc, wah::kCtlWords * sizeof(uint32_t), s); // (read by wah_select_status)
+    if (e == hipSuccess) e = wah::launch_clear(d_group_rows, n_groups * sizeof(uint64_t), s);
+    if (e == hipSuccess) e = wah::launch_clear(d_counts, n_groups * n_operands * sizeof(uint64_t), s);
+    if (e == hipSuccess) e = wah::launch_group_sum(a, f, s);
+    if (e != hipSuccess) return refuse("grouped sum launch", WAH_ERR_HIP, e);
+    return WAH_OK;
+}
+
 int wah_positions_indexed_device(uint64_t n_words, const uint32_t *d_stream, uint64_t stream_words, const uint64_t *d_offsets,
                                  uint64_t first_rank, uint64_t *d_out, uint64_t out_capacity, uint64_t *d_out_info, void *d_scratch,
                                  size_t scratch_bytes, void *stream) {

@@ -404,6 +404,28 @@ struct CountMaskedArgs {
     uint32_t *ctrl;
 };
 hipError_t launch_count_masked(const CountMaskedArgs &a, hipStream_t s);
+// wah_group_sum_indexed_device (wah_select.hip): the masked count with a CONJUNCTION for a mask -- group g's is the AND of the
+// n_filters rows of `filters` and of rows g * rows_per_group .. of `keys` --, the conjunction's own set bits beside the counts
+// (rows: n_groups entries), and the fold of the counts of every attribute's slices into its sum.  rows and counts (n_groups x
+// n_operands, row-major) are cleared by the caller and added into; every entry of sums is stored.
+constexpr uint32_t kGroupMaxFilters = 64, kGroupMaxRows = 8, kGroupMaxAttrs = 64; // WAH_GROUP_MAX_*
+struct GroupCountArgs {
+    const BitopListOperand *filters, *keys, *operands;
+    uint32_t n_filters, rows_per_group;
+    uint32_t n_groups, n_operands; // n_groups * n_operands <= kMaxBitopListOperands
+    uint32_t pad_bits;             // as SelectCountArgs
+    uint32_t chunk;                // operands that share one image, 1 .. 64 (set by the launcher)
+    uint64_t groups, n_segments;   // (groups: G of the bitmap)
+    uint64_t *rows, *counts;
+    uint32_t *ctrl;
+};
+struct GroupFoldArgs {
+    const uint64_t *counts;
+    uint64_t *sums; // n_groups x n_attrs x (low, high)
+    uint32_t n_groups, n_operands, n_attrs;
+    uint8_t bits[kGroupMaxAttrs]; // slices of every attribute, most significant first: they add up to n_operands
+};
+hipError_t launch_group_sum(const GroupCountArgs &a, const GroupFoldArgs &f, hipStream_t s);
 // the rank table's scan: chunks of this many entries, one entry per chunk a level up
 constexpr uint32_t kRankChunk = 4096;
 hipError_t launch_select_rank_scan(uint64_t *ranks, uint64_t n_segments, uint64_t *level1, uint64_t *level2, hipStream_t s);

@@ -4,9 +4,11 @@
 // in ascending order -- SELECT rowid ... LIMIT / OFFSET).  The reference has no counterpart.
 //
 // and how many bits it shares with each of many others (wah_count_masked_indexed_device: the popcount of mask AND operand for every
-// pair of two tables -- GROUP BY under a WHERE filter, the cross-tab of two attributes).
+// pair of two tables -- GROUP BY under a WHERE filter, the cross-tab of two attributes; wah_group_sum_indexed_device: the same under
+// the AND of several rows per group, with the group's own count and the sums of bit-sliced attributes -- SELECT g, h, COUNT(*),
+// SUM(x) WHERE ... GROUP BY g, h).
 //
-// Four kinds of launches, and no workgroup of any of them waits for another:
+// Five kinds of launches, and no workgroup of any of them waits for another:
 //   select_count_kernel   (operand, segment) pairs shared out over the launch's wavefronts in contiguous runs.  The table row is checked before its index pointer
 //                         is followed, the index range (seg_range) before the stream is read through it; the segment's words
 //                         are loaded two per lane per batch of 128 (seg_load_words) and counted where they lie -- a literal is
@@ -22,6 +24,11 @@
 //                         where they lie against it, lane l keeping the l-th operand's count: a literal at group lo is popcount(x & M[lo]), a one-fill of n groups P[lo + n] - P[lo], a
 //                         zero-fill nothing.  A mask segment of one fill word needs no image: zeros count nothing, ones count
 //                         as select_count_kernel does.  LDS: 10 KiB per wavefront, 40 960 B per workgroup: four workgroups per CU.
+//   group_count_kernel /  count_masked_kernel's items, LDS and atomics with an image that is the AND of the call's filter rows and the
+//   group_fold_kernel     group's own: made conjunct by conjunct, the first one stored, the later ones ANDed in place, P and the pad
+//                         bits in one pass behind the last; a conjunct of one one-fill is skipped, one zero-fill leaves nothing to
+//                         count, and the conjunction's own bits are counted once per (group, segment).  The fold: one thread per
+//                         (group, attribute) adds the counts of the attribute's slices, shifted, in 128 bits.
 //   rank_reduce_kernel /  the exclusive prefix sum of the rank table (one u64 per segment, + 1 for the total): chunks of 4096
 //   rank_scan_kernel      entries, their totals one level up (two levels up for more than 2^24 segments), scanned there, then
 //                         every chunk scans itself in place on top of what lies in front of it.  The top level is at most
@@ -405,6 +412,275 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64) void count_masked_kernel(cons
     }
 }
 
+// ---- grouped counts under a conjunction, and their sums ----------------------------------------------------------------------
+// conjunct t of group g: the call's filter rows first, then the group's own rows
+__device__ __forceinline__ SelectRow conjunct_row(const GroupCountArgs &a, u64 g, u32 t) {
+    return t < a.n_filters ? table_row(a.filters, t) : table_row(a.keys, g * a.rows_per_group + (t - a.n_filters));
+}
+
+// a segment's words judged where they lie, as seg_mark judges them: they add up to nvalid groups, none of them empty
+__device__ __forceinline__ bool words_make_segment(const SegRange &rg, const u32 (&x0)[kSegBatches], const u32 (&x1)[kSegBatches], u32 lane) {
+    u32 grps = 0;
+    bool empty_word = false;
+#pragma unroll
+    for (int b = 0; b < kSegBatches; ++b) {
+        if (128u * b < rg.cnt) { // wave-uniform
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const bool in = 128u * b + 2u * lane + h < rg.cnt;
+                const u32 n = in ? min(word_groups(h ? x1[b] : x0[b]), 2u * kSegGroups) : 0u;
+                empty_word |= in && n == 0u;
+                grps += n;
+            }
+        }
+    }
+    return !rg.bad && wave_total32(grps) == rg.nvalid && __ballot(empty_word) == 0ull;
+}
+
+// counts[g * n_operands + j] += the set bits of (filter 0 AND .. AND filter F-1 AND group g's R rows) AND operand j, and rows[g] +=
+// the set bits of that conjunction itself.  count_masked_kernel with an image that is the AND of several rows: the same items
+// -- (group g, chunk c of a.chunk <= 64 consecutive operands, segment), ordered (g, c, segment), in the same contiguous runs --, the
+// same LDS, the same atomics when (g, c) changes and the same merge of the workgroup's run ends.  The image is made once per item,
+// conjunct by conjunct: seg_load_words, seg_mark and the sixteen steps of seg_group each, the first one STORING M[g], every later one
+// ANDing into it; P -- which lies over the mark phase's flags and so cannot be written while a conjunct is still to be marked -- and
+// the pad bits of the bitmap's last group in one pass over M behind the last conjunct.  A conjunct whose segment is one one-fill
+// changes nothing and is not decoded; one zero-fill makes the item's mask zeros, and the conjuncts behind it are judged where their
+// words lie (words_make_segment) instead of being marked; if all are one-fills the operands are counted as under kMaskOnes.  EVERY
+// segment of every filter row, group row and operand is loaded and checked under every short cut.  Only the items of chunk 0 add
+// the conjunction's own bits (p_total; 31 per group under ones, less the pad bits; nothing under zeros): once per (g, segment).
+__global__ __launch_bounds__(kSegDecodeWaves * 64) void group_count_kernel(const GroupCountArgs a) {
+    __shared__ __attribute__((aligned(16))) unsigned char s_lds[kSegDecodeWaves][kMaskedWaveLds];
+    const u32 wave = wave_id(), lane = lane_id();
+    unsigned char *flag = s_lds[wave] + kMaskedP;
+    unsigned short *P = reinterpret_cast<unsigned short *>(s_lds[wave] + kMaskedP);
+    u32 *words = reinterpret_cast<u32 *>(s_lds[wave] + kMaskedWords);
+    u32 *M = reinterpret_cast<u32 *>(s_lds[wave] + kMaskedM);
+    const u32 n_conjuncts = a.n_filters + a.rows_per_group;
+    const u64 n_chunks = ((u64)a.n_operands + a.chunk - 1) / a.chunk;
+    const u64 n_items = (u64)a.n_groups * n_chunks * a.n_segments;
+    const u64 n_waves = (u64)gridDim.x * kSegDecodeWaves;
+    const u64 per = (n_items + n_waves - 1) / n_waves;
+    const u64 w = (u64)blockIdx.x * kSegDecodeWaves + wave;
+    const u64 begin = w * per < n_items ? w * per : n_items, end = begin + per < n_items ? begin + per : n_items;
+    const u32 pad_mask = kOnes31 >> a.pad_bits;
+    u64 item = begin;
+    u64 q = begin / a.n_segments; // the items' run: g * n_chunks + c
+    u64 seg = begin - q * a.n_segments;
+    u64 g = q / n_chunks, c = q - g * n_chunks;
+    u32 jj = 0;    // the operand inside the chunk
+    u64 acc = 0;   // lane l: operand c * chunk + l under group g's conjunction
+    u64 racc = 0;  // the conjunction's own bits (chunk 0 only), wave-uniform
+    bool refused = false;
+    u32 kind = kMaskNone, p_total = 0;
+    u64 img_g = 0, img_seg = 0;
+    SelectRow orow = {}, next_orow = {};
+    SegRange next_o = {};
+    if (begin < end) {
+        next_orow = table_row(a.operands, c * a.chunk);
+        next_o = select_range(next_orow, a.groups, seg);
+    }
+#pragma nounroll
+    while (item < end) {
+        const SegRange org = next_o;
+        orow = next_orow;
+        const bool fresh = jj == 0u && (kind == kMaskNone || g != img_g || seg != img_seg); // wave-uniform
+        SegmentsArgs osa = {};
+        osa.comp = reinterpret_cast<const u32 *>((uintptr_t)orow.comp);
+        u32 x0[kSegBatches], x1[kSegBatches];
+        if (!fresh) seg_load_words(osa, org, x0, x1, lane); // (under a new image: behind its last conjunct, the registers are the conjuncts' till then)
+        // what comes behind this operand's segment: the chunk's next operand, or the next item
+        const u64 j0 = c * a.chunk;
+        const u32 jn = a.n_operands - j0 < a.chunk ? (u32)(a.n_operands - j0) : a.chunk;
+        const bool last_jj = jj + 1u == jn;
+        const bool last_seg = seg + 1 == a.n_segments;
+        const bool last_c = c + 1 == n_chunks;
+        const u64 seg_next = last_seg ? 0ull : seg + 1, q_next = last_seg ? q + 1 : q;
+        const u64 c_next = !last_seg ? c : last_c ? 0ull : c + 1, g_next = last_seg && last_c ? g + 1 : g;
+        if (!last_jj) {
+            next_orow = table_row(a.operands, j0 + jj + 1u);
+            next_o = select_range(next_orow, a.groups, seg);
+        } else if (item + 1 < end) {
+            next_orow = table_row(a.operands, c_next * a.chunk);
+            next_o = select_range(next_orow, a.groups, seg_next);
+        }
+        if (fresh) {
+            img_g = g;
+            img_seg = seg;
+            bool zeros = false, bad = false, image = false; // wave-uniform, all three
+            SelectRow crow = conjunct_row(a, g, 0);
+            SegRange next_c = select_range(crow, a.groups, seg);
+#pragma nounroll
+            for (u32 t = 0; t < n_conjuncts; ++t) {
+                const SegRange crg = next_c;
+                SegmentsArgs csa = {};
+                csa.comp = reinterpret_cast<const u32 *>((uintptr_t)crow.comp);
+                u32 m0[kSegBatches], m1[kSegBatches];
+                seg_load_words(csa, crg, m0, m1, lane);
+                if (t + 1u < n_conjuncts) { // the conjunct behind this one is on its way while this one is marked
+                    crow = conjunct_row(a, g, t + 1u);
+                    next_c = select_range(crow, a.groups, seg);
+                }
+                const u32 first = (u32)__builtin_amdgcn_readfirstlane((int)m0[0]); // lane 0 holds the segment's first word
+                if (!crg.bad && crg.cnt == 1u && (first & kFillZero) && (first & kCountMask) == crg.nvalid) {
+                    zeros |= (first & kFillOne) != kFillOne; // one fill over the segment: ones change nothing, zeros leave nothing
+                } else if (zeros || bad) {
+                    bad |= !words_make_segment(crg, m0, m1, lane); // no image will be read: checked, not decoded
+                } else if (!seg_mark(crg, m0, m1, flag, words, lane)) {
+                    bad = true;
+                } else {
+                    const uint4 fq = reinterpret_cast<const uint4 *>(flag)[lane];
+                    const u32 f[4] = {fq.x, fq.y, fq.z, fq.w};
+                    u32 before = 0xFFFFFFFFu;
+#pragma unroll
+                    for (int s = 0; s < (int)kSteps; ++s) {
+                        u32 grp = seg_group(s, f, before, words, crg.cnt, crg.nvalid, lane);
+                        const u32 k = (u32)(64 * s) + lane; // (this lane's own entry, in every conjunct)
+                        if (image) grp &= M[k];
+                        M[k] = grp;
+                    }
+                    image = true;
+                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // the next conjunct is marked over these flags and words
+                }
+            }
+            kind = bad ? kMaskBad : zeros ? kMaskZeros : image ? kMaskImage : kMaskOnes;
+            seg_load_words(osa, org, x0, x1, lane);
+            if (kind == kMaskImage) {
+                // P goes over the flags: no conjunct is left to be marked.  The bitmap's last group loses its pad bits
+                const u32 pad_group = last_seg ? org.nvalid - 1u : 0xFFFFFFFFu;
+                u32 run = 0;
+#pragma unroll
+                for (int s = 0; s < (int)kSteps; ++s) {
+                    const u32 k = (u32)(64 * s) + lane;
+                    u32 grp = M[k];
+                    if (k == pad_group) M[k] = grp &= pad_mask;
+                    const u32 cnt = (u32)__builtin_popcount(grp);
+                    const u32 incl = wave_scan_incl32(cnt);
+                    P[k] = (unsigned short)(run + incl - cnt); // at most 31 744
+                    run += (u32)__builtin_amdgcn_readlane((int)incl, 63);
+                }
+                p_total = run;
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            }
+        }
+        // the operand's words, where they lie
+        const u32 last = last_seg ? org.cnt - 1u : 0xFFFFFFFFu;
+        u32 bits = 0, grps = 0;
+        bool empty_word = false;
+        if (kind == kMaskImage) { // wave-uniform
+            u32 pos = 0; // groups covered by the batches so far
+#pragma unroll
+            for (int b = 0; b < kSegBatches; ++b) {
+                if (128u * b < org.cnt) { // wave-uniform
+                    const u32 i0 = 128u * b + 2u * lane;
+                    const bool in0 = i0 < org.cnt, in1 = i0 + 1u < org.cnt;
+                    const u32 n0 = in0 ? min(word_groups(x0[b]), 2u * kSegGroups) : 0u, n1 = in1 ? min(word_groups(x1[b]), 2u * kSegGroups) : 0u;
+                    empty_word |= (in0 && n0 == 0u) || (in1 && n1 == 0u);
+                    // a full batch of literals (dense data): consecutive positions, no scan
+                    const u32 incl = (128u * b + 128u <= org.cnt && __ballot((int)(x0[b] | x1[b]) < 0) == 0) ? 2u * lane + 2u : wave_scan_incl32(n0 + n1);
+                    const u32 lo1 = pos + incl - n1, lo0 = lo1 - n0;
+                    bits += image_bits(x0[b], n0, lo0, M, P, p_total) + image_bits(x1[b], n1, lo1, M, P, p_total);
+                    pos += (u32)__builtin_amdgcn_readlane((int)incl, 63);
+                }
+            }
+            grps = pos;
+        } else {
+            const bool ones_mask = kind == kMaskOnes;
+#pragma unroll
+            for (int b = 0; b < kSegBatches; ++b) {
+                if (128u * b < org.cnt) { // wave-uniform
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        const u32 x = h ? x1[b] : x0[b];
+                        const u32 k = 128u * b + 2u * lane + h;
+                        const bool in = k < org.cnt;
+                        const u32 n = in ? min(word_groups(x), 2u * kSegGroups) : 0u;
+                        empty_word |= in && n == 0u;
+                        const bool lit = (int)x >= 0, ones = (x & kFillOne) == kFillOne;
+                        const u32 pad = k == last ? a.pad_bits : 0u;
+                        const u32 fill_bits = ones && n ? 31u * n - pad : 0u;
+                        bits += !in || !ones_mask ? 0u : lit ? (u32)__builtin_popcount(x & (k == last ? pad_mask : kOnes31)) : fill_bits;
+                        grps += n;
+                    }
+                }
+            }
+            grps = wave_total32(grps);
+        }
+        const u32 total_bits = wave_total32(bits);
+        const bool ok = kind != kMaskBad && !org.bad && grps == org.nvalid && __ballot(empty_word) == 0ull;
+        refused |= !ok;
+        if (lane == jj && ok) acc += (u64)total_bits;
+        // COUNT(*) of the group: the conjunction's own bits in this segment, once per (g, segment)
+        if (jj == 0u && c == 0)
+            racc += kind == kMaskImage ? (u64)p_total : kind == kMaskOnes ? (u64)(31u * org.nvalid - (last_seg ? a.pad_bits : 0u)) : 0ull;
+        if (!last_jj) {
+            ++jj;
+        } else {
+            if (last_seg && item + 1 < end) { // the run goes on with another chunk or group
+                if (acc) atomicAdd(reinterpret_cast<unsigned long long *>(a.counts + g * a.n_operands + j0 + lane), (unsigned long long)acc);
+                if (lane == 0 && racc) atomicAdd(reinterpret_cast<unsigned long long *>(a.rows + g), (unsigned long long)racc);
+                acc = 0;
+                racc = 0;
+            }
+            if (item + 1 < end) {
+                q = q_next;
+                seg = seg_next;
+                g = g_next;
+                c = c_next;
+            }
+            ++item;
+            jj = 0;
+        }
+    }
+    if (refused && lane == 0) atomicOr(a.ctrl + kCtlError, kErrStream);
+    // what the workgroup's wavefronts hold for the chunks their runs end in: consecutive runs, so equal chunks are neighbours
+    __syncthreads(); // (every image is done with: the merge borrows them)
+    u64 *s_q = reinterpret_cast<u64 *>(s_lds[0] + kMaskedWords), *s_r = s_q + kSegDecodeWaves;
+    reinterpret_cast<u64 *>(M)[lane] = acc;
+    if (lane == 0) {
+        s_q[wave] = begin < end ? q : ~0ull;
+        s_r[wave] = racc;
+    }
+    __syncthreads();
+    if (wave == 0) {
+        u64 at = ~0ull, sum = 0, rsum = 0;
+        for (int v = 0; v <= kSegDecodeWaves; ++v) {
+            const u64 qv = v < kSegDecodeWaves ? s_q[v] : ~0ull;
+            if (qv != at) { // wave-uniform
+                if (at != ~0ull) {
+                    const u64 mg = at / n_chunks, mc = at - mg * n_chunks;
+                    if (sum) atomicAdd(reinterpret_cast<unsigned long long *>(a.counts + mg * a.n_operands + mc * a.chunk + lane), (unsigned long long)sum);
+                    if (lane == 0 && rsum) atomicAdd(reinterpret_cast<unsigned long long *>(a.rows + mg), (unsigned long long)rsum);
+                }
+                at = qv;
+                sum = 0;
+                rsum = 0;
+            }
+            if (v < kSegDecodeWaves) {
+                sum += reinterpret_cast<const u64 *>(s_lds[v] + kMaskedM)[lane];
+                rsum += s_r[v];
+            }
+        }
+    }
+}
+
+// sums[g][t] = the counts of attribute t's slices under group g, slice i of bits[t] weighing 2^(bits[t] - 1 - i): one thread per
+// (group, attribute).  A count is below 2^45 and an attribute has at most 64 slices: below 2^109, in 128 bits
+constexpr u32 kFoldThreads = 256;
+__global__ __launch_bounds__(kFoldThreads) void group_fold_kernel(const GroupFoldArgs a) {
+    const u64 t = (u64)blockIdx.x * kFoldThreads + threadIdx.x;
+    if (t >= (u64)a.n_groups * a.n_attrs) return;
+    const u64 g = t / a.n_attrs;
+    const u32 at = (u32)(t - g * a.n_attrs);
+    u32 first = 0;
+    for (u32 i = 0; i < at; ++i) first += a.bits[i];
+    const u32 n_bits = a.bits[at];
+    const u64 *counts = a.counts + g * a.n_operands + first;
+    unsigned __int128 sum = 0;
+    for (u32 i = 0; i < n_bits; ++i) sum += (unsigned __int128)counts[i] << (n_bits - 1u - i);
+    a.sums[2 * t] = (u64)sum;
+    a.sums[2 * t + 1] = (u64)(sum >> 64);
+}
+
 // ---- the rank scan -----------------------------------------------------------------------------------------------------------
 constexpr u32 kRankThreads = 256;
 constexpr u32 kRankPerThread = kRankChunk / kRankThreads; // 16
@@ -549,6 +825,23 @@ hipError_t launch_count_masked(const CountMaskedArgs &a, hipStream_t s) {
     while (b.chunk > 1 && items(b.chunk) < 8 * most * kSegDecodeWaves) b.chunk /= 2;
     const u64 want = (items(b.chunk) + kSegDecodeWaves - 1) / kSegDecodeWaves;
     hipLaunchKernelGGL(count_masked_kernel, dim3((unsigned)(want > most ? most : want)), dim3(kSegDecodeWaves * 64), 0, s, b);
+    return hipGetLastError();
+}
+
+// ... of the grouped count: the same grid and the same chunk rule with the groups in the masks' place, then the fold on the same
+// stream (it runs for an empty bitmap too: every sum is stored)
+hipError_t launch_group_sum(const GroupCountArgs &a, const GroupFoldArgs &f, hipStream_t s) {
+    if (a.n_segments != 0) {
+        constexpr u64 most = 256u * 4u;
+        GroupCountArgs b = a;
+        b.chunk = 64;
+        auto items = [&](u64 chunk) { return (u64)a.n_groups * ((a.n_operands + chunk - 1) / chunk) * a.n_segments; };
+        while (b.chunk > 1 && items(b.chunk) < 8 * most * kSegDecodeWaves) b.chunk /= 2;
+        const u64 want = (items(b.chunk) + kSegDecodeWaves - 1) / kSegDecodeWaves;
+        hipLaunchKernelGGL(group_count_kernel, dim3((unsigned)(want > most ? most : want)), dim3(kSegDecodeWaves * 64), 0, s, b);
+    }
+    const u64 n_sums = (u64)f.n_groups * f.n_attrs;
+    hipLaunchKernelGGL(group_fold_kernel, dim3((unsigned)((n_sums + kFoldThreads - 1) / kFoldThreads)), dim3(kFoldThreads), 0, s, f);
     return hipGetLastError();
 }
 

@@ -752,19 +752,54 @@ int wah_fetch_status(void *d_scratch, void *stream);
  * and of every operand is checked, also under an empty mask segment; a mask row is refused for what an operand row is refused for.
  * Counts of a refused call are unspecified.
  *
+ * wah_group_sum_indexed_device: the grouped aggregate under a filter -- `SELECT g, h, COUNT(*), SUM(x), SUM(y) WHERE <filter>
+ * GROUP BY g, h` over bit-sliced attributes x, y -- in one call, nothing read back and no bitmap written.  The mask of group g is
+ * a CONJUNCTION: the AND of the n_filters rows of d_filters (0 <= n_filters <= WAH_GROUP_MAX_FILTERS; d_filters may be NULL when
+ * there is none) and of rows g * rows_per_group .. (g + 1) * rows_per_group - 1 of d_groups (1 <= rows_per_group <=
+ * WAH_GROUP_MAX_ROWS: one row per grouping attribute; n_groups * rows_per_group <= WAH_BITOP_LIST_MAX_OPERANDS).  d_operands are
+ * the slices of n_attrs attributes back to back (1 <= n_attrs <= WAH_GROUP_MAX_ATTRS), attribute t's attr_bits[t] slices (1 .. 64)
+ * most significant first; attr_bits is a HOST array, copied by the call, and its entries add up to n_operands.  1 <= n_groups,
+ * 1 <= n_operands, n_groups * n_operands <= WAH_BITOP_LIST_MAX_OPERANDS.  All three tables are as for the list call (8-byte aligned,
+ * windows into column matrices allowed, rows may repeat, a stream may stand in several tables; a filter row may name the output of
+ * a clause or list call enqueued before it, as a mask row above).  Three outputs:
+ *   d_group_rows[g]: the positions p < 32 * n_words set in every row of group g's conjunction -- COUNT(*) of the group;
+ *   d_counts[g * n_operands + j]: those of them that are set in operand j as well, as the call above writes them;
+ *   d_sums[(g * n_attrs + t) * 2 + {0, 1}]: the low and the high 64 bits of the sum over attribute t's slices i of
+ *     d_counts[g][first_t + i] << (attr_bits[t] - 1 - i) -- SUM(x) over the group's rows.  A count is below 2^45, a sum below 2^109.
+ * The pad bits are never counted, whichever stream sets them, in d_group_rows as little as in d_counts.  The call clears its
+ * outputs itself.  The tables are read only by the device: the call is asynchronous on `stream`, allocates nothing and never
+ * synchronises, and a captured graph replayed after a table was overwritten in place sums the NEW selection.  n_words == 0: all
+ * zeros.  Work is shared out by (group, chunk of up to 64 consecutive operands, segment); the conjunction's segment is built ONCE
+ * per chunk in LDS, row after row -- the first row's 1024 groups stored, every later row's ANDed into them, the prefix sums of the
+ * popcounts behind the last one -- and the chunk's operands are counted against it as above; a second launch on the same stream
+ * folds the counts into the sums.  A row whose segment is one one-fill changes nothing and is not expanded; one whose segment is
+ * one zero-fill leaves nothing to count; if every row's is a one-fill the operands are counted as by the count call.  EVERY
+ * segment of every filter row, group row and operand is checked under each of these short cuts; a filter row and a group row are
+ * refused for what an operand row is refused for.  The outputs of a refused call are unspecified.
+ *
  *   d_scratch: wah_select_scratch_bytes(n_words, n_operands) bytes, 256-byte aligned, no initialisation.  The size is a
  *   multiple of 256, never 0, and grows with n_words only: the control words, one uint64 per segment of 992 words + 1 (the
  *   positions call's rank table), and one uint64 per 4096 of those for each of the two upper levels of its prefix sum.
- *   Nothing in it goes with n_operands or n_masks; one scratch serves all three calls.
+ *   Nothing in it goes with n_operands, n_masks or n_groups; one scratch serves all four calls.
  * Errors the host can see come back before any HIP call, argument checks first: a null or misaligned scratch (256 B), table,
- * d_counts, d_out or d_out_info (8 B), n_operands, n_masks or their product out of range, n_words >= 2^40: WAH_ERR_ARG; too small a scratch:
- * WAH_ERR_WORKSPACE.  wah_select_status(NULL, ...): WAH_ERR_ARG. */
+ * d_counts, d_group_rows, d_sums, d_out or d_out_info (8 B; a null d_filters only with n_filters == 0), n_operands, n_masks,
+ * n_groups or their products out of range, n_filters > WAH_GROUP_MAX_FILTERS, rows_per_group outside 1 .. WAH_GROUP_MAX_ROWS,
+ * n_attrs outside 1 .. WAH_GROUP_MAX_ATTRS, a null attr_bits, a width of 0 or above 64, widths that do not add up to n_operands,
+ * n_words >= 2^40: WAH_ERR_ARG; too small a scratch: WAH_ERR_WORKSPACE.  wah_select_status(NULL, ...): WAH_ERR_ARG. */
+#define WAH_GROUP_MAX_FILTERS 64u
+#define WAH_GROUP_MAX_ROWS 8u /* rows ANDed per group: GROUP BY up to 8 attributes */
+#define WAH_GROUP_MAX_ATTRS 64u
 size_t wah_select_scratch_bytes(uint64_t n_words, uint64_t n_operands);
 int wah_count_list_indexed_device(uint64_t n_words, uint64_t n_operands, const wah_bitop_operand *d_operands,
                                   uint64_t *d_counts, void *d_scratch, size_t scratch_bytes, void *stream);
 int wah_count_masked_indexed_device(uint64_t n_words, uint64_t n_masks, const wah_bitop_operand *d_masks,
                                     uint64_t n_operands, const wah_bitop_operand *d_operands, uint64_t *d_counts,
                                     void *d_scratch, size_t scratch_bytes, void *stream);
+int wah_group_sum_indexed_device(uint64_t n_words, uint64_t n_filters, const wah_bitop_operand *d_filters,
+                                 uint64_t n_groups, uint64_t rows_per_group, const wah_bitop_operand *d_groups,
+                                 uint64_t n_operands, const wah_bitop_operand *d_operands, uint64_t n_attrs,
+                                 const uint8_t *attr_bits, uint64_t *d_group_rows, uint64_t *d_counts, uint64_t *d_sums,
+                                 void *d_scratch, size_t scratch_bytes, void *stream);
 int wah_positions_indexed_device(uint64_t n_words, const uint32_t *d_stream, uint64_t stream_words,
                                  const uint64_t *d_offsets, uint64_t first_rank, uint64_t *d_out,
                                  uint64_t out_capacity, uint64_t *d_out_info, void *d_scratch,
