@@ -66,6 +66,9 @@ from .api import (  # noqa: F401
     BSI_KTH_DESCENDING,
     BSI_KTH_QUANTILE,
     BSI_KTH_MAX_FILTERS,
+    bsi_kth_grouped_device,
+    bsi_kth_queries,
+    BSI_KTH_GROUPED_MAX_LANES,
     fetch_device,
     FETCH_BITS,
     FETCH_FIRST,

@@ -81,6 +81,9 @@ ABI_SYMBOLS = {
     "wah_bsi_kth_scratch_bytes": (_sz, [_u64, _u64]),
     "wah_bsi_kth_indexed_device": (_int, [_u64, _u64, _u64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "wah_bsi_kth_status": (_int, [_vp, _vp]),
+    "wah_bsi_kth_grouped_scratch_bytes": (_sz, [_u64, _u64, _u64, _u64]),
+    "wah_bsi_kth_grouped_indexed_device": (_int, [_u64, _u64, _vp, _u64, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
+    "wah_bsi_kth_grouped_status": (_int, [_vp, _vp]),
     "wah_fetch_scratch_bytes": (_sz, [_u64, _u64]),
     "wah_fetch_indexed_device": (_int, [ctypes.c_uint, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _sz, _vp]),
     "wah_fetch_status": (_int, [_vp, _vp]),
@@ -866,6 +869,76 @@ def bsi_kth_device(table, query, n_words, n_filters, scratch=None, result=None, 
     if check:
         _check(lib().wah_bsi_kth_status(scratch.data_ptr(), sp), "bsi_kth")
     return result
+
+
+BSI_KTH_GROUPED_MAX_LANES = 4096  # WAH_BSI_KTH_GROUPED_MAX_LANES
+
+
+def bsi_kth_queries(queries, device="cuda:0", out=None):
+    """The query list of wah_bsi_kth_grouped_indexed_device as an int64 device tensor [Q, 3]: the many-row form of bsi_kth_query, one
+    (kind, a, b) of Python ints in 0 .. 2^64 - 1 per row, stored as their two's-complement bit patterns.  Nothing is judged here.
+    out: an existing [Q, 3] tensor to overwrite in place -- what a captured graph replayed with other queries needs."""
+    import torch
+
+    rows = []
+    for query in queries:
+        kind, a, b = query
+        words = []
+        for v in (kind, a, b):
+            v = int(v)
+            if not 0 <= v < 1 << 64:
+                raise WahError("a query word is an unsigned integer below 2^64")
+            words.append(v - (1 << 64) if v >= 1 << 63 else v)
+        rows.append(words)
+    if not rows:
+        raise WahError("at least one query")
+    t = torch.tensor(rows, dtype=torch.int64)
+    if out is None:
+        return t.to(device)
+    if out.dtype != torch.int64 or tuple(out.shape) != tuple(t.shape):
+        raise WahError("out: an int64 [Q, 3] tensor")
+    out.copy_(t)
+    return out
+
+
+def bsi_kth_grouped_device(filters, groups, slices, queries, n_words, rows_per_group=1, scratch=None, results=None, check=True):
+    """`SELECT g, MIN(x), MAX(x), median(x) WHERE <filters> GROUP BY g` over ONE bit-sliced attribute in one call, nothing read back
+    and no bitmap written (wah_bsi_kth_grouped_indexed_device): for every group and every query the value of that rank among the
+    rows that all `filters` rows (None or empty: no filter) AND rows g * rows_per_group .. of `groups` select.  The three tables as
+    group_sum_device takes them: each a list of (stream, seg_offsets) pairs, or a ready [k, 3] table (bitop_operand_table,
+    columns.column_operand_table) -- only the device reads them; `slices`: one row per slice, MOST significant first.  queries: an
+    int64 device tensor [Q, 3] (bsi_kth_queries) or a list of (kind, a, b) triples; G * Q <= 4096.  Returns the int64 device tensor
+    [G, Q, 5] of {found, value, total, less, equal} (64-bit patterns: a value at or above 2^63 reads as negative).  scratch /
+    results: reuse these tensors; check=False: only enqueue (the caller reads wah_bsi_kth_grouped_status later)."""
+    torch = _torch()
+    gt, st = _operand_table(groups, "a group table"), _operand_table(slices, "a slice table")
+    dev = st.device
+    ft = _operand_table(filters, "a filter table") if filters is not None and len(filters) else None
+    if gt.device != dev or (ft is not None and ft.device != dev):
+        raise WahError("the filter table, the group table and the slice table are on one device")
+    r = int(rows_per_group)
+    if r < 1 or r > GROUP_MAX_ROWS or gt.shape[0] % r:
+        raise WahError("the group table holds 1 .. 8 rows (rows_per_group) for every group")
+    if not isinstance(queries, torch.Tensor):
+        queries = bsi_kth_queries(queries, device=dev)
+    if queries.dtype != torch.int64 or queries.dim() != 2 or queries.shape[1] != 3 or queries.shape[0] < 1 or queries.device != dev or not queries.is_contiguous():
+        raise WahError("queries: a contiguous int64 [Q, 3] tensor, Q >= 1, on the tables' device, or a list of (kind, a, b) triples")
+    n, f, g, k, q = int(n_words), 0 if ft is None else int(ft.shape[0]), int(gt.shape[0]) // r, int(st.shape[0]), int(queries.shape[0])
+    if f > BSI_KTH_MAX_FILTERS or k > BSI_MAX_SLICES or g * q > BSI_KTH_GROUPED_MAX_LANES:
+        raise WahError("at most 64 filter rows, 64 slices and 4096 (group, query) pairs")
+    if scratch is None:
+        scratch = torch.empty(int(lib().wah_bsi_kth_grouped_scratch_bytes(n, k, g, q)), dtype=torch.uint8, device=dev)
+    if results is None:
+        results = torch.empty((g, q, 5), dtype=torch.int64, device=dev)
+    elif results.dtype != torch.int64 or tuple(results.shape) != (g, q, 5) or results.device != dev or not results.is_contiguous():
+        raise WahError("results: a contiguous int64 [G, Q, 5] tensor on the tables' device")
+    sp = _stream_ptr(torch)
+    _check(lib().wah_bsi_kth_grouped_indexed_device(n, f, ft.data_ptr() if f else None, g, r, gt.data_ptr(), k, st.data_ptr(), q,
+                                                    queries.data_ptr(), results.data_ptr(), scratch.data_ptr(), scratch.numel(), sp),
+           "wah_bsi_kth_grouped_indexed_device")
+    if check:
+        _check(lib().wah_bsi_kth_grouped_status(scratch.data_ptr(), sp), "bsi_kth_grouped")
+    return results
 
 
 FETCH_BITS, FETCH_FIRST = 0, 1  # WAH_FETCH_*

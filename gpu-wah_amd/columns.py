@@ -619,6 +619,66 @@ def extremes_by(wah, keys, bsi, n_words_per_column, where=None):
     return out[0].reshape(shape), out[1].reshape(shape)
 
 
+_QUANTILE_NAMES = {"min": (0, 1), "max": (1, 1), "median": (1, 2)}
+
+
+def _quantile_queries(wah, queries):
+    """(kind, a, b) triples of a quantiles_by query list: a triple stays, "min" / "max" / "median" and (num, den) become
+    BSI_KTH_QUANTILE queries."""
+    out = []
+    for query in queries:
+        if isinstance(query, str):
+            if query not in _QUANTILE_NAMES:
+                raise ValueError('a query is (kind, a, b), (num, den), "min", "max" or "median"')
+            query = _QUANTILE_NAMES[query]
+        query = tuple(int(v) for v in query)
+        if len(query) == 2:
+            num, den = query
+            if den <= 0 or not 0 <= num <= den:
+                raise ValueError("a quantile is num / den with 0 <= num <= den and den > 0")
+            query = (wah.BSI_KTH_QUANTILE, num, den)
+        if len(query) != 3:
+            raise ValueError('a query is (kind, a, b), (num, den), "min", "max" or "median"')
+        out.append(query)
+    if not out:
+        raise ValueError("at least one query")
+    return out
+
+
+def quantiles_by(wah, keys, bsi, n_words_per_column, queries, where=None, **reuse):
+    """`SELECT g, h, MIN(value), MAX(value), median(value), ... WHERE <where> GROUP BY g, h` in ONE call that decodes no bitmap and
+    writes none (wah_bsi_kth_grouped_indexed_device), with one host read, at the end.  keys / where as aggregate_columns (the
+    groups are the Cartesian product of the keys' columns, row-major), bsi one bsi_from_values result of the same column length;
+    its existence bitmap, when it has one, is one more filter (at most 64 filter rows in all).  queries: a list of (kind, a, b)
+    triples as api.bsi_kth_query takes them, or the shorthands "min", "max", "median" and (num, den) for the quantile num / den;
+    groups x queries <= 4096.  reuse: scratch / results / check of api.bsi_kth_grouped_device.  Returns a dict:
+      values: an object array shaped by the keys' column counts + (Q,): Python ints in 0 .. 2^64 - 1, None where the query names
+              no row of the group (an empty group, a rank beyond its rows);
+      totals, less, equal: int64 device tensors of that shape: the group's selected rows, and those below / equal to the value.
+    quantiles_by(..., ["min", "max"]) returns in values[..., 0] and values[..., 1] what extremes_by returns as its two arrays."""
+    import numpy as np
+    import torch
+
+    n = int(n_words_per_column)
+    stream, seg_offsets, n_attr, n_bits, has_exists = bsi
+    if n_attr != n:
+        raise ValueError("the attribute's columns are as long as the keys'")
+    triples = _quantile_queries(wah, queries)
+    filters, groups, shape = _group_tables(wah, keys, n, where)
+    slices = column_operand_table(stream, seg_offsets, n, list(range(n_bits + (1 if has_exists else 0))))
+    if has_exists:
+        exists = slices[n_bits:]
+        filters = exists if filters is None else torch.cat([filters, exists])
+    results = wah.bsi_kth_grouped_device(filters, groups.view(-1, 3), slices[:n_bits], triples, n, rows_per_group=len(keys), **reuse)
+    full = shape + (len(triples),)
+    host = results.cpu().numpy().astype(object) & ((1 << 64) - 1)
+    values = np.empty(host.shape[:2], dtype=object)
+    for at in np.ndindex(*values.shape):
+        values[at] = int(host[at][1]) if host[at][0] else None
+    return {"values": values.reshape(full), "totals": results[:, :, 2].reshape(full), "less": results[:, :, 3].reshape(full),
+            "equal": results[:, :, 4].reshape(full)}
+
+
 def _kth_column(wah, bsi, query, mask, reuse):
     """One wah_bsi_kth_indexed_device call over a bsi_from_values result: the filters -- the mask, then the existence bitmap --
     in front of the slices.  Returns the five result words as Python ints in 0 .. 2^64 - 1."""

@@ -1451,6 +1451,87 @@ int wah_bsi_kth_status(void *d_scratch, void *stream) {
     return read_status(d_scratch, stream);
 }
 
+// The same for every (group, query) pair of a GROUP BY at once (wah_bitop_list.hip, bsi_kth_group_pass_kernel /
+// bsi_kth_group_decide_kernel).  The scratch: control block, one decision state per select, then per pass and select its
+// histograms -- nothing of it goes with n_words.  The queries stay in device memory.
+static_assert(WAH_BSI_KTH_GROUPED_MAX_LANES == wah::kBsiKthGroupMaxSelects, "one bound");
+namespace {
+struct BsiKthGroupLayout {
+    uint32_t passes;
+    size_t state, hist, total;
+};
+BsiKthGroupLayout bsi_kth_group_layout(uint64_t n_slices, uint64_t n_groups, uint64_t n_queries) {
+    BsiKthGroupLayout l;
+    // (out of range: the size of a call that is refused anyway)
+    if (n_slices < 1 || n_slices > WAH_BSI_MAX_SLICES) n_slices = WAH_BSI_MAX_SLICES;
+    const uint64_t most = wah::kBsiKthGroupMaxSelects;
+    const uint64_t selects = n_groups < 1 || n_queries < 1 || n_groups > most || n_queries > most || n_groups * n_queries > most ? most : n_groups * n_queries;
+    l.passes = (uint32_t)ceil_div(n_slices, (uint64_t)wah::kBsiKthDigitBits);
+    l.state = wah::kCtlWords * sizeof(uint32_t);
+    l.hist = l.state + round256((size_t)selects * wah::kBsiKthStateWords * sizeof(uint64_t));
+    l.total = l.hist + round256((size_t)l.passes * selects * wah::kBsiKthGroupCopies * wah::kBsiKthBuckets * sizeof(uint64_t));
+    return l;
+}
+} // namespace
+
+size_t wah_bsi_kth_grouped_scratch_bytes(uint64_t n_words, uint64_t n_slices, uint64_t n_groups, uint64_t n_queries) {
+    (void)n_words;
+    return bsi_kth_group_layout(n_slices, n_groups, n_queries).total;
+}
+
+int wah_bsi_kth_grouped_indexed_device(uint64_t n_words, uint64_t n_filters, const wah_bitop_operand *d_filters, uint64_t n_groups,
+                                       uint64_t rows_per_group, const wah_bitop_operand *d_groups, uint64_t n_slices,
+                                       const wah_bitop_operand *d_slices, uint64_t n_queries, const uint64_t *d_queries,
+                                       uint64_t *d_results, void *d_scratch, size_t scratch_bytes, void *stream) {
+    g_err[0] = 0;
+    if (n_slices < 1 || n_slices > WAH_BSI_MAX_SLICES || n_filters > WAH_BSI_KTH_MAX_FILTERS)
+        return refuse("between 1 and 64 slices, at most 64 filters", WAH_ERR_ARG);
+    if (rows_per_group < 1 || rows_per_group > wah::kGroupMaxRows || n_groups < 1 || n_groups > wah::kBsiKthGroupMaxSelects || n_queries < 1 ||
+        n_queries > wah::kBsiKthGroupMaxSelects || n_groups * n_queries > wah::kBsiKthGroupMaxSelects ||
+        n_groups * rows_per_group > wah::kMaxBitopListOperands)
+        return refuse("at least one group of 1 to 8 rows and one query, at most 4096 (group, query) pairs", WAH_ERR_ARG);
+    if ((n_filters && !d_filters) || !aligned(d_filters, 7) || !d_groups || !aligned(d_groups, 7) || !d_slices || !aligned(d_slices, 7))
+        return refuse("null or misaligned filter (null only when there is none), group or slice table", WAH_ERR_ARG);
+    if (!d_queries || !aligned(d_queries, 7) || !d_results || !aligned(d_results, 7) || !scratch_ok(d_scratch))
+        return refuse("null or misaligned queries, results or scratch", WAH_ERR_ARG);
+    if (n_words >= (1ull << 40)) return refuse("2^40 words or more", WAH_ERR_ARG);
+    const BsiKthGroupLayout l = bsi_kth_group_layout(n_slices, n_groups, n_queries);
+    if (scratch_bytes < l.total) return refuse("scratch too small", WAH_ERR_WORKSPACE);
+    char *sc = static_cast<char *>(d_scratch);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const SegGeometry g = seg_geometry(n_words);
+    wah::BsiKthGroupArgs a = {};
+    a.filters = reinterpret_cast<const wah::BitopListOperand *>(d_filters);
+    a.keys = reinterpret_cast<const wah::BitopListOperand *>(d_groups);
+    a.slices = reinterpret_cast<const wah::BitopListOperand *>(d_slices);
+    a.queries = d_queries;
+    a.results = d_results;
+    a.state = reinterpret_cast<uint64_t *>(sc + l.state);
+    a.hist = reinterpret_cast<uint64_t *>(sc + l.hist);
+    a.ctrl = reinterpret_cast<uint32_t *>(sc);
+    a.groups = g.groups;
+    a.n_segments = g.n_segments;
+    a.n_filters = (uint32_t)n_filters;
+    a.rows_per_group = (uint32_t)rows_per_group;
+    a.n_groups = (uint32_t)n_groups;
+    a.n_queries = (uint32_t)n_queries;
+    a.n_slices = (uint32_t)n_slices;
+    a.pad_bits = g.pad_bits;
+    hipError_t e = wah::launch_clear(sc, l.total, s); // the control words (read by wah_bsi_kth_grouped_status), the states, the histograms
+    for (uint32_t p = 0; p < l.passes && e == hipSuccess; ++p) {
+        a.pass = p;
+        e = wah::launch_bsi_kth_group_pass(a, s);
+        if (e == hipSuccess) e = wah::launch_bsi_kth_group_decide(a, s);
+    }
+    if (e != hipSuccess) return refuse("grouped radix select launch", WAH_ERR_HIP, e);
+    return WAH_OK;
+}
+
+int wah_bsi_kth_grouped_status(void *d_scratch, void *stream) {
+    if (!d_scratch) return WAH_ERR_ARG;
+    return read_status(d_scratch, stream);
+}
+
 // The values of listed rows (wah_bitop_list.hip, fetch_check_kernel / fetch_items_kernel).  The scratch: control block (with the
 // item count), then the item list: one entry per 64 listed rows and one more per segment a list can change into -- it goes
 // with the list, and with the bitmap only while the list is longer than the bitmap has segments.

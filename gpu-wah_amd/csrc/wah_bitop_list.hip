@@ -9,6 +9,7 @@
 //   bsi_arith_segments_kernel      A + B, A - B row by row as a new bit-sliced attribute (wah_bsi_arith_indexed_device)
 //   bsi_mul_segments_kernel        A * B row by row as a new bit-sliced attribute (wah_bsi_mul_indexed_device)
 //   bsi_kth_pass_kernel            one pass of the radix select over such an attribute (wah_bsi_kth_indexed_device)
+//   bsi_kth_group_pass_kernel      the same pass for every (group, query) pair of a GROUP BY at once (wah_bsi_kth_grouped_indexed_device)
 //   fetch_items_kernel             the values of listed rows, one wavefront per 64 listed rows of a segment (wah_fetch_indexed_device)
 // The walk itself is written once (list_walk), and so is the sweep that keeps one row at a time in the zeroed image (row_sweep);
 // a kernel adds the state it keeps per segment, how a row is folded into it, and what it stores or counts.
@@ -1006,6 +1007,270 @@ __global__ __launch_bounds__(64) void bsi_kth_decide_kernel(const BsiKthArgs a) 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
+// wah_bsi_kth_grouped_indexed_device: the same radix select for L = n_groups x n_queries selects at once -- `SELECT g, MIN(x),
+// MAX(x), median(x) ... GROUP BY g`.  Select l = g * n_queries + q asks query q of the rows that the filters AND the R rows of
+// group g select; it has a state block and, per pass, kBsiKthGroupCopies histograms of its own in the scratch.  A pass is ONE
+// launch for all selects and the decision behind it another, so a call is as many launches as the ungrouped one's.
+//
+// The ITEMS of a pass are (segment, select) pairs, the select running fastest: item i is select i % L of segment i / L.  The grid
+// is capped at what the chip holds at once and a wavefront takes item after item, a whole grid apart, so the wavefronts
+// that run at one time hold consecutive items: the L walks of one segment's slice words are neighbours in time and find them
+// in the L2 / the memory-side cache and not in HBM (WAH_BSI_KTH_GROUP_SEGMENT_FASTEST builds the other order, for the
+// measurement in DESIGN.md alone).
+//
+// An item is bsi_kth_pass_kernel's work for its segment with the select's own prefix, in three sweeps, because list_walk wants
+// a contiguous table and the three tables are contiguous each: the filter rows (none: no sweep), the group's R rows -- both
+// folded into eq as plain ANDs --, then the slices down to the digit's end, the last one left in the image and counted.  One
+// loop runs the three (one instance of the walk in the code, not three).
+//
+// The short cut that makes clustered keys cheap: behind the second sweep eq is the selection of this segment.  If no lane holds
+// a bit of it the item has nothing to count and skips its slice sweep -- with keys sorted by group that is all but one select of
+// most segments.  What is CHECKED does not depend on it: the filter rows and the group's rows are walked, and so checked, by
+// every item in every pass, in front of the short cut; and the items of select 0 in the LAST pass, which walks every slice,
+// take no short cut, so every segment of every slice is checked once per call whatever the data and the queries are.
+// The body of an item: bsi_kth_pass_kernel's, restated as functions -- the state beside the walk, how it begins, how a row is folded
+// into it, and the count behind the sweep.  It is a COPY: with bsi_kth_pass_kernel itself written over these functions its device
+// code does not come out as it was (DESIGN.md 5.14.1 has the figures), so that kernel and bsi_kth_decide_kernel stay as they are.
+typedef u32 KthEq[kSteps];                                    // selected rows whose bits above the digit equal the prefix: group 64 s + lane
+typedef u32 KthDigit[kBsiKthInRegs ? kBsiKthInRegs : 1][kSteps]; // the digit's slices in front of its last: dg[j] is bit j + 1 of the bucket number
+// eq: the segment's valid bits, the pad bits of the bitmap's last group cleared; no slice of the digit yet
+__device__ __forceinline__ void kth_pass_begin(KthEq &eq, KthDigit &dg, const WaveSegment &w, u64 groups, u32 pad_bits, u32 lane) {
+    // (in 32 bits: the group numbers are lane constants that an item loop keeps; as 64-bit pairs they are thirty-two registers)
+    const u64 behind = groups - 1ull - w.seg * kSegGroups;
+    const u32 last_group = behind < kSegGroups ? (u32)behind : kSegGroups; // (the bitmap's last group: in its last segment only)
+#pragma unroll
+    for (int s = 0; s < (int)kSteps; ++s) {
+        const u32 g = (u32)(64 * s) + lane;
+        eq[s] = g >= w.nvalid ? 0u : g == last_group ? kOnes31 >> pad_bits : kOnes31;
+#pragma unroll
+        for (int j = 0; j < kBsiKthInRegs; ++j) dg[j][s] = 0u;
+    }
+}
+// row `cur` of a sweep over nf filter rows and then the slices down to digit_end, while the image holds it
+__device__ __forceinline__ void kth_pass_fold(KthEq &eq, KthDigit &dg, u32 cur, u32 nf, u32 ns, u32 digit_first, u32 digit_end, u64 prefix, const u32 *acc,
+                                              u32 *top, u32 lane) {
+    if (cur < nf + digit_first) {
+        // a filter: AND; a slice above the digit: AND with B or ~B by the prefix's bit
+        const u32 sig = ns - 1u - (cur - nf); // (not used for a filter)
+        const u32 flip = cur < nf || ((prefix >> (sig & 63u)) & 1ull) ? 0u : kOnes31;
+#pragma unroll
+        for (int s = 0; s < (int)kSteps; ++s) eq[s] &= acc[64 * s + (int)lane] ^ flip;
+    } else {
+        const u32 j = digit_end - 2u - (cur - nf); // 0 .. digit - 2
+#pragma unroll
+        for (int jj = 0; jj < kBsiKthInRegs; ++jj)
+            if (j == (u32)jj) {
+#pragma unroll
+                for (int s = 0; s < (int)kSteps; ++s) dg[jj][s] = acc[64 * s + (int)lane];
+            }
+        if (kBsiKthInLds && j == (u32)kBsiKthInRegs) {
+#pragma unroll
+            for (int s = 0; s < (int)kSteps; ++s) top[64 * s + (int)lane] = acc[64 * s + (int)lane];
+        }
+    }
+}
+// behind the sweep: the rows of eq whose digit is b are counted into bucket b -- bit 0 the image's slice, bit j + 1 dg[j], bit 3
+// the second image's -- and lane b's return value is the wave's bucket b.  (The counters are the caller's: declared in here they cost
+// bsi_kth_pass_kernel, when it was tried over this function, fifteen spilled registers.)
+__device__ __forceinline__ u32 kth_pass_count(u32 (&count)[kBsiKthBuckets], const KthEq &eq, const KthDigit &dg, const u32 *acc, const u32 *top, u32 lane) {
+#pragma unroll
+    for (int b = 0; b < (int)kBsiKthBuckets; ++b) count[b] = 0u;
+#pragma unroll
+    for (int s = 0; s < (int)kSteps; ++s) {
+        const u32 low = acc[64 * s + (int)lane];
+        const u32 high = kBsiKthInLds ? top[64 * s + (int)lane] : 0u;
+#pragma unroll
+        for (int hi = 0; hi < (int)(kBsiKthBuckets / 2u); ++hi) {
+            u32 e = eq[s];
+#pragma unroll
+            for (int j = 0; j < kBsiKthInRegs; ++j) e &= (hi >> j) & 1 ? dg[j][s] : ~dg[j][s];
+            if (kBsiKthInLds) e &= (hi >> kBsiKthInRegs) & 1 ? high : ~high;
+            count[2 * hi + 1] += (u32)__builtin_popcount(e & low);
+            count[2 * hi] += (u32)__builtin_popcount(e & ~low);
+        }
+    }
+    u32 mine = 0; // lane b: bucket b of the wave
+#pragma unroll
+    for (int b = 0; b < (int)kBsiKthBuckets; ++b) {
+        const u32 tot = wave_total32(count[b]);
+        if (lane == (u32)b) mine = tot;
+    }
+    return mine;
+}
+
+// The decision behind a pass, bsi_kth_decide_kernel's lane 0 restated as a function (a copy, as above), run by ONE thread: hist
+// holds the pass's sixteen counts, state / query / result are the select's own.  Pass 0 turns
+// the query into a rank from the bottom (total = the sum of the first histogram; a rank from the top is total - 1 - rank); every
+// pass picks the bucket that holds the rank, adds the buckets below it to `less`, and puts its number into the prefix; the last
+// one writes the result.  A query that names no row (found = 0) changes nothing of what is walked.
+__device__ __forceinline__ void kth_decide(const u64 *hist, u64 *state, const u64 *query, u64 *result, u32 pass, u32 ns) {
+    const u32 digit_end = min((pass + 1u) * kBsiKthDigitBits, ns);
+    const bool last = digit_end == ns;
+    u64 rank = state[kKthRank], less = state[kKthLess], total = state[kKthTotal];
+    bool found = state[kKthFound] != 0ull;
+    if (pass == 0u) {
+        total = 0;
+        for (u32 b = 0; b < kBsiKthBuckets; ++b) total += hist[b];
+        const u64 kind = query[0], qa = query[1], qb = query[2];
+        found = false;
+        if (total != 0ull) {
+            if (kind == 0ull || kind == 1ull) { // WAH_BSI_KTH_ASCENDING, WAH_BSI_KTH_DESCENDING
+                found = qa < total;
+                rank = kind == 0ull ? qa : total - 1ull - qa;
+            } else if (kind == 2ull && qb != 0ull && qa <= qb) { // WAH_BSI_KTH_QUANTILE
+                found = true;
+                rank = kth_muldiv(qa, total - 1ull, qb);
+            }
+        }
+        less = 0;
+        state[kKthTotal] = total;
+        state[kKthFound] = found ? 1ull : 0ull;
+    }
+    u64 equal = 0, bucket = 0;
+    if (found) {
+        u64 below = 0;
+        for (u32 b = 0; b < kBsiKthBuckets; ++b) {
+            const u64 h = hist[b];
+            if (rank < below + h) {
+                bucket = b;
+                equal = h;
+                break;
+            }
+            below += h;
+        }
+        rank -= below;
+        less += below;
+    }
+    const u64 prefix = state[kKthPrefix] | (bucket << (ns - digit_end));
+    state[kKthPrefix] = prefix;
+    state[kKthRank] = rank;
+    state[kKthLess] = less;
+    if (last) {
+        result[0] = found ? 1ull : 0ull;
+        result[1] = found ? prefix : 0ull;
+        result[2] = total;
+        result[3] = found ? less : 0ull;
+        result[4] = found ? equal : 0ull;
+    }
+}
+
+constexpr int kBsiKthGroupWavesPerSimd = 4;
+#ifdef WAH_BSI_KTH_GROUP_SEGMENT_FASTEST
+constexpr bool kBsiKthGroupSelectFastest = false;
+#else
+constexpr bool kBsiKthGroupSelectFastest = true;
+#endif
+
+__global__ __launch_bounds__(kSegDecodeWaves * 64, kBsiKthGroupWavesPerSimd) void bsi_kth_group_pass_kernel(const BsiKthGroupArgs a) {
+    __shared__ __attribute__((aligned(16))) u32 s_acc[kSegDecodeWaves][kSegGroups];
+    __shared__ __attribute__((aligned(16))) u32 s_top[kBsiKthInLds ? kSegDecodeWaves : 1][kSegGroups]; // the slice of bucket bit 3
+    const u32 wave = wave_id(), lane = lane_id();
+    u32 *acc = s_acc[wave];
+    u32 *top = s_top[kBsiKthInLds ? wave : 0u];
+    // (a pass's digit has a slice for the second image in every item that counts, or in none: zeroed once)
+    if (kBsiKthInLds) image_fill(top, 0u, lane);
+
+    const u32 nf = a.n_filters, ns = a.n_slices, rows_per_group = a.rows_per_group;
+    const u32 digit_first = a.pass * kBsiKthDigitBits;
+    const u32 digit_end = min(digit_first + kBsiKthDigitBits, ns);
+    const bool last_pass = digit_end == ns;
+    // An item is a pair (slow, fast) of item number i = slow * n_fast + fast; a wavefront's next item is a whole grid further on.
+    // Both numbers are kept and stepped, so the loop divides nothing.  (Wave-uniform, and said so: they stay scalars.)
+    const u32 n_selects = a.n_groups * a.n_queries;
+    const u64 n_fast = kBsiKthGroupSelectFastest ? (u64)n_selects : a.n_segments, n_slow = kBsiKthGroupSelectFastest ? a.n_segments : (u64)n_selects;
+    const u64 first = (u64)blockIdx.x * kSegDecodeWaves + uniform32(wave), stride = (u64)gridDim.x * kSegDecodeWaves;
+    const u64 step_slow = stride / n_fast, step_fast = stride % n_fast;
+    u64 slow = uniform64(first / n_fast), fast = uniform64(first % n_fast);
+    // With the select running fastest, segment s holds select l at place (l + s / R) % L and not at place l, R = the segments one
+    // trip of the grid covers.  Without that turn, and with L a divisor of the grid's wavefronts, a wavefront has ONE select in all
+    // its items: the few wavefronts of select 0 then walk all slices of all their segments one after the other in the last pass
+    // (they are the items that check, below), and those of a select whose rows are one run of segments (clustered keys) do all
+    // of its work, while the rest of the chip has finished (64 sorted groups x {MIN, MAX}, 20 slices: 1.45 ms; DESIGN.md 5.14.1
+    // has what the turn makes of it).  The turn depends on the segment alone, so a segment's L items are still its L selects; it is
+    // stepped like the item itself: turn = (slow / R) % L, left = slow % R.
+    const u64 per_trip = step_slow ? step_slow : 1ull;
+    u64 left = uniform64(slow % per_trip);
+    u32 turn = uniform32((u32)((slow / per_trip) % n_selects));
+    auto turn_on = [&]() {
+        if (++turn == n_selects) turn = 0u;
+    };
+
+#pragma nounroll
+    for (; slow < n_slow; slow += step_slow, fast += step_fast, turn_on()) { // (step_slow is R, or 0 where the grid holds every item)
+        if (fast >= n_fast) { // (at most once: both summands were below n_fast)
+            fast -= n_fast;
+            if (++left == per_trip) {
+                left = 0ull;
+                turn_on();
+            }
+            if (++slow >= n_slow) break;
+        }
+        const u64 seg = kBsiKthGroupSelectFastest ? slow : fast;
+        const u32 sel = kBsiKthGroupSelectFastest ? ((u32)fast >= turn ? (u32)fast - turn : (u32)fast + n_selects - turn) : (u32)slow;
+        const u32 group = sel / a.n_queries;
+        WaveSegment w;
+        w.k = seg;
+        w.seg = seg;
+        w.nvalid = a.groups - seg * kSegGroups < kSegGroups ? (u32)(a.groups - seg * kSegGroups) : kSegGroups;
+        const u64 prefix = uniform64(a.state[(u64)sel * kBsiKthStateWords + kKthPrefix]); // what the passes in front of this one decided for this select
+        image_fill(acc, 0u, lane); // (the item before left its last slice there)
+
+        KthEq eq;
+        KthDigit dg;
+        kth_pass_begin(eq, dg, w, a.groups, a.pad_bits, lane);
+        bool ok = true, counts = true;
+#pragma nounroll
+        for (u32 sweep = 0; sweep < 3u; ++sweep) {
+            // the sweep's table, its rows, how many of them are plain ANDs, and the digit as kth_pass_fold wants it
+            const BitopListOperand *table = sweep == 0u ? a.filters : sweep == 1u ? a.keys + (u64)group * rows_per_group : a.slices;
+            const u32 n_rows = sweep == 0u ? nf : sweep == 1u ? rows_per_group : digit_end;
+            const u32 n_and = sweep == 2u ? 0u : n_rows;
+            const u32 above = sweep == 2u ? digit_first : 0u; // slices above the digit: ANDed by the prefix
+            if (n_rows == 0u) continue; // (no filter)
+            if (sweep == 2u) {
+                u32 any = 0u;
+#pragma unroll
+                for (int s = 0; s < (int)kSteps; ++s) any |= eq[s];
+                // nothing selected here: nothing to count -- unless this item is the one that checks the slices
+                if (__ballot(any != 0u) == 0ull && !(last_pass && sel == 0u)) {
+                    counts = false;
+                    break;
+                }
+            }
+            // every row of an AND sweep is folded; the slices' last stays in the image and is counted
+            ok = row_sweep(table, n_rows, sweep == 2u ? n_rows - 1u : n_rows, w, acc, lane,
+                           [&](u32 cur) { kth_pass_fold(eq, dg, cur, n_and, ns, above, digit_end, prefix, acc, top, lane); }) && ok;
+        }
+        if (!ok) return report_stream_error(a.ctrl, lane);
+        if (!counts) continue;
+        u32 count[kBsiKthBuckets];
+    const u32 mine = kth_pass_count(count, eq, dg, acc, top, lane);
+        unsigned long long *hist = reinterpret_cast<unsigned long long *>(a.hist) +
+                                   (((u64)a.pass * n_selects + sel) * kBsiKthGroupCopies + blockIdx.x % kBsiKthGroupCopies) * kBsiKthBuckets;
+        if (lane < kBsiKthBuckets && mine != 0u) atomicAdd(hist + lane, (unsigned long long)mine);
+    }
+}
+
+// One THREAD per select behind every pass: it sums the copies of its select's histogram of the pass into its own row of the
+// LDS table and decides as bsi_kth_decide_kernel's lane 0 does; every group is asked the same queries, so select l reads query
+// l % n_queries.
+constexpr u32 kBsiKthGroupDecideThreads = 64;
+__global__ __launch_bounds__(kBsiKthGroupDecideThreads) void bsi_kth_group_decide_kernel(const BsiKthGroupArgs a) {
+    __shared__ u64 s_hist[kBsiKthGroupDecideThreads][kBsiKthBuckets + 1u]; // (+ 1: the threads' rows on different banks)
+    const u64 n_selects = (u64)a.n_groups * a.n_queries;
+    const u64 sel = (u64)blockIdx.x * kBsiKthGroupDecideThreads + threadIdx.x;
+    if (sel >= n_selects) return;
+    u64 *mine = s_hist[threadIdx.x];
+    const u64 *hist = a.hist + ((u64)a.pass * n_selects + sel) * kBsiKthGroupCopies * kBsiKthBuckets;
+    for (u32 b = 0; b < kBsiKthBuckets; ++b) {
+        u64 sum = 0;
+        for (u32 c = 0; c < kBsiKthGroupCopies; ++c) sum += hist[c * kBsiKthBuckets + b];
+        mine[b] = sum;
+    }
+    kth_decide(mine, a.state + sel * kBsiKthStateWords, a.queries + (sel % a.n_queries) * 3ull, a.results + sel * 5ull, a.pass, a.n_slices);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
 // wah_fetch_indexed_device: the values of LISTED rows -- `SELECT price, city ... LIMIT 100` behind the row numbers.  The walk is
 // the range kernel's, one table row at a time ORed into the zeroed image; what is kept beside it is not per group but per
 // LISTED ROW: lane l owns one listed row of the segment, and when the walk crosses to another table row it reads the ONE bit
@@ -1154,6 +1419,23 @@ hipError_t launch_fetch_items(const FetchArgs &a, u32 mode, hipStream_t s) {
 
 hipError_t launch_bsi_kth_decide(const BsiKthArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(bsi_kth_decide_kernel, dim3(1), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+
+// one wavefront per (segment, select) item while the chip holds them all at once; beyond that a wavefront takes several
+hipError_t launch_bsi_kth_group_pass(const BsiKthGroupArgs &a, hipStream_t s) {
+    const u64 n_items = a.n_segments * a.n_groups * a.n_queries;
+    if (n_items == 0) return hipSuccess;
+    const u64 want = (n_items + kSegDecodeWaves - 1) / kSegDecodeWaves;
+    constexpr u64 most = 256u * 4u; // CUs x resident workgroups of four wavefronts at four waves per SIMD
+    hipLaunchKernelGGL(bsi_kth_group_pass_kernel, dim3((unsigned)(want > most ? most : want)), dim3(kSegDecodeWaves * 64), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_bsi_kth_group_decide(const BsiKthGroupArgs &a, hipStream_t s) {
+    const u32 n_selects = a.n_groups * a.n_queries;
+    hipLaunchKernelGGL(bsi_kth_group_decide_kernel, dim3((n_selects + kBsiKthGroupDecideThreads - 1u) / kBsiKthGroupDecideThreads),
+                       dim3(kBsiKthGroupDecideThreads), 0, s, a);
     return hipGetLastError();
 }
 

@@ -336,6 +336,34 @@ struct BsiKthArgs {
 hipError_t launch_bsi_kth_pass(const BsiKthArgs &a, hipStream_t s);
 hipError_t launch_bsi_kth_decide(const BsiKthArgs &a, hipStream_t s);
 
+// wah_bsi_kth_grouped_indexed_device (wah_bitop_list.hip): the same radix select for n_groups x n_queries SELECTS at once --
+// select g * n_queries + q asks query q of the rows that the filters AND rows g * rows_per_group .. of `keys` select.  The three
+// tables are contiguous each; queries: n_queries x {kind, a, b}, results: five words per select, both in DEVICE memory.  state
+// (kBsiKthStateWords per select) and hist (per pass and select kBsiKthGroupCopies histograms of kBsiKthBuckets counts) lie in the
+// scratch, cleared by the caller.
+#ifndef WAH_BSI_KTH_GROUP_COPIES
+#define WAH_BSI_KTH_GROUP_COPIES 1 // (one address sees a select's segments only, not a whole pass: DESIGN.md 5.14.1)
+#endif
+constexpr uint32_t kBsiKthGroupCopies = WAH_BSI_KTH_GROUP_COPIES; // histograms per pass and select, chosen by workgroup index
+constexpr uint32_t kBsiKthGroupMaxSelects = 4096;                 // WAH_BSI_KTH_GROUPED_MAX_LANES
+struct BsiKthGroupArgs {
+    const BitopListOperand *filters, *keys, *slices;
+    const uint64_t *queries;
+    uint64_t *results;
+    uint64_t *state; // selects x kBsiKthStateWords
+    uint64_t *hist;  // passes x selects x kBsiKthGroupCopies x kBsiKthBuckets
+    uint32_t *ctrl;
+    uint64_t groups, n_segments; // (groups: G of the bitmap)
+    uint32_t n_filters;          // 0 .. 64
+    uint32_t rows_per_group;     // 1 .. kGroupMaxRows
+    uint32_t n_groups, n_queries; // n_groups * n_queries <= kBsiKthGroupMaxSelects
+    uint32_t n_slices;           // 1 .. 64
+    uint32_t pass;               // 0 .. ceil(n_slices / kBsiKthDigitBits) - 1
+    uint32_t pad_bits;           // as SelectCountArgs
+};
+hipError_t launch_bsi_kth_group_pass(const BsiKthGroupArgs &a, hipStream_t s);
+hipError_t launch_bsi_kth_group_decide(const BsiKthGroupArgs &a, hipStream_t s);
+
 // wah_fetch_indexed_device (wah_bitop_list.hip): the values of listed rows -- per listed row the one bit it has in every row
 // of the table.  rows: n_rows positions in DEVICE memory, non-descending; out: one u64 per listed row.  The check pass cuts the
 // list into ITEMS -- at most 64 consecutive listed rows of one segment -- and appends the list index of every item's first row

@@ -806,6 +806,58 @@ int wah_positions_indexed_device(uint64_t n_words, const uint32_t *d_stream, uin
                                  size_t scratch_bytes, void *stream);
 int wah_select_status(void *d_scratch, void *stream);
 
+/* The order statistics PER GROUP in ONE call -- `SELECT g, h, MIN(x), MAX(x), median(x) WHERE <filter> GROUP BY g, h`: for every
+ * group g and every query q the value of rank q among the rows that `filters AND group g's rows` select, over ONE bit-sliced
+ * attribute.  It is wah_bsi_kth_indexed_device's radix select for L = n_groups * n_queries selects ("lanes") at once.
+ *   d_filters, d_groups, d_slices: three tables as for the list call (8-byte aligned, windows into column matrices allowed, rows
+ *   may repeat, a stream may stand in several tables, the length may be a capacity, a filter row may name the not-yet-checked
+ *   output of an earlier call on the stream).  0 <= n_filters <= WAH_BSI_KTH_MAX_FILTERS (d_filters may be NULL only when there
+ *   is none); 1 <= rows_per_group <= WAH_GROUP_MAX_ROWS and group g's rows are rows g * rows_per_group .. of d_groups, exactly as
+ *   for wah_group_sum_indexed_device; 1 <= n_slices <= WAH_BSI_MAX_SLICES, the MOST significant slice first.  Group g SELECTS the
+ *   positions p < 32 * n_words set in every filter row and in every one of its rows; the pad bits of the last group are never
+ *   selected, whichever stream sets them.  Groups may overlap and may be empty.
+ *   d_queries: n_queries x {kind, a, b} uint64 in DEVICE memory, 8-byte aligned, each exactly as d_query of the ungrouped call;
+ *   every group is asked the same n_queries queries.
+ *   d_results: five uint64 per (group, query), 8-byte aligned: d_results[(g * n_queries + q) * 5 + {0 .. 4}] = {found, value,
+ *   total, less, equal}, each meaning exactly what it means in the ungrouped call.  A query is data, never an error: a rank at or
+ *   beyond total, an unknown kind, b == 0 or a > b give found = 0 and value = less = equal = 0, total is still right.  n_words ==
+ *   0: total = 0 and found = 0 everywhere.  The call writes every result row itself.
+ * Bounds: 1 <= n_groups, 1 <= n_queries, n_groups * n_queries <= WAH_BSI_KTH_GROUPED_MAX_LANES, n_groups * rows_per_group <=
+ * WAH_BITOP_LIST_MAX_OPERANDS.  The lane bound is 4096 because the scratch goes with it: sixteen passes of a 64-bit attribute
+ * are 2 KiB of histograms a lane, 8.5 MiB at 4096 lanes, cleared by every call; and 64 groups x 64 queries is more than a
+ * GROUP BY with percentiles asks for.
+ * Tables and queries are read by the device only: the call is asynchronous on `stream`, allocates nothing, reads nothing back,
+ * writes nothing of bitmap size, and a captured graph replayed after the queries and / or a table were overwritten in place
+ * answers the NEW question.  Per digit of four slices ONE launch serves all lanes and one more decides for all of them:
+ * 2 * ceil(n_slices / 4) launches and the scratch clear, whatever n_groups and n_queries are.  The work items of a pass are
+ * (segment, lane) pairs, the lane running fastest; an item ANDs the filter rows and its group's rows of that segment, and, if
+ * they select anything there, walks the slices down to the digit's end and counts as the ungrouped call does.  With keys that
+ * are clustered in row order nearly every item ends behind its group's rows.
+ *   d_scratch: wah_bsi_kth_grouped_scratch_bytes(n_words, n_slices, n_groups, n_queries) bytes, 256-byte aligned, no
+ *   initialisation.  With L = n_groups * n_queries and P = ceil(n_slices / 4) it is
+ *       1024 + round256(L * 128) + round256(P * L * 128)
+ *   bytes (round256: up to a multiple of 256): the control words, a decision state of 16 uint64 per lane, and per pass and lane
+ *   one histogram of 16 uint64.  A multiple of 256, never 0; nothing in it goes with n_words, n_filters or rows_per_group.
+ * Errors the host can see come back before any HIP call, the argument checks first: n_slices outside 1 .. 64, n_filters above
+ * 64, rows_per_group outside 1 .. WAH_GROUP_MAX_ROWS, n_groups or n_queries 0 or their product above the lane bound, a null or
+ * misaligned table (a null d_filters only with n_filters == 0), queries, results (8 B) or scratch (256 B), n_words >= 2^40:
+ * WAH_ERR_ARG; too small a scratch: WAH_ERR_WORKSPACE.  Everything only the device sees is reported by
+ * wah_bsi_kth_grouped_status(), which synchronises the stream: WAH_ERR_STREAM for everything the list call refuses in an operand.
+ * The verdict depends neither on the data nor on the queries, but HOW is weaker here than "every launch checks every row it
+ * walks": every segment of every filter row and of every group's rows is walked and checked by that group's items in every
+ * pass; every segment of every SLICE is walked and checked once per call, by the items of lane 0 in the LAST pass (which walks
+ * all slices), whether or not lane 0 selects anything there.  The other items skip the slices of a segment in which they select
+ * nothing, so a malformed slice segment is always refused, but not by every launch.  The results of a refused call are
+ * unspecified.  wah_bsi_kth_grouped_status(NULL, ...): WAH_ERR_ARG. */
+#define WAH_BSI_KTH_GROUPED_MAX_LANES 4096u
+size_t wah_bsi_kth_grouped_scratch_bytes(uint64_t n_words, uint64_t n_slices, uint64_t n_groups, uint64_t n_queries);
+int wah_bsi_kth_grouped_indexed_device(uint64_t n_words, uint64_t n_filters, const wah_bitop_operand *d_filters,
+                                       uint64_t n_groups, uint64_t rows_per_group, const wah_bitop_operand *d_groups,
+                                       uint64_t n_slices, const wah_bitop_operand *d_slices, uint64_t n_queries,
+                                       const uint64_t *d_queries, uint64_t *d_results, void *d_scratch, size_t scratch_bytes,
+                                       void *stream);
+int wah_bsi_kth_grouped_status(void *d_scratch, void *stream);
+
 /* The way INTO the index that does not go through a decoded bitmap: compressed bitmaps straight from sorted lists of row numbers
  * -- the rows of every value of a key column (one stable sort groups them), the row ids a join returns, a tombstone list.  The
  * reverse of wah_positions_indexed_device; not in the reference, whose compress() takes the decoded bitmap (compress.cu:41-209).
