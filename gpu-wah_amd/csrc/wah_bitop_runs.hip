@@ -98,6 +98,39 @@ __device__ __forceinline__ u32 runs_merge(const Load &word, const u32 (&begin)[K
     return n_out;
 }
 
+// The pad rule (include/wah.h) for the result of the bitmap's last segment, w[0 .. n): the last group has pad bits, mask holds the
+// bits of it that belong to the bitmap.  A stream of compress() has the pad bits clear and so has what runs_merge makes of such
+// operands; an operand that came from elsewhere may end in a literal that sets them or in a fill of ones that runs over them.
+// The result is compress() of the bitmap either way: the last group without its pad bits -- a literal, or, where nothing is
+// left of it, one more group of the fill of zeros in front of it.  Returns the words there are then: n - 1, n or n + 1 (the
+// K words of runs_merge have room for the one more).  One lane of the whole launch comes here, behind the loop that every lane
+// runs: that loop stays what it is.
+__device__ __forceinline__ u32 runs_clear_pad(u32 *w, u32 n, u32 mask) {
+    const u32 last = w[n - 1u];
+    if ((int)last >= 0) { // a literal
+        const u32 v = last & mask;
+        if (v != 0u) {
+            if (v != last) w[n - 1u] = v;
+            return n;
+        }
+        if (n >= 2u && (w[n - 2u] >> 30) == 2u) { // (a fill of zeros in front of it)
+            w[n - 2u] += 1u;
+            return n - 1u;
+        }
+        w[n - 1u] = kFillZero | 1u;
+        return n;
+    }
+    if ((last >> 30) != 3u) return n; // a fill of zeros
+    // a fill of ones over the last group: that group is the literal `mask` (which is neither 0 nor all ones)
+    if ((last & kCountMask) == 1u) {
+        w[n - 1u] = mask;
+        return n;
+    }
+    w[n - 1u] = last - 1u;
+    w[n] = mask;
+    return n + 1u;
+}
+
 // Pass 1: kTileSegs segments per workgroup, one per thread: the segment's result to temp[sum of the operands' offsets of the
 // segment ..) (room for as many words as the operands have there: see runs_merge), its length to seg_count, the tile's to
 // tile_total.
@@ -183,6 +216,12 @@ __global__ __launch_bounds__(kTileSegs) void bitop_runs_kernel(const BitopRunsAr
                     end[j] = (u32)(hi[j] - lo[j]);
                 }
                 n_out = runs_merge<K>([&](int j, u32 i) { return p[j][i]; }, begin, end, nvalid, op, o_rsrc, o_at, bad);
+            }
+            // (31 G - 32 n_words pad bits in the bitmap's last group: G = ceil(32 n_words / 31), so that is 31 G mod 32)
+            const u32 pad_bits = (u32)((31ull * a.groups) & 31ull);
+            if (seg + 1u == a.n_segments && pad_bits != 0u && !bad) {
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent"); // the lane reads back what it has just stored
+                n_out = runs_clear_pad(a.temp + tile_at + o_at, n_out, kOnes31 >> pad_bits);
             }
         }
         if (bad) {

@@ -485,10 +485,16 @@ struct IndexedSource {
             g.x[s] = ((ga[s] & gb & k_ab) | (ga[s] & ~gb & k_a_nb) | (~ga[s] & gb & k_na_b)) & kOnes31;
         }
         if (nvalid != kSegGroups) { // the bitmap's last, short segment: absent groups become throw-away literals (regroup())
+            // ... and its last group loses the pad bits (include/wah.h, the pad rule; only a short segment has any): an operand
+            // that compress() did not write may set them -- a last literal, a fill of ones that runs over the group
+            const u32 pad_mask = kOnes31 >> (u32)((31ull * sa.groups) & 31ull);
             u32 lv = lane;
             asm volatile("" : "+v"(lv));
 #pragma unroll
-            for (int s = 0; s < (int)kSteps; ++s) g.x[s] = 64u * s + lv < nvalid ? g.x[s] : kAbsentGroup;
+            for (int s = 0; s < (int)kSteps; ++s) {
+                const u32 i = 64u * s + lv;
+                g.x[s] = i < nvalid ? (i + 1u == nvalid ? g.x[s] & pad_mask : g.x[s]) : kAbsentGroup;
+            }
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // the areas are written again by pass 2 / the next segment
     }

@@ -261,6 +261,10 @@ int wah_decompress_segments_device(const uint32_t *d_comp, uint64_t c_words, con
  * then on.  One scan of the stream (as wah_decompress_scan_device: d_out_info = [decoded words, groups]) + one pass
  * that places every word.  A stream in which a fill crosses a 1024-group boundary, or that contains an empty fill,
  * has no such index: WAH_ERR_STREAM from wah_decompress_status(); too few entries: WAH_ERR_CAPACITY.
+ * Nothing else is asked of the stream: an indexed call accepts EXACTLY the streams that have an index, whatever the
+ * maximality of their fills -- fills that could have been longer, neighbouring fills of one kind, literals 0 / 0x7FFFFFFF
+ * that could have been fills, a whole segment written as 1024 one-group words, a last group whose pad bits are set (what
+ * wah_validate_device counts in [3] and [5]).  See "Operands of the indexed calls" at wah_bitop_indexed_device.
  * Workspace: wah_decompress_workspace_bytes(c_words, 0). */
 int wah_build_index_device(const uint32_t *d_comp, uint64_t c_words, uint64_t *d_segment_offsets, uint64_t offsets_capacity,
                            uint64_t *d_out_info, void *d_workspace, size_t workspace_bytes, void *stream);
@@ -331,8 +335,16 @@ int wah_bitop_status(void *d_scratch, uint64_t n_words, uint64_t a_words, uint64
  * segment by segment through their indexes, combined group by group in registers, and ONE decoded bitmap is written,
  * which the compress kernel then reads -- no scan of the operands, no second read of them, half the intermediate
  * traffic of wah_bitop_device.  d_out_offsets (may be NULL) receives the result's own segment index, so results can
- * be combined further.  Operands must be streams of compress() for bitmaps of n_words words (anything else:
- * WAH_ERR_STREAM from wah_bitop_indexed_status()).
+ * be combined further.
+ * Operands of the indexed calls (this one and every call below that takes a stream with its segment index, or a table of
+ * such): an operand is accepted exactly when it has an index for a bitmap of n_words words -- every segment's words
+ * (offsets[s] .. offsets[s + 1]) make up exactly the segment's groups, 1024 or what is left in the last one, and no fill is
+ * empty; anything else is WAH_ERR_STREAM from the call's status function.  That is what compress() writes and what
+ * wah_build_index_device accepts, and no more: fills need not be maximal, neighbouring fills may be of one kind, a zero or
+ * all-ones group may be a literal, a segment may be 1024 one-group words.  A result that is a compressed bitmap is always in
+ * compress()'s form, word for word, whatever form the operands had.  Pad bits never matter, on any route: the 31 G - 32 n_words
+ * bits of the last group that lie behind the bitmap may be set in an operand (a last literal, a fill of ones that runs over
+ * the group); they are not part of the bitmap, are never counted, listed or fetched, and are clear in every result.
  *   d_scratch: wah_bitop_indexed_scratch_bytes(n_words) bytes, 256-byte aligned. */
 size_t wah_bitop_indexed_scratch_bytes(uint64_t n_words);
 int wah_bitop_indexed_device(int op, uint64_t n_words, const uint32_t *d_a, uint64_t a_words, const uint64_t *d_a_offsets,
