@@ -81,6 +81,10 @@ from .api import (  # noqa: F401
     positions_device,
     from_positions_device,
     from_positions_max_words,
+    splice_device,
+    splice_pieces,
+    splice_max_words,
+    SPLICE_MAX_PIECES,
     bsi_build_device,
     merge_fills_device,
     StreamReport,

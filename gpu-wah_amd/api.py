@@ -97,6 +97,10 @@ ABI_SYMBOLS = {
     "wah_from_positions_scratch_bytes": (_sz, [_u64, _u64]),
     "wah_from_positions_device": (_int, [_u64, _u64, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
     "wah_from_positions_status": (_int, [_vp, _vp]),
+    "wah_splice_max_words": (_u64, [_u64, _u64, _u64, _u64]),
+    "wah_splice_scratch_bytes": (_sz, [_u64, _u64, _u64]),
+    "wah_splice_indexed_device": (_int, [_u64, _u64, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
+    "wah_splice_status": (_int, [_vp, _vp]),
     "wah_bsi_build_scratch_bytes": (_sz, [_u64, _u64]),
     "wah_bsi_build_device": (_int, [_u64, _u64, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
     "wah_bsi_build_status": (_int, [_vp, _u64, _u64, _vp]),
@@ -1159,6 +1163,66 @@ def from_positions_device(rows, list_ends, n_words, scratch=None, out=None, out_
     if not check:
         return out, count, out_offsets
     _check(lib().wah_from_positions_status(scratch.data_ptr(), sp), "from_positions")
+    return out[: int(count.item())], out_offsets[: k * n_seg + 1]
+
+
+SPLICE_MAX_PIECES = 1 << 16  # WAH_SPLICE_MAX_PIECES
+
+
+def splice_pieces(pieces, device=None):
+    """The wah_splice_piece array of a list of (n_words, first_row, n_rows) triples as an int64 device tensor of shape
+    [n_pieces, 3] (splice_device)."""
+    torch = _torch()
+    rows = [(int(n), int(f), int(r)) for n, f, r in pieces]
+    if not rows or any(v < 0 for row in rows for v in row):
+        raise WahError("at least one piece of (n_words, first_row, n_rows), none of them negative")
+    return torch.tensor(rows, dtype=torch.int64, device="cuda" if device is None else device)
+
+
+def splice_max_words(n_words_out, n_columns, n_pieces, source_words):
+    return int(lib().wah_splice_max_words(int(n_words_out), int(n_columns), int(n_pieces), int(source_words)))
+
+
+def splice_device(pieces, table, n_columns, n_words_out, source_words=None, scratch=None, out=None, out_offsets=None, check=True):
+    """Row ranges of indexed compressed bitmaps concatenated into new ones, at any bit offset, for n_columns columns at once and
+    without a decoded bitmap (wah_splice_indexed_device).  pieces: the [n_pieces, 3] int64 table of splice_pieces, or a list of
+    (n_words, first_row, n_rows) triples; table: the [n_pieces * n_columns, 3] operand table (bitop_operand_table,
+    columns.column_operand_table), piece-major: row p * n_columns + c is column c of piece p -- only the device reads either.
+    Output column c holds, piece after piece, positions first_row .. first_row + n_rows of the pieces' column c, and zeros behind
+    them, in n_words_out words.  Returns (stream, seg_offsets): the columns' compress() streams back to back and the
+    n_columns * S + 1 entries of their segment index (S = segments of one output bitmap), as from_positions_device.
+    source_words: an upper bound on the words of the source segments that are read, which sizes a default out by
+    wah_splice_max_words (None: the bound that always holds, n_columns * wah_max_compressed_words(n_words_out));
+    scratch / out / out_offsets: reuse these tensors; check=False: only enqueue and return (out, count tensor, out_offsets)."""
+    torch = _torch()
+    table = _operand_table(table)
+    dev = table.device
+    if not isinstance(pieces, torch.Tensor):
+        pieces = splice_pieces(pieces, dev)
+    if pieces.dtype != torch.int64 or pieces.dim() != 2 or pieces.shape[1] != 3 or pieces.shape[0] < 1 or not pieces.is_contiguous() or pieces.device != dev:
+        raise WahError("pieces: a contiguous int64 tensor of shape [n_pieces, 3] on the table's device")
+    n, k, p = int(n_words_out), int(n_columns), int(pieces.shape[0])
+    if k < 1 or int(table.shape[0]) != p * k:
+        raise WahError("the operand table holds n_columns >= 1 rows for every piece")
+    n_seg = (max_compressed_words(n) + 1023) // 1024
+    if scratch is None:
+        scratch = torch.empty(int(lib().wah_splice_scratch_bytes(n, k, p)), dtype=torch.uint8, device=dev)
+    if out is None:
+        words = k * max_compressed_words(n) if source_words is None else splice_max_words(n, k, p, source_words)
+        out = torch.empty(max(words, 1), dtype=torch.int32, device=dev)
+    else:
+        _as_words(torch, out)
+    if out_offsets is None:
+        out_offsets = torch.empty(k * n_seg + 1, dtype=torch.int64, device=dev)
+    elif out_offsets.dtype != torch.int64 or out_offsets.numel() < k * n_seg + 1 or not out_offsets.is_contiguous() or out_offsets.device != dev:
+        raise WahError("out_offsets: a contiguous int64 tensor of n_columns * segments + 1 entries on the table's device")
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    sp = _stream_ptr(torch)
+    _check(lib().wah_splice_indexed_device(n, k, p, pieces.data_ptr(), table.data_ptr(), out.data_ptr(), out.numel(), count.data_ptr(),
+                                           out_offsets.data_ptr(), scratch.data_ptr(), scratch.numel(), sp), "wah_splice_indexed_device")
+    if not check:
+        return out, count, out_offsets
+    _check(lib().wah_splice_status(scratch.data_ptr(), sp), "splice")
     return out[: int(count.item())], out_offsets[: k * n_seg + 1]
 
 

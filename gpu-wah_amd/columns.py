@@ -822,6 +822,82 @@ def select_values(wah, predicates, n_words_per_column, attributes, first=0, limi
     return rows, fetched, matching
 
 
+def _index_columns(seg_offsets, n_words_per_column):
+    """The columns of a column-matrix index: its entries but the last one, over the segments of one column."""
+    n = int(n_words_per_column)
+    if n % SEGMENT_WORDS or n <= 0:
+        raise ValueError("columns of a column matrix are a multiple of 992 words long")
+    return (int(seg_offsets.numel()) - 1) // (n // SEGMENT_WORDS)
+
+
+def splice_columns(wah, parts, n_words_per_column=None, **reuse):
+    """Row ranges of column matrices concatenated into a new column matrix in one call that decodes no bitmap
+    (wah_splice_indexed_device): parts is a list of ((stream, seg_offsets, n_words_per_column), first_row, n_rows), each naming
+    rows [first_row, first_row + n_rows) of ALL columns of a compress_column_matrix / index_from_keys / bsi_from_values result;
+    the parts have equal column counts and may differ in column length.  Column c of the result holds the parts' rows of their
+    column c one after the other, and zeros behind them.  n_words_per_column defaults to the rows rounded up to a multiple of
+    992 words.  reuse: source_words / scratch / out / out_offsets / check of api.splice_device (check=False returns the whole
+    output buffer).  Returns (stream, seg_offsets, n_words_per_column), which go in as the arguments of the same names of
+    column_operand_table and everything built on it."""
+    import torch
+
+    if not parts:
+        raise ValueError("at least one part")
+    pieces, tables, counts, rows = [], [], set(), 0
+    for (stream, seg_offsets, n), first_row, n_rows in parts:
+        first_row, n_rows = int(first_row), int(n_rows)
+        if first_row < 0 or n_rows < 0 or first_row + n_rows > 32 * int(n):
+            raise ValueError("a part's rows lie inside its columns")
+        k = _index_columns(seg_offsets, n)
+        counts.add(k)
+        pieces.append((int(n), first_row, n_rows))
+        tables.append(column_operand_table(stream, seg_offsets, n, torch.arange(max(k, 1), dtype=torch.int64, device=stream.device)))
+        rows += n_rows
+    if len(counts) != 1 or min(counts) < 1:
+        raise ValueError("the parts have one column count, at least 1")
+    if n_words_per_column is None:
+        n_words_per_column = max(-(-((rows + 31) // 32) // SEGMENT_WORDS), 1) * SEGMENT_WORDS
+    n_out = int(n_words_per_column)
+    if n_out % SEGMENT_WORDS or n_out <= 0 or 32 * n_out < rows:
+        raise ValueError("columns are a multiple of 992 words long and hold every row")
+    check = reuse.pop("check", True)
+    table = torch.cat(tables)
+    got = wah.splice_device(wah.splice_pieces(pieces, table.device), table, counts.pop(), n_out, check=check, **reuse)
+    if not check:
+        return got[0], got[2], n_out
+    return got[0], got[1], n_out
+
+
+def _same_kind(index, batch):
+    """What append_rows asks of its two indexes; returns the tail of the result's tuple."""
+    if len(index) not in (3, 5) or len(index) != len(batch):
+        raise ValueError("index and batch are both index_from_keys results or both bsi_from_values results")
+    if _index_columns(index[1], index[2]) != _index_columns(batch[1], batch[2]):
+        raise ValueError("index and batch differ in their column count")
+    if tuple(index[3:]) != tuple(batch[3:]):
+        raise ValueError("index and batch differ in n_bits or has_exists")
+    return tuple(index[3:])
+
+
+def append_rows(wah, index, rows, batch, batch_rows):
+    """INSERT of a batch in one call: the first `rows` rows of `index` followed by the first batch_rows rows of `batch`, column by
+    column (splice_columns).  index and batch are both the 3-tuple of index_from_keys or both the 5-tuple of bsi_from_values (or
+    results of this function and slice_rows); ValueError when they differ in kind, in their column count, or in n_bits /
+    has_exists.  Returns the same kind of tuple, its column length the rows rounded up to a multiple of 992 words; it goes into
+    every call that takes the inputs."""
+    tail = _same_kind(index, batch)
+    return splice_columns(wah, [(tuple(index[:3]), 0, rows), (tuple(batch[:3]), 0, batch_rows)]) + tail
+
+
+def slice_rows(wah, index, first, n_rows):
+    """Rows [first, first + n_rows) of every column of an index as an index of its own (splice_columns with one part): a
+    partition, the newest day, one GPU's share of the rows.  index: the 3-tuple of index_from_keys or the 5-tuple of
+    bsi_from_values; returns the same kind of tuple, row `first` of the input being row 0 of the result."""
+    if len(index) not in (3, 5):
+        raise ValueError("index is an index_from_keys result or a bsi_from_values result")
+    return splice_columns(wah, [(tuple(index[:3]), first, n_rows)]) + tuple(index[3:])
+
+
 def compress_column_ranges(compressor, flat, lengths, wait=True):
     """Columns of DIFFERENT lengths (each a multiple of 992 words) stored back to back in `flat`: still one launch.
     Returns (stream, column_offsets) like compress_column_matrix: column c is stream[column_offsets[c] :

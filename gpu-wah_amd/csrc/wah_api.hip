@@ -1872,6 +1872,95 @@ int wah_from_positions_status(void *d_scratch, void *stream) {
     return read_status(d_scratch, stream);
 }
 
+// Row ranges of indexed bitmaps concatenated into new ones (splice_segments_kernel, wah_bitop_list.hip).  The scratch: control
+// block, the n_pieces + 1 running starts the check launch leaves, then the two upper levels of the prefix sum over the
+// n_columns x S + 1 index entries, as from_positions_layout.
+namespace {
+struct SpliceLayout {
+    uint64_t groups, n_segments, n_items;
+    size_t starts, level1, level2, total;
+};
+SpliceLayout splice_layout(uint64_t n_words_out, uint64_t n_columns, uint64_t n_pieces) {
+    SpliceLayout l;
+    const SegGeometry g = seg_geometry(n_words_out);
+    l.groups = g.groups;
+    l.n_segments = g.n_segments;
+    l.n_items = n_columns * l.n_segments;
+    const uint64_t n0 = l.n_items + 1, n1 = ceil_div(n0, (uint64_t)wah::kRankChunk), n2 = ceil_div(n1, (uint64_t)wah::kRankChunk);
+    size_t at = wah::kCtlWords * sizeof(uint32_t);
+    l.starts = at;
+    at += round256((n_pieces + 1) * sizeof(uint64_t));
+    l.level1 = at;
+    at += round256(n1 * sizeof(uint64_t));
+    l.level2 = at;
+    at += round256(n2 * sizeof(uint64_t));
+    l.total = at;
+    return l;
+}
+} // namespace
+
+static_assert(sizeof(wah_splice_piece) == 24 && sizeof(wah::SplicePiece) == 24 && WAH_SPLICE_MAX_PIECES == wah::kSpliceMaxPieces, "one piece, one bound");
+
+uint64_t wah_splice_max_words(uint64_t n_words_out, uint64_t n_columns, uint64_t n_pieces, uint64_t source_words) {
+    const SegGeometry g = seg_geometry(n_words_out);
+    const unsigned __int128 columns = n_columns;
+    const unsigned __int128 all_literals = columns * g.groups;
+    const unsigned __int128 by_words = columns * (g.n_segments + 1) + 2 * columns * n_pieces + 2 * (unsigned __int128)source_words;
+    const unsigned __int128 m = all_literals < by_words ? all_literals : by_words;
+    return m > (unsigned __int128)~0ull ? ~0ull : (uint64_t)m;
+}
+
+size_t wah_splice_scratch_bytes(uint64_t n_words_out, uint64_t n_columns, uint64_t n_pieces) {
+    return splice_layout(n_words_out, n_columns, n_pieces).total;
+}
+
+int wah_splice_indexed_device(uint64_t n_words_out, uint64_t n_columns, uint64_t n_pieces, const wah_splice_piece *d_pieces,
+                              const wah_bitop_operand *d_operands, uint32_t *d_out, uint64_t out_capacity_words, uint64_t *d_out_words,
+                              uint64_t *d_out_offsets, void *d_scratch, size_t scratch_bytes, void *stream) {
+    g_err[0] = 0;
+    if (n_columns < 1 || n_columns > wah::kMaxBitopListOperands || n_pieces < 1 || n_pieces > wah::kSpliceMaxPieces ||
+        n_pieces * n_columns > wah::kMaxBitopListOperands || n_words_out == 0 || n_words_out >= (1ull << 40))
+        return refuse("between 1 and 2^24 columns, between 1 and 2^16 pieces, at most 2^24 table entries, between 1 and 2^40 - 1 words",
+                      WAH_ERR_ARG);
+    const SpliceLayout l = splice_layout(n_words_out, n_columns, n_pieces);
+    if (l.n_items >= (1ull << 31)) return refuse("columns x segments of 992 words: fewer than 2^31", WAH_ERR_ARG);
+    if (!scratch_ok(d_scratch)) return refuse("bad scratch pointer", WAH_ERR_ARG);
+    if (!d_pieces || !aligned(d_pieces, 7) || !d_operands || !aligned(d_operands, 7))
+        return refuse("null or misaligned pieces or operand table", WAH_ERR_ARG);
+    if (!d_out || !aligned(d_out, 3) || !d_out_words || !aligned(d_out_words, 7) || !d_out_offsets || !aligned(d_out_offsets, 7))
+        return refuse("null or misaligned output", WAH_ERR_ARG);
+    if (scratch_bytes < l.total) return refuse("scratch too small", WAH_ERR_WORKSPACE);
+    char *sc = static_cast<char *>(d_scratch);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    wah::SpliceArgs a = {};
+    a.pieces = reinterpret_cast<const wah::SplicePiece *>(d_pieces);
+    a.table = reinterpret_cast<const wah::BitopListOperand *>(d_operands);
+    a.starts = reinterpret_cast<uint64_t *>(sc + l.starts);
+    a.n_pieces = n_pieces;
+    a.n_columns = n_columns;
+    a.n_bits = 32u * n_words_out;
+    a.groups = l.groups;
+    a.n_segments = l.n_segments;
+    a.out = d_out;
+    a.out_capacity = out_capacity_words;
+    a.out_words = d_out_words;
+    a.offsets = d_out_offsets;
+    a.ctrl = reinterpret_cast<uint32_t *>(sc);
+    hipError_t e = wah::launch_clear(sc, wah::kCtlWords * sizeof(uint32_t), s); // (read by wah_splice_status)
+    if (e == hipSuccess) e = wah::launch_splice_check(a, s);
+    if (e == hipSuccess) e = wah::launch_splice_segments(a, false, s);
+    if (e == hipSuccess)
+        e = wah::launch_select_rank_scan(d_out_offsets, l.n_items, reinterpret_cast<uint64_t *>(sc + l.level1), reinterpret_cast<uint64_t *>(sc + l.level2), s);
+    if (e == hipSuccess) e = wah::launch_splice_segments(a, true, s);
+    if (e != hipSuccess) return refuse("splice launch", WAH_ERR_HIP, e);
+    return WAH_OK;
+}
+
+int wah_splice_status(void *d_scratch, void *stream) {
+    if (!d_scratch) return WAH_ERR_ARG;
+    return read_status(d_scratch, stream);
+}
+
 // A bit-sliced index from a column of values (wah_bsi_build.hip): the transpose writes the decoded slice matrix into the scratch,
 // the compress passes run over it as over any column matrix.  The scratch: [control words][slice matrix][compress workspace] --
 // the layout of every call that leaves a whole attribute (wah_bsi_arith_indexed_device below: its sweep writes the matrix).

@@ -11,6 +11,8 @@
 //   bsi_kth_pass_kernel            one pass of the radix select over such an attribute (wah_bsi_kth_indexed_device)
 //   bsi_kth_group_pass_kernel      the same pass for every (group, query) pair of a GROUP BY at once (wah_bsi_kth_grouped_indexed_device)
 //   fetch_items_kernel             the values of listed rows, one wavefront per 64 listed rows of a segment (wah_fetch_indexed_device)
+//   splice_segments_kernel         row ranges of indexed bitmaps concatenated into new ones, one wavefront per (column, output
+//                                  segment) (wah_splice_indexed_device)
 // The walk itself is written once (list_walk), and so is the sweep that keeps one row at a time in the zeroed image (row_sweep);
 // a kernel adds the state it keeps per segment, how a row is folded into it, and what it stores or counts.
 //
@@ -32,6 +34,7 @@
 // Every group of the segment is covered by exactly one word of an operand (the scan's positions are disjoint whatever the words
 // say), so no two lanes touch one accumulator group for one operand: no atomics.  A segment's cost goes with the words the
 // operands hold there plus the length of the fills that change the result, not with n_operands x 1024 groups.
+#include "wah_image_words.hpp"
 #include "wah_segdecode.hpp"
 
 namespace wah {
@@ -1378,6 +1381,171 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, 8) void fetch_items_kernel(co
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// wah_splice_indexed_device: row ranges ("pieces") of indexed bitmaps concatenated into new indexed bitmaps, at any bit offset,
+// for all columns of an index at once -- INSERT of a batch, a window of rows, the rollover of a partition.  The output is written
+// as wah_from_positions_device writes it: the columns' compress() streams back to back and the index of the whole.
+//
+// Like the fetch call, ONLY the source segments that hold a spliced row are walked.  Three kinds of launches, and no workgroup of
+// any of them waits for another:
+//   splice_check_kernel      one workgroup: every piece is checked (rows inside its operands, no more rows than the output
+//                            holds, without wrapping) and the running starts start(0 .. n_pieces) are left in the scratch; a
+//                            refused piece counts as no rows.  Nothing is read through a piece unless EVERY piece was accepted:
+//                            with a stream error in the control block the other launches return at once.
+//   splice_segments_kernel<false>  (column, output segment) items shared out over the launch's wavefronts in contiguous runs,
+//                            as from_positions_kernel shares its items out.  A wavefront searches the starts for the pieces
+//                            that overlap its bit range [31744 s, 31744 (s + 1)), and for every one of them and every source
+//                            segment the piece's range touches here -- 31 744 bits lie in at most two -- walks the ONE table
+//                            entry (piece, column) for that source segment into a zeroed source image (list_walk under OR),
+//                            then moves the bits onto the destination's group grid (splice_move) and ORs them into the
+//                            destination image.  The image becomes words as in from_positions_kernel (image_words); the
+//                            count goes to offsets[item].
+//   (launch_select_rank_scan turns the counts into the index in place.)
+//   splice_segments_kernel<true>   the same items again; the words are staged in the source image's LDS and leave it 64
+//                            consecutive words per store instruction, clipped by the room the count pass found and by the capacity.
+// Two images of 4 KiB per wavefront, 32 KiB per workgroup of four: five workgroups per CU.
+constexpr u32 kSpliceSegBits = kSegGroups * 31u; // 31 744
+constexpr u32 kSpliceCheckThreads = 256;
+constexpr int kSpliceWavesPerSimd = 5;
+
+// the rows piece p adds to the output: n_rows, or 0 for a refused piece (bad is set).  A piece of no rows is legal whatever else it says.
+__device__ __forceinline__ u64 splice_piece_rows(const SpliceArgs &a, u64 p, bool &bad) {
+    const SplicePiece pc = a.pieces[p];
+    if (pc.n_rows == 0ull) return 0ull;
+    // (in this order nothing wraps: 32 n_words < 2^45, and first_row is below it before it is subtracted)
+    const bool ok = pc.n_words != 0ull && pc.n_words < (1ull << 40) && pc.n_rows <= a.n_bits && pc.first_row <= 32ull * pc.n_words &&
+                    pc.n_rows <= 32ull * pc.n_words - pc.first_row;
+    bad |= !ok;
+    return ok ? pc.n_rows : 0ull;
+}
+
+__global__ __launch_bounds__(256) void splice_check_kernel(const SpliceArgs a) {
+    __shared__ u64 s_sum[kSpliceCheckThreads];
+    const u32 t = threadIdx.x;
+    const u64 per = (a.n_pieces + kSpliceCheckThreads - 1u) / kSpliceCheckThreads;
+    const u64 begin = t * per < a.n_pieces ? t * per : a.n_pieces, end = begin + per < a.n_pieces ? begin + per : a.n_pieces;
+    bool bad = false;
+    u64 sum = 0; // (at most 2^16 pieces of at most 2^45 rows each)
+    for (u64 p = begin; p < end; ++p) sum += splice_piece_rows(a, p, bad);
+    s_sum[t] = sum;
+    __syncthreads();
+    u64 at = 0;
+    for (u32 i = 0; i < t; ++i) at += s_sum[i];
+    for (u64 p = begin; p < end; ++p) {
+        a.starts[p] = at;
+        at += splice_piece_rows(a, p, bad);
+    }
+    if (t == kSpliceCheckThreads - 1u) { // (its run ends at n_pieces: `at` is the total)
+        a.starts[a.n_pieces] = at;
+        bad |= at > a.n_bits;
+    }
+    if (__ballot(bad) != 0ull) report_stream_error(a.ctrl, lane_id());
+}
+
+// `len` >= 1 bits of the source image from bit sb on, ORed into the destination image from bit db on (both below 31 744, the
+// ranges inside their images).  With delta = sb - db = 31 q + r, 0 <= r < 31: bit j of destination group d is bit j + r of
+// source group d + q, or bit j + r - 31 of the group behind it.  Groups outside the image read as zero; what a source holds
+// outside [sb, sb + len) -- set pad bits of a foreign stream among it -- dies in the mask.  A lane writes only groups 64 k +
+// lane of the destination, its own in every call, and reads other lanes' groups of the source: the caller fences in front.
+__device__ __forceinline__ void splice_move(const u32 *src, u32 *dst, u32 sb, u32 db, u32 len, u32 lane) {
+    const int delta = (int)sb - (int)db;
+    const int q = delta >= 0 ? delta / 31 : -((30 - delta) / 31);
+    const u32 r = (u32)(delta - 31 * q);
+    const u32 g_first = db / 31u, g_last = (db + len - 1u) / 31u;
+#pragma nounroll
+    for (u32 k = g_first / 64u; k <= g_last / 64u; ++k) {
+        const u32 d = 64u * k + lane;
+        if (d >= g_first && d <= g_last) {
+            const int i = (int)d + q;
+            const u32 x = i >= 0 && i < (int)kSegGroups ? src[i] : 0u;
+            const u32 y = i + 1 >= 0 && i + 1 < (int)kSegGroups ? src[i + 1] : 0u;
+            const u32 v = ((x >> r) | (y << (31u - r))) & kOnes31;
+            const int lo = max((int)db - 31 * (int)d, 0), hi = min((int)(db + len) - 31 * (int)d, 31); // (0 <= lo < hi <= 31)
+            dst[d] |= v & ((1u << hi) - 1u) & ~((1u << lo) - 1u);
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // the next walk zeroes the source image
+}
+
+template <bool kEmit>
+__global__ __launch_bounds__(kSegDecodeWaves * 64, kSpliceWavesPerSimd) void splice_segments_kernel(const SpliceArgs a) {
+    __shared__ __attribute__((aligned(16))) u32 s_src[kSegDecodeWaves][kSegGroups];
+    __shared__ __attribute__((aligned(16))) u32 s_dst[kSegDecodeWaves][kSegGroups];
+    const u32 wave = wave_id(), lane = lane_id();
+    if ((a.ctrl[kCtlError] & kErrStream) != 0u) return; // a refused piece (or, in the emit pass, stream): no stream is read
+    u32 *src = s_src[wave], *dst = s_dst[wave];
+    u32 *stage = src; // (the emit pass: the source image is free once the bits are moved)
+    const u64 n_items = a.n_columns * a.n_segments;
+    const u64 n_waves = (u64)gridDim.x * kSegDecodeWaves;
+    const u64 per = (n_items + n_waves - 1) / n_waves;
+    const u64 w = (u64)blockIdx.x * kSegDecodeWaves + wave;
+    const u64 begin = w * per < n_items ? w * per : n_items, end = begin + per < n_items ? begin + per : n_items;
+    if (kEmit && w == 0 && lane == 0) {
+        const u64 total = a.offsets[n_items];
+        *a.out_words = total;
+        if (total > a.out_capacity) atomicOr(a.ctrl + kCtlError, kErrCapacity);
+    }
+    const u64 all_rows = uniform64(a.starts[a.n_pieces]); // T: at most 32 n_words_out (the check launch)
+    const ListOp m = list_op(1u);                         // a source segment is ORed into the zeroed image
+#pragma nounroll
+    for (u64 item = begin; item < end; ++item) {
+        const u64 c = item / a.n_segments, seg = item - c * a.n_segments;
+        const u64 base = seg * (u64)kSpliceSegBits;
+        const u32 ngroups = seg + 1 == a.n_segments ? (u32)(a.groups - seg * kSegGroups) : kSegGroups;
+        u32 total;
+        if (base >= all_rows) {
+            // behind the last piece: one zero-fill of the segment's groups; no LDS image, no load
+            total = 1u;
+            if (kEmit && lane == 0) stage[0] = fill_word(kTypeZero, ngroups);
+        } else {
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            image_fill(dst, 0u, lane);
+            const u64 limit = base + kSpliceSegBits < all_rows ? base + kSpliceSegBits : all_rows;
+            // the first piece that ends behind `base` (there is one: base < T)
+            u64 lo = 0, hi = a.n_pieces - 1;
+            while (lo < hi) {
+                const u64 mid = lo + (hi - lo) / 2;
+                if (uniform64(a.starts[mid + 1]) > base) hi = mid; else lo = mid + 1;
+            }
+#pragma nounroll
+            for (u64 p = lo; p < a.n_pieces; ++p) {
+                const u64 st = uniform64(a.starts[p]), en = uniform64(a.starts[p + 1]);
+                if (st >= limit) break;
+                if (en <= st || en <= base) continue; // (no rows; en <= base only for pieces of no rows at `base`)
+                const u64 d0 = st > base ? st : base, d1 = en < limit ? en : limit;
+                const u64 n_words = uniform64(a.pieces[p].n_words), first_row = uniform64(a.pieces[p].first_row);
+                const u64 s0 = first_row + (d0 - st), s1 = s0 + (d1 - d0); // (accepted: s1 <= 32 n_words)
+                const u64 src_groups = (32ull * n_words + 30ull) / 31ull;
+                const BitopListOperand *entry = a.table + (p * a.n_columns + c);
+#pragma nounroll
+                for (u64 ss = s0 / kSpliceSegBits; ss * kSpliceSegBits < s1; ++ss) {
+                    const u64 sbase = ss * kSpliceSegBits;
+                    const u64 t0 = s0 > sbase ? s0 : sbase, t1 = s1 < sbase + kSpliceSegBits ? s1 : sbase + kSpliceSegBits;
+                    if (ss * kSegGroups >= src_groups) break; // (never for an accepted piece)
+                    const u32 nvalid = src_groups - ss * kSegGroups < kSegGroups ? (u32)(src_groups - ss * kSegGroups) : kSegGroups;
+                    image_fill(src, 0u, lane);
+                    const bool ok = list_walk(entry, 1u, ss, nvalid, m.fill, src, lane, [&](u32) -> const ListOp & { return m; }, [](u32) {});
+                    if (!ok) return report_stream_error(a.ctrl, lane);
+                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                    splice_move(src, dst, (u32)(t0 - sbase), (u32)(d0 + (t0 - s0) - base), (u32)(t1 - t0), lane);
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            total = image_words<kEmit>(dst, ngroups, stage, lane);
+        }
+        if (kEmit) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            const u64 at = a.offsets[item], room = a.offsets[item + 1] - at; // what the count pass found
+            const u32 words = (u64)total < room ? total : (u32)room;
+            for (u32 i = lane; i < words; i += 64u)
+                if (at + i < a.out_capacity) a.out[at + i] = stage[i];
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // the next item stages over these words
+        } else if (lane == 0) {
+            a.offsets[item] = (u64)total;
+        }
+    }
+}
+
 // one wavefront per segment, kSegDecodeWaves of them per workgroup
 template <class Args>
 hipError_t launch_per_segment(void (*kernel)(const Args), u64 n_segments, const Args &a, hipStream_t s) {
@@ -1414,6 +1582,24 @@ hipError_t launch_fetch_items(const FetchArgs &a, u32 mode, hipStream_t s) {
         hipLaunchKernelGGL(fetch_items_kernel<kFetchFirst>, grid, block, 0, s, a);
     else
         hipLaunchKernelGGL(fetch_items_kernel<kFetchBits>, grid, block, 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_splice_check(const SpliceArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(splice_check_kernel, dim3(1), dim3(kSpliceCheckThreads), 0, s, a);
+    return hipGetLastError();
+}
+
+// count pass (emit = false: every item's words to a.offsets) or emit pass (a.offsets scanned: the words to their place)
+hipError_t launch_splice_segments(const SpliceArgs &a, bool emit, hipStream_t s) {
+    const u64 n_items = a.n_columns * a.n_segments;
+    const u64 want = (n_items + kSegDecodeWaves - 1) / kSegDecodeWaves;
+    constexpr u64 most = 256u * 5u; // CUs x resident workgroups of four wavefronts at 32 KiB of LDS each
+    const dim3 grid((unsigned)(want < 1 ? 1 : want > most ? most : want)), block(kSegDecodeWaves * 64);
+    if (emit)
+        hipLaunchKernelGGL(splice_segments_kernel<true>, grid, block, 0, s, a);
+    else
+        hipLaunchKernelGGL(splice_segments_kernel<false>, grid, block, 0, s, a);
     return hipGetLastError();
 }
 

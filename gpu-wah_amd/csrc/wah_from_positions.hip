@@ -33,7 +33,7 @@
 // What the check pass refuses is not trusted by the other two: ends are clamped to n_rows and to each other before they bound
 // a read of the rows, a row's place in its segment is clamped to the segment, a segment's words are clipped to the room the
 // count pass gave it, and every store to the output is compared with the capacity.
-#include "wah_device.hpp"
+#include "wah_image_words.hpp"
 
 namespace wah {
 namespace {
@@ -42,11 +42,6 @@ typedef const __attribute__((address_space(4))) u64 *FpConstU64;
 
 constexpr u32 kFpWaves = 4;
 constexpr u32 kSegBits = kSegGroups * 31u; // 31 744
-constexpr u32 kTypeZero = 0, kTypeOnes = 1, kTypeLit = 2, kTypeNone = 3;
-
-__device__ __forceinline__ u32 group_type(u32 v) { return v == 0u ? kTypeZero : v == kOnes31 ? kTypeOnes : kTypeLit; }
-__device__ __forceinline__ u32 fill_word(u32 type, u32 count) { return kFillZero | (type == kTypeOnes ? 0x40000000u : 0u) | count; }
-__device__ __forceinline__ u64 lanes_below(u32 lane) { return (1ull << lane) - 1ull; }
 
 __global__ __launch_bounds__(256) void from_positions_check_kernel(const FromPositionsArgs a) {
     const u64 stride = (u64)gridDim.x * blockDim.x;
@@ -190,30 +185,7 @@ __global__ __launch_bounds__(kFpWaves * 64) void from_positions_kernel(const Fro
                 atomicOr(img + g, 1u << (p - 31u * g));
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            const u32 n_steps = (ngroups + 63u) / 64u;
-            u32 run = 0, carry_type = kTypeNone, carry_len = 0;
-#pragma nounroll
-            for (u32 s = 0; s < n_steps; ++s) {
-                const u32 g = 64u * s + lane;
-                const bool valid = g < ngroups;
-                const u32 v = valid ? img[g] : 0u;
-                const u32 t = valid ? group_type(v) : kTypeNone;
-                u32 t_left = (u32)__shfl_up((int)t, 1), t_right = (u32)__shfl_down((int)t, 1);
-                if (lane == 0) t_left = carry_type;
-                if (lane == 63u) t_right = g + 1u < ngroups ? group_type(img[g + 1u]) : kTypeNone;
-                const bool brk = valid && (t == kTypeLit || t != t_left);   // a word begins here
-                const bool tail = valid && (t == kTypeLit || t != t_right); // ... and ends here
-                const u64 brks = __ballot(brk), tls = __ballot(tail);
-                const u32 headpos = 63u - (u32)__builtin_clzll((brks | 1ull) & (~0ull >> (63u - lane)));
-                const u32 len = lane - headpos + 1u + (headpos == 0u && !(brks & 1ull) ? carry_len : 0u);
-                if (kEmit && tail) stage[run + (u32)__popcll(tls & lanes_below(lane))] = t == kTypeLit ? v : fill_word(t, len);
-                run += (u32)__popcll(tls);
-                // the run that lane 63 is in goes on in the next step
-                const bool open = (__ballot(valid && !tail) >> 63) & 1ull;
-                carry_type = open ? (u32)__builtin_amdgcn_readlane((int)t, 63) : kTypeNone;
-                carry_len = open ? (u32)__builtin_amdgcn_readlane((int)len, 63) : 0u;
-            }
-            total = run;
+            total = image_words<kEmit>(img, ngroups, stage, lane); // (wah_image_words.hpp)
         }
         if (kEmit) {
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");

@@ -489,6 +489,30 @@ struct FromPositionsArgs {
 hipError_t launch_from_positions_check(const FromPositionsArgs &a, hipStream_t s);
 hipError_t launch_from_positions_segments(const FromPositionsArgs &a, bool emit, hipStream_t s);
 
+// wah_splice_indexed_device (wah_bitop_list.hip): row ranges of indexed bitmaps concatenated into new ones, for all columns of an
+// index at once.  pieces and table are read by the device only; the check launch leaves start(0 .. n_pieces) in `starts` (a
+// refused piece counts as no rows); offsets is used as FromPositionsArgs::offsets, n_columns * n_segments + 1 entries.
+struct SplicePiece {
+    uint64_t n_words, first_row, n_rows; // wah_splice_piece
+};
+constexpr uint64_t kSpliceMaxPieces = 1ull << 16; // WAH_SPLICE_MAX_PIECES
+struct SpliceArgs {
+    const SplicePiece *pieces;     // n_pieces
+    const BitopListOperand *table; // n_pieces * n_columns, piece-major
+    uint64_t *starts;              // scratch: n_pieces + 1
+    uint64_t n_pieces, n_columns;
+    uint64_t n_bits;               // 32 n_words_out: the rows of all pieces fit below it
+    uint64_t groups;               // G of ONE output bitmap
+    uint64_t n_segments;           // S = ceil(G / 1024), per column
+    uint32_t *out;
+    uint64_t out_capacity;
+    uint64_t *out_words;
+    uint64_t *offsets;
+    uint32_t *ctrl;
+};
+hipError_t launch_splice_check(const SpliceArgs &a, hipStream_t s);
+hipError_t launch_splice_segments(const SpliceArgs &a, bool emit, hipStream_t s);
+
 // wah_bsi_build_device (wah_bsi_build.hip): a column of 64-bit values in, the decoded slice matrix [n_bits (+ 1), n_words] out --
 // most significant slice first, the existence bitmap last when exists != nullptr.  Every word of the matrix is written.
 struct BsiBuildArgs {

@@ -911,6 +911,63 @@ int wah_from_positions_device(uint64_t n_words, uint64_t n_lists, const uint64_t
                               uint64_t *d_out_offsets, void *d_scratch, size_t scratch_bytes, void *stream);
 int wah_from_positions_status(void *d_scratch, void *stream);
 
+/* The call that changes the ROWS of an index: row ranges ("pieces") of indexed bitmaps concatenated into new indexed bitmaps, at
+ * any bit offset, for all columns of an index at once -- INSERT of a batch (the index, then the batch), the rollover of a time
+ * partition (drop the oldest range, append the newest), a [first, first + n) window of every column of an attribute, the split of
+ * an index by row ranges over the GPUs of a node.  Not in the reference.
+ *   d_pieces: n_pieces entries in DEVICE memory, 8-byte aligned.  d_operands: n_pieces * n_columns entries, piece-major: entry
+ *   p * n_columns + c is column c of piece p, an indexed bitmap of d_pieces[p].n_words words as for the list call (windows into
+ *   column matrices allowed, the length may be a capacity, streams compress() never emits are legal).
+ * With start(p) the sum of n_rows of the pieces before p and T the sum over all pieces, output bitmap c has n_words_out words;
+ * its position start(p) + i is position first_row(p) + i of operand (p, c) for i < n_rows(p), and every position at or behind T is
+ * zero, the pad bits of the last group included.  A piece of no rows is legal: its operands are not followed and may be null.
+ * The output is laid out as wah_from_positions_device's: d_out receives the n_columns compress() streams back to back, word for
+ * word, whatever form the sources had; d_out_offsets (required) receives n_columns * S + 1 entries counted from d_out[0],
+ * S = ceil(G / 1024), G = wah_max_compressed_words(n_words_out); d_out_words receives the total, also when it exceeds the capacity.
+ * For n_words_out % 992 == 0 the pair is a column matrix's (stream, whole index); for any n_words_out a wah_bitop_operand with
+ * d_offsets = d_out_offsets + c * S is column c.
+ *   wah_splice_max_words: an out_capacity_words that always suffices:
+ *   min(n_columns * G, n_columns * (S + 1) + 2 * n_pieces * n_columns + 2 * source_words), saturating at UINT64_MAX.  source_words
+ *   is any upper bound the caller has on the words of the source segments that are touched; the operands' whole streams are one.
+ *   Why it holds: a literal source word meets at most two output groups (2 * source_words); a fill leaves one fill word, and at
+ *   most one group where it ends inside an output group is charged to it (the other 1 of its 2); a piece has two ends in every
+ *   column, each of which may cut a run in two (2 * n_pieces * n_columns); every output segment cuts at most one run, and the zeros
+ *   behind T are one more run (n_columns * (S + 1)).
+ *   d_scratch: wah_splice_scratch_bytes(n_words_out, n_columns, n_pieces) bytes, 256-byte aligned, no initialisation:
+ *   1024 (the control words) + round256(8 * (n_pieces + 1)) (the running starts) + round256(8 * ceil(E / 4096)) +
+ *   round256(8 * ceil(ceil(E / 4096) / 4096)) with E = n_columns * S + 1 (the two upper levels of the prefix sum over the index,
+ *   which itself runs in place in d_out_offsets) and round256 rounding up to a multiple of 256.  A multiple of 256, never 0.
+ * Pieces and table are read only by the device: the call is asynchronous on `stream`, allocates nothing and never synchronises,
+ * and a captured graph replayed after d_pieces and d_operands were overwritten in place, with the same counts, splices the NEW
+ * pieces.  Four steps, none of which waits for another workgroup: a launch that checks every piece and leaves start(0 .. n_pieces)
+ * in the scratch; one wavefront per (column, output segment) that searches the starts for the pieces overlapping its 31 744 bits,
+ * walks for each of them the one or two source segments that hold its rows into an image of 1024 groups in LDS, moves the bits
+ * onto the output's group grid in a second image and counts the words of that; the prefix sum of the counts; the same wavefronts
+ * again, which now store the words, 64 consecutive ones at a time.  No decoded bitmap exists at any point.  Like the fetch call
+ * and unlike the others, ONLY the source segments that hold a spliced row are read and checked: the verdict depends on the
+ * pieces, not on the data.
+ * Errors the host can see come back before any HIP call, argument checks first: n_columns < 1 or > WAH_BITOP_LIST_MAX_OPERANDS,
+ * n_pieces < 1 or > WAH_SPLICE_MAX_PIECES, n_pieces * n_columns > 2^24, n_columns * S >= 2^31, n_words_out == 0 or >= 2^40, a null
+ * or misaligned d_pieces, d_operands, d_out_offsets, d_out_words (8 B), d_out (4 B) or scratch (256 B): WAH_ERR_ARG; too small a
+ * scratch: WAH_ERR_WORKSPACE.  Everything only the device sees is reported by wah_splice_status(), which synchronises the
+ * stream: WAH_ERR_STREAM for a piece with n_rows > 0 and n_words == 0 or >= 2^40, for first_row + n_rows > 32 * n_words (checked
+ * without wrapping), for an n_rows above 32 * n_words_out or T > 32 * n_words_out, and for everything the list call refuses in
+ * an operand, in the source segments that are read; WAH_ERR_CAPACITY for too small an output (nothing is written at or behind
+ * d_out[out_capacity_words]).  Every piece is checked before it steers a read, and after a refused piece the later launches read
+ * no stream.  The output of a refused call is unspecified.  wah_splice_status(NULL, ...): WAH_ERR_ARG. */
+typedef struct {
+    uint64_t n_words;   /* the words of ONE bitmap of this piece's operands          */
+    uint64_t first_row; /* first position (32 * word + bit) taken from each of them  */
+    uint64_t n_rows;    /* how many consecutive positions; 0 is legal                */
+} wah_splice_piece;     /* 24 bytes, no padding */
+#define WAH_SPLICE_MAX_PIECES (1u << 16)
+uint64_t wah_splice_max_words(uint64_t n_words_out, uint64_t n_columns, uint64_t n_pieces, uint64_t source_words);
+size_t wah_splice_scratch_bytes(uint64_t n_words_out, uint64_t n_columns, uint64_t n_pieces);
+int wah_splice_indexed_device(uint64_t n_words_out, uint64_t n_columns, uint64_t n_pieces, const wah_splice_piece *d_pieces,
+                              const wah_bitop_operand *d_operands, uint32_t *d_out, uint64_t out_capacity_words,
+                              uint64_t *d_out_words, uint64_t *d_out_offsets, void *d_scratch, size_t scratch_bytes, void *stream);
+int wah_splice_status(void *d_scratch, void *stream);
+
 /* The way into the BIT-SLICED index: a column of values in, the index of its slices out, in one call -- what
  * wah_bsi_range_indexed_device, wah_bsi_kth_indexed_device and wah_fetch_indexed_device read.  Not in the reference.
  *   d_values: n_rows unsigned 64-bit values below 2^n_bits, n_bits 1 .. 64 (a negative int64 is a value of 2^63 or more).
