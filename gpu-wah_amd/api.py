@@ -451,12 +451,53 @@ def bitop_device(op, d_a, d_b, n_words):
     return out[: int(count.item())].clone()
 
 
+def _as_int64(v, what):
+    """A Python int in 0 .. 2^64 - 1 as the int64 of the same bit pattern; what: how the refusal names the number."""
+    v = int(v)
+    if not 0 <= v < 1 << 64:
+        raise WahError(f"{what} is an unsigned integer below 2^64")
+    return v - (1 << 64) if v >= 1 << 63 else v
+
+
+def _int64_tensor(torch, given, shape, dev, refusal):
+    """The int64 tensor a call writes a result into: `given` when it is contiguous, of this shape and on dev, a new one when the
+    caller passed None; anything else raises WahError(refusal)."""
+    if given is None:
+        return torch.empty(shape, dtype=torch.int64, device=dev)
+    if given.dtype != torch.int64 or tuple(given.shape) != tuple(shape) or given.device != dev or not given.is_contiguous():
+        raise WahError(refusal)
+    return given
+
+
+def _enqueued(name, what, enqueue, status, scratch, check):
+    """The tail of the calls that leave their results in tensors of the caller's: enqueue(*tail), the C call `name` with its
+    leading arguments bound -- tail is what all of them end with, (scratch, its bytes, stream) -- and, unless check=False,
+    status(scratch pointer, stream) read under the name `what`."""
+    sp = _stream_ptr(_torch())
+    _check(enqueue(scratch.data_ptr(), scratch.numel(), sp), name)
+    if check:
+        _check(status(scratch.data_ptr(), sp), what)
+
+
+def _compressed(name, what, dev, enqueue, status, scratch, out, out_offsets, entries, check):
+    """The tail of the calls that return compressed words with their segment index: enqueue(*tail), the C call `name` with its
+    leading arguments bound -- tail is what all of them end with, (out, its capacity, count, out_offsets, scratch, its bytes,
+    stream).  check=False: returns (out, count tensor, out_offsets); otherwise status(scratch pointer, stream) is read under the
+    name `what` and the result is (out[:count], out_offsets[:entries]), the index as it is when entries is None."""
+    torch = _torch()
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    sp = _stream_ptr(torch)
+    _check(enqueue(out.data_ptr(), out.numel(), count.data_ptr(), out_offsets.data_ptr(), scratch.data_ptr(), scratch.numel(), sp), name)
+    if not check:
+        return out, count, out_offsets
+    _check(status(scratch.data_ptr(), sp), what)
+    return out[: int(count.item())], out_offsets if entries is None else out_offsets[:entries]
+
+
 def _compressed_result(name, n_words, dev, scratch_bytes, enqueue, status, scratch, out, out_offsets, check):
-    """What the calls that return a compressed bitmap with its segment index share.  Allocates what the caller did not pass --
-    scratch of scratch_bytes() bytes, out of max_compressed_words words, out_offsets of one entry per segment + 1 -- and runs
-    enqueue(*tail), the C call `name` with its leading arguments bound: tail is what all of them end with, (out, its capacity,
-    count, out_offsets, scratch, its bytes, stream).  check=False: returns (out, count tensor, out_offsets); otherwise
-    status(scratch pointer, stream) is read and the result is (out[:count], out_offsets)."""
+    """What the calls that return ONE compressed bitmap with its segment index share.  Allocates what the caller did not pass --
+    scratch of scratch_bytes() bytes, out of max_compressed_words words, out_offsets of one entry per segment + 1 -- and goes on
+    as _compressed, the index returned whole."""
     torch = _torch()
     cap = max_compressed_words(n_words)
     if scratch is None:
@@ -465,13 +506,25 @@ def _compressed_result(name, n_words, dev, scratch_bytes, enqueue, status, scrat
         out = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
     if out_offsets is None:
         out_offsets = torch.zeros((cap + 1023) // 1024 + 1, dtype=torch.int64, device=dev)
-    count = torch.zeros(1, dtype=torch.int64, device=dev)
-    sp = _stream_ptr(torch)
-    _check(enqueue(out.data_ptr(), out.numel(), count.data_ptr(), out_offsets.data_ptr(), scratch.data_ptr(), scratch.numel(), sp), name)
-    if not check:
-        return out, count, out_offsets
-    _check(status(scratch.data_ptr(), sp), name[len("wah_"):-len("_device")])
-    return out[: int(count.item())], out_offsets
+    return _compressed(name, name[len("wah_"):-len("_device")], dev, enqueue, status, scratch, out, out_offsets, None, check)
+
+
+def _compressed_streams(name, what, dev, entries, offsets_refusal, scratch_bytes, out_words, enqueue, status, scratch, out, out_offsets, check):
+    """What the calls that return SEVERAL streams back to back with one index of `entries` entries share.  Allocates what the caller
+    did not pass -- scratch of scratch_bytes() bytes, out of out_words() words, out_offsets of `entries` -- judges what it did pass
+    (out_offsets too short or of another kind: WahError(offsets_refusal)), and goes on as _compressed, the index cut to `entries`."""
+    torch = _torch()
+    if scratch is None:
+        scratch = torch.empty(int(scratch_bytes()), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.empty(out_words(), dtype=torch.int32, device=dev)
+    else:
+        _as_words(torch, out)
+    if out_offsets is None:
+        out_offsets = torch.empty(entries, dtype=torch.int64, device=dev)
+    elif out_offsets.dtype != torch.int64 or out_offsets.numel() < entries or not out_offsets.is_contiguous() or out_offsets.device != dev:
+        raise WahError(offsets_refusal)
+    return _compressed(name, what, dev, enqueue, status, scratch, out, out_offsets, entries, check)
 
 
 def bitop_indexed_device(op, d_a, a_offsets, d_b, b_offsets, n_words, scratch=None, out=None, out_offsets=None, check=True):
@@ -600,13 +653,7 @@ def bsi_bounds(lo, hi, device, out=None):
     with another range needs."""
     import torch
 
-    pair = []
-    for v in (lo, hi):
-        v = int(v)
-        if not 0 <= v < 1 << 64:
-            raise WahError("a bound is an unsigned integer below 2^64")
-        pair.append(v - (1 << 64) if v >= 1 << 63 else v)
-    t = torch.tensor(pair, dtype=torch.int64)
+    t = torch.tensor([_as_int64(v, "a bound") for v in (lo, hi)], dtype=torch.int64)
     if out is None:
         return t.to(device)
     out.copy_(t)
@@ -710,6 +757,25 @@ def bsi_arith_row_order(ka, kb, exists_a=False, exists_b=False):
     return order
 
 
+_ROWS_OUT_OFFSETS = "out_offsets: a contiguous int64 tensor of rows_out * n_words / 992 + 1 entries on the table's device"
+
+
+def _two_attributes(table, n_bits_a, n_bits_b, n_bits_out, n_words, exists_a, exists_b):
+    """The arguments of the calls that compute a new attribute from two (bsi_arith_device, bsi_mul_device), judged: the checked
+    table, the three widths and n_words as ints, the existence flags, and the result's rows (its slices, and an existence bitmap
+    where an operand has one)."""
+    table = _operand_table(table, "a row table")
+    ka, kb, k_out, n = int(n_bits_a), int(n_bits_b), int(n_bits_out), int(n_words)
+    flags = (BSI_EXISTS_A if exists_a else 0) | (BSI_EXISTS_B if exists_b else 0)
+    if not (1 <= ka <= BSI_MAX_SLICES and 1 <= kb <= BSI_MAX_SLICES and 1 <= k_out <= BSI_MAX_SLICES):
+        raise WahError("between 1 and 64 slices per attribute and in the result")
+    if int(table.shape[0]) != ka + kb + bool(exists_a) + bool(exists_b):
+        raise WahError("the table has one row per slice of either attribute and one per existence bitmap")
+    if n <= 0 or n % 992:
+        raise WahError("slices of a multiple of 992 words")
+    return table, ka, kb, k_out, n, flags, k_out + (1 if flags else 0)
+
+
 def bsi_arith_device(table, n_bits_a, n_bits_b, op, n_bits_out, n_words, exists_a=False, exists_b=False, scratch=None, out=None,
                      out_offsets=None, check=True):
     """The bit-sliced index of (A op B) mod 2^n_bits_out, row by row over two bit-sliced attributes, in one call
@@ -723,38 +789,12 @@ def bsi_arith_device(table, n_bits_a, n_bits_b, op, n_bits_out, n_words, exists_
     -- the caller reads wah_bsi_arith_status later."""
     if op not in ARITH_OPS:
         raise WahError(f"an arithmetic operation is one of {', '.join(ARITH_OPS)}")
-    torch = _torch()
-    table = _operand_table(table, "a row table")
-    dev = table.device
-    ka, kb, k_out, n = int(n_bits_a), int(n_bits_b), int(n_bits_out), int(n_words)
-    flags = (BSI_EXISTS_A if exists_a else 0) | (BSI_EXISTS_B if exists_b else 0)
-    if not (1 <= ka <= BSI_MAX_SLICES and 1 <= kb <= BSI_MAX_SLICES and 1 <= k_out <= BSI_MAX_SLICES):
-        raise WahError("between 1 and 64 slices per attribute and in the result")
-    if int(table.shape[0]) != ka + kb + bool(exists_a) + bool(exists_b):
-        raise WahError("the table has one row per slice of either attribute and one per existence bitmap")
-    if n <= 0 or n % 992:
-        raise WahError("slices of a multiple of 992 words")
-    rows_out = k_out + (1 if flags else 0)
-    entries = rows_out * (n // 992) + 1
-    if scratch is None:
-        scratch = torch.empty(int(lib().wah_bsi_arith_scratch_bytes(n, k_out, flags)), dtype=torch.uint8, device=dev)
-    if out is None:
-        out = torch.empty(max_compressed_words(rows_out * n), dtype=torch.int32, device=dev)
-    else:
-        _as_words(torch, out)
-    if out_offsets is None:
-        out_offsets = torch.empty(entries, dtype=torch.int64, device=dev)
-    elif out_offsets.dtype != torch.int64 or out_offsets.numel() < entries or not out_offsets.is_contiguous() or out_offsets.device != dev:
-        raise WahError("out_offsets: a contiguous int64 tensor of rows_out * n_words / 992 + 1 entries on the table's device")
-    count = torch.zeros(1, dtype=torch.int64, device=dev)
-    sp = _stream_ptr(torch)
-    _check(lib().wah_bsi_arith_indexed_device(ARITH_OPS[op], n, ka, kb, k_out, table.data_ptr(), flags, out.data_ptr(), out.numel(),
-                                              count.data_ptr(), out_offsets.data_ptr(), scratch.data_ptr(), scratch.numel(), sp),
-           "wah_bsi_arith_indexed_device")
-    if not check:
-        return out, count, out_offsets
-    _check(lib().wah_bsi_arith_status(scratch.data_ptr(), n, k_out, flags, sp), "bsi_arith")
-    return out[: int(count.item())], out_offsets[:entries]
+    table, ka, kb, k_out, n, flags, rows_out = _two_attributes(table, n_bits_a, n_bits_b, n_bits_out, n_words, exists_a, exists_b)
+    return _compressed_streams(
+        "wah_bsi_arith_indexed_device", "bsi_arith", table.device, rows_out * (n // 992) + 1, _ROWS_OUT_OFFSETS,
+        lambda: lib().wah_bsi_arith_scratch_bytes(n, k_out, flags), lambda: max_compressed_words(rows_out * n),
+        lambda *tail: lib().wah_bsi_arith_indexed_device(ARITH_OPS[op], n, ka, kb, k_out, table.data_ptr(), flags, *tail),
+        lambda sc, sp: lib().wah_bsi_arith_status(sc, n, k_out, flags, sp), scratch, out, out_offsets, check)
 
 
 def bsi_mul_row_order(ka, kb, exists_a=False, exists_b=False):
@@ -783,38 +823,12 @@ def bsi_mul_device(table, n_bits_a, n_bits_b, n_bits_out, n_words, exists_a=Fals
     n_bits_out: 1 .. 64; n_bits_a + n_bits_b loses nothing, fewer truncate, more zero-extend.  The call takes the operands as
     given; the narrower one as A keeps the scratch small.  n_words, the existence flags, the result and scratch / out /
     out_offsets / check: as bsi_arith_device -- with check=False the caller reads wah_bsi_mul_status later."""
-    torch = _torch()
-    table = _operand_table(table, "a row table")
-    dev = table.device
-    ka, kb, k_out, n = int(n_bits_a), int(n_bits_b), int(n_bits_out), int(n_words)
-    flags = (BSI_EXISTS_A if exists_a else 0) | (BSI_EXISTS_B if exists_b else 0)
-    if not (1 <= ka <= BSI_MAX_SLICES and 1 <= kb <= BSI_MAX_SLICES and 1 <= k_out <= BSI_MAX_SLICES):
-        raise WahError("between 1 and 64 slices per attribute and in the result")
-    if int(table.shape[0]) != ka + kb + bool(exists_a) + bool(exists_b):
-        raise WahError("the table has one row per slice of either attribute and one per existence bitmap")
-    if n <= 0 or n % 992:
-        raise WahError("slices of a multiple of 992 words")
-    rows_out = k_out + (1 if flags else 0)
-    entries = rows_out * (n // 992) + 1
-    if scratch is None:
-        scratch = torch.empty(int(lib().wah_bsi_mul_scratch_bytes(n, ka, k_out, flags)), dtype=torch.uint8, device=dev)
-    if out is None:
-        out = torch.empty(max_compressed_words(rows_out * n), dtype=torch.int32, device=dev)
-    else:
-        _as_words(torch, out)
-    if out_offsets is None:
-        out_offsets = torch.empty(entries, dtype=torch.int64, device=dev)
-    elif out_offsets.dtype != torch.int64 or out_offsets.numel() < entries or not out_offsets.is_contiguous() or out_offsets.device != dev:
-        raise WahError("out_offsets: a contiguous int64 tensor of rows_out * n_words / 992 + 1 entries on the table's device")
-    count = torch.zeros(1, dtype=torch.int64, device=dev)
-    sp = _stream_ptr(torch)
-    _check(lib().wah_bsi_mul_indexed_device(n, ka, kb, k_out, table.data_ptr(), flags, out.data_ptr(), out.numel(), count.data_ptr(),
-                                            out_offsets.data_ptr(), scratch.data_ptr(), scratch.numel(), sp),
-           "wah_bsi_mul_indexed_device")
-    if not check:
-        return out, count, out_offsets
-    _check(lib().wah_bsi_mul_status(scratch.data_ptr(), n, ka, k_out, flags, sp), "bsi_mul")
-    return out[: int(count.item())], out_offsets[:entries]
+    table, ka, kb, k_out, n, flags, rows_out = _two_attributes(table, n_bits_a, n_bits_b, n_bits_out, n_words, exists_a, exists_b)
+    return _compressed_streams(
+        "wah_bsi_mul_indexed_device", "bsi_mul", table.device, rows_out * (n // 992) + 1, _ROWS_OUT_OFFSETS,
+        lambda: lib().wah_bsi_mul_scratch_bytes(n, ka, k_out, flags), lambda: max_compressed_words(rows_out * n),
+        lambda *tail: lib().wah_bsi_mul_indexed_device(n, ka, kb, k_out, table.data_ptr(), flags, *tail),
+        lambda sc, sp: lib().wah_bsi_mul_status(sc, n, ka, k_out, flags, sp), scratch, out, out_offsets, check)
 
 
 BSI_KTH_ASCENDING, BSI_KTH_DESCENDING, BSI_KTH_QUANTILE = 0, 1, 2  # WAH_BSI_KTH_*
@@ -829,13 +843,7 @@ def bsi_kth_query(kind, a, b=1, device="cuda:0", out=None):
     replayed with another query needs."""
     import torch
 
-    words = []
-    for v in (kind, a, b):
-        v = int(v)
-        if not 0 <= v < 1 << 64:
-            raise WahError("a query word is an unsigned integer below 2^64")
-        words.append(v - (1 << 64) if v >= 1 << 63 else v)
-    t = torch.tensor(words, dtype=torch.int64)
+    t = torch.tensor([_as_int64(v, "a query word") for v in (kind, a, b)], dtype=torch.int64)
     if out is None:
         return t.to(device)
     out.copy_(t)
@@ -863,15 +871,10 @@ def bsi_kth_device(table, query, n_words, n_filters, scratch=None, result=None, 
     n = int(n_words)
     if scratch is None:
         scratch = torch.empty(int(lib().wah_bsi_kth_scratch_bytes(n, k)), dtype=torch.uint8, device=dev)
-    if result is None:
-        result = torch.empty(5, dtype=torch.int64, device=dev)
-    elif result.dtype != torch.int64 or tuple(result.shape) != (5,) or result.device != dev or not result.is_contiguous():
-        raise WahError("result: a contiguous int64 [5] tensor on the table's device")
-    sp = _stream_ptr(torch)
-    _check(lib().wah_bsi_kth_indexed_device(n, f, k, table.data_ptr(), query.data_ptr(), result.data_ptr(), scratch.data_ptr(),
-                                            scratch.numel(), sp), "wah_bsi_kth_indexed_device")
-    if check:
-        _check(lib().wah_bsi_kth_status(scratch.data_ptr(), sp), "bsi_kth")
+    result = _int64_tensor(torch, result, (5,), dev, "result: a contiguous int64 [5] tensor on the table's device")
+    _enqueued("wah_bsi_kth_indexed_device", "bsi_kth",
+              lambda *tail: lib().wah_bsi_kth_indexed_device(n, f, k, table.data_ptr(), query.data_ptr(), result.data_ptr(), *tail),
+              lib().wah_bsi_kth_status, scratch, check)
     return result
 
 
@@ -887,13 +890,7 @@ def bsi_kth_queries(queries, device="cuda:0", out=None):
     rows = []
     for query in queries:
         kind, a, b = query
-        words = []
-        for v in (kind, a, b):
-            v = int(v)
-            if not 0 <= v < 1 << 64:
-                raise WahError("a query word is an unsigned integer below 2^64")
-            words.append(v - (1 << 64) if v >= 1 << 63 else v)
-        rows.append(words)
+        rows.append([_as_int64(v, "a query word") for v in (kind, a, b)])
     if not rows:
         raise WahError("at least one query")
     t = torch.tensor(rows, dtype=torch.int64)
@@ -932,16 +929,11 @@ def bsi_kth_grouped_device(filters, groups, slices, queries, n_words, rows_per_g
         raise WahError("at most 64 filter rows, 64 slices and 4096 (group, query) pairs")
     if scratch is None:
         scratch = torch.empty(int(lib().wah_bsi_kth_grouped_scratch_bytes(n, k, g, q)), dtype=torch.uint8, device=dev)
-    if results is None:
-        results = torch.empty((g, q, 5), dtype=torch.int64, device=dev)
-    elif results.dtype != torch.int64 or tuple(results.shape) != (g, q, 5) or results.device != dev or not results.is_contiguous():
-        raise WahError("results: a contiguous int64 [G, Q, 5] tensor on the tables' device")
-    sp = _stream_ptr(torch)
-    _check(lib().wah_bsi_kth_grouped_indexed_device(n, f, ft.data_ptr() if f else None, g, r, gt.data_ptr(), k, st.data_ptr(), q,
-                                                    queries.data_ptr(), results.data_ptr(), scratch.data_ptr(), scratch.numel(), sp),
-           "wah_bsi_kth_grouped_indexed_device")
-    if check:
-        _check(lib().wah_bsi_kth_grouped_status(scratch.data_ptr(), sp), "bsi_kth_grouped")
+    results = _int64_tensor(torch, results, (g, q, 5), dev, "results: a contiguous int64 [G, Q, 5] tensor on the tables' device")
+    _enqueued("wah_bsi_kth_grouped_indexed_device", "bsi_kth_grouped",
+              lambda *tail: lib().wah_bsi_kth_grouped_indexed_device(n, f, ft.data_ptr() if f else None, g, r, gt.data_ptr(), k, st.data_ptr(), q,
+                                                                     queries.data_ptr(), results.data_ptr(), *tail),
+              lib().wah_bsi_kth_grouped_status, scratch, check)
     return results
 
 
@@ -966,15 +958,11 @@ def fetch_device(table, rows, n_words, mode, scratch=None, out=None, check=True)
     n, k, r = int(n_words), int(table.shape[0]), int(rows.numel())
     if scratch is None:
         scratch = torch.empty(int(lib().wah_fetch_scratch_bytes(n, r)), dtype=torch.uint8, device=dev)
-    if out is None:
-        out = torch.empty(r, dtype=torch.int64, device=dev)
-    elif out.dtype != torch.int64 or tuple(out.shape) != (r,) or out.device != dev or not out.is_contiguous():
-        raise WahError("out: a contiguous int64 [len(rows)] tensor on the table's device")
-    sp = _stream_ptr(torch)
-    _check(lib().wah_fetch_indexed_device(mode, n, k, table.data_ptr(), rows.data_ptr() if r else None, r, out.data_ptr() if r else None,
-                                          scratch.data_ptr(), scratch.numel(), sp), "wah_fetch_indexed_device")
-    if check:
-        _check(lib().wah_fetch_status(scratch.data_ptr(), sp), "fetch")
+    out = _int64_tensor(torch, out, (r,), dev, "out: a contiguous int64 [len(rows)] tensor on the table's device")
+    _enqueued("wah_fetch_indexed_device", "fetch",
+              lambda *tail: lib().wah_fetch_indexed_device(mode, n, k, table.data_ptr(), rows.data_ptr() if r else None, r,
+                                                           out.data_ptr() if r else None, *tail),
+              lib().wah_fetch_status, scratch, check)
     return out
 
 
@@ -990,15 +978,10 @@ def count_device(operands_or_table, n_words, scratch=None, counts=None, check=Tr
     n, k = int(n_words), int(table.shape[0])
     if scratch is None:
         scratch = torch.empty(int(lib().wah_select_scratch_bytes(n, k)), dtype=torch.uint8, device=dev)
-    if counts is None:
-        counts = torch.empty(k, dtype=torch.int64, device=dev)
-    elif counts.dtype != torch.int64 or tuple(counts.shape) != (k,) or not counts.is_contiguous() or counts.device != dev:
-        raise WahError("counts: a contiguous int64 [k] tensor on the table's device")
-    sp = _stream_ptr(torch)
-    _check(lib().wah_count_list_indexed_device(n, k, table.data_ptr(), counts.data_ptr(), scratch.data_ptr(), scratch.numel(), sp),
-           "wah_count_list_indexed_device")
-    if check:
-        _check(lib().wah_select_status(scratch.data_ptr(), sp), "count")
+    counts = _int64_tensor(torch, counts, (k,), dev, "counts: a contiguous int64 [k] tensor on the table's device")
+    _enqueued("wah_count_list_indexed_device", "count",
+              lambda *tail: lib().wah_count_list_indexed_device(n, k, table.data_ptr(), counts.data_ptr(), *tail),
+              lib().wah_select_status, scratch, check)
     return counts
 
 
@@ -1017,15 +1000,10 @@ def count_masked_device(masks, operands, n_words, scratch=None, counts=None, che
     n, m, k = int(n_words), int(mt.shape[0]), int(ot.shape[0])
     if scratch is None:
         scratch = torch.empty(int(lib().wah_select_scratch_bytes(n, k)), dtype=torch.uint8, device=dev)
-    if counts is None:
-        counts = torch.empty((m, k), dtype=torch.int64, device=dev)
-    elif counts.dtype != torch.int64 or tuple(counts.shape) != (m, k) or not counts.is_contiguous() or counts.device != dev:
-        raise WahError("counts: a contiguous int64 [m, k] tensor on the tables' device")
-    sp = _stream_ptr(torch)
-    _check(lib().wah_count_masked_indexed_device(n, m, mt.data_ptr(), k, ot.data_ptr(), counts.data_ptr(), scratch.data_ptr(),
-                                                 scratch.numel(), sp), "wah_count_masked_indexed_device")
-    if check:
-        _check(lib().wah_select_status(scratch.data_ptr(), sp), "count_masked")
+    counts = _int64_tensor(torch, counts, (m, k), dev, "counts: a contiguous int64 [m, k] tensor on the tables' device")
+    _enqueued("wah_count_masked_indexed_device", "count_masked",
+              lambda *tail: lib().wah_count_masked_indexed_device(n, m, mt.data_ptr(), k, ot.data_ptr(), counts.data_ptr(), *tail),
+              lib().wah_select_status, scratch, check)
     return counts
 
 
@@ -1060,21 +1038,14 @@ def group_sum_device(filters, groups, operands, attr_bits, n_words, rows_per_gro
     n, f, g, k, a = int(n_words), 0 if ft is None else int(ft.shape[0]), int(gt.shape[0]) // r, int(ot.shape[0]), len(bits)
     if scratch is None:
         scratch = torch.empty(int(lib().wah_select_scratch_bytes(n, k)), dtype=torch.uint8, device=dev)
-    outs = []
-    for name, given, shape in (("group_rows", group_rows, (g,)), ("counts", counts, (g, k)), ("sums", sums, (g, a, 2))):
-        if given is None:
-            given = torch.empty(shape, dtype=torch.int64, device=dev)
-        elif given.dtype != torch.int64 or tuple(given.shape) != shape or not given.is_contiguous() or given.device != dev:
-            raise WahError(f"{name}: a contiguous int64 {list(shape)} tensor on the tables' device")
-        outs.append(given)
-    group_rows, counts, sums = outs
+    group_rows, counts, sums = (
+        _int64_tensor(torch, given, shape, dev, f"{name}: a contiguous int64 {list(shape)} tensor on the tables' device")
+        for name, given, shape in (("group_rows", group_rows, (g,)), ("counts", counts, (g, k)), ("sums", sums, (g, a, 2))))
     widths = (ctypes.c_uint8 * a)(*bits)
-    sp = _stream_ptr(torch)
-    _check(lib().wah_group_sum_indexed_device(n, f, ft.data_ptr() if f else None, g, r, gt.data_ptr(), k, ot.data_ptr(), a, widths,
-                                              group_rows.data_ptr(), counts.data_ptr(), sums.data_ptr(), scratch.data_ptr(),
-                                              scratch.numel(), sp), "wah_group_sum_indexed_device")
-    if check:
-        _check(lib().wah_select_status(scratch.data_ptr(), sp), "group_sum")
+    _enqueued("wah_group_sum_indexed_device", "group_sum",
+              lambda *tail: lib().wah_group_sum_indexed_device(n, f, ft.data_ptr() if f else None, g, r, gt.data_ptr(), k, ot.data_ptr(), a, widths,
+                                                               group_rows.data_ptr(), counts.data_ptr(), sums.data_ptr(), *tail),
+              lib().wah_select_status, scratch, check)
     return group_rows, counts, sums
 
 
@@ -1103,9 +1074,8 @@ def positions_device(stream, seg_offsets, n_words, first=0, limit=None, out=None
                                                   dst.data_ptr() if cap else None, cap, info.data_ptr(), scratch.data_ptr(),
                                                   scratch.numel(), sp), "wah_positions_indexed_device")
 
-    if out is not None:
-        if out.dtype != torch.int64 or out.dim() != 1 or not out.is_contiguous() or out.device != dev:
-            raise WahError("out: a contiguous one-dimensional int64 tensor on the stream's device")
+    if out is not None:  # (one-dimensional, of whatever length)
+        _int64_tensor(torch, out, (out.numel(),), dev, "out: a contiguous one-dimensional int64 tensor on the stream's device")
         limit = int(out.numel()) if limit is None else min(int(limit), int(out.numel()))
     if limit is None:
         if not check:
@@ -1145,25 +1115,12 @@ def from_positions_device(rows, list_ends, n_words, scratch=None, out=None, out_
     dev = rows.device
     n, k, r = int(n_words), int(list_ends.numel()), int(rows.numel())
     n_seg = (max_compressed_words(n) + 1023) // 1024
-    if scratch is None:
-        scratch = torch.empty(int(lib().wah_from_positions_scratch_bytes(n, k)), dtype=torch.uint8, device=dev)
-    if out is None:
-        out = torch.empty(max(from_positions_max_words(n, k, r), 1), dtype=torch.int32, device=dev)
-    else:
-        _as_words(torch, out)
-    if out_offsets is None:
-        out_offsets = torch.empty(k * n_seg + 1, dtype=torch.int64, device=dev)
-    elif out_offsets.dtype != torch.int64 or out_offsets.numel() < k * n_seg + 1 or not out_offsets.is_contiguous() or out_offsets.device != dev:
-        raise WahError("out_offsets: a contiguous int64 tensor of n_lists * segments + 1 entries on the rows' device")
-    count = torch.zeros(1, dtype=torch.int64, device=dev)
-    sp = _stream_ptr(torch)
-    _check(lib().wah_from_positions_device(n, k, list_ends.data_ptr(), rows.data_ptr() if r else None, r, out.data_ptr(), out.numel(),
-                                           count.data_ptr(), out_offsets.data_ptr(), scratch.data_ptr(), scratch.numel(), sp),
-           "wah_from_positions_device")
-    if not check:
-        return out, count, out_offsets
-    _check(lib().wah_from_positions_status(scratch.data_ptr(), sp), "from_positions")
-    return out[: int(count.item())], out_offsets[: k * n_seg + 1]
+    return _compressed_streams(
+        "wah_from_positions_device", "from_positions", dev, k * n_seg + 1,
+        "out_offsets: a contiguous int64 tensor of n_lists * segments + 1 entries on the rows' device",
+        lambda: lib().wah_from_positions_scratch_bytes(n, k), lambda: max(from_positions_max_words(n, k, r), 1),
+        lambda *tail: lib().wah_from_positions_device(n, k, list_ends.data_ptr(), rows.data_ptr() if r else None, r, *tail),
+        lib().wah_from_positions_status, scratch, out, out_offsets, check)
 
 
 SPLICE_MAX_PIECES = 1 << 16  # WAH_SPLICE_MAX_PIECES
@@ -1205,25 +1162,13 @@ def splice_device(pieces, table, n_columns, n_words_out, source_words=None, scra
     if k < 1 or int(table.shape[0]) != p * k:
         raise WahError("the operand table holds n_columns >= 1 rows for every piece")
     n_seg = (max_compressed_words(n) + 1023) // 1024
-    if scratch is None:
-        scratch = torch.empty(int(lib().wah_splice_scratch_bytes(n, k, p)), dtype=torch.uint8, device=dev)
-    if out is None:
-        words = k * max_compressed_words(n) if source_words is None else splice_max_words(n, k, p, source_words)
-        out = torch.empty(max(words, 1), dtype=torch.int32, device=dev)
-    else:
-        _as_words(torch, out)
-    if out_offsets is None:
-        out_offsets = torch.empty(k * n_seg + 1, dtype=torch.int64, device=dev)
-    elif out_offsets.dtype != torch.int64 or out_offsets.numel() < k * n_seg + 1 or not out_offsets.is_contiguous() or out_offsets.device != dev:
-        raise WahError("out_offsets: a contiguous int64 tensor of n_columns * segments + 1 entries on the table's device")
-    count = torch.zeros(1, dtype=torch.int64, device=dev)
-    sp = _stream_ptr(torch)
-    _check(lib().wah_splice_indexed_device(n, k, p, pieces.data_ptr(), table.data_ptr(), out.data_ptr(), out.numel(), count.data_ptr(),
-                                           out_offsets.data_ptr(), scratch.data_ptr(), scratch.numel(), sp), "wah_splice_indexed_device")
-    if not check:
-        return out, count, out_offsets
-    _check(lib().wah_splice_status(scratch.data_ptr(), sp), "splice")
-    return out[: int(count.item())], out_offsets[: k * n_seg + 1]
+    return _compressed_streams(
+        "wah_splice_indexed_device", "splice", dev, k * n_seg + 1,
+        "out_offsets: a contiguous int64 tensor of n_columns * segments + 1 entries on the table's device",
+        lambda: lib().wah_splice_scratch_bytes(n, k, p),
+        lambda: max(k * max_compressed_words(n) if source_words is None else splice_max_words(n, k, p, source_words), 1),
+        lambda *tail: lib().wah_splice_indexed_device(n, k, p, pieces.data_ptr(), table.data_ptr(), *tail),
+        lib().wah_splice_status, scratch, out, out_offsets, check)
 
 
 def bsi_build_device(values, n_bits, n_words, exists=None, scratch=None, out=None, out_offsets=None, check=True):
@@ -1247,27 +1192,15 @@ def bsi_build_device(values, n_bits, n_words, exists=None, scratch=None, out=Non
     if not 1 <= bits <= 64 or n <= 0 or n % 992:
         raise WahError("between 1 and 64 bits, slices of a multiple of 992 words")
     k = bits + (exists is not None)
-    entries = k * (n // 992) + 1
-    if scratch is None:
-        scratch = torch.empty(int(lib().wah_bsi_build_scratch_bytes(n, k)), dtype=torch.uint8, device=dev)
-    if out is None:
-        out = torch.empty(max_compressed_words(k * n), dtype=torch.int32, device=dev)
-    else:
-        _as_words(torch, out)
-    if out_offsets is None:
-        out_offsets = torch.empty(entries, dtype=torch.int64, device=dev)
-    elif out_offsets.dtype != torch.int64 or out_offsets.numel() < entries or not out_offsets.is_contiguous() or out_offsets.device != dev:
-        raise WahError("out_offsets: a contiguous int64 tensor of n_slices * n_words / 992 + 1 entries on the values' device")
-    count = torch.zeros(1, dtype=torch.int64, device=dev)
-    sp = _stream_ptr(torch)
-    # (an empty bool tensor still stands for "with an existence bitmap": the library tells by the pointer, so it gets the scratch's)
-    d_exists = None if exists is None else exists.data_ptr() if r else scratch.data_ptr()
-    _check(lib().wah_bsi_build_device(n, bits, values.data_ptr() if r else None, r, d_exists, out.data_ptr(), out.numel(), count.data_ptr(),
-                                      out_offsets.data_ptr(), scratch.data_ptr(), scratch.numel(), sp), "wah_bsi_build_device")
-    if not check:
-        return out, count, out_offsets
-    _check(lib().wah_bsi_build_status(scratch.data_ptr(), n, k, sp), "bsi_build")
-    return out[: int(count.item())], out_offsets[:entries]
+    # (an empty bool tensor still stands for "with an existence bitmap": the library tells by the pointer, so it gets the scratch's,
+    # tail[4])
+    return _compressed_streams(
+        "wah_bsi_build_device", "bsi_build", dev, k * (n // 992) + 1,
+        "out_offsets: a contiguous int64 tensor of n_slices * n_words / 992 + 1 entries on the values' device",
+        lambda: lib().wah_bsi_build_scratch_bytes(n, k), lambda: max_compressed_words(k * n),
+        lambda *tail: lib().wah_bsi_build_device(n, bits, values.data_ptr() if r else None, r,
+                                                 None if exists is None else exists.data_ptr() if r else tail[4], *tail),
+        lambda sc, sp: lib().wah_bsi_build_status(sc, n, k, sp), scratch, out, out_offsets, check)
 
 
 StreamReport = collections.namedtuple(

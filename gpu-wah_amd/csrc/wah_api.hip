@@ -68,6 +68,12 @@ inline bool table_ok(uint64_t n, const void *d_table, uint64_t n_words) {
     return n >= 1 && n <= wah::kMaxBitopListOperands && d_table && aligned(d_table, 7) && n_words < (1ull << 40);
 }
 constexpr const char *kBadTable = "between 1 and 2^24 operands in an 8-byte aligned table, fewer than 2^40 words";
+// ... and of their output: the calls that leave ONE stream need its count, and its words unless the bitmap is empty (the index is
+// optional); the calls that leave several streams back to back need all three, aligned
+inline bool out_given(uint64_t n_words, const uint32_t *d_out, const uint64_t *d_out_words) { return d_out_words && (!n_words || d_out); }
+inline bool out_triple_ok(const uint32_t *d_out, const uint64_t *d_out_words, const uint64_t *d_out_offsets) {
+    return d_out && aligned(d_out, 3) && d_out_words && aligned(d_out_words, 7) && d_out_offsets && aligned(d_out_offsets, 7);
+}
 
 // Workspace layouts.  Everything a launch stamps with its epoch lives in areas whose PLACE depends on the workspace's size
 // only, never on the size of the input: one workspace serves inputs of different sizes in turn (include/wah.h), and an
@@ -173,6 +179,18 @@ int status_from_bits(uint32_t err) {
         return WAH_ERR_CAPACITY;
     }
     return WAH_OK;
+}
+
+// The *_status of the indexed calls.  A call whose kernels share the control block at the head of the scratch reads that one; a
+// call that ends in the compress passes reads its own block first (what its sweep refused in an operand), then the block of the
+// compress workspace at `ws_c`.
+int scratch_status(void *d_scratch, void *stream) {
+    if (!d_scratch) return WAH_ERR_ARG;
+    return read_status(d_scratch, stream);
+}
+int scratch_status_then(size_t ws_c, void *d_scratch, void *stream) {
+    const int rc = scratch_status(d_scratch, stream);
+    return rc != WAH_OK ? rc : read_status(static_cast<char *>(d_scratch) + ws_c, stream);
 }
 
 // Host-pointer entry points: the results of a launch (kCtlResult) lie beside its error word, so one 32-byte copy into
@@ -1145,28 +1163,54 @@ bool bitop_runs_route(int op, uint64_t n_words, int n, const uint32_t *const *co
     return true;
 }
 
-// The road of the calls that combine indexed operands into ONE decoded bitmap: the control words cleared (the call's *_status
-// reads them), the combining kernel `launch` run over every segment into the scratch's bitmap area, the compress passes over
-// that.  a: the kernel's arguments, its geometry a.g filled in here.  The bitmap area takes ceil(31 G / 32) words: n_words, or
+// The road of every call that ends in the compress passes: the control words at the head of the scratch cleared (the call's
+// *_status reads them), ONE kernel `launch` that writes decoded words into an area of the scratch, the compress passes over the
+// `n_words` words at `decoded` with the workspace at `ws_c`.  One bitmap (combine_then_compress) or a matrix of slices
+// (sweep_then_compress, further down): the compress passes take either.
+extern "C++" template <class Args, class Launch>
+int launch_then_compress(const Args &a, Launch launch, const char *label, const uint32_t *decoded, uint64_t n_words, uint32_t *d_out,
+                         uint64_t out_capacity_words, uint64_t *d_out_words, uint64_t *d_out_offsets, char *sc, size_t ws_c,
+                         size_t ws_c_bytes, void *stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = wah::launch_clear(sc, wah::kCtlWords * sizeof(uint32_t), s);
+    if (e == hipSuccess) e = launch(a, s);
+    if (e != hipSuccess) return refuse(label, WAH_ERR_HIP, e);
+    return compress_device_impl(decoded, nullptr, 0, nullptr, n_words, d_out, out_capacity_words, d_out_words, d_out_offsets, sc + ws_c,
+                                ws_c_bytes, stream, true);
+}
+
+// The calls that combine indexed operands into ONE decoded bitmap: the combining kernel runs over every segment into the scratch's
+// bitmap area.  a: the kernel's arguments, its geometry a.g filled in here.  The bitmap area takes ceil(31 G / 32) words: n_words, or
 // n_words + 1 when the last group has spare bits -- a negated clause, or a range with lo == 0, sets them, and they land in that
 // one word more, which the area has room for and the compress passes, told n_words, never read.
 extern "C++" template <class Args, class Launch>
 int combine_then_compress(Args &a, Launch launch, const char *label, uint64_t n_words, uint32_t *d_out, uint64_t out_capacity_words,
                           uint64_t *d_out_words, uint64_t *d_out_offsets, char *sc, const BitopIndexedLayout &l, void *stream) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    uint32_t *combined = reinterpret_cast<uint32_t *>(sc + l.bitmap);
     const SegGeometry g = seg_geometry(n_words);
     a.g.first_segment = 0;
     a.g.n_segments = g.n_segments;
     a.g.groups = g.groups;
     a.g.out_words = wah_decoded_words(g.groups);
-    a.g.out = combined;
+    a.g.out = reinterpret_cast<uint32_t *>(sc + l.bitmap);
     a.g.ctrl = reinterpret_cast<uint32_t *>(sc);
-    hipError_t e = wah::launch_clear(sc, wah::kCtlWords * sizeof(uint32_t), s);
-    if (e == hipSuccess) e = launch(a, s);
-    if (e != hipSuccess) return refuse(label, WAH_ERR_HIP, e);
-    return compress_device_impl(combined, nullptr, 0, nullptr, n_words, d_out, out_capacity_words, d_out_words, d_out_offsets,
-                                sc + l.ws_c, l.ws_c_bytes, stream, true);
+    return launch_then_compress(a, launch, label, a.g.out, n_words, d_out, out_capacity_words, d_out_words, d_out_offsets, sc, l.ws_c,
+                                l.ws_c_bytes, stream);
+}
+
+// The bits of `flags` that say which of two attributes comes with an existence bitmap, as the sweeps' arguments hold them
+extern "C++" template <class Args>
+void set_exists(Args &a, unsigned flags) {
+    a.exists_a = (flags & WAH_BSI_EXISTS_A) ? 1u : 0u;
+    a.exists_b = (flags & WAH_BSI_EXISTS_B) ? 1u : 0u;
+}
+
+// What the arguments of every kernel that walks whole bitmaps segment by segment hold: the bitmap's geometry and the control words
+extern "C++" template <class Args>
+void set_walk(Args &a, const SegGeometry &g, char *sc) {
+    a.pad_bits = g.pad_bits;
+    a.groups = g.groups;
+    a.n_segments = g.n_segments;
+    a.ctrl = reinterpret_cast<uint32_t *>(sc);
 }
 } // namespace
 
@@ -1241,9 +1285,7 @@ int wah_bitop_many_indexed_device(int op, uint64_t n_words, int n_operands, cons
 }
 
 int wah_bitop_indexed_status(void *d_scratch, uint64_t n_words, void *stream) {
-    if (!d_scratch) return WAH_ERR_ARG;
-    const int rc = read_status(d_scratch, stream); // the combining pass: operands that are not segmented streams of n_words
-    return rc != WAH_OK ? rc : read_status(static_cast<char *>(d_scratch) + bitop_indexed_layout(n_words).ws_c, stream);
+    return scratch_status_then(bitop_indexed_layout(n_words).ws_c, d_scratch, stream); // (first: operands that are not segmented streams of n_words)
 }
 
 // Any number of operands, named by a table in device memory (wah_bitop_list.hip).  The scratch is that of the other indexed
@@ -1261,7 +1303,7 @@ int wah_bitop_list_indexed_device(int op, uint64_t n_words, uint64_t n_operands,
     g_err[0] = 0;
     if (op < WAH_OP_AND || op > WAH_OP_ANDNOT || !scratch_ok(d_scratch)) return refuse("bad operation or scratch pointer", WAH_ERR_ARG);
     if (!table_ok(n_operands, d_operands, n_words)) return refuse(kBadTable, WAH_ERR_ARG);
-    if (!d_out_words || (n_words && !d_out)) return refuse("null pointer", WAH_ERR_ARG);
+    if (!out_given(n_words, d_out, d_out_words)) return refuse("null pointer", WAH_ERR_ARG);
     const BitopIndexedLayout l = bitop_indexed_layout(n_words);
     if (scratch_bytes < l.total) return refuse("scratch too small", WAH_ERR_WORKSPACE);
     wah::BitopListArgs a = {};
@@ -1294,7 +1336,7 @@ int wah_bitop_clauses_indexed_device(uint64_t n_words, uint64_t n_clauses, const
     if (!table_ok(n_operands, d_operands, n_words)) return refuse(kBadTable, WAH_ERR_ARG);
     if (n_clauses < 1 || n_clauses > n_operands || !d_clause_ends || !aligned(d_clause_ends, 7))
         return refuse("between 1 and n_operands clauses in an 8-byte aligned table", WAH_ERR_ARG);
-    if (!d_out_words || (n_words && !d_out)) return refuse("null pointer", WAH_ERR_ARG);
+    if (!out_given(n_words, d_out, d_out_words)) return refuse("null pointer", WAH_ERR_ARG);
     const BitopIndexedLayout l = bitop_indexed_layout(n_words);
     if (scratch_bytes < l.total) return refuse("scratch too small", WAH_ERR_WORKSPACE);
     wah::BitopClausesArgs a = {};
@@ -1328,7 +1370,7 @@ int wah_bsi_range_indexed_device(uint64_t n_words, uint64_t n_slices, const wah_
         return refuse("between 1 and 64 slices, no flag besides WAH_BSI_EXISTS", WAH_ERR_ARG);
     if (!d_slices || !aligned(d_slices, 7) || !d_bounds || !aligned(d_bounds, 7) || !scratch_ok(d_scratch))
         return refuse("null or misaligned slice table, bounds or scratch", WAH_ERR_ARG);
-    if (!d_out_words || (n_words && !d_out) || n_words >= (1ull << 40)) return refuse("null output pointer, or 2^40 words or more", WAH_ERR_ARG);
+    if (!out_given(n_words, d_out, d_out_words) || n_words >= (1ull << 40)) return refuse("null output pointer, or 2^40 words or more", WAH_ERR_ARG);
     const BitopIndexedLayout l = bitop_indexed_layout(n_words);
     if (scratch_bytes < l.total) return refuse("scratch too small", WAH_ERR_WORKSPACE);
     wah::BsiRangeArgs a = {};
@@ -1365,15 +1407,14 @@ int wah_bsi_compare_indexed_device(int op, uint64_t n_words, uint64_t n_slices_a
         (flags & ~(WAH_BSI_EXISTS_A | WAH_BSI_EXISTS_B)))
         return refuse("between 1 and 64 slices per attribute, no flag besides WAH_BSI_EXISTS_A and WAH_BSI_EXISTS_B", WAH_ERR_ARG);
     if (!d_rows || !aligned(d_rows, 7) || !scratch_ok(d_scratch)) return refuse("null or misaligned row table or scratch", WAH_ERR_ARG);
-    if (!d_out_words || (n_words && !d_out) || n_words >= (1ull << 40)) return refuse("null output pointer, or 2^40 words or more", WAH_ERR_ARG);
+    if (!out_given(n_words, d_out, d_out_words) || n_words >= (1ull << 40)) return refuse("null output pointer, or 2^40 words or more", WAH_ERR_ARG);
     const BitopIndexedLayout l = bitop_indexed_layout(n_words);
     if (scratch_bytes < l.total) return refuse("scratch too small", WAH_ERR_WORKSPACE);
     wah::BsiCompareArgs a = {};
     a.table = reinterpret_cast<const wah::BitopListOperand *>(d_rows);
     a.n_slices_a = (uint32_t)n_slices_a;
     a.n_slices_b = (uint32_t)n_slices_b;
-    a.exists_a = (flags & WAH_BSI_EXISTS_A) ? 1u : 0u;
-    a.exists_b = (flags & WAH_BSI_EXISTS_B) ? 1u : 0u;
+    set_exists(a, flags);
     a.op = (uint32_t)op;
     return combine_then_compress(a, wah::launch_bsi_compare_segments, "compare sweep launch", n_words, d_out, out_capacity_words, d_out_words,
                                  d_out_offsets, static_cast<char *>(d_scratch), l, stream);
@@ -1391,24 +1432,44 @@ int wah_bsi_compare_status(void *d_scratch, uint64_t n_words, uint64_t n_slices_
 static_assert(WAH_BSI_KTH_ASCENDING == 0 && WAH_BSI_KTH_DESCENDING == 1 && WAH_BSI_KTH_QUANTILE == 2, "the kinds the decide kernel knows");
 static_assert(WAH_BSI_KTH_MAX_FILTERS == wah::kBsiKthMaxFilters, "one bound");
 namespace {
+// (the grouped call, further down, has the same scratch with one state and one set of histograms per select)
 struct BsiKthLayout {
     uint32_t passes;
     size_t state, hist, total;
 };
-BsiKthLayout bsi_kth_layout(uint64_t n_slices) {
+BsiKthLayout bsi_kth_layout(uint64_t n_slices, uint64_t selects, uint64_t copies) {
     BsiKthLayout l;
     if (n_slices < 1 || n_slices > WAH_BSI_MAX_SLICES) n_slices = WAH_BSI_MAX_SLICES; // (the size of a call that is refused anyway)
     l.passes = (uint32_t)ceil_div(n_slices, (uint64_t)wah::kBsiKthDigitBits);
     l.state = wah::kCtlWords * sizeof(uint32_t);
-    l.hist = l.state + round256(wah::kBsiKthStateWords * sizeof(uint64_t));
-    l.total = l.hist + round256((size_t)l.passes * wah::kBsiKthCopies * wah::kBsiKthBuckets * sizeof(uint64_t));
+    l.hist = l.state + round256((size_t)selects * wah::kBsiKthStateWords * sizeof(uint64_t));
+    l.total = l.hist + round256((size_t)l.passes * selects * copies * wah::kBsiKthBuckets * sizeof(uint64_t));
     return l;
+}
+
+// The road of both calls: everything cleared -- the control words (read by the call's *_status), the states, the histograms --
+// then per digit a pass over the bitmaps and the decision on its histograms.  a: the kernels' arguments, the scratch's areas and
+// the bitmaps' geometry filled in here.
+extern "C++" template <class Args, class Launch>
+int bsi_kth_passes(Args &a, Launch pass, Launch decide, const char *label, uint64_t n_words, char *sc, const BsiKthLayout &l, void *stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    a.state = reinterpret_cast<uint64_t *>(sc + l.state);
+    a.hist = reinterpret_cast<uint64_t *>(sc + l.hist);
+    set_walk(a, seg_geometry(n_words), sc);
+    hipError_t e = wah::launch_clear(sc, l.total, s);
+    for (uint32_t p = 0; p < l.passes && e == hipSuccess; ++p) {
+        a.pass = p;
+        e = pass(a, s);
+        if (e == hipSuccess) e = decide(a, s);
+    }
+    if (e != hipSuccess) return refuse(label, WAH_ERR_HIP, e);
+    return WAH_OK;
 }
 } // namespace
 
 size_t wah_bsi_kth_scratch_bytes(uint64_t n_words, uint64_t n_slices) {
     (void)n_words;
-    return bsi_kth_layout(n_slices).total;
+    return bsi_kth_layout(n_slices, 1, wah::kBsiKthCopies).total;
 }
 
 int wah_bsi_kth_indexed_device(uint64_t n_words, uint64_t n_filters, uint64_t n_slices, const wah_bitop_operand *d_rows,
@@ -1419,58 +1480,29 @@ int wah_bsi_kth_indexed_device(uint64_t n_words, uint64_t n_filters, uint64_t n_
     if (!d_rows || !aligned(d_rows, 7) || !d_query || !aligned(d_query, 7) || !d_result || !aligned(d_result, 7) || !scratch_ok(d_scratch))
         return refuse("null or misaligned row table, query, result or scratch", WAH_ERR_ARG);
     if (n_words >= (1ull << 40)) return refuse("2^40 words or more", WAH_ERR_ARG);
-    const BsiKthLayout l = bsi_kth_layout(n_slices);
+    const BsiKthLayout l = bsi_kth_layout(n_slices, 1, wah::kBsiKthCopies);
     if (scratch_bytes < l.total) return refuse("scratch too small", WAH_ERR_WORKSPACE);
-    char *sc = static_cast<char *>(d_scratch);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const SegGeometry g = seg_geometry(n_words);
     wah::BsiKthArgs a = {};
     a.table = reinterpret_cast<const wah::BitopListOperand *>(d_rows);
     a.query = d_query;
     a.result = d_result;
-    a.state = reinterpret_cast<uint64_t *>(sc + l.state);
-    a.hist = reinterpret_cast<uint64_t *>(sc + l.hist);
-    a.ctrl = reinterpret_cast<uint32_t *>(sc);
-    a.groups = g.groups;
-    a.n_segments = g.n_segments;
     a.n_filters = (uint32_t)n_filters;
     a.n_slices = (uint32_t)n_slices;
-    a.pad_bits = g.pad_bits;
-    hipError_t e = wah::launch_clear(sc, l.total, s); // the control words (read by wah_bsi_kth_status), the state, the histograms
-    for (uint32_t p = 0; p < l.passes && e == hipSuccess; ++p) {
-        a.pass = p;
-        e = wah::launch_bsi_kth_pass(a, s);
-        if (e == hipSuccess) e = wah::launch_bsi_kth_decide(a, s);
-    }
-    if (e != hipSuccess) return refuse("radix select launch", WAH_ERR_HIP, e);
-    return WAH_OK;
+    return bsi_kth_passes(a, wah::launch_bsi_kth_pass, wah::launch_bsi_kth_decide, "radix select launch", n_words,
+                          static_cast<char *>(d_scratch), l, stream);
 }
 
-int wah_bsi_kth_status(void *d_scratch, void *stream) {
-    if (!d_scratch) return WAH_ERR_ARG;
-    return read_status(d_scratch, stream);
-}
+int wah_bsi_kth_status(void *d_scratch, void *stream) { return scratch_status(d_scratch, stream); }
 
 // The same for every (group, query) pair of a GROUP BY at once (wah_bitop_list.hip, bsi_kth_group_pass_kernel /
 // bsi_kth_group_decide_kernel).  The scratch: control block, one decision state per select, then per pass and select its
 // histograms -- nothing of it goes with n_words.  The queries stay in device memory.
 static_assert(WAH_BSI_KTH_GROUPED_MAX_LANES == wah::kBsiKthGroupMaxSelects, "one bound");
 namespace {
-struct BsiKthGroupLayout {
-    uint32_t passes;
-    size_t state, hist, total;
-};
-BsiKthGroupLayout bsi_kth_group_layout(uint64_t n_slices, uint64_t n_groups, uint64_t n_queries) {
-    BsiKthGroupLayout l;
-    // (out of range: the size of a call that is refused anyway)
-    if (n_slices < 1 || n_slices > WAH_BSI_MAX_SLICES) n_slices = WAH_BSI_MAX_SLICES;
-    const uint64_t most = wah::kBsiKthGroupMaxSelects;
+BsiKthLayout bsi_kth_group_layout(uint64_t n_slices, uint64_t n_groups, uint64_t n_queries) {
+    const uint64_t most = wah::kBsiKthGroupMaxSelects; // (out of range: the size of a call that is refused anyway)
     const uint64_t selects = n_groups < 1 || n_queries < 1 || n_groups > most || n_queries > most || n_groups * n_queries > most ? most : n_groups * n_queries;
-    l.passes = (uint32_t)ceil_div(n_slices, (uint64_t)wah::kBsiKthDigitBits);
-    l.state = wah::kCtlWords * sizeof(uint32_t);
-    l.hist = l.state + round256((size_t)selects * wah::kBsiKthStateWords * sizeof(uint64_t));
-    l.total = l.hist + round256((size_t)l.passes * selects * wah::kBsiKthGroupCopies * wah::kBsiKthBuckets * sizeof(uint64_t));
-    return l;
+    return bsi_kth_layout(n_slices, selects, wah::kBsiKthGroupCopies);
 }
 } // namespace
 
@@ -1495,42 +1527,24 @@ int wah_bsi_kth_grouped_indexed_device(uint64_t n_words, uint64_t n_filters, con
     if (!d_queries || !aligned(d_queries, 7) || !d_results || !aligned(d_results, 7) || !scratch_ok(d_scratch))
         return refuse("null or misaligned queries, results or scratch", WAH_ERR_ARG);
     if (n_words >= (1ull << 40)) return refuse("2^40 words or more", WAH_ERR_ARG);
-    const BsiKthGroupLayout l = bsi_kth_group_layout(n_slices, n_groups, n_queries);
+    const BsiKthLayout l = bsi_kth_group_layout(n_slices, n_groups, n_queries);
     if (scratch_bytes < l.total) return refuse("scratch too small", WAH_ERR_WORKSPACE);
-    char *sc = static_cast<char *>(d_scratch);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const SegGeometry g = seg_geometry(n_words);
     wah::BsiKthGroupArgs a = {};
     a.filters = reinterpret_cast<const wah::BitopListOperand *>(d_filters);
     a.keys = reinterpret_cast<const wah::BitopListOperand *>(d_groups);
     a.slices = reinterpret_cast<const wah::BitopListOperand *>(d_slices);
     a.queries = d_queries;
     a.results = d_results;
-    a.state = reinterpret_cast<uint64_t *>(sc + l.state);
-    a.hist = reinterpret_cast<uint64_t *>(sc + l.hist);
-    a.ctrl = reinterpret_cast<uint32_t *>(sc);
-    a.groups = g.groups;
-    a.n_segments = g.n_segments;
     a.n_filters = (uint32_t)n_filters;
     a.rows_per_group = (uint32_t)rows_per_group;
     a.n_groups = (uint32_t)n_groups;
     a.n_queries = (uint32_t)n_queries;
     a.n_slices = (uint32_t)n_slices;
-    a.pad_bits = g.pad_bits;
-    hipError_t e = wah::launch_clear(sc, l.total, s); // the control words (read by wah_bsi_kth_grouped_status), the states, the histograms
-    for (uint32_t p = 0; p < l.passes && e == hipSuccess; ++p) {
-        a.pass = p;
-        e = wah::launch_bsi_kth_group_pass(a, s);
-        if (e == hipSuccess) e = wah::launch_bsi_kth_group_decide(a, s);
-    }
-    if (e != hipSuccess) return refuse("grouped radix select launch", WAH_ERR_HIP, e);
-    return WAH_OK;
+    return bsi_kth_passes(a, wah::launch_bsi_kth_group_pass, wah::launch_bsi_kth_group_decide, "grouped radix select launch", n_words,
+                          static_cast<char *>(d_scratch), l, stream);
 }
 
-int wah_bsi_kth_grouped_status(void *d_scratch, void *stream) {
-    if (!d_scratch) return WAH_ERR_ARG;
-    return read_status(d_scratch, stream);
-}
+int wah_bsi_kth_grouped_status(void *d_scratch, void *stream) { return scratch_status(d_scratch, stream); }
 
 // The values of listed rows (wah_bitop_list.hip, fetch_check_kernel / fetch_items_kernel).  The scratch: control block (with the
 // item count), then the item list: one entry per 64 listed rows and one more per segment a list can change into -- it goes
@@ -1589,31 +1603,37 @@ int wah_fetch_indexed_device(unsigned mode, uint64_t n_words, uint64_t n_operand
     return WAH_OK;
 }
 
-int wah_fetch_status(void *d_scratch, void *stream) {
-    if (!d_scratch) return WAH_ERR_ARG;
-    return read_status(d_scratch, stream);
-}
+int wah_fetch_status(void *d_scratch, void *stream) { return scratch_status(d_scratch, stream); }
 
 // Set bits counted and listed in the compressed domain (wah_select.hip).  The scratch: control block, then the positions
 // call's rank table (one u64 per segment + 1) and the two upper levels of its scan (one u64 per 4096 entries of the level
 // below) -- it goes with n_words / 992, not with the operands' number or their words.
 namespace {
+// the two upper levels of launch_select_rank_scan over `n_entries` u64, laid out from `at` on: one u64 per kRankChunk entries of
+// the level below, each level rounded up to 256 bytes
+struct ScanLevels {
+    size_t level1, level2, end;
+};
+ScanLevels scan_levels(size_t at, uint64_t n_entries) {
+    const uint64_t n1 = ceil_div(n_entries, (uint64_t)wah::kRankChunk), n2 = ceil_div(n1, (uint64_t)wah::kRankChunk);
+    ScanLevels v;
+    v.level1 = at;
+    v.level2 = v.level1 + round256(n1 * sizeof(uint64_t));
+    v.end = v.level2 + round256(n2 * sizeof(uint64_t));
+    return v;
+}
+
 struct SelectLayout {
     SegGeometry g;
-    size_t ranks, level1, level2, total;
+    size_t ranks, total;
+    ScanLevels scan;
 };
 SelectLayout select_layout(uint64_t n_words) {
     SelectLayout l;
     l.g = seg_geometry(n_words);
-    const uint64_t n0 = l.g.n_segments + 1, n1 = ceil_div(n0, (uint64_t)wah::kRankChunk), n2 = ceil_div(n1, (uint64_t)wah::kRankChunk);
-    size_t at = wah::kCtlWords * sizeof(uint32_t);
-    l.ranks = at;
-    at += round256(n0 * sizeof(uint64_t));
-    l.level1 = at;
-    at += round256(n1 * sizeof(uint64_t));
-    l.level2 = at;
-    at += round256(n2 * sizeof(uint64_t));
-    l.total = at;
+    l.ranks = wah::kCtlWords * sizeof(uint32_t);
+    l.scan = scan_levels(l.ranks + round256((l.g.n_segments + 1) * sizeof(uint64_t)), l.g.n_segments + 1);
+    l.total = l.scan.end;
     return l;
 }
 } // namespace
@@ -1636,11 +1656,8 @@ int wah_count_list_indexed_device(uint64_t n_words, uint64_t n_operands, const w
     wah::SelectCountArgs a = {};
     a.table = reinterpret_cast<const wah::BitopListOperand *>(d_operands);
     a.n_operands = (uint32_t)n_operands;
-    a.pad_bits = l.g.pad_bits;
-    a.groups = l.g.groups;
-    a.n_segments = l.g.n_segments;
     a.counts = d_counts;
-    a.ctrl = reinterpret_cast<uint32_t *>(sc);
+    set_walk(a, l.g, sc);
     hipError_t e = wah::launch_clear(sc, wah::kCtlWords * sizeof(uint32_t), s); // (read by wah_select_status)
     if (e == hipSuccess) e = wah::launch_clear(d_counts, n_operands * sizeof(uint64_t), s);
     if (e == hipSuccess) e = wah::launch_select_count(a, s);
@@ -1667,11 +1684,8 @@ int wah_count_masked_indexed_device(uint64_t n_words, uint64_t n_masks, const wa
     a.operands = reinterpret_cast<const wah::BitopListOperand *>(d_operands);
     a.n_masks = (uint32_t)n_masks;
     a.n_operands = (uint32_t)n_operands;
-    a.pad_bits = l.g.pad_bits;
-    a.groups = l.g.groups;
-    a.n_segments = l.g.n_segments;
     a.counts = d_counts;
-    a.ctrl = reinterpret_cast<uint32_t *>(sc);
+    set_walk(a, l.g, sc);
     hipError_t e = wah::launch_clear(sc, wah::kCtlWords * sizeof(uint32_t), s); // (read by wah_select_status)
     if (e == hipSuccess) e = wah::launch_clear(d_counts, n_masks * n_operands * sizeof(uint64_t), s);
     if (e == hipSuccess) e = wah::launch_count_masked(a, s);
@@ -1717,12 +1731,9 @@ int wah_group_sum_indexed_device(uint64_t n_words, uint64_t n_filters, const wah
     a.rows_per_group = (uint32_t)rows_per_group;
     a.n_groups = (uint32_t)n_groups;
     a.n_operands = (uint32_t)n_operands;
-    a.pad_bits = l.g.pad_bits;
-    a.groups = l.g.groups;
-    a.n_segments = l.g.n_segments;
     a.rows = d_group_rows;
     a.counts = d_counts;
-    a.ctrl = reinterpret_cast<uint32_t *>(sc);
+    set_walk(a, l.g, sc);
     wah::GroupFoldArgs f = {};
     f.counts = d_counts;
     f.sums = d_sums;
@@ -1758,11 +1769,8 @@ int wah_positions_indexed_device(uint64_t n_words, const uint32_t *d_stream, uin
     c.one.c_words = stream_words;
     c.one.offs = d_offsets;
     c.n_operands = 1;
-    c.pad_bits = l.g.pad_bits;
-    c.groups = l.g.groups;
-    c.n_segments = l.g.n_segments;
     c.counts = ranks;
-    c.ctrl = reinterpret_cast<uint32_t *>(sc);
+    set_walk(c, l.g, sc);
     wah::SelectEmitArgs a = {};
     a.g.comp = d_stream;
     a.g.c_words = stream_words;
@@ -1780,39 +1788,58 @@ int wah_positions_indexed_device(uint64_t n_words, const uint32_t *d_stream, uin
     hipError_t e = wah::launch_clear(sc, wah::kCtlWords * sizeof(uint32_t), s); // (read by wah_select_status)
     if (e == hipSuccess) e = wah::launch_select_count(c, s);
     if (e == hipSuccess)
-        e = wah::launch_select_rank_scan(ranks, l.g.n_segments, reinterpret_cast<uint64_t *>(sc + l.level1), reinterpret_cast<uint64_t *>(sc + l.level2), s);
+        e = wah::launch_select_rank_scan(ranks, l.g.n_segments, reinterpret_cast<uint64_t *>(sc + l.scan.level1), reinterpret_cast<uint64_t *>(sc + l.scan.level2), s);
     if (e == hipSuccess) e = wah::launch_select_emit(a, s);
     if (e != hipSuccess) return refuse("positions launch", WAH_ERR_HIP, e);
     return WAH_OK;
 }
 
-int wah_select_status(void *d_scratch, void *stream) {
-    if (!d_scratch) return WAH_ERR_ARG;
-    return read_status(d_scratch, stream);
-}
+int wah_select_status(void *d_scratch, void *stream) { return scratch_status(d_scratch, stream); }
 
 // Compressed bitmaps from sorted lists of row numbers (wah_from_positions.hip).  The scratch: control block, then the two upper
 // levels of the prefix sum over the n_lists x S + 1 index entries (one u64 per 4096 entries of the level below); the scan itself
-// runs in place in the caller's index.
+// runs in place in the caller's index.  The splice call, further down, has the same scratch with its n_pieces + 1 running starts
+// between the control block and the levels, and takes the same road.
 namespace {
-struct FromPositionsLayout {
-    uint64_t groups, n_segments, n_items;
-    size_t level1, level2, total;
+struct StreamsLayout {
+    SegGeometry g;
+    uint64_t n_items; // (segment, bitmap) pairs: one index entry each, and one at the end
+    size_t starts, total;
+    ScanLevels scan;
 };
-FromPositionsLayout from_positions_layout(uint64_t n_words, uint64_t n_lists) {
-    FromPositionsLayout l;
-    const SegGeometry g = seg_geometry(n_words);
-    l.groups = g.groups;
-    l.n_segments = g.n_segments;
-    l.n_items = n_lists * l.n_segments;
-    const uint64_t n0 = l.n_items + 1, n1 = ceil_div(n0, (uint64_t)wah::kRankChunk), n2 = ceil_div(n1, (uint64_t)wah::kRankChunk);
-    size_t at = wah::kCtlWords * sizeof(uint32_t);
-    l.level1 = at;
-    at += round256(n1 * sizeof(uint64_t));
-    l.level2 = at;
-    at += round256(n2 * sizeof(uint64_t));
-    l.total = at;
+StreamsLayout streams_layout(uint64_t n_words, uint64_t n_bitmaps, uint64_t n_starts) { // n_starts == 0: no such area, no bytes
+    StreamsLayout l;
+    l.g = seg_geometry(n_words);
+    l.n_items = n_bitmaps * l.g.n_segments;
+    l.starts = wah::kCtlWords * sizeof(uint32_t);
+    l.scan = scan_levels(l.starts + round256(n_starts * sizeof(uint64_t)), l.n_items + 1);
+    l.total = l.scan.end;
     return l;
+}
+
+// The road of the calls that write n_bitmaps streams back to back with their index: the control words cleared (read by the call's
+// *_status), `check` over the call's lists, `segments` once to count every (segment, bitmap)'s words into the caller's index, the
+// index scanned in place, `segments` again to emit.  a: the kernels' arguments, geometry and output filled in here.
+extern "C++" template <class Args, class Check, class Segments>
+int count_scan_emit(Args &a, Check check, Segments segments, const char *label, uint64_t n_words, uint32_t *d_out, uint64_t out_capacity_words,
+                    uint64_t *d_out_words, uint64_t *d_out_offsets, char *sc, const StreamsLayout &l, void *stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    a.n_bits = 32u * n_words;
+    a.groups = l.g.groups;
+    a.n_segments = l.g.n_segments;
+    a.out = d_out;
+    a.out_capacity = out_capacity_words;
+    a.out_words = d_out_words;
+    a.offsets = d_out_offsets;
+    a.ctrl = reinterpret_cast<uint32_t *>(sc);
+    hipError_t e = wah::launch_clear(sc, wah::kCtlWords * sizeof(uint32_t), s);
+    if (e == hipSuccess) e = check(a, s);
+    if (e == hipSuccess) e = segments(a, false, s);
+    if (e == hipSuccess)
+        e = wah::launch_select_rank_scan(d_out_offsets, l.n_items, reinterpret_cast<uint64_t *>(sc + l.scan.level1), reinterpret_cast<uint64_t *>(sc + l.scan.level2), s);
+    if (e == hipSuccess) e = segments(a, true, s);
+    if (e != hipSuccess) return refuse(label, WAH_ERR_HIP, e);
+    return WAH_OK;
 }
 } // namespace
 
@@ -1826,7 +1853,7 @@ uint64_t wah_from_positions_max_words(uint64_t n_words, uint64_t n_lists, uint64
     return m > (unsigned __int128)~0ull ? ~0ull : (uint64_t)m;
 }
 
-size_t wah_from_positions_scratch_bytes(uint64_t n_words, uint64_t n_lists) { return from_positions_layout(n_words, n_lists).total; }
+size_t wah_from_positions_scratch_bytes(uint64_t n_words, uint64_t n_lists) { return streams_layout(n_words, n_lists, 0).total; }
 
 int wah_from_positions_device(uint64_t n_words, uint64_t n_lists, const uint64_t *d_list_ends, const uint64_t *d_rows, uint64_t n_rows,
                               uint32_t *d_out, uint64_t out_capacity_words, uint64_t *d_out_words, uint64_t *d_out_offsets,
@@ -1834,71 +1861,27 @@ int wah_from_positions_device(uint64_t n_words, uint64_t n_lists, const uint64_t
     g_err[0] = 0;
     if (n_lists < 1 || n_lists > wah::kMaxBitopListOperands || n_words == 0 || n_words >= (1ull << 40) || n_rows >= (1ull << 40))
         return refuse("between 1 and 2^24 lists, between 1 and 2^40 - 1 words, fewer than 2^40 rows", WAH_ERR_ARG);
-    const FromPositionsLayout l = from_positions_layout(n_words, n_lists);
+    const StreamsLayout l = streams_layout(n_words, n_lists, 0);
     if (l.n_items >= (1ull << 31)) return refuse("lists x segments of 992 words: fewer than 2^31", WAH_ERR_ARG);
     if (!scratch_ok(d_scratch)) return refuse("bad scratch pointer", WAH_ERR_ARG);
     if (!d_list_ends || !aligned(d_list_ends, 7) || (n_rows && !d_rows) || !aligned(d_rows, 7))
         return refuse("null or misaligned list ends or rows", WAH_ERR_ARG);
-    if (!d_out || !aligned(d_out, 3) || !d_out_words || !aligned(d_out_words, 7) || !d_out_offsets || !aligned(d_out_offsets, 7))
-        return refuse("null or misaligned output", WAH_ERR_ARG);
+    if (!out_triple_ok(d_out, d_out_words, d_out_offsets)) return refuse("null or misaligned output", WAH_ERR_ARG);
     if (scratch_bytes < l.total) return refuse("scratch too small", WAH_ERR_WORKSPACE);
-    char *sc = static_cast<char *>(d_scratch);
-    hipStream_t s = static_cast<hipStream_t>(stream);
     wah::FromPositionsArgs a = {};
     a.rows = d_rows;
     a.list_ends = d_list_ends;
     a.n_rows = n_rows;
     a.n_lists = n_lists;
-    a.n_bits = 32u * n_words;
-    a.groups = l.groups;
-    a.n_segments = l.n_segments;
-    a.out = d_out;
-    a.out_capacity = out_capacity_words;
-    a.out_words = d_out_words;
-    a.offsets = d_out_offsets;
-    a.ctrl = reinterpret_cast<uint32_t *>(sc);
-    hipError_t e = wah::launch_clear(sc, wah::kCtlWords * sizeof(uint32_t), s); // (read by wah_from_positions_status)
-    if (e == hipSuccess) e = wah::launch_from_positions_check(a, s);
-    if (e == hipSuccess) e = wah::launch_from_positions_segments(a, false, s);
-    if (e == hipSuccess)
-        e = wah::launch_select_rank_scan(d_out_offsets, l.n_items, reinterpret_cast<uint64_t *>(sc + l.level1), reinterpret_cast<uint64_t *>(sc + l.level2), s);
-    if (e == hipSuccess) e = wah::launch_from_positions_segments(a, true, s);
-    if (e != hipSuccess) return refuse("from_positions launch", WAH_ERR_HIP, e);
-    return WAH_OK;
+    return count_scan_emit(a, wah::launch_from_positions_check, wah::launch_from_positions_segments, "from_positions launch", n_words, d_out,
+                           out_capacity_words, d_out_words, d_out_offsets, static_cast<char *>(d_scratch), l, stream);
 }
 
-int wah_from_positions_status(void *d_scratch, void *stream) {
-    if (!d_scratch) return WAH_ERR_ARG;
-    return read_status(d_scratch, stream);
-}
+int wah_from_positions_status(void *d_scratch, void *stream) { return scratch_status(d_scratch, stream); }
 
 // Row ranges of indexed bitmaps concatenated into new ones (splice_segments_kernel, wah_bitop_list.hip).  The scratch: control
 // block, the n_pieces + 1 running starts the check launch leaves, then the two upper levels of the prefix sum over the
-// n_columns x S + 1 index entries, as from_positions_layout.
-namespace {
-struct SpliceLayout {
-    uint64_t groups, n_segments, n_items;
-    size_t starts, level1, level2, total;
-};
-SpliceLayout splice_layout(uint64_t n_words_out, uint64_t n_columns, uint64_t n_pieces) {
-    SpliceLayout l;
-    const SegGeometry g = seg_geometry(n_words_out);
-    l.groups = g.groups;
-    l.n_segments = g.n_segments;
-    l.n_items = n_columns * l.n_segments;
-    const uint64_t n0 = l.n_items + 1, n1 = ceil_div(n0, (uint64_t)wah::kRankChunk), n2 = ceil_div(n1, (uint64_t)wah::kRankChunk);
-    size_t at = wah::kCtlWords * sizeof(uint32_t);
-    l.starts = at;
-    at += round256((n_pieces + 1) * sizeof(uint64_t));
-    l.level1 = at;
-    at += round256(n1 * sizeof(uint64_t));
-    l.level2 = at;
-    at += round256(n2 * sizeof(uint64_t));
-    l.total = at;
-    return l;
-}
-} // namespace
-
+// n_columns x S + 1 index entries: streams_layout, and its road.
 static_assert(sizeof(wah_splice_piece) == 24 && sizeof(wah::SplicePiece) == 24 && WAH_SPLICE_MAX_PIECES == wah::kSpliceMaxPieces, "one piece, one bound");
 
 uint64_t wah_splice_max_words(uint64_t n_words_out, uint64_t n_columns, uint64_t n_pieces, uint64_t source_words) {
@@ -1911,7 +1894,7 @@ uint64_t wah_splice_max_words(uint64_t n_words_out, uint64_t n_columns, uint64_t
 }
 
 size_t wah_splice_scratch_bytes(uint64_t n_words_out, uint64_t n_columns, uint64_t n_pieces) {
-    return splice_layout(n_words_out, n_columns, n_pieces).total;
+    return streams_layout(n_words_out, n_columns, n_pieces + 1).total;
 }
 
 int wah_splice_indexed_device(uint64_t n_words_out, uint64_t n_columns, uint64_t n_pieces, const wah_splice_piece *d_pieces,
@@ -1922,44 +1905,25 @@ int wah_splice_indexed_device(uint64_t n_words_out, uint64_t n_columns, uint64_t
         n_pieces * n_columns > wah::kMaxBitopListOperands || n_words_out == 0 || n_words_out >= (1ull << 40))
         return refuse("between 1 and 2^24 columns, between 1 and 2^16 pieces, at most 2^24 table entries, between 1 and 2^40 - 1 words",
                       WAH_ERR_ARG);
-    const SpliceLayout l = splice_layout(n_words_out, n_columns, n_pieces);
+    const StreamsLayout l = streams_layout(n_words_out, n_columns, n_pieces + 1);
     if (l.n_items >= (1ull << 31)) return refuse("columns x segments of 992 words: fewer than 2^31", WAH_ERR_ARG);
     if (!scratch_ok(d_scratch)) return refuse("bad scratch pointer", WAH_ERR_ARG);
     if (!d_pieces || !aligned(d_pieces, 7) || !d_operands || !aligned(d_operands, 7))
         return refuse("null or misaligned pieces or operand table", WAH_ERR_ARG);
-    if (!d_out || !aligned(d_out, 3) || !d_out_words || !aligned(d_out_words, 7) || !d_out_offsets || !aligned(d_out_offsets, 7))
-        return refuse("null or misaligned output", WAH_ERR_ARG);
+    if (!out_triple_ok(d_out, d_out_words, d_out_offsets)) return refuse("null or misaligned output", WAH_ERR_ARG);
     if (scratch_bytes < l.total) return refuse("scratch too small", WAH_ERR_WORKSPACE);
     char *sc = static_cast<char *>(d_scratch);
-    hipStream_t s = static_cast<hipStream_t>(stream);
     wah::SpliceArgs a = {};
     a.pieces = reinterpret_cast<const wah::SplicePiece *>(d_pieces);
     a.table = reinterpret_cast<const wah::BitopListOperand *>(d_operands);
     a.starts = reinterpret_cast<uint64_t *>(sc + l.starts);
     a.n_pieces = n_pieces;
     a.n_columns = n_columns;
-    a.n_bits = 32u * n_words_out;
-    a.groups = l.groups;
-    a.n_segments = l.n_segments;
-    a.out = d_out;
-    a.out_capacity = out_capacity_words;
-    a.out_words = d_out_words;
-    a.offsets = d_out_offsets;
-    a.ctrl = reinterpret_cast<uint32_t *>(sc);
-    hipError_t e = wah::launch_clear(sc, wah::kCtlWords * sizeof(uint32_t), s); // (read by wah_splice_status)
-    if (e == hipSuccess) e = wah::launch_splice_check(a, s);
-    if (e == hipSuccess) e = wah::launch_splice_segments(a, false, s);
-    if (e == hipSuccess)
-        e = wah::launch_select_rank_scan(d_out_offsets, l.n_items, reinterpret_cast<uint64_t *>(sc + l.level1), reinterpret_cast<uint64_t *>(sc + l.level2), s);
-    if (e == hipSuccess) e = wah::launch_splice_segments(a, true, s);
-    if (e != hipSuccess) return refuse("splice launch", WAH_ERR_HIP, e);
-    return WAH_OK;
+    return count_scan_emit(a, wah::launch_splice_check, wah::launch_splice_segments, "splice launch", n_words_out, d_out, out_capacity_words,
+                           d_out_words, d_out_offsets, sc, l, stream);
 }
 
-int wah_splice_status(void *d_scratch, void *stream) {
-    if (!d_scratch) return WAH_ERR_ARG;
-    return read_status(d_scratch, stream);
-}
+int wah_splice_status(void *d_scratch, void *stream) { return scratch_status(d_scratch, stream); }
 
 // A bit-sliced index from a column of values (wah_bsi_build.hip): the transpose writes the decoded slice matrix into the scratch,
 // the compress passes run over it as over any column matrix.  The scratch: [control words][slice matrix][compress workspace] --
@@ -1976,6 +1940,15 @@ BsiBuildLayout bsi_build_layout(uint64_t n_words, uint64_t n_slices) { // n_slic
     l.total = l.ws_c + round256(l.ws_c_bytes);
     return l;
 }
+inline uint32_t *bsi_matrix(char *sc, const BsiBuildLayout &l) { return reinterpret_cast<uint32_t *>(sc + l.matrix); }
+
+// The road: launch_then_compress with a sweep that writes the decoded matrix of n_slices x n_words words
+extern "C++" template <class Args, class Launch>
+int sweep_then_compress(const Args &a, Launch launch, const char *label, uint64_t n_words, uint64_t n_slices, uint32_t *d_out,
+                        uint64_t out_capacity_words, uint64_t *d_out_words, uint64_t *d_out_offsets, char *sc, const BsiBuildLayout &l, void *stream) {
+    return launch_then_compress(a, launch, label, bsi_matrix(sc, l), n_slices * n_words, d_out, out_capacity_words, d_out_words, d_out_offsets,
+                                sc, l.ws_c, l.ws_c_bytes, stream);
+}
 } // namespace
 
 size_t wah_bsi_build_scratch_bytes(uint64_t n_words, uint64_t n_slices) { return bsi_build_layout(n_words, n_slices).total; }
@@ -1990,32 +1963,25 @@ int wah_bsi_build_device(uint64_t n_words, uint64_t n_bits, const uint64_t *d_va
         return refuse("slices of a multiple of 992 words, all slices together fewer than 2^40 words", WAH_ERR_ARG);
     if (n_rows > 32u * n_words) return refuse("more rows than a slice has bits", WAH_ERR_ARG);
     if ((n_rows && !d_values) || !aligned(d_values, 7)) return refuse("null or misaligned values", WAH_ERR_ARG);
-    if (!d_out || !aligned(d_out, 3) || !d_out_words || !aligned(d_out_words, 7) || !d_out_offsets || !aligned(d_out_offsets, 7))
-        return refuse("null or misaligned output", WAH_ERR_ARG);
+    if (!out_triple_ok(d_out, d_out_words, d_out_offsets)) return refuse("null or misaligned output", WAH_ERR_ARG);
     if (!scratch_ok(d_scratch)) return refuse("bad scratch pointer", WAH_ERR_ARG);
     const BsiBuildLayout l = bsi_build_layout(n_words, n_slices);
     if (scratch_bytes < l.total) return refuse("scratch too small", WAH_ERR_WORKSPACE);
     char *sc = static_cast<char *>(d_scratch);
-    hipStream_t s = static_cast<hipStream_t>(stream);
     wah::BsiBuildArgs a = {};
     a.values = d_values;
     a.exists = d_exists;
     a.n_rows = n_rows;
     a.n_words = n_words;
     a.n_bits = (uint32_t)n_bits;
-    a.out = reinterpret_cast<uint32_t *>(sc + l.matrix);
+    a.out = bsi_matrix(sc, l);
     a.ctrl = reinterpret_cast<uint32_t *>(sc);
-    hipError_t e = wah::launch_clear(sc, wah::kCtlWords * sizeof(uint32_t), s); // (read by wah_bsi_build_status)
-    if (e == hipSuccess) e = wah::launch_bsi_slices(a, s);
-    if (e != hipSuccess) return refuse("slice transpose launch", WAH_ERR_HIP, e);
-    return compress_device_impl(a.out, nullptr, 0, nullptr, n_slices * n_words, d_out, out_capacity_words, d_out_words, d_out_offsets,
-                                sc + l.ws_c, l.ws_c_bytes, stream, true);
+    return sweep_then_compress(a, wah::launch_bsi_slices, "slice transpose launch", n_words, n_slices, d_out, out_capacity_words, d_out_words,
+                               d_out_offsets, sc, l, stream);
 }
 
 int wah_bsi_build_status(void *d_scratch, uint64_t n_words, uint64_t n_slices, void *stream) {
-    if (!d_scratch) return WAH_ERR_ARG;
-    const int rc = read_status(d_scratch, stream); // the transpose: a value at or above 2^n_bits
-    return rc != WAH_OK ? rc : read_status(static_cast<char *>(d_scratch) + bsi_build_layout(n_words, n_slices).ws_c, stream);
+    return scratch_status_then(bsi_build_layout(n_words, n_slices).ws_c, d_scratch, stream); // (first the transpose: a value at or above 2^n_bits)
 }
 
 // A + B, A - B row by row over two bit-sliced attributes, as a new one (wah_bitop_list.hip, bsi_arith_segments_kernel).  The
@@ -2034,9 +2000,24 @@ int two_attribute_args(uint64_t n_words, uint64_t n_slices_a, uint64_t n_slices_
     if (n_words == 0 || n_words % wah::kSegWords || n_words >= (1ull << 40) || arith_rows_out(n_slices_out, flags) * n_words >= (1ull << 40))
         return refuse("slices of a multiple of 992 words, all slices of the result together fewer than 2^40 words", WAH_ERR_ARG);
     if (!d_rows || !aligned(d_rows, 7) || !scratch_ok(d_scratch)) return refuse("null or misaligned row table or scratch", WAH_ERR_ARG);
-    if (!d_out || !aligned(d_out, 3) || !d_out_words || !aligned(d_out_words, 7) || !d_out_offsets || !aligned(d_out_offsets, 7))
-        return refuse("null or misaligned output", WAH_ERR_ARG);
+    if (!out_triple_ok(d_out, d_out_words, d_out_offsets)) return refuse("null or misaligned output", WAH_ERR_ARG);
     return WAH_OK;
+}
+// ... and what the arguments of both sweeps hold
+extern "C++" template <class Args>
+void two_attribute_fill(Args &a, uint64_t n_words, uint64_t n_slices_a, uint64_t n_slices_b, uint64_t n_slices_out, const wah_bitop_operand *d_rows,
+                        unsigned flags, char *sc, const BsiBuildLayout &l) {
+    const SegGeometry g = seg_geometry(n_words);
+    a.table = reinterpret_cast<const wah::BitopListOperand *>(d_rows);
+    a.matrix = bsi_matrix(sc, l);
+    a.ctrl = reinterpret_cast<uint32_t *>(sc);
+    a.n_words = n_words;
+    a.groups = g.groups;
+    a.n_segments = g.n_segments;
+    a.n_slices_a = (uint32_t)n_slices_a;
+    a.n_slices_b = (uint32_t)n_slices_b;
+    a.n_slices_out = (uint32_t)n_slices_out;
+    set_exists(a, flags);
 }
 } // namespace
 
@@ -2055,33 +2036,16 @@ int wah_bsi_arith_indexed_device(int op, uint64_t n_words, uint64_t n_slices_a, 
     const BsiBuildLayout l = bsi_build_layout(n_words, rows_out);
     if (scratch_bytes < l.total) return refuse("scratch too small", WAH_ERR_WORKSPACE);
     char *sc = static_cast<char *>(d_scratch);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const SegGeometry g = seg_geometry(n_words);
     wah::BsiArithArgs a = {};
-    a.table = reinterpret_cast<const wah::BitopListOperand *>(d_rows);
-    a.matrix = reinterpret_cast<uint32_t *>(sc + l.matrix);
-    a.ctrl = reinterpret_cast<uint32_t *>(sc);
-    a.n_words = n_words;
-    a.groups = g.groups;
-    a.n_segments = g.n_segments;
-    a.n_slices_a = (uint32_t)n_slices_a;
-    a.n_slices_b = (uint32_t)n_slices_b;
-    a.n_slices_out = (uint32_t)n_slices_out;
-    a.exists_a = (flags & WAH_BSI_EXISTS_A) ? 1u : 0u;
-    a.exists_b = (flags & WAH_BSI_EXISTS_B) ? 1u : 0u;
+    two_attribute_fill(a, n_words, n_slices_a, n_slices_b, n_slices_out, d_rows, flags, sc, l);
     a.sub = op == WAH_ARITH_SUB ? 1u : 0u;
-    hipError_t e = wah::launch_clear(sc, wah::kCtlWords * sizeof(uint32_t), s); // (read by wah_bsi_arith_status)
-    if (e == hipSuccess) e = wah::launch_bsi_arith_segments(a, s);
-    if (e != hipSuccess) return refuse("arithmetic sweep launch", WAH_ERR_HIP, e);
-    return compress_device_impl(a.matrix, nullptr, 0, nullptr, rows_out * n_words, d_out, out_capacity_words, d_out_words, d_out_offsets,
-                                sc + l.ws_c, l.ws_c_bytes, stream, true);
+    return sweep_then_compress(a, wah::launch_bsi_arith_segments, "arithmetic sweep launch", n_words, rows_out, d_out, out_capacity_words,
+                               d_out_words, d_out_offsets, sc, l, stream);
 }
 
 int wah_bsi_arith_status(void *d_scratch, uint64_t n_words, uint64_t n_slices_out, unsigned flags, void *stream) {
-    if (!d_scratch) return WAH_ERR_ARG;
-    const int rc = read_status(d_scratch, stream); // the sweep: everything the list call refuses in an operand
-    if (rc != WAH_OK) return rc;
-    return read_status(static_cast<char *>(d_scratch) + bsi_build_layout(n_words, arith_rows_out(n_slices_out, flags)).ws_c, stream);
+    // (first the sweep: everything the list call refuses in an operand)
+    return scratch_status_then(bsi_build_layout(n_words, arith_rows_out(n_slices_out, flags)).ws_c, d_scratch, stream);
 }
 
 // A * B row by row over two bit-sliced attributes, as a new one (wah_bitop_list.hip, bsi_mul_segments_kernel).  The arithmetic
@@ -2107,34 +2071,16 @@ int wah_bsi_mul_indexed_device(uint64_t n_words, uint64_t n_slices_a, uint64_t n
     const BsiBuildLayout l = bsi_build_layout(n_words, rows_out);
     if (scratch_bytes < l.total + mul_work_bytes(n_words, n_slices_a, n_slices_out)) return refuse("scratch too small", WAH_ERR_WORKSPACE);
     char *sc = static_cast<char *>(d_scratch);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const SegGeometry g = seg_geometry(n_words);
     wah::BsiMulArgs a = {};
-    a.table = reinterpret_cast<const wah::BitopListOperand *>(d_rows);
-    a.matrix = reinterpret_cast<uint32_t *>(sc + l.matrix);
+    two_attribute_fill(a, n_words, n_slices_a, n_slices_b, n_slices_out, d_rows, flags, sc, l);
     a.work = reinterpret_cast<uint32_t *>(sc + l.total); // (a multiple of 256 bytes: the quads are aligned)
-    a.ctrl = reinterpret_cast<uint32_t *>(sc);
-    a.n_words = n_words;
-    a.groups = g.groups;
-    a.n_segments = g.n_segments;
-    a.n_slices_a = (uint32_t)n_slices_a;
-    a.n_slices_b = (uint32_t)n_slices_b;
-    a.n_slices_out = (uint32_t)n_slices_out;
-    a.exists_a = (flags & WAH_BSI_EXISTS_A) ? 1u : 0u;
-    a.exists_b = (flags & WAH_BSI_EXISTS_B) ? 1u : 0u;
-    hipError_t e = wah::launch_clear(sc, wah::kCtlWords * sizeof(uint32_t), s); // (read by wah_bsi_mul_status)
-    if (e == hipSuccess) e = wah::launch_bsi_mul_segments(a, s);
-    if (e != hipSuccess) return refuse("multiplication sweep launch", WAH_ERR_HIP, e);
-    return compress_device_impl(a.matrix, nullptr, 0, nullptr, rows_out * n_words, d_out, out_capacity_words, d_out_words, d_out_offsets,
-                                sc + l.ws_c, l.ws_c_bytes, stream, true);
+    return sweep_then_compress(a, wah::launch_bsi_mul_segments, "multiplication sweep launch", n_words, rows_out, d_out, out_capacity_words,
+                               d_out_words, d_out_offsets, sc, l, stream);
 }
 
 int wah_bsi_mul_status(void *d_scratch, uint64_t n_words, uint64_t n_slices_a, uint64_t n_slices_out, unsigned flags, void *stream) {
     (void)n_slices_a; // (the working area lies behind everything the status reads)
-    if (!d_scratch) return WAH_ERR_ARG;
-    const int rc = read_status(d_scratch, stream); // the sweep: everything the list call refuses in an operand
-    if (rc != WAH_OK) return rc;
-    return read_status(static_cast<char *>(d_scratch) + bsi_build_layout(n_words, arith_rows_out(n_slices_out, flags)).ws_c, stream);
+    return wah_bsi_arith_status(d_scratch, n_words, n_slices_out, flags, stream);
 }
 
 // ---------------------------------------------------------------------------
