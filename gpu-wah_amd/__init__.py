@@ -85,6 +85,9 @@ from .api import (  # noqa: F401
     splice_pieces,
     splice_max_words,
     SPLICE_MAX_PIECES,
+    compact_device,
+    compact_max_words,
+    COMPACT_DELETE,
     bsi_build_device,
     merge_fills_device,
     StreamReport,

@@ -101,6 +101,10 @@ ABI_SYMBOLS = {
     "wah_splice_scratch_bytes": (_sz, [_u64, _u64, _u64]),
     "wah_splice_indexed_device": (_int, [_u64, _u64, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
     "wah_splice_status": (_int, [_vp, _vp]),
+    "wah_compact_max_words": (_u64, [_u64, _u64, _u64]),
+    "wah_compact_scratch_bytes": (_sz, [_u64, _u64, _u64]),
+    "wah_compact_indexed_device": (_int, [_u64, _u64, ctypes.c_uint32, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "wah_compact_status": (_int, [_vp, _vp]),
     "wah_bsi_build_scratch_bytes": (_sz, [_u64, _u64]),
     "wah_bsi_build_device": (_int, [_u64, _u64, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
     "wah_bsi_build_status": (_int, [_vp, _u64, _u64, _vp]),
@@ -1169,6 +1173,50 @@ def splice_device(pieces, table, n_columns, n_words_out, source_words=None, scra
         lambda: max(k * max_compressed_words(n) if source_words is None else splice_max_words(n, k, p, source_words), 1),
         lambda *tail: lib().wah_splice_indexed_device(n, k, p, pieces.data_ptr(), table.data_ptr(), *tail),
         lib().wah_splice_status, scratch, out, out_offsets, check)
+
+
+COMPACT_DELETE = 1  # WAH_COMPACT_DELETE
+
+
+def compact_max_words(n_words_out, n_columns, source_words):
+    return int(lib().wah_compact_max_words(int(n_words_out), int(n_columns), int(source_words)))
+
+
+def compact_device(mask, table, n_words, n_rows, n_words_out, delete=False, source_words=None, scratch=None, out=None, out_offsets=None,
+                   out_rows=None, check=True):
+    """The rows a mask bitmap selects of every column of an index moved together into new indexed bitmaps, without a decoded
+    bitmap (wah_compact_indexed_device).  mask: a (stream, seg_offsets) pair or a ready [1, 3] operand table; table: the
+    [n_columns, 3] operand table of the columns (bitop_operand_table, columns.column_operand_table), or a list of pairs -- all
+    bitmaps of n_words words, only the device reads them.  Only positions below n_rows are rows.  A row is selected where its
+    mask bit is 1, with delete=True where it is 0; output column c holds column c's bits at the selected rows, in order, and
+    zeros behind them, in n_words_out words.  Returns (stream, seg_offsets, rows): the columns' compress() streams back to back,
+    the n_columns * S + 1 entries of their segment index (S = segments of one output bitmap), as splice_device, and a
+    one-element int64 device tensor that holds the number of selected rows.  source_words: an upper bound on the words of the
+    column segments that are read, which sizes a default out by wah_compact_max_words (None: the bound that always holds,
+    n_columns * wah_max_compressed_words(n_words_out)); scratch / out / out_offsets / out_rows: reuse these tensors;
+    check=False: only enqueue and return (out, count tensor, out_offsets, rows)."""
+    torch = _torch()
+    table = _operand_table(table)
+    dev = table.device
+    if not isinstance(mask, torch.Tensor):
+        mask = [tuple(mask)]
+    mask = _operand_table(mask, "the mask")
+    if int(mask.shape[0]) != 1 or mask.device != dev:
+        raise WahError("the mask is one operand on the table's device")
+    n, r, n_out, k = int(n_words), int(n_rows), int(n_words_out), int(table.shape[0])
+    if r < 0 or r > 32 * n:
+        raise WahError("n_rows lies between 0 and 32 * n_words")
+    rows = _int64_tensor(torch, out_rows, (1,), dev, "out_rows: a contiguous int64 tensor of one entry on the table's device")
+    flags = COMPACT_DELETE if delete else 0
+    n_seg = (max_compressed_words(n_out) + 1023) // 1024
+    got = _compressed_streams(
+        "wah_compact_indexed_device", "compact", dev, k * n_seg + 1,
+        "out_offsets: a contiguous int64 tensor of n_columns * segments + 1 entries on the table's device",
+        lambda: lib().wah_compact_scratch_bytes(n, n_out, k),
+        lambda: max(k * max_compressed_words(n_out) if source_words is None else compact_max_words(n_out, k, source_words), 1),
+        lambda *tail: lib().wah_compact_indexed_device(n, r, flags, mask.data_ptr(), k, table.data_ptr(), n_out, *tail[:4], rows.data_ptr(), *tail[4:]),
+        lib().wah_compact_status, scratch, out, out_offsets, check)
+    return got + (rows,)
 
 
 def bsi_build_device(values, n_bits, n_words, exists=None, scratch=None, out=None, out_offsets=None, check=True):

@@ -898,6 +898,61 @@ def slice_rows(wah, index, first, n_rows):
     return splice_columns(wah, [(tuple(index[:3]), first, n_rows)]) + tuple(index[3:])
 
 
+def _compact_rows(wah, index, mask, n_rows, n_rows_out, delete, reuse):
+    """keep_rows / delete_rows: the index's columns through api.compact_device, the result sized by n_rows_out or, when that is
+    None, by the count read back."""
+    import torch
+
+    if len(index) not in (3, 5):
+        raise ValueError("index is an index_from_keys result or a bsi_from_values result")
+    stream, seg_offsets, n = index[:3]
+    k = _index_columns(seg_offsets, n)
+    n_rows = int(n_rows)
+    if k < 1 or n_rows < 0 or n_rows > 32 * int(n):
+        raise ValueError("an index of at least one column, and rows that lie inside its columns")
+    if len(mask) != 2:
+        raise ValueError("mask is a (stream, seg_offsets) pair")
+    bound = n_rows if n_rows_out is None else int(n_rows_out)
+    if bound < 0:
+        raise ValueError("n_rows_out is not negative")
+    n_out = max(-(-((bound + 31) // 32) // SEGMENT_WORDS), 1) * SEGMENT_WORDS
+    check = reuse.pop("check", True)
+    if n_rows_out is None and not check:
+        raise ValueError("check=False needs n_rows_out: the exact size comes from a count that is read back")
+    table = column_operand_table(stream, seg_offsets, n, torch.arange(k, dtype=torch.int64, device=stream.device))
+    got = wah.compact_device(tuple(mask), table, n, n_rows, n_out, delete=delete, check=check, **reuse)
+    result, rows = (got[0], got[-2], n_out), got[-1]
+    if n_rows_out is None:
+        exact = max(-(-int(rows.item()) // (31 * 1024)), 1) * SEGMENT_WORDS
+        if exact < n_out:  # the segments behind the last selected row are cut off: a window of the result's first rows
+            result = splice_columns(wah, [(result, 0, 32 * exact)], n_words_per_column=exact)
+    return result + tuple(index[3:]), rows
+
+
+def keep_rows(wah, index, mask, n_rows, n_rows_out=None, **reuse):
+    """`CREATE TABLE s AS SELECT * FROM t WHERE ...`, a sample, the rows a first filter kept: of the first n_rows rows of every
+    column of `index`, those whose bit is set in `mask`, moved together in their order, in one call that decodes no bitmap
+    (wah_compact_indexed_device).  index: the 3-tuple of index_from_keys or the 5-tuple of bsi_from_values, or a result of
+    append_rows / slice_rows / keep_rows / delete_rows -- the existence slice of a bit-sliced index is compacted like any other
+    column.  mask: a (stream, seg_offsets) pair over the index's column length, as filter_columns, range_column and
+    compare_columns return it (the stream may be a whole output buffer of a call that was only enqueued: its index bounds what is
+    read); what it holds at or behind n_rows selects nothing.  Returns (index of the same kind, rows): row i of the result is the
+    i-th selected row, the rows behind them are empty, and rows is a one-element int64 device tensor, the number of selected rows.
+    n_rows_out: an upper bound on that number (n_rows itself always suffices; more selected rows than 32 * the column length it
+    gives are refused, WAH_ERR_STREAM) -- the result's column length is the bound rounded up to a multiple of 992 words and
+    nothing is read back.  n_rows_out=None: the result is sized exactly, to max(1, ceil(rows / 31744)) segments per column; for
+    that the 8-byte count is read back once, which SYNCHRONISES the stream.  reuse: source_words / scratch / out / out_offsets /
+    out_rows / check of api.compact_device (check=False, which needs n_rows_out, returns the whole output buffer as the stream)."""
+    return _compact_rows(wah, index, mask, n_rows, n_rows_out, False, reuse)
+
+
+def delete_rows(wah, index, mask, n_rows, n_rows_out=None, **reuse):
+    """`DELETE FROM t WHERE ...`, the drop of tomb-stoned rows: keep_rows with the mask complemented -- of the first n_rows rows,
+    those whose bit in `mask` is CLEAR survive (WAH_COMPACT_DELETE).  Arguments, result and the synchronisation of
+    n_rows_out=None as keep_rows."""
+    return _compact_rows(wah, index, mask, n_rows, n_rows_out, True, reuse)
+
+
 def compress_column_ranges(compressor, flat, lengths, wait=True):
     """Columns of DIFFERENT lengths (each a multiple of 992 words) stored back to back in `flat`: still one launch.
     Returns (stream, column_offsets) like compress_column_matrix: column c is stream[column_offsets[c] :

@@ -1925,6 +1925,75 @@ int wah_splice_indexed_device(uint64_t n_words_out, uint64_t n_columns, uint64_t
 
 int wah_splice_status(void *d_scratch, void *stream) { return scratch_status(d_scratch, stream); }
 
+// The rows a mask bitmap selects of every column of an index, moved together into new indexed bitmaps (wah_compact.hip).  The
+// scratch: the splice call's, with the S_src + 1 running ranks of the mask's segments in the starts' place, then the two upper
+// levels of the prefix sum over those ranks: streams_layout and its road, the rank pass being the road's check.
+namespace {
+struct CompactLayout {
+    StreamsLayout s;
+    SegGeometry src;
+    ScanLevels ranks;
+    size_t total;
+};
+CompactLayout compact_layout(uint64_t n_words, uint64_t n_words_out, uint64_t n_columns) {
+    CompactLayout l;
+    l.src = seg_geometry(n_words);
+    l.s = streams_layout(n_words_out, n_columns, l.src.n_segments + 1);
+    l.ranks = scan_levels(l.s.total, l.src.n_segments + 1);
+    l.total = l.ranks.end;
+    return l;
+}
+} // namespace
+
+uint64_t wah_compact_max_words(uint64_t n_words_out, uint64_t n_columns, uint64_t source_words) {
+    const SegGeometry g = seg_geometry(n_words_out);
+    const unsigned __int128 columns = n_columns;
+    const unsigned __int128 all_literals = columns * g.groups;
+    const unsigned __int128 by_words = columns * (g.n_segments + 1) + 2 * (unsigned __int128)source_words;
+    const unsigned __int128 m = all_literals < by_words ? all_literals : by_words;
+    return m > (unsigned __int128)~0ull ? ~0ull : (uint64_t)m;
+}
+
+size_t wah_compact_scratch_bytes(uint64_t n_words, uint64_t n_words_out, uint64_t n_columns) {
+    return compact_layout(n_words, n_words_out, n_columns).total;
+}
+
+int wah_compact_indexed_device(uint64_t n_words, uint64_t n_rows, uint32_t flags, const wah_bitop_operand *d_mask, uint64_t n_columns,
+                               const wah_bitop_operand *d_operands, uint64_t n_words_out, uint32_t *d_out, uint64_t out_capacity_words,
+                               uint64_t *d_out_words, uint64_t *d_out_offsets, uint64_t *d_out_rows, void *d_scratch, size_t scratch_bytes,
+                               void *stream) {
+    g_err[0] = 0;
+    if (n_columns < 1 || n_columns > wah::kMaxBitopListOperands || n_words == 0 || n_words >= (1ull << 40) || n_words_out == 0 ||
+        n_words_out >= (1ull << 40))
+        return refuse("between 1 and 2^24 columns, between 1 and 2^40 - 1 words in and out", WAH_ERR_ARG);
+    if (n_rows > 32u * n_words) return refuse("more rows than 32 * n_words", WAH_ERR_ARG);
+    if ((flags & ~WAH_COMPACT_DELETE) != 0u) return refuse("unknown flag bits", WAH_ERR_ARG);
+    const CompactLayout l = compact_layout(n_words, n_words_out, n_columns);
+    if (l.s.n_items >= (1ull << 31)) return refuse("columns x segments of 992 words: fewer than 2^31", WAH_ERR_ARG);
+    if (!scratch_ok(d_scratch)) return refuse("bad scratch pointer", WAH_ERR_ARG);
+    if (!d_mask || !aligned(d_mask, 7) || !d_operands || !aligned(d_operands, 7)) return refuse("null or misaligned mask or operand table", WAH_ERR_ARG);
+    if (!out_triple_ok(d_out, d_out_words, d_out_offsets) || !d_out_rows || !aligned(d_out_rows, 7))
+        return refuse("null or misaligned output", WAH_ERR_ARG);
+    if (scratch_bytes < l.total) return refuse("scratch too small", WAH_ERR_WORKSPACE);
+    char *sc = static_cast<char *>(d_scratch);
+    wah::CompactArgs a = {};
+    a.mask = reinterpret_cast<const wah::BitopListOperand *>(d_mask);
+    a.table = reinterpret_cast<const wah::BitopListOperand *>(d_operands);
+    a.starts = reinterpret_cast<uint64_t *>(sc + l.s.starts);
+    a.level1 = reinterpret_cast<uint64_t *>(sc + l.ranks.level1);
+    a.level2 = reinterpret_cast<uint64_t *>(sc + l.ranks.level2);
+    a.out_rows = d_out_rows;
+    a.n_columns = n_columns;
+    a.src_rows = n_rows;
+    a.src_groups = l.src.groups;
+    a.src_segments = l.src.n_segments;
+    a.del = (flags & WAH_COMPACT_DELETE) ? 1u : 0u;
+    return count_scan_emit(a, wah::launch_compact_check, wah::launch_compact_segments, "compact launch", n_words_out, d_out, out_capacity_words,
+                           d_out_words, d_out_offsets, sc, l.s, stream);
+}
+
+int wah_compact_status(void *d_scratch, void *stream) { return scratch_status(d_scratch, stream); }
+
 // A bit-sliced index from a column of values (wah_bsi_build.hip): the transpose writes the decoded slice matrix into the scratch,
 // the compress passes run over it as over any column matrix.  The scratch: [control words][slice matrix][compress workspace] --
 // the layout of every call that leaves a whole attribute (wah_bsi_arith_indexed_device below: its sweep writes the matrix).

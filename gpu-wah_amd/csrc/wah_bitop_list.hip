@@ -327,6 +327,13 @@ __device__ __forceinline__ void report_stream_error(u32 *ctrl, u32 lane) {
     if (lane == 0) atomicOr(ctrl + kCtlError, kErrStream);
 }
 
+// wah_compact.hip, a translation unit of its own, includes this file for the walk above and nothing else: the walk is stated
+// once, here, where its callers and the tests that read its constants look for it.
+#ifdef WAH_LIST_WALK_ONLY
+} // namespace
+} // namespace wah
+#else
+
 // the wave's result, value_of_step(s) for group 64 s + lane, as the segment's decoded words (seg_store: 31 -> 32 repack); groups at
 // and behind nvalid are written as zero
 template <class ValueOfStep>
@@ -1626,3 +1633,4 @@ hipError_t launch_bsi_kth_group_decide(const BsiKthGroupArgs &a, hipStream_t s) 
 }
 
 } // namespace wah
+#endif // WAH_LIST_WALK_ONLY

@@ -513,6 +513,33 @@ struct SpliceArgs {
 hipError_t launch_splice_check(const SpliceArgs &a, hipStream_t s);
 hipError_t launch_splice_segments(const SpliceArgs &a, bool emit, hipStream_t s);
 
+// wah_compact_indexed_device (wah_compact.hip): the rows a mask bitmap selects (or, with del, does not select) of every column of
+// an index, moved together into new indexed bitmaps.  mask and table are read by the device only; the check launches leave the
+// selected rows in front of every source segment, then their total T, in `starts` (src_segments + 1 entries; level1 / level2: the
+// upper levels of that scan); offsets is used as FromPositionsArgs::offsets, n_columns * n_segments + 1 entries.
+struct CompactArgs {
+    const BitopListOperand *mask;  // one row
+    const BitopListOperand *table; // n_columns rows
+    uint64_t *starts;              // scratch: src_segments + 1
+    uint64_t *level1, *level2;     // scratch: launch_select_rank_scan's levels over starts
+    uint64_t *out_rows;            // receives T
+    uint64_t n_columns;
+    uint64_t src_rows;             // n_rows: only positions below it are rows
+    uint64_t src_groups;           // G of ONE source bitmap
+    uint64_t src_segments;         // ceil(src_groups / 1024)
+    uint32_t del;                  // 0: a row is selected where the mask bit is 1; 1: where it is 0
+    uint64_t n_bits;               // 32 n_words_out: T is at most this
+    uint64_t groups;               // G of ONE output bitmap
+    uint64_t n_segments;           // S = ceil(G / 1024), per column
+    uint32_t *out;
+    uint64_t out_capacity;
+    uint64_t *out_words;
+    uint64_t *offsets;
+    uint32_t *ctrl;
+};
+hipError_t launch_compact_check(const CompactArgs &a, hipStream_t s);
+hipError_t launch_compact_segments(const CompactArgs &a, bool emit, hipStream_t s);
+
 // wah_bsi_build_device (wah_bsi_build.hip): a column of 64-bit values in, the decoded slice matrix [n_bits (+ 1), n_words] out --
 // most significant slice first, the existence bitmap last when exists != nullptr.  Every word of the matrix is written.
 struct BsiBuildArgs {

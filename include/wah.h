@@ -968,6 +968,64 @@ int wah_splice_indexed_device(uint64_t n_words_out, uint64_t n_columns, uint64_t
                               uint64_t *d_out_words, uint64_t *d_out_offsets, void *d_scratch, size_t scratch_bytes, void *stream);
 int wah_splice_status(void *d_scratch, void *stream);
 
+/* The call that changes an index by a PREDICATE: the rows a mask bitmap selects of every column of an index, moved together into
+ * new indexed bitmaps -- DELETE FROM t WHERE ... (WAH_COMPACT_DELETE: the rows the mask does NOT name survive), CREATE TABLE s AS
+ * SELECT * FROM t WHERE ..., a sample, the drop of tomb-stoned rows, "the next twenty queries on the rows the first filter kept".
+ * The splice call moves row RANGES the host knows; this one moves scattered rows only the device knows.  Not in the reference.
+ *   d_mask: ONE wah_bitop_operand in DEVICE memory, 8-byte aligned; d_operands: n_columns of them.  All are indexed bitmaps of
+ *   n_words words as for the list call (windows into column matrices allowed, stream_words may be a capacity, streams compress()
+ *   never emits are legal).  The mask may be the output of a clause, list or range call enqueued before this one on the same
+ *   stream and not yet checked.
+ * Only positions p < n_rows are rows, n_rows <= 32 * n_words: a position at or behind n_rows is never selected and never carried,
+ * whatever the mask or a column holds there, the pad bits of the last group included.  A row is selected where the mask bit is 1
+ * (flags == 0) or where it is 0 (WAH_COMPACT_DELETE).  With T the number of selected rows, output bitmap c has n_words_out words;
+ * its position k is column c's bit at the k-th selected row for k < T, and every position at or behind T is zero.  *d_out_rows
+ * receives T.  The output is laid out exactly as wah_splice_indexed_device's: d_out receives the n_columns compress() streams
+ * back to back, word for word, whatever form the sources had; d_out_offsets (required) receives n_columns * S_out + 1 entries
+ * counted from d_out[0], S_out = ceil(G_out / 1024), G_out = wah_max_compressed_words(n_words_out); d_out_words receives the
+ * total, also when it exceeds the capacity.
+ *   wah_compact_max_words: an out_capacity_words that always suffices:
+ *   min(n_columns * G_out, n_columns * (S_out + 1) + 2 * source_words), saturating at UINT64_MAX.  source_words is any upper bound
+ *   the caller has on the words of the column segments that are read; the columns' whole streams are one.
+ *   Why it holds: the surviving bits of a source word are consecutive in the output.  Those of a literal (at most 31) meet at most
+ *   two output groups; those of a fill are one run, which leaves one fill word and at most one group where it ends inside an
+ *   output group -- the group where it begins is the one where its predecessor ended, and is charged there (2 * source_words).
+ *   Removing rows between two runs only merges them.  Every output segment cuts at most one run, and the zeros behind T are one
+ *   more run (n_columns * (S_out + 1)).
+ *   d_scratch: wah_compact_scratch_bytes(n_words, n_words_out, n_columns) bytes, 256-byte aligned, no initialisation:
+ *   1024 (the control words) + round256(8 * R) (the running ranks: the selected rows in front of every source segment, then T)
+ *   + L(E) + L(R), with R = S_src + 1, S_src = ceil(wah_max_compressed_words(n_words) / 1024), E = n_columns * S_out + 1 and
+ *   L(x) = round256(8 * ceil(x / 4096)) + round256(8 * ceil(ceil(x / 4096) / 4096)) the two upper levels of a prefix sum over x
+ *   entries (the one over the index runs in place in d_out_offsets, the one over the ranks in place in the scratch); round256
+ *   rounds up to a multiple of 256.  A multiple of 256, never 0.
+ * Mask and table are read only by the device: the call is asynchronous on `stream`, allocates nothing, reads nothing back and
+ * never synchronises; it can be captured in a graph, and a replay after the mask's stream or the tables were overwritten in place
+ * compacts the NEW selection.  The steps, none of which waits for another workgroup: a rank pass, one wavefront per mask segment,
+ * that walks the segment into an image of 1024 groups in LDS and counts its selected rows (a mask segment that is one fill word
+ * selecting nothing costs no image); the prefix sum of the counts; one wavefront per (column, output segment) that searches the
+ * ranks for the source segments whose survivors lie in its 31 744 bits, walks the mask segment and the column segment into two
+ * images, moves the column's bits under the mask together, 64 groups per step, and deposits them on the output's group grid in a
+ * third image, whose words it counts; the prefix sum of the counts; the same wavefronts again, which now store the words, 64
+ * consecutive ones at a time.  No decoded bitmap exists at any point; ranks, rows and offsets are 64-bit throughout.
+ * The mask is read and checked in EVERY segment.  A column, as in the splice and fetch calls, is read and checked ONLY in the
+ * source segments that hold a selected row: whether a broken column segment is refused depends on the mask.  After a refused
+ * mask no column is read.
+ * Errors the host can see come back before any HIP call, argument checks first: n_columns < 1 or > WAH_BITOP_LIST_MAX_OPERANDS,
+ * n_words or n_words_out == 0 or >= 2^40, n_rows > 32 * n_words, unknown flag bits, n_columns * S_out >= 2^31, a null or misaligned
+ * d_mask, d_operands, d_out_offsets, d_out_words, d_out_rows (8 B), d_out (4 B) or scratch (256 B): WAH_ERR_ARG; too small a
+ * scratch: WAH_ERR_WORKSPACE.  Everything only the device sees is reported by wah_compact_status(), which synchronises the
+ * stream: WAH_ERR_STREAM for T > 32 * n_words_out and for everything the list call refuses in an operand, in the mask and in the
+ * column segments that are read; WAH_ERR_CAPACITY for too small an output (nothing is written at or behind
+ * d_out[out_capacity_words]).  The output of a refused call is unspecified.  wah_compact_status(NULL, ...): WAH_ERR_ARG. */
+#define WAH_COMPACT_DELETE 1u
+uint64_t wah_compact_max_words(uint64_t n_words_out, uint64_t n_columns, uint64_t source_words);
+size_t wah_compact_scratch_bytes(uint64_t n_words, uint64_t n_words_out, uint64_t n_columns);
+int wah_compact_indexed_device(uint64_t n_words, uint64_t n_rows, uint32_t flags, const wah_bitop_operand *d_mask,
+                               uint64_t n_columns, const wah_bitop_operand *d_operands, uint64_t n_words_out, uint32_t *d_out,
+                               uint64_t out_capacity_words, uint64_t *d_out_words, uint64_t *d_out_offsets, uint64_t *d_out_rows,
+                               void *d_scratch, size_t scratch_bytes, void *stream);
+int wah_compact_status(void *d_scratch, void *stream);
+
 /* The way into the BIT-SLICED index: a column of values in, the index of its slices out, in one call -- what
  * wah_bsi_range_indexed_device, wah_bsi_kth_indexed_device and wah_fetch_indexed_device read.  Not in the reference.
  *   d_values: n_rows unsigned 64-bit values below 2^n_bits, n_bits 1 .. 64 (a negative int64 is a value of 2^63 or more).
