@@ -88,6 +88,9 @@ from .api import (  # noqa: F401
     compact_device,
     compact_max_words,
     COMPACT_DELETE,
+    update_device,
+    update_operand_table,
+    update_max_words,
     bsi_build_device,
     merge_fills_device,
     StreamReport,

@@ -105,6 +105,10 @@ ABI_SYMBOLS = {
     "wah_compact_scratch_bytes": (_sz, [_u64, _u64, _u64]),
     "wah_compact_indexed_device": (_int, [_u64, _u64, ctypes.c_uint32, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "wah_compact_status": (_int, [_vp, _vp]),
+    "wah_update_max_words": (_u64, [_u64, _u64, _u64, _u64]),
+    "wah_update_scratch_bytes": (_sz, [_u64, _u64]),
+    "wah_update_indexed_device": (_int, [_u64, _u64, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
+    "wah_update_status": (_int, [_vp, _vp]),
     "wah_bsi_build_scratch_bytes": (_sz, [_u64, _u64]),
     "wah_bsi_build_device": (_int, [_u64, _u64, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
     "wah_bsi_build_status": (_int, [_vp, _u64, _u64, _vp]),
@@ -1217,6 +1221,76 @@ def compact_device(mask, table, n_words, n_rows, n_words_out, delete=False, sour
         lambda *tail: lib().wah_compact_indexed_device(n, r, flags, mask.data_ptr(), k, table.data_ptr(), n_out, *tail[:4], rows.data_ptr(), *tail[4:]),
         lib().wah_compact_status, scratch, out, out_offsets, check)
     return got + (rows,)
+
+
+def update_operand_table(entries, device=None):
+    """The wah_bitop_operand array of the else or the then side of update_device, as an int64 device tensor of shape [k, 3]: every
+    entry is a (stream, seg_offsets) pair, which becomes the row of bitop_operand_table, or the int 0 or 1, a CONSTANT bitmap of
+    that bit, which becomes the row (0, bit, 0) -- no stream, no index, nothing is read for it.  As bitop_operand_table the table
+    holds raw pointers and keeps no tensor alive.  device: where the table goes; needed when every entry is a constant."""
+    torch = _torch()
+    if not entries:
+        raise WahError("an operand table needs at least one operand")
+    rows, dev = [], device
+    for e in entries:
+        if isinstance(e, (tuple, list)):
+            st, offs = e
+            _as_words(torch, st)
+            if offs.dtype != torch.int64 or not offs.is_cuda or not offs.is_contiguous():
+                raise WahError("a segment index is a contiguous int64 CUDA tensor")
+            rows.append((st.data_ptr(), st.numel(), offs.data_ptr()))
+            if dev is None:
+                dev = st.device
+        elif e in (0, 1):
+            rows.append((0, int(e), 0))
+        else:
+            raise WahError("an entry is a (stream, seg_offsets) pair or the constant 0 or 1")
+    if dev is None:
+        raise WahError("a table of constants only needs a device")
+    return torch.tensor(rows, dtype=torch.int64, device=dev)
+
+
+def update_max_words(n_words, n_columns, mask_words, source_words):
+    return int(lib().wah_update_max_words(int(n_words), int(n_columns), int(mask_words), int(source_words)))
+
+
+def update_device(mask, else_table, then_table, n_words, n_rows, mask_words=None, source_words=None, scratch=None, out=None,
+                  out_offsets=None, check=True):
+    """Per column the blend of two indexed bitmaps under a mask bitmap, without a decoded bitmap (wah_update_indexed_device):
+    output column c is then_table's row c where the mask bit is 1 and the position lies below n_rows, else_table's row c
+    everywhere else.  mask: a (stream, seg_offsets) pair or a ready [1, 3] operand table; else_table / then_table: [n_columns, 3]
+    operand tables (update_operand_table, bitop_operand_table, columns.column_operand_table) or lists of update_operand_table's
+    entries -- all bitmaps of n_words words, only the device reads them; a row (0, bit, 0) is a constant.  Returns
+    (stream, seg_offsets): the columns' compress() streams back to back and the n_columns * S + 1 entries of their segment index,
+    as compact_device.  mask_words / source_words: upper bounds on the mask's words and on the words of all else and then rows
+    that are no constants together, which size a default out by wah_update_max_words (either None: the bound that always holds,
+    n_columns * wah_max_compressed_words(n_words)); scratch / out / out_offsets: reuse these tensors; check=False: only enqueue
+    and return (out, count tensor, out_offsets).  The output must not overlap an input."""
+    torch = _torch()
+    if not isinstance(mask, torch.Tensor):
+        mask = [tuple(mask)]
+    mask = _operand_table(mask, "the mask")
+    dev = mask.device
+
+    def side(x, what):
+        return _operand_table(x if isinstance(x, torch.Tensor) else update_operand_table(x, dev), what)
+
+    else_table, then_table = side(else_table, "the else table"), side(then_table, "the then table")
+    k = int(else_table.shape[0])
+    if int(mask.shape[0]) != 1 or int(then_table.shape[0]) != k or else_table.device != dev or then_table.device != dev:
+        raise WahError("the mask is one operand, the else and the then table have one row per column, all on one device")
+    n, r = int(n_words), int(n_rows)
+    if r < 0 or r > 32 * n:
+        raise WahError("n_rows lies between 0 and 32 * n_words")
+    g = max_compressed_words(n)
+    exact = mask_words is not None and source_words is not None
+    return _compressed_streams(
+        "wah_update_indexed_device", "update", dev, k * ((g + 1023) // 1024) + 1,
+        "out_offsets: a contiguous int64 tensor of n_columns * segments + 1 entries on the table's device",
+        lambda: lib().wah_update_scratch_bytes(n, k),
+        lambda: max(update_max_words(n, k, mask_words, source_words) if exact else k * g, 1),
+        lambda *tail: lib().wah_update_indexed_device(n, r, mask.data_ptr(), k, else_table.data_ptr(), then_table.data_ptr(), *tail),
+        lib().wah_update_status, scratch, out, out_offsets, check)
 
 
 def bsi_build_device(values, n_bits, n_words, exists=None, scratch=None, out=None, out_offsets=None, check=True):

@@ -953,6 +953,141 @@ def delete_rows(wah, index, mask, n_rows, n_rows_out=None, **reuse):
     return _compact_rows(wah, index, mask, n_rows, n_rows_out, True, reuse)
 
 
+def _update_table(entries, n, dev):
+    """One side of an update call: entries holds per output column the constant 0 or 1 or (index, column) -- column `column` of
+    the column matrix index[:3].  The [len(entries), 3] table, constants as rows (0, bit, 0), the others through
+    column_operand_table, one call per index."""
+    import torch
+
+    table = torch.tensor([(0, e, 0) if isinstance(e, int) else (0, 0, 0) for e in entries], dtype=torch.int64, device=dev)
+    sources = {}
+    for j, e in enumerate(entries):
+        if not isinstance(e, int):
+            index, column = e
+            sources.setdefault(id(index), (index, [], []))
+            sources[id(index)][1].append(j)
+            sources[id(index)][2].append(column)
+    for index, rows, columns in sources.values():
+        if int(index[2]) != n or index[0].device != dev:
+            raise ValueError("every index has the same column length and lies on the mask's device")
+        part = column_operand_table(index[0], index[1], n, columns)
+        table.index_copy_(0, torch.tensor(rows, dtype=torch.int64, device=dev), part)
+    return table
+
+
+def _update_columns(wah, mask, n, n_rows, else_entries, then_entries, reuse):
+    """The front ends of api.update_device: the two sides as _update_table takes them; returns (stream, seg_offsets, n), with
+    check=False the whole output buffer as the stream."""
+    n, n_rows = int(n), int(n_rows)
+    if len(mask) != 2:
+        raise ValueError("mask is a (stream, seg_offsets) pair")
+    if n_rows < 0 or n_rows > 32 * n:
+        raise ValueError("rows that lie inside the columns")
+    dev = mask[0].device
+    got = wah.update_device(tuple(mask), _update_table(else_entries, n, dev), _update_table(then_entries, n, dev), n, n_rows, **reuse)
+    return got[0], got[-1], n
+
+
+def _whole_index(index):
+    """(index, column) for every column of an index_from_keys or bsi_from_values result."""
+    if len(index) not in (3, 5):
+        raise ValueError("index is an index_from_keys result or a bsi_from_values result")
+    k = _index_columns(index[1], index[2])
+    if k < 1:
+        raise ValueError("an index of at least one column")
+    return [(index, c) for c in range(k)]
+
+
+def update_rows(wah, index, mask, n_rows, source, **reuse):
+    """`UPDATE t SET (*) = s.* FROM s WHERE ...`, the MERGE of a corrected batch into the rows it corrects: of the first n_rows
+    rows of every column of `index`, those whose bit is set in `mask` take `source`'s row of the SAME number, all other rows keep
+    index's, in one call that decodes no bitmap (wah_update_indexed_device).  index and source are both the 3-tuple of
+    index_from_keys or both the 5-tuple of bsi_from_values (or results of append_rows / slice_rows / keep_rows / this function),
+    of one kind, one column count and one column length.  mask: a (stream, seg_offsets) pair over that column length, as
+    filter_columns, range_column and compare_columns return it (the stream may be the whole output buffer of a call that was only
+    enqueued); what it holds at or behind n_rows selects nothing.  Returns the same kind of tuple as `index`, a NEW index that goes
+    into every call that takes one.  reuse: mask_words / source_words / scratch / out / out_offsets / check of api.update_device
+    (check=False returns the whole output buffer as the stream)."""
+    tail = _same_kind(index, source)
+    if int(index[2]) != int(source[2]):
+        raise ValueError("index and source differ in their column length")
+    return _update_columns(wah, mask, index[2], n_rows, _whole_index(index), _whole_index(source), reuse) + tail
+
+
+def set_values_where(wah, bsi, mask, n_rows, value, **reuse):
+    """`UPDATE t SET x = value WHERE ...` on a bit-sliced attribute in one call (wah_update_indexed_device): the rows below n_rows
+    that `mask` selects hold `value` afterwards, all others what they held.  bsi: what bsi_from_values returned; value: an int in
+    [0, 2^n_bits) -- the new slices are CONSTANTS, slice i bit n_bits - 1 - i of the value, the existence slice 1, and nothing is
+    read for them -- or None, which writes NULL: every slice and the existence slice 0 (ValueError for an attribute without an
+    existence slice).  mask, reuse and result as update_rows."""
+    stream, seg_offsets, n, n_bits, has_exists = bsi
+    if value is None:
+        if not has_exists:
+            raise ValueError("NULL needs an existence slice")
+        bits = [0] * (n_bits + 1)
+    else:
+        value = int(value)
+        if value < 0 or value >= 1 << n_bits:
+            raise ValueError(f"value outside [0, 2^{n_bits})")
+        bits = [(value >> (n_bits - 1 - i)) & 1 for i in range(n_bits)] + ([1] if has_exists else [])
+    return _update_columns(wah, mask, n, n_rows, _whole_index(bsi), bits, reuse) + (n_bits, has_exists)
+
+
+def set_keys_where(wah, index, mask, n_rows, key, **reuse):
+    """`UPDATE t SET city = key WHERE ...` on an equality-encoded index in one call: in the rows below n_rows that `mask` selects
+    column `key` is set and every other column cleared -- constants, for which nothing is read --, so a row stays in exactly one
+    column.  index: what index_from_keys returned; mask, reuse and result as update_rows."""
+    if len(index) != 3:
+        raise ValueError("index is an index_from_keys result")
+    columns = _whole_index(index)
+    key = int(key)
+    if key < 0 or key >= len(columns):
+        raise ValueError("key names a column of the index")
+    return _update_columns(wah, mask, index[2], n_rows, columns, [1 if c == key else 0 for c in range(len(columns))], reuse)
+
+
+def choose_columns(wah, mask, bsi_then, bsi_else, n_rows, n_bits=None, **reuse):
+    """`CASE WHEN mask THEN a ELSE b END` between two bit-sliced attributes of one column length in one call
+    (wah_update_indexed_device): the rows below n_rows that `mask` selects hold bsi_then's value, all others bsi_else's.  The
+    widths may differ: n_bits defaults to the wider and may not be narrower than either, the high slices an attribute lacks are
+    the constant 0.  If either attribute has an existence slice the result has one; an attribute without one has a value in every
+    row, the constant 1 -- in every POSITION of its columns: where bsi_else is the one without, the result's existence slice is
+    set behind n_rows as well.  mask and reuse as update_rows.  Returns a bsi_from_values tuple."""
+    _, _, n, kt, has_t = bsi_then
+    _, _, n_e, ke, has_e = bsi_else
+    if n != n_e:
+        raise ValueError("the two attributes have different column lengths")
+    n_bits = max(kt, ke) if n_bits is None else int(n_bits)
+    if n_bits < max(kt, ke):
+        raise ValueError("n_bits is not narrower than either attribute")
+    has_exists = bool(has_t or has_e)
+
+    def side(bsi, width, has):
+        slices = [(bsi, width - n_bits + i) if width - n_bits + i >= 0 else 0 for i in range(n_bits)]
+        return slices + ([(bsi, width) if has else 1] if has_exists else [])
+
+    return _update_columns(wah, mask, n, n_rows, side(bsi_else, ke, has_e), side(bsi_then, kt, has_t), reuse) + (n_bits, has_exists)
+
+
+def _extreme_columns(wah, op, bsi_a, bsi_b, n_rows):
+    if bsi_a[4] or bsi_b[4]:
+        raise ValueError("attributes without an existence slice only")
+    out, _, out_offsets = compare_columns(wah, bsi_a, op, bsi_b, check=False)
+    return choose_columns(wah, (out, out_offsets), bsi_a, bsi_b, n_rows)
+
+
+def greatest_columns(wah, bsi_a, bsi_b, n_rows):
+    """`GREATEST(a, b)` row by row between two bit-sliced attributes without existence slices (ValueError otherwise):
+    compare_columns(a >= b), only enqueued, then choose_columns under its result -- two calls, nothing decoded, and nothing read
+    back before the second one's status.  Returns a bsi_from_values tuple of the wider width."""
+    return _extreme_columns(wah, ">=", bsi_a, bsi_b, n_rows)
+
+
+def least_columns(wah, bsi_a, bsi_b, n_rows):
+    """`LEAST(a, b)` row by row: greatest_columns under a <= b."""
+    return _extreme_columns(wah, "<=", bsi_a, bsi_b, n_rows)
+
+
 def compress_column_ranges(compressor, flat, lengths, wait=True):
     """Columns of DIFFERENT lengths (each a multiple of 992 words) stored back to back in `flat`: still one launch.
     Returns (stream, column_offsets) like compress_column_matrix: column c is stream[column_offsets[c] :

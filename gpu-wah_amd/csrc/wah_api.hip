@@ -1994,6 +1994,47 @@ int wah_compact_indexed_device(uint64_t n_words, uint64_t n_rows, uint32_t flags
 
 int wah_compact_status(void *d_scratch, void *stream) { return scratch_status(d_scratch, stream); }
 
+// The rows a mask bitmap selects of every column of an index take the then column's bits, all others keep the else column's
+// (wah_update.hip).  The scratch: the from-positions call's -- control block and the two upper levels of the prefix sum over the
+// n_columns x S + 1 index entries; no ranks, no starts -- and its road, with a check step that launches nothing.
+uint64_t wah_update_max_words(uint64_t n_words, uint64_t n_columns, uint64_t mask_words, uint64_t source_words) {
+    const SegGeometry g = seg_geometry(n_words);
+    const unsigned __int128 columns = n_columns;
+    const unsigned __int128 all_literals = columns * g.groups;
+    const unsigned __int128 by_words = (unsigned __int128)source_words + columns * ((unsigned __int128)mask_words + 3);
+    const unsigned __int128 m = all_literals < by_words ? all_literals : by_words;
+    return m > (unsigned __int128)~0ull ? ~0ull : (uint64_t)m;
+}
+
+size_t wah_update_scratch_bytes(uint64_t n_words, uint64_t n_columns) { return streams_layout(n_words, n_columns, 0).total; }
+
+int wah_update_indexed_device(uint64_t n_words, uint64_t n_rows, const wah_bitop_operand *d_mask, uint64_t n_columns,
+                              const wah_bitop_operand *d_else, const wah_bitop_operand *d_then, uint32_t *d_out,
+                              uint64_t out_capacity_words, uint64_t *d_out_words, uint64_t *d_out_offsets, void *d_scratch,
+                              size_t scratch_bytes, void *stream) {
+    g_err[0] = 0;
+    if (n_columns < 1 || n_columns > wah::kMaxBitopListOperands || n_words == 0 || n_words >= (1ull << 40))
+        return refuse("between 1 and 2^24 columns, between 1 and 2^40 - 1 words", WAH_ERR_ARG);
+    if (n_rows > 32u * n_words) return refuse("more rows than 32 * n_words", WAH_ERR_ARG);
+    const StreamsLayout l = streams_layout(n_words, n_columns, 0);
+    if (l.n_items >= (1ull << 31)) return refuse("columns x segments of 992 words: fewer than 2^31", WAH_ERR_ARG);
+    if (!scratch_ok(d_scratch)) return refuse("bad scratch pointer", WAH_ERR_ARG);
+    if (!d_mask || !aligned(d_mask, 7) || !d_else || !aligned(d_else, 7) || !d_then || !aligned(d_then, 7))
+        return refuse("null or misaligned mask, else table or then table", WAH_ERR_ARG);
+    if (!out_triple_ok(d_out, d_out_words, d_out_offsets)) return refuse("null or misaligned output", WAH_ERR_ARG);
+    if (scratch_bytes < l.total) return refuse("scratch too small", WAH_ERR_WORKSPACE);
+    wah::UpdateArgs a = {};
+    a.mask = reinterpret_cast<const wah::BitopListOperand *>(d_mask);
+    a.else_table = reinterpret_cast<const wah::BitopListOperand *>(d_else);
+    a.then_table = reinterpret_cast<const wah::BitopListOperand *>(d_then);
+    a.n_columns = n_columns;
+    a.n_rows = n_rows;
+    return count_scan_emit(a, wah::launch_update_check, wah::launch_update_segments, "update launch", n_words, d_out, out_capacity_words,
+                           d_out_words, d_out_offsets, static_cast<char *>(d_scratch), l, stream);
+}
+
+int wah_update_status(void *d_scratch, void *stream) { return scratch_status(d_scratch, stream); }
+
 // A bit-sliced index from a column of values (wah_bsi_build.hip): the transpose writes the decoded slice matrix into the scratch,
 // the compress passes run over it as over any column matrix.  The scratch: [control words][slice matrix][compress workspace] --
 // the layout of every call that leaves a whole attribute (wah_bsi_arith_indexed_device below: its sweep writes the matrix).

@@ -540,6 +540,29 @@ struct CompactArgs {
 hipError_t launch_compact_check(const CompactArgs &a, hipStream_t s);
 hipError_t launch_compact_segments(const CompactArgs &a, bool emit, hipStream_t s);
 
+// wah_update_indexed_device (wah_update.hip): per column the blend of two indexed bitmaps under a mask bitmap -- then_c where the
+// mask selects a row below n_rows, else_c everywhere else -- as new indexed bitmaps.  The three tables are read by the device
+// only; an else or then row whose stream and index pointers are both null is a constant (stream_words 0 or 1).  offsets is used
+// as FromPositionsArgs::offsets, n_columns * n_segments + 1 entries.  The call has no check launch: launch_update_check launches
+// nothing.
+struct UpdateArgs {
+    const BitopListOperand *mask;       // one row
+    const BitopListOperand *else_table; // n_columns rows
+    const BitopListOperand *then_table; // n_columns rows
+    uint64_t n_columns;
+    uint64_t n_rows;                    // only positions below it are selected
+    uint64_t n_bits;                    // 32 n_words
+    uint64_t groups;                    // G of ONE bitmap
+    uint64_t n_segments;                // S = ceil(G / 1024), per column
+    uint32_t *out;
+    uint64_t out_capacity;
+    uint64_t *out_words;
+    uint64_t *offsets;
+    uint32_t *ctrl;
+};
+hipError_t launch_update_check(const UpdateArgs &a, hipStream_t s);
+hipError_t launch_update_segments(const UpdateArgs &a, bool emit, hipStream_t s);
+
 // wah_bsi_build_device (wah_bsi_build.hip): a column of 64-bit values in, the decoded slice matrix [n_bits (+ 1), n_words] out --
 // most significant slice first, the existence bitmap last when exists != nullptr.  Every word of the matrix is written.
 struct BsiBuildArgs {

@@ -1026,6 +1026,65 @@ int wah_compact_indexed_device(uint64_t n_words, uint64_t n_rows, uint32_t flags
                                void *d_scratch, size_t scratch_bytes, void *stream);
 int wah_compact_status(void *d_scratch, void *stream);
 
+/* The call that changes the VALUES of an index by a predicate: the rows a mask bitmap selects take a new value in every column,
+ * all other rows keep theirs -- UPDATE t SET x = 5 WHERE ..., UPDATE t SET city = 'X' WHERE ..., the MERGE of a corrected batch
+ * into the rows it corrects, CASE WHEN p THEN a ELSE b END.  The compact call moves the selected rows together; this one leaves
+ * every row where it is.  Not in the reference.
+ *   d_mask: ONE wah_bitop_operand in DEVICE memory, 8-byte aligned; d_else and d_then: n_columns of them each.  All are indexed
+ *   bitmaps of n_words words as for the list call (windows into column matrices allowed, stream_words may be a capacity, streams
+ *   compress() never emits are legal).  The mask may be the output of a clause, list, range or compare call enqueued before this
+ *   one on the same stream and not yet checked.
+ *   An entry of d_else or d_then whose d_stream AND d_offsets are both NULL is a CONSTANT: stream_words == 0 means every position
+ *   is 0, stream_words == 1 means every position is 1; nothing is read for it.  The mask cannot be a constant.
+ * For every column c and every position p < 32 * n_words: output c at p is then_c(p) where p < n_rows and the mask bit is 1, and
+ * else_c(p) everywhere else, n_rows <= 32 * n_words.  What the mask holds at or behind n_rows selects nothing.  The pad bits of
+ * the last group are zero in the output whatever the sources hold there.  Output bitmap c is, word for word, what compress()
+ * emits for that bitmap, whatever form the sources had.  The output is laid out exactly as wah_compact_indexed_device's with
+ * n_words_out == n_words: d_out receives the n_columns streams back to back; d_out_offsets (required) receives n_columns * S + 1
+ * entries counted from d_out[0], S = ceil(G / 1024), G = wah_max_compressed_words(n_words); d_out_words receives the total, also
+ * when it exceeds the capacity.  The output must not overlap an input (not checked): the result is a NEW index, as in the splice
+ * and compact calls.
+ *   wah_update_max_words: an out_capacity_words that always suffices:
+ *   min(n_columns * G, source_words + n_columns * (mask_words + 3)), saturating at UINT64_MAX.  source_words is any upper bound the
+ *   caller has on the words of all else and then entries that are no constants together, mask_words one on the mask's words; the
+ *   whole streams are one.
+ *   Why it holds: inside a segment an output word can begin only at a group where a word of the mask, of the else or of the then
+ *   stream begins -- between two such groups all three streams are inside fills, the selection and both sources are constant from
+ *   group to group, and so the output is one run.  Each source word is charged once (source_words), each mask word once per
+ *   column (n_columns * mask_words).  A constant begins a word only at a segment's first group, which every stream shares: it is
+ *   charged to the mask's word there.  Clipping the mask at n_rows makes the selection change inside one group and again at the
+ *   next: two more groups where a word may begin; clearing the pad bits sets the last group apart: one more (n_columns * 3).
+ *   d_scratch: wah_update_scratch_bytes(n_words, n_columns) bytes, 256-byte aligned, no initialisation: 1024 (the control words)
+ *   + L(n_columns * S + 1), L as for the compact call: the two upper levels of the prefix sum over the index, which runs in place
+ *   in d_out_offsets.  No ranks, no starts: the same as wah_from_positions_scratch_bytes(n_words, n_columns).  A multiple of 256,
+ *   never 0.
+ * Mask and tables are read only by the device: the call is asynchronous on `stream`, allocates nothing, reads nothing back and
+ * never synchronises; it can be captured in a graph, and a replay after the mask's stream or either table was overwritten in
+ * place applies the NEW update.  The steps, none of which waits for another workgroup: one wavefront per (segment, column) item,
+ * the items shared out in contiguous runs and enumerated segment by segment, so that a wavefront walks a mask segment into its
+ * image of 1024 groups in LDS once and keeps it across the columns (a mask segment that is one zero fill costs no image pass); per
+ * column the else entry is walked into a second image, where the clipped mask selects a row of the segment the then entry into a
+ * third, every lane blends its groups, (else & ~sel) | (then & sel), the pad bits are cleared and the image's words are counted;
+ * the prefix sum of the counts; the same wavefronts again, which now store the words, 64 consecutive ones at a time.  No decoded
+ * bitmap exists at any point.
+ * The mask and every else entry that is no constant are read and checked in EVERY segment.  A then entry that is no constant is
+ * read and checked ONLY in the segments where the mask, clipped at n_rows, selects a row: whether a broken then segment is
+ * refused depends on the mask, as in the compact and fetch calls.  After a refused mask segment the item reads no column.
+ * Errors the host can see come back before any HIP call, argument checks first: n_columns < 1 or > WAH_BITOP_LIST_MAX_OPERANDS,
+ * n_words == 0 or >= 2^40, n_rows > 32 * n_words, n_columns * S >= 2^31, a null or misaligned scratch (256 B), d_mask, d_else,
+ * d_then, d_out_offsets, d_out_words (8 B) or d_out (4 B): WAH_ERR_ARG; too small a scratch: WAH_ERR_WORKSPACE.  Everything only
+ * the device sees is reported by wah_update_status(), which synchronises the stream: WAH_ERR_STREAM for everything the list call
+ * refuses in an operand, in the segments that are read, for an entry with exactly one of d_stream and d_offsets NULL, for a
+ * constant with stream_words > 1 and for a constant mask; WAH_ERR_CAPACITY for too small an output (nothing is written at or
+ * behind d_out[out_capacity_words]).  The output of a refused call is unspecified.  wah_update_status(NULL, ...): WAH_ERR_ARG. */
+uint64_t wah_update_max_words(uint64_t n_words, uint64_t n_columns, uint64_t mask_words, uint64_t source_words);
+size_t wah_update_scratch_bytes(uint64_t n_words, uint64_t n_columns);
+int wah_update_indexed_device(uint64_t n_words, uint64_t n_rows, const wah_bitop_operand *d_mask, uint64_t n_columns,
+                              const wah_bitop_operand *d_else, const wah_bitop_operand *d_then, uint32_t *d_out,
+                              uint64_t out_capacity_words, uint64_t *d_out_words, uint64_t *d_out_offsets, void *d_scratch,
+                              size_t scratch_bytes, void *stream);
+int wah_update_status(void *d_scratch, void *stream);
+
 /* The way into the BIT-SLICED index: a column of values in, the index of its slices out, in one call -- what
  * wah_bsi_range_indexed_device, wah_bsi_kth_indexed_device and wah_fetch_indexed_device read.  Not in the reference.
  *   d_values: n_rows unsigned 64-bit values below 2^n_bits, n_bits 1 .. 64 (a negative int64 is a value of 2^63 or more).
