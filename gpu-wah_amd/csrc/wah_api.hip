@@ -1879,7 +1879,7 @@ int wah_from_positions_device(uint64_t n_words, uint64_t n_lists, const uint64_t
 
 int wah_from_positions_status(void *d_scratch, void *stream) { return scratch_status(d_scratch, stream); }
 
-// Row ranges of indexed bitmaps concatenated into new ones (splice_segments_kernel, wah_bitop_list.hip).  The scratch: control
+// Row ranges of indexed bitmaps concatenated into new ones (splice_segments_kernel, wah_splice.hip).  The scratch: control
 // block, the n_pieces + 1 running starts the check launch leaves, then the two upper levels of the prefix sum over the
 // n_columns x S + 1 index entries: streams_layout, and its road.
 static_assert(sizeof(wah_splice_piece) == 24 && sizeof(wah::SplicePiece) == 24 && WAH_SPLICE_MAX_PIECES == wah::kSpliceMaxPieces, "one piece, one bound");

@@ -11,328 +11,16 @@
 //   bsi_kth_pass_kernel            one pass of the radix select over such an attribute (wah_bsi_kth_indexed_device)
 //   bsi_kth_group_pass_kernel      the same pass for every (group, query) pair of a GROUP BY at once (wah_bsi_kth_grouped_indexed_device)
 //   fetch_items_kernel             the values of listed rows, one wavefront per 64 listed rows of a segment (wah_fetch_indexed_device)
-//   splice_segments_kernel         row ranges of indexed bitmaps concatenated into new ones, one wavefront per (column, output
-//                                  segment) (wah_splice_indexed_device)
-// The walk itself is written once (list_walk), and so is the sweep that keeps one row at a time in the zeroed image (row_sweep);
-// a kernel adds the state it keeps per segment, how a row is folded into it, and what it stores or counts.
+// The walk itself is written once (list_walk, wah_list_walk.hpp), and so is the sweep that keeps one row at a time in the zeroed
+// image (row_sweep); a kernel adds the state it keeps per segment, how a row is folded into it, and what it stores or counts.
 //
 // The rows are named by a table in DEVICE memory (wah_bitop_operand, include/wah.h) that only these kernels read: the host
 // never sees it, so a captured launch replayed over a rewritten table combines the new selection.  Nothing is decided from the
 // rows' lengths on the host -- one route, whatever they hold.
-//
-// One wavefront owns one output segment; its accumulator is the segment's 1024 groups in LDS (4 KiB per wavefront, 16 KiB per
-// workgroup: bitop_many_segments_kernel holds 20).  An operand's segment is never expanded: its words are loaded in batches of
-// 128 (two per lane, through a descriptor clipped to the segment's range, as seg_load_words loads them), one wave scan per
-// batch gives every word the group it starts at (the clamps and the "exactly nvalid groups, no empty word" check of
-// seg_mark), and every word is applied where it lies --
-//   a literal            combines into its one group;
-//   a fill that is the operation's identity (zeros under OR / XOR / ANDNOT, ones under AND: most of a sparse or clustered
-//                        operand) costs nothing beyond its load and its share of the scan;
-//   a fill with an effect (ones under OR: set, XOR: flip, ANDNOT: clear; zeros under AND: clear) of up to kListShortFill groups
-//                        is applied by its own lane, a longer one by the whole wave, 64 groups per step, the long fills of a
-//                        batch one after the other off a ballot mask.
-// Every group of the segment is covered by exactly one word of an operand (the scan's positions are disjoint whatever the words
-// say), so no two lanes touch one accumulator group for one operand: no atomics.  A segment's cost goes with the words the
-// operands hold there plus the length of the fills that change the result, not with n_operands x 1024 groups.
-#include "wah_image_words.hpp"
-#include "wah_segdecode.hpp"
+#include "wah_list_walk.hpp"
 
 namespace wah {
 namespace {
-
-constexpr u32 kListShortFill = 8; // groups of a fill up to which its own lane applies it
-#ifndef WAH_LIST_DEPTH
-#define WAH_LIST_DEPTH 4
-#endif
-constexpr int kListDepth = WAH_LIST_DEPTH; // batches of 128 words in flight per wave
-
-// the operation on the accumulator (runs_op(), wah_device.hpp), and the kind of fill that changes it
-struct ListOp {
-    RunsOp m;
-    u32 fill;     // kFillOne or kFillZero
-    u32 fill_val; // its 31 bits
-};
-__device__ __forceinline__ ListOp list_op(u32 op) {
-    ListOp o;
-    o.m = runs_op(op);
-    o.fill = op == 0u ? kFillZero : kFillOne;
-    o.fill_val = op == 0u ? 0u : kOnes31;
-    return o;
-}
-__device__ __forceinline__ u32 list_combine(u32 r, u32 v, const ListOp &o) { return runs_combine(r, v, o.m); }
-
-typedef const __attribute__((address_space(1))) u64 *ListGlobalU64;
-typedef const __attribute__((address_space(1))) u32 *ListGlobalU32;
-// 64 operands of the table, one per lane: where each one's words of segment `seg` lie
-struct ListChunk {
-    u32 addr_lo, addr_hi; // the segment's first word
-    u32 cnt;              // its words; 0: no such operand, one that is refused (bad), or one that is settled (list_gather)
-    bool bad;
-};
-__device__ __forceinline__ ListChunk list_gather(const BitopListOperand *table, u32 j0, u32 n, u64 seg, u32 nvalid, u32 fill_with_effect, u32 lane) {
-    const u32 j = j0 + lane;
-    const bool has = j < n;
-    u64 comp = 0, c_words = 0, offs = 0;
-    if (has) {
-        const u64 *e = reinterpret_cast<const u64 *>(table + j);
-        comp = e[0];
-        c_words = e[1];
-        offs = e[2];
-    }
-    // an entry is checked before a pointer of it is followed ...
-    const bool entry_ok = has && offs != 0ull && (offs & 7ull) == 0ull && comp != 0ull && (comp & 3ull) == 0ull && c_words < (1ull << 40);
-    u64 w0 = 0, w1 = 0;
-    if (entry_ok) {
-        const ListGlobalU64 p = (ListGlobalU64)(uintptr_t)offs + seg; // (global, not generic: no aperture test)
-        w0 = p[0];
-        w1 = p[1];
-    }
-    // ... and a range before the stream is read through it: inside the stream, in order, at least one word (the segment has
-    // groups) and at most one per group
-    ListChunk c;
-    c.bad = has && (!entry_ok || w1 <= w0 || w1 > c_words || w1 - w0 > nvalid);
-    c.cnt = has && !c.bad ? (u32)(w1 - w0) : 0u;
-    const u64 addr = comp + 4ull * w0;
-    // A segment that is ONE fill of all its groups and the operation's identity (a bin of a clustered index: nearly all of its
-    // segments) is complete and changes nothing: it is settled here, 64 operands at a time, and never becomes a batch.  (Its word
-    // is read inside the range just checked; anything else of one word -- a fill with an effect, a wrong count -- goes the
-    // general way and is applied or refused there.)
-    if (c.cnt == 1u) {
-        const u32 only = *(ListGlobalU32)(uintptr_t)addr;
-        if (only >= kFillZero && (only & kCountMask) == nvalid && (only & kFillOne) != fill_with_effect) c.cnt = 0u;
-    }
-    c.addr_lo = (u32)addr;
-    c.addr_hi = (u32)(addr >> 32);
-    return c;
-}
-
-// a place in the chunk's sequence of batches: batch b of the operand in lane j (64: behind the last one)
-struct ListCursor {
-    u32 j, b;
-};
-__device__ __forceinline__ ListCursor list_first(u64 live) {
-    ListCursor c;
-    c.j = live ? (u32)__builtin_ctzll(live) : 64u;
-    c.b = 0;
-    return c;
-}
-__device__ __forceinline__ void list_advance(ListCursor &c, const ListChunk &ch, u64 live) {
-    if (c.j >= 64u) return;
-    const u32 cnt = (u32)__builtin_amdgcn_readlane((int)ch.cnt, (int)c.j);
-    if (128u * (c.b + 1u) < cnt) {
-        ++c.b;
-    } else {
-        const u64 m = c.j >= 63u ? 0ull : live & (~0ull << (c.j + 1u)); // the next operand that has words
-        c.j = m ? (u32)__builtin_ctzll(m) : 64u;
-        c.b = 0;
-    }
-}
-// the batch's words, two per lane (reads past the range return 0; behind the last batch: a descriptor of no bytes, nothing is read)
-// (ONE 8-byte load into a register pair that stays a pair: two 4-byte loads are merged by the compiler and taken apart again with
-//  moves, which wait for the load -- and nothing would be in flight)
-typedef u32 ListPair __attribute__((__vector_size__(8)));
-__device__ __forceinline__ void list_issue(ListPair &q, const ListCursor &c, const ListChunk &ch, u32 lane) {
-    const int jj = (int)min(c.j, 63u);
-    const u32 cnt = c.j < 64u ? (u32)__builtin_amdgcn_readlane((int)ch.cnt, jj) : 0u;
-    const u64 addr = ((u64)(u32)__builtin_amdgcn_readlane((int)ch.addr_hi, jj) << 32) | (u32)__builtin_amdgcn_readlane((int)ch.addr_lo, jj);
-    const __amdgpu_buffer_rsrc_t rsrc = make_rsrc(reinterpret_cast<const void *>(addr), cnt * 4u);
-    const u32 off = (128u * c.b + 2u * lane) * 4u;
-    q = __builtin_amdgcn_raw_buffer_load_b64(rsrc, off, 0, 0);
-}
-
-// what a word's own lane applies: n groups of v from p on -- a literal (n = 1) or a short fill with an effect; the first group, and,
-// where a batch has such fills at all, the rest
-__device__ __forceinline__ void list_put_first(u32 *acc, u32 p, u32 n, u32 v, const ListOp &m) {
-    if (n) acc[p] = list_combine(acc[p], v, m);
-}
-__device__ __forceinline__ void list_put_rest(u32 *acc, u32 p, u32 n, u32 v, const ListOp &m) {
-    u32 t[kListShortFill];
-#pragma unroll
-    for (u32 i = 1; i < kListShortFill; ++i)
-        if (i < n) t[i] = acc[p + i];
-#pragma unroll
-    for (u32 i = 1; i < kListShortFill; ++i)
-        if (i < n) acc[p + i] = list_combine(t[i], v, m);
-}
-// the long fills with an effect of one batch (mask: the lanes that hold one; p, n: where each lies), by the whole wave
-__device__ __forceinline__ void list_put_long(u32 *acc, u64 mask, u32 p, u32 n, const ListOp &m, u32 lane) {
-    while (mask) {
-        const int l = __builtin_amdgcn_readfirstlane(__builtin_ctzll(mask));
-        mask &= mask - 1ull;
-        const u32 g0 = (u32)__builtin_amdgcn_readlane((int)p, l), g1 = g0 + (u32)__builtin_amdgcn_readlane((int)n, l);
-        for (u32 g = g0 + lane; g < g1; g += 64u) acc[g] = list_combine(acc[g], m.fill_val, m);
-    }
-}
-
-// One batch (words wi .. wi + 127 of an operand's `cnt`, w0 / w1 two per lane) applied to the accumulator; pos: the groups the
-// operand's batches have covered so far.  Nothing is put outside the accumulator whatever the words say.
-__device__ __forceinline__ void list_apply_batch(u32 *acc, u32 w0, u32 w1, u32 wi, u32 cnt, u32 &pos, bool &empty_word, const ListOp &m, u32 lane) {
-    // a full batch of literals (dense data: all of its batches) is 128 consecutive groups: no scan, no fills to look for
-    if (wi + 128u <= cnt && pos + 128u <= kSegGroups && __ballot((int)(w0 | w1) < 0) == 0ull) { // wave-uniform
-        const u32 p = pos + 2u * lane;
-        const u32 r0 = acc[p], r1 = acc[p + 1u];
-        acc[p] = list_combine(r0, w0, m);
-        acc[p + 1u] = list_combine(r1, w1, m);
-        pos += 128u;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        return;
-    }
-    const u32 i0 = wi + 2u * lane;
-    const bool in0 = i0 < cnt, in1 = i0 + 1u < cnt;
-    // counts are clamped so that a corrupt word cannot wrap the 32-bit sums; anything above 1024 fails the total
-    const u32 n0 = in0 ? min(word_groups(w0), 2u * kSegGroups) : 0u, n1 = in1 ? min(word_groups(w1), 2u * kSegGroups) : 0u;
-    empty_word |= (in0 && n0 == 0u) || (in1 && n1 == 0u);
-    const u32 incl = wave_scan_incl32(n0 + n1);
-    const u32 p1 = pos + incl - n1, p0 = p1 - n0;
-    const bool a0 = in0 && p0 + n0 <= kSegGroups, a1 = in1 && p1 + n1 <= kSegGroups;
-    const bool lit0 = (int)w0 >= 0, lit1 = (int)w1 >= 0;
-    const bool eff0 = a0 && (w0 & kFillOne) == m.fill, eff1 = a1 && (w1 & kFillOne) == m.fill; // (bits 31, 30: a fill of that kind)
-    const u32 v0 = lit0 ? w0 : m.fill_val, v1 = lit1 ? w1 : m.fill_val;
-    // what the lane applies itself: its literals (one group) and its short fills with an effect
-    const u32 s0 = a0 && lit0 ? 1u : (eff0 && n0 <= kListShortFill ? n0 : 0u);
-    const u32 s1 = a1 && lit1 ? 1u : (eff1 && n1 <= kListShortFill ? n1 : 0u);
-    list_put_first(acc, p0, s0, v0, m);
-    list_put_first(acc, p1, s1, v1, m);
-    if (__ballot(s0 > 1u || s1 > 1u) != 0ull) {
-        list_put_rest(acc, p0, s0, v0, m);
-        list_put_rest(acc, p1, s1, v1, m);
-    }
-    list_put_long(acc, __ballot(eff0 && n0 > kListShortFill), p0, n0, m, lane);
-    list_put_long(acc, __ballot(eff1 && n1 > kListShortFill), p1, n1, m, lane);
-    pos += (u32)__builtin_amdgcn_readlane((int)incl, 63);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // the next batch's (the next operand's) lanes touch other groups than these
-}
-
-// The walk over the first n_rows rows of a table, for segment `seg` of nvalid groups: every row's words of that segment applied to
-// the accumulator in the table's order.  op_of(j): the operation row j is applied with (fill_with_effect: the kind of fill that
-// changes the accumulator under it, kFillOne or kFillZero -- one kind for the whole walk); begin_row(j) is called, wave-uniform,
-// before the first batch of row j is applied -- where a kernel that keeps one row at a time in the accumulator folds the rows in
-// front of j.  Returns the verdict, wave-uniform: no row refused, no empty word, every row's words exactly nvalid groups.
-//
-// What such a wave waits for is memory, not instructions: an index bin of a few words per segment is two dependent round
-// trips (table entry -> index pair -> words) for a hundred instructions.  With the next operand's words in flight while the
-// current one is applied (the x / y rotation of bitop_many_segments_kernel, table entries and index pairs by scalar loads) every
-// operand still costs a whole round trip: 256 clustered operands of 32 MiB took 0.75 ms, 0.013 of the roofline.  So the
-// pipeline is not by operand:
-//   * the table is walked 64 rows at a time, one row per LANE: entry, check, index pair, range check -- two round trips
-//     per 64 rows, by vector loads (an entry is checked before its index pointer is followed, a range before the stream is
-//     read through it);
-//   * the unit in flight is a BATCH of 128 words, whatever row it belongs to: kListDepth batches are always on their way
-//     (a producer cursor runs that far ahead of the consumer's over the 64 rows' batches), in registers of their own --
-//     the loop is unrolled by the depth, so no batch is ever moved -- eight registers instead of the thirty-two of two whole
-//     segments, which lets eight waves per SIMD stay resident.
-// ... and it is instructions: with memory out of the way the walk is bound by what it issues per batch (about 125 wave
-// instructions: 256 random bins of 221 words per segment 0.89 ms).  Two cases therefore never reach the general batch code: a
-// segment that is ONE fill of all its groups and the operation's identity -- nearly every segment of a clustered bin -- is
-// settled while the chunk is gathered, 64 rows at a time (list_gather); a full batch of literals -- every batch of a
-// dense operand -- is 128 consecutive groups, combined without scan or fill tests (list_apply_batch).
-// A settled row never becomes a batch, so begin_row is not called for it: a caller finds the rows it has to fold from the row
-// NUMBERS it is given, and folds the rows behind the last one that had words after the walk.
-template <class OpOf, class BeginRow>
-__device__ __forceinline__ bool list_walk(const BitopListOperand *table, u32 n_rows, u64 seg, u32 nvalid, u32 fill_with_effect, u32 *acc, u32 lane,
-                                          OpOf op_of, BeginRow begin_row) {
-    bool lane_bad = false, empty_word = false; // per lane: a refused row of mine; an empty word among mine
-    bool sums_ok = true;                       // wave-uniform: every row's words made up exactly nvalid groups
-#pragma nounroll
-    for (u32 j0 = 0; j0 < n_rows; j0 += 64u) {
-        const ListChunk ch = list_gather(table, j0, n_rows, seg, nvalid, fill_with_effect, lane);
-        lane_bad |= ch.bad;
-        const u64 live = __ballot(ch.cnt != 0u);
-        ListCursor prod = list_first(live), cons = prod;
-        ListPair q[kListDepth];
-#pragma unroll
-        for (int i = 0; i < kListDepth; ++i) {
-            list_issue(q[i], prod, ch, lane);
-            list_advance(prod, ch, live);
-        }
-        u32 pos = 0;
-#pragma nounroll
-        while (cons.j < 64u) {
-#pragma unroll
-            for (int i = 0; i < kListDepth; ++i) {
-                if (cons.j < 64u) { // wave-uniform
-                    const u32 cnt = (u32)__builtin_amdgcn_readlane((int)ch.cnt, (int)cons.j);
-                    const u32 wi = 128u * cons.b;
-                    if (cons.b == 0u) {
-                        pos = 0u;
-                        begin_row(j0 + cons.j);
-                    }
-                    list_apply_batch(acc, q[i][0], q[i][1], wi, cnt, pos, empty_word, op_of(j0 + cons.j), lane);
-                    if (wi + 128u >= cnt) sums_ok = sums_ok && pos == nvalid; // the row's last batch
-                }
-                list_advance(cons, ch, live);
-                list_issue(q[i], prod, ch, lane); // (into the registers just used: no batch is ever moved)
-                list_advance(prod, ch, live);
-            }
-        }
-    }
-    return sums_ok && __ballot(lane_bad || empty_word) == 0ull;
-}
-
-// the segment a wavefront owns: number k of the launch's, `seg` of the bitmap, nvalid groups (1024 but for the bitmap's last)
-struct WaveSegment {
-    u64 k, seg;
-    u32 nvalid;
-};
-// false: the launch has no segment for this wave
-__device__ __forceinline__ bool wave_segment(WaveSegment &w, u64 first_segment, u64 n_segments, u64 groups, u32 wave) {
-    w.k = (u64)blockIdx.x * kSegDecodeWaves + wave;
-    if (w.k >= n_segments) return false;
-    w.seg = first_segment + w.k;
-    const u64 g0 = w.seg * kSegGroups;
-    w.nvalid = groups - g0 < kSegGroups ? (u32)(groups - g0) : kSegGroups;
-    return true;
-}
-
-// all 1024 groups of a wave's LDS image set to v, fenced: the wave's other lanes read and write them next
-__device__ __forceinline__ void image_fill(u32 *acc, u32 v, u32 lane) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) reinterpret_cast<uint4 *>(acc)[64 * i + (int)lane] = make_uint4(v, v, v, v);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-}
-
-// The sweep of a kernel that keeps ONE row of the table at a time in the image: the walk under OR into the zeroed image `acc`,
-// and fold_row(cur), wave-uniform, once for every row cur = 0 .. n_fold - 1 in order, while the image holds exactly that row.
-// Returns the walk's verdict.
-//   * The crossing to another row is found from row NUMBERS: a row settled in the gather never reaches begin_row, so when
-//     row j's words begin every row in front of j is folded -- the settled ones as the zeros they are, out of the image that
-//     the fold before them left zeroed.
-//   * Two fences frame the zeroing: the first keeps fold_row's reads of the image, which are other lanes' groups than the
-//     lane's own 16-byte stores cover, in front of those stores; the second (image_fill's) keeps the stores in front of the
-//     next row's words.
-//   * The tail: begin_row is only ever called by a row that has words, so the last row, and the settled ones in front of it,
-//     are folded behind the walk.  n_fold is n_rows, or n_rows - 1 for a caller that wants the last row left in the image.
-template <class FoldRow>
-__device__ __forceinline__ bool row_sweep(const BitopListOperand *table, u32 n_rows, u32 n_fold, const WaveSegment &w, u32 *acc, u32 lane,
-                                          FoldRow fold_row) {
-    u32 cur = 0; // the row the image holds
-    auto fold = [&]() {
-        fold_row(cur);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        image_fill(acc, 0u, lane);
-        ++cur;
-    };
-    const ListOp m = list_op(1u);
-    const bool ok = list_walk(table, n_rows, w.seg, w.nvalid, m.fill, acc, lane, [&](u32) -> const ListOp & { return m; }, [&](u32 j) {
-#pragma nounroll
-        while (cur < j) fold();
-    });
-#pragma nounroll
-    while (cur < n_fold) fold();
-    return ok;
-}
-
-// a wave that refused something: the launch reports kErrStream (and a walk kernel's wave returns without storing)
-__device__ __forceinline__ void report_stream_error(u32 *ctrl, u32 lane) {
-    if (lane == 0) atomicOr(ctrl + kCtlError, kErrStream);
-}
-
-// wah_compact.hip, a translation unit of its own, includes this file for the walk above and nothing else: the walk is stated
-// once, here, where its callers and the tests that read its constants look for it.
-#ifdef WAH_LIST_WALK_ONLY
-} // namespace
-} // namespace wah
-#else
 
 // the wave's result, value_of_step(s) for group 64 s + lane, as the segment's decoded words (seg_store: 31 -> 32 repack); groups at
 // and behind nvalid are written as zero
@@ -1303,7 +991,6 @@ __global__ __launch_bounds__(kBsiKthGroupDecideThreads) void bsi_kth_group_decid
 // ceil(R / 64) times (more where items are cut at multiples of 64 of the LIST): the call is for lists that are short beside the
 // bitmap.
 constexpr u32 kFetchGridWaves = 8192; // wavefronts of fetch_items_kernel at the most: 256 CUs x 4 SIMDs x 8 waves
-constexpr u32 kFetchSegBits = kSegGroups * 31u;
 static_assert(kFetchGridWaves % kSegDecodeWaves == 0, "whole workgroups");
 
 __global__ __launch_bounds__(256) void fetch_check_kernel(const FetchArgs a) {
@@ -1321,7 +1008,7 @@ __global__ __launch_bounds__(256) void fetch_check_kernel(const FetchArgs a) {
             if (i) before = a.rows[i - 1];
         }
         bad |= has && (p >= a.n_bits || p < before);
-        const bool head = has && (lane == 0u || p / kFetchSegBits != before / kFetchSegBits); // (base is a multiple of 64)
+        const bool head = has && (lane == 0u || p / kSegBits != before / kSegBits); // (base is a multiple of 64)
         const u64 heads = __ballot(head);                                                    // (lane 0 has a row: never 0)
         u64 first = 0;
         if (lane == 0u) first = atomicAdd(counter, (unsigned long long)__popcll(heads));
@@ -1361,7 +1048,7 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, 8) void fetch_items_kernel(co
         if (g0 >= a.groups) continue; // (no accepted row lies there)
         const bool mine = has && group / kSegGroups == seg;
         const u32 g = mine ? (u32)(group - g0) : 0u, bit = (u32)(p - group * 31u);
-        const u32 nvalid = a.groups - g0 < kSegGroups ? (u32)(a.groups - g0) : kSegGroups;
+        const u32 nvalid = segment_groups(a.groups, seg);
 
         u64 v = kMode == kFetchFirst ? ~0ull : 0ull;
         u32 cur = 0;       // the table row the image holds (wave-uniform)
@@ -1387,172 +1074,6 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, 8) void fetch_items_kernel(co
         if (mine) a.out[i] = v;
     }
 }
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// wah_splice_indexed_device: row ranges ("pieces") of indexed bitmaps concatenated into new indexed bitmaps, at any bit offset,
-// for all columns of an index at once -- INSERT of a batch, a window of rows, the rollover of a partition.  The output is written
-// as wah_from_positions_device writes it: the columns' compress() streams back to back and the index of the whole.
-//
-// Like the fetch call, ONLY the source segments that hold a spliced row are walked.  Three kinds of launches, and no workgroup of
-// any of them waits for another:
-//   splice_check_kernel      one workgroup: every piece is checked (rows inside its operands, no more rows than the output
-//                            holds, without wrapping) and the running starts start(0 .. n_pieces) are left in the scratch; a
-//                            refused piece counts as no rows.  Nothing is read through a piece unless EVERY piece was accepted:
-//                            with a stream error in the control block the other launches return at once.
-//   splice_segments_kernel<false>  (column, output segment) items shared out over the launch's wavefronts in contiguous runs,
-//                            as from_positions_kernel shares its items out.  A wavefront searches the starts for the pieces
-//                            that overlap its bit range [31744 s, 31744 (s + 1)), and for every one of them and every source
-//                            segment the piece's range touches here -- 31 744 bits lie in at most two -- walks the ONE table
-//                            entry (piece, column) for that source segment into a zeroed source image (list_walk under OR),
-//                            then moves the bits onto the destination's group grid (splice_move) and ORs them into the
-//                            destination image.  The image becomes words as in from_positions_kernel (image_words); the
-//                            count goes to offsets[item].
-//   (launch_select_rank_scan turns the counts into the index in place.)
-//   splice_segments_kernel<true>   the same items again; the words are staged in the source image's LDS and leave it 64
-//                            consecutive words per store instruction, clipped by the room the count pass found and by the capacity.
-// Two images of 4 KiB per wavefront, 32 KiB per workgroup of four: five workgroups per CU.
-constexpr u32 kSpliceSegBits = kSegGroups * 31u; // 31 744
-constexpr u32 kSpliceCheckThreads = 256;
-constexpr int kSpliceWavesPerSimd = 5;
-
-// the rows piece p adds to the output: n_rows, or 0 for a refused piece (bad is set).  A piece of no rows is legal whatever else it says.
-__device__ __forceinline__ u64 splice_piece_rows(const SpliceArgs &a, u64 p, bool &bad) {
-    const SplicePiece pc = a.pieces[p];
-    if (pc.n_rows == 0ull) return 0ull;
-    // (in this order nothing wraps: 32 n_words < 2^45, and first_row is below it before it is subtracted)
-    const bool ok = pc.n_words != 0ull && pc.n_words < (1ull << 40) && pc.n_rows <= a.n_bits && pc.first_row <= 32ull * pc.n_words &&
-                    pc.n_rows <= 32ull * pc.n_words - pc.first_row;
-    bad |= !ok;
-    return ok ? pc.n_rows : 0ull;
-}
-
-__global__ __launch_bounds__(256) void splice_check_kernel(const SpliceArgs a) {
-    __shared__ u64 s_sum[kSpliceCheckThreads];
-    const u32 t = threadIdx.x;
-    const u64 per = (a.n_pieces + kSpliceCheckThreads - 1u) / kSpliceCheckThreads;
-    const u64 begin = t * per < a.n_pieces ? t * per : a.n_pieces, end = begin + per < a.n_pieces ? begin + per : a.n_pieces;
-    bool bad = false;
-    u64 sum = 0; // (at most 2^16 pieces of at most 2^45 rows each)
-    for (u64 p = begin; p < end; ++p) sum += splice_piece_rows(a, p, bad);
-    s_sum[t] = sum;
-    __syncthreads();
-    u64 at = 0;
-    for (u32 i = 0; i < t; ++i) at += s_sum[i];
-    for (u64 p = begin; p < end; ++p) {
-        a.starts[p] = at;
-        at += splice_piece_rows(a, p, bad);
-    }
-    if (t == kSpliceCheckThreads - 1u) { // (its run ends at n_pieces: `at` is the total)
-        a.starts[a.n_pieces] = at;
-        bad |= at > a.n_bits;
-    }
-    if (__ballot(bad) != 0ull) report_stream_error(a.ctrl, lane_id());
-}
-
-// `len` >= 1 bits of the source image from bit sb on, ORed into the destination image from bit db on (both below 31 744, the
-// ranges inside their images).  With delta = sb - db = 31 q + r, 0 <= r < 31: bit j of destination group d is bit j + r of
-// source group d + q, or bit j + r - 31 of the group behind it.  Groups outside the image read as zero; what a source holds
-// outside [sb, sb + len) -- set pad bits of a foreign stream among it -- dies in the mask.  A lane writes only groups 64 k +
-// lane of the destination, its own in every call, and reads other lanes' groups of the source: the caller fences in front.
-__device__ __forceinline__ void splice_move(const u32 *src, u32 *dst, u32 sb, u32 db, u32 len, u32 lane) {
-    const int delta = (int)sb - (int)db;
-    const int q = delta >= 0 ? delta / 31 : -((30 - delta) / 31);
-    const u32 r = (u32)(delta - 31 * q);
-    const u32 g_first = db / 31u, g_last = (db + len - 1u) / 31u;
-#pragma nounroll
-    for (u32 k = g_first / 64u; k <= g_last / 64u; ++k) {
-        const u32 d = 64u * k + lane;
-        if (d >= g_first && d <= g_last) {
-            const int i = (int)d + q;
-            const u32 x = i >= 0 && i < (int)kSegGroups ? src[i] : 0u;
-            const u32 y = i + 1 >= 0 && i + 1 < (int)kSegGroups ? src[i + 1] : 0u;
-            const u32 v = ((x >> r) | (y << (31u - r))) & kOnes31;
-            const int lo = max((int)db - 31 * (int)d, 0), hi = min((int)(db + len) - 31 * (int)d, 31); // (0 <= lo < hi <= 31)
-            dst[d] |= v & ((1u << hi) - 1u) & ~((1u << lo) - 1u);
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // the next walk zeroes the source image
-}
-
-template <bool kEmit>
-__global__ __launch_bounds__(kSegDecodeWaves * 64, kSpliceWavesPerSimd) void splice_segments_kernel(const SpliceArgs a) {
-    __shared__ __attribute__((aligned(16))) u32 s_src[kSegDecodeWaves][kSegGroups];
-    __shared__ __attribute__((aligned(16))) u32 s_dst[kSegDecodeWaves][kSegGroups];
-    const u32 wave = wave_id(), lane = lane_id();
-    if ((a.ctrl[kCtlError] & kErrStream) != 0u) return; // a refused piece (or, in the emit pass, stream): no stream is read
-    u32 *src = s_src[wave], *dst = s_dst[wave];
-    u32 *stage = src; // (the emit pass: the source image is free once the bits are moved)
-    const u64 n_items = a.n_columns * a.n_segments;
-    const u64 n_waves = (u64)gridDim.x * kSegDecodeWaves;
-    const u64 per = (n_items + n_waves - 1) / n_waves;
-    const u64 w = (u64)blockIdx.x * kSegDecodeWaves + wave;
-    const u64 begin = w * per < n_items ? w * per : n_items, end = begin + per < n_items ? begin + per : n_items;
-    if (kEmit && w == 0 && lane == 0) {
-        const u64 total = a.offsets[n_items];
-        *a.out_words = total;
-        if (total > a.out_capacity) atomicOr(a.ctrl + kCtlError, kErrCapacity);
-    }
-    const u64 all_rows = uniform64(a.starts[a.n_pieces]); // T: at most 32 n_words_out (the check launch)
-    const ListOp m = list_op(1u);                         // a source segment is ORed into the zeroed image
-#pragma nounroll
-    for (u64 item = begin; item < end; ++item) {
-        const u64 c = item / a.n_segments, seg = item - c * a.n_segments;
-        const u64 base = seg * (u64)kSpliceSegBits;
-        const u32 ngroups = seg + 1 == a.n_segments ? (u32)(a.groups - seg * kSegGroups) : kSegGroups;
-        u32 total;
-        if (base >= all_rows) {
-            // behind the last piece: one zero-fill of the segment's groups; no LDS image, no load
-            total = 1u;
-            if (kEmit && lane == 0) stage[0] = fill_word(kTypeZero, ngroups);
-        } else {
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            image_fill(dst, 0u, lane);
-            const u64 limit = base + kSpliceSegBits < all_rows ? base + kSpliceSegBits : all_rows;
-            // the first piece that ends behind `base` (there is one: base < T)
-            u64 lo = 0, hi = a.n_pieces - 1;
-            while (lo < hi) {
-                const u64 mid = lo + (hi - lo) / 2;
-                if (uniform64(a.starts[mid + 1]) > base) hi = mid; else lo = mid + 1;
-            }
-#pragma nounroll
-            for (u64 p = lo; p < a.n_pieces; ++p) {
-                const u64 st = uniform64(a.starts[p]), en = uniform64(a.starts[p + 1]);
-                if (st >= limit) break;
-                if (en <= st || en <= base) continue; // (no rows; en <= base only for pieces of no rows at `base`)
-                const u64 d0 = st > base ? st : base, d1 = en < limit ? en : limit;
-                const u64 n_words = uniform64(a.pieces[p].n_words), first_row = uniform64(a.pieces[p].first_row);
-                const u64 s0 = first_row + (d0 - st), s1 = s0 + (d1 - d0); // (accepted: s1 <= 32 n_words)
-                const u64 src_groups = (32ull * n_words + 30ull) / 31ull;
-                const BitopListOperand *entry = a.table + (p * a.n_columns + c);
-#pragma nounroll
-                for (u64 ss = s0 / kSpliceSegBits; ss * kSpliceSegBits < s1; ++ss) {
-                    const u64 sbase = ss * kSpliceSegBits;
-                    const u64 t0 = s0 > sbase ? s0 : sbase, t1 = s1 < sbase + kSpliceSegBits ? s1 : sbase + kSpliceSegBits;
-                    if (ss * kSegGroups >= src_groups) break; // (never for an accepted piece)
-                    const u32 nvalid = src_groups - ss * kSegGroups < kSegGroups ? (u32)(src_groups - ss * kSegGroups) : kSegGroups;
-                    image_fill(src, 0u, lane);
-                    const bool ok = list_walk(entry, 1u, ss, nvalid, m.fill, src, lane, [&](u32) -> const ListOp & { return m; }, [](u32) {});
-                    if (!ok) return report_stream_error(a.ctrl, lane);
-                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                    splice_move(src, dst, (u32)(t0 - sbase), (u32)(d0 + (t0 - s0) - base), (u32)(t1 - t0), lane);
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            total = image_words<kEmit>(dst, ngroups, stage, lane);
-        }
-        if (kEmit) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            const u64 at = a.offsets[item], room = a.offsets[item + 1] - at; // what the count pass found
-            const u32 words = (u64)total < room ? total : (u32)room;
-            for (u32 i = lane; i < words; i += 64u)
-                if (at + i < a.out_capacity) a.out[at + i] = stage[i];
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // the next item stages over these words
-        } else if (lane == 0) {
-            a.offsets[item] = (u64)total;
-        }
-    }
-}
-
 // one wavefront per segment, kSegDecodeWaves of them per workgroup
 template <class Args>
 hipError_t launch_per_segment(void (*kernel)(const Args), u64 n_segments, const Args &a, hipStream_t s) {
@@ -1592,24 +1113,6 @@ hipError_t launch_fetch_items(const FetchArgs &a, u32 mode, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_splice_check(const SpliceArgs &a, hipStream_t s) {
-    hipLaunchKernelGGL(splice_check_kernel, dim3(1), dim3(kSpliceCheckThreads), 0, s, a);
-    return hipGetLastError();
-}
-
-// count pass (emit = false: every item's words to a.offsets) or emit pass (a.offsets scanned: the words to their place)
-hipError_t launch_splice_segments(const SpliceArgs &a, bool emit, hipStream_t s) {
-    const u64 n_items = a.n_columns * a.n_segments;
-    const u64 want = (n_items + kSegDecodeWaves - 1) / kSegDecodeWaves;
-    constexpr u64 most = 256u * 5u; // CUs x resident workgroups of four wavefronts at 32 KiB of LDS each
-    const dim3 grid((unsigned)(want < 1 ? 1 : want > most ? most : want)), block(kSegDecodeWaves * 64);
-    if (emit)
-        hipLaunchKernelGGL(splice_segments_kernel<true>, grid, block, 0, s, a);
-    else
-        hipLaunchKernelGGL(splice_segments_kernel<false>, grid, block, 0, s, a);
-    return hipGetLastError();
-}
-
 hipError_t launch_bsi_kth_decide(const BsiKthArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(bsi_kth_decide_kernel, dim3(1), dim3(64), 0, s, a);
     return hipGetLastError();
@@ -1633,4 +1136,3 @@ hipError_t launch_bsi_kth_group_decide(const BsiKthGroupArgs &a, hipStream_t s) 
 }
 
 } // namespace wah
-#endif // WAH_LIST_WALK_ONLY

@@ -19,8 +19,9 @@
 //   compact_total_kernel     one lane: *out_rows = T; T > 32 n_words_out is refused.  With a stream error in the control block
 //                            the later launches return at once: after a refused mask no column is read.
 //   compact_segments_kernel<false>  (column, output segment) items shared out over the launch's wavefronts in contiguous runs, as
-//                            splice_segments_kernel shares them out.  A wavefront binary-searches the ranks for the first source
-//                            segment that ends behind its bit range [31744 s, 31744 (s + 1)) ∩ [0, T) and walks forward.  A
+//                            splice_segments_kernel shares them out (item_run, wah_count_emit.hpp).  A wavefront
+//                            binary-searches the ranks for the first source segment that ends behind its bit range
+//                            [31744 s, 31744 (s + 1)) ∩ [0, T) (first_end_behind, wah_device.hpp) and walks forward.  A
 //                            source segment with no selected row is skipped without touching the column.  For the others the mask
 //                            segment and the column segment are walked into two images, and 64 groups per step: the lane's
 //                            selected mask bits, their popcount, a wave prefix sum with a carry across steps, the column group's
@@ -35,34 +36,18 @@
 // Per pass and column a source segment that holds a selected row is walked at most twice: its <= 31 744 survivors lie in at most
 // two output segments.  The mask segment is walked once more per column; that is accepted.
 // Three images of 4 KiB per wavefront, 48 KiB per workgroup of four: three workgroups per CU (160 KiB of LDS).
-//
-// The walk over an operand table (list_walk, image_fill, report_stream_error) is wah_bitop_list.hip's: that file is included here
-// up to the end of the walk (WAH_LIST_WALK_ONLY), so it is stated once.
-#define WAH_LIST_WALK_ONLY
-#include "wah_bitop_list.hip"
+#include "wah_count_emit.hpp"
+#include "wah_list_walk.hpp"
 
 namespace wah {
 namespace {
 
-constexpr u32 kCompactSegBits = kSegGroups * 31u; // 31 744
 constexpr int kCompactWavesPerSimd = 3;
 
-// the groups of source segment `seg` (the bitmap has `groups`)
-__device__ __forceinline__ u32 compact_nvalid(u64 groups, u64 seg) {
-    const u64 g0 = seg * kSegGroups;
-    return groups - g0 < kSegGroups ? (u32)(groups - g0) : kSegGroups;
-}
-// the positions of source segment `seg` that are rows: the first `return value` of its 31 744 (0 .. 31 744)
-__device__ __forceinline__ u32 compact_seg_rows(u64 n_rows, u64 seg) {
-    const u64 lo = seg * (u64)kCompactSegBits;
-    return n_rows <= lo ? 0u : n_rows - lo < kCompactSegBits ? (u32)(n_rows - lo) : kCompactSegBits;
-}
 // the selected bits of group g of a source segment with seg_rows rows: the mask image's group, complemented under DELETE, below
 // the row limit
 __device__ __forceinline__ u32 compact_selected(u32 image_group, u32 del, u32 g, u32 seg_rows) {
-    const u32 first = 31u * g;
-    const u32 nb = seg_rows <= first ? 0u : min(seg_rows - first, 31u);
-    return (del ? ~image_group : image_group) & ((1u << nb) - 1u); // (nb <= 31: bit 31 is never selected)
+    return (del ? ~image_group : image_group) & group_row_bits(g, seg_rows);
 }
 // the mask segment walked into its image: under OR into zeros, under DELETE under AND into ones (above).  touched: a word was
 // applied -- the image may differ from what it was filled with
@@ -76,15 +61,12 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, 8) void compact_rank_kernel(c
     const u32 wave = wave_id(), lane = lane_id();
     u32 *img = s_img[wave];
     const u32 identity = a.del ? kOnes31 : 0u;
-    const u64 n_waves = (u64)gridDim.x * kSegDecodeWaves;
-    const u64 per = (a.src_segments + n_waves - 1) / n_waves;
-    const u64 w = (u64)blockIdx.x * kSegDecodeWaves + wave;
-    const u64 begin = w * per < a.src_segments ? w * per : a.src_segments, end = begin + per < a.src_segments ? begin + per : a.src_segments;
+    const ItemRun run = item_run(a.src_segments, kSegDecodeWaves, wave);
     image_fill(img, identity, lane);
     bool bad = false;
 #pragma nounroll
-    for (u64 seg = begin; seg < end; ++seg) {
-        const u32 nvalid = compact_nvalid(a.src_groups, seg), seg_rows = compact_seg_rows(a.src_rows, seg);
+    for (u64 seg = run.begin; seg < run.end; ++seg) {
+        const u32 nvalid = segment_groups(a.src_groups, seg), seg_rows = segment_rows(a.src_rows, seg);
         bool touched = false;
         bad |= !compact_walk_mask(a, seg, nvalid, img, lane, touched);
         u32 count = 0;
@@ -135,45 +117,31 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, kCompactWavesPerSimd) void co
     u32 *msk = s_mask[wave], *col = s_col[wave], *dst = s_dst[wave];
     u32 *stage = col; // (the emit pass: the column image is free once the bits are deposited)
     const u64 n_items = a.n_columns * a.n_segments;
-    const u64 n_waves = (u64)gridDim.x * kSegDecodeWaves;
-    const u64 per = (n_items + n_waves - 1) / n_waves;
-    const u64 w = (u64)blockIdx.x * kSegDecodeWaves + wave;
-    const u64 begin = w * per < n_items ? w * per : n_items, end = begin + per < n_items ? begin + per : n_items;
-    if (kEmit && w == 0 && lane == 0) {
-        const u64 total = a.offsets[n_items];
-        *a.out_words = total;
-        if (total > a.out_capacity) atomicOr(a.ctrl + kCtlError, kErrCapacity);
-    }
+    const ItemRun run = item_run(n_items, kSegDecodeWaves, wave);
+    emit_total<kEmit>(a, a.offsets, n_items, run, lane);
     const u64 all_rows = uniform64(a.starts[a.src_segments]); // T: at most 32 n_words_out (compact_total_kernel)
     const u32 identity = a.del ? kOnes31 : 0u;
     const ListOp m_or = list_op(1u); // a column segment is ORed into the zeroed image
 #pragma nounroll
-    for (u64 item = begin; item < end; ++item) {
+    for (u64 item = run.begin; item < run.end; ++item) {
         const u64 c = item / a.n_segments, seg = item - c * a.n_segments;
-        const u64 base = seg * (u64)kCompactSegBits;
+        const u64 base = seg * (u64)kSegBits;
         const u32 ngroups = seg + 1 == a.n_segments ? (u32)(a.groups - seg * kSegGroups) : kSegGroups;
         u32 total;
-        if (base >= all_rows) {
-            // behind the last selected row: one zero-fill of the segment's groups; no LDS image, no load
-            total = 1u;
-            if (kEmit && lane == 0) stage[0] = fill_word(kTypeZero, ngroups);
+        if (base >= all_rows) { // behind the last selected row
+            total = lone_zero_fill<kEmit>(ngroups, stage, lane);
         } else {
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             image_fill(dst, 0u, lane);
-            const u64 limit = base + kCompactSegBits < all_rows ? base + kCompactSegBits : all_rows;
+            const u64 limit = base + kSegBits < all_rows ? base + kSegBits : all_rows;
             const u32 room = (u32)(limit - base); // the item's bits: 1 .. 31 744
-            // the first source segment that ends behind `base` (there is one: base < T)
-            u64 lo = 0, hi = a.src_segments - 1;
-            while (lo < hi) {
-                const u64 mid = lo + (hi - lo) / 2;
-                if (uniform64(a.starts[mid + 1]) > base) hi = mid; else lo = mid + 1;
-            }
+            // from the first source segment whose selected rows end behind `base` (there is one: base < T)
 #pragma nounroll
-            for (u64 ss = lo; ss < a.src_segments; ++ss) {
+            for (u64 ss = first_end_behind(a.starts, a.src_segments, base); ss < a.src_segments; ++ss) {
                 const u64 st = uniform64(a.starts[ss]), en = uniform64(a.starts[ss + 1]);
                 if (st >= limit) break;
                 if (en <= st) continue; // no selected row: neither mask nor column is touched
-                const u32 nvalid = compact_nvalid(a.src_groups, ss), seg_rows = compact_seg_rows(a.src_rows, ss);
+                const u32 nvalid = segment_groups(a.src_groups, ss), seg_rows = segment_rows(a.src_rows, ss);
                 image_fill(msk, identity, lane);
                 image_fill(col, 0u, lane);
                 bool touched = false;
@@ -219,16 +187,7 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, kCompactWavesPerSimd) void co
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             total = image_words<kEmit>(dst, ngroups, stage, lane);
         }
-        if (kEmit) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            const u64 at = a.offsets[item], have = a.offsets[item + 1] - at; // what the count pass found
-            const u32 words = (u64)total < have ? total : (u32)have;
-            for (u32 i = lane; i < words; i += 64u)
-                if (at + i < a.out_capacity) a.out[at + i] = stage[i];
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // the next item stages over these words
-        } else if (lane == 0) {
-            a.offsets[item] = (u64)total;
-        }
+        item_tail<kEmit>(a, a.offsets, item, total, stage, lane);
     }
 }
 
@@ -248,15 +207,8 @@ hipError_t launch_compact_check(const CompactArgs &a, hipStream_t s) {
 
 // count pass (emit = false: every item's words to a.offsets) or emit pass (a.offsets scanned: the words to their place)
 hipError_t launch_compact_segments(const CompactArgs &a, bool emit, hipStream_t s) {
-    const u64 n_items = a.n_columns * a.n_segments;
-    const u64 want = (n_items + kSegDecodeWaves - 1) / kSegDecodeWaves;
     constexpr u64 most = 256u * 3u; // CUs x resident workgroups of four wavefronts at 48 KiB of LDS each
-    const dim3 grid((unsigned)(want < 1 ? 1 : want > most ? most : want)), block(kSegDecodeWaves * 64);
-    if (emit)
-        hipLaunchKernelGGL(compact_segments_kernel<true>, grid, block, 0, s, a);
-    else
-        hipLaunchKernelGGL(compact_segments_kernel<false>, grid, block, 0, s, a);
-    return hipGetLastError();
+    return launch_count_or_emit(compact_segments_kernel<false>, compact_segments_kernel<true>, emit, a.n_columns * a.n_segments, kSegDecodeWaves, most, a, s);
 }
 
 } // namespace wah

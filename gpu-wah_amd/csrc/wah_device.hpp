@@ -217,6 +217,35 @@ __device__ __forceinline__ u32 runs_combine(u32 r, u32 v, const RunsOp &m) {
     return ((r & v & m.ab) | (r & ~v & m.a_nb) | (~r & v & m.na_b)) & kOnes31;
 }
 
+// A bitmap's segments (1024 groups of 31 positions each) as the indexed kernels cut them
+constexpr u32 kSegBits = kSegGroups * 31u; // 31 744
+// the groups of segment `seg` of a bitmap of `groups`: 1024 but for the last
+__device__ __forceinline__ u32 segment_groups(u64 groups, u64 seg) {
+    const u64 g0 = seg * kSegGroups;
+    return groups - g0 < kSegGroups ? (u32)(groups - g0) : kSegGroups;
+}
+// the positions of segment `seg` that are rows, of a bitmap of n_rows rows: the first `return value` of its 31 744 (0 .. 31 744)
+__device__ __forceinline__ u32 segment_rows(u64 n_rows, u64 seg) {
+    const u64 lo = seg * (u64)kSegBits;
+    return n_rows <= lo ? 0u : n_rows - lo < kSegBits ? (u32)(n_rows - lo) : kSegBits;
+}
+// the bits of group g of a segment with seg_rows rows that are rows
+__device__ __forceinline__ u32 group_row_bits(u32 g, u32 seg_rows) {
+    const u32 first = 31u * g;
+    const u32 nb = seg_rows <= first ? 0u : min(seg_rows - first, 31u);
+    return (1u << nb) - 1u; // (nb <= 31: bit 31 is never a row)
+}
+// the first i of 0 .. n - 1 whose run [starts[i], starts[i + 1]) ends behind `base`, for ascending starts with starts[n] > base
+// (wave-uniform)
+__device__ __forceinline__ u64 first_end_behind(const u64 *starts, u64 n, u64 base) {
+    u64 lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const u64 mid = lo + (hi - lo) / 2;
+        if (uniform64(starts[mid + 1]) > base) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
 // expand / checker / merge kernels: one workgroup of four wavefronts per 4096-word tile
 constexpr int kExpandThreads = kExpandWaves * 64;                 // 256
 constexpr int kExpandWordsPerThread = kScanTileWords / kExpandThreads; // 16

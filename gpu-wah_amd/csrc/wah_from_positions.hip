@@ -33,7 +33,7 @@
 // What the check pass refuses is not trusted by the other two: ends are clamped to n_rows and to each other before they bound
 // a read of the rows, a row's place in its segment is clamped to the segment, a segment's words are clipped to the room the
 // count pass gave it, and every store to the output is compared with the capacity.
-#include "wah_image_words.hpp"
+#include "wah_count_emit.hpp"
 
 namespace wah {
 namespace {
@@ -41,7 +41,6 @@ namespace {
 typedef const __attribute__((address_space(4))) u64 *FpConstU64;
 
 constexpr u32 kFpWaves = 4;
-constexpr u32 kSegBits = kSegGroups * 31u; // 31 744
 
 __global__ __launch_bounds__(256) void from_positions_check_kernel(const FromPositionsArgs a) {
     const u64 stride = (u64)gridDim.x * blockDim.x;
@@ -92,17 +91,11 @@ __global__ __launch_bounds__(kFpWaves * 64) void from_positions_kernel(const Fro
     u32 *img = s_img[wave];
     u32 *stage = s_stage[kEmit ? wave : 0];
     const u64 n_items = a.n_lists * a.n_segments;
-    const u64 n_waves = (u64)gridDim.x * kFpWaves;
-    const u64 per = (n_items + n_waves - 1) / n_waves;
-    const u64 w = (u64)blockIdx.x * kFpWaves + wave;
-    const u64 begin = w * per < n_items ? w * per : n_items, end = begin + per < n_items ? begin + per : n_items;
+    const ItemRun run = item_run(n_items, kFpWaves, wave);
+    const u64 begin = run.begin, end = run.end;
     const FpConstU64 ends = (FpConstU64)(uintptr_t)a.list_ends;
     const FpConstU64 offs = (FpConstU64)(uintptr_t)a.offsets;
-    if (kEmit && w == 0 && lane == 0) {
-        const u64 total = offs[n_items];
-        *a.out_words = total;
-        if (total > a.out_capacity) atomicOr(a.ctrl + kCtlError, kErrCapacity);
-    }
+    emit_total<kEmit>(a, offs, n_items, run, lane);
     u64 c = begin / a.n_segments;
     u64 seg = begin - c * a.n_segments;
     u64 lb = 0, le = 0, slice_end = 0; // the list's rows; where the segment before this one ended in them
@@ -126,8 +119,7 @@ __global__ __launch_bounds__(kFpWaves * 64) void from_positions_kernel(const Fro
         const u64 n = hi - lo;
         u32 total;
         if (n == 0) {
-            total = 1u;
-            if (kEmit && lane == 0) stage[0] = fill_word(kTypeZero, ngroups);
+            total = lone_zero_fill<kEmit>(ngroups, stage, lane);
         } else if (n <= 64) {
             // ---- in registers: lane l holds row l ----
             const u32 cnt = (u32)n;
@@ -187,16 +179,7 @@ __global__ __launch_bounds__(kFpWaves * 64) void from_positions_kernel(const Fro
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             total = image_words<kEmit>(img, ngroups, stage, lane); // (wah_image_words.hpp)
         }
-        if (kEmit) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            const u64 at = offs[item], room = offs[item + 1] - at; // what the count pass found: the same, unless the rows changed under the call
-            const u32 words = (u64)total < room ? total : (u32)room;
-            for (u32 i = lane; i < words; i += 64u)
-                if (at + i < a.out_capacity) a.out[at + i] = stage[i];
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // the next item stages over these words
-        } else if (lane == 0) {
-            a.offsets[item] = (u64)total;
-        }
+        item_tail<kEmit>(a, offs, item, total, stage, lane);
         if (last) {
             ++c;
             seg = 0;
@@ -219,16 +202,8 @@ hipError_t launch_from_positions_check(const FromPositionsArgs &a, hipStream_t s
 
 // count pass (emit = false: every item's words to a.offsets) or emit pass (a.offsets scanned: the words to their place)
 hipError_t launch_from_positions_segments(const FromPositionsArgs &a, bool emit, hipStream_t s) {
-    const u64 n_items = a.n_lists * a.n_segments;
-    const u64 want = (n_items + kFpWaves - 1) / kFpWaves;
     constexpr u64 most = 256u * 8u; // CUs x resident workgroups of four wavefronts at eight waves per SIMD
-    const dim3 grid((unsigned)(want < 1 ? 1 : want > most ? most : want));
-    if (emit) {
-        hipLaunchKernelGGL(from_positions_kernel<true>, grid, dim3(kFpWaves * 64), 0, s, a);
-    } else {
-        hipLaunchKernelGGL(from_positions_kernel<false>, grid, dim3(kFpWaves * 64), 0, s, a);
-    }
-    return hipGetLastError();
+    return launch_count_or_emit(from_positions_kernel<false>, from_positions_kernel<true>, emit, a.n_lists * a.n_segments, kFpWaves, most, a, s);
 }
 
 } // namespace wah

@@ -1,8 +1,9 @@
 // wah_image_words.hpp -- an image of one segment's 31-bit groups in LDS turned into the words compress() emits for them, by one
 // wavefront.  Written once for the kernels that build a segment as such an image: from_positions_kernel
-// (wah_from_positions.hip: the rows of a list ORed into it), splice_segments_kernel (wah_bitop_list.hip: bits of source
+// (wah_from_positions.hip: the rows of a list ORed into it), splice_segments_kernel (wah_splice.hip: bits of source
 // segments moved into it), compact_segments_kernel (wah_compact.hip: the bits a mask selects deposited into it) and
-// update_segments_kernel (wah_update.hip: two sources blended in it under a mask).
+// update_segments_kernel (wah_update.hip: two sources blended in it under a mask).  The frame those four kernels put around it is
+// wah_count_emit.hpp.
 #ifndef WAH_IMAGE_WORDS_HPP_
 #define WAH_IMAGE_WORDS_HPP_
 #include "wah_device.hpp"

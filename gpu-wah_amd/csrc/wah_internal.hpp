@@ -489,7 +489,7 @@ struct FromPositionsArgs {
 hipError_t launch_from_positions_check(const FromPositionsArgs &a, hipStream_t s);
 hipError_t launch_from_positions_segments(const FromPositionsArgs &a, bool emit, hipStream_t s);
 
-// wah_splice_indexed_device (wah_bitop_list.hip): row ranges of indexed bitmaps concatenated into new ones, for all columns of an
+// wah_splice_indexed_device (wah_splice.hip): row ranges of indexed bitmaps concatenated into new ones, for all columns of an
 // index at once.  pieces and table are read by the device only; the check launch leaves start(0 .. n_pieces) in `starts` (a
 // refused piece counts as no rows); offsets is used as FromPositionsArgs::offsets, n_columns * n_segments + 1 entries.
 struct SplicePiece {

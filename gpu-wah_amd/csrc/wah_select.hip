@@ -767,7 +767,7 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64) void select_emit_kernel(const
     u32 before = 0xFFFFFFFFu;
     // the bitmap's last group loses its pad bits
     const u32 pad_group = seg + 1 == a.g.n_segments ? rg.nvalid - 1u : 0xFFFFFFFFu;
-    const u64 base_pos = seg * (u64)(kSegGroups * 31u);
+    const u64 base_pos = seg * (u64)kSegBits;
     u64 run = r0; // the rank of the step's first set bit
 #pragma unroll
     for (int s = 0; s < (int)kSteps; ++s) {

@@ -25,16 +25,12 @@
 // The mask and every else entry that is no constant are read and checked in every segment, a then entry only in the segments
 // where the clipped mask selects a row.  After a refused mask segment the wavefront reads no column.
 // Three images of 4 KiB per wavefront, 48 KiB per workgroup of four: three workgroups per CU (160 KiB of LDS).
-//
-// The walk over an operand table (list_walk, image_fill, report_stream_error) is wah_bitop_list.hip's: that file is included here
-// up to the end of the walk (WAH_LIST_WALK_ONLY), so it is stated once.
-#define WAH_LIST_WALK_ONLY
-#include "wah_bitop_list.hip"
+#include "wah_count_emit.hpp"
+#include "wah_list_walk.hpp"
 
 namespace wah {
 namespace {
 
-constexpr u32 kUpdateSegBits = kSegGroups * 31u; // 31 744
 constexpr int kUpdateWavesPerSimd = 3;
 
 // what a row of the else or the then table names
@@ -47,17 +43,6 @@ __device__ __forceinline__ u32 update_kind(const BitopListOperand *row) {
     if (comp != 0ull || offs != 0ull) return kUpdateStream;
     return words == 0ull ? kUpdateZeros : words == 1ull ? kUpdateOnes : kUpdateBad;
 }
-// the positions of segment `seg` that are rows: the first `return value` of its 31 744 (0 .. 31 744)
-__device__ __forceinline__ u32 update_seg_rows(u64 n_rows, u64 seg) {
-    const u64 lo = seg * (u64)kUpdateSegBits;
-    return n_rows <= lo ? 0u : n_rows - lo < kUpdateSegBits ? (u32)(n_rows - lo) : kUpdateSegBits;
-}
-// the bits of group g of a segment with seg_rows rows that are rows
-__device__ __forceinline__ u32 update_row_bits(u32 g, u32 seg_rows) {
-    const u32 first = 31u * g;
-    const u32 nb = seg_rows <= first ? 0u : min(seg_rows - first, 31u);
-    return (1u << nb) - 1u; // (nb <= 31: bit 31 is never selected)
-}
 
 template <bool kEmit>
 __global__ __launch_bounds__(kSegDecodeWaves * 64, kUpdateWavesPerSimd) void update_segments_kernel(const UpdateArgs a) {
@@ -69,15 +54,9 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, kUpdateWavesPerSimd) void upd
     u32 *msk = s_mask[wave], *thn = s_then[wave], *dst = s_dst[wave];
     u32 *stage = thn; // (the emit pass: the then image is free once the blend is done)
     const u64 n_items = a.n_columns * a.n_segments;
-    const u64 n_waves = (u64)gridDim.x * kSegDecodeWaves;
-    const u64 per = (n_items + n_waves - 1) / n_waves;
-    const u64 w = (u64)blockIdx.x * kSegDecodeWaves + wave;
-    const u64 begin = w * per < n_items ? w * per : n_items, end = begin + per < n_items ? begin + per : n_items;
-    if (kEmit && w == 0 && lane == 0) {
-        const u64 total = a.offsets[n_items];
-        *a.out_words = total;
-        if (total > a.out_capacity) atomicOr(a.ctrl + kCtlError, kErrCapacity);
-    }
+    const ItemRun run = item_run(n_items, kSegDecodeWaves, wave);
+    const u64 begin = run.begin, end = run.end;
+    emit_total<kEmit>(a, a.offsets, n_items, run, lane);
     const ListOp m_or = list_op(1u); // a segment is ORed into the zeroed image
     const u32 last_bits = (u32)(a.n_bits - 31ull * (a.groups - 1)); // the bits of the bitmap's last group that are positions: 1 .. 31
     u64 seg_in_image = ~0ull; // the segment whose clipped mask the mask image holds
@@ -91,8 +70,7 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, kUpdateWavesPerSimd) void upd
             c = 0;
             ++seg;
         }
-        const u64 g0 = seg * kSegGroups;
-        const u32 nvalid = a.groups - g0 < kSegGroups ? (u32)(a.groups - g0) : kSegGroups;
+        const u32 nvalid = segment_groups(a.groups, seg);
         if (seg != seg_in_image) { // (wave-uniform) the mask segment: once per wavefront and segment
             if (touched) {
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -104,12 +82,12 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, kUpdateWavesPerSimd) void upd
             const bool ok = list_walk(a.mask, 1u, seg, nvalid, m_or.fill, msk, lane, [&](u32) -> const ListOp & { return m_or; }, [&](u32) { touched = true; });
             if (!ok) return report_stream_error(a.ctrl, lane); // no column is read behind a refused mask segment
             if (touched) {
-                const u32 seg_rows = update_seg_rows(a.n_rows, seg);
+                const u32 seg_rows = segment_rows(a.n_rows, seg);
                 u32 any = 0;
 #pragma unroll
                 for (u32 s = 0; s < kSteps; ++s) {
                     const u32 g = 64u * s + lane;
-                    const u32 sel = msk[g] & update_row_bits(g, seg_rows);
+                    const u32 sel = msk[g] & group_row_bits(g, seg_rows);
                     msk[g] = sel;
                     any |= sel;
                 }
@@ -147,16 +125,7 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, kUpdateWavesPerSimd) void upd
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         const u32 total = image_words<kEmit>(dst, nvalid, stage, lane);
         const u64 item = c * a.n_segments + seg;
-        if (kEmit) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            const u64 at = a.offsets[item], have = a.offsets[item + 1] - at; // what the count pass found
-            const u32 words = (u64)total < have ? total : (u32)have;
-            for (u32 i = lane; i < words; i += 64u)
-                if (at + i < a.out_capacity) a.out[at + i] = stage[i];
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // the next item stages over these words
-        } else if (lane == 0) {
-            a.offsets[item] = (u64)total;
-        }
+        item_tail<kEmit>(a, a.offsets, item, total, stage, lane);
     }
 }
 
@@ -167,15 +136,8 @@ hipError_t launch_update_check(const UpdateArgs &, hipStream_t) { return hipSucc
 
 // count pass (emit = false: every item's words to a.offsets) or emit pass (a.offsets scanned: the words to their place)
 hipError_t launch_update_segments(const UpdateArgs &a, bool emit, hipStream_t s) {
-    const u64 n_items = a.n_columns * a.n_segments;
-    const u64 want = (n_items + kSegDecodeWaves - 1) / kSegDecodeWaves;
     constexpr u64 most = 256u * 3u; // CUs x resident workgroups of four wavefronts at 48 KiB of LDS each
-    const dim3 grid((unsigned)(want < 1 ? 1 : want > most ? most : want)), block(kSegDecodeWaves * 64);
-    if (emit)
-        hipLaunchKernelGGL(update_segments_kernel<true>, grid, block, 0, s, a);
-    else
-        hipLaunchKernelGGL(update_segments_kernel<false>, grid, block, 0, s, a);
-    return hipGetLastError();
+    return launch_count_or_emit(update_segments_kernel<false>, update_segments_kernel<true>, emit, a.n_columns * a.n_segments, kSegDecodeWaves, most, a, s);
 }
 
 } // namespace wah

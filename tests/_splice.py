@@ -11,6 +11,7 @@ Three statements of one thing:
 A Case names the pieces, the source bitmaps of every (piece, column), and optionally the way (tests/_foreign.py) a source's
 stream is written in."""
 import functools
+import os
 
 import numpy as np
 
@@ -211,7 +212,7 @@ def met_source_words(oracle, case):
 
 def grid_cap():
     """Workgroups of splice_segments_kernel at the most, read out of the source as _grid._most reads the others."""
-    return _grid._most(_grid.FETCH_SOURCE, "launch_splice_segments")
+    return _grid._most(os.path.join(_grid.CSRC, "wah_splice.hip"), "launch_splice_segments")
 
 
 # ---- the named cases --------------------------------------------------------------------------------------------------------------

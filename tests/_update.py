@@ -126,7 +126,7 @@ def entry_image(case, side, c, seg):
 
 
 def row_bits(n_rows, seg):
-    """update_row_bits for the 1024 groups of segment `seg`: the bits of every group that are rows."""
+    """group_row_bits (wah_device.hpp) for the 1024 groups of segment `seg`: the bits of every group that are rows."""
     seg_rows = min(max(n_rows - seg * SEG_BITS, 0), SEG_BITS)
     nb = np.clip(seg_rows - 31 * np.arange(SEG_GROUPS, dtype=np.int64), 0, 31)
     return ((np.int64(1) << nb) - 1).astype(np.uint32)

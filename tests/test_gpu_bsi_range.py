@@ -140,7 +140,7 @@ def test_rows_without_existence_match_zero(wah, oracle):
 
 
 def test_settled_rows_on_both_sides_of_the_chunk_edge_are_folded(wah, oracle):
-    """The one property the shared walk (list_walk, wah_bitop_list.hip) keeps for its four callers at once: a row whose segment
+    """The one property the shared walk (list_walk, wah_list_walk.hpp) keeps for its four callers at once: a row whose segment
     was settled in the gather -- one zero fill, never a batch -- is still folded, on either side of the edge between two chunks
     of 64 table rows.  992 + 31 words: two segments, the second one ragged.  Values are 64-bit multiples of 16, so slices 60 .. 63
     are all zero.

@@ -23,8 +23,8 @@ group) came out of BOTH routes of the two-operand call with the pad bits still i
 them, a fill of ones one group too long -- where the list call, the many-operand call and everything else gave compress() of
 the bitmap.  runs_clear_pad (wah_bitop_runs.hip) and the pad mask in IndexedSource::produce (wah_compress.hip) are the fixes.
 
-That the tests bite: libraries with ONE line of gpu-wah_amd/csrc/wah_bitop_list.hip changed, this file run once against each
-on an MI355X (63 tests; the others passed).
+That the tests bite: libraries with ONE line of the walk (gpu-wah_amd/csrc/wah_list_walk.hpp, then part of wah_bitop_list.hip)
+changed, this file run once against each on an MI355X (63 tests; the others passed).
 
   the all-literal fast path of list_apply_batch takes a zero word for a read past the range:
     `acc[p] = list_combine(r0, w0, m)` -> `acc[p] = w0 ? list_combine(r0, w0, m) : r0`

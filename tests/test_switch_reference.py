@@ -41,12 +41,12 @@ SOURCES = {
     "runs image": ("wah_bitop_runs.hip", r"want = \(total \* kTileSegs \* (\d+)u / (\d+)u / a\.n_segments \+ (\d+)u\) & ~\(u64\)(\d+)u;"),
     "runs scan threads": ("wah_bitop_runs.hip", r"const u64 per = \(n_tiles \+ 1023u\) / (\d+)u;"),
     "sums offsets threads": ("wah_decode.hip", r"sums_offsets_kernel, dim3\(1\), dim3\((\d+)\)"),
-    "kListShortFill": ("wah_bitop_list.hip", r"constexpr u32 kListShortFill = (\d+);"),
-    "WAH_LIST_DEPTH": ("wah_bitop_list.hip", r"#define WAH_LIST_DEPTH (\d+)"),
-    "list batch words": ("wah_bitop_list.hip", r"if \((\d+)u \* \(c\.b \+ 1u\) < cnt\)"),
-    "list chunk operands": ("wah_bitop_list.hip", r"j0 < n_rows; j0 \+= (\d+)u\)"),
+    "kListShortFill": ("wah_list_walk.hpp", r"constexpr u32 kListShortFill = (\d+);"),
+    "WAH_LIST_DEPTH": ("wah_list_walk.hpp", r"#define WAH_LIST_DEPTH (\d+)"),
+    "list batch words": ("wah_list_walk.hpp", r"if \((\d+)u \* \(c\.b \+ 1u\) < cnt\)"),
+    "list chunk operands": ("wah_list_walk.hpp", r"j0 < n_rows; j0 \+= (\d+)u\)"),
     "WAH_SEG_WAVES": ("wah_segdecode.hpp", r"#define WAH_SEG_WAVES (\d+)"),
-    "list count clamp factor": ("wah_bitop_list.hip", r"n0 = in0 \? min\(word_groups\(w0\), (\d+)u \* kSegGroups\)"),
+    "list count clamp factor": ("wah_list_walk.hpp", r"n0 = in0 \? min\(word_groups\(w0\), (\d+)u \* kSegGroups\)"),
 }
 
 

@@ -13,6 +13,9 @@ mnemonic sequences differ -- the instruction lines between the kernel's label an
 register numbers left out, compared with difflib -- with the net change of every mnemonic's count.  --show N lists the
 first N differing stretches of a kernel.
 
+A kernel that is missing from its own source in the new build is paired by name with the one other source that gained it: a move
+between files is compared like any other kernel, under its new source.
+
 Exit status 1 if a kernel appears or disappears, gains scratch, changes its LDS or loses occupancy, or if a kernel's resource
 record is missing from either build."""
 import argparse
@@ -78,6 +81,19 @@ def read_build(directory):
     return build
 
 
+def pair_moved(old, new):
+    """A kernel that the new build lacks in its parent's source and has, under the same name, in exactly one other source that the
+    parent lacks it in has moved: the parent's record goes under the new source, so that the two are compared.  {name: old source}"""
+    moved = {}
+    for source, ko in list(old.items()):
+        for k in [k for k in ko if k not in new.get(source, {})]:
+            homes = [s for s, kn in new.items() if k in kn and k not in old.get(s, {})]
+            if len(homes) == 1:
+                moved[k] = source
+                old.setdefault(homes[0], {})[k] = ko.pop(k)
+    return moved
+
+
 def demangle(names):
     for tool in ("llvm-cxxfilt", "c++filt", "/opt/rocm/llvm/bin/llvm-cxxfilt"):
         try:
@@ -99,6 +115,7 @@ def main():
     old, new = read_build(args.parent), read_build(args.new)
     if not old or not new:
         sys.exit("no device assembly in %s" % (args.parent if not old else args.new))
+    moved = pair_moved(old, new)
     failures = []
     for source in sorted(set(old) | set(new)):
         ko, kn = old.get(source, {}), new.get(source, {})
@@ -116,7 +133,7 @@ def main():
                 if lost:
                     failures.append("%s: no %s in the %s build's resource record" % (names[k], " / ".join(lost), which))
             figures = "  ".join("%s %s->%s" % (short, ro.get(field, "?"), rn.get(field, "?")) for short, field in FIELDS)
-            print("  %s\n    %s  instructions %d->%d" % (names[k], figures, len(so), len(sn)))
+            print("  %s%s\n    %s  instructions %d->%d" % (names[k], " (the parent's: %s)" % moved[k] if k in moved else "", figures, len(so), len(sn)))
             get = lambda r, field: r.get(dict(FIELDS)[field], 0)
             if get(rn, "scratch") > get(ro, "scratch"):
                 failures.append("%s: scratch %d -> %d" % (names[k], get(ro, "scratch"), get(rn, "scratch")))
