@@ -72,6 +72,7 @@ from .api import (  # noqa: F401
     fetch_device,
     FETCH_BITS,
     FETCH_FIRST,
+    values_device,
     count_device,
     count_masked_device,
     group_sum_device,

@@ -87,6 +87,9 @@ ABI_SYMBOLS = {
     "wah_fetch_scratch_bytes": (_sz, [_u64, _u64]),
     "wah_fetch_indexed_device": (_int, [ctypes.c_uint, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _sz, _vp]),
     "wah_fetch_status": (_int, [_vp, _vp]),
+    "wah_values_scratch_bytes": (_sz, [_u64, _u64]),
+    "wah_values_indexed_device": (_int, [ctypes.c_uint, _u64, _u64, _vp, _u64, _u64, _vp, _vp, _sz, _vp]),
+    "wah_values_status": (_int, [_vp, _vp]),
     "wah_select_scratch_bytes": (_sz, [_u64, _u64]),
     "wah_count_list_indexed_device": (_int, [_u64, _u64, _vp, _vp, _vp, _sz, _vp]),
     "wah_count_masked_indexed_device": (_int, [_u64, _u64, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
@@ -971,6 +974,30 @@ def fetch_device(table, rows, n_words, mode, scratch=None, out=None, check=True)
               lambda *tail: lib().wah_fetch_indexed_device(mode, n, k, table.data_ptr(), rows.data_ptr() if r else None, r,
                                                            out.data_ptr() if r else None, *tail),
               lib().wah_fetch_status, scratch, check)
+    return out
+
+
+def values_device(table, n_words, mode, first_row=0, n_rows=None, scratch=None, out=None, check=True):
+    """The values of the row range [first_row, first_row + n_rows) in one call, a whole attribute read back out of the index
+    (wah_values_indexed_device).  table and mode as for fetch_device; first_row / n_rows: Python ints, the window, n_rows
+    defaulting to the rows behind first_row (32 * n_words - first_row).  Entry i of the result is what fetch_device gives for the
+    listed row first_row + i.  Only the segments that overlap the window are read and checked.  Returns the int64 device tensor
+    [n_rows].  scratch / out: reuse these tensors; check=False: only enqueue (the caller reads wah_values_status later)."""
+    torch = _torch()
+    table = _operand_table(table)
+    dev = table.device
+    if mode not in (FETCH_BITS, FETCH_FIRST):
+        raise WahError("mode: FETCH_BITS or FETCH_FIRST")
+    n, k, first = int(n_words), int(table.shape[0]), int(first_row)
+    r = 32 * n - first if n_rows is None else int(n_rows)
+    if first < 0 or r < 0:
+        raise WahError("a window of rows inside the bitmap")
+    if scratch is None:
+        scratch = torch.empty(int(lib().wah_values_scratch_bytes(n, k)), dtype=torch.uint8, device=dev)
+    out = _int64_tensor(torch, out, (r,), dev, "out: a contiguous int64 [n_rows] tensor on the table's device")
+    _enqueued("wah_values_indexed_device", "values",
+              lambda *tail: lib().wah_values_indexed_device(mode, n, k, table.data_ptr(), first, r, out.data_ptr() if r else None, *tail),
+              lib().wah_values_status, scratch, check)
     return out
 
 

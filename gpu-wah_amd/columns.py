@@ -808,6 +808,92 @@ def keys_at_rows(wah, index, rows):
     return _fetch_columns(wah, stream, seg_offsets, n, list(range(n_values)), rows, wah.FETCH_FIRST)
 
 
+def _column_window(n_words_per_column, first, n_rows):
+    """The window [first, first + n_rows) of a column as Python ints, n_rows defaulting to the rows behind `first`."""
+    first = int(first)
+    n_rows = 32 * int(n_words_per_column) - first if n_rows is None else int(n_rows)
+    if first < 0 or n_rows < 0 or first + n_rows > 32 * int(n_words_per_column):
+        raise ValueError("the window's rows lie inside the column")
+    return first, n_rows
+
+
+def values_of_column(wah, bsi, first=0, n_rows=None):
+    """`SELECT value FROM t` over a row range: the values a bit-sliced attribute holds in rows [first, first + n_rows), in one call
+    and without a decoded slice in global memory (wah_values_indexed_device, WAH_FETCH_BITS) -- the inverse of bsi_from_values
+    at column scale: an export, an operand for torch, the input of a sort.  bsi: what bsi_from_values returned (or add_columns,
+    multiply_columns, set_values_where ...); n_rows defaults to 32 * n_words_per_column - first.  The conventions are those of
+    values_at_rows: with an existence bitmap that bitmap is the table's first row, its bit is masked off the values and returned
+    as `have`.  Returns (values int64 tensor, have bool tensor or None), entry i for row first + i."""
+    stream, seg_offsets, n, n_bits, has_exists = bsi
+    first, n_rows = _column_window(n, first, n_rows)
+    ids = ([n_bits] if has_exists else []) + list(range(n_bits))
+    got = wah.values_device(column_operand_table(stream, seg_offsets, n, ids), n, wah.FETCH_BITS, first, n_rows)
+    if not has_exists:
+        return got, None
+    return got & ((1 << n_bits) - 1), ((got >> n_bits) & 1) != 0
+
+
+def keys_of_column(wah, index, first=0, n_rows=None):
+    """The keys an equality-encoded attribute holds in rows [first, first + n_rows), in one call over ALL its value columns
+    (wah_values_indexed_device, WAH_FETCH_FIRST) -- the inverse of index_from_keys.  index: what index_from_keys returned; the
+    window as for values_of_column.  Returns an int64 tensor, -1 where no column has the row, as keys_at_rows does."""
+    stream, seg_offsets, n = index
+    first, n_rows = _column_window(n, first, n_rows)
+    n_values = (int(seg_offsets.numel()) - 1) // (n // SEGMENT_WORDS)
+    return wah.values_device(column_operand_table(stream, seg_offsets, n, list(range(n_values))), n, wah.FETCH_FIRST, first, n_rows)
+
+
+def _values_of_column_torch(wah, bsi, first=0, n_rows=None):
+    """values_of_column as it had to be done before wah_values_indexed_device, kept to be compared against (tools/values_time.py,
+    the tests): every slice is decoded into the matrix [n_slices, n_words] (one wah_decompress_segments_device call) and the
+    values are assembled with torch shifts and ORs, one slice after the other.  Arguments and result as values_of_column."""
+    import torch
+
+    stream, seg_offsets, n, n_bits, has_exists = bsi
+    first, n_rows = _column_window(n, first, n_rows)
+    k = n_bits + (1 if has_exists else 0)
+    matrix = wah.decompress_segments_device(stream, seg_offsets, k * n)[: k * n].view(k, n)
+    shifts = torch.arange(32, dtype=torch.int32, device=stream.device)
+
+    def bits(row):  # the window's rows of one decoded bitmap as int64 0 / 1: position 32 * word + bit
+        return ((matrix[row].view(n, 1) >> shifts) & 1).reshape(-1)[first: first + n_rows].to(torch.int64)
+
+    values = torch.zeros(n_rows, dtype=torch.int64, device=stream.device)
+    for i in range(n_bits):
+        values |= bits(i) << (n_bits - 1 - i)
+    return values, (bits(n_bits) != 0 if has_exists else None)
+
+
+def reorder_rows(wah, index, order, n_rows):
+    """Every column of an index rearranged together: row i of the result is row order[i] of the input -- ORDER BY over the whole
+    table, clustering it by a sort key so that its bitmaps compress better, the gather of a join; it generalises slice_rows and
+    keep_rows to any order.  index: the 3-tuple of index_from_keys or the 5-tuple of bsi_from_values, holding n_rows rows;
+    order: an int64 device tensor in any order, repeats allowed, every entry in [0, n_rows).  Plumbing: the column is read with
+    values_of_column / keys_of_column, gathered with torch.index_select and built again with bsi_from_values (the existence bits
+    carried through) or index_from_keys (n_values as keys_at_rows derives it; a row that no column has cannot be an equality
+    index's row: ValueError).  Returns the same kind of tuple, of len(order) rows."""
+    import torch
+
+    if len(index) not in (3, 5):
+        raise ValueError("index is an index_from_keys result or a bsi_from_values result")
+    n_rows = int(n_rows)
+    if order.dtype != torch.int64 or order.dim() != 1 or order.device != index[0].device:
+        raise ValueError("order: a one-dimensional int64 tensor on the index's device")
+    if order.numel():
+        lo, hi = (int(v) for v in torch.aminmax(order))
+        if lo < 0 or hi >= n_rows:
+            raise ValueError(f"order outside [0, {n_rows})")
+    if len(index) == 5:
+        values, have = values_of_column(wah, index, 0, n_rows)
+        exists = None if have is None else torch.index_select(have, 0, order)
+        return bsi_from_values(wah, torch.index_select(values, 0, order), index[3], exists=exists)
+    keys = torch.index_select(keys_of_column(wah, index, 0, n_rows), 0, order)
+    if keys.numel() and int(keys.min()) < 0:
+        raise ValueError("a row that no column of the index has")
+    n_values = (int(index[1].numel()) - 1) // (index[2] // SEGMENT_WORDS)
+    return index_from_keys(wah, keys, n_values)
+
+
 def select_values(wah, predicates, n_words_per_column, attributes, first=0, limit=None):
     """`SELECT a, b ... WHERE <conjunction> LIMIT limit OFFSET first` without decoding a bitmap: select_rows (predicates as for
     filter_columns), then one fetch per attribute over the rows it returned.  attributes: a list whose entries are what

@@ -1605,6 +1605,44 @@ int wah_fetch_indexed_device(unsigned mode, uint64_t n_words, uint64_t n_operand
 
 int wah_fetch_status(void *d_scratch, void *stream) { return scratch_status(d_scratch, stream); }
 
+// The values of a row range (wah_values.hip, values_items_kernel).  The scratch is the control block: the window is a host
+// argument, so the items are known here and nothing is listed on the device.
+size_t wah_values_scratch_bytes(uint64_t, uint64_t) { return round256(wah::kCtlWords * sizeof(uint32_t)); }
+
+int wah_values_indexed_device(unsigned mode, uint64_t n_words, uint64_t n_operands, const wah_bitop_operand *d_operands, uint64_t first_row,
+                              uint64_t n_rows, uint64_t *d_out, void *d_scratch, size_t scratch_bytes, void *stream) {
+    g_err[0] = 0;
+    if (mode != WAH_FETCH_BITS && mode != WAH_FETCH_FIRST) return refuse("unknown mode", WAH_ERR_ARG);
+    if (n_operands < 1 || n_operands > (mode == WAH_FETCH_BITS ? (uint64_t)WAH_BSI_MAX_SLICES : (uint64_t)WAH_BITOP_LIST_MAX_OPERANDS))
+        return refuse("between 1 and 64 table rows (WAH_FETCH_BITS) or 2^24 (WAH_FETCH_FIRST)", WAH_ERR_ARG);
+    if (n_words >= (1ull << 40)) return refuse("2^40 words or more", WAH_ERR_ARG);
+    if (first_row > 32 * n_words || n_rows > 32 * n_words - first_row) return refuse("a window that leaves the bitmap's 32 n_words rows", WAH_ERR_ARG);
+    if (!table_ok(n_operands, d_operands, n_words) || (n_rows && !d_out) || !aligned(d_out, 7) || !scratch_ok(d_scratch))
+        return refuse("null or misaligned table, output or scratch", WAH_ERR_ARG);
+    if (scratch_bytes < wah_values_scratch_bytes(n_words, n_operands)) return refuse("scratch too small", WAH_ERR_WORKSPACE);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    wah::ValuesArgs a = {};
+    a.table = reinterpret_cast<const wah::BitopListOperand *>(d_operands);
+    a.out = d_out;
+    a.ctrl = static_cast<uint32_t *>(d_scratch);
+    a.first_row = first_row;
+    a.n_rows = n_rows;
+    a.groups = seg_geometry(n_words).groups;
+    a.n_operands = (uint32_t)n_operands;
+    if (n_rows) { // the segments the window overlaps
+        constexpr uint64_t seg_rows = 31ull * wah::kSegGroups;
+        a.first_segment = first_row / seg_rows;
+        const uint64_t n_segments = (first_row + n_rows - 1) / seg_rows - a.first_segment + 1;
+        a.n_items = n_segments * (mode == WAH_FETCH_BITS && n_operands > 32 ? 2u : 1u);
+    }
+    hipError_t e = wah::launch_clear(d_scratch, wah::kCtlWords * sizeof(uint32_t), s); // the error word (read by wah_values_status)
+    if (e == hipSuccess) e = wah::launch_values_items(a, mode, s);
+    if (e != hipSuccess) return refuse("values launch", WAH_ERR_HIP, e);
+    return WAH_OK;
+}
+
+int wah_values_status(void *d_scratch, void *stream) { return scratch_status(d_scratch, stream); }
+
 // Set bits counted and listed in the compressed domain (wah_select.hip).  The scratch: control block, then the positions
 // call's rank table (one u64 per segment + 1) and the two upper levels of its scan (one u64 per 4096 entries of the level
 // below) -- it goes with n_words / 992, not with the operands' number or their words.

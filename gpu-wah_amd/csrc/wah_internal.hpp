@@ -386,6 +386,21 @@ struct FetchArgs {
 hipError_t launch_fetch_check(const FetchArgs &a, hipStream_t s);
 hipError_t launch_fetch_items(const FetchArgs &a, uint32_t mode, hipStream_t s);
 
+// wah_values_indexed_device (wah_values.hip): the values of the row RANGE [first_row, first_row + n_rows), the modes as above.
+// An item is a segment of the window (n_segments of them from first_segment on), under kFetchBits with more than 32 table rows
+// a segment and a half of the value: n_items = n_segments x halves, item t being segment first_segment + t / halves, half
+// t % halves.  out: one u64 per row of the window.
+struct ValuesArgs {
+    const BitopListOperand *table;
+    uint64_t *out;
+    uint32_t *ctrl;
+    uint64_t first_row, n_rows; // n_rows >= 1, first_row + n_rows <= 32 n_words
+    uint64_t groups;            // G of the bitmap
+    uint64_t first_segment, n_items;
+    uint32_t n_operands;
+};
+hipError_t launch_values_items(const ValuesArgs &a, uint32_t mode, hipStream_t s);
+
 // ... on operands of few words per segment: their runs merged in the compressed domain, one lane per segment
 // (wah_bitop_runs.hip): count pass, scan of the tile totals, write pass
 struct BitopRunsArgs {

@@ -695,7 +695,7 @@ int wah_bsi_kth_status(void *d_scratch, void *stream);
  * rows and the words the table's rows hold in the segments they touch, not with the index -- so the verdict depends on WHICH
  * rows are listed (a malformed segment that no listed row lies in is never seen), and not on the data in them.  A segment with
  * R listed rows is walked at least ceil(R / 64) times: for a list that approaches every row, decoding the slices is the better
- * tool.
+ * tool -- and wah_values_indexed_device (below) is that tool as one call, for a row RANGE.
  *   d_scratch: wah_fetch_scratch_bytes(n_words, n_rows) bytes, 256-byte aligned, no initialisation: the control words and the
  *   item list, ceil(n_rows / 64) + min(n_rows, segments) entries.  A multiple of 256, never 0, monotone in n_rows.
  * n_rows == 0 is WAH_OK (d_rows and d_out may be null) and wah_fetch_status() then reports WAH_OK.  Errors the host can see come
@@ -713,6 +713,47 @@ int wah_fetch_indexed_device(unsigned mode, uint64_t n_words, uint64_t n_operand
                              const uint64_t *d_rows, uint64_t n_rows, uint64_t *d_out, void *d_scratch, size_t scratch_bytes,
                              void *stream);
 int wah_fetch_status(void *d_scratch, void *stream);
+
+/* The values of a ROW RANGE in ONE call, without a decoded slice in global memory: a whole attribute read back out of the index --
+ * exporting it, handing it to other code as a column, ORDER BY / DISTINCT / GROUP BY over all rows, a join probe, reordering a
+ * table by a sort key.  It is the inverse of wah_bsi_build_device (WAH_FETCH_BITS) and of an equality-encoded index
+ * (WAH_FETCH_FIRST) at column scale, as wah_fetch_indexed_device is for a short list of rows.
+ *   d_out[i], for i in 0 .. n_rows - 1, is exactly what wah_fetch_indexed_device gives for the listed row first_row + i, with
+ *   the same table and the same mode:
+ *   WAH_FETCH_BITS: the unsigned value whose bit n_operands - 1 - j is that row's bit in table row j (row 0 is the MOST
+ *   significant; an existence bitmap in front of up to 63 slices becomes the top bit), 1 <= n_operands <= WAH_BSI_MAX_SLICES.
+ *   WAH_FETCH_FIRST: the lowest j whose bitmap has the row set, UINT64_MAX if none has, 1 <= n_operands <=
+ *   WAH_BITOP_LIST_MAX_OPERANDS.
+ *   d_operands: a table exactly as for the list call (8-byte aligned, windows into column matrices allowed, rows may repeat, the
+ *   length may be a capacity, an entry may name the not-yet-checked output of an earlier call on the stream).
+ *   first_row, n_rows: HOST arguments, first_row + n_rows <= 32 * n_words -- so a pad bit can never be asked for.
+ *   d_out: n_rows uint64, 8-byte aligned.
+ * The table is read by the device only: the call is asynchronous on `stream`, allocates nothing, never synchronises, and a
+ * captured graph replayed after the table was overwritten in place reads the NEW attribute; the window stays as captured.
+ * One launch and the clear of the control words; no workgroup waits for another.  One workgroup per item, a grid of capped size
+ * striding over the items.  An item is a segment that overlaps the window; for WAH_FETCH_BITS with more than 32 table rows it is
+ * a segment and a HALF of the value -- the table rows of significance 0 .. 31 (the table's last 32 rows) or 32 .. 63 (the rows in
+ * front of them) -- and owns that 4-byte half of every output element of its segment, so no two items touch the same byte.  The
+ * workgroup keeps 32 bits per row of the segment in LDS, its wavefronts walk the item's table rows as the list call does and fold
+ * each into them, and the rows leave 64 consecutive rows per wavefront store, clipped to the window.
+ * AS WITH FETCH, ONLY THE SEGMENTS THAT OVERLAP THE WINDOW ARE READ AND CHECKED; in those segments every table row is walked and
+ * checked, so the verdict depends on the window and not on the data.
+ * Every byte of d_out[0 .. n_rows) is written exactly once: no clearing pass, no read-modify-write of global memory, no atomics on
+ * the output; nothing is written in front of d_out[0] or at or behind d_out[n_rows].
+ *   d_scratch: wah_values_scratch_bytes(n_words, n_operands) bytes, 256-byte aligned, no initialisation: the control words only.
+ *   A multiple of 256, never 0.
+ * n_rows == 0 is WAH_OK (d_out may be null) and wah_values_status() then reports WAH_OK.  Errors the host can see come back
+ * before any HIP call, the argument checks first: an unknown mode, n_operands == 0 or above 64 (BITS) or above
+ * WAH_BITOP_LIST_MAX_OPERANDS (FIRST), n_words >= 2^40, a window that leaves 32 * n_words (overflow of first_row + n_rows
+ * included), a null or misaligned table, out (8 B) or scratch (256 B): WAH_ERR_ARG; too small a scratch: WAH_ERR_WORKSPACE.
+ * Everything only the device sees is reported by wah_values_status(), which synchronises the stream: WAH_ERR_STREAM for
+ * everything the list call refuses in an operand, in the segments that are read.  The output of a refused call is unspecified.
+ * wah_values_status(NULL, ...): WAH_ERR_ARG. */
+size_t wah_values_scratch_bytes(uint64_t n_words, uint64_t n_operands);
+int wah_values_indexed_device(unsigned mode, uint64_t n_words, uint64_t n_operands, const wah_bitop_operand *d_operands,
+                              uint64_t first_row, uint64_t n_rows, uint64_t *d_out, void *d_scratch, size_t scratch_bytes,
+                              void *stream);
+int wah_values_status(void *d_scratch, void *stream);
 
 /* What a query wants from a result bitmap, WITHOUT decoding it: how many bits it has set (COUNT(*)) and which ones (row
  * numbers, with LIMIT / OFFSET).  A bitmap of n_words words has its bits at positions p = 32 * word + bit, LSB first; group g,
