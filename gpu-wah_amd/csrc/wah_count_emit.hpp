@@ -3,7 +3,8 @@
 // offsets[item], launch_select_rank_scan turns the counts into the index in place, the emit pass writes every item's words where
 // the index says.  Written once for from_positions_kernel (wah_from_positions.hip), splice_segments_kernel (wah_splice.hip),
 // compact_segments_kernel (wah_compact.hip) and update_segments_kernel (wah_update.hip):
-//   item_run        the share-out of the items over the launch's wavefronts
+//   item_run        the share-out of the items over the launch's wavefronts (wah_device.hpp: the counting kernels of
+//                   wah_select.hip share their items out the same way)
 //   emit_total      the emit pass's one lane that reports the total and judges the capacity
 //   lone_zero_fill  the item that holds no set bit
 //   item_tail       what ends every item: its count stored, or its staged words clipped and stored
@@ -16,23 +17,6 @@
 
 namespace wah {
 namespace {
-
-// the items begin .. end - 1 of n_items that this wavefront owns: contiguous runs of equal length over the launch's wavefronts
-// (`waves` per workgroup), the last ones shorter or empty
-struct ItemRun {
-    u64 begin, end;
-    bool first; // the launch's first wavefront
-};
-__device__ __forceinline__ ItemRun item_run(u64 n_items, u32 waves, u32 wave) {
-    const u64 n_waves = (u64)gridDim.x * waves;
-    const u64 per = (n_items + n_waves - 1) / n_waves;
-    const u64 w = (u64)blockIdx.x * waves + wave;
-    ItemRun r;
-    r.begin = w * per < n_items ? w * per : n_items;
-    r.end = r.begin + per < n_items ? r.begin + per : n_items;
-    r.first = w == 0;
-    return r;
-}
 
 // the emit pass: one lane of the launch writes the words of all items and raises kErrCapacity where they do not fit.  offsets:
 // a.offsets, through whatever pointer type the kernel reads the scanned index with

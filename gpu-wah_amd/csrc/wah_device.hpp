@@ -246,6 +246,23 @@ __device__ __forceinline__ u64 first_end_behind(const u64 *starts, u64 n, u64 ba
     return lo;
 }
 
+// the items begin .. end - 1 of n_items that this wavefront owns: contiguous runs of equal length over the launch's wavefronts
+// (`waves` per workgroup), the last ones shorter or empty
+struct ItemRun {
+    u64 begin, end;
+    bool first; // the launch's first wavefront
+};
+__device__ __forceinline__ ItemRun item_run(u64 n_items, u32 waves, u32 wave) {
+    const u64 n_waves = (u64)gridDim.x * waves;
+    const u64 per = (n_items + n_waves - 1) / n_waves;
+    const u64 w = (u64)blockIdx.x * waves + wave;
+    ItemRun r;
+    r.begin = w * per < n_items ? w * per : n_items;
+    r.end = r.begin + per < n_items ? r.begin + per : n_items;
+    r.first = w == 0;
+    return r;
+}
+
 // expand / checker / merge kernels: one workgroup of four wavefronts per 4096-word tile
 constexpr int kExpandThreads = kExpandWaves * 64;                 // 256
 constexpr int kExpandWordsPerThread = kScanTileWords / kExpandThreads; // 16

@@ -54,6 +54,32 @@ __device__ __forceinline__ void seg_load_words(const SegmentsArgs &a, const SegR
     }
 }
 
+// Where the two words a lane holds of the batch at word wi (x0, x1: words wi + 2 lane and the one behind it, of the segment's
+// cnt) lie in the segment: their groups n0 / n1 (0: no word there) and the groups lo0 / lo1 they start at, behind the `pos` groups
+// of the batches in front; pos moves on by the batch's groups.  empty: one of the two is a fill of no groups.  (The masked counts
+// of wah_select.hip take it.  seg_mark below, seg_expand_scatter and list_apply_batch state the same lines themselves: through a
+// function the word index 128 b + 2 lane is an add where their kernels have an or, and the hot decoders keep their sequence.)
+struct BatchPlaces {
+    u32 n0, n1, lo0, lo1;
+    bool in0, in1, empty;
+};
+__device__ __forceinline__ BatchPlaces batch_places(u32 x0, u32 x1, u32 wi, u32 cnt, u32 &pos, u32 lane) {
+    BatchPlaces p;
+    const u32 i0 = wi + 2u * lane;
+    p.in0 = i0 < cnt;
+    p.in1 = i0 + 1u < cnt;
+    // counts are clamped so that a corrupt word cannot wrap the 32-bit sums; anything above 1024 fails the total
+    p.n0 = p.in0 ? min(word_groups(x0), 2u * kSegGroups) : 0u;
+    p.n1 = p.in1 ? min(word_groups(x1), 2u * kSegGroups) : 0u;
+    p.empty = (p.in0 && p.n0 == 0u) || (p.in1 && p.n1 == 0u);
+    // a full batch of literals (dense data): consecutive positions, no scan
+    const u32 incl = (wi + 128u <= cnt && __ballot((int)(x0 | x1) < 0) == 0) ? 2u * lane + 2u : wave_scan_incl32(p.n0 + p.n1);
+    p.lo1 = pos + incl - p.n1;
+    p.lo0 = p.lo1 - p.n0;
+    pos += (u32)__builtin_amdgcn_readlane((int)incl, 63);
+    return p;
+}
+
 // Mark phase of one segment: parks its words (x0/x1, two per lane and batch) in `words` and flags the group at which
 // every word starts (as mark_pairs).  Returns false when the range is not exactly this segment: the words must add up
 // to nvalid groups, none of them empty -- then the r-th flag is the r-th word.

@@ -8,26 +8,32 @@
 // the AND of several rows per group, with the group's own count and the sums of bit-sliced attributes -- SELECT g, h, COUNT(*),
 // SUM(x) WHERE ... GROUP BY g, h).
 //
-// Five kinds of launches, and no workgroup of any of them waits for another:
-//   select_count_kernel   (operand, segment) pairs shared out over the launch's wavefronts in contiguous runs.  The table row is checked before its index pointer
-//                         is followed, the index range (seg_range) before the stream is read through it; the segment's words
-//                         are loaded two per lane per batch of 128 (seg_load_words) and counted where they lie -- a literal is
-//                         its popcount, a one-fill 31 bits per group, a zero-fill nothing: no group is ever decoded.  The
-//                         words' groups are summed beside the bits, and a segment whose words do not make up exactly its
-//                         groups, or that holds an empty fill, is refused (kErrStream) and counts nothing.  A wavefront sums
-//                         its run and adds into the operand's count with a 64-bit vector atomic when the operand changes, a
-//                         workgroup merges its four runs' ends first; the positions call stores every segment's count into its
-//                         rank table instead.  The cost goes with the operands' words.
-//   count_masked_kernel   (mask, chunk of up to 64 operands, segment) items shared out in the same contiguous runs.  The mask's segment
-//                         is decoded (seg_mark / seg_group) into a per-wavefront LDS image M[1024] of its groups, pad bits cleared,
-//                         beside P[1024], the exclusive prefix sum of their popcounts; the words of the chunk's operands are counted
-//                         where they lie against it, lane l keeping the l-th operand's count: a literal at group lo is popcount(x & M[lo]), a one-fill of n groups P[lo + n] - P[lo], a
-//                         zero-fill nothing.  A mask segment of one fill word needs no image: zeros count nothing, ones count
-//                         as select_count_kernel does.  LDS: 10 KiB per wavefront, 40 960 B per workgroup: four workgroups per CU.
-//   group_count_kernel /  count_masked_kernel's items, LDS and atomics with an image that is the AND of the call's filter rows and the
-//   group_fold_kernel     group's own: made conjunct by conjunct, the first one stored, the later ones ANDed in place, P and the pad
-//                         bits in one pass behind the last; a conjunct of one one-fill is skipped, one zero-fill leaves nothing to
-//                         count, and the conjunction's own bits are counted once per (group, segment).  The fold: one thread per
+// Five kinds of launches, and no workgroup of any of them waits for another.  The three counting kernels share their frame, and
+// every shared piece is written once, by the helper named here:
+//   the items             shared out over the launch's wavefronts in contiguous runs (item_run, wah_device.hpp).  A table row is
+//                         checked before its index pointer is followed, the index range (seg_range) before the stream is read
+//                         through it (select_range); the segment's words are loaded two per lane per batch of 128 (seg_load_words)
+//                         and the next item's row and range are on their way while this one's words are counted.
+//   where they lie        an operand's words are counted without decoding a group (count_where_they_lie): a literal is its
+//                         popcount, a one-fill 31 bits per group, a zero-fill nothing.  The words' groups are summed beside the
+//                         bits, and a segment whose words do not make up exactly its groups, or that holds an empty fill, is
+//                         refused (kErrStream) and counts nothing.
+//   the run ends          a wavefront sums its run and adds into global memory with 64-bit vector atomics only when the counter
+//                         it counts for changes; what the workgroup's four wavefronts hold at their runs' ends is merged in LDS
+//                         first (merge_run_ends; select_count_kernel: its own scalar form of it).
+//   select_count_kernel   (operand, segment) pairs, one counter per operand; the positions call stores every segment's count
+//                         into its rank table instead.  The cost goes with the operands' words.
+//   count_masked_kernel   (mask, chunk of up to 64 operands, segment) items (ChunkCursor).  The mask's segment is decoded (seg_mark /
+//                         seg_group) into a per-wavefront LDS image M[1024] of its groups, pad bits cleared, beside P[1024], the
+//                         exclusive prefix sum of their popcounts (image_prefix); the words of the chunk's operands are counted
+//                         against it (count_against_image), lane l keeping the l-th operand's count (count_under_mask): a literal
+//                         at group lo is popcount(x & M[lo]), a one-fill of n groups P[lo + n] - P[lo], a zero-fill nothing.  A
+//                         mask segment of one fill word needs no image: zeros count nothing, under ones the words count where
+//                         they lie.  LDS: 10 KiB per wavefront, 40 960 B per workgroup: four workgroups per CU.
+//   group_count_kernel /  count_masked_kernel's items, LDS and run ends with an image that is the AND of the call's filter rows and
+//   group_fold_kernel     the group's own: made conjunct by conjunct, the first one stored, the later ones ANDed in place, P and the
+//                         pad bits in one pass behind the last; a conjunct of one one-fill is skipped, one zero-fill leaves nothing
+//                         to count, and the conjunction's own bits are counted once per (group, segment).  The fold: one thread per
 //                         (group, attribute) adds the counts of the attribute's slices, shifted, in 128 bits.
 //   rank_reduce_kernel /  the exclusive prefix sum of the rank table (one u64 per segment, + 1 for the total): chunks of 4096
 //   rank_scan_kernel      entries, their totals one level up (two levels up for more than 2^24 segments), scanned there, then
@@ -93,20 +99,54 @@ __device__ __forceinline__ SegRange select_range(const SelectRow &r, u64 groups,
     return rg;
 }
 
+// what a lane's words of a segment count: their bits, their groups, and whether one of them is a fill of no groups
+struct SegCount {
+    u32 bits, grps;
+    bool empty_word;
+};
+// the verdict on a segment whose words make up `grps` groups in all, as seg_mark gives it: exactly its groups, no word empty
+__device__ __forceinline__ bool segment_ok(const SegRange &rg, u32 grps, bool empty_word) {
+    return !rg.bad && grps == rg.nvalid && __ballot(empty_word) == 0ull;
+}
+// A segment's words counted where they lie.  count_bits: a literal counts its popcount and a one-fill 31 bits per group (otherwise
+// only the groups are counted); the bitmap's last word -- the last word of its last segment -- loses the pad bits.
+__device__ __forceinline__ SegCount count_where_they_lie(const SegRange &rg, const u32 (&x0)[kSegBatches], const u32 (&x1)[kSegBatches], bool count_bits,
+                                                         bool last_seg, u32 pad_bits, u32 pad_mask, u32 lane) {
+    bool empty_word = false;
+    u32 grps = 0, bits = 0;
+#pragma unroll
+    for (int b = 0; b < kSegBatches; ++b) {
+        if (128u * b < rg.cnt) { // wave-uniform
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const u32 x = h ? x1[b] : x0[b];
+                const u32 i = 128u * b + 2u * lane + h;
+                const bool in = i < rg.cnt;
+                // counts are clamped so that a corrupt word cannot wrap the 32-bit sums; anything above 1024 fails the total
+                const u32 n = in ? min(word_groups(x), 2u * kSegGroups) : 0u;
+                empty_word |= in && n == 0u;
+                const bool lit = (int)x >= 0, ones = (x & kFillOne) == kFillOne;
+                const bool last_word = last_seg && i == rg.cnt - 1u; // of the bitmap
+                const u32 pad = last_word ? pad_bits : 0u;
+                const u32 fill_bits = ones && n ? 31u * n - pad : 0u;
+                bits += !(in && count_bits) ? 0u : lit ? (u32)__builtin_popcount(x & (last_word ? pad_mask : kOnes31)) : fill_bits;
+                grps += n;
+            }
+        }
+    }
+    return {bits, grps, empty_word};
+}
+
 // kTable: one count per table row, added up over its segments; otherwise the one operand `one`, one count per segment.
-// The (operand, segment) pairs are shared out in CONTIGUOUS runs, one per wavefront: a wavefront adds its segments' counts up
-// and issues one atomic when the operand changes, and what the four wavefronts of a workgroup hold at their ends is merged in
-// LDS first -- an atomic per segment would be 270 000 of them on ONE address for a 1 GiB operand, 11.6 ns each (3.2 ms, measured;
-// the words themselves take a tenth of that).  While a segment's words are counted the next segment's index pair is on its way.
+// Why the runs are CONTIGUOUS and their ends merged: an atomic per segment would be 270 000 of them on ONE address for a 1 GiB
+// operand, 11.6 ns each (3.2 ms, measured; the words themselves take a tenth of that).
 template <bool kTable>
 __global__ __launch_bounds__(kSegDecodeWaves * 64, 8) void select_count_kernel(const SelectCountArgs a) {
     __shared__ u64 s_j[kSegDecodeWaves], s_acc[kSegDecodeWaves];
     const u32 wave = wave_id(), lane = lane_id();
     const u64 n_items = kTable ? (u64)a.n_operands * a.n_segments : a.n_segments;
-    const u64 n_waves = (u64)gridDim.x * kSegDecodeWaves;
-    const u64 per = (n_items + n_waves - 1) / n_waves;
-    const u64 w = (u64)blockIdx.x * kSegDecodeWaves + wave;
-    const u64 begin = w * per < n_items ? w * per : n_items, end = begin + per < n_items ? begin + per : n_items;
+    const ItemRun run = item_run(n_items, kSegDecodeWaves, wave);
+    const u64 begin = run.begin, end = run.end;
     const u32 pad_mask = kOnes31 >> a.pad_bits;
     u64 j = kTable ? begin / a.n_segments : 0ull;
     u64 seg = begin - j * a.n_segments;
@@ -133,31 +173,9 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, 8) void select_count_kernel(c
             if (kTable && last_of_operand) next_row = select_row<kTable>(a, j_next);
             next = select_range(next_row, a.groups, seg_next);
         }
-        // the bitmap's last word (the last word of its last segment) loses the pad bits
-        const u32 last = last_of_operand ? rg.cnt - 1u : 0xFFFFFFFFu;
-        u32 bits = 0, grps = 0;
-        bool empty_word = false;
-#pragma unroll
-        for (int b = 0; b < kSegBatches; ++b) {
-            if (128u * b < rg.cnt) { // wave-uniform
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const u32 x = h ? x1[b] : x0[b];
-                    const u32 i = 128u * b + 2u * lane + h;
-                    const bool in = i < rg.cnt;
-                    // counts are clamped so that a corrupt word cannot wrap the 32-bit sums; anything above 1024 fails the total
-                    const u32 n = in ? min(word_groups(x), 2u * kSegGroups) : 0u;
-                    empty_word |= in && n == 0u;
-                    const bool lit = (int)x >= 0, ones = (x & kFillOne) == kFillOne;
-                    const u32 pad = i == last ? a.pad_bits : 0u;
-                    const u32 fill_bits = ones && n ? 31u * n - pad : 0u;
-                    bits += !in ? 0u : lit ? (u32)__builtin_popcount(x & (i == last ? pad_mask : kOnes31)) : fill_bits;
-                    grps += n;
-                }
-            }
-        }
-        const u32 total_grps = wave_total32(grps), total_bits = wave_total32(bits);
-        const bool ok = !rg.bad && total_grps == rg.nvalid && __ballot(empty_word) == 0ull;
+        const SegCount n = count_where_they_lie(rg, x0, x1, true, last_of_operand, a.pad_bits, pad_mask, lane);
+        const u32 total_grps = wave_total32(n.grps), total_bits = wave_total32(n.bits);
+        const bool ok = segment_ok(rg, total_grps, n.empty_word);
         refused |= !ok;
         if (kTable) {
             acc += ok ? (u64)total_bits : 0ull;
@@ -196,7 +214,7 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, 8) void select_count_kernel(c
     }
 }
 
-// ---- counts under a mask -----------------------------------------------------------------------------------------------------
+// ---- counts under a mask, and under a conjunction: what the two chunked kernels share ------------------------------------------
 __device__ __forceinline__ SelectRow table_row(const BitopListOperand *table, u64 j) {
     const SelConstU64 e = (SelConstU64)(uintptr_t)(table + j);
     SelectRow r;
@@ -213,6 +231,29 @@ constexpr u32 kMaskNone = 0, kMaskZeros = 1, kMaskOnes = 2, kMaskImage = 3, kMas
 // entry 1024 (the total is a scalar) and the workgroup's merge at the end borrows wavefront 0's M.
 constexpr u32 kMaskedP = 0, kMaskedWords = 2048, kMaskedM = 2048 + 4096, kMaskedWaveLds = 2048 + 4096 + 4096;
 
+// P and the pad rule of a new image: M[g] = group g of the image (group_of_step(s, g) for g = 64 s + lane; m_is_new: M does not
+// hold it yet), the bitmap's last group without its pad bits; P[g] = the set bits of the groups in front of g.  Returns their
+// total.  (P goes over the mark phase's flags: they are in registers, or no longer needed, when this is called.)
+template <class GroupOfStep>
+__device__ __forceinline__ u32 image_prefix(u32 *M, unsigned short *P, bool m_is_new, bool last_seg, u32 nvalid, u32 pad_mask, u32 lane,
+                                            GroupOfStep group_of_step) {
+    const u32 pad_group = last_seg ? nvalid - 1u : 0xFFFFFFFFu;
+    u32 run = 0;
+#pragma unroll
+    for (int s = 0; s < (int)kSteps; ++s) {
+        const u32 g = (u32)(64 * s) + lane;
+        u32 grp = group_of_step(s, g);
+        if (g == pad_group) grp &= pad_mask;
+        if (m_is_new || g == pad_group) M[g] = grp;
+        const u32 cnt = (u32)__builtin_popcount(grp);
+        const u32 incl = wave_scan_incl32(cnt);
+        P[g] = (unsigned short)(run + incl - cnt); // at most 31 744
+        run += (u32)__builtin_amdgcn_readlane((int)incl, 63);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    return run;
+}
+
 // the bits an operand word of n groups at group lo shares with the mask image
 __device__ __forceinline__ u32 image_bits(u32 x, u32 n, u32 lo, const u32 *M, const unsigned short *P, u32 p_total) {
     if (n == 0u) return 0u; // (no word here, or an empty fill: refused)
@@ -223,16 +264,145 @@ __device__ __forceinline__ u32 image_bits(u32 x, u32 n, u32 lo, const u32 *M, co
     const u32 p_hi = hi >= kSegGroups ? p_total : (u32)P[hi], p_lo = lo >= kSegGroups ? p_total : (u32)P[lo];
     return p_hi - p_lo;
 }
+// a segment's words counted against the image, where they lie (batch_places); grps: the segment's, in every lane
+__device__ __forceinline__ SegCount count_against_image(const SegRange &rg, const u32 (&x0)[kSegBatches], const u32 (&x1)[kSegBatches], const u32 *M,
+                                                        const unsigned short *P, u32 p_total, u32 lane) {
+    u32 bits = 0, pos = 0; // pos: groups covered by the batches so far
+    bool empty_word = false;
+#pragma unroll
+    for (int b = 0; b < kSegBatches; ++b) {
+        if (128u * b < rg.cnt) { // wave-uniform
+            const BatchPlaces p = batch_places(x0[b], x1[b], 128u * b, rg.cnt, pos, lane);
+            empty_word |= p.empty;
+            bits += image_bits(x0[b], p.n0, p.lo0, M, P, p_total) + image_bits(x1[b], p.n1, p.lo1, M, P, p_total);
+        }
+    }
+    return {bits, pos, empty_word};
+}
 
-// counts[i * n_operands + j] += the set bits of mask i AND operand j.  A work item is (mask i, chunk c of a.chunk <= 64 consecutive
-// operands, segment): the mask segment's image is made once and serves the chunk's operands one after the other, lane l of the
-// wavefront keeping the count of the chunk's l-th operand.  The items, ordered (i, c, segment), are shared out in contiguous runs
-// exactly as select_count_kernel shares its pairs out, and for the same reason: a wavefront sums its run and issues its atomics --
-// one wave instruction over the chunk's consecutive counts -- when (i, c) changes, the workgroup's run ends merged in LDS first.
-// (The first version took (mask, operand, segment) triples in the order (i, j, segment) and made the image anew for every
-// operand: 3.5 - 5 us per triple and wavefront, nearly all of it the image: DESIGN 5.11.)  Consecutive items share the mask
-// segment only in bitmaps of one segment; then the image is kept.  EVERY segment of every mask and operand is checked, also under
-// a mask segment of zeros: the verdict does not depend on the data.
+// The end of an operand's segment under the mask segment the wavefront holds (kind; M, P, p_total under kMaskImage): its words
+// counted -- against the image, where they lie under a mask of ones, not at all under one of zeros -- and judged under EVERY
+// kind, so that the verdict does not depend on the data; lane jj, which keeps the count of the chunk's jj-th operand, adds the bits.
+__device__ __forceinline__ void count_under_mask(u32 kind, const SegRange &org, const u32 (&x0)[kSegBatches], const u32 (&x1)[kSegBatches], const u32 *M,
+                                                 const unsigned short *P, u32 p_total, bool last_seg, u32 pad_bits, u32 pad_mask, u32 jj, u32 lane, u64 &acc,
+                                                 bool &refused) {
+    SegCount n;
+    if (kind == kMaskImage) { // wave-uniform
+        n = count_against_image(org, x0, x1, M, P, p_total, lane);
+    } else {
+        n = count_where_they_lie(org, x0, x1, kind == kMaskOnes, last_seg, pad_bits, pad_mask, lane);
+        n.grps = wave_total32(n.grps);
+    }
+    const u32 total_bits = wave_total32(n.bits);
+    const bool ok = kind != kMaskBad && segment_ok(org, n.grps, n.empty_word);
+    refused |= !ok;
+    if (lane == jj && ok) acc += (u64)total_bits;
+}
+
+// Where a wavefront stands in its run of (row, chunk, segment) items -- row: a mask, or a group; chunk c: `chunk` <= 64
+// consecutive operands that share the row's image of the segment, served one after the other (jj) --, ordered (row, chunk,
+// segment).  q = row * n_chunks + c names the counters the wavefront counts for: lane l's is operand c * chunk + l under the row.
+struct ChunkBehind {
+    u64 j0; // the chunk's first operand
+    u32 jn; // and how many it has
+    bool last_jj, last_seg, last_c;
+    u64 q, seg, row, c; // of the item behind this one
+};
+struct ChunkCursor {
+    u32 n_operands, chunk;
+    u64 n_segments, n_chunks;
+    u64 item, end;
+    u64 q, seg, row, c;
+    u32 jj;
+    __device__ __forceinline__ bool more() const { return item + 1 < end; } // the run goes on behind this item
+    // what comes behind this operand's segment: the chunk's next operand (!last_jj), or the next item
+    __device__ __forceinline__ ChunkBehind behind() const {
+        ChunkBehind b;
+        b.j0 = c * chunk;
+        b.jn = n_operands - b.j0 < chunk ? (u32)(n_operands - b.j0) : chunk;
+        b.last_jj = jj + 1u == b.jn;
+        b.last_seg = seg + 1 == n_segments;
+        b.last_c = c + 1 == n_chunks;
+        b.seg = b.last_seg ? 0ull : seg + 1;
+        b.q = b.last_seg ? q + 1 : q;
+        b.c = !b.last_seg ? c : b.last_c ? 0ull : c + 1;
+        b.row = b.last_seg && b.last_c ? row + 1 : row;
+        return b;
+    }
+    __device__ __forceinline__ void advance(const ChunkBehind &b) {
+        if (!b.last_jj) {
+            ++jj;
+        } else {
+            if (more()) {
+                q = b.q;
+                seg = b.seg;
+                row = b.row;
+                c = b.c;
+            }
+            ++item;
+            jj = 0;
+        }
+    }
+};
+__device__ __forceinline__ ChunkCursor chunk_cursor(u32 n_rows, u32 n_operands, u32 chunk, u64 n_segments, u32 wave) {
+    ChunkCursor at;
+    at.n_operands = n_operands;
+    at.chunk = chunk;
+    at.n_segments = n_segments;
+    at.n_chunks = ((u64)n_operands + chunk - 1) / chunk;
+    const ItemRun run = item_run((u64)n_rows * at.n_chunks * n_segments, kSegDecodeWaves, wave);
+    at.item = run.begin;
+    at.end = run.end;
+    at.q = run.begin / n_segments;
+    at.seg = run.begin - at.q * n_segments;
+    at.row = at.q / at.n_chunks;
+    at.c = at.q - at.row * at.n_chunks;
+    at.jj = 0;
+    return at;
+}
+
+// What the workgroup's wavefronts hold for the counters their runs end in (q: ~0 for a wavefront without a run; acc: lane l's
+// count; kRows: the row's own counter `rows` with racc beside it), merged and added: consecutive runs, so equal q are neighbours.
+// One wave instruction adds a chunk's consecutive counts.  (Every image is done with: the merge borrows them.)
+template <bool kRows>
+__device__ __forceinline__ void merge_run_ends(unsigned char (*lds)[kMaskedWaveLds], u64 q, u64 acc, u64 racc, u64 n_chunks, u64 *counts, u64 *rows,
+                                               u32 n_operands, u32 chunk, u32 wave, u32 lane) {
+    __syncthreads();
+    u64 *s_q = reinterpret_cast<u64 *>(lds[0] + kMaskedWords), *s_r = s_q + kSegDecodeWaves;
+    reinterpret_cast<u64 *>(lds[wave] + kMaskedM)[lane] = acc;
+    if (lane == 0) {
+        s_q[wave] = q;
+        if (kRows) s_r[wave] = racc;
+    }
+    __syncthreads();
+    if (wave == 0) {
+        u64 at = ~0ull, sum = 0, rsum = 0;
+        for (int v = 0; v <= kSegDecodeWaves; ++v) {
+            const u64 qv = v < kSegDecodeWaves ? s_q[v] : ~0ull;
+            if (qv != at) { // wave-uniform
+                if (at != ~0ull) {
+                    const u64 mr = at / n_chunks, mc = at - mr * n_chunks;
+                    if (sum) atomicAdd(reinterpret_cast<unsigned long long *>(counts + mr * n_operands + mc * chunk + lane), (unsigned long long)sum);
+                    if (kRows && lane == 0 && rsum) atomicAdd(reinterpret_cast<unsigned long long *>(rows + mr), (unsigned long long)rsum);
+                }
+                at = qv;
+                sum = 0;
+                rsum = 0;
+            }
+            if (v < kSegDecodeWaves) {
+                sum += reinterpret_cast<const u64 *>(lds[v] + kMaskedM)[lane];
+                if (kRows) rsum += s_r[v];
+            }
+        }
+    }
+}
+
+// ---- counts under a mask -----------------------------------------------------------------------------------------------------
+// counts[i * n_operands + j] += the set bits of mask i AND operand j; the cursor's row is the mask i.  The mask segment's image is
+// made once per item and serves the chunk's operands.  (The first version took (mask, operand, segment) triples in the order (i, j,
+// segment) and made the image anew for every operand: 3.5 - 5 us per triple and wavefront, nearly all of it the image: DESIGN
+// 5.11.)  Consecutive items share the mask segment only in bitmaps of one segment; then the image is kept.  The next mask row and
+// range are fetched with the next operand's, and P is made inside the steps that make M.
 __global__ __launch_bounds__(kSegDecodeWaves * 64) void count_masked_kernel(const CountMaskedArgs a) {
     __shared__ __attribute__((aligned(16))) unsigned char s_lds[kSegDecodeWaves][kMaskedWaveLds];
     const u32 wave = wave_id(), lane = lane_id();
@@ -240,62 +410,46 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64) void count_masked_kernel(cons
     unsigned short *P = reinterpret_cast<unsigned short *>(s_lds[wave] + kMaskedP);
     u32 *words = reinterpret_cast<u32 *>(s_lds[wave] + kMaskedWords);
     u32 *M = reinterpret_cast<u32 *>(s_lds[wave] + kMaskedM);
-    const u64 n_chunks = ((u64)a.n_operands + a.chunk - 1) / a.chunk;
-    const u64 n_items = (u64)a.n_masks * n_chunks * a.n_segments;
-    const u64 n_waves = (u64)gridDim.x * kSegDecodeWaves;
-    const u64 per = (n_items + n_waves - 1) / n_waves;
-    const u64 w = (u64)blockIdx.x * kSegDecodeWaves + wave;
-    const u64 begin = w * per < n_items ? w * per : n_items, end = begin + per < n_items ? begin + per : n_items;
+    ChunkCursor at = chunk_cursor(a.n_masks, a.n_operands, a.chunk, a.n_segments, wave);
+    const bool has_run = at.item < at.end;
     const u32 pad_mask = kOnes31 >> a.pad_bits;
-    u64 item = begin;
-    u64 q = begin / a.n_segments; // the pairs' group: i * n_chunks + c
-    u64 seg = begin - q * a.n_segments;
-    u64 i = q / n_chunks, c = q - i * n_chunks;
-    u32 jj = 0; // the operand inside the chunk
     u64 acc = 0; // lane l: operand c * chunk + l under mask i
     bool refused = false;
     u32 kind = kMaskNone, p_total = 0;
     u64 img_i = 0, img_seg = 0;
     SelectRow mrow = {}, orow = {}, next_mrow = {}, next_orow = {};
     SegRange next_m = {}, next_o = {};
-    if (begin < end) {
-        next_mrow = table_row(a.masks, i);
-        next_orow = table_row(a.operands, c * a.chunk);
-        next_m = select_range(next_mrow, a.groups, seg);
-        next_o = select_range(next_orow, a.groups, seg);
+    if (has_run) {
+        next_mrow = table_row(a.masks, at.row);
+        next_orow = table_row(a.operands, at.c * a.chunk);
+        next_m = select_range(next_mrow, a.groups, at.seg);
+        next_o = select_range(next_orow, a.groups, at.seg);
     }
 #pragma nounroll
-    while (item < end) {
+    while (at.item < at.end) {
         const SegRange mrg = next_m, org = next_o;
         mrow = next_mrow;
         orow = next_orow;
-        const bool fresh = jj == 0u && (kind == kMaskNone || i != img_i || seg != img_seg); // wave-uniform
+        const bool fresh = at.jj == 0u && (kind == kMaskNone || at.row != img_i || at.seg != img_seg); // wave-uniform
         SegmentsArgs msa = {}, osa = {};
         msa.comp = reinterpret_cast<const u32 *>((uintptr_t)mrow.comp);
         osa.comp = reinterpret_cast<const u32 *>((uintptr_t)orow.comp);
         u32 m0[kSegBatches], m1[kSegBatches], x0[kSegBatches], x1[kSegBatches];
         if (fresh) seg_load_words(msa, mrg, m0, m1, lane);
         seg_load_words(osa, org, x0, x1, lane);
-        // what comes behind this operand's segment: the chunk's next operand, or the next item
-        const u64 j0 = c * a.chunk;
-        const u32 jn = a.n_operands - j0 < a.chunk ? (u32)(a.n_operands - j0) : a.chunk;
-        const bool last_jj = jj + 1u == jn;
-        const bool last_seg = seg + 1 == a.n_segments;
-        const bool last_c = c + 1 == n_chunks;
-        const u64 seg_next = last_seg ? 0ull : seg + 1, q_next = last_seg ? q + 1 : q;
-        const u64 c_next = !last_seg ? c : last_c ? 0ull : c + 1, i_next = last_seg && last_c ? i + 1 : i;
-        if (!last_jj) {
-            next_orow = table_row(a.operands, j0 + jj + 1u);
-            next_o = select_range(next_orow, a.groups, seg);
-        } else if (item + 1 < end) {
-            next_orow = table_row(a.operands, c_next * a.chunk);
-            if (i_next != i) next_mrow = table_row(a.masks, i_next);
-            next_m = select_range(next_mrow, a.groups, seg_next);
-            next_o = select_range(next_orow, a.groups, seg_next);
+        const ChunkBehind nx = at.behind();
+        if (!nx.last_jj) {
+            next_orow = table_row(a.operands, nx.j0 + at.jj + 1u);
+            next_o = select_range(next_orow, a.groups, at.seg);
+        } else if (at.more()) {
+            next_orow = table_row(a.operands, nx.c * a.chunk);
+            if (nx.row != at.row) next_mrow = table_row(a.masks, nx.row);
+            next_m = select_range(next_mrow, a.groups, nx.seg);
+            next_o = select_range(next_orow, a.groups, nx.seg);
         }
         if (fresh) {
-            img_i = i;
-            img_seg = seg;
+            img_i = at.row;
+            img_seg = at.seg;
             const u32 first = (u32)__builtin_amdgcn_readfirstlane((int)m0[0]); // lane 0 holds the segment's first word
             if (!mrg.bad && mrg.cnt == 1u && (first & kFillZero) && (first & kCountMask) == mrg.nvalid) {
                 kind = (first & kFillOne) == kFillOne ? kMaskOnes : kMaskZeros; // one fill over the segment: no image
@@ -306,110 +460,20 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64) void count_masked_kernel(cons
                 const uint4 fq = reinterpret_cast<const uint4 *>(flag)[lane];
                 const u32 f[4] = {fq.x, fq.y, fq.z, fq.w};
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // P goes over the flags
-                u32 before = 0xFFFFFFFFu, run = 0;
-                // the bitmap's last group loses its pad bits
-                const u32 pad_group = last_seg ? mrg.nvalid - 1u : 0xFFFFFFFFu;
-#pragma unroll
-                for (int s = 0; s < (int)kSteps; ++s) {
-                    u32 grp = seg_group(s, f, before, words, mrg.cnt, mrg.nvalid, lane);
-                    const u32 g = (u32)(64 * s) + lane;
-                    if (g == pad_group) grp &= pad_mask;
-                    const u32 cnt = (u32)__builtin_popcount(grp);
-                    const u32 incl = wave_scan_incl32(cnt);
-                    M[g] = grp;
-                    P[g] = (unsigned short)(run + incl - cnt); // at most 31 744
-                    run += (u32)__builtin_amdgcn_readlane((int)incl, 63);
-                }
-                p_total = run;
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                u32 before = 0xFFFFFFFFu;
+                p_total = image_prefix(M, P, true, nx.last_seg, mrg.nvalid, pad_mask, lane,
+                                       [&](int s, u32) { return seg_group(s, f, before, words, mrg.cnt, mrg.nvalid, lane); });
             }
         }
-        // the operand's words, where they lie
-        const u32 last = last_seg ? org.cnt - 1u : 0xFFFFFFFFu;
-        u32 bits = 0, grps = 0;
-        bool empty_word = false;
-        if (kind == kMaskImage) { // wave-uniform
-            u32 pos = 0; // groups covered by the batches so far
-#pragma unroll
-            for (int b = 0; b < kSegBatches; ++b) {
-                if (128u * b < org.cnt) { // wave-uniform
-                    const u32 i0 = 128u * b + 2u * lane;
-                    const bool in0 = i0 < org.cnt, in1 = i0 + 1u < org.cnt;
-                    const u32 n0 = in0 ? min(word_groups(x0[b]), 2u * kSegGroups) : 0u, n1 = in1 ? min(word_groups(x1[b]), 2u * kSegGroups) : 0u;
-                    empty_word |= (in0 && n0 == 0u) || (in1 && n1 == 0u);
-                    // a full batch of literals (dense data): consecutive positions, no scan
-                    const u32 incl = (128u * b + 128u <= org.cnt && __ballot((int)(x0[b] | x1[b]) < 0) == 0) ? 2u * lane + 2u : wave_scan_incl32(n0 + n1);
-                    const u32 lo1 = pos + incl - n1, lo0 = lo1 - n0;
-                    bits += image_bits(x0[b], n0, lo0, M, P, p_total) + image_bits(x1[b], n1, lo1, M, P, p_total);
-                    pos += (u32)__builtin_amdgcn_readlane((int)incl, 63);
-                }
-            }
-            grps = pos;
-        } else {
-            const bool ones_mask = kind == kMaskOnes;
-#pragma unroll
-            for (int b = 0; b < kSegBatches; ++b) {
-                if (128u * b < org.cnt) { // wave-uniform
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        const u32 x = h ? x1[b] : x0[b];
-                        const u32 k = 128u * b + 2u * lane + h;
-                        const bool in = k < org.cnt;
-                        const u32 n = in ? min(word_groups(x), 2u * kSegGroups) : 0u;
-                        empty_word |= in && n == 0u;
-                        const bool lit = (int)x >= 0, ones = (x & kFillOne) == kFillOne;
-                        const u32 pad = k == last ? a.pad_bits : 0u;
-                        const u32 fill_bits = ones && n ? 31u * n - pad : 0u;
-                        bits += !in || !ones_mask ? 0u : lit ? (u32)__builtin_popcount(x & (k == last ? pad_mask : kOnes31)) : fill_bits;
-                        grps += n;
-                    }
-                }
-            }
-            grps = wave_total32(grps);
+        count_under_mask(kind, org, x0, x1, M, P, p_total, nx.last_seg, a.pad_bits, pad_mask, at.jj, lane, acc, refused);
+        if (nx.last_jj && nx.last_seg && at.more()) { // the run goes on with another chunk or mask
+            if (acc) atomicAdd(reinterpret_cast<unsigned long long *>(a.counts + at.row * a.n_operands + nx.j0 + lane), (unsigned long long)acc);
+            acc = 0;
         }
-        const u32 total_bits = wave_total32(bits);
-        const bool ok = kind != kMaskBad && !org.bad && grps == org.nvalid && __ballot(empty_word) == 0ull;
-        refused |= !ok;
-        if (lane == jj && ok) acc += (u64)total_bits;
-        if (!last_jj) {
-            ++jj;
-        } else {
-            if (last_seg && item + 1 < end) { // the run goes on with another chunk or mask
-                if (acc) atomicAdd(reinterpret_cast<unsigned long long *>(a.counts + i * a.n_operands + j0 + lane), (unsigned long long)acc);
-                acc = 0;
-            }
-            if (item + 1 < end) {
-                q = q_next;
-                seg = seg_next;
-                i = i_next;
-                c = c_next;
-            }
-            ++item;
-            jj = 0;
-        }
+        at.advance(nx);
     }
     if (refused && lane == 0) atomicOr(a.ctrl + kCtlError, kErrStream);
-    // what the workgroup's wavefronts hold for the chunks their runs end in: consecutive runs, so equal chunks are neighbours
-    __syncthreads(); // (every image is done with: the merge borrows them)
-    u64 *s_q = reinterpret_cast<u64 *>(s_lds[0] + kMaskedWords);
-    reinterpret_cast<u64 *>(M)[lane] = acc;
-    if (lane == 0) s_q[wave] = begin < end ? q : ~0ull;
-    __syncthreads();
-    if (wave == 0) {
-        u64 at = ~0ull, sum = 0;
-        for (int v = 0; v <= kSegDecodeWaves; ++v) {
-            const u64 qv = v < kSegDecodeWaves ? s_q[v] : ~0ull;
-            if (qv != at) { // wave-uniform
-                if (at != ~0ull && sum) {
-                    const u64 mi = at / n_chunks, mc = at - mi * n_chunks;
-                    atomicAdd(reinterpret_cast<unsigned long long *>(a.counts + mi * a.n_operands + mc * a.chunk + lane), (unsigned long long)sum);
-                }
-                at = qv;
-                sum = 0;
-            }
-            if (v < kSegDecodeWaves) sum += reinterpret_cast<const u64 *>(s_lds[v] + kMaskedM)[lane];
-        }
-    }
+    merge_run_ends<false>(s_lds, has_run ? at.q : ~0ull, acc, 0ull, at.n_chunks, a.counts, nullptr, a.n_operands, a.chunk, wave, lane);
 }
 
 // ---- grouped counts under a conjunction, and their sums ----------------------------------------------------------------------
@@ -418,36 +482,15 @@ __device__ __forceinline__ SelectRow conjunct_row(const GroupCountArgs &a, u64 g
     return t < a.n_filters ? table_row(a.filters, t) : table_row(a.keys, g * a.rows_per_group + (t - a.n_filters));
 }
 
-// a segment's words judged where they lie, as seg_mark judges them: they add up to nvalid groups, none of them empty
-__device__ __forceinline__ bool words_make_segment(const SegRange &rg, const u32 (&x0)[kSegBatches], const u32 (&x1)[kSegBatches], u32 lane) {
-    u32 grps = 0;
-    bool empty_word = false;
-#pragma unroll
-    for (int b = 0; b < kSegBatches; ++b) {
-        if (128u * b < rg.cnt) { // wave-uniform
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const bool in = 128u * b + 2u * lane + h < rg.cnt;
-                const u32 n = in ? min(word_groups(h ? x1[b] : x0[b]), 2u * kSegGroups) : 0u;
-                empty_word |= in && n == 0u;
-                grps += n;
-            }
-        }
-    }
-    return !rg.bad && wave_total32(grps) == rg.nvalid && __ballot(empty_word) == 0ull;
-}
-
 // counts[g * n_operands + j] += the set bits of (filter 0 AND .. AND filter F-1 AND group g's R rows) AND operand j, and rows[g] +=
-// the set bits of that conjunction itself.  count_masked_kernel with an image that is the AND of several rows: the same items
-// -- (group g, chunk c of a.chunk <= 64 consecutive operands, segment), ordered (g, c, segment), in the same contiguous runs --, the
-// same LDS, the same atomics when (g, c) changes and the same merge of the workgroup's run ends.  The image is made once per item,
-// conjunct by conjunct: seg_load_words, seg_mark and the sixteen steps of seg_group each, the first one STORING M[g], every later one
-// ANDing into it; P -- which lies over the mark phase's flags and so cannot be written while a conjunct is still to be marked -- and
-// the pad bits of the bitmap's last group in one pass over M behind the last conjunct.  A conjunct whose segment is one one-fill
-// changes nothing and is not decoded; one zero-fill makes the item's mask zeros, and the conjuncts behind it are judged where their
-// words lie (words_make_segment) instead of being marked; if all are one-fills the operands are counted as under kMaskOnes.  EVERY
-// segment of every filter row, group row and operand is loaded and checked under every short cut.  Only the items of chunk 0 add
-// the conjunction's own bits (p_total; 31 per group under ones, less the pad bits; nothing under zeros): once per (g, segment).
+// the set bits of that conjunction itself; the cursor's row is the group g.  The image is made once per item, conjunct by conjunct:
+// seg_load_words, seg_mark and the sixteen steps of seg_group each, the first one STORING M[g], every later one ANDing into it; P
+// -- which lies over the mark phase's flags and so cannot be written while a conjunct is still to be marked -- and the pad bits in
+// one pass over M behind the last conjunct.  A conjunct whose segment is one one-fill changes nothing and is not decoded; one
+// zero-fill makes the item's mask zeros, and the conjuncts behind it are judged where their words lie instead of being marked; if
+// all are one-fills the operands are counted as under kMaskOnes.  EVERY segment of every filter row, group row and operand is
+// loaded and checked under every short cut.  Only the items of chunk 0 add the conjunction's own bits (p_total; 31 per group under
+// ones, less the pad bits; nothing under zeros): once per (g, segment).
 __global__ __launch_bounds__(kSegDecodeWaves * 64) void group_count_kernel(const GroupCountArgs a) {
     __shared__ __attribute__((aligned(16))) unsigned char s_lds[kSegDecodeWaves][kMaskedWaveLds];
     const u32 wave = wave_id(), lane = lane_id();
@@ -456,18 +499,9 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64) void group_count_kernel(const
     u32 *words = reinterpret_cast<u32 *>(s_lds[wave] + kMaskedWords);
     u32 *M = reinterpret_cast<u32 *>(s_lds[wave] + kMaskedM);
     const u32 n_conjuncts = a.n_filters + a.rows_per_group;
-    const u64 n_chunks = ((u64)a.n_operands + a.chunk - 1) / a.chunk;
-    const u64 n_items = (u64)a.n_groups * n_chunks * a.n_segments;
-    const u64 n_waves = (u64)gridDim.x * kSegDecodeWaves;
-    const u64 per = (n_items + n_waves - 1) / n_waves;
-    const u64 w = (u64)blockIdx.x * kSegDecodeWaves + wave;
-    const u64 begin = w * per < n_items ? w * per : n_items, end = begin + per < n_items ? begin + per : n_items;
+    ChunkCursor at = chunk_cursor(a.n_groups, a.n_operands, a.chunk, a.n_segments, wave);
+    const bool has_run = at.item < at.end;
     const u32 pad_mask = kOnes31 >> a.pad_bits;
-    u64 item = begin;
-    u64 q = begin / a.n_segments; // the items' run: g * n_chunks + c
-    u64 seg = begin - q * a.n_segments;
-    u64 g = q / n_chunks, c = q - g * n_chunks;
-    u32 jj = 0;    // the operand inside the chunk
     u64 acc = 0;   // lane l: operand c * chunk + l under group g's conjunction
     u64 racc = 0;  // the conjunction's own bits (chunk 0 only), wave-uniform
     bool refused = false;
@@ -475,40 +509,33 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64) void group_count_kernel(const
     u64 img_g = 0, img_seg = 0;
     SelectRow orow = {}, next_orow = {};
     SegRange next_o = {};
-    if (begin < end) {
-        next_orow = table_row(a.operands, c * a.chunk);
-        next_o = select_range(next_orow, a.groups, seg);
+    if (has_run) {
+        next_orow = table_row(a.operands, at.c * a.chunk);
+        next_o = select_range(next_orow, a.groups, at.seg);
     }
 #pragma nounroll
-    while (item < end) {
+    while (at.item < at.end) {
         const SegRange org = next_o;
         orow = next_orow;
-        const bool fresh = jj == 0u && (kind == kMaskNone || g != img_g || seg != img_seg); // wave-uniform
+        const bool fresh = at.jj == 0u && (kind == kMaskNone || at.row != img_g || at.seg != img_seg); // wave-uniform
         SegmentsArgs osa = {};
         osa.comp = reinterpret_cast<const u32 *>((uintptr_t)orow.comp);
         u32 x0[kSegBatches], x1[kSegBatches];
         if (!fresh) seg_load_words(osa, org, x0, x1, lane); // (under a new image: behind its last conjunct, the registers are the conjuncts' till then)
-        // what comes behind this operand's segment: the chunk's next operand, or the next item
-        const u64 j0 = c * a.chunk;
-        const u32 jn = a.n_operands - j0 < a.chunk ? (u32)(a.n_operands - j0) : a.chunk;
-        const bool last_jj = jj + 1u == jn;
-        const bool last_seg = seg + 1 == a.n_segments;
-        const bool last_c = c + 1 == n_chunks;
-        const u64 seg_next = last_seg ? 0ull : seg + 1, q_next = last_seg ? q + 1 : q;
-        const u64 c_next = !last_seg ? c : last_c ? 0ull : c + 1, g_next = last_seg && last_c ? g + 1 : g;
-        if (!last_jj) {
-            next_orow = table_row(a.operands, j0 + jj + 1u);
-            next_o = select_range(next_orow, a.groups, seg);
-        } else if (item + 1 < end) {
-            next_orow = table_row(a.operands, c_next * a.chunk);
-            next_o = select_range(next_orow, a.groups, seg_next);
+        const ChunkBehind nx = at.behind();
+        if (!nx.last_jj) {
+            next_orow = table_row(a.operands, nx.j0 + at.jj + 1u);
+            next_o = select_range(next_orow, a.groups, at.seg);
+        } else if (at.more()) {
+            next_orow = table_row(a.operands, nx.c * a.chunk);
+            next_o = select_range(next_orow, a.groups, nx.seg);
         }
         if (fresh) {
-            img_g = g;
-            img_seg = seg;
+            img_g = at.row;
+            img_seg = at.seg;
             bool zeros = false, bad = false, image = false; // wave-uniform, all three
-            SelectRow crow = conjunct_row(a, g, 0);
-            SegRange next_c = select_range(crow, a.groups, seg);
+            SelectRow crow = conjunct_row(a, at.row, 0);
+            SegRange next_c = select_range(crow, a.groups, at.seg);
 #pragma nounroll
             for (u32 t = 0; t < n_conjuncts; ++t) {
                 const SegRange crg = next_c;
@@ -517,14 +544,15 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64) void group_count_kernel(const
                 u32 m0[kSegBatches], m1[kSegBatches];
                 seg_load_words(csa, crg, m0, m1, lane);
                 if (t + 1u < n_conjuncts) { // the conjunct behind this one is on its way while this one is marked
-                    crow = conjunct_row(a, g, t + 1u);
-                    next_c = select_range(crow, a.groups, seg);
+                    crow = conjunct_row(a, at.row, t + 1u);
+                    next_c = select_range(crow, a.groups, at.seg);
                 }
                 const u32 first = (u32)__builtin_amdgcn_readfirstlane((int)m0[0]); // lane 0 holds the segment's first word
                 if (!crg.bad && crg.cnt == 1u && (first & kFillZero) && (first & kCountMask) == crg.nvalid) {
                     zeros |= (first & kFillOne) != kFillOne; // one fill over the segment: ones change nothing, zeros leave nothing
                 } else if (zeros || bad) {
-                    bad |= !words_make_segment(crg, m0, m1, lane); // no image will be read: checked, not decoded
+                    const SegCount n = count_where_they_lie(crg, m0, m1, false, false, 0u, 0u, lane); // no image will be read: judged, not decoded
+                    bad |= !segment_ok(crg, wave_total32(n.grps), n.empty_word);
                 } else if (!seg_mark(crg, m0, m1, flag, words, lane)) {
                     bad = true;
                 } else {
@@ -544,123 +572,23 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64) void group_count_kernel(const
             }
             kind = bad ? kMaskBad : zeros ? kMaskZeros : image ? kMaskImage : kMaskOnes;
             seg_load_words(osa, org, x0, x1, lane);
-            if (kind == kMaskImage) {
-                // P goes over the flags: no conjunct is left to be marked.  The bitmap's last group loses its pad bits
-                const u32 pad_group = last_seg ? org.nvalid - 1u : 0xFFFFFFFFu;
-                u32 run = 0;
-#pragma unroll
-                for (int s = 0; s < (int)kSteps; ++s) {
-                    const u32 k = (u32)(64 * s) + lane;
-                    u32 grp = M[k];
-                    if (k == pad_group) M[k] = grp &= pad_mask;
-                    const u32 cnt = (u32)__builtin_popcount(grp);
-                    const u32 incl = wave_scan_incl32(cnt);
-                    P[k] = (unsigned short)(run + incl - cnt); // at most 31 744
-                    run += (u32)__builtin_amdgcn_readlane((int)incl, 63);
-                }
-                p_total = run;
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            }
+            if (kind == kMaskImage) // no conjunct is left to be marked
+                p_total = image_prefix(M, P, false, nx.last_seg, org.nvalid, pad_mask, lane, [&](int, u32 k) { return M[k]; });
         }
-        // the operand's words, where they lie
-        const u32 last = last_seg ? org.cnt - 1u : 0xFFFFFFFFu;
-        u32 bits = 0, grps = 0;
-        bool empty_word = false;
-        if (kind == kMaskImage) { // wave-uniform
-            u32 pos = 0; // groups covered by the batches so far
-#pragma unroll
-            for (int b = 0; b < kSegBatches; ++b) {
-                if (128u * b < org.cnt) { // wave-uniform
-                    const u32 i0 = 128u * b + 2u * lane;
-                    const bool in0 = i0 < org.cnt, in1 = i0 + 1u < org.cnt;
-                    const u32 n0 = in0 ? min(word_groups(x0[b]), 2u * kSegGroups) : 0u, n1 = in1 ? min(word_groups(x1[b]), 2u * kSegGroups) : 0u;
-                    empty_word |= (in0 && n0 == 0u) || (in1 && n1 == 0u);
-                    // a full batch of literals (dense data): consecutive positions, no scan
-                    const u32 incl = (128u * b + 128u <= org.cnt && __ballot((int)(x0[b] | x1[b]) < 0) == 0) ? 2u * lane + 2u : wave_scan_incl32(n0 + n1);
-                    const u32 lo1 = pos + incl - n1, lo0 = lo1 - n0;
-                    bits += image_bits(x0[b], n0, lo0, M, P, p_total) + image_bits(x1[b], n1, lo1, M, P, p_total);
-                    pos += (u32)__builtin_amdgcn_readlane((int)incl, 63);
-                }
-            }
-            grps = pos;
-        } else {
-            const bool ones_mask = kind == kMaskOnes;
-#pragma unroll
-            for (int b = 0; b < kSegBatches; ++b) {
-                if (128u * b < org.cnt) { // wave-uniform
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        const u32 x = h ? x1[b] : x0[b];
-                        const u32 k = 128u * b + 2u * lane + h;
-                        const bool in = k < org.cnt;
-                        const u32 n = in ? min(word_groups(x), 2u * kSegGroups) : 0u;
-                        empty_word |= in && n == 0u;
-                        const bool lit = (int)x >= 0, ones = (x & kFillOne) == kFillOne;
-                        const u32 pad = k == last ? a.pad_bits : 0u;
-                        const u32 fill_bits = ones && n ? 31u * n - pad : 0u;
-                        bits += !in || !ones_mask ? 0u : lit ? (u32)__builtin_popcount(x & (k == last ? pad_mask : kOnes31)) : fill_bits;
-                        grps += n;
-                    }
-                }
-            }
-            grps = wave_total32(grps);
-        }
-        const u32 total_bits = wave_total32(bits);
-        const bool ok = kind != kMaskBad && !org.bad && grps == org.nvalid && __ballot(empty_word) == 0ull;
-        refused |= !ok;
-        if (lane == jj && ok) acc += (u64)total_bits;
+        count_under_mask(kind, org, x0, x1, M, P, p_total, nx.last_seg, a.pad_bits, pad_mask, at.jj, lane, acc, refused);
         // COUNT(*) of the group: the conjunction's own bits in this segment, once per (g, segment)
-        if (jj == 0u && c == 0)
-            racc += kind == kMaskImage ? (u64)p_total : kind == kMaskOnes ? (u64)(31u * org.nvalid - (last_seg ? a.pad_bits : 0u)) : 0ull;
-        if (!last_jj) {
-            ++jj;
-        } else {
-            if (last_seg && item + 1 < end) { // the run goes on with another chunk or group
-                if (acc) atomicAdd(reinterpret_cast<unsigned long long *>(a.counts + g * a.n_operands + j0 + lane), (unsigned long long)acc);
-                if (lane == 0 && racc) atomicAdd(reinterpret_cast<unsigned long long *>(a.rows + g), (unsigned long long)racc);
-                acc = 0;
-                racc = 0;
-            }
-            if (item + 1 < end) {
-                q = q_next;
-                seg = seg_next;
-                g = g_next;
-                c = c_next;
-            }
-            ++item;
-            jj = 0;
+        if (at.jj == 0u && at.c == 0)
+            racc += kind == kMaskImage ? (u64)p_total : kind == kMaskOnes ? (u64)(31u * org.nvalid - (nx.last_seg ? a.pad_bits : 0u)) : 0ull;
+        if (nx.last_jj && nx.last_seg && at.more()) { // the run goes on with another chunk or group
+            if (acc) atomicAdd(reinterpret_cast<unsigned long long *>(a.counts + at.row * a.n_operands + nx.j0 + lane), (unsigned long long)acc);
+            if (lane == 0 && racc) atomicAdd(reinterpret_cast<unsigned long long *>(a.rows + at.row), (unsigned long long)racc);
+            acc = 0;
+            racc = 0;
         }
+        at.advance(nx);
     }
     if (refused && lane == 0) atomicOr(a.ctrl + kCtlError, kErrStream);
-    // what the workgroup's wavefronts hold for the chunks their runs end in: consecutive runs, so equal chunks are neighbours
-    __syncthreads(); // (every image is done with: the merge borrows them)
-    u64 *s_q = reinterpret_cast<u64 *>(s_lds[0] + kMaskedWords), *s_r = s_q + kSegDecodeWaves;
-    reinterpret_cast<u64 *>(M)[lane] = acc;
-    if (lane == 0) {
-        s_q[wave] = begin < end ? q : ~0ull;
-        s_r[wave] = racc;
-    }
-    __syncthreads();
-    if (wave == 0) {
-        u64 at = ~0ull, sum = 0, rsum = 0;
-        for (int v = 0; v <= kSegDecodeWaves; ++v) {
-            const u64 qv = v < kSegDecodeWaves ? s_q[v] : ~0ull;
-            if (qv != at) { // wave-uniform
-                if (at != ~0ull) {
-                    const u64 mg = at / n_chunks, mc = at - mg * n_chunks;
-                    if (sum) atomicAdd(reinterpret_cast<unsigned long long *>(a.counts + mg * a.n_operands + mc * a.chunk + lane), (unsigned long long)sum);
-                    if (lane == 0 && rsum) atomicAdd(reinterpret_cast<unsigned long long *>(a.rows + mg), (unsigned long long)rsum);
-                }
-                at = qv;
-                sum = 0;
-                rsum = 0;
-            }
-            if (v < kSegDecodeWaves) {
-                sum += reinterpret_cast<const u64 *>(s_lds[v] + kMaskedM)[lane];
-                rsum += s_r[v];
-            }
-        }
-    }
+    merge_run_ends<true>(s_lds, has_run ? at.q : ~0ull, acc, racc, at.n_chunks, a.counts, a.rows, a.n_operands, a.chunk, wave, lane);
 }
 
 // sums[g][t] = the counts of attribute t's slices under group g, slice i of bits[t] weighing 2^(bits[t] - 1 - i): one thread per
@@ -814,31 +742,37 @@ hipError_t launch_select_count(const SelectCountArgs &a, hipStream_t s) {
     return hipGetLastError();
 }
 
-// ... of the masked count: its 40 960 B of LDS let four workgroups onto a CU.  The chunk: as many operands per mask image as leave
-// every wavefront of a full grid eight items or more, 64 at the most
+// ... of the two chunked kernels (rows: masks, or groups): their 40 960 B of LDS let four workgroups onto a CU.  The chunk: as many
+// operands per image as leave every wavefront of a full grid eight items or more, 64 at the most
+struct ChunkedGrid {
+    u32 chunk;
+    unsigned workgroups;
+};
+static ChunkedGrid chunked_count_grid(u64 rows, u64 operands, u64 segments) {
+    constexpr u64 most = 256u * 4u;
+    u64 chunk = 64;
+    auto items = [&](u64 by) { return rows * ((operands + by - 1) / by) * segments; };
+    while (chunk > 1 && items(chunk) < 8 * most * kSegDecodeWaves) chunk /= 2;
+    const u64 want = (items(chunk) + kSegDecodeWaves - 1) / kSegDecodeWaves;
+    return {(u32)chunk, (unsigned)(want > most ? most : want)};
+}
+
 hipError_t launch_count_masked(const CountMaskedArgs &a, hipStream_t s) {
     if (a.n_segments == 0) return hipSuccess;
-    constexpr u64 most = 256u * 4u;
+    const ChunkedGrid g = chunked_count_grid(a.n_masks, a.n_operands, a.n_segments);
     CountMaskedArgs b = a;
-    b.chunk = 64;
-    auto items = [&](u64 chunk) { return (u64)a.n_masks * ((a.n_operands + chunk - 1) / chunk) * a.n_segments; };
-    while (b.chunk > 1 && items(b.chunk) < 8 * most * kSegDecodeWaves) b.chunk /= 2;
-    const u64 want = (items(b.chunk) + kSegDecodeWaves - 1) / kSegDecodeWaves;
-    hipLaunchKernelGGL(count_masked_kernel, dim3((unsigned)(want > most ? most : want)), dim3(kSegDecodeWaves * 64), 0, s, b);
+    b.chunk = g.chunk;
+    hipLaunchKernelGGL(count_masked_kernel, dim3(g.workgroups), dim3(kSegDecodeWaves * 64), 0, s, b);
     return hipGetLastError();
 }
 
-// ... of the grouped count: the same grid and the same chunk rule with the groups in the masks' place, then the fold on the same
-// stream (it runs for an empty bitmap too: every sum is stored)
+// ... of the grouped count, then the fold on the same stream (it runs for an empty bitmap too: every sum is stored)
 hipError_t launch_group_sum(const GroupCountArgs &a, const GroupFoldArgs &f, hipStream_t s) {
     if (a.n_segments != 0) {
-        constexpr u64 most = 256u * 4u;
+        const ChunkedGrid g = chunked_count_grid(a.n_groups, a.n_operands, a.n_segments);
         GroupCountArgs b = a;
-        b.chunk = 64;
-        auto items = [&](u64 chunk) { return (u64)a.n_groups * ((a.n_operands + chunk - 1) / chunk) * a.n_segments; };
-        while (b.chunk > 1 && items(b.chunk) < 8 * most * kSegDecodeWaves) b.chunk /= 2;
-        const u64 want = (items(b.chunk) + kSegDecodeWaves - 1) / kSegDecodeWaves;
-        hipLaunchKernelGGL(group_count_kernel, dim3((unsigned)(want > most ? most : want)), dim3(kSegDecodeWaves * 64), 0, s, b);
+        b.chunk = g.chunk;
+        hipLaunchKernelGGL(group_count_kernel, dim3(g.workgroups), dim3(kSegDecodeWaves * 64), 0, s, b);
     }
     const u64 n_sums = (u64)f.n_groups * f.n_attrs;
     hipLaunchKernelGGL(group_fold_kernel, dim3((unsigned)((n_sums + kFoldThreads - 1) / kFoldThreads)), dim3(kFoldThreads), 0, s, f);

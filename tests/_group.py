@@ -18,7 +18,7 @@ from tests import _select as sel
 MAX_FILTERS, MAX_ROWS, MAX_ATTRS = 64, 8, 64  # WAH_GROUP_MAX_*
 
 
-# ---- the items and the chunk (gpu-wah_amd/csrc/wah_select.hip: group_count_kernel, launch_group_sum) ---------------------------
+# ---- the items and the chunk (gpu-wah_amd/csrc/wah_select.hip: ChunkCursor, chunked_count_grid) --------------------------------
 def chunk_of(n_groups, n_operands, n_segments):
     """Operands that share one conjunction image: the masked count's rule with the groups in the masks' place."""
     return msk.chunk_of(n_groups, n_operands, n_segments)

@@ -16,7 +16,7 @@ ITEMS_PER_WAVE = 8                # the launcher lets operands share a mask imag
 
 
 def chunk_of(n_masks, n_operands, n_segments):
-    """Operands that share one mask image (launch_count_masked): 64, halved while a full grid would get fewer than eight
+    """Operands that share one mask image (chunked_count_grid): 64, halved while a full grid would get fewer than eight
     (mask, chunk, segment) items per wavefront."""
     chunk = 64
     while chunk > 1 and n_masks * ((n_operands + chunk - 1) // chunk) * n_segments < ITEMS_PER_WAVE * GRID_WAVES:
