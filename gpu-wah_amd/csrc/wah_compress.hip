@@ -373,13 +373,25 @@ __device__ __forceinline__ u64 tile_scan_resolve(const CompressArgs &a, const Sc
 //      what they PUBLISH differs and stays with them: a 4-byte granule, an 8-byte granule with (T, L), or the no-wait table
 enum : int { kTileScan = 0, kTileCount = 1, kTilePlace = 2 }; // kMode of a body: the one launch / the halves of the no-wait route
 
-// A workgroup of the one-launch route begins: its tile (arrival ticket) and the launch epoch (wah_device.hpp: the same value
-// for every workgroup of the launch).  le.bad: the workspace is not one of ours (includes a tile number outside the grid:
-// nothing has been indexed with it) -- no words come out, and the kernel returns.
-__device__ __forceinline__ LaunchEpoch tile_begin(const CompressArgs &a, u32 *s_tile, u32 &tile) {
-    tile = draw_tile(a.ctrl, s_tile);
-    const LaunchEpoch le = launch_epoch_begin(a.ctrl, tile, a.n_tiles, a.gen_desc, a.scan_words, a.keep_error);
-    if (le.bad && blockIdx.x == 0 && threadIdx.x == 0) *a.out_words = 0;
+// A workgroup of the one-launch route begins, in two halves with the tile's first loads between them (wah_device.hpp: ask,
+// ticket, decide).  tile_ticket: what the control block says is asked for, and the tile (arrival ticket) drawn, in ONE round
+// trip.  The body then issues its first loads, under tile_live() alone -- a tile number inside the grid indexes nothing but the
+// caller's input -- and only then calls tile_begin: the launch epoch (the same value for every workgroup of the launch).
+// le.bad: the workspace is not one of ours (includes a tile number outside the grid: nothing has been indexed with it) -- no
+// words come out, and the kernel returns, once the loads that are in flight have come back.
+__device__ __forceinline__ EpochAsk tile_ticket(const CompressArgs &a, u32 *s_tile, u32 &tile) {
+    EpochAsk ask = launch_epoch_ask(a.ctrl);
+    tile = draw_tile(a.ctrl, s_tile, ask);
+    return ask;
+}
+template <int kMode>
+__device__ __forceinline__ bool tile_live(const CompressArgs &a, u32 tile) { return kMode != kTileScan || tile < a.n_tiles; } // (no ticket: tile = blockIdx)
+__device__ __forceinline__ LaunchEpoch tile_begin(const CompressArgs &a, const EpochAsk &ask, u32 tile) {
+    const LaunchEpoch le = launch_epoch_begin(a.ctrl, ask, tile, a.n_tiles, a.gen_desc, a.scan_words, a.keep_error);
+    if (le.bad) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) *a.out_words = 0;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the tile's first loads (bounded descriptors over the input) are not left behind
+    }
     return le;
 }
 // the no-wait route's count launch is a new launch: forget the previous one's status (no error is raised before its offsets kernel)
@@ -520,8 +532,7 @@ __device__ __forceinline__ void compress_tile_body(const CompressArgs &a, Source
     const u32 lane = lane_id();
     const u32 wave = wave_id();
     u32 tile = blockIdx.x;
-    const LaunchEpoch le = kMode == kTileScan ? tile_begin(a, &s_tile, tile) : LaunchEpoch{};
-    if (le.bad) return;
+    const EpochAsk ask = kMode == kTileScan ? tile_ticket(a, &s_tile, tile) : EpochAsk{};
     if (kMode == kTileCount) count_launch_reset(a, tile);
     const u32 seg0 = (tile * kTileWaves + wave) * kWaveSegs; // this wave's segments: seg0 .. seg0 + kWaveSegs - 1
 
@@ -537,7 +548,9 @@ __device__ __forceinline__ void compress_tile_body(const CompressArgs &a, Source
     u32 nval[kWaveSegs];
     u32 never;
     asm volatile("v_mov_b32 %0, -1" : "=v"(never)); // "group after the last one": a value no 31-bit group can equal
-    src.begin(a, seg0, kWaveSegs, lane);
+    if (tile_live<kMode>(a, tile)) src.begin(a, seg0, kWaveSegs, lane); // the first segment's loads: in flight while the epoch is decided
+    const LaunchEpoch le = kMode == kTileScan ? tile_begin(a, ask, tile) : LaunchEpoch{};
+    if (le.bad) return;
     // ---- pass 1 of all the wave's segments: nothing but their word counts, which is all the other workgroups wait for.
     //      What follows the publication (pass 2, final words) has the round trip of the sweep to hide in ----------------
 #pragma unroll

@@ -223,7 +223,8 @@ __device__ __forceinline__ void emit_pair(const CompressArgs &a, u64 base, u32 c
 }
 
 // ---- the wave's work on its pairs, shared by the two bodies (compress_pair_body below, compress_unseg_pair_body) ------------
-//   pair_wave_begin   what a wave knows before its first pair, and that pair's loads
+//   pair_wave_begin   what a wave knows before its first pair, and that pair's loads -- issued right behind the ticket; the body
+//                     decides the launch epoch (tile_begin) with them in flight
 //   pair_count        PASS 1 of one pair: its words staged and regrouped, the next pair's loads issued, run ends flagged and ranked
 //   pair_pass2_park   PASS 2 of one pair: final words compacted in LDS, then parked in registers (the wave's last pair: left in LDS)
 //   emit_wave_pair    one pair's words, parked or still in LDS, to their place in the output
@@ -270,7 +271,7 @@ __device__ __forceinline__ PairWave pair_wave_begin(const CompressArgs &a, const
     w.stage = sm.stage[w.wave];
     w.pair0 = first_pair + w.wave * kWavePairs;
     asm volatile("v_mov_b32 %0, -1" : "=v"(w.never));
-    prefetch_pair<kAligned>(a, w.pair0, w.lane, pre);
+    if (tile_live<kMode>(a, tile)) prefetch_pair<kAligned>(a, w.pair0, w.lane, pre); // (a ticket outside the grid indexes nothing)
     return w;
 }
 
@@ -342,10 +343,10 @@ __device__ __forceinline__ void emit_wave_pair(const CompressArgs &a, const Pair
 
 // ---- the segmented body adds: the words of a pair's FIRST segment (cnt_a) for the index, the 4-byte granule, (WAH_DIAG) the time line
 template <bool kAligned, u32 kWavePairs, int kMode = kTileScan>
-__device__ __forceinline__ void compress_pair_body(const CompressArgs &a, const PairLds &sm, u32 tile, u32 first_pair, const LaunchEpoch &le) {
+__device__ __forceinline__ void compress_pair_body(const CompressArgs &a, const PairLds &sm, u32 tile, u32 first_pair, const EpochAsk &ask, u64 dg_start = 0) {
 #ifdef WAH_DIAG
     u64 dg_t[8] = {};
-    dg_t[0] = __builtin_amdgcn_s_memrealtime();
+    dg_t[0] = dg_start ? dg_start : __builtin_amdgcn_s_memrealtime(); // (the kernel's entry: the time line includes ask and ticket)
 #define DG(i) dg_t[i] = __builtin_amdgcn_s_memrealtime()
 #define DG_AT(i) (dg_t + (i))
 #else
@@ -354,6 +355,8 @@ __device__ __forceinline__ void compress_pair_body(const CompressArgs &a, const 
 #endif
     PairLoad pre;
     const PairWave w = pair_wave_begin<kAligned, kWavePairs, kMode>(a, sm, tile, first_pair, pre);
+    const LaunchEpoch le = kMode == kTileScan ? tile_begin(a, ask, tile) : LaunchEpoch{};
+    if (le.bad) return;
     const u32 lane = w.lane, wave = w.wave;
 
     LaneGroups grp[kWavePairs];
@@ -466,15 +469,19 @@ __global__ __launch_bounds__(kTileWaves * 64, 4) void compress_pair_kernel(const
     const PairLds lds = pair_lds<kTileScan>();
     __shared__ u32 s_tile;
     u32 tile;
-    const LaunchEpoch le = tile_begin(a, &s_tile, tile);
-    if (le.bad) return;
+#ifdef WAH_DIAG
+    const u64 dg_start = __builtin_amdgcn_s_memrealtime();
+#else
+    const u64 dg_start = 0;
+#endif
+    const EpochAsk ask = tile_ticket(a, &s_tile, tile);
     run_tile_shape<kBody, kTail>(a, tile, [&](auto n, u32 first_pair) __attribute__((always_inline)) {
-        compress_pair_body<kAligned, decltype(n)::value>(a, lds, tile, first_pair, le);
+        compress_pair_body<kAligned, decltype(n)::value>(a, lds, tile, first_pair, ask, dg_start);
     });
 }
 
 // ---- the no-wait route (kTileCount / kTilePlace): two pairs per wave, whatever the size of the bitmap; no ticket, no epoch ------
 template <bool kAligned, int kMode>
 __global__ __launch_bounds__(kTileWaves * 64, 4) void compress_nowait_kernel(const CompressArgs a) {
-    compress_pair_body<kAligned, kNoWaitWaveSegs / 2, kMode>(a, pair_lds<kMode>(), blockIdx.x, blockIdx.x * (kTileWaves * (kNoWaitWaveSegs / 2)), LaunchEpoch{});
+    compress_pair_body<kAligned, kNoWaitWaveSegs / 2, kMode>(a, pair_lds<kMode>(), blockIdx.x, blockIdx.x * (kTileWaves * (kNoWaitWaveSegs / 2)), EpochAsk{});
 }

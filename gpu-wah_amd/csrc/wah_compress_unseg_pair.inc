@@ -25,19 +25,22 @@ __device__ __forceinline__ UnsegLds unseg_lds() {
 
 template <bool kAligned, u32 kWavePairs, int kMode = kTileScan>
 __device__ __forceinline__ void compress_unseg_pair_body(const CompressArgs &a, const PairLds &sm, const UnsegLds &us, u32 tile, u32 first_pair,
-                                                         const LaunchEpoch &le) {
+                                                         const EpochAsk &ask) {
     constexpr u32 kCutPairs = kCutSegs / 2u;
     PairLoad pre;
     const PairWave w = pair_wave_begin<kAligned, kWavePairs, kMode>(a, sm, tile, first_pair, pre);
     const u32 lane = w.lane, wave = w.wave, n_pairs = w.n_pairs, pair0 = w.pair0;
+    const bool live = tile_live<kMode>(a, tile); // (the loads below go out with the first pair's, in front of tile_begin)
     // the group in front of the wave's first pair and the one behind its last: one word of the bitmap each.  Loads without a
     // branch around them (a descriptor of four bytes or of none), looked at only after pass 1: as `if (...) x = a.in[i]` each
     // of them was waited for on the spot -- two memory round trips in a row in front of every tile's first pass.
     const u32 pair_next = pair0 + kWavePairs;
-    const bool has_prev = pair0 > 0 && pair0 < n_pairs, has_next = pair_next < n_pairs;
+    const bool has_prev = live && pair0 > 0 && pair0 < n_pairs, has_next = live && pair_next < n_pairs;
     const u64 i_prev = has_prev ? (u64)pair0 * kPairWords - 1u : 0ull, i_next = has_next ? (u64)pair_next * kPairWords : 0ull;
     const u32 w_prev = __builtin_amdgcn_raw_buffer_load_b32(make_rsrc(a.in + i_prev, has_prev ? 4u : 0u), 0, 0, 0);
     const u32 w_next = __builtin_amdgcn_raw_buffer_load_b32(make_rsrc(a.in + i_next, has_next && i_next < a.n_words ? 4u : 0u), 0, 0, 0);
+    const LaunchEpoch le = kMode == kTileScan ? tile_begin(a, ask, tile) : LaunchEpoch{};
+    if (le.bad) return;
 
     LaneGroups grp[kWavePairs];
     u32 flags[kWavePairs], rank0[kWavePairs], cnt[kWavePairs];
@@ -147,15 +150,14 @@ __global__ __launch_bounds__(kTileWaves * 64, 4) void compress_unseg_pair_kernel
     const UnsegLds us = unseg_lds<kTileScan>();
     __shared__ u32 s_tile;
     u32 tile;
-    const LaunchEpoch le = tile_begin(a, &s_tile, tile);
-    if (le.bad) return;
+    const EpochAsk ask = tile_ticket(a, &s_tile, tile);
     run_tile_shape<kBody, kTail>(a, tile, [&](auto n, u32 first_pair) __attribute__((always_inline)) {
-        compress_unseg_pair_body<kAligned, decltype(n)::value>(a, lds, us, tile, first_pair, le);
+        compress_unseg_pair_body<kAligned, decltype(n)::value>(a, lds, us, tile, first_pair, ask);
     });
 }
 
 // ---- the no-wait route of the unsegmented mode: two pairs per wave, whatever the size of the bitmap ------------------------
 template <bool kAligned, int kMode>
 __global__ __launch_bounds__(kTileWaves * 64, 4) void compress_unseg_pair_nowait_kernel(const CompressArgs a) {
-    compress_unseg_pair_body<kAligned, kNoWaitWaveSegs / 2, kMode>(a, pair_lds<kMode>(), unseg_lds<kMode>(), blockIdx.x, blockIdx.x * (kTileWaves * (kNoWaitWaveSegs / 2)), LaunchEpoch{});
+    compress_unseg_pair_body<kAligned, kNoWaitWaveSegs / 2, kMode>(a, pair_lds<kMode>(), unseg_lds<kMode>(), blockIdx.x, blockIdx.x * (kTileWaves * (kNoWaitWaveSegs / 2)), EpochAsk{});
 }

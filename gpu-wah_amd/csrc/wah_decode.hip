@@ -112,9 +112,11 @@ __device__ __forceinline__ void defer_counters_next(u32 *c) {
     __hip_atomic_store(c + kDeferSeq, seq + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 // the counter pair {entries:32, parts:32} a launch that may append counts in (read by every workgroup at its start)
-__device__ __forceinline__ u64 *defer_counters_mine(u32 *c) {
-    return reinterpret_cast<u64 *>(c) + (uniform32(__hip_atomic_load(c + kDeferSeq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) & 1u);
-}
+// (decode_tile_kernel asks for the launch count in front of its ticket, with the launch epoch's words -- launch_epoch_ask,
+//  wah_device.hpp: the last batch flips it only after every workgroup has published, hence asked)
+__device__ __forceinline__ u32 defer_seq_ask(u32 *c) { return __hip_atomic_load(c + kDeferSeq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ u64 *defer_counters_mine(u32 *c, u32 seq) { return reinterpret_cast<u64 *>(c) + (uniform32(seq) & 1u); }
+__device__ __forceinline__ u64 *defer_counters_mine(u32 *c) { return defer_counters_mine(c, defer_seq_ask(c)); }
 
 // One expand tile onto the list of tiles that are decoded by workgroups of their own (the one-pass decoder's second launch,
 // the launch behind decode_expand_kernel).  An entry = {tile, parts} {sum of the parts of the entries before it}: the tile's
@@ -178,14 +180,15 @@ __global__ __launch_bounds__(kSumWaves * 64) void decode_sums_kernel(const ScanA
 
     const u32 lane = lane_id();
     const u32 wave = wave_id();
-    const u32 wt = kNoWait ? blockIdx.x : draw_tile(a.ctrl, &s_tile); // workgroup tile: arrival order (wah_device.hpp)
+    EpochAsk ask = kNoWait ? EpochAsk{} : launch_epoch_ask(a.ctrl); // (in flight with the ticket: wah_device.hpp)
+    const u32 wt = kNoWait ? blockIdx.x : draw_tile(a.ctrl, &s_tile, ask); // workgroup tile: arrival order (wah_device.hpp)
     const u32 n_tiles = (u32)a.n_tiles;            // expand tiles (4096 words)
     const u32 n_wg_tiles = gridDim.x;
     const u32 et0 = (wt * kSumWaves + wave) * kWaveTiles; // this wave's expand tiles: et0 .. et0 + kWaveTiles - 1
 
     LaunchEpoch le = {};
     if (!kNoWait) {
-        le = launch_epoch_begin(a.ctrl, wt, n_wg_tiles, a.gen_desc, a.scan_words, 0);
+        le = launch_epoch_begin(a.ctrl, ask, wt, n_wg_tiles, a.gen_desc, a.scan_words, 0);
         if (le.bad) {
             if (blockIdx.x == 0 && threadIdx.x == 0) a.info[0] = a.info[1] = 0;
             return;

@@ -161,24 +161,24 @@ __global__ __launch_bounds__(kDtWaves * 64, (kP <= 2 ? WAH_DT_MINW : 4)) void de
 #else
 #define DGT(i)
 #endif
-    const u32 wt = draw_tile(a.ctrl, &s_tile);
-    const LaunchEpoch le = launch_epoch_begin(a.ctrl, wt, a.n_wg_tiles, a.gen_desc, a.scan_words, 0);
-    if (le.bad) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) a.info[0] = a.info[1] = 0;
-        return;
-    }
-    const u32 epoch = le.epoch;
-    // which of the two counters of deferred tiles this launch uses (read by every workgroup at its start, advanced by the
-    // last batch at its end: the protocol of the launch epoch)
-    u64 *const defer_count = defer_counters_mine(a.defer_count);
+    // ask, ticket, decide (wah_device.hpp): what the control block says -- the launch epoch's words, and which of the two counters
+    // of deferred tiles this launch uses (read by every workgroup at its start, advanced by the last batch at its end: the
+    // protocol of the launch epoch) -- is asked for in front of the ticket and is in flight with it; the batch's loads go out right
+    // behind the ticket, which is all they depend on, and the epoch is decided with them in flight
+    EpochAsk ask = launch_epoch_ask(a.ctrl);
+    u32 defer_seq = defer_seq_ask(a.defer_count);
+    const u32 wt = draw_tile(a.ctrl, &s_tile, ask);
+    defer_seq = uniform32(defer_seq); // (taken with the epoch's words, in front of the loads: draw_tile)
+    asm volatile("" : "+s"(defer_seq)); // (here, not where it is first used: behind the branches of the loads below the wait would be for some of them too)
     constexpr u32 kBatchWords = kP * kDtTileWords;
     const u64 batch_w0 = (u64)wt * kBatchWords;
     const u64 left64 = a.c_words - batch_w0;                                  // words of the stream from the batch's start on
-    const u32 left = left64 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)left64;
+    // (a ticket outside the grid -- a workspace that is not ours, le.bad below -- has no words left: every descriptor of the loads
+    //  is one of no bytes then, and nothing is read with a number that was not checked)
+    const u32 left = wt < a.n_wg_tiles ? (left64 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)left64) : 0u;
     u32x4 *const words4 = reinterpret_cast<u32x4 *>(s_words);
 
-    // ---- the start flags are cleared; the wave's words of all the batch's tiles are loaded -------------------------------------
-    for (u32 i = threadIdx.x; i < kDtMaskWords / 4u; i += kDtWaves * 64u) reinterpret_cast<uint4 *>(s_mask)[i] = make_uint4(0, 0, 0, 0);
+    // ---- the wave's words of all the batch's tiles are loaded ---------------------------------------------------------------------
     const u32 w0 = wave * kDtWaveWords; // tile-local index of the wave's first word
     u32x4 hold[kP][4];                  // (the last tile's go to LDS at once)
 #pragma unroll
@@ -189,15 +189,34 @@ __global__ __launch_bounds__(kDtWaves * 64, (kP <= 2 ? WAH_DT_MINW : 4)) void de
 #pragma unroll
         for (int k = 0; k < 4; ++k) hold[j][k] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane * 16u, 1024 * k, WAH_DT_LOAD_AUX); // nontemporal: read once
     }
+    u32 behind_w[3] = {0, 0, 0};
     {
         // ... and the wave's share of the words BEHIND the batch (18 batches of 64: what the last tile's last segment may need)
         const __amdgpu_buffer_rsrc_t rb = make_rsrc(a.comp + batch_w0 + kBatchWords, left > kBatchWords ? (left - kBatchWords >= kDtBehind ? kDtBehind * 4u : (left - kBatchWords) * 4u) : 0u);
+#pragma unroll
+        for (u32 b = 0; b < 3; ++b)
+            if (wave + 8u * b < kDtBehind / 64u) behind_w[b] = __builtin_amdgcn_raw_buffer_load_b32(rb, (64u * (wave + 8u * b) + lane) * 4u, 0, 0);
+    }
+
+    // ---- decide: the launch epoch, from what was asked for in front of the ticket ------------------------------------------------
+    const LaunchEpoch le = launch_epoch_begin(a.ctrl, ask, wt, a.n_wg_tiles, a.gen_desc, a.scan_words, 0);
+    if (le.bad) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) a.info[0] = a.info[1] = 0;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the batch's loads (bounded descriptors over the stream) are not left behind
+        return;
+    }
+    const u32 epoch = le.epoch;
+    u64 *const defer_count = defer_counters_mine(a.defer_count, defer_seq);
+
+    // ---- the start flags are cleared; the words behind the batch go to their place ------------------------------------------------
+    for (u32 i = threadIdx.x; i < kDtMaskWords / 4u; i += kDtWaves * 64u) reinterpret_cast<uint4 *>(s_mask)[i] = make_uint4(0, 0, 0, 0);
+    {
         u32 any_fill = 0;
 #pragma unroll
         for (u32 b = 0; b < 3; ++b) {
             const u32 i = 64u * (wave + 8u * b) + lane; // index among the words behind the batch
             if (wave + 8u * b < kDtBehind / 64u) {
-                const u32 w = __builtin_amdgcn_raw_buffer_load_b32(rb, i * 4u, 0, 0);
+                const u32 w = behind_w[b];
                 const u32 v = kBatchWords + i < left ? w : kFillZero;
                 s_words[kDtTileWords + i] = v;
                 any_fill |= v;

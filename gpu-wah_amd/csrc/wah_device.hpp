@@ -140,10 +140,43 @@ __device__ __forceinline__ u32 draw_tile(u32 *ctrl, u32 *s_tile) {
     return uniform32(*s_tile);
 }
 
-__device__ __forceinline__ LaunchEpoch launch_epoch_begin(u32 *ctrl, u32 tile, u32 n_tiles, u32 *scan_area, u64 scan_words, int keep_error) {
+// A workgroup's prologue is ASK, TICKET, DECIDE.  What launch_epoch_begin needs of the control block does not depend on the
+// tile number, so it is asked for BEFORE the ticket is drawn: the three loads and thread 0's ticket atomic are in flight together,
+// one round trip instead of two in front of the tile's first data load (which needs the ticket and nothing else: the callers issue
+// it right behind draw_tile, under tile < n_tiles, and call launch_epoch_begin with it in flight).  Reading early is allowed: the
+// words are written by launch_epoch_end alone, by the LAST tile once every other tile has published -- hence started, hence asked
+// -- and the protocol wants no more of a workgroup than that it has read the epoch before it publishes.  Relaxed atomic loads
+// (wavefront scope: the plain global_load they were, no cache bits -- nothing of THIS launch writes the words while they are
+// read): the compiler moves no atomic across draw_tile's atomic and barrier, so they stay in front of s_barrier.  Vector loads,
+// not scalar ones: the scalar cache is shared between CUs and is not what an earlier launch's agent-scope stores are ordered
+// against.
+struct EpochAsk {
+    u32 stored, magic, wraps;
+};
+__device__ __forceinline__ EpochAsk launch_epoch_ask(u32 *ctrl) {
+    EpochAsk q;
+    q.stored = __hip_atomic_load(ctrl + kCtlEpoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    q.magic = __hip_atomic_load(ctrl + kCtlMagic, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    q.wraps = __hip_atomic_load(ctrl + kCtlWraps, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); // (used when the epoch space wraps; the epoch's line)
+    return q;
+}
+// TICKET, with the answers taken behind its barrier (scalar registers from here on).  They have had the ticket's round trip and
+// the barrier to arrive, so this wait is over before it begins -- and it is the last one for them: the wait counters count in
+// order, and a wait for the answers placed BEHIND the tile's data loads waits, wherever a branch lies between, for the data too
+// (seen: s_waitcnt vmcnt(1) behind the eight loads of a pair, in front of the decision).
+__device__ __forceinline__ u32 draw_tile(u32 *ctrl, u32 *s_tile, EpochAsk &ask) {
+    const u32 tile = draw_tile(ctrl, s_tile);
+    ask.stored = uniform32(ask.stored);
+    ask.magic = uniform32(ask.magic);
+    ask.wraps = uniform32(ask.wraps);
+    return tile;
+}
+
+// DECIDE, behind the ticket's barrier, from what launch_epoch_ask brought (the caller's data loads may be in flight: on le.bad it
+// waits for them before it returns; the wrap path's wait happens with them in flight)
+__device__ __forceinline__ LaunchEpoch launch_epoch_begin(u32 *ctrl, const EpochAsk &ask, u32 tile, u32 n_tiles, u32 *scan_area, u64 scan_words, int keep_error) {
     LaunchEpoch le;
-    const u32 stored = uniform32(ctrl[kCtlEpoch]);
-    const u32 magic = uniform32(ctrl[kCtlMagic]);
+    const u32 stored = ask.stored, magic = ask.magic; // (draw_tile has made them scalar)
     // neither a zeroed nor a used workspace: a foreign magic word, an epoch no launch can have left, or a ticket counter
     // that did not start at zero -- a tile number outside the grid, checked BEFORE anything is indexed with it (recycled
     // memory often reads as magic == 0 with garbage elsewhere)
@@ -155,7 +188,7 @@ __device__ __forceinline__ LaunchEpoch launch_epoch_begin(u32 *ctrl, u32 tile, u
         return le;
     }
     if (le.wrap) {
-        const u32 wraps = uniform32(ctrl[kCtlWraps]);
+        const u32 wraps = ask.wraps;
         if (tile == 0) {
             for (u64 k = threadIdx.x; k < scan_words; k += blockDim.x)
                 __hip_atomic_store(scan_area + k, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
