@@ -50,6 +50,10 @@ from .api import (  # noqa: F401
     bsi_bounds,
     BSI_MAX_SLICES,
     BSI_EXISTS,
+    bsi_member_device,
+    member_set,
+    MEMBER_NEGATE,
+    MEMBER_BITSET,
     bsi_compare_device,
     bsi_compare_row_order,
     BSI_EXISTS_A,

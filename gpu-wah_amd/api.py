@@ -69,6 +69,9 @@ ABI_SYMBOLS = {
     "wah_bsi_range_scratch_bytes": (_sz, [_u64, _u64]),
     "wah_bsi_range_indexed_device": (_int, [_u64, _u64, _vp, _vp, ctypes.c_uint, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
     "wah_bsi_range_status": (_int, [_vp, _u64, _u64, _vp]),
+    "wah_bsi_member_scratch_bytes": (_sz, [_u64, _u64]),
+    "wah_bsi_member_indexed_device": (_int, [_u64, _u64, _vp, _vp, _u64, _vp, ctypes.c_uint, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
+    "wah_bsi_member_status": (_int, [_vp, _u64, _u64, _vp]),
     "wah_bsi_compare_scratch_bytes": (_sz, [_u64, _u64, _u64]),
     "wah_bsi_compare_indexed_device": (_int, [_int, _u64, _u64, _u64, _vp, ctypes.c_uint, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
     "wah_bsi_compare_status": (_int, [_vp, _u64, _u64, _u64, _vp]),
@@ -694,6 +697,64 @@ def bsi_range_device(table, bounds, n_words, exists=False, scratch=None, out=Non
         "wah_bsi_range_indexed_device", n, dev, lambda: lib().wah_bsi_range_scratch_bytes(n, k),
         lambda *tail: lib().wah_bsi_range_indexed_device(n, k, table.data_ptr(), bounds.data_ptr(), BSI_EXISTS if exists else 0, *tail),
         lambda sc, sp: lib().wah_bsi_range_status(sc, n, k, sp), scratch, out, out_offsets, check)
+
+
+MEMBER_NEGATE, MEMBER_BITSET = 2, 4  # WAH_MEMBER_NEGATE, WAH_MEMBER_BITSET
+
+
+def member_set(values, device):
+    """The set of wah_bsi_member_indexed_device as the sorted int64 device tensor the call reads: values are Python ints in
+    0 .. 2^64 - 1 or a numpy uint64 array, sorted as UNSIGNED numbers and stored as their two's-complement bit patterns, the way
+    bsi_bounds stores a bound.  Duplicates stay: the call allows them."""
+    import torch
+
+    if isinstance(values, np.ndarray):
+        if values.dtype != np.uint64:
+            raise WahError("a numpy set is a uint64 array")
+        v = np.sort(values.reshape(-1))
+    else:
+        v = np.array(sorted(_as_int64(x, "a set entry") & ((1 << 64) - 1) for x in values), dtype=np.uint64)
+    return torch.from_numpy(v.view(np.int64).copy()).to(device)
+
+
+def bsi_member_device(table, members, n_words, count=None, exists=False, negate=False, bitset=False, set_bits=None, scratch=None, out=None,
+                      out_offsets=None, check=True):
+    """compress(value IN members [AND exists]) -- negate=True: NOT IN -- over a bit-sliced attribute in one call
+    (wah_bsi_member_indexed_device).  table: as for bsi_range_device, one row per slice, MOST significant first, and with
+    exists=True the existence bitmap as one more row behind them.  members: a contiguous int64 device tensor, the set as 64-bit
+    patterns in non-decreasing UNSIGNED order (member_set; duplicates allowed), of which the first count[0] entries count when
+    count, an int64 device tensor [1], is given -- or with bitset=True a contiguous int32 device tensor of words, a bit array of
+    set_bits bits (default: 32 per word) in which value v is bit v % 32 of word v / 32: a decoded bitmap.  Only the device reads
+    members and count.  Returns as bsi_range_device: (stream, seg_offsets), or with check=False, which only enqueues, (out, count
+    tensor, out_offsets)."""
+    torch = _torch()
+    table = _operand_table(table, "a slice table")
+    dev = table.device
+    k = int(table.shape[0]) - (1 if exists else 0)
+    if not 1 <= k <= BSI_MAX_SLICES:
+        raise WahError("between 1 and 64 slices (and one more row with exists=True)")
+    if not isinstance(members, torch.Tensor) or members.dim() != 1 or members.device != dev or not members.is_contiguous():
+        raise WahError("members: a contiguous one-dimensional tensor on the table's device")
+    if bitset:
+        if members.dtype not in (torch.int32, torch.uint32) or count is not None:
+            raise WahError("a bit array is a 32-bit integer tensor of words and has no count")
+        capacity = 32 * int(members.numel()) if set_bits is None else int(set_bits)
+        if not 0 <= capacity <= 32 * int(members.numel()):
+            raise WahError("set_bits: at most 32 bits per word of the bit array")
+    else:
+        if members.dtype != torch.int64 or set_bits is not None:
+            raise WahError("a list is an int64 tensor (member_set) and has no set_bits")
+        capacity = int(members.numel())
+        if count is not None and (count.dtype != torch.int64 or count.numel() != 1 or count.device != dev):
+            raise WahError("count: a one-element int64 tensor on the table's device")
+    flags = (BSI_EXISTS if exists else 0) | (MEMBER_NEGATE if negate else 0) | (MEMBER_BITSET if bitset else 0)
+    set_ptr = members.data_ptr() if members.numel() else None
+    count_ptr = None if count is None else count.data_ptr()
+    n = int(n_words)
+    return _compressed_result(
+        "wah_bsi_member_indexed_device", n, dev, lambda: lib().wah_bsi_member_scratch_bytes(n, k),
+        lambda *tail: lib().wah_bsi_member_indexed_device(n, k, table.data_ptr(), set_ptr, capacity, count_ptr, flags, *tail),
+        lambda sc, sp: lib().wah_bsi_member_status(sc, n, k, sp), scratch, out, out_offsets, check)
 
 
 BSI_EXISTS_A, BSI_EXISTS_B = 1, 2  # WAH_BSI_EXISTS_A, WAH_BSI_EXISTS_B

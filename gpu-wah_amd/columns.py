@@ -359,6 +359,94 @@ def range_column(wah, bsi, lo, hi, table=None, bounds=None, **reuse):
     return wah.bsi_range_device(table, bounds, n, exists=has_exists, **reuse)
 
 
+def _sort_unsigned(values):
+    """An int64 tensor of 64-bit patterns in non-decreasing UNSIGNED order (the order wah_bsi_member_indexed_device wants): the
+    sign bit is flipped around a signed torch.sort."""
+    import torch
+
+    top = -(1 << 63)
+    return (torch.sort(values.reshape(-1) ^ top)[0] ^ top).contiguous()
+
+
+def _slice_table(bsi):
+    """The slice table of a bit-sliced attribute in sweep order: its slices, most significant first, then its existence bitmap."""
+    stream, seg_offsets, n, n_bits, has_exists = bsi
+    return column_operand_table(stream, seg_offsets, n, list(range(n_bits + (1 if has_exists else 0))))
+
+
+def isin_column(wah, bsi, values, negate=False, **reuse):
+    """`value IN (values)`, with negate=True `value NOT IN (values)`, over a bit-sliced attribute in one call
+    (wah_bsi_member_indexed_device): bsi is what bsi_from_values returned; values: Python ints up to 2^64 - 1 or a numpy uint64
+    array (api.member_set), or an int64 DEVICE tensor of 64-bit patterns in any order, which is sorted on the device -- nothing
+    of it is read back.  Duplicates are allowed, an empty list is an empty set, a value beyond the attribute's width matches
+    nothing.  Rows without a value (the existence bitmap) are in neither result.  reuse: count / scratch / out / out_offsets /
+    check of api.bsi_member_device.  Returns (stream, seg_offsets) of the result bitmap, a predicate like range_column's."""
+    import torch
+
+    stream, _, n, _, has_exists = bsi
+    members = _sort_unsigned(values) if torch.is_tensor(values) else wah.member_set(values, stream.device)
+    return wah.bsi_member_device(_slice_table(bsi), members, n, exists=has_exists, negate=negate, **reuse)
+
+
+def semi_join_rows(wah, bsi_fk, dim_mask, dim_n_words, negate=False, **reuse):
+    """The star join's probe: the fact rows whose foreign key -- a ROW NUMBER of the dimension table, the bit-sliced attribute
+    bsi_fk -- is a row that dim_mask selects (`WHERE fk IN (SELECT rowid FROM dim WHERE ...)`), in one call
+    (wah_bsi_member_indexed_device, WAH_MEMBER_BITSET).  dim_mask: (stream, seg_offsets) of an indexed compressed bitmap of
+    dim_n_words words, a filter_columns or range_column result over the dimension table.  It is decoded once
+    (api.decompress_segments_device) and its words ARE the set, 32 * dim_n_words bits: a key at or beyond them matches nothing.
+    negate: the rows whose key is not selected; rows without a key are in neither result.  reuse: scratch / out / out_offsets /
+    check of api.bsi_member_device.  Returns (stream, seg_offsets) of the result bitmap."""
+    stream, _, n, _, has_exists = bsi_fk
+    m = int(dim_n_words)
+    words = wah.decompress_segments_device(dim_mask[0], dim_mask[1], m)[:m].contiguous()
+    return wah.bsi_member_device(_slice_table(bsi_fk), words, n, exists=has_exists, negate=negate, bitset=True, set_bits=32 * m, **reuse)
+
+
+def semi_join_values(wah, bsi, bsi_other, other_mask=None, negate=False, other_rows=None, capacity=None, **reuse):
+    """The rows of one attribute whose value occurs in another (`a.x IN (SELECT y FROM b WHERE ...)`): the other attribute's
+    values become a sorted list on the device and one wah_bsi_member_indexed_device call probes it.  bsi, bsi_other: what
+    bsi_from_values returned, of any two lengths and widths.  Rows of bsi_other without a value (its existence bitmap) do not
+    enter the set; WITHOUT an existence bitmap every row of its bitmaps has a value, the rows behind the caller's own count the
+    value 0 -- other_rows cuts the set to the first other_rows rows.
+      other_mask=None  the set is values_of_column(bsi_other), a torch.sort follows, and the count (the rows that have a
+                       value) stays in a device tensor: nothing is read back;
+      other_mask       (stream, seg_offsets), a bitmap over bsi_other's rows: the set is values_at_rows of select_rows.  The
+                       number of selected rows is READ BACK ONCE to size the list -- unless capacity= is given: the list then
+                       has that many entries, padded with UINT64_MAX behind the selected rows' values, and the count stays on the
+                       device; more selected rows than capacity are refused by the call's status (a count above the capacity).
+    negate: the rows whose value does not occur; rows of bsi without a value are in neither result.  reuse: scratch / out /
+    out_offsets / check of api.bsi_member_device.  Returns (stream, seg_offsets) of the result bitmap."""
+    import torch
+
+    stream, _, n, _, has_exists = bsi
+    o_stream, o_offsets, o_n, o_bits, o_exists = bsi_other
+    count = None
+    if other_mask is None:
+        if capacity is not None:
+            raise ValueError("capacity sizes the list of a masked set")
+        values, have = values_of_column(wah, bsi_other, 0, other_rows)
+        if have is not None:
+            values = torch.where(have, values, torch.full_like(values, -1))  # (UINT64_MAX: sorted behind every counted entry)
+            count = have.sum().reshape(1)
+    else:
+        if other_rows is not None:
+            raise ValueError("other_rows cuts an unmasked set: a mask selects its own rows")
+        predicates = [(other_mask[0], other_mask[1], [0], False)]
+        if o_exists:
+            predicates.append((o_stream, o_offsets, [o_bits], False))
+        if capacity is None:
+            rows, _ = select_rows(wah, predicates, o_n)
+            values, _ = values_at_rows(wah, bsi_other, rows)
+        else:
+            selected, selected_offsets = filter_columns(wah, predicates, o_n)
+            rows = torch.zeros(int(capacity), dtype=torch.int64, device=stream.device)
+            rows, info = wah.positions_device(selected, selected_offsets, o_n, limit=int(capacity), out=rows, check=False)
+            values, _ = values_at_rows(wah, bsi_other, rows)
+            count = info[:1].contiguous()  # (the total: above the capacity the call refuses it)
+            values = torch.where(torch.arange(int(capacity), device=stream.device) < count, values, torch.full_like(values, -1))
+    return wah.bsi_member_device(_slice_table(bsi), _sort_unsigned(values), n, count=count, exists=has_exists, negate=negate, **reuse)
+
+
 def compare_column(wah, bsi, op, c, **reuse):
     """`value op c` over a bit-sliced attribute, op one of "<", "<=", ">", ">=", "==", as the matching range of range_column
     ("<" with c == 0 and ">" with c at the attribute's maximum are empty ranges, not errors; != is == as a negated predicate of

@@ -1387,6 +1387,48 @@ int wah_bsi_range_status(void *d_scratch, uint64_t n_words, uint64_t n_slices, v
     return wah_bitop_indexed_status(d_scratch, n_words, stream);
 }
 
+// value IN (set) over a bit-sliced attribute (wah_member.hip, member_items_kernel behind member_check_kernel).  Scratch and road
+// as the range call's: one decoded bitmap, then the compress passes.  The set and its count stay in device memory: nothing here
+// reads them.
+size_t wah_bsi_member_scratch_bytes(uint64_t n_words, uint64_t n_slices) {
+    (void)n_slices;
+    return bitop_indexed_layout(n_words).total;
+}
+
+int wah_bsi_member_indexed_device(uint64_t n_words, uint64_t n_slices, const wah_bitop_operand *d_slices, const void *d_set,
+                                  uint64_t set_capacity, const uint64_t *d_set_count, unsigned flags, uint32_t *d_out,
+                                  uint64_t out_capacity_words, uint64_t *d_out_words, uint64_t *d_out_offsets, void *d_scratch,
+                                  size_t scratch_bytes, void *stream) {
+    g_err[0] = 0;
+    if (n_slices < 1 || n_slices > WAH_BSI_MAX_SLICES || (flags & ~(WAH_BSI_EXISTS | WAH_MEMBER_NEGATE | WAH_MEMBER_BITSET)))
+        return refuse("between 1 and 64 slices, no flag besides WAH_BSI_EXISTS, WAH_MEMBER_NEGATE and WAH_MEMBER_BITSET", WAH_ERR_ARG);
+    const bool bitset = (flags & WAH_MEMBER_BITSET) != 0;
+    if (!d_slices || !aligned(d_slices, 7) || !scratch_ok(d_scratch)) return refuse("null or misaligned slice table or scratch", WAH_ERR_ARG);
+    if (set_capacity >= (1ull << 40) || (set_capacity && !d_set) || !aligned(d_set, bitset ? 3 : 7) || !aligned(d_set_count, 7) ||
+        (bitset && d_set_count))
+        return refuse("a set of fewer than 2^40 entries or bits, aligned to its entries (8 bytes, a bit array's words: 4), a count only with a list", WAH_ERR_ARG);
+    if (!out_given(n_words, d_out, d_out_words) || n_words >= (1ull << 40)) return refuse("null output pointer, or 2^40 words or more", WAH_ERR_ARG);
+    const BitopIndexedLayout l = bitop_indexed_layout(n_words);
+    if (scratch_bytes < l.total) return refuse("scratch too small", WAH_ERR_WORKSPACE);
+    wah::MemberArgs a = {};
+    a.table = reinterpret_cast<const wah::BitopListOperand *>(d_slices);
+    a.set = d_set;
+    a.set_capacity = set_capacity;
+    a.set_count = d_set_count;
+    a.n_slices = (uint32_t)n_slices;
+    a.has_exists = (flags & WAH_BSI_EXISTS) ? 1u : 0u;
+    a.negate = (flags & WAH_MEMBER_NEGATE) ? 1u : 0u;
+    a.bitset = bitset ? 1u : 0u;
+    a.n_items = seg_geometry(n_words).n_segments * (n_slices > 32 ? 2u : 1u);
+    return combine_then_compress(a, wah::launch_member, "member launch", n_words, d_out, out_capacity_words, d_out_words, d_out_offsets,
+                                 static_cast<char *>(d_scratch), l, stream);
+}
+
+int wah_bsi_member_status(void *d_scratch, uint64_t n_words, uint64_t n_slices, void *stream) {
+    (void)n_slices;
+    return wah_bitop_indexed_status(d_scratch, n_words, stream);
+}
+
 // A op B row by row over two bit-sliced attributes (wah_bitop_list.hip, bsi_compare_segments_kernel).  Scratch and road as the
 // range call's: one decoded bitmap, then the compress passes.
 static_assert(WAH_CMP_LT == wah::kCmpLT && WAH_CMP_LE == wah::kCmpLE && WAH_CMP_GT == wah::kCmpGT && WAH_CMP_GE == wah::kCmpGE &&

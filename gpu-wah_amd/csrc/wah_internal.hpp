@@ -401,6 +401,25 @@ struct ValuesArgs {
 };
 hipError_t launch_values_items(const ValuesArgs &a, uint32_t mode, hipStream_t s);
 
+// wah_bsi_member_indexed_device (wah_member.hip): value IN (set) over a bit-sliced attribute.  table: n_slices rows, most
+// significant slice first, then the existence bitmap if has_exists.  set: a list of set_capacity u64, the first *set_count (or
+// all, set_count == nullptr) non-decreasing, or with `bitset` the words of a bit array of set_capacity bits.  An item is a
+// segment, above 32 slices a segment and a half of its groups: n_items = n_segments x (n_slices > 32 ? 2 : 1), item t being
+// segment t / halves, groups 512 (t % halves) .. of it.  g as in BitopListArgs (first_segment is 0).
+struct MemberArgs {
+    SegmentsArgs g;
+    const BitopListOperand *table;
+    const void *set;
+    uint64_t set_capacity;
+    const uint64_t *set_count;
+    uint64_t n_items;
+    uint32_t n_slices;   // 1 .. 64
+    uint32_t has_exists; // 0 or 1: one more row
+    uint32_t negate;     // 0 or 1: NOT IN
+    uint32_t bitset;     // 0 or 1
+};
+hipError_t launch_member(const MemberArgs &a, hipStream_t s); // the list's check, then the items
+
 // ... on operands of few words per segment: their runs merged in the compressed domain, one lane per segment
 // (wah_bitop_runs.hip): count pass, scan of the tile totals, write pass
 struct BitopRunsArgs {

@@ -2,7 +2,8 @@
 // one segment: every row's words of that segment applied to an image of the segment's 1024 groups in LDS (list_walk), the sweep
 // that keeps one row at a time in the zeroed image (row_sweep), the segment a wavefront owns (wave_segment), image_fill and
 // report_stream_error.  Written once for the kernels that read such a table: the queries of wah_bitop_list.hip, the
-// (column, segment) items of wah_splice.hip, wah_compact.hip and wah_update.hip, and the (segment, half) items of wah_values.hip.
+// (column, segment) items of wah_splice.hip, wah_compact.hip and wah_update.hip, and the (segment, half) items of wah_values.hip and
+// wah_member.hip.
 //
 // One wavefront owns one output segment; its accumulator is the segment's 1024 groups in LDS (4 KiB per wavefront, 16 KiB per
 // workgroup: bitop_many_segments_kernel holds 20).  An operand's segment is never expanded: its words are loaded in batches of

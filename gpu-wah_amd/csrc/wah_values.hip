@@ -29,7 +29,7 @@
 //
 // The grid is capped (kValuesGridItems workgroups, two per CU: one resident, one waiting for its LDS) and strides over the items:
 // a bitmap may have 2^40 words.
-#include "wah_list_walk.hpp"
+#include "wah_fold_bits.hpp"
 
 namespace wah {
 namespace {
@@ -77,17 +77,7 @@ __global__ __launch_bounds__(kValuesWaves * 64) void values_items_kernel(const V
                 const u32 j = w_lo + cur;
                 if (kMode == kFetchBits) {
                     const u32 sig = (a.n_operands - 1u - j) & 31u; // (significance s lies in half s / 32 at bit s % 32)
-#pragma nounroll
-                    for (u32 k = 0; k < kSegGroups / 64u; ++k) {
-                        const u32 g = 64u * k + lane;
-                        const u32 w = acc[g];
-                        if (__ballot(w != 0u) == 0ull) continue;
-                        u32 *row = s_rows + 31u * g;
-                        // (every lane ORs, a zero where its bit is clear: two instructions a bit and no branch on the lanes)
-#pragma unroll
-                        for (u32 b = 0; b < 31u; ++b)
-                            __hip_atomic_fetch_or(row + b, ((w >> b) & 1u) << sig, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    }
+                    fold_slice_bits(acc, s_rows, 0u, kSegGroups / 64u, sig, lane); // (wah_fold_bits.hpp: shared with wah_member.hip)
                 } else {
 #pragma nounroll
                     for (u32 k = 0; k < kSegGroups / 64u; ++k) {

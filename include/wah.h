@@ -482,6 +482,50 @@ int wah_bsi_range_indexed_device(uint64_t n_words, uint64_t n_slices, const wah_
                                  uint64_t *d_out_offsets, void *d_scratch, size_t scratch_bytes, void *stream);
 int wah_bsi_range_status(void *d_scratch, uint64_t n_words, uint64_t n_slices, void *stream);
 
+/* `value IN (set)` / `value NOT IN (set)` over a BIT-SLICED attribute in ONE call: an IN list of constants, or a SEMI-JOIN --
+ * `WHERE fk IN (SELECT id FROM dim WHERE ...)`, the probe side of a star join -- without the value column in global memory.
+ *   d_slices: exactly the range call's table: n_slices rows (1 .. WAH_BSI_MAX_SLICES), most significant slice first, plus ONE
+ *   more with WAH_BSI_EXISTS, the existence bitmap; windows into column matrices, capacities as lengths and the not-yet-checked
+ *   output of an earlier call on the stream are allowed.
+ *   The set as a SORTED LIST (no WAH_MEMBER_BITSET): d_set is set_capacity uint64 in DEVICE memory, 8-byte aligned; its first
+ *   *d_set_count entries are the set, in NON-DECREASING order -- duplicates are allowed, so the torch.sort of a value column
+ *   is a set.  d_set_count is one uint64 in device memory, read by the device only; NULL: the count is set_capacity.
+ *   set_capacity == 0 is an empty set (d_set may then be NULL).  An entry at or above 2^n_slices matches nothing: entries
+ *   are data, never errors.
+ *   The set as a BIT ARRAY (WAH_MEMBER_BITSET): d_set is ceil(set_capacity / 32) uint32 words, 4-byte aligned; value v is in the
+ *   set iff v < set_capacity and bit v % 32 of word v / 32 is set -- the layout of a DECODED bitmap, so the decoded filter of a
+ *   dimension table is the set for the fact table's foreign key.  Bits of the last word at or behind set_capacity are never
+ *   looked at; d_set_count must be NULL; set_capacity may be anything below 2^40.
+ * The result is the bitmap of the rows whose value is in the set, with WAH_MEMBER_NEGATE of those whose value is NOT, either
+ * ANDed with the existence bitmap where there is one (NOT IN over an attribute with NULLs is one call): word for word what
+ * compress() emits for that bitmap of n_words words (ragged ends included; n_words == 0: an empty stream); d_out_offsets (may
+ * be NULL) receives its segment index.  WITHOUT an existence bitmap the rows beyond the caller's own row count have the value 0,
+ * as in the range call: they match when 0 is in the set, and under NEGATE when it is not.
+ * Set, count and table are read by the device only: the call is asynchronous on `stream`, allocates nothing, never
+ * synchronises, and a captured graph replayed after any of them was overwritten in place answers the NEW query.  One check
+ * launch over the list, then one launch of one workgroup per segment (per half segment above 32 slices) that folds the slices
+ * into one word (two) per row in LDS and probes the set per row -- about log2(count) dependent 8-byte loads a row for a list,
+ * one 4-byte load for a bit array; then the compress passes over the one decoded bitmap that leaves.
+ *   d_scratch: wah_bsi_member_scratch_bytes(n_words, n_slices) bytes, 256-byte aligned, no initialisation; it EQUALS
+ *   wah_bitop_indexed_scratch_bytes(n_words) for every n_slices.
+ * Errors the host can see come back before any HIP call, in this order: n_slices outside 1 .. 64 or unknown flag bits; a null
+ * or misaligned table (8 B) or scratch (256 B); set_capacity >= 2^40, a null d_set with set_capacity > 0, a misaligned set (8 B
+ * for a list, 4 B for a bit array) or count (8 B), a count with WAH_MEMBER_BITSET; a null d_out_words, a null d_out with
+ * n_words > 0, n_words >= 2^40 -- all WAH_ERR_ARG; then too small a scratch: WAH_ERR_WORKSPACE.  Everything only the device
+ * sees is reported by wah_bsi_member_status(), which synchronises the stream: WAH_ERR_STREAM for everything the list call
+ * refuses in an operand, for *d_set_count > set_capacity (nothing is read behind the capacity) and for a list that is not
+ * non-decreasing within its count (what lies behind the count is never looked at); then WAH_ERR_CAPACITY for too small an
+ * output, and nothing is written behind out_capacity_words.  The set is checked whole and every table row's every segment is
+ * walked: the verdict depends neither on the attribute's data nor on which values match. */
+#define WAH_MEMBER_NEGATE 2u /* NOT IN: the rows (that exist) whose value is not in the set */
+#define WAH_MEMBER_BITSET 4u /* the set is a bit array over the value domain, not a sorted list */
+size_t wah_bsi_member_scratch_bytes(uint64_t n_words, uint64_t n_slices);
+int wah_bsi_member_indexed_device(uint64_t n_words, uint64_t n_slices, const wah_bitop_operand *d_slices, const void *d_set,
+                                  uint64_t set_capacity, const uint64_t *d_set_count, unsigned flags, uint32_t *d_out,
+                                  uint64_t out_capacity_words, uint64_t *d_out_words, uint64_t *d_out_offsets, void *d_scratch,
+                                  size_t scratch_bytes, void *stream);
+int wah_bsi_member_status(void *d_scratch, uint64_t n_words, uint64_t n_slices, void *stream);
+
 /* `A op B` ROW BY ROW over TWO bit-sliced attributes in ONE call -- `ship_date > commit_date`, `price < cost`, `a == b`: the
  * range call's sweep with the constant's bit replaced by the other attribute's slice.  A has n_slices_a slices and B has
  * n_slices_b, each 1 .. WAH_BSI_MAX_SLICES and possibly different; the narrower one counts as zero above its width.  BOTH
