@@ -83,6 +83,9 @@ from .api import (  # noqa: F401
     GROUP_MAX_FILTERS,
     GROUP_MAX_ROWS,
     GROUP_MAX_ATTRS,
+    bsi_group_by_device,
+    GROUP_BY_ACCUMULATE,
+    GROUP_BY_MAX_BUCKETS,
     positions_device,
     from_positions_device,
     from_positions_max_words,

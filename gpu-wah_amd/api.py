@@ -99,6 +99,9 @@ ABI_SYMBOLS = {
     "wah_group_sum_indexed_device": (_int, [_u64, _u64, _vp, _u64, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "wah_positions_indexed_device": (_int, [_u64, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _sz, _vp]),
     "wah_select_status": (_int, [_vp, _vp]),
+    "wah_bsi_group_by_scratch_bytes": (_sz, [_u64]),
+    "wah_bsi_group_by_indexed_device": (_int, [_u64, _u64, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _u64, ctypes.c_uint, _vp, _vp, _vp, _sz, _vp]),
+    "wah_bsi_group_by_status": (_int, [_vp, _vp]),
     "wah_from_positions_max_words": (_u64, [_u64, _u64, _u64]),
     "wah_from_positions_scratch_bytes": (_sz, [_u64, _u64]),
     "wah_from_positions_device": (_int, [_u64, _u64, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
@@ -1143,6 +1146,58 @@ def group_sum_device(filters, groups, operands, attr_bits, n_words, rows_per_gro
                                                                group_rows.data_ptr(), counts.data_ptr(), sums.data_ptr(), *tail),
               lib().wah_select_status, scratch, check)
     return group_rows, counts, sums
+
+
+GROUP_BY_ACCUMULATE = 2  # WAH_GROUP_BY_ACCUMULATE
+GROUP_BY_MAX_BUCKETS = 1 << 30  # WAH_GROUP_BY_MAX_BUCKETS
+
+
+def bsi_group_by_device(key_table, n_words, n_rows, n_buckets, value_table=None, filters=None, exists=False, lookup=None, accumulate=False,
+                        scratch=None, counts=None, sums=None, check=True):
+    """`SELECT key, COUNT(*), SUM(value) WHERE <filters> GROUP BY key` over a BIT-SLICED key in one call, no bitmap and no value
+    column written and nothing read back (wah_bsi_group_by_indexed_device).  key_table: the key's 1 .. 32 slices, most significant
+    first, and with exists=True its existence bitmap as one more row behind them; value_table: the value attribute's 1 .. 32 slices,
+    most significant first, no existence row, or None: count only; filters: rows ANDed into the selection (None or empty: no
+    filter).  The three tables: each a list of (stream, seg_offsets) pairs or a ready [k, 3] table (bitop_operand_table,
+    columns.column_operand_table) -- only the device reads them.  Rows at or behind n_rows are never counted.  lookup: a contiguous
+    int32 / uint32 device tensor, key -> bucket (a key at or behind its end, and an entry at or above n_buckets -- 0xFFFFFFFF, -1 as
+    int32, drops a key -- go to the bucket "other"), or None: the key is the bucket.  Returns (counts [n_buckets + 1], sums
+    [n_buckets + 1, 2] or None) as int64 device tensors, "other" last, the sums as low and high 64 bits (bit patterns: a low word
+    at or above 2^63 reads as negative).  accumulate=True ADDS into the counts / sums passed in, which are otherwise cleared by the
+    call.  scratch / counts / sums: reuse these tensors; check=False: only enqueue (the caller reads wah_bsi_group_by_status
+    later)."""
+    torch = _torch()
+    kt = _operand_table(key_table, "a key table")
+    dev = kt.device
+    vt = _operand_table(value_table, "a value table") if value_table is not None else None
+    ft = _operand_table(filters, "a filter table") if filters is not None and len(filters) else None
+    if (vt is not None and vt.device != dev) or (ft is not None and ft.device != dev):
+        raise WahError("the filter table, the key table and the value table are on one device")
+    if lookup is not None and (not isinstance(lookup, torch.Tensor) or lookup.dtype not in (torch.int32, torch.uint32) or lookup.dim() != 1 or
+                               lookup.device != dev or not lookup.is_contiguous() or not lookup.numel()):
+        raise WahError("lookup: a contiguous one-dimensional int32 or uint32 tensor of at least one key on the tables' device")
+    if accumulate and (counts is None or (vt is not None and sums is None)):
+        raise WahError("accumulate=True adds into the counts and sums it is given")
+    n, r, b = int(n_words), int(n_rows), int(n_buckets)
+    if not 1 <= b <= GROUP_BY_MAX_BUCKETS:
+        raise WahError("between 1 and 2^30 buckets")
+    ks = int(kt.shape[0]) - (1 if exists else 0)
+    vs, f = 0 if vt is None else int(vt.shape[0]), 0 if ft is None else int(ft.shape[0])
+    if scratch is None:
+        scratch = torch.empty(int(lib().wah_bsi_group_by_scratch_bytes(n)), dtype=torch.uint8, device=dev)
+    counts = _int64_tensor(torch, counts, (b + 1,), dev, "counts: a contiguous int64 [n_buckets + 1] tensor on the tables' device")
+    if vt is not None:
+        sums = _int64_tensor(torch, sums, (b + 1, 2), dev, "sums: a contiguous int64 [n_buckets + 1, 2] tensor on the tables' device")
+    elif sums is not None:
+        raise WahError("sums go with a value table")
+    flags = (BSI_EXISTS if exists else 0) | (GROUP_BY_ACCUMULATE if accumulate else 0)
+    _enqueued("wah_bsi_group_by_indexed_device", "bsi_group_by",
+              lambda *tail: lib().wah_bsi_group_by_indexed_device(n, r, f, ft.data_ptr() if f else None, ks, kt.data_ptr(), vs,
+                                                                  vt.data_ptr() if vs else None, None if lookup is None else lookup.data_ptr(),
+                                                                  0 if lookup is None else int(lookup.numel()), b, flags, counts.data_ptr(),
+                                                                  sums.data_ptr() if vs else None, *tail),
+              lib().wah_bsi_group_by_status, scratch, check)
+    return counts, sums
 
 
 def positions_device(stream, seg_offsets, n_words, first=0, limit=None, out=None, scratch=None, check=True):

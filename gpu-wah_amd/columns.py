@@ -676,6 +676,109 @@ def aggregate_columns(wah, keys, attributes, n_words_per_column, where=None, **r
             "counts": [rows if ex is None else sums[:, ex, 0].reshape(shape) for _, ex in places]}
 
 
+GROUP_BY_DROP = 0xFFFFFFFF  # a lookup entry that no bucket count reaches: the key's rows go to "other"
+
+
+def _lookup_tensor(lookup, dev):
+    """A key -> bucket table as the contiguous int32 device tensor the call reads (bit patterns: 0xFFFFFFFF is -1)."""
+    import torch
+
+    if not torch.is_tensor(lookup):
+        lookup = torch.as_tensor(lookup, dtype=torch.int64)
+    if lookup.dtype not in (torch.int32, torch.uint32):
+        low = lookup.to(torch.int64) & 0xFFFFFFFF
+        lookup = ((low ^ 0x80000000) - 0x80000000).to(torch.int32)  # the low 32 bits as the int32 of the same pattern
+    return lookup.to(dev).reshape(-1).contiguous()
+
+
+def group_by_column(wah, key, n_rows, attributes=(), where=None, lookup=None, n_buckets=None):
+    """`SELECT key, COUNT(*), SUM(x), COUNT(x), SUM(y) WHERE <where> GROUP BY key` where the key is a BIT-SLICED attribute of up
+    to 32 bits -- a customer id, a date key -- with one wah_bsi_group_by_indexed_device call per attribute piece and no value
+    column, decoded filter or bitmap in between.  key: a bsi_from_values result (rows outside its existence bitmap are in no
+    bucket); n_rows: the table's rows, at most 32 * the column length; attributes: bsi_from_values / add_columns / ... results of
+    the key's column length -- one wider than 32 slices goes as two calls over its low and high slices, combined as
+    hi << 32 | lo in Python ints, and one with an existence bitmap gets that bitmap as one more attribute of 1 slice, whose
+    sum is COUNT(value); where: None, one (stream, seg_offsets) pair or a list of them, all ANDed; lookup: key -> bucket (a device
+    tensor or a sequence of ints; a key at or behind its end, and an entry at or above n_buckets such as GROUP_BY_DROP, go to
+    "other"), or None: the key is the bucket; n_buckets defaults to 2 ** n_bits of the key, or to the largest lookup entry that
+    is not GROUP_BY_DROP, plus one (read back).  Returns a dict shaped like aggregate_columns':
+      rows:   int64 device tensor [n_buckets]: COUNT(*) per bucket;
+      sums:   per attribute an object array [n_buckets] of Python ints, low + (high << 64): SUM(value);
+      counts: per attribute COUNT(value) as an int64 device tensor [n_buckets]: `rows` itself without an existence bitmap;
+      other:  the same three for the bucket "other": {"rows": int, "sums": [int], "counts": [int]}."""
+    import numpy as np
+    import torch
+
+    stream, seg_offsets, n, n_bits, has_exists = key
+    if n_bits > 32:
+        raise ValueError("a key of at most 32 slices: bucket its low slices, or group after subtract_columns / range_column")
+    dev = stream.device
+    key_table = _slice_table(key)
+    if where is None:
+        where = []
+    elif isinstance(where, tuple):
+        where = [where]
+    filters = wah.bitop_operand_table(list(where)) if len(where) else None
+    if lookup is not None:
+        lookup = _lookup_tensor(lookup, dev)
+    if n_buckets is None:
+        if lookup is None:
+            n_buckets = 1 << n_bits
+        else:
+            wide = lookup.to(torch.int64) & 0xFFFFFFFF
+            n_buckets = int(torch.where(wide == GROUP_BY_DROP, torch.full_like(wide, -1), wide).max().item()) + 1
+    b = max(int(n_buckets), 1)
+
+    def call(table):
+        return wah.bsi_group_by_device(key_table, n, n_rows, b, value_table=table, filters=filters, exists=has_exists, lookup=lookup)
+
+    def whole(sums, shift=0):  # [b + 1, 2] int64 -> Python ints
+        words = sums.cpu().numpy().astype(object) & ((1 << 64) - 1)
+        return (words[:, 0] + (words[:, 1] << 64)) << shift
+
+    rows, all_sums, all_counts = None, [], []
+    for a_stream, a_offsets, n_attr, a_bits, a_exists in attributes:
+        if n_attr != n:
+            raise ValueError("the attributes' columns are as long as the key's")
+        ids = list(range(a_bits))
+        low = column_operand_table(a_stream, a_offsets, n, ids[-32:])
+        rows, sums = call(low)
+        total = whole(sums)
+        if a_bits > 32:
+            total = total + whole(call(column_operand_table(a_stream, a_offsets, n, ids[:-32]))[1], 32)
+        all_sums.append(total)
+        all_counts.append(call(column_operand_table(a_stream, a_offsets, n, [a_bits]))[1][:, 0].contiguous() if a_exists else rows)
+    if rows is None:
+        rows = call(None)[0]
+    return {"rows": rows[:b],
+            "sums": [np.ascontiguousarray(s[:b]) for s in all_sums],
+            "counts": [c[:b] for c in all_counts],
+            "other": {"rows": int(rows[b]), "sums": [int(s[b]) for s in all_sums], "counts": [int(c[b]) for c in all_counts]}}
+
+
+def group_by_joined(wah, fk, n_rows, dim_groups, dim_keep=None, attributes=(), where=None, n_buckets=None):
+    """The star join's GROUP BY in the fact table's index: `SELECT d.g, COUNT(*), SUM(f.x) FROM f JOIN d ON f.fk = d.rowid WHERE
+    <d filter> AND <where> GROUP BY d.g`.  fk: the fact table's foreign key, a ROW NUMBER of the dimension table, as a bit-sliced
+    attribute; dim_groups: an integer device tensor with the group of every dimension row; dim_keep: a bool device tensor, the
+    dimension rows the dimension's filter keeps, or None: all.  The lookup is built on the device -- dim_groups where dim_keep,
+    else GROUP_BY_DROP -- and group_by_column does the rest: fact rows whose dimension row is filtered out, or lies behind the
+    dimension table, are in "other".  n_buckets defaults to the largest group + 1 (read back).  Returns group_by_column's dict."""
+    import torch
+
+    groups = dim_groups.reshape(-1).to(torch.int64)
+    if n_buckets is None:
+        n_buckets = int(groups.max().item()) + 1 if groups.numel() else 1
+    if dim_keep is not None:
+        groups = torch.where(dim_keep.reshape(-1), groups, torch.full_like(groups, GROUP_BY_DROP))
+    return group_by_column(wah, fk, n_rows, attributes=attributes, where=where, lookup=groups, n_buckets=n_buckets)
+
+
+def count_distinct_where(wah, key, n_rows, where=None):
+    """`SELECT COUNT(DISTINCT key) WHERE <where>` over a bit-sliced key of up to 32 bits: the buckets of group_by_column that are
+    not empty, counted on the device ("other" holds nothing without a lookup).  Returns an int64 device scalar."""
+    return (group_by_column(wah, key, n_rows, where=where)["rows"] != 0).sum()
+
+
 def extremes_by(wah, keys, bsi, n_words_per_column, where=None):
     """`SELECT g, h, MIN(value), MAX(value) WHERE <where> GROUP BY g, h` as plumbing over wah_bsi_kth_indexed_device, which ANDs
     its filter rows itself: per group TWO quantile calls (0/1 and 1/1) whose filters are the `where` rows, the group's own rows

@@ -1685,6 +1685,60 @@ int wah_values_indexed_device(unsigned mode, uint64_t n_words, uint64_t n_operan
 
 int wah_values_status(void *d_scratch, void *stream) { return scratch_status(d_scratch, stream); }
 
+// COUNT and SUM per value of a bit-sliced key (wah_group_by.hip, group_by_items_kernel).  The scratch is the control block: the
+// items are segments (and halves), known here.  The map, the tables and the outputs stay in device memory: nothing here reads them.
+size_t wah_bsi_group_by_scratch_bytes(uint64_t) { return round256(wah::kCtlWords * sizeof(uint32_t)); }
+
+int wah_bsi_group_by_indexed_device(uint64_t n_words, uint64_t n_rows, uint64_t n_filters, const wah_bitop_operand *d_filters,
+                                    uint64_t n_slices_key, const wah_bitop_operand *d_key, uint64_t n_slices_val,
+                                    const wah_bitop_operand *d_val, const uint32_t *d_map, uint64_t n_keys, uint64_t n_buckets,
+                                    unsigned flags, uint64_t *d_counts, uint64_t *d_sums, void *d_scratch, size_t scratch_bytes,
+                                    void *stream) {
+    g_err[0] = 0;
+    if (n_slices_key < 1 || n_slices_key > 32 || n_slices_val > 32 || (flags & ~(WAH_BSI_EXISTS | WAH_GROUP_BY_ACCUMULATE)) ||
+        n_filters > wah::kGroupMaxFilters)
+        return refuse("a key of 1 to 32 slices, a value of at most 32, no flag besides WAH_BSI_EXISTS and WAH_GROUP_BY_ACCUMULATE, at most 64 filter rows", WAH_ERR_ARG);
+    if (!d_key || !aligned(d_key, 7) || !scratch_ok(d_scratch) || (n_slices_val != 0) != (d_val != nullptr) || !aligned(d_val, 7) ||
+        (n_filters && !d_filters) || !aligned(d_filters, 7))
+        return refuse("null or misaligned key table or scratch, a value table that does not go with n_slices_val, or a null or misaligned filter table", WAH_ERR_ARG);
+    if ((n_keys != 0) != (d_map != nullptr) || !aligned(d_map, 3) || n_keys > (1ull << 32))
+        return refuse("a 4-byte aligned map of 1 to 2^32 keys, or neither a map nor keys", WAH_ERR_ARG);
+    if (n_buckets < 1 || n_buckets > WAH_GROUP_BY_MAX_BUCKETS || !d_counts || !aligned(d_counts, 7) ||
+        (n_slices_val != 0) != (d_sums != nullptr) || !aligned(d_sums, 7))
+        return refuse("between 1 and 2^30 buckets, null or misaligned counts, or sums that do not go with n_slices_val", WAH_ERR_ARG);
+    if (n_words >= (1ull << 40) || n_rows > 32 * n_words) return refuse("2^40 words or more, or more rows than the bitmap's 32 n_words", WAH_ERR_ARG);
+    if (scratch_bytes < wah_bsi_group_by_scratch_bytes(n_words)) return refuse("scratch too small", WAH_ERR_WORKSPACE);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const SegGeometry g = seg_geometry(n_words);
+    wah::GroupByArgs a = {};
+    a.filters = reinterpret_cast<const wah::BitopListOperand *>(d_filters);
+    a.key = reinterpret_cast<const wah::BitopListOperand *>(d_key);
+    a.val = reinterpret_cast<const wah::BitopListOperand *>(d_val);
+    a.map = d_map;
+    a.counts = d_counts;
+    a.sums = d_sums;
+    a.ctrl = static_cast<uint32_t *>(d_scratch);
+    a.n_rows = n_rows;
+    a.groups = g.groups;
+    a.n_items = g.n_segments * (n_slices_val ? 2u : 1u);
+    a.n_keys = n_keys;
+    a.n_buckets = (uint32_t)n_buckets;
+    a.n_filters = (uint32_t)n_filters;
+    a.n_slices_key = (uint32_t)n_slices_key;
+    a.n_slices_val = (uint32_t)n_slices_val;
+    a.has_exists = (flags & WAH_BSI_EXISTS) ? 1u : 0u;
+    hipError_t e = wah::launch_clear(d_scratch, wah::kCtlWords * sizeof(uint32_t), s); // the error word (read by wah_bsi_group_by_status)
+    if (!(flags & WAH_GROUP_BY_ACCUMULATE)) {
+        if (e == hipSuccess) e = wah::launch_clear(d_counts, (n_buckets + 1) * sizeof(uint64_t), s);
+        if (e == hipSuccess && d_sums) e = wah::launch_clear(d_sums, 2 * (n_buckets + 1) * sizeof(uint64_t), s);
+    }
+    if (e == hipSuccess) e = wah::launch_group_by(a, s);
+    if (e != hipSuccess) return refuse("group-by launch", WAH_ERR_HIP, e);
+    return WAH_OK;
+}
+
+int wah_bsi_group_by_status(void *d_scratch, void *stream) { return scratch_status(d_scratch, stream); }
+
 // Set bits counted and listed in the compressed domain (wah_select.hip).  The scratch: control block, then the positions
 // call's rank table (one u64 per segment + 1) and the two upper levels of its scan (one u64 per 4096 entries of the level
 // below) -- it goes with n_words / 992, not with the operands' number or their words.

@@ -420,6 +420,28 @@ struct MemberArgs {
 };
 hipError_t launch_member(const MemberArgs &a, hipStream_t s); // the list's check, then the items
 
+// wah_bsi_group_by_indexed_device (wah_group_by.hip): COUNT and SUM per value of a bit-sliced key.  filters: n_filters rows; key:
+// n_slices_key rows, most significant slice first, then the existence bitmap if has_exists; val: n_slices_val rows, most
+// significant first (0: count only, val and sums are nullptr).  map: n_keys u32, key -> bucket, or nullptr (n_keys is 0): the key
+// is the bucket.  counts: n_buckets + 1 u64, sums: as many (low, high) pairs, both added into; the last bucket is "other".  An item
+// is a segment, with a value attribute a segment and a half of its groups: n_items = n_segments x (n_slices_val ? 2 : 1).
+struct GroupByArgs {
+    const BitopListOperand *filters, *key, *val;
+    const uint32_t *map;
+    uint64_t *counts, *sums;
+    uint32_t *ctrl;
+    uint64_t n_rows;  // rows at or behind it are never selected; <= 32 n_words
+    uint64_t groups;  // G of the bitmap
+    uint64_t n_items;
+    uint64_t n_keys;  // 0 .. 2^32
+    uint32_t n_buckets;    // 1 .. 2^30
+    uint32_t n_filters;    // 0 .. kGroupMaxFilters
+    uint32_t n_slices_key; // 1 .. 32
+    uint32_t n_slices_val; // 0 .. 32
+    uint32_t has_exists;   // 0 or 1: one more key row
+};
+hipError_t launch_group_by(const GroupByArgs &a, hipStream_t s);
+
 // ... on operands of few words per segment: their runs merged in the compressed domain, one lane per segment
 // (wah_bitop_runs.hip): count pass, scan of the tile totals, write pass
 struct BitopRunsArgs {

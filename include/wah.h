@@ -903,6 +903,53 @@ int wah_positions_indexed_device(uint64_t n_words, const uint32_t *d_stream, uin
                                  size_t scratch_bytes, void *stream);
 int wah_select_status(void *d_scratch, void *stream);
 
+/* GROUP BY a BIT-SLICED key in ONE call -- `SELECT custkey, COUNT(*), SUM(revenue) WHERE <filters> GROUP BY custkey`, and with
+ * a lookup table in front of the add the star join's GROUP BY: `SELECT d.year, SUM(f.revenue) FROM f JOIN d ON f.datekey = d.key
+ * WHERE <d filter> GROUP BY d.year`.  The grouped calls above take one BITMAP per group; this one takes the grouping attribute
+ * as slices, so a key of a million values is one table of twenty rows.  No value column, no decoded filter, no row list is
+ * written.
+ *   SELECTION: a row p < n_rows is selected if it is set in every row of d_filters (0 <= n_filters <= WAH_GROUP_MAX_FILTERS;
+ *   d_filters may be NULL when there is none) and, with WAH_BSI_EXISTS in flags, in the key's existence bitmap, which is ONE more
+ *   row behind the key's slices in d_key.  n_rows <= 32 n_words; rows at or behind n_rows and pad bits are never counted.
+ *   KEY AND BUCKET: the key k of a selected row is the unsigned value of the key's n_slices_key slices (1 .. 32, most significant
+ *   first).  With d_map (n_keys uint32 in DEVICE memory, 4-byte aligned, 1 <= n_keys <= 2^32) the row's bucket is b = d_map[k]
+ *   when k < n_keys; without one (d_map NULL and n_keys == 0) b = k.  A row with k >= n_keys (with a map) or b >= n_buckets goes
+ *   to the bucket "other", index n_buckets.  Keys and map entries are data, never errors, and nothing is read behind n_keys: a
+ *   map entry of 0xFFFFFFFF drops a key, so a dimension's filter can ride in the map.
+ *   OUTPUTS: d_counts is n_buckets + 1 uint64, bucket b the number of selected rows that map to b; d_sums is 2 (n_buckets + 1)
+ *   uint64, per bucket the LOW then the HIGH word of the sum of the value attribute over those rows.  The value attribute is
+ *   n_slices_val slices (1 .. 32, most significant first) WITHOUT an existence row: rows outside an existence bitmap were stored
+ *   as 0 and add nothing.  n_slices_val == 0 is count only: d_val and d_sums must then be NULL.  The call clears both outputs
+ *   itself unless WAH_GROUP_BY_ACCUMULATE is set; with the flag it ADDS into what is there, the carry from the low sum word
+ *   going into the high one -- partitions of a table, or batches, land in one histogram.
+ * Tables are 8-byte aligned; windows into column matrices, capacities as lengths and the not-yet-checked output of an earlier
+ * call on the stream are allowed.  Tables and map are read by the device only: the call is asynchronous on `stream`, allocates
+ * nothing, never synchronises, and a captured graph replayed after the map or a table was overwritten in place answers the NEW
+ * query.  n_words == 0: all zeros, or under ACCUMULATE nothing added.  One launch of one workgroup per segment (two per segment
+ * with a value attribute: each walks the segment and owns half of its groups, so a value attribute doubles the operand reads)
+ * that folds the slices into one word per row in LDS and adds per row -- runs of equal consecutive buckets of a lane merged
+ * first -- into buckets in LDS while n_buckets + 1 <= 2048, else into the outputs with 64-bit atomics.
+ *   d_scratch: the control words only, 256-byte aligned, no initialisation:
+ *   wah_bsi_group_by_scratch_bytes(n_words) = 1024 for every n_words (a multiple of 256, never 0).
+ * Errors the host can see come back before any HIP call, in this order: (1) n_slices_key outside 1 .. 32, n_slices_val above 32,
+ * unknown flag bits, n_filters above the cap; (2) a null or misaligned key table or scratch, a value table that does not go
+ * with n_slices_val, a null filter table with n_filters > 0; (3) a map that does not go with n_keys or is misaligned, n_keys >
+ * 2^32; (4) n_buckets outside 1 .. WAH_GROUP_BY_MAX_BUCKETS, null or misaligned d_counts, a d_sums that does not go with
+ * n_slices_val; (5) n_words >= 2^40 or n_rows > 32 n_words -- all WAH_ERR_ARG; then too small a scratch: WAH_ERR_WORKSPACE.
+ * Everything only the device sees is reported by wah_bsi_group_by_status(), which synchronises the stream: WAH_ERR_STREAM for
+ * everything the list call refuses in an operand of any of the three tables.  EVERY row's every segment is walked and checked:
+ * the verdict depends neither on the data nor on which rows are selected.  A key of more than 32 slices is refused -- a dense
+ * array of buckets over such a domain does not exist: bucket its low slices, or group after a subtraction or a range. */
+#define WAH_GROUP_BY_ACCUMULATE 2u /* add into the outputs instead of clearing them first */
+#define WAH_GROUP_BY_MAX_BUCKETS (1u << 30)
+size_t wah_bsi_group_by_scratch_bytes(uint64_t n_words);
+int wah_bsi_group_by_indexed_device(uint64_t n_words, uint64_t n_rows, uint64_t n_filters, const wah_bitop_operand *d_filters,
+                                    uint64_t n_slices_key, const wah_bitop_operand *d_key, uint64_t n_slices_val,
+                                    const wah_bitop_operand *d_val, const uint32_t *d_map, uint64_t n_keys, uint64_t n_buckets,
+                                    unsigned flags, uint64_t *d_counts, uint64_t *d_sums, void *d_scratch, size_t scratch_bytes,
+                                    void *stream);
+int wah_bsi_group_by_status(void *d_scratch, void *stream);
+
 /* The order statistics PER GROUP in ONE call -- `SELECT g, h, MIN(x), MAX(x), median(x) WHERE <filter> GROUP BY g, h`: for every
  * group g and every query q the value of rank q among the rows that `filters AND group g's rows` select, over ONE bit-sliced
  * attribute.  It is wah_bsi_kth_indexed_device's radix select for L = n_groups * n_queries selects ("lanes") at once.
