@@ -86,6 +86,9 @@ from .api import (  # noqa: F401
     bsi_group_by_device,
     GROUP_BY_ACCUMULATE,
     GROUP_BY_MAX_BUCKETS,
+    bsi_map_device,
+    MAP_PARTIAL,
+    MAP_NULL,
     positions_device,
     from_positions_device,
     from_positions_max_words,

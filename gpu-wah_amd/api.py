@@ -102,6 +102,9 @@ ABI_SYMBOLS = {
     "wah_bsi_group_by_scratch_bytes": (_sz, [_u64]),
     "wah_bsi_group_by_indexed_device": (_int, [_u64, _u64, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _u64, ctypes.c_uint, _vp, _vp, _vp, _sz, _vp]),
     "wah_bsi_group_by_status": (_int, [_vp, _vp]),
+    "wah_bsi_map_scratch_bytes": (_sz, [_u64, _u64, ctypes.c_uint]),
+    "wah_bsi_map_indexed_device": (_int, [_u64, _u64, _u64, _vp, _vp, _u64, _u64, ctypes.c_uint, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
+    "wah_bsi_map_status": (_int, [_vp, _u64, _u64, ctypes.c_uint, _vp]),
     "wah_from_positions_max_words": (_u64, [_u64, _u64, _u64]),
     "wah_from_positions_scratch_bytes": (_sz, [_u64, _u64]),
     "wah_from_positions_device": (_int, [_u64, _u64, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
@@ -1198,6 +1201,49 @@ def bsi_group_by_device(key_table, n_words, n_rows, n_buckets, value_table=None,
                                                                   sums.data_ptr() if vs else None, *tail),
               lib().wah_bsi_group_by_status, scratch, check)
     return counts, sums
+
+
+MAP_PARTIAL = 2  # WAH_MAP_PARTIAL
+MAP_NULL = 0xFFFFFFFF  # WAH_MAP_NULL
+
+
+def bsi_map_device(key_table, n_words, n_rows, lookup, n_bits_out, exists=False, partial=False, scratch=None, out=None, out_offsets=None,
+                   check=True):
+    """A BIT-SLICED key pushed through a lookup table, the looked-up value as a NEW bit-sliced attribute, in one call and with
+    nothing read back (wah_bsi_map_indexed_device).  key_table: the key's 1 .. 32 slices, most significant first, and with
+    exists=True its existence bitmap as one more row behind them -- a list of (stream, seg_offsets) pairs or a ready [k, 3] table;
+    only the device reads it.  lookup: key -> value, a device tensor or a sequence of ints (converted as columns._lookup_tensor
+    does: the low 32 bits), at least one entry; MAP_NULL (0xFFFFFFFF, -1 as int32) is "no value", so 2^32 - 1 is not a storable
+    value.  n_bits_out: 1 .. 32, the result's slices; an entry with a bit at or above it is refused (WAH_ERR_STREAM).  A row has a
+    value when it lies in front of n_rows, exists in the key, its key lies inside the lookup and its entry is not MAP_NULL;
+    partial=False refuses (WAH_ERR_STREAM) an existing row in front of n_rows without one, partial=True stores it as 0 outside the
+    result's existence bitmap.  The result has an existence bitmap as its last slice exactly when exists or partial.  n_words:
+    the words of one slice, a multiple of 992.  Returns as bsi_build_device: (stream, seg_offsets), the slices' compress() streams
+    back to back, MOST significant first, and the rows_out * (n_words / 992) + 1 entries of their segment index; scratch / out /
+    out_offsets: reuse these tensors; check=False: only enqueue and return (out, count tensor, out_offsets) -- the caller reads
+    wah_bsi_map_status later."""
+    from .columns import _lookup_tensor
+
+    kt = _operand_table(key_table, "a key table")
+    dev = kt.device
+    lookup = _lookup_tensor(lookup, dev)
+    if not lookup.numel():
+        raise WahError("lookup: at least one key")
+    n, r, k_out = int(n_words), int(n_rows), int(n_bits_out)
+    ks = int(kt.shape[0]) - (1 if exists else 0)
+    if not (1 <= ks <= 32 and 1 <= k_out <= 32):
+        raise WahError("a key of 1 to 32 slices and a result of 1 to 32")
+    if n <= 0 or n % 992:
+        raise WahError("slices of a multiple of 992 words")
+    flags = (BSI_EXISTS if exists else 0) | (MAP_PARTIAL if partial else 0)
+    rows_out = k_out + (1 if flags else 0)
+    n_keys = int(lookup.numel())
+    # (the lookup converted here lives until the call is enqueued: the stream keeps its memory valid for the launches behind it)
+    return _compressed_streams(
+        "wah_bsi_map_indexed_device", "bsi_map", dev, rows_out * (n // 992) + 1, _ROWS_OUT_OFFSETS,
+        lambda: lib().wah_bsi_map_scratch_bytes(n, k_out, flags), lambda: max_compressed_words(rows_out * n),
+        lambda *tail: lib().wah_bsi_map_indexed_device(n, r, ks, kt.data_ptr(), lookup.data_ptr(), n_keys, k_out, flags, *tail),
+        lambda sc, sp: lib().wah_bsi_map_status(sc, n, k_out, flags, sp), scratch, out, out_offsets, check)
 
 
 def positions_device(stream, seg_offsets, n_words, first=0, limit=None, out=None, scratch=None, check=True):

@@ -2327,6 +2327,61 @@ int wah_bsi_mul_status(void *d_scratch, uint64_t n_words, uint64_t n_slices_a, u
     return wah_bsi_arith_status(d_scratch, n_words, n_slices_out, flags, stream);
 }
 
+// A bit-sliced key through a lookup table key -> value, as a new bit-sliced attribute (wah_map.hip, bsi_map_segments_kernel).  The
+// builder's scratch and its road: the kernel writes the result's decoded slice matrix, the compress passes run over it.  The map
+// and the key table stay in device memory: nothing here reads them.
+static_assert(WAH_MAP_PARTIAL != WAH_BSI_EXISTS, "a flag bit of its own");
+namespace {
+constexpr unsigned kMapFlags = WAH_BSI_EXISTS | WAH_MAP_PARTIAL;
+// the result's matrix rows: its slices, and the rows that have a value where either flag is set
+inline uint64_t map_rows_out(uint64_t n_slices_out, unsigned flags) { return n_slices_out + ((flags & kMapFlags) ? 1u : 0u); }
+} // namespace
+
+size_t wah_bsi_map_scratch_bytes(uint64_t n_words, uint64_t n_slices_out, unsigned flags) {
+    return bsi_build_layout(n_words, map_rows_out(n_slices_out, flags)).total;
+}
+
+int wah_bsi_map_indexed_device(uint64_t n_words, uint64_t n_rows, uint64_t n_slices_key, const wah_bitop_operand *d_key,
+                               const uint32_t *d_map, uint64_t n_keys, uint64_t n_slices_out, unsigned flags, uint32_t *d_out,
+                               uint64_t out_capacity_words, uint64_t *d_out_words, uint64_t *d_out_offsets, void *d_scratch,
+                               size_t scratch_bytes, void *stream) {
+    g_err[0] = 0;
+    if (n_slices_key < 1 || n_slices_key > 32 || n_slices_out < 1 || n_slices_out > 32 || (flags & ~kMapFlags))
+        return refuse("a key of 1 to 32 slices, a result of 1 to 32, no flag besides WAH_BSI_EXISTS and WAH_MAP_PARTIAL", WAH_ERR_ARG);
+    if (!d_key || !aligned(d_key, 7) || !scratch_ok(d_scratch) || !out_triple_ok(d_out, d_out_words, d_out_offsets))
+        return refuse("null or misaligned key table, scratch or output", WAH_ERR_ARG);
+    if (!d_map || !aligned(d_map, 3) || n_keys < 1 || n_keys > (1ull << 32)) return refuse("a 4-byte aligned map of 1 to 2^32 keys", WAH_ERR_ARG);
+    const uint64_t rows_out = map_rows_out(n_slices_out, flags);
+    if (n_words == 0 || n_words % wah::kSegWords || n_words >= (1ull << 40) || rows_out * n_words >= (1ull << 40) || n_rows > 32 * n_words)
+        return refuse("slices of a multiple of 992 words, all slices of the result together fewer than 2^40 words, at most 32 n_words rows", WAH_ERR_ARG);
+    const BsiBuildLayout l = bsi_build_layout(n_words, rows_out);
+    if (scratch_bytes < l.total) return refuse("scratch too small", WAH_ERR_WORKSPACE);
+    char *sc = static_cast<char *>(d_scratch);
+    const SegGeometry g = seg_geometry(n_words);
+    wah::BsiMapArgs a = {};
+    a.key = reinterpret_cast<const wah::BitopListOperand *>(d_key);
+    a.map = d_map;
+    a.matrix = bsi_matrix(sc, l);
+    a.ctrl = reinterpret_cast<uint32_t *>(sc);
+    a.n_rows = n_rows;
+    a.n_words = n_words;
+    a.groups = g.groups;
+    a.n_segments = g.n_segments;
+    a.n_keys = n_keys;
+    a.n_slices_key = (uint32_t)n_slices_key;
+    a.n_slices_out = (uint32_t)n_slices_out;
+    a.has_exists = (flags & WAH_BSI_EXISTS) ? 1u : 0u;
+    a.out_exists = (flags & kMapFlags) ? 1u : 0u;
+    a.partial = (flags & WAH_MAP_PARTIAL) ? 1u : 0u;
+    return sweep_then_compress(a, wah::launch_bsi_map, "map launch", n_words, rows_out, d_out, out_capacity_words, d_out_words, d_out_offsets, sc, l,
+                               stream);
+}
+
+int wah_bsi_map_status(void *d_scratch, uint64_t n_words, uint64_t n_slices_out, unsigned flags, void *stream) {
+    // (first the kernel: a bad key operand, a miss without WAH_MAP_PARTIAL, an entry too wide for the result)
+    return scratch_status_then(bsi_build_layout(n_words, map_rows_out(n_slices_out, flags)).ws_c, d_scratch, stream);
+}
+
 // ---------------------------------------------------------------------------
 // host-pointer entry points (the reference's API)
 // ---------------------------------------------------------------------------

@@ -18,11 +18,7 @@
 //            masked by n_words in the last block.  No LDS, no register array indexed by the slice.
 // Every word of every row is written, the zeros behind the last row up to n_words included: the matrix needs no clearing.  The
 // only atomic is the one OR into the sticky error word, by one lane of a wavefront that saw a value at or above 2^n_bits.
-#include "wah_device.hpp"
-
-// v_writelane_b32: `into` with lane `lane` replaced by the wave-uniform `value`.  This compiler has no builtin of that name, so
-// the LLVM intrinsic is named directly: the compiler still knows what it does and schedules around it.
-extern "C" __device__ int wah_writelane(int value, int lane, int into) __asm("llvm.amdgcn.writelane.i32");
+#include "wah_slice_words.hpp" // put_lane and slice_words: shared with wah_map.hip
 
 namespace wah {
 namespace {
@@ -31,20 +27,6 @@ constexpr u32 kBsiBuildWaves = 4;    // wavefronts of a workgroup (nothing is sh
 constexpr u32 kBsiBlockWords = 64;   // slice words per block: one per lane
 constexpr u32 kBsiBlockSteps = 32;   // loads of 64 rows per block
 constexpr u64 kBsiBlockRows = 2048;  // 32 * kBsiBlockWords
-
-__device__ __forceinline__ u32 put_lane(u32 value, u32 lane, u32 into) { return (u32)wah_writelane((int)value, (int)lane, (int)into); }
-
-// lane j: word j of the block's bitmap of "half & mask is not zero", half[t] of lane l belonging to row 64 t + l
-__device__ __forceinline__ u32 slice_words(const u32 (&half)[kBsiBlockSteps], u32 mask) {
-    u32 acc = 0u;
-#pragma unroll
-    for (u32 t = 0; t < kBsiBlockSteps; ++t) {
-        const u64 m = __ballot((half[t] & mask) != 0u);
-        acc = put_lane((u32)m, 2u * t, acc);
-        acc = put_lane((u32)(m >> 32), 2u * t + 1u, acc);
-    }
-    return acc;
-}
 
 template <bool kExists>
 __global__ __launch_bounds__(kBsiBuildWaves * 64, 4) void bsi_slices_kernel(const BsiBuildArgs a) {

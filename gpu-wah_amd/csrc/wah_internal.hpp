@@ -442,6 +442,27 @@ struct GroupByArgs {
 };
 hipError_t launch_group_by(const GroupByArgs &a, hipStream_t s);
 
+// wah_bsi_map_indexed_device (wah_map.hip): a bit-sliced key through a lookup table, as a new bit-sliced attribute.  key:
+// n_slices_key rows, most significant slice first, then the existence bitmap if has_exists.  map: n_keys u32, key -> value,
+// 0xFFFFFFFF: no value.  matrix: the decoded slice matrix [n_slices_out (+ 1 with out_exists), n_words] the kernel writes every
+// word of, most significant slice first, the rows that have a value last.  An item is a segment.
+struct BsiMapArgs {
+    const BitopListOperand *key;
+    const uint32_t *map;
+    uint32_t *matrix;
+    uint32_t *ctrl;
+    uint64_t n_rows;             // rows at or behind it never have a value; <= 32 n_words
+    uint64_t n_words;            // words of one slice, a multiple of kSegWords
+    uint64_t groups, n_segments; // of one slice
+    uint64_t n_keys;             // 1 .. 2^32
+    uint32_t n_slices_key;       // 1 .. 32
+    uint32_t n_slices_out;       // 1 .. 32
+    uint32_t has_exists;         // 0 or 1: one more key row
+    uint32_t out_exists;         // 0 or 1: one more matrix row
+    uint32_t partial;            // 0: a miss is refused; 1: a miss is a row without a value
+};
+hipError_t launch_bsi_map(const BsiMapArgs &a, hipStream_t s);
+
 // ... on operands of few words per segment: their runs merged in the compressed domain, one lane per segment
 // (wah_bitop_runs.hip): count pass, scan of the tile totals, write pass
 struct BitopRunsArgs {

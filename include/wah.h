@@ -950,6 +950,52 @@ int wah_bsi_group_by_indexed_device(uint64_t n_words, uint64_t n_rows, uint64_t 
                                     void *stream);
 int wah_bsi_group_by_status(void *d_scratch, void *stream);
 
+/* A BIT-SLICED key pushed through a lookup table in ONE call, the looked-up value leaving as a NEW bit-sliced attribute that
+ * every call here takes -- the star join's PROJECTION, `SELECT d.unit_price FROM f JOIN d ON f.fk = d.rowid` as an attribute of f
+ * (then compared, multiplied, ranked); a unary function of a small-domain key tabulated once (`EXTRACT(year FROM date_key)`,
+ * `price / 10`, a CASE, histogram bins); a dictionary recoding.  The group-by call above pushes a key through the same kind of
+ * table and leaves a histogram; this one leaves the column.  No value column is written and read again.
+ *   KEY: d_key is the key's table, n_slices_key rows (1 .. 32, most significant slice first); with WAH_BSI_EXISTS in flags the
+ *   key's existence bitmap follows as ONE more row.  n_rows <= 32 n_words.
+ *   MAP: d_map is n_keys uint32 in DEVICE memory (4-byte aligned, 1 <= n_keys <= 2^32), key -> value.  An entry of WAH_MAP_NULL
+ *   (0xFFFFFFFF) means "no value"; n_slices_out is 1 .. 32, so THE VALUE 2^32 - 1 IS NOT STORABLE: it is the null entry.
+ *   WHICH ROWS HAVE A VALUE: a row p has one when p < n_rows, p exists in the key, its key k < n_keys and d_map[k] is not
+ *   WAH_MAP_NULL; every other row is 0 in every result slice.  A MISS is an existing row in front of n_rows whose key is at or
+ *   behind n_keys or whose entry is WAH_MAP_NULL.  With WAH_MAP_PARTIAL in flags a miss is simply a row without a value -- a
+ *   dimension's filter rides in the map as null entries.  Without the flag a miss sets the sticky WAH_ERR_STREAM that
+ *   wah_bsi_map_status reports, as a value at or above 2^n_bits does in wah_bsi_build_device.  In both modes an entry other
+ *   than WAH_MAP_NULL with a bit at or above n_slices_out, loaded for a row, is WAH_ERR_STREAM.  Nothing is read at or behind
+ *   n_keys, and nothing is loaded for a row that is not selected.
+ *   RESULT: n_slices_out slices, most significant first, and an existence row as the LAST row exactly when
+ *   flags & (WAH_BSI_EXISTS | WAH_MAP_PARTIAL): the rows that have a value (rows at or behind n_rows never do).  d_out,
+ *   d_out_words and d_out_offsets receive exactly what wah_bsi_build_device leaves for the resulting value column: the
+ *   compress() of the result's slice matrix [rows_out, n_words] as ONE bitmap and its whole segment index, rows_out * (n_words /
+ *   992) + 1 entries, rows_out = n_slices_out (+ 1 with an existence row).
+ * n_words is a non-zero multiple of 992 below 2^40, and rows_out * n_words stays below 2^40, as in the arithmetic call.  The
+ * table and the map are read by the device only: the call is asynchronous on `stream`, allocates nothing, never synchronises and
+ * reads nothing back, and a captured graph replayed after the map or the table was overwritten in place computes the NEW
+ * attribute.  One launch of one workgroup per segment that folds the key's slices into one word per row in LDS, looks every
+ * selected row up with many loads in flight per lane and transposes the values in registers into slice words by ballots; then
+ * the compress passes.
+ *   d_scratch: the builder's layout, 256-byte aligned, no initialisation:
+ *   wah_bsi_map_scratch_bytes(n_words, n_slices_out, flags) = wah_bsi_build_scratch_bytes(n_words, rows_out).
+ * Errors the host can see come back before any HIP call, in this order: (1) n_slices_key or n_slices_out outside 1 .. 32,
+ * unknown flag bits; (2) a null or misaligned key table, scratch or output; (3) a null or misaligned map, n_keys outside 1 ..
+ * 2^32; (4) n_words 0, no multiple of 992 or >= 2^40, rows_out * n_words >= 2^40, n_rows > 32 n_words -- all WAH_ERR_ARG; then
+ * too small a scratch: WAH_ERR_WORKSPACE.  Everything only the device sees is reported by wah_bsi_map_status(), which
+ * synchronises the stream: WAH_ERR_STREAM for everything the list call refuses in a row of the key table, for a miss without
+ * WAH_MAP_PARTIAL and for an entry too wide for the result; then the compress passes' verdict (WAH_ERR_CAPACITY: nothing is
+ * written at or behind d_out[out_capacity_words]).  A miss in a row that does not exist, or at or behind n_rows, is no miss.  The
+ * output of a refused call is unspecified.  wah_bsi_map_status(NULL, ...): WAH_ERR_ARG. */
+#define WAH_MAP_PARTIAL 2u /* flags: a miss is a row without a value, and the result has an existence row */
+#define WAH_MAP_NULL 0xFFFFFFFFu /* a map entry without a value */
+size_t wah_bsi_map_scratch_bytes(uint64_t n_words, uint64_t n_slices_out, unsigned flags);
+int wah_bsi_map_indexed_device(uint64_t n_words, uint64_t n_rows, uint64_t n_slices_key, const wah_bitop_operand *d_key,
+                               const uint32_t *d_map, uint64_t n_keys, uint64_t n_slices_out, unsigned flags, uint32_t *d_out,
+                               uint64_t out_capacity_words, uint64_t *d_out_words, uint64_t *d_out_offsets, void *d_scratch,
+                               size_t scratch_bytes, void *stream);
+int wah_bsi_map_status(void *d_scratch, uint64_t n_words, uint64_t n_slices_out, unsigned flags, void *stream);
+
 /* The order statistics PER GROUP in ONE call -- `SELECT g, h, MIN(x), MAX(x), median(x) WHERE <filter> GROUP BY g, h`: for every
  * group g and every query q the value of rank q among the rows that `filters AND group g's rows` select, over ONE bit-sliced
  * attribute.  It is wah_bsi_kth_indexed_device's radix select for L = n_groups * n_queries selects ("lanes") at once.
