@@ -81,6 +81,9 @@ ABI_SYMBOLS = {
     "wah_bsi_mul_scratch_bytes": (_sz, [_u64, _u64, _u64, ctypes.c_uint]),
     "wah_bsi_mul_indexed_device": (_int, [_u64, _u64, _u64, _u64, _vp, ctypes.c_uint, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
     "wah_bsi_mul_status": (_int, [_vp, _u64, _u64, _u64, ctypes.c_uint, _vp]),
+    "wah_bsi_div_scratch_bytes": (_sz, [_u64, _u64, _u64, ctypes.c_uint]),
+    "wah_bsi_div_indexed_device": (_int, [_int, _u64, _u64, _u64, _u64, _vp, ctypes.c_uint, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
+    "wah_bsi_div_status": (_int, [_vp, _u64, _u64, _u64, ctypes.c_uint, _vp]),
     "wah_bsi_kth_scratch_bytes": (_sz, [_u64, _u64]),
     "wah_bsi_kth_indexed_device": (_int, [_u64, _u64, _u64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "wah_bsi_kth_status": (_int, [_vp, _vp]),
@@ -907,6 +910,46 @@ def bsi_mul_device(table, n_bits_a, n_bits_b, n_bits_out, n_words, exists_a=Fals
         lambda: lib().wah_bsi_mul_scratch_bytes(n, ka, k_out, flags), lambda: max_compressed_words(rows_out * n),
         lambda *tail: lib().wah_bsi_mul_indexed_device(n, ka, kb, k_out, table.data_ptr(), flags, *tail),
         lambda sc, sp: lib().wah_bsi_mul_status(sc, n, ka, k_out, flags, sp), scratch, out, out_offsets, check)
+
+
+DIV_QUOTIENT, DIV_REMAINDER = 0, 1  # WAH_DIV_*
+
+
+def bsi_div_row_order(ka, kb, exists_a=False, exists_b=False):
+    """The table order of wah_bsi_div_indexed_device for a dividend A of ka and a divisor B of kb slices, as a list of (attribute,
+    slice index) counted as in bsi_compare_row_order: 0 is an attribute's MOST significant slice, ka (kb) its existence bitmap.
+    A's existence row, then B's, come FIRST; then ALL of B's slices, LEAST significant first; then ALL of A's, MOST significant
+    first -- the divisor is whole before long division takes the dividend from the top.  Needs neither torch nor a device."""
+    ka, kb = int(ka), int(kb)
+    if not (1 <= ka <= BSI_MAX_SLICES and 1 <= kb <= BSI_MAX_SLICES):
+        raise WahError("between 1 and 64 slices per attribute")
+    order = []
+    if exists_a:
+        order.append(("a", ka))
+    if exists_b:
+        order.append(("b", kb))
+    order += [("b", kb - 1 - sig) for sig in range(kb)]
+    order += [("a", i) for i in range(ka)]
+    return order
+
+
+def bsi_div_device(table, n_bits_a, n_bits_b, n_bits_out, n_words, remainder=False, exists_a=False, exists_b=False, scratch=None,
+                   out=None, out_offsets=None, check=True):
+    """The bit-sliced index of floor(A / B) mod 2^n_bits_out -- with remainder=True of (A mod B) mod 2^n_bits_out -- row by row
+    over two bit-sliced attributes, in one call (wah_bsi_div_indexed_device).  table: a list of (stream, seg_offsets) pairs or a
+    ready [rows, 3] table in the order of bsi_div_row_order(n_bits_a, n_bits_b, exists_a, exists_b) -- only the device reads it.
+    Both values are read as unsigned.  n_bits_out: 1 .. 64; n_bits_a loses nothing of the quotient, min(n_bits_a, n_bits_b)
+    nothing of the remainder, fewer truncate, more zero-extend.  The result ALWAYS has an existence bitmap as its last slice:
+    the AND of the operands' bitmaps that are there and of B != 0 -- a division by zero is NULL.  n_words, the result and
+    scratch / out / out_offsets / check: as bsi_mul_device with n_bits_out + 1 rows -- with check=False the caller reads
+    wah_bsi_div_status later."""
+    table, ka, kb, k_out, n, flags, _ = _two_attributes(table, n_bits_a, n_bits_b, n_bits_out, n_words, exists_a, exists_b)
+    what, rows_out = (DIV_REMAINDER if remainder else DIV_QUOTIENT), k_out + 1
+    return _compressed_streams(
+        "wah_bsi_div_indexed_device", "bsi_div", table.device, rows_out * (n // 992) + 1, _ROWS_OUT_OFFSETS,
+        lambda: lib().wah_bsi_div_scratch_bytes(n, kb, k_out, flags), lambda: max_compressed_words(rows_out * n),
+        lambda *tail: lib().wah_bsi_div_indexed_device(what, n, ka, kb, k_out, table.data_ptr(), flags, *tail),
+        lambda sc, sp: lib().wah_bsi_div_status(sc, n, kb, k_out, flags, sp), scratch, out, out_offsets, check)
 
 
 BSI_KTH_ASCENDING, BSI_KTH_DESCENDING, BSI_KTH_QUANTILE = 0, 1, 2  # WAH_BSI_KTH_*

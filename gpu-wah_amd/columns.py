@@ -596,6 +596,62 @@ def multiply_columns(wah, bsi_a, bsi_b, n_bits=None, table=None, **reuse):
     return out[: int(count.item())], out_offsets, n, n_bits, has_exists
 
 
+def _div_columns(wah, remainder, bsi_a, bsi_b, n_bits, table, reuse):
+    """divide_columns / modulo_columns: one wah_bsi_div_indexed_device call over two bsi_from_values results, operands as given."""
+    import torch
+
+    from . import api
+
+    _, _, n, ka, has_a = bsi_a
+    _, _, n_b, kb, has_b = bsi_b
+    if n != n_b:
+        raise ValueError("the two attributes have different column lengths")
+    n_bits = (min(ka, kb) if remainder else ka) if n_bits is None else int(n_bits)
+    if not 1 <= n_bits <= 64:
+        raise ValueError("between 1 and 64 bits")
+    table = _two_attribute_table(wah.bsi_div_row_order(ka, kb, has_a, has_b), bsi_a, bsi_b, table)
+    flags = (wah.BSI_EXISTS_A if has_a else 0) | (wah.BSI_EXISTS_B if has_b else 0)
+    check = reuse.pop("check", True)
+    if reuse.get("scratch") is None:
+        reuse["scratch"] = torch.empty(int(wah.lib().wah_bsi_div_scratch_bytes(n, kb, n_bits, flags)), dtype=torch.uint8, device=table.device)
+    out, count, out_offsets = wah.bsi_div_device(table, ka, kb, n_bits, n, remainder=remainder, exists_a=has_a, exists_b=has_b, check=False, **reuse)
+    if not check:
+        return out, out_offsets, n, n_bits, True
+    api._check(wah.lib().wah_bsi_div_status(reuse["scratch"].data_ptr(), n, kb, n_bits, flags, api._stream_ptr(torch)), "bsi_div")
+    return out[: int(count.item())], out_offsets, n, n_bits, True
+
+
+def divide_columns(wah, bsi_a, bsi_b, n_bits=None, table=None, **reuse):
+    """`A / B` row by row over TWO bit-sliced attributes in one call, as a NEW bit-sliced attribute (wah_bsi_div_indexed_device):
+    arguments and result as add_columns.  The result holds floor(A / B) mod 2^n_bits, both values read as unsigned; n_bits
+    defaults to ka, which loses nothing.  A division by zero is NULL: the result ALWAYS has an existence bitmap (has_exists is
+    True), the AND of those the operands have and of B != 0, and a row outside it is stored as 0.  The operands are taken as
+    given.  The table puts the existence rows first, then all of B's slices, least significant first, then all of A's, most
+    significant first (api.bsi_div_row_order); a table passed in is overwritten in that order."""
+    return _div_columns(wah, False, bsi_a, bsi_b, n_bits, table, reuse)
+
+
+def modulo_columns(wah, bsi_a, bsi_b, n_bits=None, table=None, **reuse):
+    """`A % B` row by row, arguments and result as divide_columns.  The result holds (A mod B) mod 2^n_bits; n_bits defaults to
+    min(ka, kb), which loses nothing.  Its existence bitmap is that of the quotient, so A == Q * B + R holds in exactly the rows
+    both have."""
+    return _div_columns(wah, True, bsi_a, bsi_b, n_bits, table, reuse)
+
+
+def divide_column_by(wah, bsi, c, remainder=False, n_bits=None):
+    """`value / c`, or with remainder=True `value % c`, for a Python int 1 <= c < 2^63: divide_columns / modulo_columns by a
+    constant attribute of c.bit_length() slices built with bsi_from_values from a full column -- each of its slices is one fill
+    per segment.  Result as divide_columns; ValueError for c < 1."""
+    import torch
+
+    c = int(c)
+    if not 1 <= c < (1 << 63):
+        raise ValueError("a divisor between 1 and 2^63 - 1")
+    n = bsi[2]
+    constant = bsi_from_values(wah, torch.full((32 * n,), c, dtype=torch.int64, device=bsi[0].device), c.bit_length(), n_words_per_column=n)
+    return (modulo_columns if remainder else divide_columns)(wah, bsi, constant, n_bits=n_bits)
+
+
 def sum_product_where(wah, bsi_a, bsi_b, mask_stream, mask_offsets):
     """`SELECT SUM(a * b) WHERE <mask>` over two bit-sliced attributes: multiply_columns with all ka + kb slices, then
     sum_column_where over the product.  Raises ValueError where ka + kb > 64: the product would be truncated.  Returns a

@@ -2235,19 +2235,21 @@ namespace {
 constexpr unsigned kArithFlags = WAH_BSI_EXISTS_A | WAH_BSI_EXISTS_B;
 // the result's matrix rows: its slices, and the AND of the existence bitmaps where there is one
 inline uint64_t arith_rows_out(uint64_t n_slices_out, unsigned flags) { return n_slices_out + ((flags & kArithFlags) ? 1u : 0u); }
-// the argument checks of the calls that compute a new attribute from two (arithmetic, multiplication): WAH_OK or the refusal
-int two_attribute_args(uint64_t n_words, uint64_t n_slices_a, uint64_t n_slices_b, uint64_t n_slices_out, const wah_bitop_operand *d_rows,
-                       unsigned flags, const uint32_t *d_out, const uint64_t *d_out_words, const uint64_t *d_out_offsets, const void *d_scratch) {
+// the argument checks of the calls that compute a new attribute from two (arithmetic, multiplication, division): WAH_OK or the
+// refusal.  rows_out: the result's matrix rows as the call counts them
+int two_attribute_args(uint64_t n_words, uint64_t n_slices_a, uint64_t n_slices_b, uint64_t n_slices_out, uint64_t rows_out,
+                       const wah_bitop_operand *d_rows, unsigned flags, const uint32_t *d_out, const uint64_t *d_out_words,
+                       const uint64_t *d_out_offsets, const void *d_scratch) {
     if (n_slices_a < 1 || n_slices_a > WAH_BSI_MAX_SLICES || n_slices_b < 1 || n_slices_b > WAH_BSI_MAX_SLICES || n_slices_out < 1 ||
         n_slices_out > WAH_BSI_MAX_SLICES || (flags & ~kArithFlags))
         return refuse("between 1 and 64 slices per attribute and in the result, no flag besides WAH_BSI_EXISTS_A and WAH_BSI_EXISTS_B", WAH_ERR_ARG);
-    if (n_words == 0 || n_words % wah::kSegWords || n_words >= (1ull << 40) || arith_rows_out(n_slices_out, flags) * n_words >= (1ull << 40))
+    if (n_words == 0 || n_words % wah::kSegWords || n_words >= (1ull << 40) || rows_out * n_words >= (1ull << 40))
         return refuse("slices of a multiple of 992 words, all slices of the result together fewer than 2^40 words", WAH_ERR_ARG);
     if (!d_rows || !aligned(d_rows, 7) || !scratch_ok(d_scratch)) return refuse("null or misaligned row table or scratch", WAH_ERR_ARG);
     if (!out_triple_ok(d_out, d_out_words, d_out_offsets)) return refuse("null or misaligned output", WAH_ERR_ARG);
     return WAH_OK;
 }
-// ... and what the arguments of both sweeps hold
+// ... and what the arguments of the three sweeps hold
 extern "C++" template <class Args>
 void two_attribute_fill(Args &a, uint64_t n_words, uint64_t n_slices_a, uint64_t n_slices_b, uint64_t n_slices_out, const wah_bitop_operand *d_rows,
                         unsigned flags, char *sc, const BsiBuildLayout &l) {
@@ -2274,9 +2276,9 @@ int wah_bsi_arith_indexed_device(int op, uint64_t n_words, uint64_t n_slices_a, 
                                  uint64_t *d_out_words, uint64_t *d_out_offsets, void *d_scratch, size_t scratch_bytes, void *stream) {
     g_err[0] = 0;
     if (op != WAH_ARITH_ADD && op != WAH_ARITH_SUB) return refuse("unknown arithmetic operation", WAH_ERR_ARG);
-    if (const int rc = two_attribute_args(n_words, n_slices_a, n_slices_b, n_slices_out, d_rows, flags, d_out, d_out_words, d_out_offsets, d_scratch))
-        return rc;
     const uint64_t rows_out = arith_rows_out(n_slices_out, flags);
+    if (const int rc = two_attribute_args(n_words, n_slices_a, n_slices_b, n_slices_out, rows_out, d_rows, flags, d_out, d_out_words, d_out_offsets, d_scratch))
+        return rc;
     const BsiBuildLayout l = bsi_build_layout(n_words, rows_out);
     if (scratch_bytes < l.total) return refuse("scratch too small", WAH_ERR_WORKSPACE);
     char *sc = static_cast<char *>(d_scratch);
@@ -2309,9 +2311,9 @@ int wah_bsi_mul_indexed_device(uint64_t n_words, uint64_t n_slices_a, uint64_t n
                                const wah_bitop_operand *d_rows, unsigned flags, uint32_t *d_out, uint64_t out_capacity_words,
                                uint64_t *d_out_words, uint64_t *d_out_offsets, void *d_scratch, size_t scratch_bytes, void *stream) {
     g_err[0] = 0;
-    if (const int rc = two_attribute_args(n_words, n_slices_a, n_slices_b, n_slices_out, d_rows, flags, d_out, d_out_words, d_out_offsets, d_scratch))
-        return rc;
     const uint64_t rows_out = arith_rows_out(n_slices_out, flags);
+    if (const int rc = two_attribute_args(n_words, n_slices_a, n_slices_b, n_slices_out, rows_out, d_rows, flags, d_out, d_out_words, d_out_offsets, d_scratch))
+        return rc;
     const BsiBuildLayout l = bsi_build_layout(n_words, rows_out);
     if (scratch_bytes < l.total + mul_work_bytes(n_words, n_slices_a, n_slices_out)) return refuse("scratch too small", WAH_ERR_WORKSPACE);
     char *sc = static_cast<char *>(d_scratch);
@@ -2325,6 +2327,47 @@ int wah_bsi_mul_indexed_device(uint64_t n_words, uint64_t n_slices_a, uint64_t n
 int wah_bsi_mul_status(void *d_scratch, uint64_t n_words, uint64_t n_slices_a, uint64_t n_slices_out, unsigned flags, void *stream) {
     (void)n_slices_a; // (the working area lies behind everything the status reads)
     return wah_bsi_arith_status(d_scratch, n_words, n_slices_out, flags, stream);
+}
+
+// floor(A / B), A mod B row by row over two bit-sliced attributes, as a new one (wah_bitop_list.hip, bsi_div_segments_kernel).
+// The arithmetic call's scratch and road for n_slices_out + 1 rows -- the existence row, which holds B != 0, is always there --
+// and behind them the sweep's working area: per segment B's image and two remainder buffers of n_slices_b + 1 slices in group
+// form, which needs no initialisation.
+static_assert(WAH_DIV_QUOTIENT == wah::kDivQuotient && WAH_DIV_REMAINDER == wah::kDivRemainder, "the results the sweep knows");
+namespace {
+inline size_t div_work_bytes(uint64_t n_words, uint64_t n_slices_b) {
+    return (size_t)(n_words / wah::kSegWords) * (size_t)(3u * n_slices_b + 2u) * wah::kSegGroups * sizeof(uint32_t);
+}
+} // namespace
+
+size_t wah_bsi_div_scratch_bytes(uint64_t n_words, uint64_t n_slices_b, uint64_t n_slices_out, unsigned flags) {
+    (void)flags; // (the result has its existence row whatever the flags)
+    return bsi_build_layout(n_words, n_slices_out + 1u).total + div_work_bytes(n_words, n_slices_b);
+}
+
+int wah_bsi_div_indexed_device(int what, uint64_t n_words, uint64_t n_slices_a, uint64_t n_slices_b, uint64_t n_slices_out,
+                               const wah_bitop_operand *d_rows, unsigned flags, uint32_t *d_out, uint64_t out_capacity_words,
+                               uint64_t *d_out_words, uint64_t *d_out_offsets, void *d_scratch, size_t scratch_bytes, void *stream) {
+    g_err[0] = 0;
+    if (what != WAH_DIV_QUOTIENT && what != WAH_DIV_REMAINDER) return refuse("unknown division result", WAH_ERR_ARG);
+    const uint64_t rows_out = n_slices_out + 1u;
+    if (const int rc = two_attribute_args(n_words, n_slices_a, n_slices_b, n_slices_out, rows_out, d_rows, flags, d_out, d_out_words, d_out_offsets, d_scratch))
+        return rc;
+    const BsiBuildLayout l = bsi_build_layout(n_words, rows_out);
+    if (scratch_bytes < l.total + div_work_bytes(n_words, n_slices_b)) return refuse("scratch too small", WAH_ERR_WORKSPACE);
+    char *sc = static_cast<char *>(d_scratch);
+    wah::BsiDivArgs a = {};
+    two_attribute_fill(a, n_words, n_slices_a, n_slices_b, n_slices_out, d_rows, flags, sc, l);
+    a.work = reinterpret_cast<uint32_t *>(sc + l.total); // (a multiple of 256 bytes: the quads are aligned)
+    a.remainder = what == WAH_DIV_REMAINDER ? 1u : 0u;
+    return sweep_then_compress(a, wah::launch_bsi_div_segments, "division sweep launch", n_words, rows_out, d_out, out_capacity_words,
+                               d_out_words, d_out_offsets, sc, l, stream);
+}
+
+int wah_bsi_div_status(void *d_scratch, uint64_t n_words, uint64_t n_slices_b, uint64_t n_slices_out, unsigned flags, void *stream) {
+    (void)n_slices_b; // (the working area lies behind everything the status reads)
+    (void)flags;
+    return scratch_status_then(bsi_build_layout(n_words, n_slices_out + 1u).ws_c, d_scratch, stream);
 }
 
 // A bit-sliced key through a lookup table key -> value, as a new bit-sliced attribute (wah_map.hip, bsi_map_segments_kernel).  The

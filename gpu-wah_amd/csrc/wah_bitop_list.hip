@@ -8,6 +8,7 @@
 //   bsi_compare_segments_kernel    A op B row by row over two bit-sliced attributes (wah_bsi_compare_indexed_device)
 //   bsi_arith_segments_kernel      A + B, A - B row by row as a new bit-sliced attribute (wah_bsi_arith_indexed_device)
 //   bsi_mul_segments_kernel        A * B row by row as a new bit-sliced attribute (wah_bsi_mul_indexed_device)
+//   bsi_div_segments_kernel        A / B, A % B row by row as a new bit-sliced attribute (wah_bsi_div_indexed_device)
 //   bsi_kth_pass_kernel            one pass of the radix select over such an attribute (wah_bsi_kth_indexed_device)
 //   bsi_kth_group_pass_kernel      the same pass for every (group, query) pair of a GROUP BY at once (wah_bsi_kth_grouped_indexed_device)
 //   fetch_items_kernel             the values of listed rows, one wavefront per 64 listed rows of a segment (wah_fetch_indexed_device)
@@ -511,6 +512,186 @@ __global__ __launch_bounds__(kSegDecodeWaves * 64, kBsiWavesPerSimd) void bsi_mu
 #pragma unroll
         for (int s = 0; s < (int)kSteps; ++s) seg_store(st, s, ex[s]);
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// wah_bsi_div_indexed_device: floor(A / B) or A mod B row by row over two bit-sliced attributes of ka and kb slices, as a NEW
+// bit-sliced attribute of n_out slices -- restoring long division over the slices, the multiplication kernel's machine run the
+// other way.  The dividend is consumed from the top and the divisor has to be whole before the first quotient slice leaves, so
+// the table is: A's existence row, then B's, where they have one; then ALL of B's slices, LEAST significant first; then ALL of
+// A's, MOST significant first.  A row with B = 0 has no result: the existence row of the output, which is ALWAYS there, is the
+// AND of the bitmaps present and of (B != 0).
+//
+// The wave's own area of the scratch (BsiDivArgs.work), in the multiplication kernel's group form (quad 64 q + lane, a lane only
+// ever reads back what it wrote itself): kb slices of B's image, then R and T of kb + 1 slices each -- 3 kb + 2 slices of 4 KiB.
+// R is the remainder shifted up by one with the dividend's next bit below it, T = R - B, and which of the two is the remainder
+// is the quotient bit q: nobody moves anything, the next step blends while it reads.  The state beside the walk is ex (preset
+// to all ones) and, while B arrives, nz (the OR of B's slices, preset to zero).  The fold:
+//   an existence row      ex &= acc
+//   B's slice s           the image's groups leave into slice s of the wave's area;  nz |= acc;  at s = kb - 1:  ex &= nz
+//   A's slice i           Rn = the image's groups (the dividend's bit);  borrow = 0;  for s = 0 .. kb, with b = B_s (0 at s = kb):
+//                             Tn = Rn ^ b ^ borrow;  borrow = (~Rn & b) | (~(Rn ^ b) & borrow);
+//                             Re = q ? T[s] : R[s]  (s < kb: the remainder the step before left, read in front of the stores);
+//                             R[s] = Rn;  T[s] = Tn;  Rn = Re  (the shift: slice s of the old remainder is slice s + 1 of R)
+//                         then q = ~borrow;  q & ex leaves as matrix row n_out - 1 - i of the quotient
+// The ripple runs over kb + 1 slices: the shifted remainder reaches 2^(kb + 1) - 1 where B's top slice is set.  Slice kb of the
+// remainder itself is always zero (it is below B), so nothing reads R[kb] or T[kb], and step kb needs only its borrow: it
+// stores neither.  q lives in the slot of T[kb]: the fold runs quarter by quarter in a loop, as the multiplication fold does,
+// and sixteen registers picked by the quarter's number would become an array in private memory (Makefile: asm -- with q
+// in registers the kernel spills, rolled or unrolled); a quarter reads its quad of q in front of its steps and writes it behind.
+// While every slice of A seen so far was all zero in this segment (wave-uniform: one ballot over the image; a settled row is
+// folded as the zeros it is) the remainder is still zero and every row that exists has B >= 1: the step stores a zero quotient
+// slice and touches nothing.  The first step that runs takes Re as zeros without reading the area -- which is why nothing needs
+// clearing, as j == 0 in the multiplication fold -- and from then on no zero slice is skipped: values far below their declared
+// width cost their real width.  So do divisors: B's slices above its last one that is not all zero in this segment (kb_run of
+// them remain, wave-uniform, known when B is complete) are zeros in every row, the remainder stays below 2^kb_run, and the
+// ripple of every step runs over kb_run + 1 slices instead of kb + 1.  Both skips are inside the fold: every row's every
+// segment is walked and checked whatever the data, the mode and n_out.  A quotient slice at or above n_out, and every one in
+// REMAINDER mode, is stored through a descriptor of no bytes.  In a quarter b, borrow, Rn, Re and the next step's b, R and T are one quad each, so the loads of step s + 1 are in
+// flight behind the stores of step s within the launch bound.
+// Behind the sweep: QUOTIENT zeros for the slices at and above ka; REMAINDER Re[sig] & ex for sig < min(kb, n_out) (zeros where
+// no step ran) and zeros above; then the ex row.  Every word of the matrix is written by exactly one wave.  A wave that refuses
+// something reports and stores nothing more.
+__global__ __launch_bounds__(kSegDecodeWaves * 64, kBsiWavesPerSimd) void bsi_div_segments_kernel(const BsiDivArgs a) {
+    __shared__ __attribute__((aligned(16))) u32 s_acc[kSegDecodeWaves][kSegGroups];
+    const u32 wave = wave_id(), lane = lane_id();
+    WaveSegment w;
+    if (!wave_segment(w, 0ull, a.n_segments, a.groups, wave)) return;
+    u32 *acc = s_acc[wave];
+    image_fill(acc, 0u, lane);
+
+    const u32 ka = a.n_slices_a, kb = a.n_slices_b, n_out = a.n_slices_out;
+    const u32 n_ex = a.exists_a + a.exists_b, n_rows = n_ex + kb + ka;
+    const bool quotient = a.remainder == 0u;
+    // (wave-uniform) quad 0 of B's slice 0, of R[0] and of T[0]; the lane's quad of quarter qd is 64 qd + lane behind them
+    MulQuad *const divisor = reinterpret_cast<MulQuad *>(a.work) + w.k * (u64)(3u * kb + 2u) * kSliceQuads;
+    MulQuad *const rem = divisor + (u64)kb * kSliceQuads;
+    MulQuad *const tri = rem + (u64)(kb + 1u) * kSliceQuads;
+    // the lane's quad of quarter qd of slice s behind one of them
+    auto quad = [&](MulQuad *base, u32 s, u32 qd) -> MulQuad & { return base[(u64)s * kSliceQuads + 64u * qd + lane]; };
+
+    // matrix row `row` of this wave's segment; live == false: a descriptor of no bytes, every store through it is dropped
+    auto row_store = [&](u32 row, bool live) {
+        return seg_store_setup(a.matrix + (u64)row * a.n_words, live ? a.n_words : 0ull, w.seg, w.k, lane);
+    };
+
+    u32 ex[kSteps], nz[kSteps]; // group 64 s + lane
+#pragma unroll
+    for (int s = 0; s < (int)kSteps; ++s) {
+        ex[s] = kOnes31;
+        nz[s] = 0u;
+    }
+    bool started = false; // (wave-uniform) a slice of A that is not all zero has been seen: R and T hold a step's result
+    u32 kb_run = 1u;      // (wave-uniform) B's slices up to its last one that is not all zero in this segment, at least one
+    const bool ok = row_sweep(a.table, n_rows, n_rows, w, acc, lane, [&](u32 cur) {
+        if (cur < n_ex) {
+#pragma unroll
+            for (int s = 0; s < (int)kSteps; ++s) ex[s] &= acc[64 * s + (int)lane];
+            return;
+        }
+        const u32 r = cur - n_ex;
+        if (r < kb) { // B's slice r
+            u32 any = 0u;
+#pragma unroll
+            for (int qd = 0; qd < 4; ++qd) {
+                MulQuad v;
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    v[t] = acc[64 * (4 * qd + t) + (int)lane];
+                    nz[4 * qd + t] |= v[t];
+                    any |= v[t];
+                }
+                quad(divisor, r, (u32)qd) = v;
+            }
+            if (__ballot(any != 0u) != 0ull) kb_run = r + 1u;
+            if (r + 1u == kb) {
+#pragma unroll
+                for (int s = 0; s < (int)kSteps; ++s) ex[s] &= nz[s];
+            }
+            return;
+        }
+        // A's slice i
+        const u32 i = ka - 1u - (r - kb);
+        const bool live = quotient && i < n_out;
+        const SegStore st = row_store(live ? n_out - 1u - i : 0u, live);
+        const bool first = !started;
+        if (first) {
+            u32 any = 0u;
+#pragma unroll
+            for (int s = 0; s < (int)kSteps; ++s) any |= acc[64 * s + (int)lane];
+            if (__ballot(any != 0u) == 0ull) { // the remainder is still zero: a zero quotient slice, nothing else
+#pragma unroll
+                for (int s = 0; s < (int)kSteps; ++s) seg_store(st, s, 0u);
+                return;
+            }
+            started = true;
+        }
+#pragma nounroll
+        for (u32 qd = 0; qd < 4u; ++qd) {
+            MulQuad rn;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) rn[t] = acc[64u * (4u * qd + (u32)t) + lane];
+            MulQuad qm = MulQuad(0u), re = MulQuad(0u); // re: Re[s], which becomes slice s + 1 of the next R
+            if (!first) {
+                qm = quad(tri, kb, qd);
+                re = (quad(tri, 0u, qd) & qm) | (quad(rem, 0u, qd) & ~qm);
+            }
+            MulQuad borrow = MulQuad(0u), b = quad(divisor, 0u, qd);
+#pragma nounroll
+            for (u32 s = 0; s < kb_run; ++s) {
+                MulQuad bn = MulQuad(0u), rx = MulQuad(0u), tx = MulQuad(0u);
+                if (s + 1u < kb_run) { // (wave-uniform) step s + 1's loads, in front of step s's stores
+                    bn = quad(divisor, s + 1u, qd);
+                    if (!first) {
+                        rx = quad(rem, s + 1u, qd);
+                        tx = quad(tri, s + 1u, qd);
+                    }
+                }
+                const MulQuad x = rn ^ b;
+                quad(rem, s, qd) = rn;
+                quad(tri, s, qd) = x ^ borrow;
+                borrow = (~rn & b) | (~x & borrow);
+                rn = re;
+                b = bn;
+                re = (tx & qm) | (rx & ~qm);
+            }
+            // the last step, where b = 0, stores nothing: the borrow goes on where that slice of R is clear, and q = ~borrow
+            quad(tri, kb, qd) = rn | ~borrow;
+        }
+#pragma unroll
+        for (int qd = 0; qd < 4; ++qd) {
+            const MulQuad qn = quad(tri, kb, (u32)qd);
+#pragma unroll
+            for (int t = 0; t < 4; ++t) seg_store(st, 4 * qd + t, qn[t] & ex[4 * qd + t]);
+        }
+    });
+    if (!ok) return report_stream_error(a.ctrl, lane);
+    if (quotient) { // at and above ka there is nothing but zeros
+#pragma nounroll
+        for (u32 sig = ka; sig < n_out; ++sig) {
+            const SegStore st = row_store(n_out - 1u - sig, true);
+#pragma unroll
+            for (int s = 0; s < (int)kSteps; ++s) seg_store(st, s, 0u);
+        }
+    } else { // the remainder the last step left, least significant first; at and above kb zeros
+        const u32 n_rem = started ? (kb_run < n_out ? kb_run : n_out) : 0u;
+        MulQuad qm[4];
+#pragma unroll
+        for (int qd = 0; qd < 4; ++qd) qm[qd] = started ? quad(tri, kb, (u32)qd) : MulQuad(0u);
+#pragma nounroll
+        for (u32 sig = 0; sig < n_out; ++sig) {
+            const SegStore st = row_store(n_out - 1u - sig, true);
+            MulQuad v[4];
+#pragma unroll
+            for (int qd = 0; qd < 4; ++qd)
+                v[qd] = sig < n_rem ? (quad(tri, sig, (u32)qd) & qm[qd]) | (quad(rem, sig, (u32)qd) & ~qm[qd]) : MulQuad(0u);
+#pragma unroll
+            for (int s = 0; s < (int)kSteps; ++s) seg_store(st, s, v[s / 4][s % 4] & ex[s]);
+        }
+    }
+    const SegStore st = row_store(n_out, true);
+#pragma unroll
+    for (int s = 0; s < (int)kSteps; ++s) seg_store(st, s, ex[s]);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -1091,6 +1272,7 @@ hipError_t launch_bsi_range_segments(const BsiRangeArgs &a, hipStream_t s) { ret
 hipError_t launch_bsi_compare_segments(const BsiCompareArgs &a, hipStream_t s) { return launch_per_segment(bsi_compare_segments_kernel, a.g.n_segments, a, s); }
 hipError_t launch_bsi_arith_segments(const BsiArithArgs &a, hipStream_t s) { return launch_per_segment(bsi_arith_segments_kernel, a.n_segments, a, s); }
 hipError_t launch_bsi_mul_segments(const BsiMulArgs &a, hipStream_t s) { return launch_per_segment(bsi_mul_segments_kernel, a.n_segments, a, s); }
+hipError_t launch_bsi_div_segments(const BsiDivArgs &a, hipStream_t s) { return launch_per_segment(bsi_div_segments_kernel, a.n_segments, a, s); }
 hipError_t launch_bsi_kth_pass(const BsiKthArgs &a, hipStream_t s) { return launch_per_segment(bsi_kth_pass_kernel, a.n_segments, a, s); }
 
 hipError_t launch_fetch_check(const FetchArgs &a, hipStream_t s) {

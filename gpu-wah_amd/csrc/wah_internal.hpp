@@ -299,6 +299,26 @@ struct BsiMulArgs {
 };
 hipError_t launch_bsi_mul_segments(const BsiMulArgs &a, hipStream_t s);
 
+// wah_bsi_div_indexed_device (wah_bitop_list.hip): floor(A / B) or A mod B row by row as a new bit-sliced attribute.  table: A's
+// existence bitmap if exists_a, then B's if exists_b, then ALL of B's slices, least significant first, then ALL of A's, MOST
+// significant first.  matrix: [n_slices_out + 1, n_words], the existence row -- the bitmaps present AND (B != 0) -- always there.
+// work: n_segments areas of (3 n_slices_b + 2) slices of kSegGroups groups each, a wave's own: B's image, then the two
+// remainder buffers of n_slices_b + 1 slices (the top slot of the second holds the last quotient slice); uninitialised
+constexpr uint32_t kDivQuotient = 0, kDivRemainder = 1; // WAH_DIV_*
+struct BsiDivArgs {
+    const BitopListOperand *table;
+    uint32_t *matrix;
+    uint32_t *work;
+    uint32_t *ctrl;
+    uint64_t n_words;                // words of one slice, a multiple of kSegWords
+    uint64_t groups, n_segments;     // of one slice
+    uint32_t n_slices_a, n_slices_b; // 1 .. 64 each
+    uint32_t n_slices_out;           // 1 .. 64
+    uint32_t exists_a, exists_b;     // 0 or 1: one more row each
+    uint32_t remainder;              // 0: the quotient, 1: the remainder
+};
+hipError_t launch_bsi_div_segments(const BsiDivArgs &a, hipStream_t s);
+
 // wah_bsi_kth_indexed_device (wah_bitop_list.hip): the value of a given rank among the rows the filters select -- a radix select
 // over the slices, kBsiKthDigitBits of them per pass, most significant digit first.  table: n_filters filter rows, then
 // n_slices slice rows, most significant first; query: kind, a, b in DEVICE memory; result: found, value, total, less, equal.

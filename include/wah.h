@@ -670,6 +670,58 @@ int wah_bsi_mul_indexed_device(uint64_t n_words, uint64_t n_slices_a, uint64_t n
                                uint64_t *d_out_words, uint64_t *d_out_offsets, void *d_scratch, size_t scratch_bytes, void *stream);
 int wah_bsi_mul_status(void *d_scratch, uint64_t n_words, uint64_t n_slices_a, uint64_t n_slices_out, unsigned flags, void *stream);
 
+/* `A / B` and `A % B` ROW BY ROW over TWO bit-sliced attributes in ONE call, as a NEW bit-sliced attribute -- `revenue / qty`,
+ * `elapsed / 60`, `id % 1024`, `ORDER BY clicks * 1000 / views DESC LIMIT k`, `WHERE a % b = 0`: restoring long division over
+ * the slices, most significant slice of the dividend first.  The result is an attribute like any other, as that of
+ * wah_bsi_mul_indexed_device, whose contract this one follows word for word except where stated here.  Not in the reference.
+ *   BOTH operands are read as UNSIGNED, n_slices_a and n_slices_b 1 .. 64 each, n_slices_out 1 .. 64 and the caller's choice.
+ *   what = WAH_DIV_QUOTIENT: floor(A / B) mod 2^n_slices_out -- n_slices_a slices lose nothing, fewer truncate, more zero-extend.
+ *   what = WAH_DIV_REMAINDER: (A mod B) mod 2^n_slices_out -- min(n_slices_a, n_slices_b) slices lose nothing.  One result per
+ *   call: a caller who wants both calls twice.
+ *   DIVISION BY ZERO IS NULL.  The result ALWAYS has an existence bitmap as the LAST row of its output, whatever the flags:
+ *   rows_out = n_slices_out + 1.  It is (A's existence bitmap with WAH_BSI_EXISTS_A) AND (B's with WAH_BSI_EXISTS_B) AND
+ *   (B != 0), and every output slice is ANDed with it: a row that does not exist is stored as value 0, as the builder stores it.
+ *   n_words is a multiple of 992, so the last group has no pad bits; rows of a column behind the caller's own row count hold
+ *   B = 0 and fall out by themselves.
+ *   d_rows: n_slices_a + n_slices_b rows, plus one for each flag, entries as for the list call.  TABLE ORDER: A's existence
+ *   bitmap with WAH_BSI_EXISTS_A; then B's with WAH_BSI_EXISTS_B; then ALL of B's slices, LEAST significant first; then ALL of A's
+ *   slices, MOST significant first.  B has to be complete, and with it the existence mask, before the first quotient slice
+ *   leaves, and long division consumes the dividend from the top.  (For 3 and 2 slices with both flags:
+ *   XA, XB, B0, B1, A2, A1, A0.)  Nothing else describes the table.
+ *   n_words, d_out, d_out_words, d_out_offsets, out_capacity_words: exactly those of wah_bsi_mul_indexed_device with THIS call's
+ *   rows_out -- slices MOST significant first, the existence bitmap last, rows_out * (n_words / 992) + 1 index entries, n_words
+ *   a non-zero multiple of 992 with rows_out * n_words < 2^40.
+ * Asynchronous on `stream`, allocates nothing, never synchronises; the table is read by the device only, so a captured graph
+ * replayed after the table was overwritten in place computes the NEW rows (what, the widths and the flags are host arguments
+ * and stay as captured).  One route: one wavefront per segment walks the table as the multiplication call does; the fold of a
+ * slice of B puts the segment's 1024 groups into the wave's own area of the scratch and ORs them into the mask B != 0; the
+ * fold of slice i of A shifts the remainder up by one with A_i below it (R) and subtracts B from it by one ripple borrow over
+ * n_slices_b + 1 slices (T); the quotient bit q is set where nothing is borrowed, and the next step reads the remainder as
+ * q ? T : R -- nothing is moved, nothing is cleared.  While every slice of A so far was all zero in a segment the step is
+ * skipped, and the slices of B above its last one that is not all zero in a segment are left out of every ripple there (values
+ * far below their declared width cost their real width), but every row is walked and checked like any other.
+ * Behind the sweep the one-launch compressor runs over the result's decoded slice matrix.
+ *   d_scratch: wah_bsi_div_scratch_bytes(n_words, n_slices_b, n_slices_out, flags) bytes, 256-byte aligned, no initialisation:
+ *       wah_bsi_build_scratch_bytes(n_words, n_slices_out + 1) + 4096 * (n_words / 992) * (3 * n_slices_b + 2),
+ *   that is 1024 + round256(4 * rows_out * n_words) + round256(wah_compress_workspace_bytes(rows_out * n_words)) and 4 KiB per
+ *   segment for each slice of B's image and of the two remainder buffers of n_slices_b + 1 slices.
+ * Errors the host can see come back before any HIP call, the argument checks first and in this order: an unknown `what`; a
+ * slice count (of A, of B or of the result) outside 1 .. 64 or unknown flag bits; n_words == 0, not a multiple of 992 or
+ * rows_out * n_words >= 2^40; a null or misaligned table (8 B) or scratch (256 B); a null or misaligned d_out (4 B), d_out_words
+ * or d_out_offsets (8 B): WAH_ERR_ARG; too small a scratch: WAH_ERR_WORKSPACE.  Everything only the device sees is reported by
+ * wah_bsi_div_status(), which synchronises the stream and reads the sweep's control words, then the compressor's:
+ * WAH_ERR_STREAM for everything the list call refuses in an operand, WAH_ERR_CAPACITY for too small an output (nothing is
+ * written at or behind d_out[out_capacity_words]).  EVERY row's every segment is walked and checked, so the verdict depends
+ * neither on the data, nor on `what`, nor on n_slices_out.  The output of a refused call is unspecified.
+ * wah_bsi_div_status(NULL, ...): WAH_ERR_ARG. */
+#define WAH_DIV_QUOTIENT 0
+#define WAH_DIV_REMAINDER 1
+size_t wah_bsi_div_scratch_bytes(uint64_t n_words, uint64_t n_slices_b, uint64_t n_slices_out, unsigned flags);
+int wah_bsi_div_indexed_device(int what, uint64_t n_words, uint64_t n_slices_a, uint64_t n_slices_b, uint64_t n_slices_out,
+                               const wah_bitop_operand *d_rows, unsigned flags, uint32_t *d_out, uint64_t out_capacity_words,
+                               uint64_t *d_out_words, uint64_t *d_out_offsets, void *d_scratch, size_t scratch_bytes, void *stream);
+int wah_bsi_div_status(void *d_scratch, uint64_t n_words, uint64_t n_slices_b, uint64_t n_slices_out, unsigned flags, void *stream);
+
 /* The ORDER statistics of a bit-sliced attribute in ONE call -- `MIN(price) WHERE ...`, MAX, the median or any percentile, the
  * k-th largest, the threshold of `ORDER BY price DESC LIMIT k`: the value of a given rank among the rows that a set of filter
  * bitmaps selects (O'Neil & Quass; Rinfret, O'Neil & O'Neil).  It is a radix select over the slices, most significant first, all
