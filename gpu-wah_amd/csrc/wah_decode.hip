@@ -83,18 +83,19 @@ struct SumScanPolicy {
 // groups in front of the tile; `end` = that + total, both saturating at 2^47 (overflow: reported by the caller as
 // WAH_ERR_STREAM).  kPublish = false: the caller has published the granule already (sums_publish) and sweeps LATE -- the
 // sweep of a tile that has other work to do first is the cheaper the later it goes out, as in compress_pair_kernel.
+// kDropPriority: the caller runs the scan at raised issue priority; a wave that has to wait drops to 0 first (row_scan_wait).
 __device__ __forceinline__ void sums_publish(u32 *gen_desc, u32 wt, u32 epoch, u64 total) {
     const ScanGeom g = scan_geom(wt);
     u64 *const my_row = reinterpret_cast<u64 *>(gen_desc + (u64)g.sup * kSumScanBlockWords) + (u64)(g.row - g.row0) * kRowTiles;
     __hip_atomic_store(my_row + g.idx, ((u64)epoch << kSlotShift) | total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-template <bool kPublish = true>
+template <bool kPublish = true, bool kDropPriority = false>
 __device__ __forceinline__ u64 sums_resolve(u32 *ctrl, u32 *gen_desc, u32 wt, u32 epoch, u64 total, u32 lane, u64 &end) {
     if (kPublish && lane == 0) sums_publish(gen_desc, wt, epoch, total);
     const ScanGeom g = scan_geom(wt);
     SumScanPolicy p = {g, gen_desc + (u64)g.sup * kSumScanBlockWords, epoch, total};
     p.issue(lane, true, g.has_prev, true);
-    row_scan_wait<0>(p, g, ctrl, epoch, lane);
+    row_scan_wait<0, kDropPriority>(p, g, ctrl, epoch, lane);
     const u64 base = sat_add(sat_add(p.sum_c, p.sum_b), p.sum_a);
     end = sat_add(base, total);
     if (lane == 0 && g.idx == kRowTiles - 1u && g.row - g.row0 == kSuperRows - 1u) // last tile of a superrow

@@ -152,6 +152,12 @@ __global__ __launch_bounds__(kDtWaves * 64, (kP <= 2 ? WAH_DT_MINW : 4)) void de
     // beside them the kernel would not fit the 80 registers that six waves per SIMD leave)
     __shared__ __attribute__((aligned(16))) u32 s_park[kP > 1 ? (kP - 1) * kDtWaveWords : 4];
 
+    // ISSUE PRIORITY (DESIGN 6.8).  A SIMD holds six waves of three workgroups of different ages, and at equal priority the oldest
+    // wave wins every issue slot.  The youngest workgroup is the one still loading, counting and publishing -- what every later batch
+    // of the launch waits for -- and it would lose to the older workgroups' expansion steps, which nothing waits for.  So every wave
+    // runs at priority 1 from here to the publication of the batch's total, and wave 0 again for its row scan until the batch's base
+    // is in LDS; everything else, and every wait (the epoch wrap's, row_scan_wait's), runs at 0.
+    __builtin_amdgcn_s_setprio(1);
     const u32 lane = lane_id();
     const u32 wave = wave_id();
 #ifdef WAH_DIAG
@@ -199,7 +205,10 @@ __global__ __launch_bounds__(kDtWaves * 64, (kP <= 2 ? WAH_DT_MINW : 4)) void de
     }
 
     // ---- decide: the launch epoch, from what was asked for in front of the ticket ------------------------------------------------
+    const bool wrap_wait = ask.stored >= kEpochWrap; // (scalar: draw_tile) the one launch in 65 535 whose tiles wait for tile 0 in there
+    if (wrap_wait) __builtin_amdgcn_s_setprio(0);
     const LaunchEpoch le = launch_epoch_begin(a.ctrl, ask, wt, a.n_wg_tiles, a.gen_desc, a.scan_words, 0);
+    if (wrap_wait) __builtin_amdgcn_s_setprio(1);
     if (le.bad) {
         if (blockIdx.x == 0 && threadIdx.x == 0) a.info[0] = a.info[1] = 0;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the batch's loads (bounded descriptors over the stream) are not left behind
@@ -300,6 +309,7 @@ __global__ __launch_bounds__(kDtWaves * 64, (kP <= 2 ? WAH_DT_MINW : 4)) void de
         }
     }
     if (WAH_DT_EARLY && wave == 0 && lane == 0) sums_publish(a.gen_desc, wt, epoch, batch_total);
+    __builtin_amdgcn_s_setprio(0); // published: from the flags on the workgroup is one of those that nothing waits for
 
     u64 base = 0; // groups in front of the batch (known after the first tile's flags are made)
 
@@ -379,14 +389,20 @@ __global__ __launch_bounds__(kDtWaves * 64, (kP <= 2 ? WAH_DT_MINW : 4)) void de
 #pragma unroll
                 for (int k = 0; k < 4; ++k) *reinterpret_cast<volatile u32x4 *>(s_park + ((t * 4u + k) * 64u + lane) * 4u) = hold[t][k];
             u64 end;
-            const u64 b = sums_resolve<!WAH_DT_EARLY>(a.ctrl, a.gen_desc, wt, epoch, batch_total, lane, end);
+            __builtin_amdgcn_s_setprio(1); // the seven other waves wait for this one (row_scan_wait drops it before it sleeps)
+            const u64 b = sums_resolve<!WAH_DT_EARLY, true>(a.ctrl, a.gen_desc, wt, epoch, batch_total, lane, end);
             DGT(4);
 #pragma unroll
             for (u32 t = 0; t + 1 < kP; ++t)
 #pragma unroll
                 for (int k = 0; k < 4; ++k) hold[t][k] = *reinterpret_cast<const volatile u32x4 *>(s_park + ((t * 4u + k) * 64u + lane) * 4u);
+            if (lane == 0) s_base = b;
+            __builtin_amdgcn_s_setprio(0);
+            // barrier 3, for wave 0 HERE: the other waves (theirs is below) go on into their first segments while lane 0 does the
+            // batch's bookkeeping, which no expansion needs.  (wave is a scalar: the branch is the whole wave's.)
+            __syncthreads();
+            DGT(5);
             if (lane == 0) {
-                s_base = b;
                 const u64 n_et = (a.c_words + kScanTileWords - 1) / kScanTileWords;
                 u64 bj = b;
                 u64 d_tile[2 * kP], d_groups[2 * kP]; // the expand tiles that go onto the list (bit set in d_valid): appended by ONE atomic below
@@ -480,9 +496,9 @@ __global__ __launch_bounds__(kDtWaves * 64, (kP <= 2 ? WAH_DT_MINW : 4)) void de
             asm volatile("" : "+v"(lc)); // (opaque: the address is made here, not hoisted to the kernel's top and kept -- or spilled)
             s_coarse[lc] = incl - cnt;
         }
-        __syncthreads();
+        if (!(wave == 0 && jj == 0)) __syncthreads(); // barrier 3 (wave 0, first time round: above, in front of its bookkeeping)
         if (jj == 0) {
-            DGT(5);
+            if (wave != 0) { DGT(5); } // (wave 0: at its own barrier 3)
             base = uniform64(s_base);
         }
         if (deferred[j]) continue;

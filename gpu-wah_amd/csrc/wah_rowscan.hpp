@@ -137,9 +137,14 @@ __device__ __forceinline__ void row_scan_timeout(u32 *ctrl, u32 lane) {
 // with the highest tile number, the one that will be published last (row a before row b before the slots), and sweeps again
 // when that one is there.
 // kDirectLanes: up to this many lanes with missing entries (the nearest ~64 predecessors) are read again at once; 0 = always
-// park.  Both compress scans take 16; the decoder's scan never had the direct re-read and keeps not having it (a deliberate
-// "as it was", not a measured choice).
-template <u32 kDirectLanes, class Policy>
+// park.  Both compress scans take 16; the decoder's scan takes 0, measured: decode_tile_kernel on the 1 GiB bitmaps with 0 / 16 /
+// 64 takes 0.3204 / 0.3208 / 0.3209 ms (sparse) and 0.4117 / 0.4115 / 0.4118 ms (dense), each +- 0.001 -- no difference, so it
+// keeps the shorter code (profiles/critical_path_priority_time.txt).
+// kDropPriority: the caller runs its scan at raised issue priority (s_setprio).  The first evaluation of the sweep
+// runs raised; as soon as something is missing the wave drops to priority 0 and stays there -- no s_sleep and no polling load is
+// ever issued at raised priority, where it would take issue slots from the waves it is waiting for.  The caller drops again
+// (a no-op then) once it has used the result.
+template <u32 kDirectLanes, bool kDropPriority = false, class Policy>
 __device__ __forceinline__ void row_scan_wait(Policy &p, const ScanGeom &g, u32 *ctrl, u32 epoch, u32 lane, u32 *polls = nullptr) {
     (void)polls; // (WAH_DIAG: sweeps issued beyond the first)
     bool need_a = true, need_b = g.has_prev, need_c = true;
@@ -173,6 +178,7 @@ __device__ __forceinline__ void row_scan_wait(Policy &p, const ScanGeom &g, u32 
         }
         if (!(need_a || need_b || need_c)) return;
         if (++spins > kMaxSpins) return row_scan_timeout(ctrl, lane);
+        if (kDropPriority) __builtin_amdgcn_s_setprio(0); // something is missing: from here on the wave only waits, and waits at priority 0
         if (kDirectLanes != 0u && (u32)__builtin_popcountll(ba) + (u32)__builtin_popcountll(bb) + (u32)__builtin_popcountll(bc) <= kDirectLanes) {
             __builtin_amdgcn_s_sleep(4);
         } else {
