@@ -108,6 +108,9 @@ ABI_SYMBOLS = {
     "wah_bsi_map_scratch_bytes": (_sz, [_u64, _u64, ctypes.c_uint]),
     "wah_bsi_map_indexed_device": (_int, [_u64, _u64, _u64, _vp, _vp, _u64, _u64, ctypes.c_uint, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
     "wah_bsi_map_status": (_int, [_vp, _u64, _u64, ctypes.c_uint, _vp]),
+    "wah_bsi_cumsum_scratch_bytes": (_sz, [_u64, _u64, ctypes.c_uint]),
+    "wah_bsi_cumsum_indexed_device": (_int, [_u64, _u64, _u64, _vp, _u64, _vp, _u64, ctypes.c_uint, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
+    "wah_bsi_cumsum_status": (_int, [_vp, _u64, _u64, ctypes.c_uint, _vp]),
     "wah_from_positions_max_words": (_u64, [_u64, _u64, _u64]),
     "wah_from_positions_scratch_bytes": (_sz, [_u64, _u64]),
     "wah_from_positions_device": (_int, [_u64, _u64, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
@@ -1287,6 +1290,52 @@ def bsi_map_device(key_table, n_words, n_rows, lookup, n_bits_out, exists=False,
         lambda: lib().wah_bsi_map_scratch_bytes(n, k_out, flags), lambda: max_compressed_words(rows_out * n),
         lambda *tail: lib().wah_bsi_map_indexed_device(n, r, ks, kt.data_ptr(), lookup.data_ptr(), n_keys, k_out, flags, *tail),
         lambda sc, sp: lib().wah_bsi_map_status(sc, n, k_out, flags, sp), scratch, out, out_offsets, check)
+
+
+CUMSUM_EXCLUSIVE = 2  # WAH_CUMSUM_EXCLUSIVE
+CUMSUM_ALL_ROWS = 4  # WAH_CUMSUM_ALL_ROWS
+
+
+def bsi_cumsum_device(val_table, n_words, n_rows, n_bits_val, n_bits_out, filters=None, exists=False, exclusive=False, all_rows=False,
+                      scratch=None, out=None, out_offsets=None, check=True):
+    """The RUNNING SUM of a bit-sliced value over the rows that the filters select, as a NEW bit-sliced attribute, in one call and
+    with nothing read back (wah_bsi_cumsum_indexed_device): `SUM(x) OVER (ORDER BY rowid) ... WHERE f`, and with n_bits_val == 0
+    the running COUNT, ROW_NUMBER() over the selected rows.  val_table: the value's n_bits_val slices (0 .. 32), most significant
+    first, unsigned, and with exists=True its existence bitmap as one more row behind them -- a list of (stream, seg_offsets) pairs
+    or a ready [k, 3] table, None when it has no row at all; filters: rows ANDed into the selection (None or empty: no filter).
+    Only the device reads the tables.  A row is selected when it lies in front of n_rows, is set in every filter row and, with
+    exists=True, in the existence bitmap.  Row p of the result holds the sum of the values of the selected rows q <= p
+    (exclusive=True: q < p) mod 2^n_bits_out, n_bits_out 1 .. 64; the sum is carried in 64 bits and cut where it is stored.
+    all_rows=False: only selected rows hold a value, every other row is 0, and the result's last slice is its existence bitmap,
+    the selection; all_rows=True: every row in front of n_rows holds the running value, unselected rows carrying it forward, and
+    the result has no existence bitmap.  n_words: the words of one slice, a multiple of 992.  Returns as bsi_build_device:
+    (stream, seg_offsets), the slices' compress() streams back to back, MOST significant first, and the rows_out * (n_words / 992)
+    + 1 entries of their segment index, rows_out = n_bits_out + (0 if all_rows else 1); scratch / out / out_offsets: reuse these
+    tensors; check=False: only enqueue and return (out, count tensor, out_offsets) -- the caller reads wah_bsi_cumsum_status
+    later."""
+    n, r, kv, k_out = int(n_words), int(n_rows), int(n_bits_val), int(n_bits_out)
+    if not (0 <= kv <= 32 and 1 <= k_out <= 64):
+        raise WahError("a value of 0 to 32 slices and a result of 1 to 64")
+    if n <= 0 or n % 992:
+        raise WahError("slices of a multiple of 992 words")
+    vt = _operand_table(val_table, "a value table") if kv or exists else None
+    ft = _operand_table(filters, "a filter table") if filters is not None and len(filters) else None
+    if vt is None and ft is None:
+        raise WahError("without value slices and without an existence bitmap the call needs a filter: its device is the call's")
+    if vt is not None and int(vt.shape[0]) != kv + (1 if exists else 0):
+        raise WahError("a value table of n_bits_val rows, and one more with exists=True")
+    if vt is not None and ft is not None and vt.device != ft.device:
+        raise WahError("the filter table and the value table are on one device")
+    dev = vt.device if vt is not None else ft.device
+    f = 0 if ft is None else int(ft.shape[0])
+    flags = (BSI_EXISTS if exists else 0) | (CUMSUM_EXCLUSIVE if exclusive else 0) | (CUMSUM_ALL_ROWS if all_rows else 0)
+    rows_out = k_out + (0 if all_rows else 1)
+    return _compressed_streams(
+        "wah_bsi_cumsum_indexed_device", "bsi_cumsum", dev, rows_out * (n // 992) + 1, _ROWS_OUT_OFFSETS,
+        lambda: lib().wah_bsi_cumsum_scratch_bytes(n, k_out, flags), lambda: max_compressed_words(rows_out * n),
+        lambda *tail: lib().wah_bsi_cumsum_indexed_device(n, r, f, ft.data_ptr() if f else None, kv, None if vt is None else vt.data_ptr(), k_out,
+                                                          flags, *tail),
+        lambda sc, sp: lib().wah_bsi_cumsum_status(sc, n, k_out, flags, sp), scratch, out, out_offsets, check)
 
 
 def positions_device(stream, seg_offsets, n_words, first=0, limit=None, out=None, scratch=None, check=True):

@@ -2425,6 +2425,66 @@ int wah_bsi_map_status(void *d_scratch, uint64_t n_words, uint64_t n_slices_out,
     return scratch_status_then(bsi_build_layout(n_words, map_rows_out(n_slices_out, flags)).ws_c, d_scratch, stream);
 }
 
+// The running sum of a bit-sliced value over the selected rows, as a new bit-sliced attribute (wah_cumsum.hip).  The builder's
+// scratch and its road, and behind them one u64 per segment: the segments' totals, scanned in place into their bases.  The
+// kernels write the result's decoded slice matrix, the compress passes run over it.  The tables stay in device memory: nothing
+// here reads them.
+static_assert(WAH_CUMSUM_EXCLUSIVE != WAH_BSI_EXISTS && WAH_CUMSUM_ALL_ROWS != WAH_BSI_EXISTS && WAH_CUMSUM_EXCLUSIVE != WAH_CUMSUM_ALL_ROWS,
+              "flag bits of their own");
+namespace {
+constexpr unsigned kCumsumFlags = WAH_BSI_EXISTS | WAH_CUMSUM_EXCLUSIVE | WAH_CUMSUM_ALL_ROWS;
+// the result's matrix rows: its slices, and the selection unless every row holds a value
+inline uint64_t cumsum_rows_out(uint64_t n_slices_out, unsigned flags) { return n_slices_out + ((flags & WAH_CUMSUM_ALL_ROWS) ? 0u : 1u); }
+inline size_t cumsum_totals_bytes(uint64_t n_words) { return round256((size_t)(n_words / wah::kSegWords) * sizeof(uint64_t)); }
+} // namespace
+
+size_t wah_bsi_cumsum_scratch_bytes(uint64_t n_words, uint64_t n_slices_out, unsigned flags) {
+    return bsi_build_layout(n_words, cumsum_rows_out(n_slices_out, flags)).total + cumsum_totals_bytes(n_words);
+}
+
+int wah_bsi_cumsum_indexed_device(uint64_t n_words, uint64_t n_rows, uint64_t n_filters, const wah_bitop_operand *d_filters,
+                                  uint64_t n_slices_val, const wah_bitop_operand *d_val, uint64_t n_slices_out, unsigned flags,
+                                  uint32_t *d_out, uint64_t out_capacity_words, uint64_t *d_out_words, uint64_t *d_out_offsets,
+                                  void *d_scratch, size_t scratch_bytes, void *stream) {
+    g_err[0] = 0;
+    if (n_slices_val > 32 || n_slices_out < 1 || n_slices_out > WAH_BSI_MAX_SLICES || (flags & ~kCumsumFlags) || n_filters > wah::kGroupMaxFilters)
+        return refuse("a value of at most 32 slices, a result of 1 to 64, no flag besides WAH_BSI_EXISTS, WAH_CUMSUM_EXCLUSIVE and WAH_CUMSUM_ALL_ROWS, at most 64 filter rows", WAH_ERR_ARG);
+    const bool has_val = n_slices_val != 0 || (flags & WAH_BSI_EXISTS);
+    if (!scratch_ok(d_scratch) || !out_triple_ok(d_out, d_out_words, d_out_offsets) || has_val != (d_val != nullptr) || !aligned(d_val, 7) ||
+        (n_filters && !d_filters) || !aligned(d_filters, 7))
+        return refuse("null or misaligned scratch or output, a value table that does not go with n_slices_val and WAH_BSI_EXISTS, or a null or misaligned filter table", WAH_ERR_ARG);
+    const uint64_t rows_out = cumsum_rows_out(n_slices_out, flags);
+    if (n_words == 0 || n_words % wah::kSegWords || n_words >= (1ull << 40) || rows_out * n_words >= (1ull << 40) || n_rows > 32 * n_words)
+        return refuse("slices of a multiple of 992 words, all slices of the result together fewer than 2^40 words, at most 32 n_words rows", WAH_ERR_ARG);
+    const BsiBuildLayout l = bsi_build_layout(n_words, rows_out);
+    if (scratch_bytes < l.total + cumsum_totals_bytes(n_words)) return refuse("scratch too small", WAH_ERR_WORKSPACE);
+    char *sc = static_cast<char *>(d_scratch);
+    const SegGeometry g = seg_geometry(n_words);
+    wah::BsiCumsumArgs a = {};
+    a.filters = reinterpret_cast<const wah::BitopListOperand *>(d_filters);
+    a.val = reinterpret_cast<const wah::BitopListOperand *>(d_val);
+    a.totals = reinterpret_cast<uint64_t *>(sc + l.total); // (a multiple of 256 bytes)
+    a.matrix = bsi_matrix(sc, l);
+    a.ctrl = reinterpret_cast<uint32_t *>(sc);
+    a.n_rows = n_rows;
+    a.n_words = n_words;
+    a.groups = g.groups;
+    a.n_segments = g.n_segments;
+    a.n_filters = (uint32_t)n_filters;
+    a.n_slices_val = (uint32_t)n_slices_val;
+    a.n_slices_out = (uint32_t)n_slices_out;
+    a.has_exists = (flags & WAH_BSI_EXISTS) ? 1u : 0u;
+    a.exclusive = (flags & WAH_CUMSUM_EXCLUSIVE) ? 1u : 0u;
+    a.all_rows = (flags & WAH_CUMSUM_ALL_ROWS) ? 1u : 0u;
+    return sweep_then_compress(a, wah::launch_bsi_cumsum, "running sum launch", n_words, rows_out, d_out, out_capacity_words, d_out_words,
+                               d_out_offsets, sc, l, stream);
+}
+
+int wah_bsi_cumsum_status(void *d_scratch, uint64_t n_words, uint64_t n_slices_out, unsigned flags, void *stream) {
+    // (first the kernels: everything the list call refuses in a row of the filter table or the value table)
+    return scratch_status_then(bsi_build_layout(n_words, cumsum_rows_out(n_slices_out, flags)).ws_c, d_scratch, stream);
+}
+
 // ---------------------------------------------------------------------------
 // host-pointer entry points (the reference's API)
 // ---------------------------------------------------------------------------

@@ -1,0 +1,346 @@
+// wah_cumsum.hip -- wah_bsi_cumsum_indexed_device: the RUNNING SUM of a bit-sliced value over the rows a conjunction of filters
+// selects, R[p] = sum of the values of the selected rows q <= p (q < p: exclusive) mod 2^n_slices_out, leaving as a NEW bit-sliced
+// attribute of up to 64 slices: `SUM(x) OVER (ORDER BY rowid)`, and with no value slices at all the running COUNT -- ROW_NUMBER()
+// over the selected rows, or with all_rows the rank of ANY row among them.  No value column is written and read again.  It is the
+// one call of the family whose answer for a row depends on the rows in front of it, so it is three launches, none of which waits
+// for another workgroup: segments are independent items of a capped grid-stride grid in the first and the last.
+//
+// cumsum_totals_kernel   one workgroup of eight wavefronts per segment.  Wavefront 7 makes the SELECTION image as the group-by
+//             kernel does (wah_group_by.hip): all ones clipped to segment_groups / segment_rows(n_rows), the value's existence row
+//             and the filter rows walked into it under AND.  Behind a barrier wavefronts 0 .. 6 walk their share of the value's
+//             slices under OR, one row at a time in the zeroed image, and where a row is complete add popcount(slice & selection)
+//             << significance: a total needs no per-row fold.  Without value slices the total is the selection's popcount.  One
+//             u64 per segment leaves, EVERY segment's: the scratch needs no clearing.  32 KiB of LDS.
+// cumsum_scan_kernel     ONE workgroup turns the totals in place into the sum of the segments in front of each: 8192 entries per
+//             round (eight per thread, a wave scan, sixteen wave totals through LDS), a carry from round to round.
+// cumsum_rows_kernel     bsi_map_segments_kernel's frame (wah_map.hip): s_rows[kSegBits] plus eight images, 159 872 bytes of LDS,
+//             one workgroup per CU.  Wavefronts 0 .. 6 fold the value's slices into one word per row, wavefront 7 makes the
+//             selection.  Behind the barrier wavefront w takes blocks w and w + 8 with map_block's row ownership (lane l of step t:
+//             row 2048 blk + 64 t + l), twice:
+//   totals    a block's selected values are reduced to one u64, sixteen of them in LDS; a barrier.
+//   scan      per block the base is the segment's base plus the block totals in front of it (wave-uniform).  Per step one
+//             inclusive scan of the 64 lanes with DPP -- values of up to 26 bits in one u32 scan, wider ones as two scans of
+//             their 16-bit halves, which 64 lanes cannot overflow -- added to the carry of the steps in front in 64 bits; minus
+//             the lane's own value when exclusive; zero for an unselected row unless all_rows, and for a row at or behind n_rows.
+//             The block's results stay in two statically indexed register arrays, low and high halves.
+//   transpose a RUNTIME loop over the result's slices, most significant first: slice_words (wah_slice_words.hpp) on the high half
+//             for slices 63 .. 32, on the low half below, and one store of 256 contiguous bytes (128 in the half block) per slice
+//             and block.  Without all_rows the ballots of the selection are the last row.
+// Every word of every result row is written exactly once: the matrix needs no clearing.  No register array is indexed by a
+// runtime value.  Every table row's every segment is walked by the first kernel and again by the last: both report what the walk
+// refuses.
+#include "wah_fold_bits.hpp"
+#include "wah_slice_words.hpp"
+
+namespace wah {
+namespace {
+
+constexpr u32 kCumsumGridItems = 512;  // workgroups of the two segment kernels at the most (bsi_map_segments_kernel's cap)
+constexpr u32 kCumsumWaves = 8;        // wavefronts of their workgroups
+constexpr u32 kCumsumSliceWaves = kCumsumWaves - 1u; // ... that walk slices; the last one walks the selection rows
+constexpr u32 kCumsumBlockWords = 64;  // slice words per block: one per lane (map_block's block)
+constexpr u32 kCumsumBlockSteps = 32;  // steps of 64 rows per block
+constexpr u32 kCumsumBlockRows = 2048; // 32 * kCumsumBlockWords
+constexpr u32 kCumsumBlocks = 16;      // blocks of a segment: 15 of kCumsumBlockRows rows and a half one
+constexpr u32 kCumsumNarrowBits = 26;  // value slices up to which 64 lanes' sum stays below 2^32: one u32 scan
+constexpr u32 kScanWaves = 16;         // wavefronts of cumsum_scan_kernel's one workgroup
+constexpr u32 kScanPer = 8;            // entries per thread and round
+static_assert((kSegBits + kCumsumWaves * kSegGroups) * sizeof(u32) + kCumsumBlocks * sizeof(u64) <= 160u * 1024u, "one workgroup fits a CU's LDS");
+static_assert((kCumsumBlocks - 1u) * kCumsumBlockRows + kCumsumBlockRows / 2u == kSegBits &&
+                  (kCumsumBlocks - 1u) * kCumsumBlockWords + kCumsumBlockWords / 2u == kSegWords,
+              "a segment: fifteen blocks and a half");
+static_assert(kCumsumBlocks == 2u * kCumsumWaves, "two blocks per wavefront");
+static_assert(64u * ((1u << kCumsumNarrowBits) - 1u) < (1ull << 32) && 64u * 0xFFFFu < (1ull << 32), "neither scan can wrap");
+
+// the selection image of segment seg before the walks: every row of the segment that lies in front of n_rows
+__device__ __forceinline__ void selection_preset(u32 *acc, u64 n_rows, u64 seg, u32 nvalid, u32 lane) {
+    const u32 rows = segment_rows(n_rows, seg), full = rows / 31u, rest = rows % 31u;
+#pragma unroll
+    for (u32 i = 0; i < kSegGroups / 64u; ++i) {
+        const u32 g = 64u * i + lane;
+        acc[g] = g >= nvalid ? 0u : g < full ? kOnes31 : g == full ? (1u << rest) - 1u : 0u;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+}
+
+// ... and the walks: the value table's last row if it is an existence row, then the filter rows, ANDed in
+__device__ __forceinline__ void selection_walk(const BsiCumsumArgs &a, u32 *acc, u64 seg, u32 nvalid, u32 lane) {
+    const ListOp m_and = list_op(0u);
+    bool ok = true;
+    if (a.has_exists)
+        ok = list_walk(a.val + a.n_slices_val, 1u, seg, nvalid, m_and.fill, acc, lane, [&](u32) -> const ListOp & { return m_and; }, [](u32) {});
+    if (a.n_filters != 0u)
+        ok = list_walk(a.filters, a.n_filters, seg, nvalid, m_and.fill, acc, lane, [&](u32) -> const ListOp & { return m_and; }, [](u32) {}) && ok;
+    if (!ok) report_stream_error(a.ctrl, lane);
+}
+
+// the table rows [lo, hi) of the value's n slices that wavefront `wave` of the seven walks
+__device__ __forceinline__ void slice_share(u32 n, u32 wave, u32 &lo, u32 &hi) {
+    const u32 per = (n + kCumsumSliceWaves - 1u) / kCumsumSliceWaves;
+    lo = min(wave * per, n);
+    hi = wave < kCumsumSliceWaves ? min(lo + per, n) : lo;
+}
+
+// The slices [w_lo, w_hi) of the value walked under OR one row at a time in the zeroed image; done(sig) is called, wave-uniform,
+// while the image holds exactly the slice of significance sig.  (A slice settled in the gather is all zeros here and is not seen.)
+template <class Done>
+__device__ __forceinline__ void walk_slices(const BsiCumsumArgs &a, u32 w_lo, u32 w_hi, u64 seg, u32 nvalid, u32 *acc, u32 lane, Done done) {
+    const ListOp m_or = list_op(1u);
+    u32 cur = 0;       // the table row the image holds (wave-uniform)
+    bool open = false; // ... if it holds one
+    auto close = [&]() {
+        done(a.n_slices_val - 1u - w_lo - cur);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        image_fill(acc, 0u, lane);
+    };
+    const bool ok = list_walk(a.val + w_lo, w_hi - w_lo, seg, nvalid, m_or.fill, acc, lane, [&](u32) -> const ListOp & { return m_or; }, [&](u32 j) {
+        if (open) close(); // this row's words begin: the one in the image is complete
+        cur = j;
+        open = true;
+    });
+    if (open) close();
+    // (no early return: the workgroup's barriers are for all its wavefronts; the output of a refused call is unspecified)
+    if (!ok) report_stream_error(a.ctrl, lane);
+}
+
+__global__ __launch_bounds__(kCumsumWaves * 64) void cumsum_totals_kernel(const BsiCumsumArgs a) {
+    __shared__ __attribute__((aligned(16))) u32 s_acc[kCumsumWaves][kSegGroups];
+    __shared__ u64 s_part[kCumsumWaves];
+    const u32 wave = wave_id(), lane = lane_id();
+    u32 *acc = s_acc[wave];
+    const u32 *sel = s_acc[kCumsumSliceWaves];
+    u32 w_lo, w_hi;
+    slice_share(a.n_slices_val, wave, w_lo, w_hi);
+
+#pragma nounroll
+    for (u64 seg = blockIdx.x; seg < a.n_segments; seg += gridDim.x) { // (workgroup-uniform)
+        const u32 nvalid = segment_groups(a.groups, seg);
+        if (wave < kCumsumSliceWaves) {
+            image_fill(acc, 0u, lane);
+        } else {
+            selection_preset(acc, a.n_rows, seg, nvalid, lane);
+            selection_walk(a, acc, seg, nvalid, lane);
+        }
+        __syncthreads();
+
+        u64 sum = 0; // the lane's share of the wavefront's
+        auto count = [&](u32 sig) { // the image's set bits among the selected rows, at weight 2^sig
+            u32 c = 0;
+#pragma unroll
+            for (u32 i = 0; i < kSegGroups / 64u; ++i) c += (u32)__popc((wave < kCumsumSliceWaves ? acc[64u * i + lane] : kOnes31) & sel[64u * i + lane]);
+            sum += (u64)c << sig;
+        };
+        if (wave < kCumsumSliceWaves) {
+            if (w_lo < w_hi) walk_slices(a, w_lo, w_hi, seg, nvalid, acc, lane, count); // (wave-uniform)
+        } else if (a.n_slices_val == 0u) {
+            count(0u);
+        }
+        sum = wave_sum(sum);
+        if (lane == 0) s_part[wave] = sum;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            u64 total = 0;
+#pragma unroll
+            for (u32 w = 0; w < kCumsumWaves; ++w) total += s_part[w];
+            a.totals[seg] = total;
+        }
+        // (no third barrier: the next segment's selection is written by wavefront 7 behind this one, its partial sums behind the next)
+    }
+}
+
+// totals[i] becomes the sum of totals[0 .. i), mod 2^64
+__global__ __launch_bounds__(kScanWaves * 64) void cumsum_scan_kernel(u64 *totals, u64 n) {
+    __shared__ u64 s_wave[kScanWaves];
+    const u32 wave = wave_id(), lane = lane_id();
+    u64 carry = 0; // the sum of the rounds in front (workgroup-uniform)
+#pragma nounroll
+    for (u64 i0 = 0; i0 < n; i0 += (u64)kScanWaves * 64u * kScanPer) {
+        const u64 first = i0 + (u64)threadIdx.x * kScanPer;
+        u64 v[kScanPer], mine = 0;
+#pragma unroll
+        for (u32 i = 0; i < kScanPer; ++i) {
+            v[i] = first + i < n ? totals[first + i] : 0ull;
+            mine += v[i];
+        }
+        const u64 incl = wave_scan_incl(mine, lane);
+        if (lane == 63u) s_wave[wave] = incl;
+        __syncthreads();
+        u64 before = 0, all = 0;
+#pragma unroll
+        for (u32 w = 0; w < kScanWaves; ++w) {
+            const u64 x = s_wave[w];
+            before += w < wave ? x : 0ull;
+            all += x;
+        }
+        u64 run = carry + before + incl - mine;
+#pragma unroll
+        for (u32 i = 0; i < kScanPer; ++i) {
+            if (first + i < n) totals[first + i] = run;
+            run += v[i];
+        }
+        carry += all;
+        __syncthreads(); // the next round's wave totals
+    }
+}
+
+// Block blk of a segment: the values of its kSteps steps of 64 rows -- a row that is not selected holds 0, a selected one its
+// value, or 1 where the value has no slices.  Returns the selection: bit t for the lane's row of step t.
+template <u32 kSteps>
+__device__ __forceinline__ u32 load_block(const u32 *s_rows, const u32 *sel, u32 n_slices_val, u32 blk, u32 lane, u32 (&v)[kSteps]) {
+    u32 row0 = (u32)kCumsumBlockRows * blk + lane;
+    // (opaque: the steps' selection words and shifts depend on lane and block alone, and hoisted out of the loop over the
+    //  segments they would take two hundred registers)
+    asm volatile("" : "+v"(row0));
+    u32 picked = 0u;
+#pragma unroll
+    for (u32 t = 0; t < kSteps; ++t) {
+        const u32 r = row0 + 64u * t;
+        const u32 bit = (sel[r / 31u] >> (r % 31u)) & 1u;
+        picked |= bit << t;
+        v[t] = n_slices_val == 0u ? bit : s_rows[r] & (0u - bit); // (wave-uniform choice)
+    }
+    return picked;
+}
+
+// the sum of block blk's selected values (wave-uniform)
+template <u32 kSteps>
+__device__ __forceinline__ u64 block_total(const u32 *s_rows, const u32 *sel, u32 n_slices_val, u32 blk, u32 lane) {
+    u32 v[kSteps];
+    load_block<kSteps>(s_rows, sel, n_slices_val, blk, lane, v);
+    u64 sum = 0;
+#pragma unroll
+    for (u32 t = 0; t < kSteps; ++t) sum += v[t];
+    return uniform64(wave_sum(sum));
+}
+
+// Block blk of segment seg, rows of it in front of n_rows: the running sums of its kSteps steps from `base` on, stored as
+// 2 kSteps words of every result row.  kWide: values above kCumsumNarrowBits slices; kHigh: a result above 32 slices.
+template <u32 kSteps, bool kWide, bool kHigh>
+__device__ __forceinline__ void scan_block(const BsiCumsumArgs &a, const u32 *s_rows, const u32 *sel, u64 seg, u32 rows, u32 blk, u32 lane, u64 base) {
+    u32 lo[kSteps], hi[kSteps];
+    u32 have = 0u; // lane j: word j of the block's selection
+    {
+        u32 v[kSteps];
+        const u32 picked = load_block<kSteps>(s_rows, sel, a.n_slices_val, blk, lane, v);
+        const u32 row0 = (u32)kCumsumBlockRows * blk + lane;
+        u64 carry = base; // the sum in front of the step (wave-uniform)
+#pragma unroll
+        for (u32 t = 0; t < kSteps; ++t) {
+            const u32 x = v[t];
+            const u64 s = kWide ? (u64)wave_scan_incl32(x & 0xFFFFu) + ((u64)wave_scan_incl32(x >> 16) << 16) : (u64)wave_scan_incl32(x);
+            u64 r = carry + s - (a.exclusive != 0u ? x : 0u);
+            carry += ((u64)(kWide ? (u32)__builtin_amdgcn_readlane((int)(u32)(s >> 32), 63) : 0u) << 32) | (u32)__builtin_amdgcn_readlane((int)(u32)s, 63);
+            const bool on = ((picked >> t) & 1u) != 0u;
+            if (!((on || a.all_rows != 0u) && row0 + 64u * t < rows)) r = 0ull;
+            lo[t] = (u32)r;
+            hi[t] = (u32)(r >> 32);
+            const u64 m = __ballot(on);
+            have = put_lane((u32)m, 2u * t, have);
+            have = put_lane((u32)(m >> 32), 2u * t + 1u, have);
+        }
+    }
+    const bool store = lane < 2u * kSteps; // (the half block: 32 words)
+    u32 *out = a.matrix + (seg * kSegWords + kCumsumBlockWords * blk + lane); // row 0 of the matrix; every row is n_words further
+    u32 b = a.n_slices_out;
+    if (kHigh) {
+#pragma nounroll
+        for (; b > 32u; --b) {
+            const u32 w = slice_words(hi, 1u << (b - 33u));
+            if (store) *out = w;
+            out += a.n_words;
+        }
+    }
+#pragma nounroll
+    for (; b > 0u; --b) {
+        const u32 w = slice_words(lo, 1u << (b - 1u));
+        if (store) *out = w;
+        out += a.n_words;
+    }
+    if (a.all_rows == 0u && store) *out = have;
+}
+
+template <bool kWide, bool kHigh>
+__global__ __launch_bounds__(kCumsumWaves * 64) void cumsum_rows_kernel(const BsiCumsumArgs a) {
+    __shared__ __attribute__((aligned(16))) u32 s_rows[kSegBits];
+    __shared__ __attribute__((aligned(16))) u32 s_acc[kCumsumWaves][kSegGroups];
+    __shared__ u64 s_block[kCumsumBlocks];
+    const u32 wave = wave_id(), lane = lane_id();
+    u32 *acc = s_acc[wave];
+    const u32 *sel = s_acc[kCumsumSliceWaves];
+    const u32 nv = a.n_slices_val;
+    u32 w_lo, w_hi;
+    slice_share(nv, wave, w_lo, w_hi);
+    const bool last_half = wave + kCumsumWaves == kCumsumBlocks - 1u; // (wave-uniform: the wavefront whose second block is the half one)
+
+#pragma nounroll
+    for (u64 seg = blockIdx.x; seg < a.n_segments; seg += gridDim.x) { // (workgroup-uniform)
+        const u32 nvalid = segment_groups(a.groups, seg);
+        const u32 rows = segment_rows(a.n_rows, seg);
+
+        if (nv != 0u) // (without value slices the rows' words are never read)
+            for (u32 p = threadIdx.x * 4u; p < kSegBits; p += kCumsumWaves * 64u * 4u) *reinterpret_cast<uint4 *>(s_rows + p) = make_uint4(0u, 0u, 0u, 0u);
+        if (wave < kCumsumSliceWaves)
+            image_fill(acc, 0u, lane);
+        else
+            selection_preset(acc, a.n_rows, seg, nvalid, lane);
+        __syncthreads();
+
+        if (wave < kCumsumSliceWaves) {
+            if (w_lo < w_hi) // (wave-uniform)
+                walk_slices(a, w_lo, w_hi, seg, nvalid, acc, lane, [&](u32 sig) { fold_slice_bits(acc, s_rows, 0u, kSegGroups / 64u, sig, lane); });
+        } else {
+            selection_walk(a, acc, seg, nvalid, lane);
+        }
+        __syncthreads();
+
+        {
+            const u64 t0 = block_total<kCumsumBlockSteps>(s_rows, sel, nv, wave, lane);
+            const u64 t1 = last_half ? block_total<kCumsumBlockSteps / 2u>(s_rows, sel, nv, kCumsumBlocks - 1u, lane)
+                                     : block_total<kCumsumBlockSteps>(s_rows, sel, nv, wave + kCumsumWaves, lane);
+            if (lane == 0) {
+                s_block[wave] = t0;
+                s_block[wave + kCumsumWaves] = t1;
+            }
+        }
+        __syncthreads();
+
+        u64 base = a.totals[seg]; // (scanned: the sum of the segments in front)
+#pragma nounroll
+        for (u32 b = 0; b < wave; ++b) base += s_block[b];
+        base = uniform64(base);
+        scan_block<kCumsumBlockSteps, kWide, kHigh>(a, s_rows, sel, seg, rows, wave, lane, base);
+#pragma nounroll
+        for (u32 b = wave; b < wave + kCumsumWaves; ++b) base += s_block[b];
+        base = uniform64(base);
+        if (last_half)
+            scan_block<kCumsumBlockSteps / 2u, kWide, kHigh>(a, s_rows, sel, seg, rows, kCumsumBlocks - 1u, lane, base);
+        else
+            scan_block<kCumsumBlockSteps, kWide, kHigh>(a, s_rows, sel, seg, rows, wave + kCumsumWaves, lane, base);
+        __syncthreads(); // the next segment clears the rows and the images
+    }
+}
+
+} // namespace
+
+hipError_t launch_bsi_cumsum(const BsiCumsumArgs &a, hipStream_t s) {
+    if (a.n_segments == 0) return hipSuccess;
+    const dim3 grid((unsigned)(a.n_segments < kCumsumGridItems ? a.n_segments : kCumsumGridItems)), block(kCumsumWaves * 64);
+    hipLaunchKernelGGL(cumsum_totals_kernel, grid, block, 0, s, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(cumsum_scan_kernel, dim3(1), dim3(kScanWaves * 64), 0, s, a.totals, a.n_segments);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const bool wide = a.n_slices_val > kCumsumNarrowBits, high = a.n_slices_out > 32u;
+    if (wide && high)
+        hipLaunchKernelGGL((cumsum_rows_kernel<true, true>), grid, block, 0, s, a);
+    else if (wide)
+        hipLaunchKernelGGL((cumsum_rows_kernel<true, false>), grid, block, 0, s, a);
+    else if (high)
+        hipLaunchKernelGGL((cumsum_rows_kernel<false, true>), grid, block, 0, s, a);
+    else
+        hipLaunchKernelGGL((cumsum_rows_kernel<false, false>), grid, block, 0, s, a);
+    return hipGetLastError();
+}
+
+} // namespace wah

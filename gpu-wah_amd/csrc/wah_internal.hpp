@@ -483,6 +483,28 @@ struct BsiMapArgs {
 };
 hipError_t launch_bsi_map(const BsiMapArgs &a, hipStream_t s);
 
+// wah_bsi_cumsum_indexed_device (wah_cumsum.hip): the running sum of a bit-sliced value over the selected rows, as a new bit-sliced
+// attribute.  filters: n_filters rows; val: n_slices_val rows, most significant slice first (0: every selected row counts 1),
+// then the existence bitmap if has_exists.  totals: n_segments u64 in the scratch: a segment's sum, then -- scanned in place -- the
+// sum of the segments in front of it.  matrix: the decoded slice matrix [n_slices_out (+ 1 without all_rows), n_words] the last
+// kernel writes every word of, most significant slice first, the selection last.  An item is a segment.
+struct BsiCumsumArgs {
+    const BitopListOperand *filters, *val;
+    uint64_t *totals;
+    uint32_t *matrix;
+    uint32_t *ctrl;
+    uint64_t n_rows;             // rows at or behind it are never selected and hold 0; <= 32 n_words
+    uint64_t n_words;            // words of one slice, a multiple of kSegWords
+    uint64_t groups, n_segments; // of one slice
+    uint32_t n_filters;          // 0 .. kGroupMaxFilters
+    uint32_t n_slices_val;       // 0 .. 32
+    uint32_t n_slices_out;       // 1 .. 64
+    uint32_t has_exists;         // 0 or 1: one more value row
+    uint32_t exclusive;          // 0: rows q <= p; 1: rows q < p
+    uint32_t all_rows;           // 0: unselected rows hold 0, the selection is the last matrix row; 1: they carry the sum, no such row
+};
+hipError_t launch_bsi_cumsum(const BsiCumsumArgs &a, hipStream_t s); // the segment totals, their scan, the rows
+
 // ... on operands of few words per segment: their runs merged in the compressed domain, one lane per segment
 // (wah_bitop_runs.hip): count pass, scan of the tile totals, write pass
 struct BitopRunsArgs {

@@ -1048,6 +1048,55 @@ int wah_bsi_map_indexed_device(uint64_t n_words, uint64_t n_rows, uint64_t n_sli
                                size_t scratch_bytes, void *stream);
 int wah_bsi_map_status(void *d_scratch, uint64_t n_words, uint64_t n_slices_out, unsigned flags, void *stream);
 
+/* The RUNNING SUM of a bit-sliced value over the rows a conjunction of filters selects, in ONE call, leaving as a NEW bit-sliced
+ * attribute that every call here takes -- `SELECT SUM(x) OVER (ORDER BY rowid) FROM t WHERE f`, and without value slices the
+ * running COUNT: ROW_NUMBER() over the selected rows, the cumulative distribution behind "the first row at which the running
+ * revenue passes L", the rank of any row among the selected ones.  It is the one call here whose answer for row p depends on the
+ * rows in front of p.  No value column is written and read again.
+ *   SELECTION: as in the group-by call.  A row p < n_rows is selected if it is set in every row of d_filters (0 <= n_filters <=
+ *   WAH_GROUP_MAX_FILTERS; d_filters may be NULL when there is none) and, with WAH_BSI_EXISTS in flags, in the value's existence
+ *   bitmap, which is ONE more row behind the slices in d_val.  n_rows <= 32 n_words; rows at or behind n_rows and pad bits are
+ *   never selected.
+ *   VALUE: d_val is the value's table, n_slices_val rows (0 .. 32, most significant slice first), unsigned.  n_slices_val == 0:
+ *   every selected row counts 1; d_val is then NULL unless WAH_BSI_EXISTS is set, and with the flag holds just the existence row.
+ *   RESULT: R[p] = (the sum of the values of the selected rows q <= p) mod 2^n_slices_out, with WAH_CUMSUM_EXCLUSIVE over q < p;
+ *   n_slices_out is 1 .. WAH_BSI_MAX_SLICES, most significant slice first.  The sum is carried in 64 bits everywhere and cut only
+ *   where it is stored: a result narrower than the true sum holds its low bits.  By default only SELECTED rows hold a value, every
+ *   other row is 0 in every slice, and the result's LAST row is its existence row, equal to the selection.  With
+ *   WAH_CUMSUM_ALL_ROWS every row in front of n_rows holds the running value -- an unselected row carries it forward: the rank of
+ *   row p among the selected rows, for any p -- and the result has NO existence row.  rows_out = n_slices_out + (ALL_ROWS ? 0 : 1).
+ *   d_out, d_out_words and d_out_offsets receive exactly what wah_bsi_build_device leaves for a value column of rows_out rows:
+ *   the compress() of the result's slice matrix [rows_out, n_words] as ONE bitmap and its whole segment index, rows_out *
+ *   (n_words / 992) + 1 entries.
+ * n_words is a non-zero multiple of 992 below 2^40, and rows_out * n_words stays below 2^40, as in the map call.  Tables are
+ * 8-byte aligned; windows into column matrices, capacities as lengths and the not-yet-checked output of an earlier call on the
+ * stream are allowed.  The tables are read by the device only: the call is asynchronous on `stream`, allocates nothing, never
+ * synchronises and reads nothing back, and a captured graph replayed after a table was overwritten in place computes the NEW
+ * result.  Three launches, no workgroup of which waits for another -- one workgroup per segment adds popcount(slice AND
+ * selection) << significance into one total per segment; one workgroup scans the totals; one workgroup per segment folds the
+ * slices into one word per row in LDS, scans the rows 64 at a time with the carry of the steps, blocks and segments in front, and
+ * transposes the sums in registers into slice words by ballots -- then the compress passes.
+ *   d_scratch: the builder's layout and one uint64 per segment behind it, 256-byte aligned, no initialisation:
+ *   wah_bsi_cumsum_scratch_bytes(n_words, n_slices_out, flags) = wah_bsi_build_scratch_bytes(n_words, rows_out) + 8 (n_words /
+ *   992) rounded up to a multiple of 256.
+ * Errors the host can see come back before any HIP call, in this order: (1) n_slices_val above 32, n_slices_out outside 1 .. 64,
+ * unknown flag bits, n_filters above the cap; (2) a null or misaligned scratch or output, a d_val that does not go with
+ * n_slices_val and the flags, a null filter table with n_filters > 0; (3) n_words 0, no multiple of 992 or >= 2^40, rows_out *
+ * n_words >= 2^40, n_rows > 32 n_words -- all WAH_ERR_ARG; then too small a scratch: WAH_ERR_WORKSPACE.  Everything only the
+ * device sees is reported by wah_bsi_cumsum_status(), which synchronises the stream: WAH_ERR_STREAM for everything the list call
+ * refuses in a row of either table, EVERY row's every segment being walked whatever is selected; then the compress passes'
+ * verdict (WAH_ERR_CAPACITY: nothing is written at or behind d_out[out_capacity_words]).  The output of a refused call is
+ * unspecified.  wah_bsi_cumsum_status(NULL, ...): WAH_ERR_ARG.  Not here: sums that start again per partition, signed values,
+ * values above 32 slices. */
+#define WAH_CUMSUM_EXCLUSIVE 2u /* flags: the sum runs over the rows in front of a row, not up to it */
+#define WAH_CUMSUM_ALL_ROWS 4u  /* flags: unselected rows carry the sum forward, and the result has no existence row */
+size_t wah_bsi_cumsum_scratch_bytes(uint64_t n_words, uint64_t n_slices_out, unsigned flags);
+int wah_bsi_cumsum_indexed_device(uint64_t n_words, uint64_t n_rows, uint64_t n_filters, const wah_bitop_operand *d_filters,
+                                  uint64_t n_slices_val, const wah_bitop_operand *d_val, uint64_t n_slices_out, unsigned flags,
+                                  uint32_t *d_out, uint64_t out_capacity_words, uint64_t *d_out_words, uint64_t *d_out_offsets,
+                                  void *d_scratch, size_t scratch_bytes, void *stream);
+int wah_bsi_cumsum_status(void *d_scratch, uint64_t n_words, uint64_t n_slices_out, unsigned flags, void *stream);
+
 /* The order statistics PER GROUP in ONE call -- `SELECT g, h, MIN(x), MAX(x), median(x) WHERE <filter> GROUP BY g, h`: for every
  * group g and every query q the value of rank q among the rows that `filters AND group g's rows` select, over ONE bit-sliced
  * attribute.  It is wah_bsi_kth_indexed_device's radix select for L = n_groups * n_queries selects ("lanes") at once.
