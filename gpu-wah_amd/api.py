@@ -111,6 +111,9 @@ ABI_SYMBOLS = {
     "wah_bsi_cumsum_scratch_bytes": (_sz, [_u64, _u64, ctypes.c_uint]),
     "wah_bsi_cumsum_indexed_device": (_int, [_u64, _u64, _u64, _vp, _u64, _vp, _u64, ctypes.c_uint, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
     "wah_bsi_cumsum_status": (_int, [_vp, _u64, _u64, ctypes.c_uint, _vp]),
+    "wah_bsi_cumsum_parts_scratch_bytes": (_sz, [_u64, _u64, ctypes.c_uint]),
+    "wah_bsi_cumsum_parts_indexed_device": (_int, [_u64, _u64, _u64, _vp, _u64, _vp, _vp, _u64, ctypes.c_uint, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
+    "wah_bsi_cumsum_parts_status": (_int, [_vp, _u64, _u64, ctypes.c_uint, _vp]),
     "wah_from_positions_max_words": (_u64, [_u64, _u64, _u64]),
     "wah_from_positions_scratch_bytes": (_sz, [_u64, _u64]),
     "wah_from_positions_device": (_int, [_u64, _u64, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
@@ -1336,6 +1339,42 @@ def bsi_cumsum_device(val_table, n_words, n_rows, n_bits_val, n_bits_out, filter
         lambda *tail: lib().wah_bsi_cumsum_indexed_device(n, r, f, ft.data_ptr() if f else None, kv, None if vt is None else vt.data_ptr(), k_out,
                                                           flags, *tail),
         lambda sc, sp: lib().wah_bsi_cumsum_status(sc, n, k_out, flags, sp), scratch, out, out_offsets, check)
+
+
+def bsi_cumsum_parts_device(val_table, n_words, n_rows, n_bits_val, n_bits_out, starts, filters=None, exists=False, exclusive=False,
+                            all_rows=False, scratch=None, out=None, out_offsets=None, check=True):
+    """The RUNNING SUM PER PARTITION (wah_bsi_cumsum_parts_indexed_device): bsi_cumsum_device with a sum that starts again at
+    every row set in `starts` -- `SUM(x) OVER (PARTITION BY g ORDER BY rowid) ... WHERE f` on a table clustered by g, and with
+    n_bits_val == 0 ROW_NUMBER() OVER (PARTITION BY g).  starts: ONE indexed bitmap of n_words words, a one-row operand table or a
+    (stream, seg_offsets) pair; row p starts a partition when its bit is set and p < n_rows, selected or not.  Row p of the result
+    holds the sum of the values of the selected rows q with s(p) <= q <= p (exclusive=True: q < p), s(p) the last start at or in
+    front of p, row 0 without one.  Everything else -- tables, flags, the result, scratch / out / out_offsets / check -- as
+    bsi_cumsum_device; the status call is wah_bsi_cumsum_parts_status."""
+    n, r, kv, k_out = int(n_words), int(n_rows), int(n_bits_val), int(n_bits_out)
+    if not (0 <= kv <= 32 and 1 <= k_out <= 64):
+        raise WahError("a value of 0 to 32 slices and a result of 1 to 64")
+    if n <= 0 or n % 992:
+        raise WahError("slices of a multiple of 992 words")
+    if isinstance(starts, tuple) and len(starts) == 2:
+        starts = [starts]
+    st = _operand_table(starts, "a starts row")
+    if int(st.shape[0]) != 1:
+        raise WahError("a starts table of one row")
+    vt = _operand_table(val_table, "a value table") if kv or exists else None
+    ft = _operand_table(filters, "a filter table") if filters is not None and len(filters) else None
+    if vt is not None and int(vt.shape[0]) != kv + (1 if exists else 0):
+        raise WahError("a value table of n_bits_val rows, and one more with exists=True")
+    if any(t is not None and t.device != st.device for t in (vt, ft)):
+        raise WahError("the starts row, the filter table and the value table are on one device")
+    f = 0 if ft is None else int(ft.shape[0])
+    flags = (BSI_EXISTS if exists else 0) | (CUMSUM_EXCLUSIVE if exclusive else 0) | (CUMSUM_ALL_ROWS if all_rows else 0)
+    rows_out = k_out + (0 if all_rows else 1)
+    return _compressed_streams(
+        "wah_bsi_cumsum_parts_indexed_device", "bsi_cumsum_parts", st.device, rows_out * (n // 992) + 1, _ROWS_OUT_OFFSETS,
+        lambda: lib().wah_bsi_cumsum_parts_scratch_bytes(n, k_out, flags), lambda: max_compressed_words(rows_out * n),
+        lambda *tail: lib().wah_bsi_cumsum_parts_indexed_device(n, r, f, ft.data_ptr() if f else None, kv, None if vt is None else vt.data_ptr(),
+                                                                st.data_ptr(), k_out, flags, *tail),
+        lambda sc, sp: lib().wah_bsi_cumsum_parts_status(sc, n, k_out, flags, sp), scratch, out, out_offsets, check)
 
 
 def positions_device(stream, seg_offsets, n_words, first=0, limit=None, out=None, scratch=None, check=True):

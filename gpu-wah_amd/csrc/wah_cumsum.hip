@@ -320,7 +320,351 @@ __global__ __launch_bounds__(kCumsumWaves * 64) void cumsum_rows_kernel(const Bs
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// wah_bsi_cumsum_parts_indexed_device: the same running sum, starting again at every row that is set in ONE more bitmap, the
+// partition STARTS -- `SUM(x) OVER (PARTITION BY g ORDER BY rowid)` on a table clustered by g.  The frame is the one above: three
+// launches, no workgroup waits for another.  Plain addition becomes the segmented operator on pairs (has_start, sum),
+//   (f1, s1) o (f2, s2) = (f1 | f2, f2 ? s2 : s1 + s2),
+// at every level:
+// cumsum_parts_totals_kernel  as cumsum_totals_kernel, but wavefront 7 first walks the starts row into its image, clips it to the
+//             rows in front of n_rows and finds its last set bit; then it makes the selection in the same image and ANDs "rows at
+//             or behind the last start" into it.  What the popcounts then see is the segment's TAIL: the selected values at or
+//             behind its last start, the whole segment where it has none.  A record (tail, has_start) per segment leaves, EVERY
+//             segment's.
+// cumsum_parts_scan_kernel    cumsum_scan_kernel on the pairs: a record's sum becomes what flows INTO the segment, the tails
+//             since the last segment that held a start; the carry from round to round is a pair too.
+// cumsum_parts_rows_kernel    cumsum_rows_kernel's frame and footprint: SIX wavefronts share the value's slices, wavefront 6 walks
+//             the starts row into its image (clipped to the rows in front of n_rows), wavefront 7 makes the selection.  A
+//             block's total is a pair (has_start, the values at or behind its last start); a block's base is the fold of the
+//             segment's incoming sum and the blocks in front.  Per step of 64 rows the heads are one ballot of the start bits:
+//   no head   (wave-uniform, the common case) the step above: one DPP scan, the carry on the scalar unit.
+//   heads     the same DPP scan S, minus the EXCLUSIVE scan value at the lane's own head lane -- the last head at or in front
+//             of it, from the ballot masked to the lanes <= lane: one ds_bpermute per scanned word.  The lanes in front of the
+//             first head keep the carry, the others drop it; the carry out is S[63] minus the exclusive value at the last head.
+//             The u32 scans cannot wrap, so the differences are exact.
+constexpr u32 kPartsSliceWaves = kCumsumWaves - 2u; // wavefronts of cumsum_parts_rows_kernel that walk slices
+constexpr u32 kPartsStartsWave = kCumsumWaves - 2u; // ... the one that walks the starts row; the last one walks the selection rows
+static_assert((kSegBits + kCumsumWaves * kSegGroups) * sizeof(u32) + kCumsumBlocks * (sizeof(u64) + sizeof(u32)) <= 160u * 1024u,
+              "one workgroup fits a CU's LDS");
+
+// group g of a segment of nvalid groups and `rows` rows in front of n_rows: the bits of its rows
+__device__ __forceinline__ u32 rows_mask(u32 g, u32 nvalid, u32 rows) {
+    const u32 full = rows / 31u, rest = rows % 31u;
+    return g >= nvalid ? 0u : g < full ? kOnes31 : g == full ? (1u << rest) - 1u : 0u;
+}
+
+// the starts row of segment seg walked under OR into the zeroed image, then clipped to the rows in front of n_rows
+__device__ __forceinline__ void starts_walk(const BsiCumsumPartsArgs &a, u32 *acc, u64 seg, u32 nvalid, u32 rows, u32 lane) {
+    const ListOp m_or = list_op(1u);
+    const bool ok = list_walk(a.starts, 1u, seg, nvalid, m_or.fill, acc, lane, [&](u32) -> const ListOp & { return m_or; }, [](u32) {});
+    if (!ok) report_stream_error(a.c.ctrl, lane);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+#pragma unroll
+    for (u32 i = 0; i < kSegGroups / 64u; ++i) acc[64u * i + lane] &= rows_mask(64u * i + lane, nvalid, rows);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+}
+
+__global__ __launch_bounds__(kCumsumWaves * 64) void cumsum_parts_totals_kernel(const BsiCumsumPartsArgs a) {
+    __shared__ __attribute__((aligned(16))) u32 s_acc[kCumsumWaves][kSegGroups];
+    __shared__ u64 s_part[kCumsumWaves];
+    const u32 wave = wave_id(), lane = lane_id();
+    u32 *acc = s_acc[wave];
+    const u32 *sel = s_acc[kCumsumSliceWaves];
+    u32 w_lo, w_hi;
+    slice_share(a.c.n_slices_val, wave, w_lo, w_hi);
+
+#pragma nounroll
+    for (u64 seg = blockIdx.x; seg < a.c.n_segments; seg += gridDim.x) { // (workgroup-uniform)
+        const u32 nvalid = segment_groups(a.c.groups, seg);
+        image_fill(acc, 0u, lane);
+        if (wave == kCumsumSliceWaves) {
+            const u32 rows = segment_rows(a.c.n_rows, seg);
+            starts_walk(a, acc, seg, nvalid, rows, lane);
+            u32 last = 0u; // 1 + the last start among the lane's groups, 0: none
+#pragma unroll
+            for (u32 i = 0; i < kSegGroups / 64u; ++i) {
+                const u32 g = 64u * i + lane, w = acc[g];
+                if (w != 0u) last = 31u * g + 32u - (u32)__clz(w);
+            }
+            last = (u32)__builtin_amdgcn_readlane((int)wave_scan_max32(last), 63);
+            if (lane == 0) a.records[seg].has_start = last != 0u ? 1ull : 0ull;
+            const u32 first = last != 0u ? last - 1u : 0u; // the rows from here on are the segment's tail
+            selection_preset(acc, a.c.n_rows, seg, nvalid, lane);
+            selection_walk(a.c, acc, seg, nvalid, lane);
+#pragma unroll
+            for (u32 i = 0; i < kSegGroups / 64u; ++i) {
+                const u32 g = 64u * i + lane;
+                acc[g] &= g < first / 31u ? 0u : g == first / 31u ? (kOnes31 << (first % 31u)) & kOnes31 : kOnes31;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        }
+        __syncthreads();
+
+        u64 sum = 0; // the lane's share of the wavefront's
+        auto count = [&](u32 sig) { // the image's set bits among the selected rows of the tail, at weight 2^sig
+            u32 c = 0;
+#pragma unroll
+            for (u32 i = 0; i < kSegGroups / 64u; ++i) c += (u32)__popc((wave < kCumsumSliceWaves ? acc[64u * i + lane] : kOnes31) & sel[64u * i + lane]);
+            sum += (u64)c << sig;
+        };
+        if (wave < kCumsumSliceWaves) {
+            if (w_lo < w_hi) walk_slices(a.c, w_lo, w_hi, seg, nvalid, acc, lane, count); // (wave-uniform)
+        } else if (a.c.n_slices_val == 0u) {
+            count(0u);
+        }
+        sum = wave_sum(sum);
+        if (lane == 0) s_part[wave] = sum;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            u64 total = 0;
+#pragma unroll
+            for (u32 w = 0; w < kCumsumWaves; ++w) total += s_part[w];
+            a.records[seg].sum = total;
+        }
+        // (no third barrier, as above; has_start went out from wavefront 7's own registers)
+    }
+}
+
+struct PartsPair {
+    u64 s;
+    u32 f;
+};
+// x in front of y
+__device__ __forceinline__ PartsPair parts_fold(PartsPair x, PartsPair y) { return {y.f != 0u ? y.s : x.s + y.s, x.f | y.f}; }
+
+// records[i].sum becomes what flows into segment i: the fold of records[0 .. i)
+__global__ __launch_bounds__(kScanWaves * 64) void cumsum_parts_scan_kernel(BsiCumsumPartsRecord *records, u64 n) {
+    __shared__ u64 s_wave_s[kScanWaves];
+    __shared__ u32 s_wave_f[kScanWaves];
+    const u32 wave = wave_id(), lane = lane_id();
+    PartsPair carry = {0ull, 0u}; // the fold of the rounds in front (workgroup-uniform)
+#pragma nounroll
+    for (u64 i0 = 0; i0 < n; i0 += (u64)kScanWaves * 64u * kScanPer) {
+        const u64 first = i0 + (u64)threadIdx.x * kScanPer;
+        PartsPair v[kScanPer], mine = {0ull, 0u};
+#pragma unroll
+        for (u32 i = 0; i < kScanPer; ++i) {
+            v[i] = {0ull, 0u};
+            if (first + i < n) v[i] = {records[first + i].sum, (u32)records[first + i].has_start};
+            mine = parts_fold(mine, v[i]);
+        }
+        PartsPair incl = mine;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const PartsPair t = {__shfl_up(incl.s, off), (u32)__shfl_up((int)incl.f, off)};
+            if (lane >= (u32)off) incl = parts_fold(t, incl);
+        }
+        if (lane == 63u) {
+            s_wave_s[wave] = incl.s;
+            s_wave_f[wave] = incl.f;
+        }
+        PartsPair excl = {__shfl_up(incl.s, 1), (u32)__shfl_up((int)incl.f, 1)};
+        if (lane == 0u) excl = {0ull, 0u};
+        __syncthreads();
+        PartsPair before = carry, all = carry;
+#pragma unroll
+        for (u32 w = 0; w < kScanWaves; ++w) {
+            const PartsPair x = {s_wave_s[w], s_wave_f[w]};
+            if (w < wave) before = parts_fold(before, x);
+            all = parts_fold(all, x);
+        }
+        PartsPair run = parts_fold(before, excl);
+#pragma unroll
+        for (u32 i = 0; i < kScanPer; ++i) {
+            if (first + i < n) records[first + i].sum = run.s;
+            run = parts_fold(run, v[i]);
+        }
+        carry = all;
+        __syncthreads(); // the next round's wave totals
+    }
+}
+
+// load_block with the starts beside it: `heads` gets bit t where the lane's row of step t starts a partition
+template <u32 kSteps>
+__device__ __forceinline__ u32 load_block_parts(const u32 *s_rows, const u32 *sel, const u32 *st, u32 n_slices_val, u32 blk, u32 lane, u32 (&v)[kSteps],
+                                                u32 &heads) {
+    u32 row0 = (u32)kCumsumBlockRows * blk + lane;
+    asm volatile("" : "+v"(row0)); // (opaque, as in load_block)
+    u32 picked = 0u, hd = 0u;
+#pragma unroll
+    for (u32 t = 0; t < kSteps; ++t) {
+        const u32 r = row0 + 64u * t;
+        const u32 bit = (sel[r / 31u] >> (r % 31u)) & 1u;
+        picked |= bit << t;
+        hd |= ((st[r / 31u] >> (r % 31u)) & 1u) << t;
+        v[t] = n_slices_val == 0u ? bit : s_rows[r] & (0u - bit); // (wave-uniform choice)
+    }
+    heads = hd;
+    return picked;
+}
+
+// block blk's pair (wave-uniform): whether it holds a start, and the sum of its selected values at or behind its last one
+template <u32 kSteps>
+__device__ __forceinline__ PartsPair block_pair(const u32 *s_rows, const u32 *sel, const u32 *st, u32 n_slices_val, u32 blk, u32 lane) {
+    u32 v[kSteps], heads;
+    load_block_parts<kSteps>(s_rows, sel, st, n_slices_val, blk, lane, v, heads);
+    // 1 + the block row (64 t + lane) of the lane's last start
+    u32 last = heads != 0u ? 64u * (31u - (u32)__clz(heads)) + lane + 1u : 0u;
+    last = (u32)__builtin_amdgcn_readlane((int)wave_scan_max32(last), 63);
+    const u32 first = last != 0u ? last - 1u : 0u;
+    u64 sum = 0;
+#pragma unroll
+    for (u32 t = 0; t < kSteps; ++t) sum += 64u * t + lane >= first ? v[t] : 0u;
+    return {uniform64(wave_sum(sum)), last != 0u ? 1u : 0u};
+}
+
+// scan_block with the starts: a step without a head is scan_block's
+template <u32 kSteps, bool kWide, bool kHigh>
+__device__ __forceinline__ void scan_block_parts(const BsiCumsumArgs &a, const u32 *s_rows, const u32 *sel, const u32 *st, u64 seg, u32 rows, u32 blk,
+                                                 u32 lane, u64 base) {
+    u32 lo[kSteps], hi[kSteps];
+    u32 have = 0u; // lane j: word j of the block's selection
+    {
+        u32 v[kSteps], heads;
+        const u32 picked = load_block_parts<kSteps>(s_rows, sel, st, a.n_slices_val, blk, lane, v, heads);
+        const u32 row0 = (u32)kCumsumBlockRows * blk + lane;
+        const u64 le = ~0ull >> (63u - lane); // the lanes at or in front of this one
+        u64 carry = base; // the sum in front of the step since the last start (wave-uniform)
+#pragma unroll
+        for (u32 t = 0; t < kSteps; ++t) {
+            const u32 x = v[t];
+            const u64 s = kWide ? (u64)wave_scan_incl32(x & 0xFFFFu) + ((u64)wave_scan_incl32(x >> 16) << 16) : (u64)wave_scan_incl32(x);
+            const u64 hm = __ballot(((heads >> t) & 1u) != 0u);
+            u64 r;
+            if (hm == 0ull) { // (wave-uniform)
+                r = carry + s - (a.exclusive != 0u ? x : 0u);
+                carry += ((u64)(kWide ? (u32)__builtin_amdgcn_readlane((int)(u32)(s >> 32), 63) : 0u) << 32) | (u32)__builtin_amdgcn_readlane((int)(u32)s, 63);
+            } else {
+                const u64 e = s - x; // the exclusive scan
+                const u64 mine = hm & le;
+                const u32 hl = 63u - (u32)__clzll((long long)(mine | 1ull)); // the lane's head lane (lane 0 where it has none: not used)
+                const u64 eh = ((u64)(kWide ? (u32)__builtin_amdgcn_ds_bpermute((int)(4u * hl), (int)(u32)(e >> 32)) : 0u) << 32) |
+                               (u32)__builtin_amdgcn_ds_bpermute((int)(4u * hl), (int)(u32)e);
+                r = (mine != 0ull ? s - eh : carry + s) - (a.exclusive != 0u ? x : 0u);
+                const int hlast = 63 - (int)__clzll((long long)hm); // (scalar)
+                const u64 s63 = ((u64)(kWide ? (u32)__builtin_amdgcn_readlane((int)(u32)(s >> 32), 63) : 0u) << 32) | (u32)__builtin_amdgcn_readlane((int)(u32)s, 63);
+                const u64 el = ((u64)(kWide ? (u32)__builtin_amdgcn_readlane((int)(u32)(e >> 32), hlast) : 0u) << 32) | (u32)__builtin_amdgcn_readlane((int)(u32)e, hlast);
+                carry = s63 - el;
+            }
+            const bool on = ((picked >> t) & 1u) != 0u;
+            if (!((on || a.all_rows != 0u) && row0 + 64u * t < rows)) r = 0ull;
+            lo[t] = (u32)r;
+            hi[t] = (u32)(r >> 32);
+            const u64 m = __ballot(on);
+            have = put_lane((u32)m, 2u * t, have);
+            have = put_lane((u32)(m >> 32), 2u * t + 1u, have);
+        }
+    }
+    const bool store = lane < 2u * kSteps; // (the half block: 32 words)
+    u32 *out = a.matrix + (seg * kSegWords + kCumsumBlockWords * blk + lane); // row 0 of the matrix; every row is n_words further
+    u32 b = a.n_slices_out;
+    if (kHigh) {
+#pragma nounroll
+        for (; b > 32u; --b) {
+            const u32 w = slice_words(hi, 1u << (b - 33u));
+            if (store) *out = w;
+            out += a.n_words;
+        }
+    }
+#pragma nounroll
+    for (; b > 0u; --b) {
+        const u32 w = slice_words(lo, 1u << (b - 1u));
+        if (store) *out = w;
+        out += a.n_words;
+    }
+    if (a.all_rows == 0u && store) *out = have;
+}
+
+template <bool kWide, bool kHigh>
+__global__ __launch_bounds__(kCumsumWaves * 64) void cumsum_parts_rows_kernel(const BsiCumsumPartsArgs pa) {
+    __shared__ __attribute__((aligned(16))) u32 s_rows[kSegBits];
+    __shared__ __attribute__((aligned(16))) u32 s_acc[kCumsumWaves][kSegGroups];
+    __shared__ u64 s_block[kCumsumBlocks];
+    __shared__ u32 s_block_f[kCumsumBlocks];
+    const BsiCumsumArgs &a = pa.c;
+    const u32 wave = wave_id(), lane = lane_id();
+    u32 *acc = s_acc[wave];
+    const u32 *sel = s_acc[kCumsumSliceWaves];
+    const u32 *st = s_acc[kPartsStartsWave];
+    const u32 nv = a.n_slices_val;
+    const u32 per = (nv + kPartsSliceWaves - 1u) / kPartsSliceWaves; // the value's slices shared among six wavefronts
+    const u32 w_lo = min(wave * per, nv), w_hi = wave < kPartsSliceWaves ? min(w_lo + per, nv) : w_lo;
+    const bool last_half = wave + kCumsumWaves == kCumsumBlocks - 1u; // (wave-uniform: the wavefront whose second block is the half one)
+
+#pragma nounroll
+    for (u64 seg = blockIdx.x; seg < a.n_segments; seg += gridDim.x) { // (workgroup-uniform)
+        const u32 nvalid = segment_groups(a.groups, seg);
+        const u32 rows = segment_rows(a.n_rows, seg);
+
+        if (nv != 0u) // (without value slices the rows' words are never read)
+            for (u32 p = threadIdx.x * 4u; p < kSegBits; p += kCumsumWaves * 64u * 4u) *reinterpret_cast<uint4 *>(s_rows + p) = make_uint4(0u, 0u, 0u, 0u);
+        if (wave < kCumsumSliceWaves)
+            image_fill(acc, 0u, lane);
+        else
+            selection_preset(acc, a.n_rows, seg, nvalid, lane);
+        __syncthreads();
+
+        if (wave < kPartsSliceWaves) {
+            if (w_lo < w_hi) // (wave-uniform)
+                walk_slices(a, w_lo, w_hi, seg, nvalid, acc, lane, [&](u32 sig) { fold_slice_bits(acc, s_rows, 0u, kSegGroups / 64u, sig, lane); });
+        } else if (wave == kPartsStartsWave) {
+            starts_walk(pa, acc, seg, nvalid, rows, lane);
+        } else {
+            selection_walk(a, acc, seg, nvalid, lane);
+        }
+        __syncthreads();
+
+        {
+            const PartsPair t0 = block_pair<kCumsumBlockSteps>(s_rows, sel, st, nv, wave, lane);
+            const PartsPair t1 = last_half ? block_pair<kCumsumBlockSteps / 2u>(s_rows, sel, st, nv, kCumsumBlocks - 1u, lane)
+                                           : block_pair<kCumsumBlockSteps>(s_rows, sel, st, nv, wave + kCumsumWaves, lane);
+            if (lane == 0) {
+                s_block[wave] = t0.s;
+                s_block_f[wave] = t0.f;
+                s_block[wave + kCumsumWaves] = t1.s;
+                s_block_f[wave + kCumsumWaves] = t1.f;
+            }
+        }
+        __syncthreads();
+
+        u64 base = pa.records[seg].sum; // (scanned: what flows into the segment)
+#pragma nounroll
+        for (u32 b = 0; b < wave; ++b) base = s_block_f[b] != 0u ? s_block[b] : base + s_block[b];
+        base = uniform64(base);
+        scan_block_parts<kCumsumBlockSteps, kWide, kHigh>(a, s_rows, sel, st, seg, rows, wave, lane, base);
+#pragma nounroll
+        for (u32 b = wave; b < wave + kCumsumWaves; ++b) base = s_block_f[b] != 0u ? s_block[b] : base + s_block[b];
+        base = uniform64(base);
+        if (last_half)
+            scan_block_parts<kCumsumBlockSteps / 2u, kWide, kHigh>(a, s_rows, sel, st, seg, rows, kCumsumBlocks - 1u, lane, base);
+        else
+            scan_block_parts<kCumsumBlockSteps, kWide, kHigh>(a, s_rows, sel, st, seg, rows, wave + kCumsumWaves, lane, base);
+        __syncthreads(); // the next segment clears the rows and the images
+    }
+}
+
 } // namespace
+
+hipError_t launch_bsi_cumsum_parts(const BsiCumsumPartsArgs &a, hipStream_t s) {
+    if (a.c.n_segments == 0) return hipSuccess;
+    const dim3 grid((unsigned)(a.c.n_segments < kCumsumGridItems ? a.c.n_segments : kCumsumGridItems)), block(kCumsumWaves * 64);
+    hipLaunchKernelGGL(cumsum_parts_totals_kernel, grid, block, 0, s, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(cumsum_parts_scan_kernel, dim3(1), dim3(kScanWaves * 64), 0, s, a.records, a.c.n_segments);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const bool wide = a.c.n_slices_val > kCumsumNarrowBits, high = a.c.n_slices_out > 32u;
+    if (wide && high)
+        hipLaunchKernelGGL((cumsum_parts_rows_kernel<true, true>), grid, block, 0, s, a);
+    else if (wide)
+        hipLaunchKernelGGL((cumsum_parts_rows_kernel<true, false>), grid, block, 0, s, a);
+    else if (high)
+        hipLaunchKernelGGL((cumsum_parts_rows_kernel<false, true>), grid, block, 0, s, a);
+    else
+        hipLaunchKernelGGL((cumsum_parts_rows_kernel<false, false>), grid, block, 0, s, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_bsi_cumsum(const BsiCumsumArgs &a, hipStream_t s) {
     if (a.n_segments == 0) return hipSuccess;

@@ -505,6 +505,20 @@ struct BsiCumsumArgs {
 };
 hipError_t launch_bsi_cumsum(const BsiCumsumArgs &a, hipStream_t s); // the segment totals, their scan, the rows
 
+// wah_bsi_cumsum_parts_indexed_device (wah_cumsum.hip): the same, starting again at every row set in `starts`, ONE row.  c: as
+// above, c.totals unused.  records: n_segments of them in the scratch: whether the segment holds a start and the sum of its
+// selected values at or behind its last one, then -- scanned in place -- in `sum` what flows into the segment.
+struct BsiCumsumPartsRecord {
+    uint64_t sum;
+    uint64_t has_start; // 0 or 1
+};
+struct BsiCumsumPartsArgs {
+    BsiCumsumArgs c;
+    const BitopListOperand *starts;
+    BsiCumsumPartsRecord *records;
+};
+hipError_t launch_bsi_cumsum_parts(const BsiCumsumPartsArgs &a, hipStream_t s);
+
 // ... on operands of few words per segment: their runs merged in the compressed domain, one lane per segment
 // (wah_bitop_runs.hip): count pass, scan of the tile totals, write pass
 struct BitopRunsArgs {

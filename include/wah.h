@@ -1086,8 +1086,8 @@ int wah_bsi_map_status(void *d_scratch, uint64_t n_words, uint64_t n_slices_out,
  * device sees is reported by wah_bsi_cumsum_status(), which synchronises the stream: WAH_ERR_STREAM for everything the list call
  * refuses in a row of either table, EVERY row's every segment being walked whatever is selected; then the compress passes'
  * verdict (WAH_ERR_CAPACITY: nothing is written at or behind d_out[out_capacity_words]).  The output of a refused call is
- * unspecified.  wah_bsi_cumsum_status(NULL, ...): WAH_ERR_ARG.  Not here: sums that start again per partition, signed values,
- * values above 32 slices. */
+ * unspecified.  wah_bsi_cumsum_status(NULL, ...): WAH_ERR_ARG.  Not here: signed values, values above 32 slices.  (Sums that
+ * start again per partition: wah_bsi_cumsum_parts_indexed_device, below.) */
 #define WAH_CUMSUM_EXCLUSIVE 2u /* flags: the sum runs over the rows in front of a row, not up to it */
 #define WAH_CUMSUM_ALL_ROWS 4u  /* flags: unselected rows carry the sum forward, and the result has no existence row */
 size_t wah_bsi_cumsum_scratch_bytes(uint64_t n_words, uint64_t n_slices_out, unsigned flags);
@@ -1096,6 +1096,46 @@ int wah_bsi_cumsum_indexed_device(uint64_t n_words, uint64_t n_rows, uint64_t n_
                                   uint32_t *d_out, uint64_t out_capacity_words, uint64_t *d_out_words, uint64_t *d_out_offsets,
                                   void *d_scratch, size_t scratch_bytes, void *stream);
 int wah_bsi_cumsum_status(void *d_scratch, uint64_t n_words, uint64_t n_slices_out, unsigned flags, void *stream);
+
+/* The RUNNING SUM PER PARTITION: wah_bsi_cumsum_indexed_device with a sum that starts again at every row of a bitmap of partition
+ * starts -- `SELECT SUM(x) OVER (PARTITION BY g ORDER BY rowid) FROM t WHERE f` on a table clustered by g, without value slices
+ * `ROW_NUMBER() OVER (PARTITION BY g)`, and with the starts the complement of the filter the length of the current streak of
+ * selected rows.  Selection, value, flags (WAH_BSI_EXISTS, WAH_CUMSUM_EXCLUSIVE, WAH_CUMSUM_ALL_ROWS), the result's layout,
+ * rows_out, the compress road and the status call's behaviour are those of wah_bsi_cumsum_indexed_device.
+ *   STARTS: d_starts names ONE indexed bitmap of n_words words in device memory, in the operand form of a filter row, 8-byte
+ *   aligned.  Row p STARTS A PARTITION if its bit is set and p < n_rows -- whether or not p is selected.  Bits at or behind n_rows
+ *   and pad bits have no effect.
+ *   RESULT: let s(p) be the largest start row <= p, or 0 if there is none; R[p] = (the sum of the values of the selected rows q
+ *   with s(p) <= q <= p) mod 2^n_slices_out, with WAH_CUMSUM_EXCLUSIVE over s(p) <= q < p.  A selected start row holds its own
+ *   value, under EXCLUSIVE 0.  With WAH_CUMSUM_ALL_ROWS an unselected row carries its partition's running value forward, and an
+ *   unselected start row holds 0.  Without value slices the result is the running COUNT within the partition.  A starts bitmap
+ *   with no bit set gives, word for word, what wah_bsi_cumsum_indexed_device gives.  The sum is carried in 64 bits and cut only
+ *   where it is stored.
+ * The same three launches, none of which waits for another workgroup, with the segmented operator on pairs (has_start, sum),
+ * (f1, s1) o (f2, s2) = (f1 | f2, f2 ? s2 : s1 + s2), in the place of addition: per segment whether it holds a start and the sum of
+ * the selected values at or behind its last one (popcounts under a "rows at or behind the last start" mask); one workgroup scans
+ * the pairs into what flows into each segment; the rows kernel folds block pairs the same way and, in a step of 64 rows that
+ * holds a start, subtracts from the ordinary scan its exclusive value at the lane's own head lane.
+ *   d_scratch: the builder's layout and one record of 16 bytes per segment behind it, 256-byte aligned, no initialisation:
+ *   wah_bsi_cumsum_parts_scratch_bytes(n_words, n_slices_out, flags) = wah_bsi_build_scratch_bytes(n_words, rows_out) + 16
+ *   (n_words / 992) rounded up to a multiple of 256.
+ * Errors the host can see come back before any HIP call, in the order of wah_bsi_cumsum_indexed_device, with texts of this call's
+ * own: (1) n_slices_val above 32, n_slices_out outside 1 .. 64, unknown flag bits, n_filters above the cap; (2) a null or
+ * misaligned scratch or output, a d_val that does not go with n_slices_val and the flags, a null filter table with n_filters > 0,
+ * a null or misaligned d_starts; (3) n_words 0, no multiple of 992 or >= 2^40, rows_out * n_words >= 2^40, n_rows > 32 n_words --
+ * all WAH_ERR_ARG; then too small a scratch: WAH_ERR_WORKSPACE.  Everything only the device sees is reported by
+ * wah_bsi_cumsum_parts_status(), which synchronises the stream: WAH_ERR_STREAM for everything the list call refuses in a row of
+ * either table or in the starts row, EVERY row's every segment being walked; then the compress passes' verdict.  Nothing is read
+ * back: the call is asynchronous on `stream`, allocates nothing and can be captured in a graph.  The output of a refused call is
+ * unspecified.  wah_bsi_cumsum_parts_status(NULL, ...): WAH_ERR_ARG.  Not here: partition totals broadcast to every row (a
+ * backward pass), signed values, values above 32 slices. */
+size_t wah_bsi_cumsum_parts_scratch_bytes(uint64_t n_words, uint64_t n_slices_out, unsigned flags);
+int wah_bsi_cumsum_parts_indexed_device(uint64_t n_words, uint64_t n_rows, uint64_t n_filters, const wah_bitop_operand *d_filters,
+                                        uint64_t n_slices_val, const wah_bitop_operand *d_val, const wah_bitop_operand *d_starts,
+                                        uint64_t n_slices_out, unsigned flags, uint32_t *d_out, uint64_t out_capacity_words,
+                                        uint64_t *d_out_words, uint64_t *d_out_offsets, void *d_scratch, size_t scratch_bytes,
+                                        void *stream);
+int wah_bsi_cumsum_parts_status(void *d_scratch, uint64_t n_words, uint64_t n_slices_out, unsigned flags, void *stream);
 
 /* The order statistics PER GROUP in ONE call -- `SELECT g, h, MIN(x), MAX(x), median(x) WHERE <filter> GROUP BY g, h`: for every
  * group g and every query q the value of rank q among the rows that `filters AND group g's rows` select, over ONE bit-sliced
