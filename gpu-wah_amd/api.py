@@ -114,6 +114,9 @@ ABI_SYMBOLS = {
     "wah_bsi_cumsum_parts_scratch_bytes": (_sz, [_u64, _u64, ctypes.c_uint]),
     "wah_bsi_cumsum_parts_indexed_device": (_int, [_u64, _u64, _u64, _vp, _u64, _vp, _vp, _u64, ctypes.c_uint, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
     "wah_bsi_cumsum_parts_status": (_int, [_vp, _u64, _u64, ctypes.c_uint, _vp]),
+    "wah_bsi_total_parts_scratch_bytes": (_sz, [_u64, _u64, ctypes.c_uint]),
+    "wah_bsi_total_parts_indexed_device": (_int, [_u64, _u64, _u64, _vp, _u64, _vp, _vp, _u64, ctypes.c_uint, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
+    "wah_bsi_total_parts_status": (_int, [_vp, _u64, _u64, ctypes.c_uint, _vp]),
     "wah_from_positions_max_words": (_u64, [_u64, _u64, _u64]),
     "wah_from_positions_scratch_bytes": (_sz, [_u64, _u64]),
     "wah_from_positions_device": (_int, [_u64, _u64, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
@@ -1350,6 +1353,15 @@ def bsi_cumsum_parts_device(val_table, n_words, n_rows, n_bits_val, n_bits_out, 
     holds the sum of the values of the selected rows q with s(p) <= q <= p (exclusive=True: q < p), s(p) the last start at or in
     front of p, row 0 without one.  Everything else -- tables, flags, the result, scratch / out / out_offsets / check -- as
     bsi_cumsum_device; the status call is wah_bsi_cumsum_parts_status."""
+    flags = (BSI_EXISTS if exists else 0) | (CUMSUM_EXCLUSIVE if exclusive else 0) | (CUMSUM_ALL_ROWS if all_rows else 0)
+    return _bsi_parts_call("bsi_cumsum_parts", val_table, n_words, n_rows, n_bits_val, n_bits_out, starts, filters, exists, flags, all_rows,
+                           scratch, out, out_offsets, check)
+
+
+def _bsi_parts_call(name, val_table, n_words, n_rows, n_bits_val, n_bits_out, starts, filters, exists, flags, all_rows, scratch, out, out_offsets,
+                    check):
+    """bsi_cumsum_parts_device's and bsi_total_parts_device's road: the argument checks, the three tables and the call
+    wah_<name>_indexed_device with its scratch_bytes and status calls."""
     n, r, kv, k_out = int(n_words), int(n_rows), int(n_bits_val), int(n_bits_out)
     if not (0 <= kv <= 32 and 1 <= k_out <= 64):
         raise WahError("a value of 0 to 32 slices and a result of 1 to 64")
@@ -1367,14 +1379,27 @@ def bsi_cumsum_parts_device(val_table, n_words, n_rows, n_bits_val, n_bits_out, 
     if any(t is not None and t.device != st.device for t in (vt, ft)):
         raise WahError("the starts row, the filter table and the value table are on one device")
     f = 0 if ft is None else int(ft.shape[0])
-    flags = (BSI_EXISTS if exists else 0) | (CUMSUM_EXCLUSIVE if exclusive else 0) | (CUMSUM_ALL_ROWS if all_rows else 0)
     rows_out = k_out + (0 if all_rows else 1)
+    call, size, status = (getattr(lib(), f"wah_{name}_{tail}") for tail in ("indexed_device", "scratch_bytes", "status"))
     return _compressed_streams(
-        "wah_bsi_cumsum_parts_indexed_device", "bsi_cumsum_parts", st.device, rows_out * (n // 992) + 1, _ROWS_OUT_OFFSETS,
-        lambda: lib().wah_bsi_cumsum_parts_scratch_bytes(n, k_out, flags), lambda: max_compressed_words(rows_out * n),
-        lambda *tail: lib().wah_bsi_cumsum_parts_indexed_device(n, r, f, ft.data_ptr() if f else None, kv, None if vt is None else vt.data_ptr(),
-                                                                st.data_ptr(), k_out, flags, *tail),
-        lambda sc, sp: lib().wah_bsi_cumsum_parts_status(sc, n, k_out, flags, sp), scratch, out, out_offsets, check)
+        f"wah_{name}_indexed_device", name, st.device, rows_out * (n // 992) + 1, _ROWS_OUT_OFFSETS,
+        lambda: size(n, k_out, flags), lambda: max_compressed_words(rows_out * n),
+        lambda *tail: call(n, r, f, ft.data_ptr() if f else None, kv, None if vt is None else vt.data_ptr(), st.data_ptr(), k_out, flags, *tail),
+        lambda sc, sp: status(sc, n, k_out, flags, sp), scratch, out, out_offsets, check)
+
+
+def bsi_total_parts_device(val_table, n_words, n_rows, n_bits_val, n_bits_out, starts, filters=None, exists=False, all_rows=False, scratch=None,
+                           out=None, out_offsets=None, check=True):
+    """The PARTITION'S TOTAL IN EVERY ROW (wah_bsi_total_parts_indexed_device): `SUM(x) OVER (PARTITION BY g) ... WHERE f` on a table
+    clustered by g, and with n_bits_val == 0 COUNT(*) OVER (PARTITION BY g).  starts as bsi_cumsum_parts_device's.  Row p of the
+    result holds the sum of the values of the selected rows from s(p), the last start at or in front of p (row 0 without one), up to
+    the row in front of the next start behind p (the last row in front of n_rows without one); with all_rows=True every row in
+    front of n_rows holds it, otherwise the selected ones.  No start at all: the grand total in every row.  Everything else --
+    tables, exists, the result, scratch / out / out_offsets / check -- as bsi_cumsum_parts_device; there is no exclusive form; the
+    status call is wah_bsi_total_parts_status."""
+    flags = (BSI_EXISTS if exists else 0) | (CUMSUM_ALL_ROWS if all_rows else 0)
+    return _bsi_parts_call("bsi_total_parts", val_table, n_words, n_rows, n_bits_val, n_bits_out, starts, filters, exists, flags, all_rows, scratch,
+                           out, out_offsets, check)
 
 
 def positions_device(stream, seg_offsets, n_words, first=0, limit=None, out=None, scratch=None, check=True):

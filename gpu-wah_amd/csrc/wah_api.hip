@@ -2539,6 +2539,61 @@ int wah_bsi_cumsum_parts_status(void *d_scratch, uint64_t n_words, uint64_t n_sl
     return scratch_status_then(bsi_build_layout(n_words, cumsum_rows_out(n_slices_out, flags)).ws_c, d_scratch, stream);
 }
 
+// The partition's total in every one of its rows (wah_cumsum.hip).  The road above with records of 24 bytes per segment:
+// (head, tail, has_start), head and tail scanned in place from behind and from the front.  No WAH_CUMSUM_EXCLUSIVE.
+namespace {
+constexpr unsigned kTotalPartsFlags = WAH_BSI_EXISTS | WAH_CUMSUM_ALL_ROWS;
+inline size_t total_parts_records_bytes(uint64_t n_words) { return round256((size_t)(n_words / wah::kSegWords) * sizeof(wah::BsiTotalPartsRecord)); }
+} // namespace
+
+size_t wah_bsi_total_parts_scratch_bytes(uint64_t n_words, uint64_t n_slices_out, unsigned flags) {
+    return bsi_build_layout(n_words, cumsum_rows_out(n_slices_out, flags)).total + total_parts_records_bytes(n_words);
+}
+
+int wah_bsi_total_parts_indexed_device(uint64_t n_words, uint64_t n_rows, uint64_t n_filters, const wah_bitop_operand *d_filters,
+                                       uint64_t n_slices_val, const wah_bitop_operand *d_val, const wah_bitop_operand *d_starts,
+                                       uint64_t n_slices_out, unsigned flags, uint32_t *d_out, uint64_t out_capacity_words,
+                                       uint64_t *d_out_words, uint64_t *d_out_offsets, void *d_scratch, size_t scratch_bytes, void *stream) {
+    g_err[0] = 0;
+    if (n_slices_val > 32 || n_slices_out < 1 || n_slices_out > WAH_BSI_MAX_SLICES || (flags & ~kTotalPartsFlags) || n_filters > wah::kGroupMaxFilters)
+        return refuse("partition totals: a value of at most 32 slices, a result of 1 to 64, no flag besides WAH_BSI_EXISTS and WAH_CUMSUM_ALL_ROWS, at most 64 filter rows", WAH_ERR_ARG);
+    const bool has_val = n_slices_val != 0 || (flags & WAH_BSI_EXISTS);
+    if (!scratch_ok(d_scratch) || !out_triple_ok(d_out, d_out_words, d_out_offsets) || has_val != (d_val != nullptr) || !aligned(d_val, 7) ||
+        (n_filters && !d_filters) || !aligned(d_filters, 7) || !d_starts || !aligned(d_starts, 7))
+        return refuse("partition totals: null or misaligned scratch or output, a value table that does not go with n_slices_val and WAH_BSI_EXISTS, a null or misaligned filter table, or a null or misaligned starts row", WAH_ERR_ARG);
+    const uint64_t rows_out = cumsum_rows_out(n_slices_out, flags);
+    if (n_words == 0 || n_words % wah::kSegWords || n_words >= (1ull << 40) || rows_out * n_words >= (1ull << 40) || n_rows > 32 * n_words)
+        return refuse("partition totals: slices of a multiple of 992 words, all slices of the result together fewer than 2^40 words, at most 32 n_words rows", WAH_ERR_ARG);
+    const BsiBuildLayout l = bsi_build_layout(n_words, rows_out);
+    if (scratch_bytes < l.total + total_parts_records_bytes(n_words)) return refuse("partition totals: scratch too small", WAH_ERR_WORKSPACE);
+    char *sc = static_cast<char *>(d_scratch);
+    const SegGeometry g = seg_geometry(n_words);
+    wah::BsiTotalPartsArgs a = {};
+    wah::BsiCumsumArgs &c = a.p.c;
+    c.filters = reinterpret_cast<const wah::BitopListOperand *>(d_filters);
+    c.val = reinterpret_cast<const wah::BitopListOperand *>(d_val);
+    a.p.starts = reinterpret_cast<const wah::BitopListOperand *>(d_starts);
+    a.records = reinterpret_cast<wah::BsiTotalPartsRecord *>(sc + l.total); // (a multiple of 256 bytes)
+    c.matrix = bsi_matrix(sc, l);
+    c.ctrl = reinterpret_cast<uint32_t *>(sc);
+    c.n_rows = n_rows;
+    c.n_words = n_words;
+    c.groups = g.groups;
+    c.n_segments = g.n_segments;
+    c.n_filters = (uint32_t)n_filters;
+    c.n_slices_val = (uint32_t)n_slices_val;
+    c.n_slices_out = (uint32_t)n_slices_out;
+    c.has_exists = (flags & WAH_BSI_EXISTS) ? 1u : 0u;
+    c.all_rows = (flags & WAH_CUMSUM_ALL_ROWS) ? 1u : 0u;
+    return sweep_then_compress(a, wah::launch_bsi_total_parts, "partition totals launch", n_words, rows_out, d_out, out_capacity_words, d_out_words,
+                               d_out_offsets, sc, l, stream);
+}
+
+int wah_bsi_total_parts_status(void *d_scratch, uint64_t n_words, uint64_t n_slices_out, unsigned flags, void *stream) {
+    // (first the kernels: everything the list call refuses in a row of the filter table, the value table or the starts row)
+    return scratch_status_then(bsi_build_layout(n_words, cumsum_rows_out(n_slices_out, flags)).ws_c, d_scratch, stream);
+}
+
 // ---------------------------------------------------------------------------
 // host-pointer entry points (the reference's API)
 // ---------------------------------------------------------------------------

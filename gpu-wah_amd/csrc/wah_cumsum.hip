@@ -643,7 +643,402 @@ __global__ __launch_bounds__(kCumsumWaves * 64) void cumsum_parts_rows_kernel(co
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// wah_bsi_total_parts_indexed_device: the partition's TOTAL in every one of its rows -- `SUM(x) OVER (PARTITION BY g)` without an
+// ORDER BY.  A row's total is the running sum at its partition's last row, so what the kernels above send forward has to come
+// back: the frame stays (three launches, no workgroup waits for another), every level keeps TWO sums beside has_start,
+//   head  the selected values in front of the first start (the whole item where it holds none): what it gives to the partition
+//         that is open in front of it,
+//   tail  the selected values at or behind the last start (the whole item likewise): what it gives to the one open behind it,
+// and is folded in both directions -- forward with the operator above on (has_start, tail), backward with its mirror on
+// (has_start, head): what flows in from BEHIND an item is the heads of the items behind it up to and including the first that
+// holds a start.
+// total_parts_records_kernel  cumsum_parts_totals_kernel with two masks: wavefront 7 finds the first and the last start of the starts
+//             row and leaves them in LDS, the selection stays whole, and every popcount is taken twice, under "rows in front of
+//             the first start" and under "rows at or behind the last start".  A record (head, tail, has_start) per segment, EVERY
+//             segment's.
+// total_parts_scan_kernel     ONE workgroup, both directions one after the other: cumsum_parts_scan_kernel's rounds over the tails
+//             from the front, then the same rounds over the heads from the end (entry k of a round is record n - 1 - k, so the
+//             short round is the last one and the carry pair crosses the same seams mirrored).  `tail` becomes what flows into
+//             the segment from the front, `head` what flows into it from behind.
+// total_parts_rows_kernel     cumsum_parts_rows_kernel's frame and footprint with a triple per block.  Per block the forward base is
+//             folded as there, the backward inflow from the heads of the blocks behind it (and the segment's where none of them
+//             holds a start).  The forward pass is the inclusive step above and leaves the segmented running sum r of every
+//             row in the two register arrays.  The backward pass walks the steps from the last to the first with a wave-uniform
+//             `after`, the total of the partition that is open at the step's end: a lane's total is r at the lane in front of
+//             the next head behind it in the step (one ds_bpermute per word) and `after` where there is none; behind a step
+//             with a first head at lane f, `after` is r[t][f - 1], for f = 0 r[t - 1][63], at t = 0 the block's forward base.
+//             A step without a head is one select.  Then clip, transpose and store as above.
+static_assert((kSegBits + kCumsumWaves * kSegGroups) * sizeof(u32) + kCumsumBlocks * (2u * sizeof(u64) + sizeof(u32)) <= 160u * 1024u,
+              "one workgroup fits a CU's LDS");
+
+__global__ __launch_bounds__(kCumsumWaves * 64) void total_parts_records_kernel(const BsiTotalPartsArgs ta) {
+    __shared__ __attribute__((aligned(16))) u32 s_acc[kCumsumWaves][kSegGroups];
+    __shared__ u64 s_head[kCumsumWaves];
+    __shared__ u64 s_tail[kCumsumWaves];
+    __shared__ u32 s_bound[2];
+    const BsiCumsumPartsArgs &a = ta.p;
+    const u32 wave = wave_id(), lane = lane_id();
+    u32 *acc = s_acc[wave];
+    const u32 *sel = s_acc[kCumsumSliceWaves];
+    u32 w_lo, w_hi;
+    slice_share(a.c.n_slices_val, wave, w_lo, w_hi);
+
+#pragma nounroll
+    for (u64 seg = blockIdx.x; seg < a.c.n_segments; seg += gridDim.x) { // (workgroup-uniform)
+        const u32 nvalid = segment_groups(a.c.groups, seg);
+        image_fill(acc, 0u, lane);
+        if (wave == kCumsumSliceWaves) {
+            const u32 rows = segment_rows(a.c.n_rows, seg);
+            starts_walk(a, acc, seg, nvalid, rows, lane);
+            u32 last = 0u; // 1 + the last start among the lane's groups, 0: none
+            u32 near = 0u; // 32768 - the first start among them, 0: none
+#pragma unroll
+            for (u32 i = 0; i < kSegGroups / 64u; ++i) {
+                const u32 g = 64u * i + lane, w = acc[g];
+                if (w != 0u) {
+                    last = 31u * g + 32u - (u32)__clz(w);
+                    if (near == 0u) near = 32768u - (31u * g + (u32)__builtin_ctz(w));
+                }
+            }
+            last = (u32)__builtin_amdgcn_readlane((int)wave_scan_max32(last), 63);
+            near = (u32)__builtin_amdgcn_readlane((int)wave_scan_max32(near), 63);
+            if (lane == 0) {
+                ta.records[seg].has_start = last != 0u ? 1ull : 0ull;
+                s_bound[0] = near != 0u ? 32768u - near : 31u * kSegGroups; // the rows in front of here are the segment's head
+                s_bound[1] = last != 0u ? last - 1u : 0u;                   // the rows from here on are its tail
+            }
+            selection_preset(acc, a.c.n_rows, seg, nvalid, lane);
+            selection_walk(a.c, acc, seg, nvalid, lane);
+        }
+        __syncthreads();
+
+        const u32 head_to = s_bound[0], tail_from = s_bound[1];
+        u64 sum_h = 0, sum_t = 0; // the lane's share of the wavefront's
+        auto count = [&](u32 sig) { // the image's set bits among the selected rows of the head and of the tail, at weight 2^sig
+            u32 ch = 0, ct = 0;
+#pragma unroll
+            for (u32 i = 0; i < kSegGroups / 64u; ++i) {
+                const u32 g = 64u * i + lane;
+                const u32 m = (wave < kCumsumSliceWaves ? acc[g] : kOnes31) & sel[g];
+                ch += (u32)__popc(m & (g < head_to / 31u ? kOnes31 : g == head_to / 31u ? (1u << (head_to % 31u)) - 1u : 0u));
+                ct += (u32)__popc(m & (g < tail_from / 31u ? 0u : g == tail_from / 31u ? (kOnes31 << (tail_from % 31u)) & kOnes31 : kOnes31));
+            }
+            sum_h += (u64)ch << sig;
+            sum_t += (u64)ct << sig;
+        };
+        if (wave < kCumsumSliceWaves) {
+            if (w_lo < w_hi) walk_slices(a.c, w_lo, w_hi, seg, nvalid, acc, lane, count); // (wave-uniform)
+        } else if (a.c.n_slices_val == 0u) {
+            count(0u);
+        }
+        sum_h = wave_sum(sum_h);
+        sum_t = wave_sum(sum_t);
+        if (lane == 0) {
+            s_head[wave] = sum_h;
+            s_tail[wave] = sum_t;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            u64 head = 0, tail = 0;
+#pragma unroll
+            for (u32 w = 0; w < kCumsumWaves; ++w) {
+                head += s_head[w];
+                tail += s_tail[w];
+            }
+            ta.records[seg].head = head;
+            ta.records[seg].tail = tail;
+        }
+        // (no third barrier, as above: the bounds were read behind the first barrier, wavefront 7 writes the next ones behind this one)
+    }
+}
+
+// One direction of the scan.  kBack false: records[i].tail becomes the fold of (has_start, tail) of records[0 .. i); true: entry k
+// is record n - 1 - k, and records[i].head becomes the fold of (has_start, head) of the records behind i, the nearest last.
+template <bool kBack>
+__device__ __forceinline__ void total_parts_scan_pass(BsiTotalPartsRecord *records, u64 n, u64 *s_wave_s, u32 *s_wave_f, u32 wave, u32 lane) {
+    PartsPair carry = {0ull, 0u}; // the fold of the rounds done (workgroup-uniform)
+#pragma nounroll
+    for (u64 i0 = 0; i0 < n; i0 += (u64)kScanWaves * 64u * kScanPer) {
+        const u64 first = i0 + (u64)threadIdx.x * kScanPer;
+        PartsPair v[kScanPer], mine = {0ull, 0u};
+#pragma unroll
+        for (u32 i = 0; i < kScanPer; ++i) {
+            v[i] = {0ull, 0u};
+            if (first + i < n) {
+                const BsiTotalPartsRecord &r = records[kBack ? n - 1u - (first + i) : first + i];
+                v[i] = {kBack ? r.head : r.tail, (u32)r.has_start};
+            }
+            mine = parts_fold(mine, v[i]);
+        }
+        PartsPair incl = mine;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const PartsPair t = {__shfl_up(incl.s, off), (u32)__shfl_up((int)incl.f, off)};
+            if (lane >= (u32)off) incl = parts_fold(t, incl);
+        }
+        if (lane == 63u) {
+            s_wave_s[wave] = incl.s;
+            s_wave_f[wave] = incl.f;
+        }
+        PartsPair excl = {__shfl_up(incl.s, 1), (u32)__shfl_up((int)incl.f, 1)};
+        if (lane == 0u) excl = {0ull, 0u};
+        __syncthreads();
+        PartsPair before = carry, all = carry;
+#pragma unroll
+        for (u32 w = 0; w < kScanWaves; ++w) {
+            const PartsPair x = {s_wave_s[w], s_wave_f[w]};
+            if (w < wave) before = parts_fold(before, x);
+            all = parts_fold(all, x);
+        }
+        PartsPair run = parts_fold(before, excl);
+#pragma unroll
+        for (u32 i = 0; i < kScanPer; ++i) {
+            if (first + i < n) {
+                BsiTotalPartsRecord &r = records[kBack ? n - 1u - (first + i) : first + i];
+                if (kBack)
+                    r.head = run.s;
+                else
+                    r.tail = run.s;
+            }
+            run = parts_fold(run, v[i]);
+        }
+        carry = all;
+        __syncthreads(); // the next round's wave totals
+    }
+}
+
+__global__ __launch_bounds__(kScanWaves * 64) void total_parts_scan_kernel(BsiTotalPartsRecord *records, u64 n) {
+    __shared__ u64 s_wave_s[kScanWaves];
+    __shared__ u32 s_wave_f[kScanWaves];
+    const u32 wave = wave_id(), lane = lane_id();
+    total_parts_scan_pass<false>(records, n, s_wave_s, s_wave_f, wave, lane);
+    total_parts_scan_pass<true>(records, n, s_wave_s, s_wave_f, wave, lane); // (other fields: a thread reads what it wrote itself or nobody wrote)
+}
+
+struct TotalTriple {
+    u64 head, tail;
+    u32 f;
+};
+
+// block blk's triple (wave-uniform): whether it holds a start, the sum of its selected values in front of its first one and at or
+// behind its last one
+template <u32 kSteps>
+__device__ __forceinline__ TotalTriple block_triple(const u32 *s_rows, const u32 *sel, const u32 *st, u32 n_slices_val, u32 blk, u32 lane) {
+    u32 v[kSteps], heads;
+    load_block_parts<kSteps>(s_rows, sel, st, n_slices_val, blk, lane, v, heads);
+    u32 last = heads != 0u ? 64u * (31u - (u32)__clz(heads)) + lane + 1u : 0u;         // 1 + the block row of the lane's last start
+    u32 near = heads != 0u ? 4096u - (64u * (u32)__builtin_ctz(heads) + lane) : 0u;    // 4096 - the block row of its first one
+    last = (u32)__builtin_amdgcn_readlane((int)wave_scan_max32(last), 63);
+    near = (u32)__builtin_amdgcn_readlane((int)wave_scan_max32(near), 63);
+    const u32 tail_from = last != 0u ? last - 1u : 0u, head_to = near != 0u ? 4096u - near : 64u * kSteps;
+    u64 head = 0, tail = 0;
+#pragma unroll
+    for (u32 t = 0; t < kSteps; ++t) {
+        head += 64u * t + lane < head_to ? v[t] : 0u;
+        tail += 64u * t + lane >= tail_from ? v[t] : 0u;
+    }
+    return {uniform64(wave_sum(head)), uniform64(wave_sum(tail)), last != 0u ? 1u : 0u};
+}
+
+// Block blk of segment seg: the totals of the partitions its rows lie in, stored as 2 kSteps words of every result row.  base: the
+// running sum in front of the block since the last start; back: what flows into the block from behind.
+template <u32 kSteps, bool kWide, bool kHigh>
+__device__ __forceinline__ void total_block(const BsiCumsumArgs &a, const u32 *s_rows, const u32 *sel, const u32 *st, u64 seg, u32 rows, u32 blk, u32 lane,
+                                            u64 base, u64 back) {
+    u32 lo[kSteps], hi[kSteps];
+    u32 picked, heads;
+    const u64 le = ~0ull >> (63u - lane); // the lanes at or in front of this one
+    u64 carry = base; // the sum in front of the step since the last start (wave-uniform)
+    {
+        // the forward pass: scan_block_parts' step, inclusive, for every row whether selected or not
+        u32 v[kSteps];
+        picked = load_block_parts<kSteps>(s_rows, sel, st, a.n_slices_val, blk, lane, v, heads);
+#pragma unroll
+        for (u32 t = 0; t < kSteps; ++t) {
+            const u32 x = v[t];
+            const u64 s = kWide ? (u64)wave_scan_incl32(x & 0xFFFFu) + ((u64)wave_scan_incl32(x >> 16) << 16) : (u64)wave_scan_incl32(x);
+            const u64 hm = __ballot(((heads >> t) & 1u) != 0u);
+            u64 r;
+            if (hm == 0ull) { // (wave-uniform)
+                r = carry + s;
+                carry += ((u64)(kWide ? (u32)__builtin_amdgcn_readlane((int)(u32)(s >> 32), 63) : 0u) << 32) | (u32)__builtin_amdgcn_readlane((int)(u32)s, 63);
+            } else {
+                const u64 e = s - x; // the exclusive scan
+                const u64 mine = hm & le;
+                const u32 hl = 63u - (u32)__clzll((long long)(mine | 1ull)); // the lane's head lane (lane 0 where it has none: not used)
+                const u64 eh = ((u64)(kWide ? (u32)__builtin_amdgcn_ds_bpermute((int)(4u * hl), (int)(u32)(e >> 32)) : 0u) << 32) |
+                               (u32)__builtin_amdgcn_ds_bpermute((int)(4u * hl), (int)(u32)e);
+                r = mine != 0ull ? s - eh : carry + s;
+                const int hlast = 63 - (int)__clzll((long long)hm); // (scalar)
+                const u64 s63 = ((u64)(kWide ? (u32)__builtin_amdgcn_readlane((int)(u32)(s >> 32), 63) : 0u) << 32) | (u32)__builtin_amdgcn_readlane((int)(u32)s, 63);
+                const u64 el = ((u64)(kWide ? (u32)__builtin_amdgcn_readlane((int)(u32)(e >> 32), hlast) : 0u) << 32) | (u32)__builtin_amdgcn_readlane((int)(u32)e, hlast);
+                carry = s63 - el;
+            }
+            lo[t] = (u32)r;
+            hi[t] = (u32)(r >> 32);
+        }
+    }
+    // the backward pass: `after` is the total of the partition that is open at the step's end (wave-uniform; the carry is now the
+    // running sum at the block's last row)
+    u64 after = carry + back;
+    u32 have = 0u; // lane j: word j of the block's selection
+    const u32 row0 = (u32)kCumsumBlockRows * blk + lane;
+#pragma unroll
+    for (u32 i = 0; i < kSteps; ++i) {
+        const u32 t = kSteps - 1u - i;
+        const u64 hm = __ballot(((heads >> t) & 1u) != 0u);
+        u32 tl = (u32)after, th = (u32)(after >> 32);
+        if (hm != 0ull) { // (wave-uniform)
+            const u64 behind = hm & ~le; // the heads behind this lane
+            const u32 src = behind != 0ull ? (u32)__builtin_ctzll(behind) - 1u : lane; // the lane in front of the next one
+            const u32 gl = (u32)__builtin_amdgcn_ds_bpermute((int)(4u * src), (int)lo[t]);
+            const u32 gh = kHigh ? (u32)__builtin_amdgcn_ds_bpermute((int)(4u * src), (int)hi[t]) : 0u;
+            if (behind != 0ull) {
+                tl = gl;
+                th = gh;
+            }
+            const int f = (int)__builtin_ctzll(hm); // the step's first head (scalar)
+            if (f > 0)
+                after = ((u64)(kHigh ? (u32)__builtin_amdgcn_readlane((int)hi[t], f - 1) : 0u) << 32) | (u32)__builtin_amdgcn_readlane((int)lo[t], f - 1);
+            else if (t > 0u)
+                after = ((u64)(kHigh ? (u32)__builtin_amdgcn_readlane((int)hi[t > 0u ? t - 1u : 0u], 63) : 0u) << 32) |
+                        (u32)__builtin_amdgcn_readlane((int)lo[t > 0u ? t - 1u : 0u], 63);
+            else
+                after = base;
+        }
+        const bool on = ((picked >> t) & 1u) != 0u;
+        if (!((on || a.all_rows != 0u) && row0 + 64u * t < rows)) tl = th = 0u;
+        lo[t] = tl;
+        hi[t] = th;
+        const u64 m = __ballot(on);
+        have = put_lane((u32)m, 2u * t, have);
+        have = put_lane((u32)(m >> 32), 2u * t + 1u, have);
+    }
+    const bool store = lane < 2u * kSteps; // (the half block: 32 words)
+    u32 *out = a.matrix + (seg * kSegWords + kCumsumBlockWords * blk + lane); // row 0 of the matrix; every row is n_words further
+    u32 b = a.n_slices_out;
+    if (kHigh) {
+#pragma nounroll
+        for (; b > 32u; --b) {
+            const u32 w = slice_words(hi, 1u << (b - 33u));
+            if (store) *out = w;
+            out += a.n_words;
+        }
+    }
+#pragma nounroll
+    for (; b > 0u; --b) {
+        const u32 w = slice_words(lo, 1u << (b - 1u));
+        if (store) *out = w;
+        out += a.n_words;
+    }
+    if (a.all_rows == 0u && store) *out = have;
+}
+
+template <bool kWide, bool kHigh>
+__global__ __launch_bounds__(kCumsumWaves * 64) void total_parts_rows_kernel(const BsiTotalPartsArgs ta) {
+    __shared__ __attribute__((aligned(16))) u32 s_rows[kSegBits];
+    __shared__ __attribute__((aligned(16))) u32 s_acc[kCumsumWaves][kSegGroups];
+    __shared__ u64 s_block[kCumsumBlocks];   // tails
+    __shared__ u64 s_block_h[kCumsumBlocks]; // heads
+    __shared__ u32 s_block_f[kCumsumBlocks];
+    const BsiCumsumPartsArgs &pa = ta.p;
+    const BsiCumsumArgs &a = pa.c;
+    const u32 wave = wave_id(), lane = lane_id();
+    u32 *acc = s_acc[wave];
+    const u32 *sel = s_acc[kCumsumSliceWaves];
+    const u32 *st = s_acc[kPartsStartsWave];
+    const u32 nv = a.n_slices_val;
+    const u32 per = (nv + kPartsSliceWaves - 1u) / kPartsSliceWaves; // the value's slices shared among six wavefronts
+    const u32 w_lo = min(wave * per, nv), w_hi = wave < kPartsSliceWaves ? min(w_lo + per, nv) : w_lo;
+    const bool last_half = wave + kCumsumWaves == kCumsumBlocks - 1u; // (wave-uniform: the wavefront whose second block is the half one)
+
+#pragma nounroll
+    for (u64 seg = blockIdx.x; seg < a.n_segments; seg += gridDim.x) { // (workgroup-uniform)
+        const u32 nvalid = segment_groups(a.groups, seg);
+        const u32 rows = segment_rows(a.n_rows, seg);
+
+        if (nv != 0u) // (without value slices the rows' words are never read)
+            for (u32 p = threadIdx.x * 4u; p < kSegBits; p += kCumsumWaves * 64u * 4u) *reinterpret_cast<uint4 *>(s_rows + p) = make_uint4(0u, 0u, 0u, 0u);
+        if (wave < kCumsumSliceWaves)
+            image_fill(acc, 0u, lane);
+        else
+            selection_preset(acc, a.n_rows, seg, nvalid, lane);
+        __syncthreads();
+
+        if (wave < kPartsSliceWaves) {
+            if (w_lo < w_hi) // (wave-uniform)
+                walk_slices(a, w_lo, w_hi, seg, nvalid, acc, lane, [&](u32 sig) { fold_slice_bits(acc, s_rows, 0u, kSegGroups / 64u, sig, lane); });
+        } else if (wave == kPartsStartsWave) {
+            starts_walk(pa, acc, seg, nvalid, rows, lane);
+        } else {
+            selection_walk(a, acc, seg, nvalid, lane);
+        }
+        __syncthreads();
+
+        {
+            const TotalTriple t0 = block_triple<kCumsumBlockSteps>(s_rows, sel, st, nv, wave, lane);
+            const TotalTriple t1 = last_half ? block_triple<kCumsumBlockSteps / 2u>(s_rows, sel, st, nv, kCumsumBlocks - 1u, lane)
+                                             : block_triple<kCumsumBlockSteps>(s_rows, sel, st, nv, wave + kCumsumWaves, lane);
+            if (lane == 0) {
+                s_block[wave] = t0.tail;
+                s_block_h[wave] = t0.head;
+                s_block_f[wave] = t0.f;
+                s_block[wave + kCumsumWaves] = t1.tail;
+                s_block_h[wave + kCumsumWaves] = t1.head;
+                s_block_f[wave + kCumsumWaves] = t1.f;
+            }
+        }
+        __syncthreads();
+
+        // what flows into the wavefront's two blocks from behind: the heads of the blocks behind up to the first with a start
+        u64 back = ta.records[seg].head; // (scanned: what flows into the segment from behind)
+#pragma nounroll
+        for (u32 b = kCumsumBlocks - 1u; b > wave + kCumsumWaves; --b) back = s_block_f[b] != 0u ? s_block_h[b] : back + s_block_h[b];
+        const u64 back1 = uniform64(back);
+#pragma nounroll
+        for (u32 b = wave + kCumsumWaves; b > wave; --b) back = s_block_f[b] != 0u ? s_block_h[b] : back + s_block_h[b];
+        const u64 back0 = uniform64(back);
+
+        u64 base = ta.records[seg].tail; // (scanned: what flows into the segment from the front)
+#pragma nounroll
+        for (u32 b = 0; b < wave; ++b) base = s_block_f[b] != 0u ? s_block[b] : base + s_block[b];
+        base = uniform64(base);
+        total_block<kCumsumBlockSteps, kWide, kHigh>(a, s_rows, sel, st, seg, rows, wave, lane, base, back0);
+#pragma nounroll
+        for (u32 b = wave; b < wave + kCumsumWaves; ++b) base = s_block_f[b] != 0u ? s_block[b] : base + s_block[b];
+        base = uniform64(base);
+        if (last_half)
+            total_block<kCumsumBlockSteps / 2u, kWide, kHigh>(a, s_rows, sel, st, seg, rows, kCumsumBlocks - 1u, lane, base, back1);
+        else
+            total_block<kCumsumBlockSteps, kWide, kHigh>(a, s_rows, sel, st, seg, rows, wave + kCumsumWaves, lane, base, back1);
+        __syncthreads(); // the next segment clears the rows and the images
+    }
+}
+
 } // namespace
+
+hipError_t launch_bsi_total_parts(const BsiTotalPartsArgs &a, hipStream_t s) {
+    const BsiCumsumArgs &c = a.p.c;
+    if (c.n_segments == 0) return hipSuccess;
+    const dim3 grid((unsigned)(c.n_segments < kCumsumGridItems ? c.n_segments : kCumsumGridItems)), block(kCumsumWaves * 64);
+    hipLaunchKernelGGL(total_parts_records_kernel, grid, block, 0, s, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(total_parts_scan_kernel, dim3(1), dim3(kScanWaves * 64), 0, s, a.records, c.n_segments);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const bool wide = c.n_slices_val > kCumsumNarrowBits, high = c.n_slices_out > 32u;
+    if (wide && high)
+        hipLaunchKernelGGL((total_parts_rows_kernel<true, true>), grid, block, 0, s, a);
+    else if (wide)
+        hipLaunchKernelGGL((total_parts_rows_kernel<true, false>), grid, block, 0, s, a);
+    else if (high)
+        hipLaunchKernelGGL((total_parts_rows_kernel<false, true>), grid, block, 0, s, a);
+    else
+        hipLaunchKernelGGL((total_parts_rows_kernel<false, false>), grid, block, 0, s, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_bsi_cumsum_parts(const BsiCumsumPartsArgs &a, hipStream_t s) {
     if (a.c.n_segments == 0) return hipSuccess;

@@ -519,6 +519,21 @@ struct BsiCumsumPartsArgs {
 };
 hipError_t launch_bsi_cumsum_parts(const BsiCumsumPartsArgs &a, hipStream_t s);
 
+// wah_bsi_total_parts_indexed_device (wah_cumsum.hip): the partition's TOTAL in every row.  p: as above, p.records unused,
+// p.c.exclusive 0.  records: n_segments of them in the scratch: whether the segment holds a start, the sum of its selected values in
+// front of its first one (head) and at or behind its last one (tail), both the whole segment's where it holds none; then -- scanned
+// in place -- in `tail` what flows into the segment from the front and in `head` what flows into it from behind.
+struct BsiTotalPartsRecord {
+    uint64_t head;
+    uint64_t tail;
+    uint64_t has_start; // 0 or 1
+};
+struct BsiTotalPartsArgs {
+    BsiCumsumPartsArgs p;
+    BsiTotalPartsRecord *records;
+};
+hipError_t launch_bsi_total_parts(const BsiTotalPartsArgs &a, hipStream_t s);
+
 // ... on operands of few words per segment: their runs merged in the compressed domain, one lane per segment
 // (wah_bitop_runs.hip): count pass, scan of the tile totals, write pass
 struct BitopRunsArgs {

@@ -1087,7 +1087,8 @@ int wah_bsi_map_status(void *d_scratch, uint64_t n_words, uint64_t n_slices_out,
  * refuses in a row of either table, EVERY row's every segment being walked whatever is selected; then the compress passes'
  * verdict (WAH_ERR_CAPACITY: nothing is written at or behind d_out[out_capacity_words]).  The output of a refused call is
  * unspecified.  wah_bsi_cumsum_status(NULL, ...): WAH_ERR_ARG.  Not here: signed values, values above 32 slices.  (Sums that
- * start again per partition: wah_bsi_cumsum_parts_indexed_device, below.) */
+ * start again per partition: wah_bsi_cumsum_parts_indexed_device, below; a partition's total in every one of its rows:
+ * wah_bsi_total_parts_indexed_device, below that.) */
 #define WAH_CUMSUM_EXCLUSIVE 2u /* flags: the sum runs over the rows in front of a row, not up to it */
 #define WAH_CUMSUM_ALL_ROWS 4u  /* flags: unselected rows carry the sum forward, and the result has no existence row */
 size_t wah_bsi_cumsum_scratch_bytes(uint64_t n_words, uint64_t n_slices_out, unsigned flags);
@@ -1127,8 +1128,8 @@ int wah_bsi_cumsum_status(void *d_scratch, uint64_t n_words, uint64_t n_slices_o
  * wah_bsi_cumsum_parts_status(), which synchronises the stream: WAH_ERR_STREAM for everything the list call refuses in a row of
  * either table or in the starts row, EVERY row's every segment being walked; then the compress passes' verdict.  Nothing is read
  * back: the call is asynchronous on `stream`, allocates nothing and can be captured in a graph.  The output of a refused call is
- * unspecified.  wah_bsi_cumsum_parts_status(NULL, ...): WAH_ERR_ARG.  Not here: partition totals broadcast to every row (a
- * backward pass), signed values, values above 32 slices. */
+ * unspecified.  wah_bsi_cumsum_parts_status(NULL, ...): WAH_ERR_ARG.  Not here: signed values, values above 32 slices.  (Partition
+ * totals broadcast to every row: wah_bsi_total_parts_indexed_device, below.) */
 size_t wah_bsi_cumsum_parts_scratch_bytes(uint64_t n_words, uint64_t n_slices_out, unsigned flags);
 int wah_bsi_cumsum_parts_indexed_device(uint64_t n_words, uint64_t n_rows, uint64_t n_filters, const wah_bitop_operand *d_filters,
                                         uint64_t n_slices_val, const wah_bitop_operand *d_val, const wah_bitop_operand *d_starts,
@@ -1136,6 +1137,48 @@ int wah_bsi_cumsum_parts_indexed_device(uint64_t n_words, uint64_t n_rows, uint6
                                         uint64_t *d_out_words, uint64_t *d_out_offsets, void *d_scratch, size_t scratch_bytes,
                                         void *stream);
 int wah_bsi_cumsum_parts_status(void *d_scratch, uint64_t n_words, uint64_t n_slices_out, unsigned flags, void *stream);
+
+/* The PARTITION'S TOTAL IN EVERY ROW: `SELECT SUM(x) OVER (PARTITION BY g) FROM t WHERE f` on a table clustered by g -- the window
+ * aggregate without ORDER BY, for a share of total (x / SUM(x) OVER ...), without value slices `COUNT(*) OVER (PARTITION BY g)`,
+ * the size of a row's group, both divided the group mean, and compared with a bound the rows of the groups that a HAVING keeps.
+ * Selection, value, starts, widths, alignment, limits, the result's layout, rows_out, the compress road and the status call's
+ * behaviour are those of wah_bsi_cumsum_parts_indexed_device.
+ *   RESULT: let s(p) be the largest start row <= p, or 0 if there is none, and e(p) the smallest start row > p, minus 1, or
+ *   n_rows - 1 if there is none; T[p] = (the sum of the values of the selected rows q with s(p) <= q <= e(p)) mod 2^n_slices_out.
+ *   By default only selected rows hold T, every other row is 0 in every slice, and the result's last row is its existence row,
+ *   the selection.  With WAH_CUMSUM_ALL_ROWS every row in front of n_rows holds its partition's total, a partition without a
+ *   selected row 0, and there is no existence row.  Without value slices T is the number of selected rows of the partition.  A
+ *   starts bitmap with no bit set puts the grand total into every row.  The sum is carried in 64 bits and cut only where it is
+ *   stored.  T[p] is what wah_bsi_cumsum_parts_indexed_device with WAH_CUMSUM_ALL_ROWS holds at row e(p).
+ *   FLAGS: WAH_BSI_EXISTS and WAH_CUMSUM_ALL_ROWS.  WAH_CUMSUM_EXCLUSIVE has no meaning here and is refused with the unknown bits.
+ * The same three launches, none of which waits for another workgroup, with TWO sums per item beside has_start: its head, the
+ * selected values in front of its first start, and its tail, those at or behind its last one (both the whole item where it holds
+ * no start).  Per segment a record from popcounts under the two masks; one workgroup scans the records in both directions, the
+ * tails from the front with the operator above, the heads from the end with its mirror -- what flows in from behind a segment is
+ * the heads of the segments behind it up to and including the first that holds a start; the rows kernel folds block triples the
+ * same way, runs the partitioned call's inclusive step forward over a block and then walks the steps backward: a row's total is
+ * the running sum at the lane in front of the next start behind it in its step of 64 rows (one ds_bpermute per word), and where
+ * the step holds none behind it a wave-uniform value carried from step to step.
+ *   d_scratch: the builder's layout and one record of 24 bytes per segment behind it, 256-byte aligned, no initialisation:
+ *   wah_bsi_total_parts_scratch_bytes(n_words, n_slices_out, flags) = wah_bsi_build_scratch_bytes(n_words, rows_out) + 24
+ *   (n_words / 992) rounded up to a multiple of 256.
+ * Errors the host can see come back before any HIP call, in the groups and the order of wah_bsi_cumsum_parts_indexed_device, with
+ * texts of this call's own: (1) n_slices_val above 32, n_slices_out outside 1 .. 64, unknown flag bits -- WAH_CUMSUM_EXCLUSIVE
+ * among them --, n_filters above the cap; (2) a null or misaligned scratch or output, a d_val that does not go with n_slices_val
+ * and the flags, a null filter table with n_filters > 0, a null or misaligned d_starts; (3) n_words 0, no multiple of 992 or
+ * >= 2^40, rows_out * n_words >= 2^40, n_rows > 32 n_words -- all WAH_ERR_ARG; then too small a scratch: WAH_ERR_WORKSPACE.
+ * Everything only the device sees is reported by wah_bsi_total_parts_status(), which synchronises the stream: WAH_ERR_STREAM for
+ * everything the list call refuses in a row of either table or in the starts row, EVERY row's every segment being walked; then
+ * the compress passes' verdict.  Nothing is read back: the call is asynchronous on `stream`, allocates nothing and can be
+ * captured in a graph.  The output of a refused call is unspecified.  wah_bsi_total_parts_status(NULL, ...): WAH_ERR_ARG.  Not
+ * here: MIN / MAX per partition in every row, frames (ROWS BETWEEN), signed values, values above 32 slices. */
+size_t wah_bsi_total_parts_scratch_bytes(uint64_t n_words, uint64_t n_slices_out, unsigned flags);
+int wah_bsi_total_parts_indexed_device(uint64_t n_words, uint64_t n_rows, uint64_t n_filters, const wah_bitop_operand *d_filters,
+                                       uint64_t n_slices_val, const wah_bitop_operand *d_val, const wah_bitop_operand *d_starts,
+                                       uint64_t n_slices_out, unsigned flags, uint32_t *d_out, uint64_t out_capacity_words,
+                                       uint64_t *d_out_words, uint64_t *d_out_offsets, void *d_scratch, size_t scratch_bytes,
+                                       void *stream);
+int wah_bsi_total_parts_status(void *d_scratch, uint64_t n_words, uint64_t n_slices_out, unsigned flags, void *stream);
 
 /* The order statistics PER GROUP in ONE call -- `SELECT g, h, MIN(x), MAX(x), median(x) WHERE <filter> GROUP BY g, h`: for every
  * group g and every query q the value of rank q among the rows that `filters AND group g's rows` select, over ONE bit-sliced
